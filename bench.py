@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — MULLS-ICP hot path throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B | --total-pairs T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B | --total-pairs T] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torch.distributed environment, bench.py starts its N ranks itself (python -m
 torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...); started under torch.distributed.run
@@ -73,6 +73,9 @@ def parse_args(argv=None):
     ap.add_argument("--nn-mode", type=int, default=0, help="0 auto (grid staged in LDS), 1 brute force, 2 grid in global memory, 3 grid in LDS")
     ap.add_argument("--tiny", action="store_true", help="plumbing-test sizes (12-beam scans, 4 scenes, 3 iterations): never a bench line")
     ap.add_argument("--dump-table", default="", help="rank 0 writes the gathered result table (npy) here")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the results of the last timed step as DIR/<name>.npy (float64; see dump_outputs): same arguments, same inputs, so two builds "
+                         "can be compared output for output")
     ap.add_argument("--data", default="synthetic", choices=["synthetic", "demo"],
                     help="demo: BASELINE configs[0] on real data — the reference's demo pair and its consecutive frames from tests/golden/demo_pair.npz (class clouds by "
                          "the reference's own extract_semantic_pts lines), test/mulls_reg.cpp:194-195's mm_lls_icp arguments; delta_T against the reference lines' results")
@@ -417,6 +420,37 @@ def abi_T(r):
     return np.array(r.T[:]).reshape(4, 4).T
 
 
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: every file of the directory together, npy headers included
+
+
+def ncorr_of(results, n):
+    """(n, NCLASS) float64: the per-class correspondence counts of the final iteration, read from the result records."""
+    rec = abi.C.sizeof(abi.Result)
+    raw = np.frombuffer(results, dtype=np.uint8, count=n * rec).reshape(n, rec)
+    off = abi.Result.ncorr.offset
+    return np.ascontiguousarray(raw[:, off:off + 4 * abi.NCLASS]).view(np.uint32).astype(np.float64)
+
+
+def dump_outputs(out_dir, table, ncorr=None):
+    """--dump-outputs DIR: what the timed path returned in its last timed step, one float64 .npy per output, rows in pair order — T (n, 4, 4) and
+    information (n, 6, 6) row-major, code, iterations, sigma, confidence (n,), ncorr (n, NCLASS) where one process holds every pair, and rows (n,):
+    the pair indices kept.  Above DUMP_CAP_BYTES a fixed seeded sample of the pairs is written instead."""
+    n = len(table)
+    cols = {"T": table[:, :16].reshape(n, 4, 4).transpose(0, 2, 1), "information": table[:, 16:52].reshape(n, 6, 6).transpose(0, 2, 1),
+            "code": table[:, 52], "iterations": table[:, 53], "sigma": table[:, 54], "confidence": table[:, 55]}
+    if ncorr is not None:
+        cols["ncorr"] = ncorr
+    rows = np.arange(n)
+    row_bytes = sum(a[:1].nbytes for a in cols.values()) + 8  # (+ the row index itself)
+    fit = (DUMP_CAP_BYTES - 1024 * (len(cols) + 1)) // row_bytes
+    if n > fit:
+        rows = np.sort(np.random.default_rng(SEED0).choice(n, fit, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in cols.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a[rows], dtype=np.float64))
+    np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------------------------------
 def free_port():
     s = socket.socket()
@@ -547,6 +581,7 @@ def large_main(args, rank, local_rank, world, engine_factory=None):
             acc[k] += getattr(pf, k)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+    dump_ncorr = ncorr_of(results, n_pairs) if args.dump_outputs and world == 1 else None  # (the records of the last timed step, before any later step)
     engine.set_profiling(1)
     for _ in range(args.steps):
         step()
@@ -569,6 +604,8 @@ def large_main(args, rank, local_rank, world, engine_factory=None):
                 "all_converged_code_1": bool(all(res_c[i].code == 1 for i in range(n_pairs))),
                 "params": "the same pairs with the call site's convergence thresholds (converge_tran 0.0005 m, converge_rot_d 0.001 deg) instead of the forced iteration count"}
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, gathered, dump_ncorr)
         n_reg = n_total * args.steps
         launches = max(acc["launches_nn"], 1)
         avg_ms = acc["ms_nn"] / launches
@@ -771,6 +808,7 @@ def main(argv=None, engine_factory=None):
     gathered = shard.gather_wait(pending)
     barrier()
     elapsed = time.perf_counter() - t0
+    dump_ncorr = ncorr_of(results, len(pairs)) if args.dump_outputs and world == 1 and pairs else None  # (the records of the last timed step, before any later step)
     if not events_live:
         engine.set_profiling(2)
         step()
@@ -946,6 +984,8 @@ def main(argv=None, engine_factory=None):
         tsha = hashlib.sha256(np.ascontiguousarray(gathered).tobytes()).hexdigest()
         if args.dump_table:
             np.save(args.dump_table, gathered)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, gathered, dump_ncorr)
         launches = max(acc["launches_nn"], 1)
         avg_ms = acc["ms_nn"] / launches
         # Algorithmic bytes per launch of the search: per live source point 64 B (pos+nrm read and written back by

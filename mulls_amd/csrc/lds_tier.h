@@ -817,7 +817,9 @@ struct CertLds
 {
 	float4 uq[SMALL];
 	uint32_t us[SMALL];
-	static constexpr bool LOOK = MULLS_LDS_KCERT != 0 && SMALL >= 128; // lists of a few dozen entries (the resident loop, the small batches' one-launch search) never get the look: no room kept
+	// lists of a few dozen entries (the resident loop, the small batches' one-launch search) never get the look: no room kept; nor do lists longer than the
+	// light pass's workgroup (the 768-entry list of k_cert<MULLS_CERT_BLOCK, 3, 768>): kcert_list takes one lane per listed point
+	static constexpr bool LOOK = MULLS_LDS_KCERT != 0 && SMALL >= 128 && SMALL <= MULLS_CERT_BLOCK;
 	float um[LOOK ? SMALL : 1];				   // how far this iteration's step moved the listed point (entries flagged MULLS_US_KCERT: the k-candidate certificate's look needs it)
 	uint32_t ucount, red[3 * 16];
 };

@@ -93,9 +93,11 @@ g++ -O3 -ffp-contract=off -std=c++17 -fPIC -shared -w -I"$TMP" -I"$HERE" -I"$HER
 	"$HERE/ref_driver.cpp" -o "$HERE/_ref/libmulls_ref.so"
 echo "build_ref: built $HERE/_ref/libmulls_ref.so from $REF"
 # end-to-end drop-in check of include/cregistration_hip.hpp against the same reference lines (needs libmulls_hip.so)
+# (linked by name, not by path: the library has no SONAME, and a path would be recorded as it is and bind the binary to this checkout;
+# by name the loader finds it through $ORIGIN in whichever checkout oracle/_ref/ sits)
 HIPLIB="$HERE/../mulls_amd/libmulls_hip.so"
 if [ -f "$HIPLIB" ]; then
 	g++ -O2 -ffp-contract=off -std=c++17 -w -I"$TMP" -I"$HERE" -I"$HERE/../include" "$HERE/adapter_check.cpp" \
-		-o "$HERE/_ref/adapter_check" "$HIPLIB" -Wl,-rpath,'$ORIGIN/../../mulls_amd' -Wl,-rpath,/opt/rocm/lib
+		-o "$HERE/_ref/adapter_check" -L"$(dirname "$HIPLIB")" -l:libmulls_hip.so -Wl,-rpath,'$ORIGIN/../../mulls_amd' -Wl,-rpath,/opt/rocm/lib
 	echo "build_ref: built $HERE/_ref/adapter_check"
 fi
