@@ -174,12 +174,15 @@ typedef struct mulls_profile
 	double ms_host_wait;	/* host time spent waiting for the device epoch, summed over iterations */
 	double ms_host_launch;	/* host time spent enqueueing the launch set, summed over iterations */
 	uint64_t nn_tgt_unique; /* target points of the searched class clouds (once per cloud), summed over launches */
-	uint64_t nn_corr_pts;	/* device-resident loop: correspondences that entered the estimation, summed over the iterations */
-	double icp_fused_ms[6];	/* device-resident loop: the fused class pass by stage (set-up, rigid step + certificates, leftover queries, rejection
-							   chain, normal-equation terms), summed over the pairs */
-	double icp_search_ms[24]; /* device-resident loop: the search phase by iteration (summed over the pairs) */
-	double icp_phase_ms[6]; /* device-resident loop: workgroup time summed over the pairs, by phase: search, counters + count test, normal
-							   equations, solve + step tests, residual pass, whole loop (one workgroup per CU: divide by the CUs for wall time) */
+	uint64_t nn_corr_pts;	/* loop stepped on the device: correspondences that entered the estimation, summed over the iterations (0 when the
+							   host steps the loop) */
+	double icp_fused_ms[6];	/* diagnostics of a loop stepped on the device, 0 otherwise.  MULLS_OPT_DEBUG_STOP = 20: k_cert's phase clocks summed over
+							   its workgroups ([0..4], ms) and the workgroup count ([5]); = 21: the global-memory tier's leftover queries ([0]) and
+							   its workgroup time ([1], ms) */
+	double icp_search_ms[24]; /* ... MULLS_OPT_DEBUG_STOP = 20: k_cert's k-candidate certificates — points the plain certificate left over, points
+							   given the second chance, points it certified, points searched ([0..3]); 0 otherwise */
+	double icp_phase_ms[6]; /* ... MULLS_OPT_DEBUG_STOP = 20: k_nn_lds's phase clocks summed over its class clouds ([0..3], ms) and the class cloud
+							   count ([4]); 0 otherwise, and [5] always */
 	double ms_stage;		/* mulls_icp / mulls_icp_batch: wall time of staging the caller's clouds (host gather into pinned memory + upload), */
 	double ms_stage_pack;	/* ... of which the host gather, */
 	uint64_t stage_bytes;	/* ... and the bytes that crossed PCIe */
@@ -196,11 +199,10 @@ const char *mulls_last_error(const mulls_ctx *ctx);
 int mulls_set_profiling(mulls_ctx *ctx, int on);
 int mulls_get_profile(const mulls_ctx *ctx, mulls_profile *out);
 /* correspondence-search tier: 0 = auto, 1 = LDS-tiled brute force, 2 = uniform grid in global memory, 3 = uniform grid staged in LDS with lock-step
- * launches (MULLS_E_INVALID when a searched target class cloud exceeds 9728 points), 4 = device-resident loop (k_icp: one launch iterates every pair
- * of the batch to the end; the lock-step LDS tier where the loop does not apply: normal shooting, source class clouds above 16384 points).
+ * launches (MULLS_E_INVALID when a searched target class cloud exceeds 9728 points), 4 = the same as 3 (kept for existing callers).
  * Auto: searched target class clouds of <= 9728 points -> the grid staged in LDS, stepped by lock-step launch sets (the O(1) half of the iteration
- * on the device too; the device-resident loop only inside the window MULLS_OPT_RESIDENT_MIN_PAIRS .. _MAX_PAIRS, empty by default); larger targets ->
- * the grid in global memory.  All tiers are exact and return bit-identical results (tests/test_gpu_stages.py, test_gpu_icp.py). */
+ * on the device too); larger targets -> the grid in global memory.  All tiers are exact and return bit-identical results (tests/test_gpu_stages.py,
+ * test_gpu_icp.py). */
 int mulls_set_nn_mode(mulls_ctx *ctx, int mode);
 /* Execution options of a context (none of them changes a result: every path returns the same bits).  mulls_create presets each from the environment
  * variable named after it (MULLS_OPT_HOST_STEP <- MULLS_HOST_STEP=1, ...: diagnostics and the A/B scripts under tools/); nothing reads the
@@ -208,9 +210,7 @@ int mulls_set_nn_mode(mulls_ctx *ctx, int mode);
 enum mulls_option
 {
 	MULLS_OPT_HOST_STEP = 0,			  /* [0] 1: the lock-step loop is stepped by the host (what per-iteration traces switch on anyway) */
-	MULLS_OPT_RESIDENT_MIN_PAIRS = 1,	  /* [1] auto mode runs the device-resident loop (one persistent workgroup per pair) for batches of MIN .. MAX pairs; MAX < MIN (the  */
-	MULLS_OPT_RESIDENT_MAX_PAIRS = 2,	  /* [0] default): never — since round 3 the lock-step path is at least as fast at every size (profiles/r03_modes.txt: 256 pairs
-											 139 k both, 320 pairs 152 k against 100 k).  nn_mode 4 asks for the loop at any size */
+										  /* 1, 2: reserved (mulls_set_option / mulls_get_option return MULLS_E_INVALID) */
 	MULLS_OPT_FEW_LAUNCHES_MAX_PAIRS = 3, /* [640; 384 until round 6: +1 % at 384 - 512 pairs] lock-step loop: batches up to this size run 3 - 4 launches per iteration instead of 7 (one accumulation launch;
 											 finish + step + publication as one kernel; light and heavy pass of the search as one launch while there are at most
 											 two class clouds per CU) — small batches are bound by the launch count */

@@ -1,6 +1,6 @@
 // accum.h — one correspondence's contribution to the normal equations (or to the posterior residual), and the fixed-order
-// reduction of a class cloud's contributions: shared by k_accum (lock-step path) and k_icp (device-resident loop), so that both
-// add the same numbers in the same order and produce the same bits.
+// reduction of a class cloud's contributions (k_accum / k_accum_wave + k_finish, k_sum_step): every kernel that sums a class cloud
+// adds the same numbers in the same order and produces the same bits.
 #pragma once
 #include "device_util.h"
 
@@ -337,8 +337,8 @@ __device__ __forceinline__ void point_terms(const AccumCtx &A, const double *x, 
 #undef ACC
 
 // ---------------------------------------------------------------------------------------------------------------
-// Summation order of a class cloud's row — the one order every path of the library uses (k_accum + k_finish in the lock-step
-// path, k_icp in the device-resident loop), so that they produce the same bits:
+// Summation order of a class cloud's row — the one order every path of the library uses (k_accum / k_accum_wave + k_finish,
+// k_sum_step), so that they produce the same bits:
 //   the source slots are taken in trips of MULLS_ACC_LANES = 1024; the term of slot trip * 1024 + v is value v of the trip (0 for
 //   a dead / invalid slot); for each of the 27 terms lane j of a wave adds the 16 values j, j + 64, ..., j + 960 in that order
 //   (in double), a butterfly adds the 64 partial sums ((xor 1, xor 2, mirror 8, mirror 16) inside the 16-lane rows, then
@@ -538,23 +538,6 @@ __device__ __forceinline__ void trip_sum(const AccumCtx &A, const double *x, con
 	trip_sum_regs<HALF, LANES>(A, x, valid, P, Q, N, w, R, part);
 	if (valid && __float_as_uint(w) != __float_as_uint(w0))
 		wd[g] = w; // pcl::Correspondence::weight
-}
-
-// one class cloud's whole row: trip sums in trip order -> row[0..26] (LDS)
-__device__ __forceinline__ void class_row(const AccumCtx &A, const double *x, const CloudDesc &d, const float4 *__restrict__ spos,
-										   const float4 *__restrict__ mq, const uint8_t *__restrict__ flag, float *__restrict__ wd, void *R, double *row)
-{
-	__shared__ double part[MULLS_NTERM_PAD];
-	const uint32_t src_n = d.src_n;
-	uint32_t trip0 = 0;
-	do
-	{
-		trip_sum(A, x, d, trip0, spos, mq, flag, wd, R, part);
-		if (threadIdx.x < MULLS_NTERM)
-			row[threadIdx.x] = trip0 ? row[threadIdx.x] + part[threadIdx.x] : 0.0 + part[threadIdx.x]; // as k_finish adds the trip partials to 0.0
-		__syncthreads();
-		trip0 += MULLS_ACC_LANES;
-	} while (trip0 < src_n);
 }
 
 // Term t (0..26) of the one system the reference solves, from the class rows.  The 6x6 the reference inverts: pt2pl / pt2pt

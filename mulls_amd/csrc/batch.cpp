@@ -147,7 +147,7 @@ namespace mulls_drv
 void options_init(mulls_ctx *ctx)
 {
 	double *o = ctx->opt;
-	o[MULLS_OPT_HOST_STEP] = 0, o[MULLS_OPT_RESIDENT_MIN_PAIRS] = 1, o[MULLS_OPT_RESIDENT_MAX_PAIRS] = 0, o[MULLS_OPT_FEW_LAUNCHES_MAX_PAIRS] = 640;
+	o[MULLS_OPT_HOST_STEP] = 0, o[MULLS_OPT_FEW_LAUNCHES_MAX_PAIRS] = 640;
 	o[MULLS_OPT_SUBBATCHES] = 0, o[MULLS_OPT_TWO_STREAMS] = 0, o[MULLS_OPT_CERTIFICATES] = 1;
 	o[MULLS_OPT_CERT_SLACK_MIN] = 0.02, o[MULLS_OPT_CERT_SLACK_MAX] = 0.10, o[MULLS_OPT_CERT_SLACK_RATE] = 1.0;
 	o[MULLS_OPT_SPLIT_MIN_PAIRS] = 96, o[MULLS_OPT_SPLIT_MAX_PAIRS] = 1 << 30, o[MULLS_OPT_FUSED_TGT_SETUP] = 1, o[MULLS_OPT_STAGGER] = 4352, o[MULLS_OPT_STEP_LAUNCH_MAX_PAIRS] = 640, o[MULLS_OPT_LDS_DEDUP] = 1, o[MULLS_OPT_GRID_H0] = 0, o[MULLS_OPT_BM_H0] = 0, o[MULLS_OPT_LEAN_STAGING] = 0, o[MULLS_OPT_DEBUG_STOP] = 0, o[MULLS_OPT_DEBUG_TICK] = 0, o[MULLS_OPT_MIXED_TIERS] = 1, o[MULLS_OPT_BIG_EARLY_SETS] = 5, o[MULLS_OPT_KCERT] = 1, o[MULLS_OPT_KCERT_MIN] = 64, o[MULLS_OPT_ACCUM_WAVE_MIN_TRIPS] = 768;
@@ -157,8 +157,7 @@ void options_init(mulls_ctx *ctx)
 	{
 		const char *name;
 		int opt;
-	} env[] = {{"MULLS_HOST_STEP", MULLS_OPT_HOST_STEP}, {"MULLS_RESIDENT_MIN_PAIRS", MULLS_OPT_RESIDENT_MIN_PAIRS}, {"MULLS_RESIDENT_MAX_PAIRS", MULLS_OPT_RESIDENT_MAX_PAIRS},
-			   {"MULLS_FEW_LAUNCHES_MAX_PAIRS", MULLS_OPT_FEW_LAUNCHES_MAX_PAIRS}, {"MULLS_SUBBATCHES", MULLS_OPT_SUBBATCHES}, {"MULLS_TWO_STREAMS", MULLS_OPT_TWO_STREAMS},
+	} env[] = {{"MULLS_HOST_STEP", MULLS_OPT_HOST_STEP}, {"MULLS_FEW_LAUNCHES_MAX_PAIRS", MULLS_OPT_FEW_LAUNCHES_MAX_PAIRS}, {"MULLS_SUBBATCHES", MULLS_OPT_SUBBATCHES}, {"MULLS_TWO_STREAMS", MULLS_OPT_TWO_STREAMS},
 			   {"MULLS_CERTIFICATES", MULLS_OPT_CERTIFICATES}, {"MULLS_LDS_DEDUP", MULLS_OPT_LDS_DEDUP}, {"MULLS_GRID_H0", MULLS_OPT_GRID_H0}, {"MULLS_BM_H0", MULLS_OPT_BM_H0},
 			   {"MULLS_LEAN_STAGING", MULLS_OPT_LEAN_STAGING}, {"MULLS_FUSED_TGT_SETUP", MULLS_OPT_FUSED_TGT_SETUP}, {"MULLS_STAGGER", MULLS_OPT_STAGGER}, {"MULLS_STEP_LAUNCH_MAX_PAIRS", MULLS_OPT_STEP_LAUNCH_MAX_PAIRS}, {"MULLS_SPLIT_MIN_PAIRS", MULLS_OPT_SPLIT_MIN_PAIRS}, {"MULLS_SPLIT_MAX_PAIRS", MULLS_OPT_SPLIT_MAX_PAIRS}, {"MULLS_DEBUG_STOP", MULLS_OPT_DEBUG_STOP}, {"MULLS_DEBUG_TICK", MULLS_OPT_DEBUG_TICK}, {"MULLS_MIXED_TIERS", MULLS_OPT_MIXED_TIERS}, {"MULLS_BIG_EARLY_SETS", MULLS_OPT_BIG_EARLY_SETS}, {"MULLS_KCERT", MULLS_OPT_KCERT}, {"MULLS_KCERT_MIN", MULLS_OPT_KCERT_MIN}, {"MULLS_ACCUM_WAVE_MIN_TRIPS", MULLS_OPT_ACCUM_WAVE_MIN_TRIPS}, {"MULLS_FIRST_DIRECT", MULLS_OPT_FIRST_DIRECT}, {"MULLS_SUM_STEP", MULLS_OPT_SUM_STEP}};
 	for (const auto &e : env)
@@ -184,7 +183,7 @@ void options_init(mulls_ctx *ctx)
 // table (prepare_run: dedup_fits): the LDS tier's one-pass walk needs it, so auto mode keeps larger clouds off that tier
 uint32_t lds_dedup_max_pts()
 {
-	const long room = 160L * 1024L - 64L - (long)MULLS_ICP_STATIC_LDS - (long)MULLS_LDS_QCHUNK * 16L - (long)MULLS_LDS_AUX - 2L * (4096L + 8L);
+	const long room = 160L * 1024L - 64L - (long)MULLS_LDS_CELL_RESERVE - (long)MULLS_LDS_QCHUNK * 16L - (long)MULLS_LDS_AUX - 2L * (4096L + 8L);
 	return (uint32_t)((room / 18L) & ~7L);
 }
 
@@ -339,30 +338,6 @@ void build_jobs(mulls_batch *B, const mulls_params *P, int nsub, int mode)
 			std::stable_sort(first_of((uint32_t)((long)B->n * k / nsub)), first_of((uint32_t)((long)B->n * (k + 1) / nsub)),
 							 [&](const Job &a, const Job &b) { return cost(a) > cost(b); });
 	}
-	// device-resident loop: one class-level job per (pair, used class with source points), in pair order; pairs taken from the
-	// queue most expensive first (same cost model), so that the last pairs in flight are the cheap ones
-	B->rjobs_h.clear();
-	B->pair_rjob_h.assign((size_t)B->n + 1, 0u);
-	std::vector<uint64_t> pair_cost(B->n, 0);
-	for (int p = 0; p < B->n; p++)
-	{
-		B->pair_rjob_h[p] = (uint32_t)B->rjobs_h.size();
-		for (int c = 0; c < MULLS_NC; c++)
-		{
-			const CloudDesc &d = B->descs_h[p * MULLS_NC + c];
-			if (P->used_feature_type[c] == '1' && d.src_cap > 0)
-			{
-				Job j = {(uint32_t)p, (uint32_t)c, 0u, d.src_cap};
-				B->rjobs_h.push_back(j);
-				pair_cost[p] += (uint64_t)d.src_cap * (uint64_t)(64u + d.tgt_n0 / 64u);
-			}
-		}
-	}
-	B->pair_rjob_h[B->n] = (uint32_t)B->rjobs_h.size();
-	B->order_h.resize(B->n);
-	for (int p = 0; p < B->n; p++)
-		B->order_h[p] = (uint32_t)p;
-	std::stable_sort(B->order_h.begin(), B->order_h.end(), [&](uint32_t a, uint32_t b) { return pair_cost[a] > pair_cost[b]; });
 	B->tjobs_h.clear();
 	for (int p = 0; p < B->n; p++)
 		for (int c = 0; c < MULLS_NC; c++)
@@ -833,7 +808,7 @@ int batch_fill(mulls_ctx *ctx, mulls_batch *B, const mulls_pair *pairs, int n, c
 // used classes, so they are uploaded once (pinned copies would not help: they are simply not re-sent) and every run
 // restores the mutable descriptors / box keys with device-to-device copies — no pageable H2D traffic per run.
 // nsub: sub-batches the lock-step job tables are laid out for (0 = subbatch_count)
-int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunParams &rp, uint32_t *lds_cap_out, int *tier_out, bool *resident_out, int nsub, bool allow_mixed)
+int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunParams &rp, uint32_t *lds_cap_out, int *tier_out, int nsub, bool allow_mixed)
 {
 	hipStream_t st = ctx->stream;
 	const int n = B->n;
@@ -856,31 +831,20 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 	rp.lds_dedup = 0;
 	rp.grid_maxcells = MULLS_MAXCELLS;
 	rp.cell_stride = ((rp.grid_maxcells + 1u + 15u) & ~15u);
-	bool resident = false;
 	if (tier == 2 || tier == 3)
 	{
 		rp.grid_maxcells = lds_cells_for(lds_cap);
 		// class-level jobs (one workgroup sees every query of a class cloud): keep the duplicate table in LDS if 4 B per target
-		// still leave a useful cell budget next to the staged cloud (MULLS_ICP_STATIC_LDS bytes stay free for the static LDS of k_icp)
+		// still leave a useful cell budget next to the staged cloud (MULLS_LDS_CELL_RESERVE bytes stay out of the budget)
 		const bool class_level = tier == 3 || (!B->cjobs_h.empty() && B->cjobs_h[0].count != MULLS_SRC_PER_BLOCK);
-		const long left = 160L * 1024L - 64L - (long)MULLS_ICP_STATIC_LDS - (long)MULLS_LDS_QCHUNK * 16L - (long)MULLS_LDS_AUX - (long)lds_cap * 18L;
+		const long left = 160L * 1024L - 64L - (long)MULLS_LDS_CELL_RESERVE - (long)MULLS_LDS_QCHUNK * 16L - (long)MULLS_LDS_AUX - (long)lds_cap * 18L;
 		const bool dedup_fits = !rp.normal_shooting && left / 2 - 8 >= 4096 && ctx->opt[MULLS_OPT_LDS_DEDUP] != 0.0; // k_nn_shoot uses the global table
 		if (tier == 3 && !dedup_fits)
 		{
 			ctx->err = "internal: a mixed batch whose LDS-tier clouds do not fit the on-chip duplicate table";
 			return MULLS_E_INVALID;
 		}
-		// Device-resident loop (k_icp: one workgroup carries a pair through all its iterations): only on request (nn_mode 4) since round 3 — the lock-step
-		// path, whose light kernels run several workgroups per CU and whose per-iteration step runs on the device too, is at least as fast at every
-		// batch size (profiles/r03_modes.txt); MULLS_OPT_RESIDENT_MIN_PAIRS .. _MAX_PAIRS can still open a window for it in auto mode.  It needs the
-		// on-chip duplicate table, the plain mm_lls_icp loop (resident_out) and no source class cloud so large that one workgroup per pair would be the
-		// wrong shape; nn_mode 4 gets the lock-step LDS tier where the loop does not apply.
-		uint32_t max_src = 0;
-		for (const Job &j : B->rjobs_h)
-			max_src = std::max(max_src, j.count);
-		resident = tier == 2 && resident_out && dedup_fits && max_src <= 16384u && P_jobs->max_iter_num > 0 &&
-				   (ctx->nn_mode == 4 || (ctx->nn_mode == 0 && n >= (int)ctx->opt[MULLS_OPT_RESIDENT_MIN_PAIRS] && n <= (int)ctx->opt[MULLS_OPT_RESIDENT_MAX_PAIRS]));
-		if ((class_level || resident) && dedup_fits)
+		if (class_level && dedup_fits)
 		{
 			rp.lds_dedup = 1;
 			rp.grid_maxcells = (uint32_t)std::min<long>(left / 2 - 8, (long)MULLS_MAXCELLS);
@@ -903,9 +867,6 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 		rp.bm_maxwords = rp.bm_stride = (uint32_t)words;
 	}
 
-	if (resident_out)
-		*resident_out = resident;
-
 	bool grew = false, g2 = false;
 	int rc = MULLS_OK;
 	auto A = [&](int r) { if (rc == MULLS_OK) rc = r; };
@@ -927,20 +888,6 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 	A(grow(ctx, &B->wl, &B->cap_wl, B->cjobs_h.size()));
 	A(grow(ctx, &B->ajobs, &B->cap_ajobs, B->ajobs_h.size(), &g2));
 	grew |= g2;
-	if (resident)
-	{
-		A(grow(ctx, &B->rjobs, &B->cap_icp[0], B->rjobs_h.size(), &g2));
-		grew |= g2;
-		A(grow(ctx, &B->pair_rjob, &B->cap_icp[1], (size_t)n + 1, &g2));
-		grew |= g2;
-		A(grow(ctx, &B->order, &B->cap_icp[2], (size_t)n, &g2));
-		grew |= g2;
-		A(grow(ctx, &B->icp_outs, &B->cap_icp[3], (size_t)n));
-		if (!B->icp_queue)
-			A(dmalloc(ctx, &B->icp_queue, 16));
-		if (rc == MULLS_OK)
-			HIPCHK(ctx, hipMemsetAsync(B->icp_queue, 0, 16 * sizeof(uint32_t), st));
-	}
 	if (!B->wl_ctr)
 		A(dmalloc(ctx, &B->wl_ctr, 16));
 	if (rc == MULLS_OK)
@@ -966,8 +913,7 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 	}
 	if (rc != MULLS_OK)
 		return rc;
-	const std::string want_key = B->jobs_key + (resident ? "R" : "");
-	if (grew || B->dev_key != want_key || B->dev_key.empty())
+	if (grew || B->dev_key != B->jobs_key || B->dev_key.empty())
 	{
 		SegCopier up(ctx); // one launch for the dozen tables
 		up.add_host(B->jobs, B->jobs_h.data(), sizeof(Job) * B->njobs);
@@ -978,12 +924,6 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 		up.add_host(B->ejobs, B->ejobs_h.data(), sizeof(Job) * B->ejobs_h.size());
 		up.add_host(B->lclouds, B->lclouds_h.data(), sizeof(uint32_t) * B->lclouds_h.size());
 		up.add_host(B->ajobs, B->ajobs_h.data(), sizeof(uint32_t) * B->ajobs_h.size());
-		if (resident)
-		{
-			up.add_host(B->rjobs, B->rjobs_h.data(), sizeof(Job) * B->rjobs_h.size());
-			up.add_host(B->pair_rjob, B->pair_rjob_h.data(), sizeof(uint32_t) * B->pair_rjob_h.size());
-			up.add_host(B->order, B->order_h.data(), sizeof(uint32_t) * B->order_h.size());
-		}
 		up.add_host(B->descs_init, B->descs_h.data(), sizeof(CloudDesc) * B->descs_h.size());
 		up.add_host(B->bbox_init, B->bbox_h, sizeof(uint32_t) * 6 * n);
 		if (up.flush(st) != MULLS_OK)
@@ -992,7 +932,7 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 			return MULLS_E_HIP;
 		}
 		HIPCHK(ctx, hipStreamSynchronize(st)); // the host vectors may be rebuilt by a later call
-		B->dev_key = want_key;
+		B->dev_key = B->jobs_key;
 	}
 	{
 		SegCopier reset(ctx); // this run's working copies of the descriptors and of the crop boxes

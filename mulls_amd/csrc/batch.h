@@ -75,12 +75,8 @@ struct mulls_batch
 	std::vector<uint32_t> ajobs_h; // jobs that start a trip of 1024 source slots: k_accum's workgroups (indices into jobs_h) — per sub-batch slice,
 								   // and inside a slice grouped by trip length (ajob_split)
 	uint32_t ajob_split[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}; // [sub-batch][0..3]: the slice's trips of > 512, 257..512, <= 256 slots
-	// device-resident loop (k_icp): class-level jobs in pair order, each pair's range in them, the pairs most expensive first
-	std::vector<Job> rjobs_h;
-	std::vector<uint32_t> pair_rjob_h, order_h;
-	IcpOut *icp_outs_pin = nullptr; // the result records of a device-stepped / device-resident run, downloaded into pinned memory (results_from_device)
+	IcpOut *icp_outs_pin = nullptr; // the result records of a device-stepped run, downloaded into pinned memory (results_from_device)
 	size_t cap_icp_pin = 0;
-	std::vector<mulls_iter_trace> trace_h;
 	std::string jobs_key;
 	uint32_t njobs = 0;
 	// device
@@ -118,13 +114,10 @@ struct mulls_batch
 	uint32_t *bm_rank = nullptr; // bitmap grids: every target point's (cell counter index, arrival number in its cell), from k_bm_count to k_bm_scatter — the scatter is
 								 // pure data movement: one pass of atomics per build instead of two
 	size_t cap_bm_rank = 0;
-	Job *rjobs = nullptr;
 	uint32_t *ajobs = nullptr;
 	size_t cap_ajobs = 0;
-	uint32_t *pair_rjob = nullptr, *order = nullptr, *icp_queue = nullptr;
 	IcpOut *icp_outs = nullptr;
-	mulls_iter_trace *trace_dev = nullptr;
-	size_t cap_icp[5] = {};
+	size_t cap_icp_outs = 0;
 	mulls::StepState *steps = nullptr; // lock-step loop with the device step: per-pair loop state
 	size_t cap_steps = 0;
 	uint32_t epoch2 = 0, epoch3 = 0; // ... and the last epochs issued on its 8-byte words (words 32-33 / 48-49 of epoch_h: one per sub-batch)
@@ -203,8 +196,7 @@ uint32_t lds_cells_for(uint32_t cap);
 int choose_tier(const mulls_ctx *ctx, const mulls_batch *B, const uint8_t used[MULLS_NC], uint32_t *lds_cap, const mulls_params *P_mixed = nullptr);
 int batch_fill(mulls_ctx *ctx, mulls_batch *B, const mulls_pair *pairs, int n, const mulls_params *P = nullptr);
 // nsub: sub-batches the lock-step job tables are laid out for (0 = subbatch_count)
-int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunParams &rp, uint32_t *lds_cap_out, int *tier_out, bool *resident_out = nullptr, int nsub = 0,
-				bool allow_mixed = false);
+int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunParams &rp, uint32_t *lds_cap_out, int *tier_out, int nsub = 0, bool allow_mixed = false);
 mulls::IcpConst icp_const(const mulls_params *P);
 int take_epochs(mulls_ctx *ctx, mulls_batch *B, uint32_t n, RunParams &rp);
 

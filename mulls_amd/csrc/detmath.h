@@ -1,5 +1,5 @@
 // detmath.h — the three transcendental functions of the per-iteration algebra (sin, cos, atan2), written out so that the
-// host driver and the device-resident ICP loop compute THE SAME BITS: plain IEEE-754 double operations in a fixed order
+// host driver and the device step of the ICP loop compute THE SAME BITS: plain IEEE-754 double operations in a fixed order
 // (the library is built -ffp-contract=off; the only fused operation is the explicit fma of the exact product), no libm.
 //
 // Evaluation is in double-double (~104 bits) and the result is the rounding of that value to double, i.e. the correctly
@@ -20,7 +20,7 @@
 #define MULLS_HD
 #endif
 // Work arrays of the per-iteration algebra: plain locals on the host; on the device they live in LDS (the algebra is run by one
-// lane of a workgroup — k_icp — and dynamically indexed locals would otherwise sit in scratch memory, ~10x the latency).
+// lane of a workgroup — k_reduce.hip's device step — and dynamically indexed locals would otherwise sit in scratch memory, ~10x the latency).
 #if defined(__HIP_DEVICE_COMPILE__)
 #define MULLS_WORK static __shared__
 #else

@@ -22,9 +22,9 @@
 #define MULLS_LDS_QCHUNK 1024u // LDS tier: queries searched between two workgroup barriers (one per lane in the rigid-step phase)
 #define MULLS_LDS_AUX (320u + 2u * MULLS_LDS_QCHUNK) // LDS tier: cost histogram and query order of a chunk
 #define MULLS_CERT_BLOCK 512	   // k_cert: lanes per class cloud (one source point per lane and trip); several workgroups per CU
-#define MULLS_CERT_SMALL 64u   // the device-resident loop searches up to this many uncertified points of a class cloud against the grid in global memory
+#define MULLS_CERT_SMALL 64u   // k_cert_nn / k_cert_mixed (light and heavy pass in one workgroup) search up to this many uncertified points of a class cloud against the grid in global memory
 #define MULLS_CERT_SMALL_LOCKSTEP 512u // ... k_cert up to this many (four workgroups per CU hide the walks' latency: 64 -> 512 took 1.5 ms off a 4096-pair step, profiles/r03_sweeps.txt)
-#define MULLS_ICP_STATIC_LDS 9216 // LDS the device-resident loop keeps next to the dynamic block (pair state, class rows, ...; checked at its first launch)
+#define MULLS_LDS_CELL_RESERVE 9216 // bytes of a workgroup's LDS the LDS tier's cell budget leaves unused (prepare_run, lds_dedup_max_pts); retuning it is separate work
 #ifndef MULLS_LDS_GROUP // (4u / 16u: A/B builds, tools/build_variant.sh)
 #define MULLS_LDS_GROUP 8u	   // lanes that cooperate on one query in the LDS grid tier (DPP reductions stay inside a 16-lane row)
 #endif
@@ -130,7 +130,7 @@ struct PairOut
 	uint32_t pad_[2];
 };
 
-// Result of one pair of the device-resident loop (k_icp), read back by the host after the launch.
+// Result of one pair of a device-stepped run (k_step / k_finish_step / k_sum_step), read back by the host at the end of the run.
 struct IcpOut
 {
 	double T[16];	 // Trans1_2, column-major
@@ -141,10 +141,7 @@ struct IcpOut
 	int32_t code, iters, singular, trace_len;
 	uint32_t ncorr[MULLS_NC], nsrc0[MULLS_NC], ntgt0[MULLS_NC], bbox[6];
 	uint32_t pad_;
-	unsigned long long t_fused[6]; // ... of the fused class pass by stage: set-up, stage 1, leftovers, stage 3, stage 4, (unused)
-	uint32_t t_search_it[24]; // ... and of the search phase of the first 24 iterations
-	unsigned long long t_phase[6]; // time of this pair in the loop's phases, 10-ns ticks (wall_clock64): search, counters + count test, normal equations, solve, residual pass, total
-	unsigned long long tgt_job_pts, pair_evals; // lock-step loop with the device step only: target points times the workgroups that read them; brute-force pair evaluations
+	unsigned long long tgt_job_pts, pair_evals; // profile counters: target points times the workgroups that read them; brute-force pair evaluations
 };
 
 // One workgroup's worth of the correspondence search / filter / accumulation.

@@ -2,12 +2,12 @@
 // (reference: CRegistration::mm_lls_icp, include/common/cregistration.hpp:1114-1440).
 //
 // Division of labour (BASELINE.json north_star): correspondences, rejection, the normal-equation reduction AND the per-iteration 6x6 solve with
-// its step / convergence / health tests run in the HIP kernels of k_setup / k_grid / k_search / k_reduce / k_icp .hip; the host queues launch
+// its step / convergence / health tests run in the HIP kernels of k_setup / k_grid / k_search / k_reduce .hip; the host queues launch
 // sets (loop.cpp), reads one 8-byte word per set to learn how many pairs still iterate, and downloads the result records at the end.  Only when
 // the caller asks for per-iteration traces does the host step the loop itself.  There is no CPU fallback anywhere in the driver: without a usable
 // HIP device every entry point fails with MULLS_E_NO_DEVICE / MULLS_E_HIP.
 //   batch.cpp    options, job tables, staging (batch_fill), per-run tables and tier choice (prepare_run)
-//   loop.cpp     mulls_batch_run: set-up launches and the three loops
+//   loop.cpp     mulls_batch_run: set-up launches and the two loops
 //   variants.cpp lls_icp_3dof_ground, mm_lls_icp_4dof_global
 //   stage.cpp    mulls_stage_*
 #include "batch.h"
@@ -177,6 +177,9 @@ void HostPool::parallel_for(long begin, long end, long grain, const std::functio
 
 using namespace mulls_drv;
 
+// enum mulls_option: slots 1 and 2 are reserved
+static bool option_known(int option) { return option >= 0 && option < MULLS_OPT_COUNT && option != 1 && option != 2; }
+
 extern "C"
 {
 
@@ -305,7 +308,7 @@ extern "C"
 
 	int mulls_set_option(mulls_ctx *ctx, int option, double value)
 	{
-		if (!ctx || option < 0 || option >= MULLS_OPT_COUNT)
+		if (!ctx || !option_known(option))
 			return MULLS_E_INVALID;
 		if (!option_value_ok(option, &value))
 		{
@@ -317,7 +320,7 @@ extern "C"
 	}
 	int mulls_get_option(const mulls_ctx *ctx, int option, double *value)
 	{
-		if (!ctx || !value || option < 0 || option >= MULLS_OPT_COUNT)
+		if (!ctx || !value || !option_known(option))
 			return MULLS_E_INVALID;
 		*value = ctx->opt[option];
 		return MULLS_OK;
@@ -345,7 +348,7 @@ extern "C"
 		void *dev[] = {B->stage, B->tmp_pos, B->tmp_nrm, B->spos, B->snrm, B->tpos, B->tnrm, B->flag, B->match, B->nn_idx, B->nn_hint, B->nn_cand, B->mq, B->wd,
 					   B->nn_d2, B->winner, B->descs, B->setup, B->states, B->outs, B->ticket, B->bbox, B->setup_jobs, B->big_segs, B->big_clouds, B->seg_cnt, B->big_box, B->jobs, B->partial,
 					   B->tjobs, B->cjobs, B->bjobs, B->fjobs, B->ejobs, B->lclouds, B->bm_cs, B->wl, B->wl_ctr, B->grids, B->tsorted, B->tmap, B->dbg, B->cell_cnt, B->cell_start, B->bm, B->pf, B->descs_init, B->bbox_init,
-					   B->rjobs, B->ajobs, B->pair_rjob, B->order, B->icp_queue, B->icp_outs, B->trace_dev, B->steps, B->bm_rank};
+					   B->ajobs, B->icp_outs, B->steps, B->bm_rank};
 		for (void *p : dev)
 			if (p)
 				staggered_free(p);

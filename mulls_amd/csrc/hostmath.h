@@ -8,7 +8,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "detmath.h" // sin / cos / atan2 shared bit for bit by the host driver and the device-resident loop
+#include "detmath.h" // sin / cos / atan2 shared bit for bit by the host driver and the device step
 
 namespace mulls
 {

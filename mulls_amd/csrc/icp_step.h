@@ -1,6 +1,6 @@
 // icp_step.h — the O(1)-per-iteration half of mm_lls_icp (cregistration.hpp:1296-1401): correspondence-count test, threshold
 // update, 6x6 solve, step-size and convergence tests, posterior sigma and information matrix.  Host AND device code: the
-// lock-step driver (driver.cpp, host_step) and the device-resident loop (k_icp.hip) both call these functions, and every
+// host-stepped loop (loop.cpp, run_host_step) and the device step (k_reduce.hip) both call these functions, and every
 // operation in them is IEEE arithmetic in a fixed order (hostmath.h / detmath.h), so the two paths produce the same bits.
 #pragma once
 #include <stdint.h>

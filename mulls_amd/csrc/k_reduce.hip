@@ -8,7 +8,7 @@
 // Normal-equation accumulation (active pairs) or posterior residual (pairs flagged want_residual), lock-step path.  The job
 // table is the one of the search (512 source slots per job); one workgroup per job that starts a trip of MULLS_ACC_LANES slots
 // (`leaders`) sums the whole trip in the library's summation order (accum.h) into that job's slot of `partial`; k_finish
-// adds the trip partials in order (run-to-run deterministic, unlike atomicAdd(double), and the same bits as k_icp).
+// adds the trip partials in order (run-to-run deterministic, unlike atomicAdd(double), and the same bits as k_sum_step).
 // LANES: the workgroup size and the most slots the trip can have.  A trip of 100-400 slots (the roof, beam and pillar clouds of a scan, the tail of
 // a facade cloud) in a 1024-lane workgroup occupies a 56-KiB buffer and sixteen waves for the latency of its four barriers; as a 256- or
 // 512-lane workgroup it shares the CU with seven or three others.  The sums are the same (accum.h: reduce_terms).
@@ -688,7 +688,7 @@ __device__ __forceinline__ bool step_pair(uint32_t pair, const CloudDesc *__rest
 			for (uint32_t w = (uint32_t)l; w < sizeof(mulls::StepState) / 8; w += 64u)
 				dst[w] = src[w];
 		}
-		if (L.done) // the result record (the fields k_icp's timers fill stay zero)
+		if (L.done) // the result record
 		{
 			IcpOut &O = results[pair];
 			if (l < 16)

@@ -1,7 +1,7 @@
-// lds_tier.h — device code of the LDS grid tier of the correspondence search, shared by the lock-step kernels (k_cert / k_nn_lds /
-// k_filter in k_search.hip) and the device-resident registration loop (k_icp.hip): the rejection chain of one source point, the
-// exact grid search of one query by a sub-group of lanes, and the two per-class-cloud passes of an ICP iteration (cert_class:
-// rigid step + certificates + leftovers; lds_search_class: target cloud staged in LDS + search of the uncertified points).
+// lds_tier.h — device code of the LDS grid tier of the correspondence search, used by the lock-step kernels (k_cert / k_nn_lds /
+// k_filter in k_search.hip): the rejection chain of one source point, the exact grid search of one query by a sub-group of lanes,
+// and the two per-class-cloud passes of an ICP iteration (cert_class: rigid step + certificates + leftovers; lds_search_class:
+// target cloud staged in LDS + search of the uncertified points).
 #pragma once
 #include "device_util.h"
 // ---------------------------------------------------------------------------------------------------------------
@@ -817,7 +817,7 @@ struct CertLds
 {
 	float4 uq[SMALL];
 	uint32_t us[SMALL];
-	// lists of a few dozen entries (the resident loop, the small batches' one-launch search) never get the look: no room kept; nor do lists longer than the
+	// lists of a few dozen entries (the small batches' one-launch search) never get the look: no room kept; nor do lists longer than the
 	// light pass's workgroup (the 768-entry list of k_cert<MULLS_CERT_BLOCK, 3, 768>): kcert_list takes one lane per listed point
 	static constexpr bool LOOK = MULLS_LDS_KCERT != 0 && SMALL >= 128 && SMALL <= MULLS_CERT_BLOCK;
 	float um[LOOK ? SMALL : 1];				   // how far this iteration's step moved the listed point (entries flagged MULLS_US_KCERT: the k-candidate certificate's look needs it)
@@ -1009,7 +1009,7 @@ __device__ __forceinline__ uint32_t kcert_list(CertLds<SMALL> &CL, const RunPara
 // memory, the duplicate rule and the rejection chain.  Returns true when the class cloud is done for this iteration, false when
 // the caller has to stage the target cloud (lds_search_class).  W: LDS, tgt_n words (only touched with rp.lds_dedup).  Every lane
 // of the workgroup must call it (barriers inside).
-template <int BLK, bool W16 = false, int SMALL = MULLS_CERT_SMALL>
+template <int BLK, bool W16, int SMALL>
 __device__ __forceinline__ bool cert_class(CertLds<SMALL> &CL, const RunParams &rp, const PairState &ps, const Job &job, CloudDesc &d, const GridDesc &g, uint32_t *W,
 											float4 *__restrict__ spos, float4 *__restrict__ snrm, const uint32_t *__restrict__ cell_start,
 											const float4 *__restrict__ tsorted, uint8_t *flag, int32_t *__restrict__ nn_idx, float *__restrict__ nn_d2,

@@ -1,6 +1,5 @@
 // loop.cpp — mulls_batch_run: one registration run of a device-resident batch (reference: CRegistration::mm_lls_icp, cregistration.hpp:1114-1440).
-// Set-up launches (clone + initial guess, intersection crop, keep-less thinning, target grids), then one of three loops with identical results:
-//   run_resident      the device-resident loop (k_icp: one launch iterates every pair to the end)
+// Set-up launches (clone + initial guess, intersection crop, keep-less thinning, target grids), then one of two loops with identical results:
 //   run_device_step   the lock-step loop stepped on the device: four or seven launches per iteration, one 8-byte word back per launch set
 //   run_host_step     the lock-step loop stepped by the host (per-iteration traces)
 #include "batch.h"
@@ -25,7 +24,7 @@ struct Run
 	uint32_t lds_cap = 0;
 	uint32_t max_big_tgt = 0; // the largest target class cloud on the global-memory tier (launch_search: how long a small batch keeps chunk-level jobs)
 	int tier = 0;
-	bool use_grid = false, dstep = false, resident = false;
+	bool use_grid = false, dstep = false;
 };
 #define RUN_ALIASES \
 	mulls_ctx *ctx = R.ctx; \
@@ -90,15 +89,14 @@ int run_setup(Run &R)
 	dstep = dstep && ctx->opt[MULLS_OPT_HOST_STEP] == 0.0;
 	uint32_t lds_cap = 0;
 	int tier = 0;
-	bool resident = false;
 	// device-stepped loop: one sub-batch, or two on two streams for the batch sizes whose kernels leave most of the chip idle (not while profiling:
 	// the event sets are laid out for one)
 	const int dstep_nsub = (ctx->profiling == 0 && n >= (int)ctx->opt[MULLS_OPT_SPLIT_MIN_PAIRS] && n <= (int)ctx->opt[MULLS_OPT_SPLIT_MAX_PAIRS]) ? 2 : 1;
-	rc = prepare_run(ctx, B, P, rp, &lds_cap, &tier, &resident, dstep ? dstep_nsub : 0, true);
+	rc = prepare_run(ctx, B, P, rp, &lds_cap, &tier, dstep ? dstep_nsub : 0, true);
 	if (rc != MULLS_OK)
 		return rc;
 	const bool use_grid = tier != 0;
-	R.lds_cap = lds_cap, R.tier = tier, R.use_grid = use_grid, R.dstep = dstep, R.resident = resident;
+	R.lds_cap = lds_cap, R.tier = tier, R.use_grid = use_grid, R.dstep = dstep;
 	R.max_big_tgt = 0;
 	if (tier == 3)
 		for (const CloudDesc &d : B->descs_h)
@@ -283,8 +281,8 @@ RUN_ALIASES
 	return MULLS_OK;
 }
 
-// results of the loops that end on the device (k_icp; k_finish_step): IcpOut records -> mulls_result, profile counters
-int results_from_device(Run &R, uint32_t trace_cap, bool from_icp)
+// results of the device-stepped loop: IcpOut records -> mulls_result, profile counters
+int results_from_device(Run &R)
 {
 RUN_ALIASES
 	const auto wall0 = R.wall0;
@@ -293,11 +291,6 @@ RUN_ALIASES
 		if (grow_pinned(ctx, &B->icp_outs_pin, &B->cap_icp_pin, (size_t)n, hipHostMallocDefault) != MULLS_OK)
 			return MULLS_E_NOMEM;
 		HIPCHK(ctx, hipMemcpyAsync(B->icp_outs_pin, B->icp_outs, sizeof(IcpOut) * (size_t)n, hipMemcpyDeviceToHost, st));
-		if (trace_cap)
-		{
-			B->trace_h.resize((size_t)n * trace_cap);
-			HIPCHK(ctx, hipMemcpyAsync(B->trace_h.data(), B->trace_dev, sizeof(mulls_iter_trace) * (size_t)n * trace_cap, hipMemcpyDeviceToHost, st));
-		}
 		HIPCHK(ctx, hipStreamSynchronize(st));
 		evt.collect();
 		const double wall_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3;
@@ -324,30 +317,15 @@ RUN_ALIASES
 			std::memset(R.crop_box, 0, sizeof(R.crop_box));
 			fill_crop_box(rp, B->setup_h[p].tgt_bound, o.bbox, R);
 			R.trace_len = 0;
-			if (trace_cap && R.trace && R.trace_cap > 0)
-			{
-				R.trace_len = std::min(o.trace_len, R.trace_cap);
-				std::memcpy(R.trace, &B->trace_h[(size_t)p * trace_cap], sizeof(mulls_iter_trace) * (size_t)R.trace_len);
-			}
 			ctx->prof.nn_src_pts += o.src_pts;
 			ctx->prof.nn_tgt_unique += o.tgt_pts;
-			ctx->prof.nn_tgt_pts += from_icp ? o.tgt_pts : o.tgt_job_pts;
+			ctx->prof.nn_tgt_pts += o.tgt_job_pts;
 			ctx->prof.nn_corr_pts += o.corr_pts;
-			if (!from_icp)
-				ctx->prof.nn_pair_evals += o.pair_evals;
-			if (from_icp)
-			{
-				for (int k = 0; k < 6; k++)
-					ctx->prof.icp_phase_ms[k] += (double)o.t_phase[k] * 1e-5; // 10-ns ticks -> ms (summed over the pairs)
-				for (int k = 0; k < 6; k++)
-					ctx->prof.icp_fused_ms[k] += (double)o.t_fused[k] * 1e-5;
-				for (int k = 0; k < 24 && k < o.iters; k++)
-					ctx->prof.icp_search_ms[k] += (double)o.t_search_it[k] * 1e-5;
-			}
+			ctx->prof.nn_pair_evals += o.pair_evals;
 			max_it = std::max(max_it, o.iters);
 		}
 		ctx->prof.iterations = max_it;
-		if (rp.dbg_ticks) // diagnostics: k_cert's phase clocks, summed over its workgroups, in the resident loop's slots ([5] = workgroups)
+		if (rp.dbg_ticks) // diagnostics: k_cert's phase clocks, summed over its workgroups, in the profile's icp_*_ms slots ([5] = workgroups)
 		{
 			unsigned long long t[16];
 			HIPCHK(ctx, hipMemcpy(t, rp.dbg_ticks, sizeof(t), hipMemcpyDeviceToHost));
@@ -369,38 +347,6 @@ RUN_ALIASES
 		return MULLS_OK;
 }
 
-// ---- device-resident loop: ONE launch iterates every pair to the end (k_icp.hip) ------------------------------------------------------
-int run_resident(Run &R)
-{
-RUN_ALIASES
-
-	// ---- device-resident loop: ONE launch iterates every pair to the end (k_icp.hip) ------------------------------------------
-	uint32_t trace_cap = 0;
-	for (int p = 0; p < n; p++)
-		if (results[p].trace && results[p].trace_cap > 0)
-			trace_cap = std::max(trace_cap, (uint32_t)results[p].trace_cap);
-	if (trace_cap)
-	{
-		trace_cap = std::min(trace_cap, (uint32_t)std::max(P->max_iter_num, 1));
-		if (grow(ctx, &B->trace_dev, &B->cap_icp[4], (size_t)n * trace_cap) != MULLS_OK)
-			return MULLS_E_HIP;
-	}
-	evt.begin(&ctx->prof.ms_nn);
-	if (launch_icp(st, (uint32_t)n, 0u, B->rjobs, B->pair_rjob, B->order, B->icp_queue, B->descs, B->setup, rp, K, B->spos, B->snrm, B->grids, B->cell_start,
-				   B->tsorted, B->flag, B->nn_idx, B->nn_d2, B->winner, B->tnrm, B->match, B->wd, B->tpos, B->nn_hint, B->mq, B->bbox, lds_cap, rp.grid_maxcells,
-				   B->icp_outs, trace_cap ? B->trace_dev : nullptr, trace_cap) != 0)
-	{
-		ctx->err = "could not raise the dynamic LDS limit of k_icp";
-		return MULLS_E_HIP;
-	}
-	evt.end();
-	const int rcr = results_from_device(R, trace_cap, true);
-	if (rcr != MULLS_OK)
-		return rcr;
-	ctx->prof.launches_nn = 1;
-	return MULLS_OK;
-}
-
 // ---- lock-step loop with the O(1) half of the iteration on the device (k_reduce.hip: k_finish / k_step / k_step_publish, or k_finish_step) -----
 int run_device_step(Run &R)
 {
@@ -410,7 +356,7 @@ RUN_ALIASES
 	// 8-byte word per set — (epoch << 32 | pairs still iterating) — to know when to stop queueing; a set queued behind the last useful one finds no
 	// active pair and falls through.  Mid-size batches (R.nsub == 2) run as two sub-batches on two streams, each with its own sets, word and
 	// ticket: their kernels are a few hundred workgroups each and bound by latency, so the chip runs one sub-batch's kernel beside the other's.
-	if (grow(ctx, &B->steps, &B->cap_steps, (size_t)n) != MULLS_OK || grow(ctx, &B->icp_outs, &B->cap_icp[3], (size_t)n) != MULLS_OK)
+	if (grow(ctx, &B->steps, &B->cap_steps, (size_t)n) != MULLS_OK || grow(ctx, &B->icp_outs, &B->cap_icp_outs, (size_t)n) != MULLS_OK)
 		return MULLS_E_HIP;
 	HIPCHK(ctx, hipMemsetAsync(B->icp_outs, 0, sizeof(IcpOut) * (size_t)n, st));
 	launch_step_init(st, (uint32_t)n, B->setup, K, B->steps, B->states);
@@ -583,7 +529,7 @@ RUN_ALIASES
 		HIPCHK(ctx, hipEventRecord(ctx->ev_setup, ctx->stream2));
 		HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_setup, 0));
 	}
-	rc = results_from_device(R, 0, false); // (synchronises ctx->stream, and with it — through the event — the second sub-batch's stream)
+	rc = results_from_device(R); // (synchronises ctx->stream, and with it — through the event — the second sub-batch's stream)
 	if (rc != MULLS_OK)
 		return rc;
 	drain.armed = false;
@@ -914,8 +860,6 @@ extern "C"
 		Run R{ctx, B, P, results, B->n, ctx->stream, std::chrono::steady_clock::now(), EvTimer{ctx}};
 		if ((rc = run_setup(R)) != MULLS_OK)
 			return rc;
-		if (R.resident)
-			return run_resident(R);
 		if (R.dstep)
 			return run_device_step(R);
 		return run_host_step(R);

@@ -1,13 +1,13 @@
-// solve_wave.h — icp_step.h's step_solve spread over the 64 lanes of one wave.  Device code shared by the device-resident loop (k_icp.hip) and
-// the lock-step loop's device step (k_reduce.hip: k_finish_step).
+// solve_wave.h — icp_step.h's step_solve spread over the 64 lanes of one wave.  Device code of the lock-step loop's device step
+// (k_reduce.hip: k_step / k_finish_step / k_sum_step).
 #pragma once
 #include "icp_step.h"
 
 // icp_step.h's step_solve, by the 64 lanes of ONE wave (the other waves of the workgroup wait at the next barrier): the same
 // operations on the same operands in the same order as the host functions it mirrors (hostmath.h: invert6, solve_step,
 // quat_euler_jacobian, euler_step_to_matrix, operator*), only spread over lanes wherever the host loops over independent
-// elements — so the result is bit-identical to the host's (tests/test_gpu_icp.py::test_resident_loop_equals_lock_step compares
-// every iteration's system, step and transform with the lock-step path's).  All data goes through LDS; a wave's LDS traffic is
+// elements — so the result is bit-identical to the host's (tests/test_gpu_icp.py::test_device_step_equals_host_step compares every
+// output of the device-stepped loop with the host-stepped loop's).  All data goes through LDS; a wave's LDS traffic is
 // executed in order, so a wavefront-scope fence between dependent steps is all the synchronisation needed.
 struct SolveWs
 {

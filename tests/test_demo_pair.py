@@ -127,7 +127,7 @@ def _register_all(gold, c):
     for name in CASES:
         r = c.icp(pair_of(gold, name), reg_params())[0]
         check_against_fixture(gold, name, r, exact=False)
-    # ... and as one batch (the device-resident loop / the lock-step path): the same results as one at a time
+    # ... and as one batch: the same results as one at a time
     rb = c.icp_batch([pair_of(gold, name) for name in CASES] * 2, reg_params())
     for k, name in enumerate(CASES * 2):
         check_against_fixture(gold, name, rb[k], exact=False)
@@ -135,7 +135,7 @@ def _register_all(gold, c):
 
 @pytest.mark.gpu
 def test_device_registers_the_demo_pair_on_every_tier(gold, ctx):
-    _register_all(gold, ctx)  # ctx: once per search tier (resident loop, LDS grid, global-memory grid, brute force)
+    _register_all(gold, ctx)  # ctx: once per search tier (LDS grid as nn_mode 4 and 3, global-memory grid, brute force)
 
 
 @pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""mulls_amd/csrc/detmath.h: the sin / cos / atan2 the host driver and the device-resident loop share (same bits on both).
+"""mulls_amd/csrc/detmath.h: the sin / cos / atan2 the host driver and the device step share (same bits on both).
 Checked here: correctly rounded against 300-bit mpmath values, and how often glibc's functions (what the reference and the
 oracle call) differ from them over the range of angles an ICP step produces."""
 import ctypes as C

@@ -168,7 +168,7 @@ def mixed_tier_block(rng, per):
 @pytest.mark.parametrize("block", [0, 1, 2, 3])
 def test_mixed_tier_degenerate_batches_match_oracle(ctx_auto, block):
     """Auto mode (a tier per class cloud) and the global-memory tier forced on every cloud, on batches whose class clouds span every search tier,
-    pathological shapes included: each pair equals the oracle's.  (The LDS tier and the resident loop refuse clouds of that size when forced.)"""
+    pathological shapes included: each pair equals the oracle's.  (The LDS tier refuses clouds of that size when forced.)"""
     from mulls_amd import lib
 
     rng = np.random.default_rng(block * 15485863 + 11)

@@ -242,7 +242,7 @@ def test_k_candidate_certificates_are_bit_identical(ctx, pairs_small):
 def test_fused_target_setup_is_bit_identical(ctx, pairs_small):
     """LDS tier: k_tgt_grid (crop + grid build of a target class cloud in one pass, no cropped copy: the records a correspondence needs are gathered
     from the staged cloud through the crop's map) against k_crop + k_grid_build_sort: same bits, with and without the intersection filter, healthy
-    and failing pairs, lock-step and resident loop (the ctx fixture's tiers), single calls and batches."""
+    and failing pairs, every search tier of the ctx fixture, single calls and batches."""
     rng = np.random.default_rng(17)
     tgt = planes_scene(rng)
     far = abi.PairData(tgt, transformed_copy(tgt, synth.se3(200.0, 0, 0)))
@@ -321,9 +321,9 @@ def test_profiling_levels_do_not_change_results(ctx, pairs_small):
     b.close()
 
 
-def test_resident_loop_equals_lock_step(ctx_auto, pairs_small):
-    """The device-resident loop (one launch, 6x6 solve on the device) and the lock-step path (host-stepped launches) run the same
-    arithmetic in the same order: every output bit-identical, trace included."""
+def test_lds_grid_equals_global_grid(ctx_auto, pairs_small):
+    """The grid staged in LDS (nn_mode 3, and 4, its synonym) and the grid in global memory (nn_mode 2) find the same correspondences and run
+    the same arithmetic in the same order: every output bit-identical, trace included."""
     from mulls_amd import lib
 
     plist = [p for p, _ in pairs_small] * 4  # 12 pairs: more than the 8 below which auto mode keeps the global-memory tier
@@ -473,7 +473,8 @@ def test_normal_shooting_survives_nan_queries(ctx, pairs_small):
 
 def test_option_values_are_validated(ctx):
     """mulls_set_option refuses what a cast to a count or a size could not take (non-finite, negative, absurd) and keeps the old value; the array stagger is
-    rounded down to a multiple of 256 bytes (the per-point arrays hold 16-byte records)."""
+    rounded down to a multiple of 256 bytes (the per-point arrays hold 16-byte records); mulls_set_option / mulls_get_option refuse the reserved slots
+    and the slots past the enum."""
     from mulls_amd import lib
 
     before = ctx.get_option(abi.OPT_STAGGER)
@@ -487,3 +488,8 @@ def test_option_values_are_validated(ctx):
     ctx.set_option(abi.OPT_STAGGER, before)
     with pytest.raises(lib.MullsError):
         ctx.set_option(abi.OPT_COUNT, 1)
+    for reserved in (1, 2):  # enum mulls_option: reserved slots
+        with pytest.raises(lib.MullsError):
+            ctx.set_option(reserved, 0)
+        with pytest.raises(lib.MullsError):
+            ctx.get_option(reserved)

@@ -1,4 +1,4 @@
-"""Device-resident loop (mode 4) vs lock-step path (mode 3) vs auto (mode 0) by batch size on the bench workload: median and minimum of the
+"""Lock-step LDS tier (mode 3) vs auto (mode 0) by batch size on the bench workload: median and minimum of the
 resident run time over `reps` runs each.  usage: gpu_modes.py [sizes ...]   (MULLS_* option presets apply, see include/mulls_hip.h)"""
 import sys, warnings, time, os
 sys.path.insert(0, "."); warnings.filterwarnings("ignore")
@@ -11,7 +11,7 @@ for nb in ([int(a) for a in sys.argv[1:]] or [1, 8, 32, 128, 512, 1024, 2048, 40
     pairs = [bench.global_pair(scenes, g) for g in range(nb)]
     row = []
     ctxs = []
-    for mode in (4, 3, 0):
+    for mode in (3, 0):
         ctx = lib.Context(0); ctx.set_nn_mode(mode)
         b = ctx.batch(pairs); res = abi.make_result_array(nb)
         b.run(P, results=res); b.run(P, results=res)
