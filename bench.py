@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — MULLS-ICP hot path throughput on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B | --total-pairs T] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs B | --total-pairs T] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no torch.distributed environment, bench.py starts its N ranks itself (python -m
 torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...); started under torch.distributed.run
@@ -19,10 +19,17 @@ One "step" = one lock-step registration of the rank's pairs, clouds already stag
 step re-cloning them like cloudblock_t::clone_feature does.  value = registrations of all ranks / T, T = max over
 ranks of the barrier-bracketed time of the K steps.
 
-The JSON line also carries
+A plain run does only what the headline needs: it builds the pairs, stages them, primes and warms up, times the K steps,
+writes --dump-outputs and prints the JSON line.  Its line carries
   roofline      — the dominant kernel: algorithmic HBM bytes per launch / average launch duration (hipEvents on the
                   library's own stream, live in the timed region) against the 8 TB/s HBM peak; traffic and the VALU
-                  issue view from the committed rocprofv3 --pmc passes of this very configuration.
+                  issue view from the committed rocprofv3 --pmc passes of this very configuration.  null where the
+                  timed steps run without the event pairs (batches below 512 pairs) and --full is not given.
+Everything else takes work or runs of its own and comes with --full only (the --no-* and --sustain-s options select among
+these legs):
+  kernel_ms_per_step, value_all_kernel_events_on — K further steps with hipEvents around every launch;
+                  value_without_gather (N > 1) — K further steps without the result gather; the roofline of a batch
+                  below 512 pairs — K further steps with the search launches bracketed.
   cpu_baseline  — the CPU oracle (restatement of the reference, kd-tree NN, the reference's 3-wide OpenMP sections)
                   timed on this box's host cores on a bounded sample of the same workload; cpu_baseline_manycore: 8
                   oracle processes side by side.
@@ -31,12 +38,14 @@ The JSON line also carries
   value_end_to_end — the same registrations from host buffers (mulls_icp_batch: staging upload included).
   value_converging — the same pairs with the call site's convergence thresholds (test/mulls_slam.cpp:642-648: converge_tran 0.0005 m,
                   converge_rot_d 0.001 deg) instead of the metric's forced 20 iterations: registrations/s and the mean iteration count.
-  other_configs  — (default one-GPU line only) compact legs of every other BASELINE configuration on the same box, same process: configs[0] (the reference's demo
+  other_configs  — (default one-GPU --full line only) compact legs of every other BASELINE configuration on the same box, same process: configs[0] (the reference's demo
                   scans), configs[2] (scans against a ~1 M-point map), the 128-pair shard configs[3] gives each of 8 GPUs, configs[4] (128-beam dense pairs, six
                   classes, 40 iterations) and the reference's own scan-to-map regime (64 scans against 20 000-point local maps) — value, ms per step, the search's
                   roofline fraction, delta T against the checker.  `python bench.py --config k` is the full-length line of each.
   value_sustained — the timed configuration again over a fixed wall budget (>= 2 s of back-to-back steps), so that a sampler outside
                   the process sees the device busy; value stays the K-step figure the contract defines.
+  delta_T_vs_reference_lines — (--data demo) the fixture's three registrations against the reference lines' results.
+--config 2 / 4 likewise: kernel_ms_per_step, value_converging, cpu_baseline and delta_T_vs_ref with --full only.
 """
 import argparse
 import hashlib
@@ -87,7 +96,10 @@ def parse_args(argv=None):
     ap.add_argument("--large-pairs", type=int, default=0, help="configs 2 / 4: pairs per GPU and step (default 32 / 16)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the compact legs of the other BASELINE configurations (configs[0], [2], the 128-pair shard of [3], [4] and the 20 000-point scan-to-map batch) "
-                         "that the default one-GPU line carries as `other_configs`")
+                         "that the default one-GPU --full line carries as `other_configs`")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (CPU baselines, checks against the oracle, converging, sustained, end-to-end, other_configs, per-kernel "
+                         "times); without it a run sets up, warms up, times the K steps and prints the line")
     a = ap.parse_args(argv)
     if a.config == 0:
         a.data = "demo"
@@ -508,7 +520,7 @@ def large_main(args, rank, local_rank, world, engine_factory=None):
     used = bytes(P.used_feature_type).decode()[:6]
     n_total = n_pairs * world
     cpu, checks = None, None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         from oracle import pyoracle
 
         if world == 1:
@@ -582,15 +594,16 @@ def large_main(args, rank, local_rank, world, engine_factory=None):
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
     dump_ncorr = ncorr_of(results, n_pairs) if args.dump_outputs and world == 1 else None  # (the records of the last timed step, before any later step)
-    engine.set_profiling(1)
-    for _ in range(args.steps):
-        step()
-        pf = engine.profile()
-        for k in ("ms_setup", "ms_filter", "ms_accum", "ms_residual"):
-            acc[k] += getattr(pf, k)
+    if args.full:
+        engine.set_profiling(1)
+        for _ in range(args.steps):
+            step()
+            pf = engine.profile()
+            for k in ("ms_setup", "ms_filter", "ms_accum", "ms_residual"):
+                acc[k] += getattr(pf, k)
     engine.set_profiling(0)
     conv = None
-    if Pc is not None and not args.no_converging:
+    if args.full and Pc is not None and not args.no_converging:
         res_c = abi.make_result_array(n_pairs)
         engine.run(Pc, res_c)
         barrier()
@@ -644,7 +657,7 @@ def large_main(args, rank, local_rank, world, engine_factory=None):
                 "avg_launch_ms": avg_ms, "launches": int(acc["launches_nn"]), "algorithmic_bytes_per_launch": alg_bytes,
                 "whole_path": {"B_reg_bytes_per_registration": b_reg, "achieved_GBs": b_reg * value / 1e9, "frac": b_reg * value / 1e9 / HBM_PEAK_GBS,
                                "note": "SURVEY 8d's B_reg (setup + every iteration's search and accumulation + residual pass) x registrations/s against the HBM peak"},
-                "kernel_ms_per_step": {k: acc[k] / args.steps for k in ("ms_setup", "ms_nn", "ms_filter", "ms_accum", "ms_residual")},
+                "kernel_ms_per_step": {k: acc[k] / args.steps for k in ("ms_setup", "ms_nn", "ms_filter", "ms_accum", "ms_residual")} if args.full else None,
                 "note": "live hipEvent duration of the search launches of the timed steps (the library's stream)",
             },
         }
@@ -684,10 +697,10 @@ def main(argv=None, engine_factory=None):
     n_total = args.total_pairs if args.total_pairs else world * args.pairs
     workers = max(1, min(16, (os.cpu_count() or 1) // max(world, 1)))
     demo = args.data == "demo"
-    # the default one-GPU line also carries compact legs of the other BASELINE configurations: their clouds are ray-cast by three forked workers while the
+    # the default one-GPU --full line also carries compact legs of the other BASELINE configurations: their clouds are ray-cast by three forked workers while the
     # headline's scenes are (before this process runs an OpenMP region or touches the device)
-    others_on = (world == 1 and not args.tiny and not demo and not args.total_pairs and not args.no_other_configs and args.nn_mode == 0 and engine_factory is None
-                 and args.config == 1)
+    others_on = (args.full and world == 1 and not args.tiny and not demo and not args.total_pairs and not args.no_other_configs and args.nn_mode == 0
+                 and engine_factory is None and args.config == 1)
     other_pool, other_jobs = None, {}
     if others_on:
         import multiprocessing as mp
@@ -712,7 +725,7 @@ def main(argv=None, engine_factory=None):
         other_work["configs[0]"] = ([global_pair(d_scenes, g) for g in range(n_demo)], d_P)
     checks, cpu, cpu_mc, cpu_ref, checks_conv = None, None, None, None, None
     other_checks = {}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         if world == 1:  # first: its children fork, and libgomp does not survive a fork once this process has run a parallel region
             if not demo:
                 cpu_mc = cpu_baseline_manycore(scenes, args.tiny, procs=2 if args.tiny else None, budget_s=1.0 if args.tiny else 6.0)
@@ -809,7 +822,8 @@ def main(argv=None, engine_factory=None):
     barrier()
     elapsed = time.perf_counter() - t0
     dump_ncorr = ncorr_of(results, len(pairs)) if args.dump_outputs and world == 1 and pairs else None  # (the records of the last timed step, before any later step)
-    if not events_live:
+    # --- --full only from here to the JSON line: every figure below takes steps of its own --------------------------------------------
+    if args.full and not events_live:
         engine.set_profiling(2)
         step()
         for _ in range(args.steps):
@@ -818,24 +832,25 @@ def main(argv=None, engine_factory=None):
             for k in prof_keys:
                 acc[k] += pf.icp_phase_ms[5] if k == "icp_loop_ms" else getattr(pf, k)
     # the same K steps without the result gather (N > 1: what the exchange step costs)
-    elapsed_nogather = None
-    if world > 1:
+    elapsed_nogather, elapsed_all = None, None
+    if args.full and world > 1:
         barrier()
         t5 = time.perf_counter()
         for _ in range(args.steps):
             step_post(gather=False)
         barrier()
         elapsed_nogather = time.perf_counter() - t5
-    engine.set_profiling(1)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-        pf = engine.profile()
-        for k in ("ms_setup", "ms_filter", "ms_accum", "ms_residual"):
-            acc[k] += getattr(pf, k)
-    barrier()
-    elapsed_all = time.perf_counter() - t1
+    if args.full:
+        engine.set_profiling(1)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+            pf = engine.profile()
+            for k in ("ms_setup", "ms_filter", "ms_accum", "ms_residual"):
+                acc[k] += getattr(pf, k)
+        barrier()
+        elapsed_all = time.perf_counter() - t1
     engine.set_profiling(0)
 
     def max_over_ranks(x):
@@ -845,13 +860,15 @@ def main(argv=None, engine_factory=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    elapsed, elapsed_all = max_over_ranks(elapsed), max_over_ranks(elapsed_all)
+    elapsed = max_over_ranks(elapsed)
+    if elapsed_all is not None:
+        elapsed_all = max_over_ranks(elapsed_all)
     if elapsed_nogather is not None:
         elapsed_nogather = max_over_ranks(elapsed_nogather)
 
     # --- the realistic case next to the metric's case: same pairs, the call site's convergence thresholds ---------------------------
     conv = None
-    if not args.no_converging:
+    if args.full and not args.no_converging:
         Pc = converging_params(args.tiny)
         res_c = abi.make_result_array(max(len(pairs), 1))
 
@@ -879,7 +896,7 @@ def main(argv=None, engine_factory=None):
 
     # --- the timed configuration again over a fixed wall budget (a sampler outside the process then sees the device busy) -----------------
     sustained = None
-    if args.sustain_s > 0 and pairs:
+    if args.full and args.sustain_s > 0 and pairs:
         barrier()
         t4 = time.perf_counter()
         k_s = 0
@@ -898,7 +915,7 @@ def main(argv=None, engine_factory=None):
         sustained = {"value": n_total * k_s / el_s, "unit": "registrations/s", "steps": k_s, "seconds": el_s}
 
     e2e = None
-    if rank == 0 and world == 1 and pairs and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and pairs and not args.no_end_to_end:
         sub = pairs[: min(1024, len(pairs))]
         lean = hasattr(engine, "ctx")
         if lean:  # what the C++ bridge switches on: only the clouds the registration reads are staged (28 live bytes of each 48-byte record)
@@ -1032,7 +1049,7 @@ def main(argv=None, engine_factory=None):
             "dtype": "f32",
             "data": "real" if demo else "synthetic",
             "profiling_events_on": "around the dominant kernel (correspondence search) in the timed steps" if events_live else "none in the timed steps (see roofline.measured_in)",
-            "value_all_kernel_events_on": n_reg / elapsed_all,
+            "value_all_kernel_events_on": n_reg / elapsed_all if elapsed_all else None,
             "value_without_gather": n_reg / elapsed_nogather if elapsed_nogather else None,
             "config": {
                 "workload": ("configs[0]: the reference's demo data — 000000 <-> 000001, 000000 <-> 000015 (identity guess), 000000 <-> 000015 (odometry's guess), real 64-beam scans of "
@@ -1078,12 +1095,14 @@ def main(argv=None, engine_factory=None):
                         "the heavy pass (k_nn_lds, first iterations) by LDS-latency and VALU issue with one workgroup per CU (DESIGN.md sections 4 and 12.3); "
                         "the HBM fraction on the algorithmic bytes is reported as the contract asks",
                 "valu_view": valu_view,
-                "kernel_ms_per_step": {k: acc[k] / args.steps for k in ("ms_setup", "ms_nn", "ms_filter", "ms_accum", "ms_residual")},
+                "kernel_ms_per_step": {k: acc[k] / args.steps for k in ("ms_setup", "ms_nn", "ms_filter", "ms_accum", "ms_residual")} if args.full else None,
             },
         }
+        if not (events_live or args.full):  # (the search launches were bracketed in no step)
+            out["roofline"] = None
         if checks is not None:
             out["delta_T_vs_ref"] = oracle_check_compare(checks, results)
-        if demo and lo == 0 and len(pairs) >= len(scenes):
+        if args.full and demo and lo == 0 and len(pairs) >= len(scenes):
             # the first three pairs are the fixture's registrations themselves: against the REFERENCE'S OWN LINES' results
             dt_max = dr_max = 0.0
             codes_equal = True

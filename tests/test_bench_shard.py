@@ -87,7 +87,7 @@ def test_config_flag_selects_every_baseline_configuration():
     assert bench.parse_args(["--config", "0"]).data == "demo"
     assert bench.parse_args(["--config", "3"]).total_pairs == 1024 and bench.parse_args(["--config", "3", "--total-pairs", "64"]).total_pairs == 64
     common = ["--tiny", "--steps", "1", "--warmup", "0"]
-    p4 = _run([sys.executable, SHIM, "--config", "4"] + common)
+    p4 = _run([sys.executable, SHIM, "--config", "4", "--full"] + common)
     assert p4.returncode == 0, p4.stderr[-2000:]
     j4 = _json_line(p4.stdout)
     assert j4["config"]["workload"].startswith("configs[4]") and j4["unit"] == "registrations/s" and j4["scaling"] == "weak" and j4["dtype"] == "f32"
@@ -97,3 +97,23 @@ def test_config_flag_selects_every_baseline_configuration():
     assert p2.returncode == 0, p2.stderr[-2000:]
     j2 = _json_line(p2.stdout)
     assert j2["n_gpus"] == 2 and j2["config"]["workload"].startswith("configs[2]") and j2["config"]["pairs_per_step"] == 2 * j2["config"]["pairs_per_gpu_per_step"]
+
+
+def test_plain_line_is_the_headline_and_full_adds_the_legs(tmp_path):
+    """A plain run times and reports the headline alone; --full adds every other leg and leaves the headline's results as they are."""
+    common = ["--tiny", "--pairs", "3", "--steps", "2", "--warmup", "0"]
+    legs = {"delta_T_vs_ref", "value_converging", "value_sustained", "value_end_to_end", "cpu_baseline", "cpu_baseline_manycore"}
+    p = _run([sys.executable, SHIM, "--dump-table", str(tmp_path / "plain.npy")] + common)
+    assert p.returncode == 0, p.stderr[-2000:]
+    jp = _json_line(p.stdout)
+    assert not (legs | {"other_configs", "cpu_baseline_reference_lines", "delta_T_vs_reference_lines"}) & set(jp)
+    assert jp["value_all_kernel_events_on"] is None and jp["roofline"]["kernel_ms_per_step"] is None
+    f = _run([sys.executable, SHIM, "--full", "--sustain-s", "0.2", "--dump-table", str(tmp_path / "full.npy")] + common)
+    assert f.returncode == 0, f.stderr[-2000:]
+    jf = _json_line(f.stdout)
+    assert legs <= set(jf) and jf["delta_T_vs_ref"]["integer_outputs_equal"] and jf["value_all_kernel_events_on"] > 0
+    assert set(jf["roofline"]["kernel_ms_per_step"]) == {"ms_setup", "ms_nn", "ms_filter", "ms_accum", "ms_residual"}
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert jp[k] == jf[k], k
+    assert jp["config"]["result_table_sha256"] == jf["config"]["result_table_sha256"]
+    assert np.array_equal(np.load(tmp_path / "plain.npy"), np.load(tmp_path / "full.npy"))

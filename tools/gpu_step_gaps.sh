@@ -4,7 +4,7 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 T=${1:-gaps}; O=$PWD/gpurun_out/$T; mkdir -p $O
-timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/trace -- python bench.py --no-other-configs --steps 4 --warmup 1 --no-cpu-baseline --no-end-to-end --no-converging --sustain-s 0 > $O/run.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/trace -- python bench.py --full --no-other-configs --steps 4 --warmup 1 --no-cpu-baseline --no-end-to-end --no-converging --sustain-s 0 > $O/run.log 2>&1
 python - $O/trace <<'PY'
 import csv, glob, sys
 rows = []

@@ -4,7 +4,7 @@
 set -u
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 T=$1; ARGS=$2; L=${3:-mulls_amd/libmulls_hip.so}; O=$PWD/gpurun_out/$T; mkdir -p $O
-MULLS_HIP_LIB=$PWD/$L timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python bench.py $ARGS --no-other-configs --no-cpu-baseline --no-end-to-end --no-converging --sustain-s 0 > $O/run.log 2>&1
+MULLS_HIP_LIB=$PWD/$L timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python bench.py --full $ARGS --no-other-configs --no-cpu-baseline --no-end-to-end --no-converging --sustain-s 0 > $O/run.log 2>&1
 python tools/kernel_stats.py $O/trace "$T: $ARGS" > $O/stats.txt
 python - $O/trace > $O/series.txt <<'PY'
 import csv, glob, os, sys
