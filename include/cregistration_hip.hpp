@@ -632,6 +632,41 @@ inline bool voxel_downsample(const typename pcl::PointCloud<PointT>::Ptr &cloud_
 	return 1;
 }
 
+// CRegistration<PointT>::find_feature_correspondence_ncc (include/common/cregistration.hpp:409-601), verbatim signature and defaults: the correspondence
+// stage of the global (coarse) registration (test/mulls_reg.cpp:173-174, test/mulls_slam.cpp:532-540) in one device call (mulls_ncc_correspond).  The
+// binding is one early return at the top of the member function:
+//     #ifdef MULLS_USE_HIP
+//         return lo::hip::find_feature_correspondence_ncc<PointT>(target_kpts, source_kpts, target_corrs, source_corrs, fixed_num_corr, corr_num, reciprocal_on);
+//     #endif
+// The matched key points are appended to target_corrs / source_corrs (upstream push_backs).  With fixed_num_corr, pairs at exactly equal descriptor distances
+// come in ascending (target index, source index) order — upstream's unstable std::sort leaves that order open (include/mulls_hip.h).  The solver behind it
+// (coarse_reg_teaser / coarse_reg_ransac: TEASER++, PCL) stays the caller's.
+template <typename PointT>
+inline bool find_feature_correspondence_ncc(const typename pcl::PointCloud<PointT>::Ptr &target_kpts, const typename pcl::PointCloud<PointT>::Ptr &source_kpts,
+											typename pcl::PointCloud<PointT>::Ptr &target_corrs, typename pcl::PointCloud<PointT>::Ptr &source_corrs,
+											bool fixed_num_corr = false, int corr_num = 2000, bool reciprocal_on = true)
+{
+	mulls_ctx *ctx = thread_context();
+	const mulls_cloud tgt = borrow(target_kpts), src = borrow(source_kpts);
+	mulls_ncc_params P;
+	mulls_ncc_default_params(&P);
+	P.fixed_num_corr = fixed_num_corr ? 1 : 0;
+	P.corr_num = corr_num;
+	P.reciprocal_on = reciprocal_on ? 1 : 0;
+	const uint32_t cap = fixed_num_corr ? (uint32_t)(corr_num > 0 ? corr_num : 0) : tgt.n;
+	std::vector<int32_t> ti(cap ? cap : 1), si(cap ? cap : 1);
+	uint32_t n = 0;
+	const int rc = mulls_ncc_correspond(ctx, &tgt, &src, &P, ti.data(), si.data(), cap, &n);
+	if (rc < 0)
+		throw std::runtime_error(std::string("mulls_ncc_correspond failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (uint32_t k = 0; k < n && k < cap; k++)
+	{
+		target_corrs->points.push_back(target_kpts->points[ti[k]]); // :547-548, :584-585
+		source_corrs->points.push_back(source_kpts->points[si[k]]);
+	}
+	return rc != 0;
+}
+
 // CFilter<PointT>::extract_semantic_pts (include/common/cfilter.hpp:2295-2413), verbatim signature: the whole chain in one device call
 // (mulls_extract_features).  The binding is one early return at the top of the member function:
 //     #ifdef MULLS_USE_HIP

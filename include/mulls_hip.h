@@ -583,6 +583,33 @@ int mulls_block_motion_compensate(mulls_ctx *ctx, mulls_block *block, const doub
  * out: host buffer of cap 48-byte records; *n_out = size of pc_down (truncated to cap when larger). */
 int mulls_voxel_downsample(mulls_ctx *ctx, const void *pts, uint32_t n, uint32_t stride, float voxel_size, void *out, uint32_t cap, uint32_t *n_out);
 
+/* ---- key-point descriptor matching: CRegistration<PointT>::find_feature_correspondence_ncc (include/common/cregistration.hpp:409-601) ----
+ * The correspondence stage of the reference's global (coarse) registration (test/mulls_reg.cpp:170-179, test/mulls_slam.cpp:532-540): the key points of two
+ * scans (pc_vertex, MULLS_EX_VERTEX) are matched by the L1 distance of their 11-entry "neighbourhood category context" descriptors — the two packed codes
+ * encode_stable_points left in normal[0] / normal[1], the intensity normalised by the TARGET's range, normal[3] (curvature) and data[3] (height above
+ * ground).  The solver that consumes the pairs (TEASER++ / PCL RANSAC) is not part of this library.
+ *   not fixed_num_corr: every target key point i with the first source key point j* at the strictly smallest distance (a row without any distance below
+ *     FLT_MAX yields j* = 0), in ascending i; with reciprocal_on only while no other target is strictly closer to j*.
+ *   fixed_num_corr: the corr_num smallest of the Nt * Ns distances in ascending order, a pair being skipped once its target or its source point has been
+ *     used seven times (`count > 6`, :578).  Upstream orders them with a std::sort that looks at the distance only and is not stable: the order among exactly
+ *     equal distances is whatever that sort leaves.  THIS LIBRARY DEFINES IT as ascending flat index i * Ns + j (a stable sort of the table).  NaN distances are
+ *     never selected.  MULLS_E_UNSUPPORTED: Nt * Ns > INT32_MAX in this mode (upstream's int index overflows), corr_num > 65536.  corr_num <= 0: no pairs.
+ * The Nt x Ns table is never stored: the nearest-neighbour modes take 65536 x 65536 key points and more. */
+typedef struct mulls_ncc_params
+{
+	int32_t fixed_num_corr; /* [0] cregistration.hpp:411 */
+	int32_t corr_num;		/* [2000] */
+	int32_t reciprocal_on;	/* [1]; ignored when fixed_num_corr, as upstream */
+	int32_t reserved;
+} mulls_ncc_params;
+void mulls_ncc_default_params(mulls_ncc_params *p);
+/* returns 1: the reference's `true` (n_corr pairs, possibly 0); 0: its `false` (fewer than 10 key points on a side, *n_corr = 0); < 0: MULLS_E_*.
+ * tgt_idx[k] / src_idx[k]: indices into the two clouds, in the reference's push_back order.  *n_corr is the full count; at most cap pairs are written.
+ * The clouds are host memory (any stride that is a multiple of 4 and at least 36; the 20 bytes per key point the descriptor reads go up) or device-resident
+ * clouds of 48-byte records (mulls_block_cloud(..., MULLS_EX_VERTEX, ...), mulls_map_cloud). */
+int mulls_ncc_correspond(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const mulls_ncc_params *params, int32_t *tgt_idx,
+						 int32_t *src_idx, uint32_t cap, uint32_t *n_corr);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

@@ -307,6 +307,18 @@ def extract_params(ground=None, classify=None, apply_scanner_filter=0, approx_sc
     return p
 
 
+class NccParams(C.Structure):
+    """mulls_ncc_params: find_feature_correspondence_ncc's arguments behind the clouds (cregistration.hpp:411)"""
+
+    _fields_ = [("fixed_num_corr", C.c_int32), ("corr_num", C.c_int32), ("reciprocal_on", C.c_int32), ("reserved", C.c_int32)]
+
+
+def ncc_params(fixed_num_corr=0, corr_num=2000, reciprocal_on=1):
+    p = NccParams()
+    p.fixed_num_corr, p.corr_num, p.reciprocal_on = int(fixed_num_corr), int(corr_num), int(reciprocal_on)
+    return p
+
+
 def records(a):
     """Any point array (POINT_DTYPE records or raw (n, 48) bytes) as contiguous raw (n, 48) uint8 records, every byte kept."""
     a = np.asarray(a)

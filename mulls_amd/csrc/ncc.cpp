@@ -1,0 +1,201 @@
+// ncc.cpp — mulls_ncc_correspond: CRegistration<PointT>::find_feature_correspondence_ncc (cregistration.hpp:409-601), the correspondence stage of the
+// reference's global (coarse) registration, on the device (k_ncc.hip).  Host side: argument checks, staging of host clouds (the five live floats per key
+// point), the launch sequence, one download, and — fixed-number mode — the ordering of the at most 65 536 selected entries and upstream's serial walk.
+#include <cfloat>
+
+#include "ctx.h"
+#include "ncc_launch.h"
+
+// a context's scratch of this entry point: one device arena and one pinned host buffer, grow-only, reused between calls
+struct mulls_ncc_scratch
+{
+	unsigned char *dev = nullptr, *pin = nullptr;
+	size_t dev_cap = 0, pin_cap = 0;
+};
+
+void mulls_ncc_release(mulls_ctx *ctx)
+{
+	if (!ctx->ncc)
+		return;
+	staggered_free(ctx->ncc->dev);
+	if (ctx->ncc->pin)
+		(void)hipHostFree(ctx->ncc->pin);
+	delete ctx->ncc;
+	ctx->ncc = nullptr;
+}
+
+namespace
+{
+size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+
+// device-resident cloud (the library's own block / map memory, or any device allocation of the caller's) or host memory — as mulls_motion_compensate tells them apart
+bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
+{
+	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * MULLS_POINT_BYTES))
+		return true;
+	hipPointerAttribute_t at;
+	std::memset(&at, 0, sizeof(at));
+	if (hipPointerGetAttributes(&at, c.pts) == hipSuccess)
+		return at.type == hipMemoryTypeDevice;
+	(void)hipGetLastError(); // (an ordinary host pointer: the query reports an error on some runtimes — cleared)
+	return false;
+}
+
+void pack_live(const mulls_cloud &c, float *out)
+{
+	const unsigned char *p = static_cast<const unsigned char *>(c.pts);
+	for (uint32_t i = 0; i < c.n; i++, p += c.stride, out += MULLS_NCC_LIVE)
+	{
+		std::memcpy(out, p + 12, 12);	  // data[3], normal[0], normal[1]
+		std::memcpy(out + 3, p + 28, 8); // normal[3], intensity
+	}
+}
+} // namespace
+
+extern "C"
+{
+	void mulls_ncc_default_params(mulls_ncc_params *p)
+	{
+		if (!p)
+			return;
+		std::memset(p, 0, sizeof(*p));
+		p->fixed_num_corr = 0; // cregistration.hpp:411
+		p->corr_num = 2000;
+		p->reciprocal_on = 1;
+	}
+
+	int mulls_ncc_correspond(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const mulls_ncc_params *params, int32_t *tgt_idx,
+							 int32_t *src_idx, uint32_t cap, uint32_t *n_corr)
+	try
+	{
+		if (!ctx || !tgt_kpts || !src_kpts || !params || !n_corr || (cap && (!tgt_idx || !src_idx)))
+			return MULLS_E_INVALID;
+		*n_corr = 0;
+		const mulls_cloud T = *tgt_kpts, S = *src_kpts;
+		if ((T.n && !T.pts) || (S.n && !S.pts))
+			return MULLS_E_INVALID;
+		if (T.n > (uint32_t)INT32_MAX || S.n > (uint32_t)INT32_MAX) // upstream's sizes are ints
+			return MULLS_E_UNSUPPORTED;
+		if (T.n < 10u || S.n < 10u) // "Too few key points" (:421-425)
+			return 0;
+		const bool fixed = params->fixed_num_corr != 0;
+		uint32_t K = 0;
+		if (fixed)
+		{
+			if ((uint64_t)T.n * S.n > (uint64_t)INT32_MAX || params->corr_num > (int32_t)MULLS_NCC_MAX_CORR)
+			{
+				ctx->err = "mulls_ncc_correspond: fixed-number mode takes at most 2^31 - 1 table entries and corr_num <= 65536";
+				return MULLS_E_UNSUPPORTED;
+			}
+			if (params->corr_num <= 0)
+				return 1;
+			K = (uint32_t)std::min<uint64_t>((uint64_t)params->corr_num, (uint64_t)T.n * S.n); // :565
+		}
+		HIPCHK(ctx, hipSetDevice(ctx->device));
+		const bool t_dev = cloud_on_device(ctx, T), s_dev = cloud_on_device(ctx, S);
+		if ((t_dev && T.stride != MULLS_POINT_BYTES) || (s_dev && S.stride != MULLS_POINT_BYTES) || (!t_dev && (T.stride < 36u || T.stride % 4u)) ||
+			(!s_dev && (S.stride < 36u || S.stride % 4u)))
+		{
+			ctx->err = "mulls_ncc_correspond: stride (device clouds: 48; host clouds: a multiple of 4, at least 36)";
+			return MULLS_E_INVALID;
+		}
+		if (!ctx->ncc)
+			ctx->ncc = new mulls_ncc_scratch();
+		mulls_ncc_scratch &sc = *ctx->ncc;
+
+		// device arena
+		size_t off = 0;
+		auto take = [&](size_t bytes) {
+			const size_t at = off;
+			off += up256(bytes);
+			return at;
+		};
+		const size_t live = MULLS_NCC_LIVE * sizeof(float);
+		const size_t up_bytes = (t_dev ? 0 : T.n * live) + (s_dev ? 0 : S.n * live);
+		const size_t o_in_t = take(up_bytes), o_in_s = o_in_t + (t_dev ? 0 : T.n * live); // side by side: one upload
+		const size_t o_desc_t = take((size_t)T.n * 48u), o_desc_s = take((size_t)S.n * 48u);
+		const size_t o_rowkey = take((size_t)T.n * 8u), o_colkey = take((size_t)S.n * 8u);
+		const size_t o_mm = take(8);
+		const size_t out_bytes = fixed ? (size_t)(1u + K) * 8u : (size_t)(2u + 2u * (size_t)T.n) * 4u;
+		const size_t o_out = take(out_bytes);
+		const size_t sel_bytes = sizeof(NccSel) + (size_t)MULLS_NCC_HIST_LEVELS * MULLS_NCC_HIST_BUCKETS * 4u;
+		const size_t o_sel = take(fixed ? sel_bytes : 0);
+		if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
+			return rc;
+		if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, up256(up_bytes) + out_bytes, hipHostMallocDefault))
+			return rc;
+		unsigned char *pin_out = sc.pin + up256(up_bytes);
+		unsigned char *d = sc.dev;
+		hipStream_t st = ctx->stream;
+		mulls::StreamDrain drain{st};
+
+		// one upload: the live floats of the host clouds
+		if (!t_dev)
+			pack_live(T, reinterpret_cast<float *>(sc.pin));
+		if (!s_dev)
+			pack_live(S, reinterpret_cast<float *>(sc.pin + (t_dev ? 0 : T.n * live)));
+		if (up_bytes)
+			HIPCHK(ctx, hipMemcpyAsync(d + o_in_t, sc.pin, up_bytes, hipMemcpyHostToDevice, st));
+		const NccCloudIn in_t{t_dev ? static_cast<const float *>(T.pts) : reinterpret_cast<const float *>(d + o_in_t), T.n, t_dev ? 0u : 1u};
+		const NccCloudIn in_s{s_dev ? static_cast<const float *>(S.pts) : reinterpret_cast<const float *>(d + o_in_s), S.n, s_dev ? 0u : 1u};
+		float4 *desc_t = reinterpret_cast<float4 *>(d + o_desc_t), *desc_s = reinterpret_cast<float4 *>(d + o_desc_s);
+		unsigned long long *rowkey = reinterpret_cast<unsigned long long *>(d + o_rowkey), *colkey = reinterpret_cast<unsigned long long *>(d + o_colkey);
+		float *mm = reinterpret_cast<float *>(d + o_mm);
+		HIPCHK(ctx, launch_ncc_minmax(st, in_t, mm));
+		HIPCHK(ctx, launch_ncc_desc(st, in_t, in_s, mm, desc_t, desc_s, rowkey, colkey));
+
+		if (!fixed)
+		{
+			uint32_t *out = reinterpret_cast<uint32_t *>(d + o_out);
+			HIPCHK(ctx, launch_ncc_rowmin(st, desc_t, T.n, desc_s, S.n, rowkey));
+			if (params->reciprocal_on)
+				HIPCHK(ctx, launch_ncc_rowmin(st, desc_s, S.n, desc_t, T.n, colkey)); // the roles swapped: column minima
+			HIPCHK(ctx, launch_ncc_recip(st, rowkey, colkey, T.n, params->reciprocal_on != 0, out));
+			HIPCHK(ctx, hipMemcpyAsync(pin_out, out, out_bytes, hipMemcpyDeviceToHost, st));
+			HIPCHK(ctx, hipStreamSynchronize(st));
+			const uint32_t *h = reinterpret_cast<const uint32_t *>(pin_out);
+			const uint32_t n = std::min(h[0], T.n), w = std::min(n, cap);
+			if (w)
+			{
+				std::memcpy(tgt_idx, h + 2, (size_t)w * 4u);
+				std::memcpy(src_idx, h + 2 + T.n, (size_t)w * 4u);
+			}
+			*n_corr = n;
+			return 1;
+		}
+
+		unsigned long long *cand = reinterpret_cast<unsigned long long *>(d + o_out);
+		HIPCHK(ctx, hipMemsetAsync(d + o_sel, 0, sel_bytes, st));
+		HIPCHK(ctx, hipMemsetAsync(cand, 0, 8, st));
+		HIPCHK(ctx, launch_ncc_select(st, desc_t, T.n, desc_s, S.n, K, reinterpret_cast<NccSel *>(d + o_sel), reinterpret_cast<uint32_t *>(d + o_sel + sizeof(NccSel)), cand));
+		HIPCHK(ctx, hipMemcpyAsync(pin_out, cand, out_bytes, hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		unsigned long long *keys = reinterpret_cast<unsigned long long *>(pin_out);
+		const uint32_t got = (uint32_t)std::min<unsigned long long>(keys[0] & 0xffffffffull, K);
+		// ascending distance, equal distances by ascending flat index: the order this library defines where upstream's unstable std::sort leaves it open
+		std::sort(keys + 1, keys + 1 + got);
+		// :567-586 — a point may take part while its count is not above 6, i.e. seven times
+		std::vector<int32_t> count_t(T.n, 0), count_s(S.n, 0);
+		uint32_t n = 0;
+		for (uint32_t k = 0; k < got; k++)
+		{
+			const uint32_t index = (uint32_t)keys[1 + k], i = index / S.n, j = index % S.n;
+			if (count_t[i] > 6 || count_s[j] > 6)
+				continue;
+			count_t[i]++;
+			count_s[j]++;
+			if (n < cap)
+			{
+				tgt_idx[n] = (int32_t)i;
+				src_idx[n] = (int32_t)j;
+			}
+			n++;
+		}
+		*n_corr = n;
+		return 1;
+	}
+	catch (...)
+	{
+		return mulls::abi_caught(ctx); // nothing is thrown across the ABI
+	}
+}

@@ -101,6 +101,9 @@ def load():
     lib.mulls_motion_compensate.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_float]
     lib.mulls_block_motion_compensate.argtypes = [vp, vp, C.POINTER(C.c_double), C.c_int]
     lib.mulls_voxel_downsample.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_float, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.mulls_ncc_default_params.argtypes = [C.POINTER(abi.NccParams)]
+    lib.mulls_ncc_default_params.restype = None
+    lib.mulls_ncc_correspond.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.NccParams), vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_read_kitti_bin.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_read_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_write_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_int]
@@ -120,6 +123,7 @@ EXPORTS = [
     "mulls_set_option", "mulls_get_option", "mulls_block_create", "mulls_block_destroy", "mulls_extract_features_resident", "mulls_block_cloud", "mulls_block_download",
     "mulls_motion_compensate", "mulls_block_motion_compensate",
     "mulls_pack_results", "mulls_icp_batch_sharded", "mulls_pipe_create", "mulls_pipe_destroy", "mulls_pipe_depth", "mulls_pipe_ctx", "mulls_pipe_set_option", "mulls_icp_batch_begin", "mulls_icp_batch_end",
+    "mulls_ncc_default_params", "mulls_ncc_correspond",
 ]
 
 
@@ -384,6 +388,35 @@ class Context:
         self._check(self.lib.mulls_voxel_downsample(self.h, raw_in.ctypes.data_as(C.c_void_p), n, abi.POINT_BYTES, C.c_float(voxel_size),
                                                     out.ctypes.data_as(C.c_void_p), n, C.byref(n_out)), "mulls_voxel_downsample")
         return out[: n_out.value].copy()
+
+    # --- key-point descriptor matching -------------------------------------------------------------------------------
+    def ncc_correspond(self, tgt_kpts, src_kpts, params=None, cap=None):
+        """find_feature_correspondence_ncc (mulls_ncc_correspond).  tgt_kpts / src_kpts: host clouds (POINT_DTYPE records or raw (n, 48) bytes) or
+        device-resident abi.Cloud objects (Block.cloud(abi.EX_VERTEX)).  Returns (ok, tgt_idx, src_idx, n_corr): the reference's bool, the index pairs
+        actually written (min(n_corr, cap) of them; cap defaults to what the mode can return at most) and the full count."""
+        keep = []
+
+        def cloud(k):
+            if isinstance(k, abi.Cloud):
+                return k
+            raw = abi.records(k)
+            keep.append(raw)
+            c = abi.Cloud()
+            c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+            return c
+
+        ct, cs = cloud(tgt_kpts), cloud(src_kpts)
+        p = params if params is not None else abi.ncc_params()
+        if cap is None:
+            cap = max(0, min(p.corr_num, 65536)) if p.fixed_num_corr else ct.n
+        ti, si = np.full(cap + 1, -1, np.int32), np.full(cap + 1, -1, np.int32)  # one slot past cap: callers may check that it is left alone
+        n = C.c_uint32(0)
+        rc = self.lib.mulls_ncc_correspond(self.h, C.byref(ct), C.byref(cs), C.byref(p), ti.ctypes.data_as(C.c_void_p), si.ctypes.data_as(C.c_void_p), cap, C.byref(n))
+        if rc < 0:
+            raise MullsError("mulls_ncc_correspond failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        w = min(n.value, cap)
+        assert ti[cap] == -1 and si[cap] == -1
+        return bool(rc), ti[:w].copy(), si[:w].copy(), n.value
 
     # --- stage-level entry points --------------------------------------------------------------------------------
     def motion_compensate(self, pts, Tran, s_ambiguous_thre=0.0):

@@ -1,8 +1,9 @@
 """Pairwise registration of two point clouds with the library, stage for stage what test/mulls_reg.cpp does (script/run_mulls_reg.sh):
 read -> voxel_downsample (cloud_*_down_res, 0 = off as in run_mulls_reg.sh) -> fast_ground_filter -> classify_nground_pts per cloud -> the
 cloud with more down-sampled feature points is the target -> mm_lls_icp -> the source's pc_down, transformed, written out.  Flags carry the
-reference's names and defaults (test/mulls_reg.cpp:24-60).  Not here: the global coarse registration (TEASER / RANSAC on key-point
-correspondences: --is_global_reg must be false, the initial guess is the identity), the viewers.
+reference's names and defaults (test/mulls_reg.cpp:24-60).  Not here: the solver of the global coarse registration (TEASER++ / PCL RANSAC — the
+key-point correspondences it consumes are in the library, mulls_ncc_correspond, but have no consumer in this tool: --is_global_reg must be false, the initial
+guess is the identity), the viewers.
 
     python tools/mulls_reg.py --point_cloud_1_path a.pcd --point_cloud_2_path b.pcd --output_point_cloud_path b_reg.pcd --is_global_reg=false
 """
