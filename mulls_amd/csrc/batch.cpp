@@ -944,6 +944,71 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 	return MULLS_OK;
 }
 
+// ---- the launch sequences every entry point that runs a batch shares (mulls_batch_run, the 3-DOF variant, the stage-level entry points) ----------------------
+
+// clone + initial guess + intersection filter (cregistration.hpp:1180-1188)
+void queue_clone_crop(hipStream_t st, const mulls_batch *B, const RunParams &rp)
+{
+	launch_clone_src(st, *B, rp, (uint32_t)B->setup_jobs_h.size());
+	launch_crop(st, *B, rp, (uint32_t)B->n, (uint32_t)B->big_segs_h.size(), (uint32_t)B->big_clouds_h.size());
+}
+
+// keep_less_source_points: thin the cropped clouds by the caller's keep masks (one byte per staged source / target point)
+int apply_keep_masks(mulls_ctx *ctx, const mulls_batch *B, const std::vector<uint8_t> &skeep, const std::vector<uint8_t> &tkeep, const char *what)
+{
+	hipStream_t st = ctx->stream;
+	uint8_t *d_sk = nullptr, *d_tk = nullptr;
+	if (dmalloc(ctx, &d_sk, skeep.size()) != MULLS_OK || dmalloc(ctx, &d_tk, tkeep.size()) != MULLS_OK)
+		return MULLS_E_HIP;
+	hipError_t e = hipMemcpyAsync(d_sk, skeep.data(), skeep.size(), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(d_tk, tkeep.data(), tkeep.size(), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess)
+	{
+		launch_thin(st, *B, (uint32_t)B->n, d_sk, d_tk);
+		e = hipStreamSynchronize(st); // the masks are freed right below
+	}
+	(void)hipFree(d_sk);
+	(void)hipFree(d_tk);
+	if (e != hipSuccess)
+	{
+		ctx->err = std::string(what) + hipGetErrorString(e);
+		return MULLS_E_HIP;
+	}
+	return MULLS_OK;
+}
+
+// the target grids: the LDS tier's (fused_tgt: crop and grid in one pass, no cropped copy; else from the copies k_crop wrote), then the bitmap grids
+void queue_target_grids(hipStream_t st, const mulls_batch *B, const RunParams &rp, int tier, bool fused_tgt)
+{
+	if (fused_tgt)
+		(void)launch_tgt_grid(st, *B, rp, (uint32_t)B->n);
+	else if (tier == 2)
+		launch_grid_build_sort(st, *B, rp, (uint32_t)B->n);
+	launch_bm_build(st, *B, (uint32_t)B->lclouds_h.size(), (uint32_t)B->tjobs_h.size());
+}
+
+// one iteration's search of a batch on ONE tier (0 / 1 / 2), every job in one slice, then k_filter unless the search kernels ran the rejection chain themselves
+int queue_tier_search(mulls_ctx *ctx, const mulls_batch *B, const RunParams &rp, int tier, uint32_t lds_cap, uint32_t parity)
+{
+	hipStream_t st = ctx->stream;
+	if (tier == 2)
+	{
+		if (launch_nn_lds(st, *B, rp, B->cjobs, (uint32_t)B->cjobs_h.size(), lds_cap, B->wl, B->wl_ctr, parity) != 0)
+		{
+			ctx->err = "could not raise the dynamic LDS limit of k_nn_lds";
+			return MULLS_E_HIP;
+		}
+	}
+	else if (tier == 1)
+		launch_cert_big(st, *B, rp, B->bjobs, (uint32_t)B->bjobs_h.size(), 2048u);
+	else
+		launch_nn(st, *B, rp, B->jobs, B->njobs);
+	if (!rp.lds_dedup)
+		launch_filter(st, *B, rp, B->jobs, B->njobs);
+	return MULLS_OK;
+}
+
 // run-wide constants of the per-iteration algebra (the float conversions of cregistration.hpp:1150-1157)
 mulls::IcpConst icp_const(const mulls_params *P)
 {

@@ -53,7 +53,8 @@ struct SegCopier
 	int flush(hipStream_t st); // batch.cpp
 };
 
-struct mulls_batch
+// (the device arrays the launch wrappers read are the base: BatchDev, launch.h)
+struct mulls_batch : BatchDev
 {
 	int n = 0;
 	size_t n_src = 0, n_tgt = 0; // staged points over all pairs and classes
@@ -79,61 +80,23 @@ struct mulls_batch
 	size_t cap_icp_pin = 0;
 	std::string jobs_key;
 	uint32_t njobs = 0;
-	// device
-	float4 *stage = nullptr;
-	float4 *tmp_pos = nullptr, *tmp_nrm = nullptr;
-	float4 *spos = nullptr, *snrm = nullptr, *tpos = nullptr, *tnrm = nullptr;
-	uint8_t *flag = nullptr;
-	int32_t *match = nullptr, *nn_idx = nullptr, *nn_hint = nullptr;
+	// device (besides BatchDev's)
 	uint4 *nn_cand = nullptr; // per source point: candidate record of the k-candidate certificates (RunParams::cand)
-	float4 *mq = nullptr; // per source point: position and direction of its matched target (2 records), written with match[]
-	float *wd = nullptr, *nn_d2 = nullptr;
-	unsigned long long *winner = nullptr;
 	uint32_t tick = 1; // duplicate-table epoch counter of THIS batch's winner table, monotone between resets (take_epochs)
-	CloudDesc *descs = nullptr;
-	PairSetup *setup = nullptr;
-	PairState *states = nullptr;	 // HBM copy of the pair states (filled by k_push_states every iteration)
-	PairState *states_pin = nullptr; // device address of the pinned host array states_h
-	PairOut *outs = nullptr;	   // HBM: filled by k_finish
 	size_t cap_outs = 0;
-	PairOut *outs_pin = nullptr; // device address of the pinned host array outs_h (packed records, k_pull_outs)
-	uint32_t *bbox = nullptr;
-	Job *setup_jobs = nullptr;
-	Job *big_segs = nullptr, *big_clouds = nullptr;
-	uint32_t *seg_cnt = nullptr, *big_box = nullptr;
 	size_t cap_big[4] = {};
-	Job *jobs = nullptr;
-	double *partial = nullptr;
-	Job *tjobs = nullptr;
-	Job *cjobs = nullptr;
-	Job *bjobs = nullptr, *fjobs = nullptr, *ejobs = nullptr;
-	uint32_t *lclouds = nullptr;
 	size_t cap_bjobs[4] = {};
-	uint32_t *bm_cs = nullptr; // bitmap grids: first sorted position of every occupied cell (indexed like cell_cnt)
 	size_t cap_bm_cs = 0;
-	uint32_t *bm_rank = nullptr; // bitmap grids: every target point's (cell counter index, arrival number in its cell), from k_bm_count to k_bm_scatter — the scatter is
-								 // pure data movement: one pass of atomics per build instead of two
 	size_t cap_bm_rank = 0;
-	uint32_t *ajobs = nullptr;
 	size_t cap_ajobs = 0;
-	IcpOut *icp_outs = nullptr;
 	size_t cap_icp_outs = 0;
-	mulls::StepState *steps = nullptr; // lock-step loop with the device step: per-pair loop state
 	size_t cap_steps = 0;
-	uint32_t epoch2 = 0, epoch3 = 0; // ... and the last epochs issued on its 8-byte words (words 32-33 / 48-49 of epoch_h: one per sub-batch)
+	uint32_t epoch2 = 0, epoch3 = 0; // the device-stepped loop's last epochs issued on its 8-byte words (words 32-33 / 48-49 of epoch_h: one per sub-batch)
 	int nsub = 1;		 // sub-batches the job tables are laid out for (build_jobs)
 	double fill_ms = 0.0, fill_pack_ms = 0.0; // the last batch_fill: wall time, host packing time ...
 	uint64_t fill_bytes = 0;				   // ... and bytes staged
-	uint32_t *wl = nullptr;		// LDS tier: class clouds k_cert queued for k_nn_lds (one slot per class-level job)
-	uint32_t *wl_ctr = nullptr; // ... and the queue counters: per sub-batch 8 words = (queued, taken) x launch parity
 	size_t cap_wl = 0;
-	GridDesc *grids = nullptr;
-	float4 *tsorted = nullptr;
 	unsigned long long *dbg = nullptr; // diagnostics (MULLS_OPT_DEBUG_STOP = 20): RunParams::dbg_ticks
-	uint16_t *tmap = nullptr; // LDS tier without a cropped copy of the target clouds (k_tgt_grid): rank in the cropped cloud -> staged index
-	uint32_t *cell_cnt = nullptr, *cell_start = nullptr; // bitmap grids: per-occupied-cell counters (start positions: bm_cs); LDS tier: dense cell tables
-	unsigned long long *bm = nullptr;					  // global tier: occupancy words of every grid
-	uint32_t *pf = nullptr;								  // global tier: occupied cells before each word
 	size_t cap_bm = 0, cap_pf = 0;
 	// pinned, device-mapped host memory (zero-copy): per-iteration pair states in, per-pair sums out, completion epoch
 	PairState *states_h = nullptr;
@@ -142,7 +105,6 @@ struct mulls_batch
 	uint32_t *epoch_dev = nullptr;
 	uint32_t epoch = 0;			// last epoch issued on word 0 (sub-batch 0 and the single-shot entry points)
 	uint32_t epoch1 = 0;		// last epoch issued on word 16 (sub-batch 1)
-	uint32_t *ticket = nullptr; // device: arrival counters of k_finish (one per sub-batch, 16 words apart)
 	uint32_t *bbox_h = nullptr;
 	uint8_t *upload_h = nullptr; // pinned staging buffer of the caller's point records
 	CloudDesc *descs_init = nullptr; // pristine descriptors (device): restored into `descs` by a D2D copy every run
@@ -197,6 +159,11 @@ int choose_tier(const mulls_ctx *ctx, const mulls_batch *B, const uint8_t used[M
 int batch_fill(mulls_ctx *ctx, mulls_batch *B, const mulls_pair *pairs, int n, const mulls_params *P = nullptr);
 // nsub: sub-batches the lock-step job tables are laid out for (0 = subbatch_count)
 int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunParams &rp, uint32_t *lds_cap_out, int *tier_out, int nsub = 0, bool allow_mixed = false);
+// the launch sequences the entry points share (batch.cpp, behind prepare_run); st: where the set-up goes, ctx->stream otherwise
+void queue_clone_crop(hipStream_t st, const mulls_batch *B, const RunParams &rp);
+int apply_keep_masks(mulls_ctx *ctx, const mulls_batch *B, const std::vector<uint8_t> &skeep, const std::vector<uint8_t> &tkeep, const char *what);
+void queue_target_grids(hipStream_t st, const mulls_batch *B, const RunParams &rp, int tier, bool fused_tgt);
+int queue_tier_search(mulls_ctx *ctx, const mulls_batch *B, const RunParams &rp, int tier, uint32_t lds_cap, uint32_t parity);
 mulls::IcpConst icp_const(const mulls_params *P);
 int take_epochs(mulls_ctx *ctx, mulls_batch *B, uint32_t n, RunParams &rp);
 

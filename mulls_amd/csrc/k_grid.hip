@@ -622,35 +622,32 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 #include <algorithm>
 
 // LDS tier without the fused setup: one workgroup per cropped target class cloud (k_crop wrote the copies)
-void launch_grid_build_sort(hipStream_t st, uint32_t npairs, const CloudDesc *descs, GridDesc *grids, const RunParams &rp, const float4 *tpos, uint32_t *cell_start,
-							float4 *tsorted)
+void launch_grid_build_sort(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs)
 {
 	if (npairs)
-		hipLaunchKernelGGL(k_grid_build_sort, dim3(npairs * MULLS_NC), dim3(MULLS_LDS_BLOCK), 0, st, descs, grids, rp, tpos, cell_start, tsorted);
+		hipLaunchKernelGGL(k_grid_build_sort, dim3(npairs * MULLS_NC), dim3(MULLS_LDS_BLOCK), 0, st, b.descs, b.grids, rp, b.tpos, b.cell_start, b.tsorted);
 }
 
-// global-memory tier: occupancy bitmap + ranks + counting sort by rank (cs holds the start positions) of the `nl` class clouds lclouds[]; tjobs = their
+// global-memory tier: occupancy bitmap + ranks + counting sort by rank (bm_cs holds the start positions) of the `nl` class clouds b.lclouds[]; b.tjobs = their
 // 256-point chunks
-void launch_bm_build(hipStream_t st, uint32_t nl, const uint32_t *lclouds, uint32_t ntjobs, const Job *tjobs, const CloudDesc *descs, GridDesc *grids, const float4 *tpos,
-					 unsigned long long *bm, uint32_t *pf, uint32_t *cnt, uint32_t *cs, float4 *tsorted, uint32_t *rank)
+void launch_bm_build(hipStream_t st, const BatchDev &b, uint32_t nl, uint32_t ntjobs)
 {
 	if (!nl)
 		return;
-	hipLaunchKernelGGL(k_bm_clear, dim3(nl, nl >= 64 ? 4 : 64), dim3(MULLS_BLOCK), 0, st, lclouds, grids, bm);
+	hipLaunchKernelGGL(k_bm_clear, dim3(nl, nl >= 64 ? 4 : 64), dim3(MULLS_BLOCK), 0, st, b.lclouds, b.grids, b.bm);
 	if (ntjobs)
-		hipLaunchKernelGGL(k_bm_mark, dim3((ntjobs + MULLS_BM_CH - 1) / MULLS_BM_CH), dim3(MULLS_BLOCK), 0, st, tjobs, ntjobs, descs, grids, tpos, bm);
-	hipLaunchKernelGGL(k_bm_scan, dim3(nl), dim3(1024), 0, st, lclouds, grids, bm, pf);
+		hipLaunchKernelGGL(k_bm_mark, dim3((ntjobs + MULLS_BM_CH - 1) / MULLS_BM_CH), dim3(MULLS_BLOCK), 0, st, b.tjobs, ntjobs, b.descs, b.grids, b.tpos, b.bm);
+	hipLaunchKernelGGL(k_bm_scan, dim3(nl), dim3(1024), 0, st, b.lclouds, b.grids, b.bm, b.pf);
 	if (ntjobs)
-		hipLaunchKernelGGL(k_bm_count, dim3((ntjobs + MULLS_BM_CH - 1) / MULLS_BM_CH), dim3(MULLS_BLOCK), 0, st, tjobs, ntjobs, descs, grids, tpos, bm, pf, cnt, rank);
-	hipLaunchKernelGGL(k_bm_starts, dim3(nl), dim3(1024), 0, st, lclouds, descs, grids, cnt, cs);
+		hipLaunchKernelGGL(k_bm_count, dim3((ntjobs + MULLS_BM_CH - 1) / MULLS_BM_CH), dim3(MULLS_BLOCK), 0, st, b.tjobs, ntjobs, b.descs, b.grids, b.tpos, b.bm, b.pf, b.cell_cnt, b.bm_rank);
+	hipLaunchKernelGGL(k_bm_starts, dim3(nl), dim3(1024), 0, st, b.lclouds, b.descs, b.grids, b.cell_cnt, b.bm_cs);
 	if (ntjobs)
-		hipLaunchKernelGGL(k_bm_scatter, dim3((ntjobs + MULLS_BM_CH - 1) / MULLS_BM_CH), dim3(MULLS_BLOCK), 0, st, tjobs, ntjobs, descs, tpos, rank, cs, tsorted);
+		hipLaunchKernelGGL(k_bm_scatter, dim3((ntjobs + MULLS_BM_CH - 1) / MULLS_BM_CH), dim3(MULLS_BLOCK), 0, st, b.tjobs, ntjobs, b.descs, b.tpos, b.bm_rank, b.bm_cs, b.tsorted);
 }
 
-int launch_tgt_grid(hipStream_t st, uint32_t npairs, CloudDesc *descs, const PairSetup *setup, const uint32_t *bbox, const float4 *stage, const RunParams &rp,
-					GridDesc *grids, uint16_t *tmap, uint32_t *cell_start, float4 *tsorted)
+int launch_tgt_grid(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs)
 {
 	if (npairs)
-		hipLaunchKernelGGL(k_tgt_grid, dim3(npairs * MULLS_NC), dim3(MULLS_TG_LANES), 0, st, descs, setup, bbox, stage, rp, grids, tmap, cell_start, tsorted);
+		hipLaunchKernelGGL(k_tgt_grid, dim3(npairs * MULLS_NC), dim3(MULLS_TG_LANES), 0, st, b.descs, b.setup, b.bbox, b.stage, rp, b.grids, b.tmap, b.cell_start, b.tsorted);
 	return 0;
 }

@@ -904,8 +904,7 @@ __global__ void k_set_corr(uint32_t src_off, const int32_t *__restrict__ cs, con
 // host-callable launch wrappers (the driver is plain C++ and never sees <<< >>>)
 #include "launch.h"
 
-void launch_accum(hipStream_t st, const uint32_t *leaders, const uint32_t split[4], const Job *jobs, const CloudDesc *descs, const PairState *states, const RunParams &rp,
-				  const float4 *spos, const float4 *mq, const uint8_t *flag, float *wd, double *partial, bool single, uint32_t wave_min_trips)
+void launch_accum(hipStream_t st, const BatchDev &b, const RunParams &rp, const uint32_t split[4], bool single, uint32_t wave_min_trips)
 {
 	(void)dev_launch<3>([](DevLaunch &) { // per device (launch.h)
 		return hipFuncSetAttribute(reinterpret_cast<const void *>(k_accum<1024, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MULLS_RED_BYTES_HALF) == hipSuccess;
@@ -915,8 +914,8 @@ void launch_accum(hipStream_t st, const uint32_t *leaders, const uint32_t split[
 	const uint32_t n_trips = split[3] - split[0];
 	if (wave_min_trips && n_trips >= wave_min_trips && rp.faithful && rp.pull_comb)
 	{
-		hipLaunchKernelGGL(k_accum_wave, dim3((n_trips + MULLS_ACCW_WAVES / MULLS_ACCW_SPLIT - 1u) / (MULLS_ACCW_WAVES / MULLS_ACCW_SPLIT)), dim3(64 * MULLS_ACCW_WAVES), 0, st, leaders + split[0], n_trips, jobs, descs, states, rp, spos,
-						   mq, flag, wd, partial);
+		hipLaunchKernelGGL(k_accum_wave, dim3((n_trips + MULLS_ACCW_WAVES / MULLS_ACCW_SPLIT - 1u) / (MULLS_ACCW_WAVES / MULLS_ACCW_SPLIT)), dim3(64 * MULLS_ACCW_WAVES), 0, st, b.ajobs + split[0], n_trips, b.jobs, b.descs, b.states, rp, b.spos,
+						   b.mq, b.flag, b.wd, b.partial);
 		return;
 	}
 	if (single)
@@ -924,72 +923,71 @@ void launch_accum(hipStream_t st, const uint32_t *leaders, const uint32_t split[
 		// small batches: one launch for every trip length (a kernel of a few hundred workgroups takes ~5 us whatever it does: two launches saved
 		// are worth more than the short trips' better occupancy)
 		if (split[3] > split[0])
-			hipLaunchKernelGGL((k_accum<1024, 2>), dim3(split[3] - split[0]), dim3(1024), MULLS_RED_BYTES_HALF, st, leaders + split[0], jobs, descs, states, rp, spos, mq,
-							   flag, wd, partial);
+			hipLaunchKernelGGL((k_accum<1024, 2>), dim3(split[3] - split[0]), dim3(1024), MULLS_RED_BYTES_HALF, st, b.ajobs + split[0], b.jobs, b.descs, b.states, rp, b.spos, b.mq,
+							   b.flag, b.wd, b.partial);
 		return;
 	}
 	// leaders[split[0] .. split[1]): trips of more than 512 slots; [split[1] .. split[2]): 257..512; [split[2] .. split[3]): up to 256
 	if (split[1] > split[0])
-		hipLaunchKernelGGL((k_accum<1024, 2>), dim3(split[1] - split[0]), dim3(1024), MULLS_RED_BYTES_HALF, st, leaders + split[0], jobs, descs, states, rp, spos, mq, flag,
-						   wd, partial);
+		hipLaunchKernelGGL((k_accum<1024, 2>), dim3(split[1] - split[0]), dim3(1024), MULLS_RED_BYTES_HALF, st, b.ajobs + split[0], b.jobs, b.descs, b.states, rp, b.spos, b.mq, b.flag,
+						   b.wd, b.partial);
 	if (split[2] > split[1])
-		hipLaunchKernelGGL((k_accum<512, 4>), dim3(split[2] - split[1]), dim3(512), MULLS_RED_BYTES_HALF / 2, st, leaders + split[1], jobs, descs, states, rp, spos, mq, flag,
-						   wd, partial);
+		hipLaunchKernelGGL((k_accum<512, 4>), dim3(split[2] - split[1]), dim3(512), MULLS_RED_BYTES_HALF / 2, st, b.ajobs + split[1], b.jobs, b.descs, b.states, rp, b.spos, b.mq, b.flag,
+						   b.wd, b.partial);
 	if (split[3] > split[2])
-		hipLaunchKernelGGL((k_accum<256, 8>), dim3(split[3] - split[2]), dim3(256), MULLS_RED_BYTES_HALF / 4, st, leaders + split[2], jobs, descs, states, rp, spos, mq, flag,
-						   wd, partial);
+		hipLaunchKernelGGL((k_accum<256, 8>), dim3(split[3] - split[2]), dim3(256), MULLS_RED_BYTES_HALF / 4, st, b.ajobs + split[2], b.jobs, b.descs, b.states, rp, b.spos, b.mq, b.flag,
+						   b.wd, b.partial);
 }
 
-void launch_finish(hipStream_t st, uint32_t npairs, CloudDesc *descs, const PairState *states, const RunParams &rp, const double *partial,
-				   PairOut *out, PairOut *out_host, const uint32_t *bbox, uint32_t *ticket, volatile uint32_t *host_epoch, uint32_t epoch,
-				   uint32_t pair_base)
+void launch_finish(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t pair_base, uint32_t npairs, uint32_t *ticket, volatile uint32_t *host_epoch, uint32_t epoch)
 {
 	if (!npairs)
 		return;
 	const bool direct = rp.pull_comb && npairs <= 64u; // launch-bound iterations: k_finish ships the records itself
-	hipLaunchKernelGGL(k_finish, dim3(npairs), dim3(MULLS_BLOCK), 0, st, descs, states, rp, partial, out, bbox, pair_base,
-					   direct ? reinterpret_cast<uint4 *>(out_host) : nullptr, ticket, host_epoch, epoch);
+	hipLaunchKernelGGL(k_finish, dim3(npairs), dim3(MULLS_BLOCK), 0, st, b.descs, b.states, rp, b.partial, b.outs, b.bbox, pair_base,
+					   direct ? reinterpret_cast<uint4 *>(b.outs_pin) : nullptr, ticket, host_epoch, epoch);
 	if (direct)
 		return;
 	uint32_t n_used = 0;
 	for (int c = 0; c < MULLS_NC; c++)
 		n_used += rp.used[c] ? 1u : 0u;
 	const uint32_t nwords = npairs * (8u + (MULLS_NTERM_PAD / 2u) * (rp.pull_comb ? 1u : n_used));
-	hipLaunchKernelGGL(k_pull_outs, dim3((nwords + MULLS_BLOCK - 1) / MULLS_BLOCK), dim3(MULLS_BLOCK), 0, st, reinterpret_cast<const uint4 *>(out),
-					   reinterpret_cast<uint4 *>(out_host), rp, pair_base, npairs, ticket, host_epoch, epoch);
+	hipLaunchKernelGGL(k_pull_outs, dim3((nwords + MULLS_BLOCK - 1) / MULLS_BLOCK), dim3(MULLS_BLOCK), 0, st, reinterpret_cast<const uint4 *>(b.outs),
+					   reinterpret_cast<uint4 *>(b.outs_pin), rp, pair_base, npairs, ticket, host_epoch, epoch);
 }
 
-void launch_step_init(hipStream_t st, uint32_t npairs, const PairSetup *setup, const mulls::IcpConst &K, mulls::StepState *steps, PairState *states)
+void launch_step_init(hipStream_t st, const BatchDev &b, const mulls::IcpConst &K, uint32_t npairs)
 {
 	if (npairs)
-		hipLaunchKernelGGL(k_step_init, dim3((npairs + 63u) / 64u), dim3(64), 0, st, npairs, setup, K, steps, states);
+		hipLaunchKernelGGL(k_step_init, dim3((npairs + 63u) / 64u), dim3(64), 0, st, npairs, b.setup, K, b.steps, b.states);
 }
 
-void launch_finish_step(hipStream_t st, uint32_t pair_base, uint32_t npairs, CloudDesc *descs, PairState *states, const RunParams &rp, const mulls::IcpConst &K, const double *partial,
-						PairOut *out, const uint32_t *bbox, mulls::StepState *steps, IcpOut *results, unsigned long long *host_word, uint32_t epoch, int brute,
-						uint32_t *ticket, bool sum_step)
+void launch_finish_step(hipStream_t st, const BatchDev &b, const RunParams &rp, const mulls::IcpConst &K, uint32_t pair_base, uint32_t npairs, unsigned long long *host_word, uint32_t epoch,
+						int brute, uint32_t *ticket, bool sum_step)
 {
 	if (!npairs)
 		return;
 	if (ticket) // small batch: one launch
 	{
-		hipLaunchKernelGGL(k_finish_step, dim3(npairs), dim3(MULLS_BLOCK), 0, st, descs, states, rp, K, partial, out, bbox, steps, results, brute, ticket, host_word, epoch,
+		hipLaunchKernelGGL(k_finish_step, dim3(npairs), dim3(MULLS_BLOCK), 0, st, b.descs, b.states, rp, K, b.partial, b.outs, b.bbox, b.steps, b.icp_outs, brute, ticket, host_word, epoch,
 						   pair_base);
 		return;
 	}
 	if (sum_step && rp.pull_comb)
-		hipLaunchKernelGGL(k_sum_step, dim3(npairs), dim3(64), 0, st, descs, states, rp, K, partial, out, bbox, steps, results, brute, pair_base);
+		hipLaunchKernelGGL(k_sum_step, dim3(npairs), dim3(64), 0, st, b.descs, b.states, rp, K, b.partial, b.outs, b.bbox, b.steps, b.icp_outs, brute, pair_base);
 	else
 	{
-		hipLaunchKernelGGL(k_finish, dim3(npairs), dim3(MULLS_BLOCK), 0, st, descs, states, rp, partial, out, bbox, pair_base, static_cast<uint4 *>(nullptr),
+		hipLaunchKernelGGL(k_finish, dim3(npairs), dim3(MULLS_BLOCK), 0, st, b.descs, b.states, rp, b.partial, b.outs, b.bbox, pair_base, static_cast<uint4 *>(nullptr),
 						   static_cast<uint32_t *>(nullptr), static_cast<volatile uint32_t *>(nullptr), 0u);
-		hipLaunchKernelGGL(k_step, dim3(npairs), dim3(64), 0, st, descs, states, rp, K, out, steps, results, brute, pair_base);
+		hipLaunchKernelGGL(k_step, dim3(npairs), dim3(64), 0, st, b.descs, b.states, rp, K, b.outs, b.steps, b.icp_outs, brute, pair_base);
 	}
-	hipLaunchKernelGGL(k_step_publish, dim3(1), dim3(1024), 0, st, states + pair_base, npairs, host_word, epoch);
+	hipLaunchKernelGGL(k_step_publish, dim3(1), dim3(1024), 0, st, b.states + pair_base, npairs, host_word, epoch);
 }
 
-void launch_push_states(hipStream_t st, const PairState *host_states, PairState *dev_states, uint32_t npairs)
+void launch_push_states(hipStream_t st, const BatchDev &b, uint32_t pair_base, uint32_t npairs)
 {
+	const PairState *host_states = b.states_pin + pair_base;
+	PairState *dev_states = b.states + pair_base;
 	const uint32_t nwords = npairs * (uint32_t)(sizeof(PairState) / 16);
 	if (nwords)
 		hipLaunchKernelGGL(k_push_states, dim3((nwords + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4 *>(host_states),
@@ -1018,9 +1016,8 @@ void launch_transform_aos(hipStream_t st, float4 *recs, uint32_t n, const double
 		hipLaunchKernelGGL(k_transform_aos, dim3((n + 255) / 256), dim3(256), 0, st, recs, n, T12);
 }
 
-void launch_set_corr(hipStream_t st, uint32_t src_off, const int32_t *cs, const int32_t *ct, const float *cd, uint32_t n, uint8_t *flag,
-					 int32_t *match, float *wd, uint32_t tgt_off, const float4 *tpos, const float4 *tnrm, float4 *mq)
+void launch_set_corr(hipStream_t st, const BatchDev &b, uint32_t src_off, const int32_t *cs, const int32_t *ct, const float *cd, uint32_t n, uint32_t tgt_off)
 {
 	if (n)
-		hipLaunchKernelGGL(k_set_corr, dim3((n + 255) / 256), dim3(256), 0, st, src_off, cs, ct, cd, n, flag, match, wd, tgt_off, tpos, tnrm, mq);
+		hipLaunchKernelGGL(k_set_corr, dim3((n + 255) / 256), dim3(256), 0, st, src_off, cs, ct, cd, n, b.flag, b.match, b.wd, tgt_off, b.tpos, b.tnrm, b.mq);
 }

@@ -592,11 +592,9 @@ size_t nn_lds_bytes(uint32_t cap, uint32_t maxcells, bool dedup)
 
 // one iteration of the LDS tier over the class clouds `jobs[0..njobs)`: k_cert for all of them, then k_nn_lds for the ones it
 // queued in `wl` (njobs entries; wl_ctr: 4 counters = (queued, taken) x the parity of this launch and of the next one)
-int launch_nn_lds(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *descs, const PairState *states, const RunParams &rp, float4 *spos,
-				  float4 *snrm, const GridDesc *grids, const uint32_t *cell_start, const float4 *tsorted, uint8_t *flag, int32_t *nn_idx,
-				  float *nn_d2, unsigned long long *winner, const float4 *tnrm, int32_t *match, float *wd, const float4 *tpos, int32_t *nn_hint, float4 *mq, uint32_t cap, uint32_t maxcells,
-				  uint32_t *wl, uint32_t *wl_ctr, uint32_t parity, bool first)
+int launch_nn_lds(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs, uint32_t cap, uint32_t *wl, uint32_t *wl_ctr, uint32_t parity, bool first)
 {
+	const uint32_t maxcells = rp.grid_maxcells;
 	// first: the run's iteration 0 with the rigid step applied by the setup (identity_step; class-level jobs, rp.lds_dedup, no normal shooting: the caller's
 	// conditions) — every called class cloud goes straight to the staged search (first_goes_direct)
 	// per device (launch.h: DevLaunch): k_nn_lds may take the whole LDS; dyn_max[0] = the dynamic LDS k_cert_nn can have next to its static block
@@ -627,34 +625,33 @@ int launch_nn_lds(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *de
 	if (njobs <= 2u * n_cu && rp.debug_stop != 10u && fused_lds_bytes(cap, maxcells, dedup) <= fused_dyn_max)
 	{
 		// light and heavy pass in one launch
-		hipLaunchKernelGGL(k_cert_nn, dim3(njobs), dim3(MULLS_LDS_BLOCK), fused_lds_bytes(cap, maxcells, dedup), st, jobs, descs, states, rp, spos, snrm, grids, cell_start,
-						   tsorted, flag, nn_idx, nn_d2, winner, tnrm, match, wd, tpos, nn_hint, mq, cap, first ? 1u : 0u);
+		hipLaunchKernelGGL(k_cert_nn, dim3(njobs), dim3(MULLS_LDS_BLOCK), fused_lds_bytes(cap, maxcells, dedup), st, jobs, b.descs, b.states, rp, b.spos, b.snrm, b.grids, b.cell_start,
+						   b.tsorted, b.flag, b.nn_idx, b.nn_d2, b.winner, b.tnrm, b.match, b.wd, b.tpos, b.nn_hint, b.mq, cap, first ? 1u : 0u);
 		return 0;
 	}
 	if (first)
 		; // no light pass in iteration 0 (first_goes_direct; the next iteration's queue counters are as prepare_run cleared them)
 	else if (njobs <= 2u * n_cu)
-		hipLaunchKernelGGL(k_cert<1024>, dim3(njobs), dim3(1024), dedup ? ((size_t)cap * 2u + 3u) & ~(size_t)3 : 0u, st, jobs, descs, states, rp, spos, snrm, grids, cell_start, tsorted,
-						   flag, nn_idx, nn_d2, winner, tnrm, match, wd, tpos, nn_hint, mq, wl, wl_ctr, parity & 1u);
+		hipLaunchKernelGGL(k_cert<1024>, dim3(njobs), dim3(1024), dedup ? ((size_t)cap * 2u + 3u) & ~(size_t)3 : 0u, st, jobs, b.descs, b.states, rp, b.spos, b.snrm, b.grids, b.cell_start, b.tsorted,
+						   b.flag, b.nn_idx, b.nn_d2, b.winner, b.tnrm, b.match, b.wd, b.tpos, b.nn_hint, b.mq, wl, wl_ctr, parity & 1u);
 	else if (dedup && MULLS_CERT_BLOCK == 512 && D.dyn_max[1] && (((size_t)cap * 2u + 3u) & ~(size_t)3) + D.dyn_max[1] <= 40u * 1024u)
 		// (four workgroups per CU with the longer leftover list: dyn_max[1] = the 768-entry kernel's static LDS)
-		hipLaunchKernelGGL((k_cert<MULLS_CERT_BLOCK, 3, 768>), dim3(njobs), dim3(MULLS_CERT_BLOCK), ((size_t)cap * 2u + 3u) & ~(size_t)3, st, jobs, descs, states, rp, spos, snrm, grids,
-						   cell_start, tsorted, flag, nn_idx, nn_d2, winner, tnrm, match, wd, tpos, nn_hint, mq, wl, wl_ctr, parity & 1u);
+		hipLaunchKernelGGL((k_cert<MULLS_CERT_BLOCK, 3, 768>), dim3(njobs), dim3(MULLS_CERT_BLOCK), ((size_t)cap * 2u + 3u) & ~(size_t)3, st, jobs, b.descs, b.states, rp, b.spos, b.snrm, b.grids,
+						   b.cell_start, b.tsorted, b.flag, b.nn_idx, b.nn_d2, b.winner, b.tnrm, b.match, b.wd, b.tpos, b.nn_hint, b.mq, wl, wl_ctr, parity & 1u);
 	else
-		hipLaunchKernelGGL(k_cert<MULLS_CERT_BLOCK>, dim3(njobs), dim3(MULLS_CERT_BLOCK), dedup ? ((size_t)cap * 2u + 3u) & ~(size_t)3 : 0u, st, jobs, descs, states, rp, spos, snrm, grids,
-						   cell_start, tsorted, flag, nn_idx, nn_d2, winner, tnrm, match, wd, tpos, nn_hint, mq, wl, wl_ctr, parity & 1u);
+		hipLaunchKernelGGL(k_cert<MULLS_CERT_BLOCK>, dim3(njobs), dim3(MULLS_CERT_BLOCK), dedup ? ((size_t)cap * 2u + 3u) & ~(size_t)3 : 0u, st, jobs, b.descs, b.states, rp, b.spos, b.snrm, b.grids,
+						   b.cell_start, b.tsorted, b.flag, b.nn_idx, b.nn_d2, b.winner, b.tnrm, b.match, b.wd, b.tpos, b.nn_hint, b.mq, wl, wl_ctr, parity & 1u);
 	// one workgroup per CU is all the LDS allows: they take the queued class clouds by ticket
-	hipLaunchKernelGGL(k_nn_lds, dim3(njobs < n_cu ? njobs : n_cu), dim3(MULLS_LDS_BLOCK), nn_lds_bytes(cap, maxcells, dedup), st, jobs, descs, states, rp, spos, snrm,
-					   grids, cell_start, tsorted, flag, nn_idx, nn_d2, winner, tnrm, match, wd, tpos, nn_hint, mq, cap, wl, wl_ctr, parity & 1u, first ? njobs : 0u);
+	hipLaunchKernelGGL(k_nn_lds, dim3(njobs < n_cu ? njobs : n_cu), dim3(MULLS_LDS_BLOCK), nn_lds_bytes(cap, maxcells, dedup), st, jobs, b.descs, b.states, rp, b.spos, b.snrm,
+					   b.grids, b.cell_start, b.tsorted, b.flag, b.nn_idx, b.nn_d2, b.winner, b.tnrm, b.match, b.wd, b.tpos, b.nn_hint, b.mq, cap, wl, wl_ctr, parity & 1u, first ? njobs : 0u);
 	return 0;
 }
 
 // both tiers' class clouds of a small mixed batch in one launch (k_cert_mixed): 1 = launched, 0 = not applicable (the caller launches the tiers one after the other)
-int launch_cert_mixed(hipStream_t st, uint32_t n_lds, const Job *cjobs, uint32_t n_big, const Job *bjobs, uint32_t max_wgs, uint32_t rounds, CloudDesc *descs, const PairState *states,
-					  const RunParams &rp, float4 *spos, float4 *snrm, const GridDesc *grids, const uint32_t *cell_start, const unsigned long long *bm, const uint32_t *pf,
-					  const uint32_t *cs, const float4 *tsorted, uint8_t *flag, int32_t *nn_idx, float *nn_d2, unsigned long long *winner, const float4 *tnrm, int32_t *match,
-					  float *wd, const float4 *tpos, int32_t *nn_hint, float4 *mq, uint32_t cap, uint32_t maxcells, bool first)
+int launch_cert_mixed(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *cjobs, uint32_t n_lds, const Job *bjobs, uint32_t n_big, uint32_t max_wgs, uint32_t rounds,
+					  uint32_t cap, bool first)
 {
+	const uint32_t maxcells = rp.grid_maxcells;
 	const DevLaunch D = dev_launch<1>([](DevLaunch &d) { // per device (launch.h): the dynamic LDS k_cert_mixed can have next to its static block, the CU count
 		hipFuncAttributes fa;
 		d.dyn_max[0] = 1;
@@ -685,14 +682,12 @@ int launch_cert_mixed(hipStream_t st, uint32_t n_lds, const Job *cjobs, uint32_t
 	const size_t dyn = fused_lds_bytes(cap, maxcells, dedup) > sizeof(BigLds<MULLS_BIG_BLOCK * 3>) ? fused_lds_bytes(cap, maxcells, dedup) : sizeof(BigLds<MULLS_BIG_BLOCK * 3>);
 	if (n_lds + n_big * split > n_cu * rounds || n_lds > n_cu || dyn > dyn_max)
 		return 0;
-	hipLaunchKernelGGL(k_cert_mixed, dim3(n_lds + n_big * split), dim3(MULLS_LDS_BLOCK), dyn, st, n_lds, cjobs, bjobs, split, descs, states, rp, spos, snrm, grids, cell_start, bm, pf, cs,
-					   tsorted, flag, nn_idx, nn_d2, winner, tnrm, match, wd, tpos, nn_hint, mq, cap, first ? 1u : 0u);
+	hipLaunchKernelGGL(k_cert_mixed, dim3(n_lds + n_big * split), dim3(MULLS_LDS_BLOCK), dyn, st, n_lds, cjobs, bjobs, split, b.descs, b.states, rp, b.spos, b.snrm, b.grids, b.cell_start, b.bm, b.pf, b.bm_cs,
+					   b.tsorted, b.flag, b.nn_idx, b.nn_d2, b.winner, b.tnrm, b.match, b.wd, b.tpos, b.nn_hint, b.mq, cap, first ? 1u : 0u);
 	return 1;
 }
 
-void launch_cert_big(hipStream_t st, uint32_t njobs, const Job *jobs, uint32_t max_wgs, CloudDesc *descs, const PairState *states, const RunParams &rp, float4 *spos, float4 *snrm,
-					 const GridDesc *grids, const unsigned long long *bm, const uint32_t *pf, const uint32_t *cs, const float4 *tsorted, uint8_t *flag, int32_t *nn_idx,
-					 float *nn_d2, unsigned long long *winner, const float4 *tpos, const float4 *tnrm, int32_t *nn_hint, int32_t *match, float *wd, float4 *mq)
+void launch_cert_big(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs, uint32_t max_wgs)
 {
 	if (!njobs)
 		return;
@@ -702,30 +697,26 @@ void launch_cert_big(hipStream_t st, uint32_t njobs, const Job *jobs, uint32_t m
 	uint32_t split = 1;
 	while (split < 16 && njobs * split * 2u <= max_wgs)
 		split <<= 1;
-	hipLaunchKernelGGL(k_cert_big, dim3(njobs * split), dim3(MULLS_BIG_BLOCK), 0, st, jobs, descs, states, rp, spos, snrm, grids, bm, pf, cs, tsorted, flag, nn_idx, nn_d2, winner,
-					   split, tpos, tnrm, nn_hint, match, wd, mq);
+	hipLaunchKernelGGL(k_cert_big, dim3(njobs * split), dim3(MULLS_BIG_BLOCK), 0, st, jobs, b.descs, b.states, rp, b.spos, b.snrm, b.grids, b.bm, b.pf, b.bm_cs, b.tsorted, b.flag, b.nn_idx, b.nn_d2, b.winner,
+					   split, b.tpos, b.tnrm, b.nn_hint, b.match, b.wd, b.mq);
 }
 
-void launch_nn(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *descs, const PairState *states, const RunParams &rp, float4 *spos,
-			   float4 *snrm, const float4 *tpos, const uint8_t *flag, int32_t *nn_idx, float *nn_d2, unsigned long long *winner)
+void launch_nn(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs)
 {
 	if (njobs)
-		hipLaunchKernelGGL(k_nn, dim3(njobs), dim3(MULLS_NN_BLOCK), 0, st, jobs, descs, states, rp, spos, snrm, tpos, flag, nn_idx, nn_d2, winner);
+		hipLaunchKernelGGL(k_nn, dim3(njobs), dim3(MULLS_NN_BLOCK), 0, st, jobs, b.descs, b.states, rp, b.spos, b.snrm, b.tpos, b.flag, b.nn_idx, b.nn_d2, b.winner);
 }
 
-void launch_nn_shoot(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *descs, const PairState *states, const RunParams &rp,
-					 float4 *spos, float4 *snrm, const float4 *tpos, const uint8_t *flag, int32_t *nn_idx, float *nn_d2, unsigned long long *winner)
+void launch_nn_shoot(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs)
 {
 	if (njobs)
-		hipLaunchKernelGGL(k_nn_shoot, dim3(njobs), dim3(MULLS_BLOCK), 0, st, jobs, descs, states, rp, spos, snrm, tpos, flag, nn_idx, nn_d2,
-						   winner);
+		hipLaunchKernelGGL(k_nn_shoot, dim3(njobs), dim3(MULLS_BLOCK), 0, st, jobs, b.descs, b.states, rp, b.spos, b.snrm, b.tpos, b.flag, b.nn_idx, b.nn_d2,
+						   b.winner);
 }
 
-void launch_filter(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *descs, const PairState *states, const RunParams &rp,
-				   const float4 *snrm, const float4 *tnrm, uint8_t *flag, const int32_t *nn_idx, const float *nn_d2, int32_t *match, float *wd,
-				   const unsigned long long *winner, const float4 *tpos, float4 *mq, bool big)
+void launch_filter(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs, bool big)
 {
 	if (njobs)
-		hipLaunchKernelGGL(k_filter, dim3(njobs), dim3(MULLS_BLOCK), 0, st, jobs, descs, states, rp, snrm, tnrm, flag, nn_idx, nn_d2, match, wd,
-						   winner, tpos, mq, big ? 1u : 0u);
+		hipLaunchKernelGGL(k_filter, dim3(njobs), dim3(MULLS_BLOCK), 0, st, jobs, b.descs, b.states, rp, b.snrm, b.tnrm, b.flag, b.nn_idx, b.nn_d2, b.match, b.wd,
+						   b.winner, b.tpos, b.mq, big ? 1u : 0u);
 }

@@ -602,36 +602,31 @@ void launch_motion_comp(hipStream_t st, float4 *recs, uint32_t n, const double q
 	hipLaunchKernelGGL(k_motion_comp, dim3((n + MULLS_BLOCK - 1) / MULLS_BLOCK), dim3(MULLS_BLOCK), 0, st, recs, n, M);
 }
 
-void launch_clone_src(hipStream_t st, uint32_t njobs, const Job *jobs, const CloudDesc *descs, const PairSetup *setup, const float4 *stage,
-					  float4 *tmp_pos, float4 *tmp_nrm, uint32_t *bbox, const RunParams &rp)
+void launch_clone_src(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t njobs)
 {
 	if (njobs)
-		hipLaunchKernelGGL(k_clone_src, dim3(njobs), dim3(MULLS_BLOCK), 0, st, jobs, descs, setup, stage, tmp_pos, tmp_nrm, bbox, rp);
+		hipLaunchKernelGGL(k_clone_src, dim3(njobs), dim3(MULLS_BLOCK), 0, st, b.setup_jobs, b.descs, b.setup, b.stage, b.tmp_pos, b.tmp_nrm, b.bbox, rp);
 }
 
-void launch_crop(hipStream_t st, uint32_t npairs, CloudDesc *descs, const PairSetup *setup, const uint32_t *bbox, const float4 *stage,
-				 const float4 *tmp_pos, const float4 *tmp_nrm, float4 *spos, float4 *snrm, float4 *tpos, float4 *tnrm, uint8_t *flag,
-				 int32_t *match, float *wd, const RunParams &rp, GridDesc *grids, uint32_t nbig_segs, const Job *big_segs, uint32_t nbig_clouds,
-				 const Job *big_clouds, uint32_t *seg_cnt, uint32_t *big_box)
+void launch_crop(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs, uint32_t nbig_segs, uint32_t nbig_clouds)
 {
 	if (!npairs)
 		return;
-	hipLaunchKernelGGL(k_crop, dim3(npairs * MULLS_NC * 2), dim3(MULLS_BLOCK), 0, st, descs, setup, bbox, stage, tmp_pos, tmp_nrm, spos, snrm, tpos,
-					   tnrm, flag, match, wd, rp, grids, big_box);
+	hipLaunchKernelGGL(k_crop, dim3(npairs * MULLS_NC * 2), dim3(MULLS_BLOCK), 0, st, b.descs, b.setup, b.bbox, b.stage, b.tmp_pos, b.tmp_nrm, b.spos, b.snrm, b.tpos,
+					   b.tnrm, b.flag, b.match, b.wd, rp, b.grids, b.big_box);
 	if (nbig_clouds)
 	{
-		hipLaunchKernelGGL(k_crop_big_count, dim3(nbig_segs), dim3(MULLS_BLOCK), 0, st, big_segs, descs, setup, bbox, stage, tmp_pos, rp, seg_cnt, big_box + (size_t)nbig_clouds * 6u);
-		hipLaunchKernelGGL(k_crop_big_scan, dim3(nbig_clouds), dim3(64), 0, st, big_clouds, descs, rp, seg_cnt, big_box + (size_t)nbig_clouds * 6u, grids);
-		hipLaunchKernelGGL(k_crop_big_scatter, dim3(nbig_segs), dim3(MULLS_BLOCK), 0, st, big_segs, descs, setup, bbox, stage, rp, seg_cnt, tpos,
-						   tnrm, tmp_pos, tmp_nrm, spos, snrm, flag, match, wd);
+		hipLaunchKernelGGL(k_crop_big_count, dim3(nbig_segs), dim3(MULLS_BLOCK), 0, st, b.big_segs, b.descs, b.setup, b.bbox, b.stage, b.tmp_pos, rp, b.seg_cnt, b.big_box + (size_t)nbig_clouds * 6u);
+		hipLaunchKernelGGL(k_crop_big_scan, dim3(nbig_clouds), dim3(64), 0, st, b.big_clouds, b.descs, rp, b.seg_cnt, b.big_box + (size_t)nbig_clouds * 6u, b.grids);
+		hipLaunchKernelGGL(k_crop_big_scatter, dim3(nbig_segs), dim3(MULLS_BLOCK), 0, st, b.big_segs, b.descs, b.setup, b.bbox, b.stage, rp, b.seg_cnt, b.tpos,
+						   b.tnrm, b.tmp_pos, b.tmp_nrm, b.spos, b.snrm, b.flag, b.match, b.wd);
 	}
 }
 
-void launch_thin(hipStream_t st, uint32_t npairs, CloudDesc *descs, const uint8_t *src_keep, const uint8_t *tgt_keep, float4 *spos, float4 *snrm,
-				 float4 *tpos, float4 *tnrm)
+void launch_thin(hipStream_t st, const BatchDev &b, uint32_t npairs, const uint8_t *src_keep, const uint8_t *tgt_keep)
 {
 	if (npairs)
-		hipLaunchKernelGGL(k_thin, dim3(npairs * MULLS_NC * 2), dim3(MULLS_BLOCK), 0, st, descs, src_keep, tgt_keep, spos, snrm, tpos, tnrm);
+		hipLaunchKernelGGL(k_thin, dim3(npairs * MULLS_NC * 2), dim3(MULLS_BLOCK), 0, st, b.descs, src_keep, tgt_keep, b.spos, b.snrm, b.tpos, b.tnrm);
 }
 
 void launch_copy_segs(hipStream_t st, const CopySeg *segs, uint32_t n)

@@ -37,69 +37,94 @@ inline DevLaunch dev_launch(Init init)
 	}
 	return D;
 }
-void launch_clone_src(hipStream_t st, uint32_t njobs, const Job *jobs, const CloudDesc *descs, const PairSetup *setup, const float4 *stage,
-					  float4 *tmp_pos, float4 *tmp_nrm, uint32_t *bbox, const RunParams &rp);
-void launch_crop(hipStream_t st, uint32_t npairs, CloudDesc *descs, const PairSetup *setup, const uint32_t *bbox, const float4 *stage,
-				 const float4 *tmp_pos, const float4 *tmp_nrm, float4 *spos, float4 *snrm, float4 *tpos, float4 *tnrm, uint8_t *flag,
-				 int32_t *match, float *wd, const RunParams &rp, GridDesc *grids, uint32_t nbig_segs, const Job *big_segs, uint32_t nbig_clouds,
-				 const Job *big_clouds, uint32_t *seg_cnt, uint32_t *big_box);
-// n byte ranges in one launch per MULLS_COPY_SEGS of them (device_types.h: CopySeg)
-void launch_copy_segs(hipStream_t st, const CopySeg *segs, uint32_t n);
-// CFilter::apply_motion_compensation on `n` 48-byte records in device memory (q: w x y z of Tran's rotation, t: its translation)
-void launch_motion_comp(hipStream_t st, float4 *recs, uint32_t n, const double q[4], const double t[3], float thre);
-void launch_thin(hipStream_t st, uint32_t npairs, CloudDesc *descs, const uint8_t *src_keep, const uint8_t *tgt_keep, float4 *spos, float4 *snrm,
-				 float4 *tpos, float4 *tnrm);
-// LDS tier with rp.tgt_map: crop + grid build of every target class cloud (<= MULLS_LDS_MAXPTS points) in one pass, no working copy (k_grid.hip)
-int launch_tgt_grid(hipStream_t st, uint32_t npairs, CloudDesc *descs, const PairSetup *setup, const uint32_t *bbox, const float4 *stage, const RunParams &rp,
-					GridDesc *grids, uint16_t *tmap, uint32_t *cell_start, float4 *tsorted);
-// LDS tier without the fused setup (k_crop wrote the cropped copies)
-void launch_grid_build_sort(hipStream_t st, uint32_t npairs, const CloudDesc *descs, GridDesc *grids, const RunParams &rp, const float4 *tpos, uint32_t *cell_start,
-							float4 *tsorted);
-// bitmap grids of the `nl` class clouds lclouds[] (pair * MULLS_NC + class each); tjobs: their 256-point chunks
-void launch_bm_build(hipStream_t st, uint32_t nl, const uint32_t *lclouds, uint32_t ntjobs, const Job *tjobs, const CloudDesc *descs, GridDesc *grids, const float4 *tpos,
-					 unsigned long long *bm, uint32_t *pf, uint32_t *cnt, uint32_t *cs, float4 *tsorted, uint32_t *rank);
-size_t nn_lds_bytes(uint32_t cap, uint32_t maxcells, bool dedup);
-int launch_nn_lds(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *descs, const PairState *states, const RunParams &rp, float4 *spos,
-				  float4 *snrm, const GridDesc *grids, const uint32_t *cell_start, const float4 *tsorted, uint8_t *flag, int32_t *nn_idx,
-				  float *nn_d2, unsigned long long *winner, const float4 *tnrm, int32_t *match, float *wd, const float4 *tpos, int32_t *nn_hint, float4 *mq, uint32_t cap, uint32_t maxcells,
-				  uint32_t *wl, uint32_t *wl_ctr, uint32_t parity, bool first = false);
-// a small mixed batch: the class clouds of both tiers in one launch (k_cert_mixed); returns 1 when it launched, 0 when the caller has to launch the tiers separately
-int launch_cert_mixed(hipStream_t st, uint32_t n_lds, const Job *cjobs, uint32_t n_big, const Job *bjobs, uint32_t max_wgs, uint32_t rounds, CloudDesc *descs, const PairState *states,
-					  const RunParams &rp, float4 *spos, float4 *snrm, const GridDesc *grids, const uint32_t *cell_start, const unsigned long long *bm, const uint32_t *pf,
-					  const uint32_t *cs, const float4 *tsorted, uint8_t *flag, int32_t *nn_idx, float *nn_d2, unsigned long long *winner, const float4 *tnrm, int32_t *match,
-					  float *wd, const float4 *tpos, int32_t *nn_hint, float4 *mq, uint32_t cap, uint32_t maxcells, bool first = false);
-// global-memory tier (big_tier.h): class-level (MULLS_JOB_CLASS) and chunk-level jobs; max_wgs: chunk-level jobs are shared by 2 / 4 / 8 / 16 workgroups while
-// the launch stays within this many
-void launch_cert_big(hipStream_t st, uint32_t njobs, const Job *jobs, uint32_t max_wgs, CloudDesc *descs, const PairState *states, const RunParams &rp, float4 *spos, float4 *snrm,
-					 const GridDesc *grids, const unsigned long long *bm, const uint32_t *pf, const uint32_t *cs, const float4 *tsorted, uint8_t *flag, int32_t *nn_idx,
-					 float *nn_d2, unsigned long long *winner, const float4 *tpos, const float4 *tnrm, int32_t *nn_hint, int32_t *match, float *wd, float4 *mq);
-void launch_nn(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *descs, const PairState *states, const RunParams &rp, float4 *spos,
-			   float4 *snrm, const float4 *tpos, const uint8_t *flag, int32_t *nn_idx, float *nn_d2, unsigned long long *winner);
-void launch_nn_shoot(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *descs, const PairState *states, const RunParams &rp,
-					 float4 *spos, float4 *snrm, const float4 *tpos, const uint8_t *flag, int32_t *nn_idx, float *nn_d2, unsigned long long *winner);
-void launch_filter(hipStream_t st, uint32_t njobs, const Job *jobs, CloudDesc *descs, const PairState *states, const RunParams &rp,
-				   const float4 *snrm, const float4 *tnrm, uint8_t *flag, const int32_t *nn_idx, const float *nn_d2, int32_t *match, float *wd,
-				   const unsigned long long *winner, const float4 *tpos, float4 *mq, bool big = false);
-// leaders: job indices of the trip starts, grouped by trip length (split[0..3]: see k_reduce.hip)
-void launch_accum(hipStream_t st, const uint32_t *leaders, const uint32_t split[4], const Job *jobs, const CloudDesc *descs, const PairState *states, const RunParams &rp,
-				  const float4 *spos, const float4 *mq, const uint8_t *flag, float *wd, double *partial, bool single = false, uint32_t wave_min_trips = 0);
-void launch_finish(hipStream_t st, uint32_t npairs, CloudDesc *descs, const PairState *states, const RunParams &rp, const double *partial,
-				   PairOut *out, PairOut *out_host, const uint32_t *bbox, uint32_t *ticket, volatile uint32_t *host_epoch, uint32_t epoch,
-				   uint32_t pair_base);
-void launch_push_states(hipStream_t st, const PairState *host_states, PairState *dev_states, uint32_t npairs);
 namespace mulls
 {
 struct IcpConst;
 struct StepState;
 } // namespace mulls
+// The device arrays of a batch, as the wrappers below hand them to the kernels (mulls_batch, batch.h, derives from it and owns the memory: capacities, host mirrors
+// and epochs live there).  A wrapper takes the view and, besides it, only what its call sites choose: a slice of a job table, counts, a parity, an epoch.
+struct BatchDev
+{
+	float4 *stage = nullptr;
+	float4 *tmp_pos = nullptr, *tmp_nrm = nullptr;
+	float4 *spos = nullptr, *snrm = nullptr, *tpos = nullptr, *tnrm = nullptr;
+	uint8_t *flag = nullptr;
+	int32_t *match = nullptr, *nn_idx = nullptr, *nn_hint = nullptr;
+	float4 *mq = nullptr; // per source point: position and direction of its matched target (2 records), written with match[]
+	float *wd = nullptr, *nn_d2 = nullptr;
+	unsigned long long *winner = nullptr;
+	CloudDesc *descs = nullptr;
+	PairSetup *setup = nullptr;
+	PairState *states = nullptr;	 // HBM copy of the pair states (filled by k_push_states every iteration)
+	PairState *states_pin = nullptr; // device address of the pinned host array states_h
+	PairOut *outs = nullptr;		 // HBM: filled by k_finish
+	PairOut *outs_pin = nullptr;	 // device address of the pinned host array outs_h (packed records, k_pull_outs)
+	uint32_t *bbox = nullptr;
+	Job *setup_jobs = nullptr;
+	Job *big_segs = nullptr, *big_clouds = nullptr;
+	uint32_t *seg_cnt = nullptr, *big_box = nullptr;
+	Job *jobs = nullptr;
+	double *partial = nullptr;
+	Job *tjobs = nullptr;
+	Job *cjobs = nullptr;
+	Job *bjobs = nullptr, *fjobs = nullptr, *ejobs = nullptr;
+	uint32_t *lclouds = nullptr;
+	uint32_t *bm_cs = nullptr;	 // bitmap grids: first sorted position of every occupied cell (indexed like cell_cnt)
+	uint32_t *bm_rank = nullptr; // bitmap grids: every target point's (cell counter index, arrival number in its cell), from k_bm_count to k_bm_scatter — the scatter is
+								 // pure data movement: one pass of atomics per build instead of two
+	uint32_t *ajobs = nullptr;
+	IcpOut *icp_outs = nullptr;
+	mulls::StepState *steps = nullptr; // lock-step loop with the device step: per-pair loop state
+	uint32_t *wl = nullptr;		// LDS tier: class clouds k_cert queued for k_nn_lds (one slot per class-level job)
+	uint32_t *wl_ctr = nullptr; // ... and the queue counters: per sub-batch 8 words = (queued, taken) x launch parity
+	GridDesc *grids = nullptr;
+	float4 *tsorted = nullptr;
+	uint16_t *tmap = nullptr; // LDS tier without a cropped copy of the target clouds (k_tgt_grid): rank in the cropped cloud -> staged index
+	uint32_t *cell_cnt = nullptr, *cell_start = nullptr; // bitmap grids: per-occupied-cell counters (start positions: bm_cs); LDS tier: dense cell tables
+	unsigned long long *bm = nullptr;					  // global tier: occupancy words of every grid
+	uint32_t *pf = nullptr;								  // global tier: occupied cells before each word
+	uint32_t *ticket = nullptr; // device: arrival counters of k_finish (one per sub-batch, 16 words apart)
+};
+// clone + initial guess of the `njobs` setup jobs (b.setup_jobs)
+void launch_clone_src(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t njobs);
+// nbig_segs / nbig_clouds: entries of b.big_segs / b.big_clouds (class clouds cropped segment-wise)
+void launch_crop(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs, uint32_t nbig_segs, uint32_t nbig_clouds);
+// n byte ranges in one launch per MULLS_COPY_SEGS of them (device_types.h: CopySeg)
+void launch_copy_segs(hipStream_t st, const CopySeg *segs, uint32_t n);
+// CFilter::apply_motion_compensation on `n` 48-byte records in device memory (q: w x y z of Tran's rotation, t: its translation)
+void launch_motion_comp(hipStream_t st, float4 *recs, uint32_t n, const double q[4], const double t[3], float thre);
+void launch_thin(hipStream_t st, const BatchDev &b, uint32_t npairs, const uint8_t *src_keep, const uint8_t *tgt_keep);
+// LDS tier with rp.tgt_map: crop + grid build of every target class cloud (<= MULLS_LDS_MAXPTS points) in one pass, no working copy (k_grid.hip)
+int launch_tgt_grid(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs);
+// LDS tier without the fused setup (k_crop wrote the cropped copies)
+void launch_grid_build_sort(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs);
+// bitmap grids of the `nl` class clouds b.lclouds[] (pair * MULLS_NC + class each); ntjobs: their 256-point chunks (b.tjobs)
+void launch_bm_build(hipStream_t st, const BatchDev &b, uint32_t nl, uint32_t ntjobs);
+size_t nn_lds_bytes(uint32_t cap, uint32_t maxcells, bool dedup);
+// wl, wl_ctr: the slice's part of b.wl and the sub-batch's counters in b.wl_ctr
+int launch_nn_lds(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs, uint32_t cap, uint32_t *wl, uint32_t *wl_ctr, uint32_t parity,
+				  bool first = false);
+// a small mixed batch: the class clouds of both tiers in one launch (k_cert_mixed); returns 1 when it launched, 0 when the caller has to launch the tiers separately
+int launch_cert_mixed(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *cjobs, uint32_t n_lds, const Job *bjobs, uint32_t n_big, uint32_t max_wgs, uint32_t rounds,
+					  uint32_t cap, bool first = false);
+// global-memory tier (big_tier.h): class-level (MULLS_JOB_CLASS) and chunk-level jobs; max_wgs: chunk-level jobs are shared by 2 / 4 / 8 / 16 workgroups while
+// the launch stays within this many
+void launch_cert_big(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs, uint32_t max_wgs);
+void launch_nn(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs);
+void launch_nn_shoot(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs);
+void launch_filter(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs, bool big = false);
+// b.ajobs: job indices of the trip starts, grouped by trip length (split[0..3]: see k_reduce.hip)
+void launch_accum(hipStream_t st, const BatchDev &b, const RunParams &rp, const uint32_t split[4], bool single = false, uint32_t wave_min_trips = 0);
+void launch_finish(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t pair_base, uint32_t npairs, uint32_t *ticket, volatile uint32_t *host_epoch, uint32_t epoch);
+void launch_push_states(hipStream_t st, const BatchDev &b, uint32_t pair_base, uint32_t npairs);
 // lock-step loop with the O(1) half of the iteration on the device: initial per-pair state and first PairState; k_finish followed by the step (k_step)
-void launch_step_init(hipStream_t st, uint32_t npairs, const PairSetup *setup, const mulls::IcpConst &K, mulls::StepState *steps, PairState *states);
-void launch_finish_step(hipStream_t st, uint32_t pair_base, uint32_t npairs, CloudDesc *descs, PairState *states, const RunParams &rp, const mulls::IcpConst &K, const double *partial,
-						PairOut *out, const uint32_t *bbox, mulls::StepState *steps, IcpOut *results, unsigned long long *host_word, uint32_t epoch, int brute,
-						uint32_t *ticket = nullptr, bool sum_step = false); // ticket: two zeroed device words -> finish, step and publication in one launch (small batches);
+void launch_step_init(hipStream_t st, const BatchDev &b, const mulls::IcpConst &K, uint32_t npairs);
+void launch_finish_step(hipStream_t st, const BatchDev &b, const RunParams &rp, const mulls::IcpConst &K, uint32_t pair_base, uint32_t npairs, unsigned long long *host_word, uint32_t epoch,
+						int brute, uint32_t *ticket = nullptr, bool sum_step = false); // ticket: two zeroed device words -> finish, step and publication in one launch (small batches);
 						// sum_step (large batches): one wave per pair sums and steps (k_sum_step) instead of k_finish + k_step
 void launch_transform_aos(hipStream_t st, float4 *recs, uint32_t n, const double *T12);
 // the same on `count` (<= 6) clouds in one launch, T12 (host) by value
 void launch_transform_clouds(hipStream_t st, float4 *const recs[], const uint32_t n[], int count, const double T12[12]);
-void launch_set_corr(hipStream_t st, uint32_t src_off, const int32_t *cs, const int32_t *ct, const float *cd, uint32_t n, uint8_t *flag,
-					 int32_t *match, float *wd, uint32_t tgt_off, const float4 *tpos, const float4 *tnrm, float4 *mq);
+// cs, ct, cd: the caller's correspondence list (device copies), forced into the batch's flag / match / wd / mq arrays
+void launch_set_corr(hipStream_t st, const BatchDev &b, uint32_t src_off, const int32_t *cs, const int32_t *ct, const float *cd, uint32_t n, uint32_t tgt_off);

@@ -26,21 +26,21 @@ struct Run
 	int tier = 0;
 	bool use_grid = false, dstep = false;
 };
-#define RUN_ALIASES \
-	mulls_ctx *ctx = R.ctx; \
-	mulls_batch *B = R.B; \
-	const mulls_params *P = R.P; \
-	mulls_result *results = R.results; \
-	const int n = R.n; \
-	hipStream_t st = R.st; \
-	RunParams &rp = R.rp; \
-	const mulls::IcpConst &K = R.K; \
-	EvTimer &evt = R.evt; \
-	const uint32_t lds_cap = R.lds_cap; \
-	const int tier = R.tier; \
-	const bool use_grid = R.use_grid; \
-	(void)P, (void)results, (void)n, (void)st, (void)rp, (void)K, (void)evt, (void)lds_cap, (void)tier, (void)use_grid;
-
+// an error once a loop has queued kernels leaves some in flight that still write the pinned result / epoch buffers: drain both streams before the caller
+// can refill or free them
+struct DrainOnError
+{
+	mulls_ctx *ctx;
+	bool armed = true;
+	~DrainOnError()
+	{
+		if (armed)
+		{
+			(void)hipStreamSynchronize(ctx->stream);
+			(void)hipStreamSynchronize(ctx->stream2);
+		}
+	}
+};
 
 // run parameters, job tables, tier; then the set-up launches: clone + initial guess + intersection filter (cregistration.hpp:1180-1188), keep-less
 // thinning, the target grids
@@ -129,10 +129,7 @@ int run_setup(Run &R)
 
 	// setup: clone + initial guess + intersection filter (cregistration.hpp:1180-1188), then the target grids
 	evt.begin(&ctx->prof.ms_setup);
-	launch_clone_src(st, (uint32_t)B->setup_jobs_h.size(), B->setup_jobs, B->descs, B->setup, B->stage, B->tmp_pos, B->tmp_nrm, B->bbox, rp);
-	launch_crop(st, (uint32_t)n, B->descs, B->setup, B->bbox, B->stage, B->tmp_pos, B->tmp_nrm, B->spos, B->snrm, B->tpos, B->tnrm, B->flag,
-				B->match, B->wd, rp, B->grids, (uint32_t)B->big_segs_h.size(), B->big_segs, (uint32_t)B->big_clouds_h.size(), B->big_clouds, B->seg_cnt,
-				B->big_box);
+	queue_clone_crop(st, B, rp);
 	if (P->keep_less_source_points && !rp.undistort)
 	{
 		// keep_less_source_pts (cregistration.hpp:2866-2892): needs the post-filter sizes, so this (map-to-map only) option
@@ -155,31 +152,10 @@ int run_setup(Run &R)
 			S(MULLS_ROOF, (int)pd[MULLS_ROOF].tgt_n);
 			S(MULLS_VERTEX, (int)pd[MULLS_VERTEX].tgt_n);
 		}
-		uint8_t *d_sk = nullptr, *d_tk = nullptr;
-		if (dmalloc(ctx, &d_sk, skeep.size()) != MULLS_OK || dmalloc(ctx, &d_tk, tkeep.size()) != MULLS_OK)
-			return MULLS_E_HIP;
-		hipError_t e = hipMemcpyAsync(d_sk, skeep.data(), skeep.size(), hipMemcpyHostToDevice, st);
-		if (e == hipSuccess)
-			e = hipMemcpyAsync(d_tk, tkeep.data(), tkeep.size(), hipMemcpyHostToDevice, st);
-		if (e == hipSuccess)
-		{
-			launch_thin(st, (uint32_t)n, B->descs, d_sk, d_tk, B->spos, B->snrm, B->tpos, B->tnrm);
-			e = hipStreamSynchronize(st); // the masks are freed right below
-		}
-		(void)hipFree(d_sk);
-		(void)hipFree(d_tk);
-		if (e != hipSuccess)
-		{
-			ctx->err = std::string("keep_less_source_points: ") + hipGetErrorString(e);
-			return MULLS_E_HIP;
-		}
+		if ((rc = apply_keep_masks(ctx, B, skeep, tkeep, "keep_less_source_points: ")) != MULLS_OK)
+			return rc;
 	}
-	if (fused_tgt)
-		(void)launch_tgt_grid(st, (uint32_t)n, B->descs, B->setup, B->bbox, B->stage, rp, B->grids, B->tmap, B->cell_start, B->tsorted);
-	else if (tier == 2)
-		launch_grid_build_sort(st, (uint32_t)n, B->descs, B->grids, rp, B->tpos, B->cell_start, B->tsorted);
-	launch_bm_build(st, (uint32_t)B->lclouds_h.size(), B->lclouds, (uint32_t)B->tjobs_h.size(), B->tjobs, B->descs, B->grids, B->tpos, B->bm, B->pf, B->cell_cnt, B->bm_cs,
-					B->tsorted, B->bm_rank);
+	queue_target_grids(st, B, rp, tier, fused_tgt);
 	evt.end();
 
 	R.K = icp_const(P);
@@ -216,11 +192,14 @@ Slice slice_of(const mulls_batch *B, int lo, int hi, int k)
 // families; a batch on one tier only its own), then k_filter for the clouds whose correspondences are spread over several workgroups
 int launch_search(Run &R, hipStream_t sst, const Slice &L, uint32_t *wl, uint32_t *wl_ctr, uint32_t parity, EvTimer &ev, int iter)
 {
-RUN_ALIASES
+	mulls_ctx *ctx = R.ctx;
+	const mulls_batch *B = R.B;
+	const RunParams &rp = R.rp;
+	const int tier = R.tier;
 	const Job *jobs = B->jobs + L.job_lo;
 	ev.begin(&ctx->prof.ms_nn);
 	if (tier == 0)
-		launch_nn(sst, L.job_n, jobs, B->descs, B->states, rp, B->spos, B->snrm, B->tpos, B->flag, B->nn_idx, B->nn_d2, B->winner);
+		launch_nn(sst, *B, rp, jobs, L.job_n);
 	// mixed batch, first iterations: chunk-level jobs for every cloud of the global-memory tier (MULLS_OPT_BIG_EARLY_SETS)
 	// ... and every iteration of a small one: a handful of class-level workgroups cannot search a dense map's leftovers fast enough (a 1 M-point map leaves most
 	// points uncertified for ten iterations: its second-nearest targets are millimetres behind the nearest), while k_filter costs such a batch 6 us
@@ -243,34 +222,24 @@ RUN_ALIASES
 	// goes straight to the staged search, no light pass (k_search.hip: first_goes_direct)
 	const bool first = iter == 0 && rp.lds_dedup != 0u && !rp.normal_shooting && ctx->opt[MULLS_OPT_FIRST_DIRECT] != 0.0;
 	const bool together = tier == 3 && L.cjob_n && big_n &&
-						  launch_cert_mixed(sst, L.cjob_n, B->cjobs + L.cjob_lo, big_n, big_jobs, max_wgs, mixed_rounds, B->descs, B->states, rp, B->spos, B->snrm, B->grids, B->cell_start, B->bm,
-											B->pf, B->bm_cs, B->tsorted, B->flag, B->nn_idx, B->nn_d2, B->winner, B->tnrm, B->match, B->wd, B->tpos, B->nn_hint, B->mq, lds_cap,
-											rp.grid_maxcells, first) != 0;
-	if (!together && L.cjob_n &&
-		launch_nn_lds(sst, L.cjob_n, B->cjobs + L.cjob_lo, B->descs, B->states, rp, B->spos, B->snrm, B->grids, B->cell_start, B->tsorted, B->flag, B->nn_idx, B->nn_d2, B->winner,
-					  B->tnrm, B->match, B->wd, B->tpos, B->nn_hint, B->mq, lds_cap, rp.grid_maxcells, wl, wl_ctr, parity, first) != 0)
+						  launch_cert_mixed(sst, *B, rp, B->cjobs + L.cjob_lo, L.cjob_n, big_jobs, big_n, max_wgs, mixed_rounds, R.lds_cap, first) != 0;
+	if (!together && L.cjob_n && launch_nn_lds(sst, *B, rp, B->cjobs + L.cjob_lo, L.cjob_n, R.lds_cap, wl, wl_ctr, parity, first) != 0)
 	{
 		ctx->err = "could not raise the dynamic LDS limit of k_nn_lds";
 		return MULLS_E_HIP;
 	}
-	if (together)
-		;
-	else if (early)
-		launch_cert_big(sst, L.ejob_n, B->ejobs + L.ejob_lo, max_wgs, B->descs, B->states, rp, B->spos, B->snrm, B->grids, B->bm, B->pf, B->bm_cs, B->tsorted, B->flag, B->nn_idx,
-						B->nn_d2, B->winner, B->tpos, B->tnrm, B->nn_hint, B->match, B->wd, B->mq);
-	else if (L.bjob_n)
-		launch_cert_big(sst, L.bjob_n, B->bjobs + L.bjob_lo, max_wgs, B->descs, B->states, rp, B->spos, B->snrm, B->grids, B->bm, B->pf, B->bm_cs, B->tsorted, B->flag, B->nn_idx,
-						B->nn_d2, B->winner, B->tpos, B->tnrm, B->nn_hint, B->match, B->wd, B->mq);
+	if (!together && (early || L.bjob_n))
+		launch_cert_big(sst, *B, rp, big_jobs, big_n, max_wgs);
 	if (rp.normal_shooting)
-		launch_nn_shoot(sst, L.job_n, jobs, B->descs, B->states, rp, B->spos, B->snrm, B->tpos, B->flag, B->nn_idx, B->nn_d2, B->winner);
+		launch_nn_shoot(sst, *B, rp, jobs, L.job_n);
 	ev.end();
 	ev.begin(&ctx->prof.ms_filter);
 	if (tier == 0 || (tier == 2 && !rp.lds_dedup)) // (else the LDS tier's kernels ran the rejection chain themselves)
-		launch_filter(sst, L.job_n, jobs, B->descs, B->states, rp, B->snrm, B->tnrm, B->flag, B->nn_idx, B->nn_d2, B->match, B->wd, B->winner, B->tpos, B->mq);
+		launch_filter(sst, *B, rp, jobs, L.job_n);
 	else if (early)
-		launch_filter(sst, L.ejob_n, B->ejobs + L.ejob_lo, B->descs, B->states, rp, B->snrm, B->tnrm, B->flag, B->nn_idx, B->nn_d2, B->match, B->wd, B->winner, B->tpos, B->mq, true);
+		launch_filter(sst, *B, rp, B->ejobs + L.ejob_lo, L.ejob_n, true);
 	else if (L.fjob_n)
-		launch_filter(sst, L.fjob_n, B->fjobs + L.fjob_lo, B->descs, B->states, rp, B->snrm, B->tnrm, B->flag, B->nn_idx, B->nn_d2, B->match, B->wd, B->winner, B->tpos, B->mq, true);
+		launch_filter(sst, *B, rp, B->fjobs + L.fjob_lo, L.fjob_n, true);
 	ev.end();
 	const hipError_t e = hipGetLastError();
 	if (e != hipSuccess)
@@ -284,73 +253,82 @@ RUN_ALIASES
 // results of the device-stepped loop: IcpOut records -> mulls_result, profile counters
 int results_from_device(Run &R)
 {
-RUN_ALIASES
-	const auto wall0 = R.wall0;
+	mulls_ctx *ctx = R.ctx;
+	mulls_batch *B = R.B;
+	mulls_result *results = R.results;
+	const RunParams &rp = R.rp;
+	const int n = R.n;
 
-		// (pinned: a copy into pageable memory goes through the runtime's staging buffers and holds the calling thread)
-		if (grow_pinned(ctx, &B->icp_outs_pin, &B->cap_icp_pin, (size_t)n, hipHostMallocDefault) != MULLS_OK)
-			return MULLS_E_NOMEM;
-		HIPCHK(ctx, hipMemcpyAsync(B->icp_outs_pin, B->icp_outs, sizeof(IcpOut) * (size_t)n, hipMemcpyDeviceToHost, st));
-		HIPCHK(ctx, hipStreamSynchronize(st));
-		evt.collect();
-		const double wall_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3;
-		int max_it = 0;
-		for (int p = 0; p < n; p++)
+	// (pinned: a copy into pageable memory goes through the runtime's staging buffers and holds the calling thread)
+	if (grow_pinned(ctx, &B->icp_outs_pin, &B->cap_icp_pin, (size_t)n, hipHostMallocDefault) != MULLS_OK)
+		return MULLS_E_NOMEM;
+	HIPCHK(ctx, hipMemcpyAsync(B->icp_outs_pin, B->icp_outs, sizeof(IcpOut) * (size_t)n, hipMemcpyDeviceToHost, R.st));
+	HIPCHK(ctx, hipStreamSynchronize(R.st));
+	R.evt.collect();
+	const double wall_ms = std::chrono::duration<double>(std::chrono::steady_clock::now() - R.wall0).count() * 1e3;
+	int max_it = 0;
+	for (int p = 0; p < n; p++)
+	{
+		const IcpOut &o = B->icp_outs_pin[p];
+		mulls_result &R = results[p];
+		R.code = o.code;
+		R.iters = o.iters;
+		std::memcpy(R.T, o.T, sizeof(R.T));
+		std::memcpy(R.info, o.info, sizeof(R.info));
+		R.sigma = (float)std::sqrt(o.sigma2);
+		R.confidence = o.ratio;
+		R.singular = o.singular;
+		R.ms_total = (float)(wall_ms / n);
+		for (int c = 0; c < MULLS_NC; c++)
 		{
-			const IcpOut &o = B->icp_outs_pin[p];
-			mulls_result &R = results[p];
-			R.code = o.code;
-			R.iters = o.iters;
-			std::memcpy(R.T, o.T, sizeof(R.T));
-			std::memcpy(R.info, o.info, sizeof(R.info));
-			R.sigma = (float)std::sqrt(o.sigma2);
-			R.confidence = o.ratio;
-			R.singular = o.singular;
-			R.ms_total = (float)(wall_ms / n);
-			for (int c = 0; c < MULLS_NC; c++)
-			{
-				R.ncorr[c] = o.ncorr[c];
-				R.nsrc0[c] = o.nsrc0[c];
-				R.ntgt0[c] = o.ntgt0[c];
-			}
-			R.cropped = 0;
-			std::memset(R.crop_box, 0, sizeof(R.crop_box));
-			fill_crop_box(rp, B->setup_h[p].tgt_bound, o.bbox, R);
-			R.trace_len = 0;
-			ctx->prof.nn_src_pts += o.src_pts;
-			ctx->prof.nn_tgt_unique += o.tgt_pts;
-			ctx->prof.nn_tgt_pts += o.tgt_job_pts;
-			ctx->prof.nn_corr_pts += o.corr_pts;
-			ctx->prof.nn_pair_evals += o.pair_evals;
-			max_it = std::max(max_it, o.iters);
+			R.ncorr[c] = o.ncorr[c];
+			R.nsrc0[c] = o.nsrc0[c];
+			R.ntgt0[c] = o.ntgt0[c];
 		}
-		ctx->prof.iterations = max_it;
-		if (rp.dbg_ticks) // diagnostics: k_cert's phase clocks, summed over its workgroups, in the profile's icp_*_ms slots ([5] = workgroups)
+		R.cropped = 0;
+		std::memset(R.crop_box, 0, sizeof(R.crop_box));
+		fill_crop_box(rp, B->setup_h[p].tgt_bound, o.bbox, R);
+		R.trace_len = 0;
+		ctx->prof.nn_src_pts += o.src_pts;
+		ctx->prof.nn_tgt_unique += o.tgt_pts;
+		ctx->prof.nn_tgt_pts += o.tgt_job_pts;
+		ctx->prof.nn_corr_pts += o.corr_pts;
+		ctx->prof.nn_pair_evals += o.pair_evals;
+		max_it = std::max(max_it, o.iters);
+	}
+	ctx->prof.iterations = max_it;
+	if (rp.dbg_ticks) // diagnostics: k_cert's phase clocks, summed over its workgroups, in the profile's icp_*_ms slots ([5] = workgroups)
+	{
+		unsigned long long t[16];
+		HIPCHK(ctx, hipMemcpy(t, rp.dbg_ticks, sizeof(t), hipMemcpyDeviceToHost));
+		if (rp.debug_stop == 21u) // the global-memory tier's leftover search: queries, workgroup time (summed over the workgroups)
 		{
-			unsigned long long t[16];
-			HIPCHK(ctx, hipMemcpy(t, rp.dbg_ticks, sizeof(t), hipMemcpyDeviceToHost));
-			if (rp.debug_stop == 21u) // the global-memory tier's leftover search: queries, workgroup time (summed over the workgroups)
-			{
-				ctx->prof.icp_fused_ms[0] += (double)t[13], ctx->prof.icp_fused_ms[1] += (double)t[7] * 1e-5;
-				return MULLS_OK;
-			}
-			for (int k = 0; k < 5; k++)
-				ctx->prof.icp_fused_ms[k] += (double)t[k] * 1e-5;
-			ctx->prof.icp_fused_ms[5] += (double)t[6];
-			// the k-candidate certificates of the one-pass walk, in the (otherwise unused) per-iteration slots: points the plain certificate left over, points
-			// that got the second chance, points it certified, points searched
-			ctx->prof.icp_search_ms[0] += (double)t[13], ctx->prof.icp_search_ms[1] += (double)t[14], ctx->prof.icp_search_ms[2] += (double)t[15], ctx->prof.icp_search_ms[3] += (double)t[7];
-			for (int k = 0; k < 4; k++) // ... and the heavy pass's (k_nn_lds), in the phase slots ([4] = class clouds)
-				ctx->prof.icp_phase_ms[k] += (double)t[8 + k] * 1e-5;
-			ctx->prof.icp_phase_ms[4] += (double)t[12];
+			ctx->prof.icp_fused_ms[0] += (double)t[13], ctx->prof.icp_fused_ms[1] += (double)t[7] * 1e-5;
+			return MULLS_OK;
 		}
-		return MULLS_OK;
+		for (int k = 0; k < 5; k++)
+			ctx->prof.icp_fused_ms[k] += (double)t[k] * 1e-5;
+		ctx->prof.icp_fused_ms[5] += (double)t[6];
+		// the k-candidate certificates of the one-pass walk, in the (otherwise unused) per-iteration slots: points the plain certificate left over, points
+		// that got the second chance, points it certified, points searched
+		ctx->prof.icp_search_ms[0] += (double)t[13], ctx->prof.icp_search_ms[1] += (double)t[14], ctx->prof.icp_search_ms[2] += (double)t[15], ctx->prof.icp_search_ms[3] += (double)t[7];
+		for (int k = 0; k < 4; k++) // ... and the heavy pass's (k_nn_lds), in the phase slots ([4] = class clouds)
+			ctx->prof.icp_phase_ms[k] += (double)t[8 + k] * 1e-5;
+		ctx->prof.icp_phase_ms[4] += (double)t[12];
+	}
+	return MULLS_OK;
 }
 
 // ---- lock-step loop with the O(1) half of the iteration on the device (k_reduce.hip: k_finish / k_step / k_step_publish, or k_finish_step) -----
 int run_device_step(Run &R)
 {
-RUN_ALIASES
+	mulls_ctx *ctx = R.ctx;
+	mulls_batch *B = R.B;
+	const mulls_params *P = R.P;
+	const RunParams &rp = R.rp;
+	EvTimer &evt = R.evt;
+	const int n = R.n;
+	hipStream_t st = R.st;
 	int rc;
 	// One launch set per iteration: search (+ filter), accumulation, finish + step + publication.  The host keeps two sets queued and reads one
 	// 8-byte word per set — (epoch << 32 | pairs still iterating) — to know when to stop queueing; a set queued behind the last useful one finds no
@@ -359,7 +337,7 @@ RUN_ALIASES
 	if (grow(ctx, &B->steps, &B->cap_steps, (size_t)n) != MULLS_OK || grow(ctx, &B->icp_outs, &B->cap_icp_outs, (size_t)n) != MULLS_OK)
 		return MULLS_E_HIP;
 	HIPCHK(ctx, hipMemsetAsync(B->icp_outs, 0, sizeof(IcpOut) * (size_t)n, st));
-	launch_step_init(st, (uint32_t)n, B->setup, K, B->steps, B->states);
+	launch_step_init(st, *B, R.K, (uint32_t)n);
 	// Small batches are bound by the NUMBER of launches (a kernel of a few hundred workgroups takes ~5 us whatever it does; one pair is bound by
 	// the host's ~4 us per launch): the three accumulation launches become one, finish + step + publication one (k_finish_step)
 	const bool few_launches = n <= (int)ctx->opt[MULLS_OPT_FEW_LAUNCHES_MAX_PAIRS];
@@ -413,19 +391,7 @@ RUN_ALIASES
 		HIPCHK(ctx, hipEventRecord(ctx->ev_setup, ctx->stream));
 		HIPCHK(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_setup, 0));
 	}
-	struct DrainOnError // an error from here on leaves kernels in flight that still write the pinned words
-	{
-		mulls_ctx *ctx;
-		bool armed = true;
-		~DrainOnError()
-		{
-			if (armed)
-			{
-				(void)hipStreamSynchronize(ctx->stream);
-				(void)hipStreamSynchronize(ctx->stream2);
-			}
-		}
-	} drain{ctx};
+	DrainOnError drain{ctx}; // from here on an error leaves kernels in flight
 	// wait until launch set `set` of a sub-batch has published; S.left = its pairs still iterating after the newest published set
 	auto wait_set = [&](Sub &S, int set) -> int {
 		const uint32_t want = S.epoch0 + (uint32_t)set + 1u;
@@ -491,9 +457,9 @@ RUN_ALIASES
 		// a set without a search holds only posterior-residual passes (every pair ran its last iteration in the set before): that is the
 		// residual kernel time; a set of a converging batch mixes both kinds of pairs and is charged to the accumulation
 		ev.begin(search ? &ctx->prof.ms_accum : &ctx->prof.ms_residual);
-		launch_accum(sst, B->ajobs, S.L.ajob_split, B->jobs, B->descs, B->states, rp, B->spos, B->mq, B->flag, B->wd, B->partial, few_launches, (uint32_t)ctx->opt[MULLS_OPT_ACCUM_WAVE_MIN_TRIPS]);
-		launch_finish_step(sst, (uint32_t)S.lo, (uint32_t)(S.hi - S.lo), B->descs, B->states, rp, K, B->partial, B->outs, B->bbox, B->steps, B->icp_outs, S.word_dev,
-						   ++*S.epoch_ctr, use_grid ? 0 : 1, (few_launches || n <= (int)ctx->opt[MULLS_OPT_STEP_LAUNCH_MAX_PAIRS]) ? S.ticket : nullptr, sum_step);
+		launch_accum(sst, *B, rp, S.L.ajob_split, few_launches, (uint32_t)ctx->opt[MULLS_OPT_ACCUM_WAVE_MIN_TRIPS]);
+		launch_finish_step(sst, *B, rp, R.K, (uint32_t)S.lo, (uint32_t)(S.hi - S.lo), S.word_dev, ++*S.epoch_ctr, R.use_grid ? 0 : 1,
+						   (few_launches || n <= (int)ctx->opt[MULLS_OPT_STEP_LAUNCH_MAX_PAIRS]) ? S.ticket : nullptr, sum_step);
 		ev.end();
 		{
 			const hipError_t e = hipGetLastError(); // a rejected launch (dynamic LDS size, ...) would otherwise only show as an epoch that never arrives
@@ -544,7 +510,16 @@ RUN_ALIASES
 // ---- lock-step loop stepped by the host: per-iteration traces -----------------------------------------------------------------------------------
 int run_host_step(Run &R)
 {
-RUN_ALIASES
+	mulls_ctx *ctx = R.ctx;
+	mulls_batch *B = R.B;
+	const mulls_params *P = R.P;
+	mulls_result *results = R.results;
+	const RunParams &rp = R.rp;
+	const mulls::IcpConst &K = R.K;
+	EvTimer &evt = R.evt;
+	const int n = R.n;
+	const bool use_grid = R.use_grid;
+	hipStream_t st = R.st;
 	const auto wall0 = R.wall0;
 	int rc;
 
@@ -661,7 +636,7 @@ RUN_ALIASES
 			s.pad_[0] = s.pad_[1] = s.pad_[2] = 0;
 		}
 		EvTimer &ev = S.evt;
-		launch_push_states(st, B->states_pin + S.lo, B->states + S.lo, (uint32_t)(S.hi - S.lo));
+		launch_push_states(st, *B, (uint32_t)S.lo, (uint32_t)(S.hi - S.lo));
 		if (any_active)
 		{
 			int rcs;
@@ -672,9 +647,8 @@ RUN_ALIASES
 				ctx->prof.iterations++;
 		}
 		ev.begin(any_active ? &ctx->prof.ms_accum : &ctx->prof.ms_residual);
-		launch_accum(st, B->ajobs, S.L.ajob_split, B->jobs, B->descs, B->states, rp, B->spos, B->mq, B->flag, B->wd, B->partial, false, (uint32_t)ctx->opt[MULLS_OPT_ACCUM_WAVE_MIN_TRIPS]);
-		launch_finish(st, (uint32_t)(S.hi - S.lo), B->descs, B->states, rp, B->partial, B->outs, B->outs_pin, B->bbox, S.ticket, S.word_dev, ++*S.epoch_ctr,
-					  (uint32_t)S.lo);
+		launch_accum(st, *B, rp, S.L.ajob_split, false, (uint32_t)ctx->opt[MULLS_OPT_ACCUM_WAVE_MIN_TRIPS]);
+		launch_finish(st, *B, rp, (uint32_t)S.lo, (uint32_t)(S.hi - S.lo), S.ticket, S.word_dev, ++*S.epoch_ctr);
 		ev.end();
 		S.inflight = true;
 		S.seq = ++launch_seq;
@@ -773,21 +747,7 @@ RUN_ALIASES
 		S.iter++;
 	};
 
-	// an error from here on leaves kernels in flight that still write the pinned result / epoch buffers: drain both streams
-	// before the caller can refill or free them
-	struct DrainOnError
-	{
-		mulls_ctx *ctx;
-		bool armed = true;
-		~DrainOnError()
-		{
-			if (armed)
-			{
-				(void)hipStreamSynchronize(ctx->stream);
-				(void)hipStreamSynchronize(ctx->stream2);
-			}
-		}
-	} drain{ctx};
+	DrainOnError drain{ctx}; // from here on an error leaves kernels in flight
 	for (int k = 0; k < nsub; k++)
 		if ((rc = launch(subs[k])) != MULLS_OK)
 			return rc;

@@ -172,14 +172,8 @@ extern "C"
 		ctx->opt[MULLS_OPT_LDS_DEDUP] = dedup_opt;
 		if (rc != MULLS_OK)
 			return rc;
-		launch_clone_src(st, (uint32_t)B->setup_jobs_h.size(), B->setup_jobs, B->descs, B->setup, B->stage, B->tmp_pos, B->tmp_nrm, B->bbox, *rp);
-		launch_crop(st, 1, B->descs, B->setup, B->bbox, B->stage, B->tmp_pos, B->tmp_nrm, B->spos, B->snrm, B->tpos, B->tnrm, B->flag, B->match,
-					B->wd, *rp, B->grids, (uint32_t)B->big_segs_h.size(), B->big_segs, (uint32_t)B->big_clouds_h.size(), B->big_clouds, B->seg_cnt,
-					B->big_box);
-		if (tier == 2)
-			launch_grid_build_sort(st, 1, B->descs, B->grids, *rp, B->tpos, B->cell_start, B->tsorted);
-		launch_bm_build(st, (uint32_t)B->lclouds_h.size(), B->lclouds, (uint32_t)B->tjobs_h.size(), B->tjobs, B->descs, B->grids, B->tpos, B->bm, B->pf, B->cell_cnt, B->bm_cs,
-						B->tsorted, B->bm_rank);
+		queue_clone_crop(st, B, *rp);
+		queue_target_grids(st, B, *rp, tier, false);
 		return MULLS_OK;
 	}
 	void identity_state(PairState *s, int iter)
@@ -212,22 +206,10 @@ extern "C"
 				B->states_h[0].thr[c] = dis_thre;
 			hipStream_t st = ctx->stream;
 			hipError_t e = hipSuccess;
-			launch_push_states(st, B->states_pin, B->states, 1);
+			launch_push_states(st, *B, 0, 1);
 			uint32_t lds_cap = 0;
 			const int tier = choose_tier(ctx, B, rp.used, &lds_cap);
-			if (tier == 2)
-				launch_nn_lds(st, (uint32_t)B->cjobs_h.size(), B->cjobs, B->descs, B->states, rp, B->spos, B->snrm, B->grids, B->cell_start, B->tsorted, B->flag,
-							  B->nn_idx, B->nn_d2, B->winner, B->tnrm, B->match, B->wd, B->tpos, B->nn_hint, B->mq, lds_cap, rp.grid_maxcells, B->wl, B->wl_ctr, 0u);
-			else if (tier == 1)
-				launch_cert_big(st, (uint32_t)B->bjobs_h.size(), B->bjobs, 2048u, B->descs, B->states, rp, B->spos, B->snrm, B->grids, B->bm, B->pf, B->bm_cs, B->tsorted, B->flag,
-								B->nn_idx, B->nn_d2, B->winner, B->tpos, B->tnrm, B->nn_hint, B->match, B->wd, B->mq);
-			else if (tier < 0)
-				rc = MULLS_E_INVALID;
-			else
-				launch_nn(st, B->njobs, B->jobs, B->descs, B->states, rp, B->spos, B->snrm, B->tpos, B->flag, B->nn_idx, B->nn_d2, B->winner);
-			if (!rp.lds_dedup)
-				launch_filter(st, B->njobs, B->jobs, B->descs, B->states, rp, B->snrm, B->tnrm, B->flag, B->nn_idx, B->nn_d2, B->match, B->wd,
-						  B->winner, B->tpos, B->mq);
+			rc = tier < 0 ? MULLS_E_INVALID : queue_tier_search(ctx, B, rp, tier, lds_cap, 0u);
 			const uint32_t off = B->descs_h[cls].src_off;
 			if (e == hipSuccess)
 				e = hipMemcpyAsync(match, B->nn_idx + off, sizeof(int32_t) * src->n, hipMemcpyDeviceToHost, st);
@@ -298,16 +280,16 @@ extern "C"
 			if (e == hipSuccess && corr_d2)
 				e = hipMemcpyAsync(dcd, corr_d2, sizeof(float) * ncorr, hipMemcpyHostToDevice, st);
 			identity_state(&B->states_h[0], iter_num);
-			launch_push_states(ctx->stream, B->states_pin, B->states, 1);
+			launch_push_states(ctx->stream, *B, 0, 1);
 			const uint32_t off = B->descs_h[cls].src_off;
 			if (e == hipSuccess)
 			{
 				// clear every flag to "alive, not a correspondence", then switch the requested ones on
 				e = hipMemsetAsync(B->flag + off, MULLS_F_ALIVE, src->n, st);
-				launch_set_corr(st, off, dcs, dct, corr_d2 ? dcd : nullptr, ncorr, B->flag, B->match, B->wd, B->descs_h[cls].tgt_off, B->tpos, B->tnrm, B->mq);
+				launch_set_corr(st, *B, off, dcs, dct, corr_d2 ? dcd : nullptr, ncorr, B->descs_h[cls].tgt_off);
 				for (int k = 0; k < B->nsub; k++)
-				launch_accum(st, B->ajobs, B->ajob_split[k], B->jobs, B->descs, B->states, rp, B->spos, B->mq, B->flag, B->wd, B->partial);
-				launch_finish(st, 1, B->descs, B->states, rp, B->partial, B->outs, B->outs_pin, B->bbox, B->ticket, B->epoch_dev, ++B->epoch, 0);
+					launch_accum(st, *B, rp, B->ajob_split[k]);
+				launch_finish(st, *B, rp, 0, 1, B->ticket, B->epoch_dev, ++B->epoch);
 			}
 			std::vector<float> wall(src->n);
 			if (e == hipSuccess)

@@ -48,10 +48,7 @@ extern "C"
 		rc = prepare_run(ctx, B, &Pj, rp, &lds_cap, &tier);
 		if (rc != MULLS_OK)
 			return rc;
-		launch_clone_src(st, (uint32_t)B->setup_jobs_h.size(), B->setup_jobs, B->descs, B->setup, B->stage, B->tmp_pos, B->tmp_nrm, B->bbox, rp);
-		launch_crop(st, (uint32_t)n, B->descs, B->setup, B->bbox, B->stage, B->tmp_pos, B->tmp_nrm, B->spos, B->snrm, B->tpos, B->tnrm, B->flag,
-					B->match, B->wd, rp, B->grids, (uint32_t)B->big_segs_h.size(), B->big_segs, (uint32_t)B->big_clouds_h.size(), B->big_clouds, B->seg_cnt,
-					B->big_box);
+		queue_clone_crop(st, B, rp);
 		if (P->keep_less_source_points)
 		{
 			// random_downsample_pcl(pc_ground_sc, tc.size() / down_rate), down_rate = 3 (:1462, :1485): no filter ran, sizes are known
@@ -61,29 +58,10 @@ extern "C"
 				const CloudDesc &dg = B->descs_h[(size_t)p * MULLS_NC + MULLS_GROUND];
 				thin_mask(skeep.data() + dg.src_off, dg.src_n0, (int)(dg.tgt_n0 / 3), P->rng_seed, 1 * 6 + MULLS_GROUND);
 			}
-			uint8_t *d_sk = nullptr, *d_tk = nullptr;
-			if (dmalloc(ctx, &d_sk, skeep.size()) != MULLS_OK || dmalloc(ctx, &d_tk, tkeep.size()) != MULLS_OK)
-				return MULLS_E_HIP;
-			hipError_t e = hipMemcpyAsync(d_sk, skeep.data(), skeep.size(), hipMemcpyHostToDevice, st);
-			if (e == hipSuccess)
-				e = hipMemcpyAsync(d_tk, tkeep.data(), tkeep.size(), hipMemcpyHostToDevice, st);
-			if (e == hipSuccess)
-			{
-				launch_thin(st, (uint32_t)n, B->descs, d_sk, d_tk, B->spos, B->snrm, B->tpos, B->tnrm);
-				e = hipStreamSynchronize(st);
-			}
-			(void)hipFree(d_sk);
-			(void)hipFree(d_tk);
-			if (e != hipSuccess)
-			{
-				ctx->err = std::string("3dof keep_less_source_points: ") + hipGetErrorString(e);
-				return MULLS_E_HIP;
-			}
+			if ((rc = apply_keep_masks(ctx, B, skeep, tkeep, "3dof keep_less_source_points: ")) != MULLS_OK)
+				return rc;
 		}
-		if (tier == 2)
-			launch_grid_build_sort(st, (uint32_t)n, B->descs, B->grids, rp, B->tpos, B->cell_start, B->tsorted);
-		launch_bm_build(st, (uint32_t)B->lclouds_h.size(), B->lclouds, (uint32_t)B->tjobs_h.size(), B->tjobs, B->descs, B->grids, B->tpos, B->bm, B->pf, B->cell_cnt, B->bm_cs,
-						B->tsorted, B->bm_rank);
+		queue_target_grids(st, B, rp, tier, false);
 
 		struct H3
 		{
@@ -124,24 +102,12 @@ extern "C"
 				s.iter = it;
 				s.active = H[p].active ? 1 : 0;
 			}
-			launch_push_states(st, B->states_pin, B->states, (uint32_t)n);
-			if (tier == 2)
-			{
-				if (launch_nn_lds(st, (uint32_t)B->cjobs_h.size(), B->cjobs, B->descs, B->states, rp, B->spos, B->snrm, B->grids, B->cell_start, B->tsorted, B->flag,
-								  B->nn_idx, B->nn_d2, B->winner, B->tnrm, B->match, B->wd, B->tpos, B->nn_hint, B->mq, lds_cap, rp.grid_maxcells, B->wl, B->wl_ctr,
-							  (uint32_t)it) != 0)
-					return MULLS_E_HIP;
-			}
-			else if (tier == 1)
-				launch_cert_big(st, (uint32_t)B->bjobs_h.size(), B->bjobs, 2048u, B->descs, B->states, rp, B->spos, B->snrm, B->grids, B->bm, B->pf, B->bm_cs, B->tsorted, B->flag,
-								B->nn_idx, B->nn_d2, B->winner, B->tpos, B->tnrm, B->nn_hint, B->match, B->wd, B->mq);
-			else
-				launch_nn(st, B->njobs, B->jobs, B->descs, B->states, rp, B->spos, B->snrm, B->tpos, B->flag, B->nn_idx, B->nn_d2, B->winner);
-			if (!rp.lds_dedup)
-				launch_filter(st, B->njobs, B->jobs, B->descs, B->states, rp, B->snrm, B->tnrm, B->flag, B->nn_idx, B->nn_d2, B->match, B->wd, B->winner, B->tpos, B->mq);
+			launch_push_states(st, *B, 0, (uint32_t)n);
+			if ((rc = queue_tier_search(ctx, B, rp, tier, lds_cap, (uint32_t)it)) != MULLS_OK)
+				return rc;
 			for (int k = 0; k < B->nsub; k++)
-				launch_accum(st, B->ajobs, B->ajob_split[k], B->jobs, B->descs, B->states, rp, B->spos, B->mq, B->flag, B->wd, B->partial);
-			launch_finish(st, (uint32_t)n, B->descs, B->states, rp, B->partial, B->outs, B->outs_pin, B->bbox, B->ticket, B->epoch_dev, ++B->epoch, 0);
+				launch_accum(st, *B, rp, B->ajob_split[k]);
+			launch_finish(st, *B, rp, 0, (uint32_t)n, B->ticket, B->epoch_dev, ++B->epoch);
 			if (wait_epoch(ctx, B) != MULLS_OK)
 				return MULLS_E_HIP;
 			for (int p = 0; p < n; p++)
