@@ -6,7 +6,7 @@
 // called with the positional arguments of test/mulls_slam.cpp:642-648 / test/mulls_reg.cpp:194-195, and their
 // constraint_t outputs are printed side by side as JSON for tests/test_gpu_adapter.py to compare.
 //
-// usage: adapter_check <dump file written by the test> <kitti|reg|variants|map>
+// usage: adapter_check <dump file written by the test> <kitti|reg|variants|map|features|motion|ncc|ncc_ref>
 #include <chrono>
 #include <cstdio>
 
@@ -26,6 +26,18 @@ typedef pcl::search::KdTree<Point_T>::Ptr pcTreePtr;
 typedef pcl::search::KdTree<Point_T> pcTree;
 
 #include "util_typedefs.inc"
+
+// what find_feature_correspondence_ncc's lines use of Eigen::VectorXf: a sized vector of floats with operator()
+namespace Eigen
+{
+struct VectorXf
+{
+	std::vector<float> v;
+	explicit VectorXf(int n) : v(n) {}
+	float &operator()(int i) { return v[i]; }
+	const float &operator()(int i) const { return v[i]; }
+};
+} // namespace Eigen
 
 namespace lo
 {
@@ -61,6 +73,7 @@ class CRegistration : public CloudUtility<PointT>
 {
   public:
 #include "creg_body.inc"
+#include "creg_ncc.inc"
 };
 #include "map_decl.inc"
 #include "map_body.inc"
@@ -211,6 +224,55 @@ int main(int argc, char **argv)
 		}
 		return 0;
 	}
+	if (std::string(argv[2]) == "ncc" || std::string(argv[2]) == "ncc_ref")
+	{
+		// find_feature_correspondence_ncc (test/mulls_reg.cpp:173-174): the reference member vs the bridge function of the same name on the same key-point
+		// clouds (slot 0 of each side of the dump), same arguments.  ncc_ref: the reference member alone, nothing of the device touched.  The two output
+		// clouds of every call are also written to <dump file>.<who>.<mode> (target_corrs' records, then source_corrs'), for a test to look the points up.
+		const bool with_hip = std::string(argv[2]) == "ncc";
+		const pcTPtr tgt = con_ref.block1->pc_ground, src = con_ref.block2->pc_ground_down;
+		pcTPtr few(new pcT());
+		few->points.assign(tgt->points.begin(), tgt->points.begin() + std::min<size_t>(9, tgt->points.size()));
+		struct Mode
+		{
+			const char *name;
+			bool fixed;
+			int corr_num;
+			bool recip, prefill, few;
+		};
+		static const Mode modes[6] = {{"recip", false, 2000, true, false, false},	  {"nn", false, 2000, false, false, false},
+									  {"fixed2000", true, 2000, false, false, false}, {"fixed300", true, 300, false, false, false},
+									  {"recip_prefilled", false, 2000, true, true, false}, {"few", false, 2000, true, true, true}};
+		lo::CRegistration<Point_T> cr;
+		for (const Mode &m : modes)
+			for (int w = 0; w < (with_hip ? 2 : 1); w++)
+			{
+				pcTPtr t_in = m.few ? few : tgt, s_in = src, tc(new pcT()), sc(new pcT());
+				if (m.prefill) // three points that are there already: results are appended behind them (sources in target_corrs: which is which shows)
+					for (size_t k = 0; k < 3 && k < src->points.size() && k < tgt->points.size(); k++)
+						tc->points.push_back(src->points[k]), sc->points.push_back(tgt->points[k]);
+				const bool ok = w == 0 ? cr.find_feature_correspondence_ncc(t_in, s_in, tc, sc, m.fixed, m.corr_num, m.recip)
+									   : lo::hip::find_feature_correspondence_ncc<Point_T>(t_in, s_in, tc, sc, m.fixed, m.corr_num, m.recip);
+				const char *who = w == 0 ? "reference" : "hip";
+				unsigned long long h[2];
+				FILE *o = fopen((std::string(argv[1]) + "." + who + "." + m.name).c_str(), "wb");
+				for (int c = 0; c < 2; c++)
+				{
+					const pcT &cl = c == 0 ? *tc : *sc;
+					const unsigned char *b = reinterpret_cast<const unsigned char *>(cl.points.data());
+					h[c] = 1469598103934665603ull; // FNV-1a over every byte in order
+					for (size_t i = 0; i < cl.points.size() * sizeof(Point_T); i++)
+						h[c] = (h[c] ^ b[i]) * 1099511628211ull;
+					if (o && !cl.points.empty())
+						fwrite(b, sizeof(Point_T), cl.points.size(), o);
+				}
+				if (o)
+					fclose(o);
+				printf("{\"who\": \"%s\", \"mode\": \"%s\", \"ok\": %s, \"n_target\": %zu, \"n_source\": %zu, \"hash_target\": \"%016llx\", \"hash_source\": \"%016llx\"}\n",
+					   who, m.name, ok ? "true" : "false", tc->points.size(), sc->points.size(), h[0], h[1]);
+			}
+		return 0;
+	}
 	if (std::string(argv[2]) == "motion")
 	{
 		// test/mulls_slam.cpp:703-712: the frame's clouds (block2 here: the *_down clouds and the key points) moved by their time-stamp fraction of the
@@ -316,6 +378,11 @@ int main(int argc, char **argv)
 		return 0;
 	}
 	const bool kitti = std::string(argv[2]) == "kitti";
+	if (!kitti && std::string(argv[2]) != "reg")
+	{
+		fprintf(stderr, "adapter_check: unknown mode '%s' (modes: kitti reg variants map features motion ncc ncc_ref)\n", argv[2]);
+		return 2;
+	}
 	lo::CRegistration<Point_T> cReg;
 	int code[2];
 	for (int w = 0; w < 2; w++)

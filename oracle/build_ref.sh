@@ -16,7 +16,7 @@ if [ ! -f "$INC/cregistration.hpp" ]; then
 	echo "build_ref: $REF not present, skipping"
 	exit 0
 fi
-TMP="$(mktemp -d /tmp/mulls_ref.XXXXXX)"
+TMP="$(mktemp -d "${TMPDIR:-/tmp}/mulls_ref.XXXXXX")" # (where /tmp is not writable the caller's TMPDIR is)
 trap 'rm -rf "$TMP"' EXIT
 
 # extract <file> <first> <last> <expected substring of first line> <out>
@@ -79,6 +79,8 @@ extract cregistration.hpp 2518 2722 "bool get_multi_metrics_lls_residual" creg_b
 extract cregistration.hpp 2740 2764 "bool construct_trans_a" creg_body.inc
 extract cregistration.hpp 2795 2836 "bool get_quat_euler_jacobi" creg_body.inc
 extract cregistration.hpp 2866 2922 "bool keep_less_source_pts" creg_body.inc
+# key-point descriptor matching, an include of its own: adapter_check.cpp alone has the Eigen::VectorXf stand-in its lines need
+extract cregistration.hpp 409 601 "bool find_feature_correspondence_ncc" creg_ncc.inc
 # local map manager: class declaration, update_local_map, dynamic removal, PCA refresh of the linear features
 extract "$REF/include/pgo/map_manager.h" 19 52 "class MapManager" map_decl.inc
 extract "$REF/src/map_manager.cpp" 18 140 "bool MapManager::update_local_map" map_body.inc

@@ -1,6 +1,8 @@
-"""Regenerates tests/golden/ncc_demo.npz: what the reference's own find_feature_correspondence_ncc lines return on the key points of its demo scans.
+"""Regenerates tests/golden/ncc_demo.npz and tests/golden/ncc_edges.npz: what the reference's own find_feature_correspondence_ncc lines return on the key
+points of its demo scans, and on small synthetic key-point sets at the edges of the descriptor arithmetic.
 
-    python tests/golden/make_ncc_golden.py      (needs the reference tree and oracle/_ref/, i.e. __graft_entry__.build() run where the tree exists)
+    python tests/golden/make_ncc_golden.py            (needs the reference tree and oracle/_ref/, i.e. __graft_entry__.build() run where the tree exists)
+    python tests/golden/make_ncc_golden.py --edges    (ncc_edges.npz only: needs the reference tree alone)
 
 The two demo scans come out of tests/golden/demo_pair.npz (scan_0, scan_15); the reference's extract_semantic_pts (oracle/pyref.py) with
 make_demo_pair_golden.extract_params()'s values (ncc_restated.demo_extract_params) leaves their key points (pc_vertex, MULLS_EX_VERTEX: 2840 and 2767 records).  Lines 409-601 of the
@@ -12,6 +14,11 @@ Fixture contents: kpts_0, kpts_15 ((n, 48) uint8 records); cases (names); per ca
 reciprocal_on, n_target or -1, constant_target_intensity), <name>_ok, <name>_pairs ((n, 2) int32: target, source index in push_back order), and for the
 fixed-number cases <name>_tied = 1 when the sorted prefix of corr_num + 1 distances holds two equal neighbours (the order upstream's unstable sort leaves
 among them is not defined: such a case may be compared as a set up to the tied entries only).
+
+ncc_edges.npz (edge_sets() below): sets (names); per set <set>_t, <set>_s ((n, 48) uint8 records, at most 700, unique through an index in the x field, the
+bytes the descriptor does not read zero); cases (names); per case <name>_args = (index of its set, fixed_num_corr, corr_num, reciprocal_on), <name>_ok,
+<name>_pairs, and <name>_tied for the fixed-number cases.  Fixed-number cases exist only for the sets without a NaN distance (a NaN under upstream's std::sort
+is undefined behaviour); one whose sorted prefix holds equal neighbours is kept only if the stable order of tests/ncc_restated.py reproduces it exactly.
 """
 import ctypes as C
 import os
@@ -25,8 +32,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from mulls_amd import abi  # noqa: E402
-from oracle import pyref  # noqa: E402
 import ncc_restated  # noqa: E402
 
 REF_HEADER = "/root/reference/include/common/cregistration.hpp"
@@ -111,7 +116,98 @@ def tied_prefix(traw, sraw, corr_num):
     return int((np.diff(s) == 0).any())
 
 
+def compact(raw):
+    """the five live floats kept, everything else zero, the record's index in its x field: unique records that compress well"""
+    f = np.ascontiguousarray(raw).view(np.float32).reshape(len(raw), 12)
+    out = np.zeros_like(f)
+    out[:, [3, 4, 5, 7, 8]] = f[:, [3, 4, 5, 7, 8]]
+    out[:, 0] = np.arange(len(f), dtype=np.float32)
+    return out.view(np.uint8).reshape(len(raw), 48)
+
+
+def edge_sets():
+    """-> [(name, target, source, fixed-number corr_nums or ())]: the sets of ncc_edges.npz"""
+    kp = lambda seed, n, family="plain": compact(ncc_restated.random_kpts(seed, n, family))
+    f32 = lambda raw: raw.view(np.float32).reshape(len(raw), 12)  # a view: writes go to the records
+    sets = [("bigcodes", kp(701, 600, "bigcodes"), kp(702, 500, "bigcodes"), (300, 2000)), ("quantised", kp(703, 600, "quantised"), kp(704, 500, "quantised"), ())]
+    for tag, at in (("nan_first", (0,)), ("nan_middle", (150,)), ("nan_last", (299,)), ("nan_two", (37, 211))):
+        t = kp(710 + len(sets), 300)
+        f32(t)[list(at), 8] = np.nan
+        sets.append((tag, t, kp(720 + len(sets), 200), ()))
+    t = kp(731, 300)
+    f32(t)[:, 8] = -1.0 - f32(t)[:, 8]  # every target intensity negative: intensity_max stays 0
+    sets.append(("negative", t, kp(732, 200), (300, 2000)))
+    t = t.copy()
+    f32(t)[0, 8] = np.nan  # ... and behind a NaN no clamp to 0 either: intensity_max is the largest of them, below 0
+    sets.append(("nan_negative", t, kp(732, 200), ()))
+    s = kp(734, 200)
+    f32(s)[::3, 8] += 300.0  # source intensities above and below the target's range
+    f32(s)[1::3, 8] -= 300.0
+    sets.append(("outside", kp(733, 300), s, (300, 2000)))
+    s = kp(736, 40)
+    f32(s)[::4, 3] = np.inf  # source heights of +inf (the target has none: no inf - inf)
+    sets.append(("inf_height", kp(735, 50), s, (300, 1700)))  # 50 x 30 finite distances: 1700 reaches into the infinite ones
+    # one infinite distance, no two equal: heights so far apart that every entry is its own float, and d(5, 7) = |3e38 + 3e38| overflows.  The sorted table
+    # is then the same under any sort, +inf its last entry, and corr_num = 144 takes it
+    t, s = kp(741, 12), kp(742, 12)
+    f32(t)[:, 3] = np.arange(1, 13, dtype=np.float32) * np.float32(1e32)
+    f32(s)[:, 3] = np.arange(1, 13, dtype=np.float32) * np.float32(1e35)
+    f32(t)[5, 3], f32(s)[7, 3] = 1e37, -1e37
+    sets.append(("inf_single", t, s, (143, 144)))
+    s = kp(738, 200)
+    f32(s)[5::7, 7] = np.nan  # source curvature NaN: whole columns of NaN distances
+    sets.append(("nan_source", kp(737, 300), s, ()))
+    return sets
+
+
+def tied(traw, sraw, corr_num):
+    """tied_prefix() for tables with infinite entries (inf - inf is no zero)"""
+    imin, imax = ncc_restated.intensity_range(ncc_restated.fields(traw)["inten"])
+    dt = ncc_restated.table(ncc_restated.descriptors(traw, imin, imax), ncc_restated.descriptors(sraw, imin, imax)).reshape(-1)
+    assert not np.isnan(dt).any(), "a fixed-number case on a table with NaN distances"
+    s = np.sort(dt)[: corr_num + 1]
+    return int((s[1:] == s[:-1]).any())
+
+
+def edges(L):
+    out, set_names, names = {}, [], []
+    for k, (sname, t, s, nums) in enumerate(edge_sets()):
+        assert len(t) <= 700 and len(s) <= 700 and len({r.tobytes() for r in t}) == len(t) and len({r.tobytes() for r in s}) == len(s)
+        out[sname + "_t"], out[sname + "_s"] = t, s
+        set_names.append(sname)
+        for tag, fixed, cn, recip in [("recip", 0, 2000, 1), ("nn", 0, 2000, 0)] + [("fixed%d" % cn, 1, cn, 0) for cn in nums]:
+            name = "%s_%s" % (sname, tag)
+            ok, pairs = run_lines(L, t, s, fixed, cn, recip)
+            note = ""
+            if fixed:
+                flag = tied(t, s, cn)
+                if flag and not np.array_equal(ncc_restated.restate(t, s, fixed, cn, recip)[1], pairs):
+                    print("%-24s tied prefix, and upstream's sort left another order than the stable one: not kept" % name)
+                    continue
+                out[name + "_tied"] = np.array(flag, np.int32)
+                note = ", tied prefix" if flag else ""
+            out[name + "_args"] = np.array([k, fixed, cn, recip], np.int32)
+            out[name + "_ok"] = np.array(int(ok), np.int32)
+            out[name + "_pairs"] = pairs
+            names.append(name)
+            print("%-24s ok %d, %d pairs%s" % (name, ok, len(pairs), note))
+    out["sets"], out["cases"] = np.array(set_names), np.array(names)
+    path = os.path.join(HERE, "ncc_edges.npz")
+    np.savez_compressed(path, **out)
+    print("wrote %s (%d bytes)" % (path, os.path.getsize(path)))
+    assert os.path.getsize(path) <= os.path.getsize(os.path.join(HERE, "ncc_demo.npz"))
+
+
 def main():
+    if "--edges" in sys.argv:
+        with tempfile.TemporaryDirectory() as tmp:
+            L = build_lines(tmp)
+            L.ncc_lines.restype = C.c_int
+            edges(L)
+        return
+    from mulls_amd import abi
+    from oracle import pyref
+
     Z = np.load(os.path.join(HERE, "demo_pair.npz"))
     X = ncc_restated.demo_extract_params()
     V = {}
@@ -147,6 +243,7 @@ def main():
                 flagged += int(out[name + "_tied"])
             names.append(name)
             print("%-20s ok %d, %d pairs%s" % (name, ok, len(pairs), ", tied prefix" if fixed and out[name + "_tied"] else ""))
+        edges(L)
     assert flagged <= 2, "more than 2 of the 4 fixed-number cases have equal neighbours in their sorted prefix: choose other corr_num values"
     out["cases"] = np.array(names)
     path = os.path.join(HERE, "ncc_demo.npz")

@@ -152,3 +152,45 @@ def test_adapter_motion_compensation_matches_reference_members(pairs_small):
     assert d.max() <= 1 and (d != 0).sum() <= max(1, len(a) // 10000)
     moved = np.array(ref["xyz"], np.uint32).view(np.float32).reshape(-1, 3)[: ref["sizes"][0]]
     assert np.abs(moved - np.stack([src[0]["x"], src[0]["y"], src[0]["z"]], 1)).max() > 0.5  # the ground cloud really moved
+
+
+def _has_ncc_mode():
+    from test_ncc import adapter_check_has
+
+    return adapter_check_has("ncc")
+
+
+@pytest.mark.skipif(not _has_ncc_mode(), reason="oracle/_ref/adapter_check was left by an older recipe: no ncc mode (build() rebuilds it where the reference tree is)")
+def test_adapter_ncc_matches_reference_member():
+    """lo::hip::find_feature_correspondence_ncc vs the reference member on the demo scans' key points (tests/golden/ncc_demo.npz), both directions, the modes
+    (false, 2000, true), (false, 2000, false), (true, 2000, false), (true, 300, false), one run appended behind three points that were there and one with 9
+    target points (false, the clouds left alone): the bool, both sizes and an order-sensitive hash of each output cloud's bytes, all equal."""
+    from test_ncc import FIXTURE, pairs_by_bytes, write_adapter_dump
+
+    Z = np.load(FIXTURE)
+    modes = ["recip", "nn", "fixed2000", "fixed300", "recip_prefilled", "few"]
+    for a, b in ((0, 15), (15, 0)):
+        t, s = Z["kpts_%d" % a], Z["kpts_%d" % b]
+        with tempfile.TemporaryDirectory() as d:
+            path = os.path.join(d, "kpts.bin")
+            write_adapter_dump(path, t, s)
+            out = subprocess.check_output([BIN, path, "ncc"], timeout=300).decode().strip().split("\n")
+            rows = [json.loads(l) for l in out]
+            assert [(r["who"], r["mode"]) for r in rows] == [(w, m) for m in modes for w in ("reference", "hip")]
+            hip_clouds = {m: np.fromfile(path + ".hip." + m, np.uint8).reshape(2, -1, 48) for m in modes}
+        rows = {(r["who"], r["mode"]): r for r in rows}
+        for m in modes:
+            ref, hip = rows["reference", m], rows["hip", m]
+            for key in ("ok", "n_target", "n_source", "hash_target", "hash_source"):
+                assert ref[key] == hip[key], (a, b, m, key, ref[key], hip[key])
+            assert ref["ok"] is (m != "few") and ref["n_target"] == ref["n_source"]
+        for m, case in (("recip", "recip"), ("nn", "nn"), ("fixed2000", "fixed2000"), ("fixed300", "fixed300")):
+            want = Z["%s_%d_%d_pairs" % (case, a, b)]  # ... and they are the fixture's pairs, in its order
+            assert rows["hip", m]["n_target"] == len(want)
+            assert np.array_equal(pairs_by_bytes(t, s, hip_clouds[m][0], hip_clouds[m][1]), want), (a, b, m)
+        assert rows["hip", "recip_prefilled"]["n_target"] == rows["hip", "recip"]["n_target"] + 3
+        assert np.array_equal(hip_clouds["recip_prefilled"][0, :3], s[:3]) and np.array_equal(hip_clouds["recip_prefilled"][1, :3], t[:3])
+        assert np.array_equal(hip_clouds["recip_prefilled"][:, 3:], hip_clouds["recip"])
+        assert rows["hip", "few"]["n_target"] == 3 and np.array_equal(hip_clouds["few"], hip_clouds["recip_prefilled"][:, :3])
+        if (a, b) == (0, 15):
+            assert rows["hip", "recip"]["n_target"] == 517 and rows["hip", "fixed2000"]["n_target"] == 1543
