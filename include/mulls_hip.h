@@ -587,7 +587,7 @@ int mulls_voxel_downsample(mulls_ctx *ctx, const void *pts, uint32_t n, uint32_t
  * The correspondence stage of the reference's global (coarse) registration (test/mulls_reg.cpp:170-179, test/mulls_slam.cpp:532-540): the key points of two
  * scans (pc_vertex, MULLS_EX_VERTEX) are matched by the L1 distance of their 11-entry "neighbourhood category context" descriptors — the two packed codes
  * encode_stable_points left in normal[0] / normal[1], the intensity normalised by the TARGET's range, normal[3] (curvature) and data[3] (height above
- * ground).  The solver that consumes the pairs (TEASER++ / PCL RANSAC) is not part of this library.
+ * ground).  mulls_coarse_reg_ransac(_indexed) below is the solver that consumes the pairs; TEASER++ is not part of this library.
  *   not fixed_num_corr: every target key point i with the first source key point j* at the strictly smallest distance (a row without any distance below
  *     FLT_MAX yields j* = 0), in ascending i; with reciprocal_on only while no other target is strictly closer to j*.
  *   fixed_num_corr: the corr_num smallest of the Nt * Ns distances in ascending order, a pair being skipped once its target or its source point has been
@@ -609,6 +609,68 @@ void mulls_ncc_default_params(mulls_ncc_params *p);
  * clouds of 48-byte records (mulls_block_cloud(..., MULLS_EX_VERTEX, ...), mulls_map_cloud). */
 int mulls_ncc_correspond(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const mulls_ncc_params *params, int32_t *tgt_idx,
 						 int32_t *src_idx, uint32_t cap, uint32_t *n_corr);
+
+/* ---- RANSAC coarse registration: CRegistration<PointT>::coarse_reg_ransac (include/common/cregistration.hpp:605-661) ----
+ * The solver that turns mulls_ncc_correspond's pairs into the initial guess of mulls_icp.  Upstream's body is one call of PCL's
+ * CorrespondenceRejectorSampleConsensus (RANSAC over SampleConsensusModelRegistration, then refineModel).  PCL is not available where this library is
+ * built and tested, so nothing below was checked against it: the lines marked [PCL] restate PCL 1.8 - 1.10 from memory
+ * (correspondence_rejection_sample_consensus.hpp, ransac.hpp, sac_model.h, sac_model_registration.h, sac.h), the lines marked [LIB] are defined by this
+ * library where PCL's result depends on Eigen's decompositions, which cannot be pinned.  tests/ransac_restated.py restates all of it independently in
+ * numpy, bit for bit.  DESIGN.md section 7 has the same list with its reasons.  Correspondence i pairs point i of each cloud (:621-627).
+ *   draws      [PCL] std::mt19937(12345), rnd() = eng() >> 1; a sample is three steps of a Fisher-Yates shuffle, swap(shuffled[i], shuffled[i + rnd() % (N - i)]),
+ *              i = 0, 1, 2, on an index array that is carried from draw to draw; up to 1000 draws until isSampleGood; none found: the loop ends.
+ *   sample     [PCL] good when the three pairwise squared distances between the SOURCE sample points exceed sample_dist_thresh.  The distance runs over the
+ *              point's four-float map: x, y, z and data[3], which key points use for their height above ground — a quirk, kept.  It is summed as Eigen's
+ *              packet reduction does, (dx*dx + dz*dz) + (dy*dy + dw*dw), in float.  sample_dist_thresh = (mean of the square roots of the three
+ *              eigenvalues of the source cloud's covariance)^2, in double; the covariance is pcl::computeMeanAndCovarianceMatrix's (float raw moments
+ *              summed in index order, divided by N, E[xx^T] - c c^T).   [LIB] the eigenvalues: cyclic Jacobi in double on that float covariance.
+ *   model      [LIB] the rigid transform of the sample pairs (PCL: float demeaning, H, JacobiSVD<Matrix3f>).  Float centroids ((p0 + p1) + p2) / 3, float
+ *              H[a][b] = sum of (s_k[a] - cs[a]) * (t_k[b] - ct[b]) in the samples' order; then in double Horn's symmetric 4 x 4 matrix of H, exactly
+ *              10 sweeps of cyclic Jacobi over (0,1) (0,2) (0,3) (1,2) (1,3) (2,3), the column of the largest diagonal entry (the first among equals)
+ *              normalised to a unit quaternion, its rotation matrix R, t = ct - R cs; all of it rounded to float once.  Only + - * / sqrt, no
+ *              contraction.  DESIGN.md section 7 lists it operation by operation.
+ *   score      count = #{ i : |T (s_i, 1) - (t_i, 1)|^2 < (double)noise_bound^2 }, float: p_r = ((T_r0 sx + T_r1 sy) + T_r2 sz) + T_r3, d_r = p_r - t_r,
+ *              d2 = (dx dx + dy dy) + dz dz, compared as (double)d2 < threshold.
+ *   loop       [PCL] iteration i = 0, 1, ...: a count above the best so far installs the model and k = log(1 - 0.99) / log(clamp(1 - (best / N)^3, eps, 1 - eps))
+ *              (std::log, std::pow); the loop goes on while iterations < k, and ends once ++iterations > max_iter_num.  The device scores every hypothesis
+ *              the loop could reach in one launch and the host applies this rule to the counts: the same result, as the samples do not depend on the counts.
+ *   refinement [PCL] refineModel(3.0, 1000): fit all current inliers, select within error_threshold, variance = 2.1981 * the selected squared distances'
+ *              element of rank size/2, error_threshold = sqrt(min(noise_bound^2, 9 variance)); repeated while the inlier set changes; a 2-cycle in the
+ *              last four set sizes ends it and KEEPS THE UNREFINED model and inliers (PCL returns true there without installing anything); 1000 rounds
+ *              or an empty selection: failure.   [LIB] the fit is the model estimator with double sums: centroids, then H of the demeaned doubles; each
+ *              sum in the fixed order "256 strided partial sums in ascending index, then a pairwise tree" (DESIGN.md section 7).
+ *   outcomes   [PCL] no model (N < 3, no good sample) or fewer than 3 inliers: every correspondence passes with T = identity, so status follows N; a failed
+ *              refinement: no inliers, status -1; else status = 1 if n_inliers >= 2 min_inlier_num, 0 if >= min_inlier_num, -1 below.
+ * Non-finite coordinates follow the arithmetic above (a NaN covariance means no sample is good: the pass-through outcome). */
+typedef struct mulls_ransac_params
+{
+	float noise_bound;		/* [0.2]   inlier threshold, metres (setInlierThreshold) */
+	int32_t min_inlier_num; /* [8]     */
+	int32_t max_iter_num;	/* [20000] */
+	int32_t refine;			/* [1]     upstream: setRefineModel(true) */
+} mulls_ransac_params;
+
+typedef struct mulls_ransac_result
+{
+	int32_t status;			   /* upstream's return: 1 reliable, 0 need check, -1 failed */
+	int32_t iterations;		   /* hypotheses the sequential definition evaluated */
+	int32_t best_iteration;	   /* index of the winning hypothesis, -1 if none */
+	int32_t refine_iterations; /* rounds of the refinement that fitted a model */
+	uint32_t n_inliers;		   /* size of final_corres */
+	double T[16];			   /* column-major; upstream's Matrix4f cast to double; identity when status == -1 */
+} mulls_ransac_result;
+
+void mulls_ransac_default_params(mulls_ransac_params *p);
+/* returns MULLS_OK or MULLS_E_*: MULLS_E_INVALID when the sizes differ (upstream reads out of bounds then), for a non-finite noise_bound or a bad stride;
+ * MULLS_E_UNSUPPORTED above 65536 points or max_iter_num > 2^20.  inliers: the indices of final_corres, ascending, at most cap of them (NULL / 0 allowed).
+ * The clouds are host memory (any stride that is a multiple of 4 and at least 16: x, y, z, data[3] go up) or device-resident clouds of 48-byte records. */
+int mulls_coarse_reg_ransac(mulls_ctx *ctx, const mulls_cloud *tgt_pts, const mulls_cloud *src_pts, const mulls_ransac_params *params,
+							mulls_ransac_result *result, int32_t *inliers, uint32_t cap);
+/* the same solver on tgt_kpts[tgt_idx[k]] <-> src_kpts[src_idx[k]], k < n_corr: the index lists mulls_ncc_correspond wrote (host memory).  The gather
+ * runs on the device; results equal mulls_coarse_reg_ransac on the gathered clouds (inliers are positions k in the lists).  MULLS_E_INVALID for an
+ * index outside its cloud. */
+int mulls_coarse_reg_ransac_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const int32_t *tgt_idx, const int32_t *src_idx,
+									uint32_t n_corr, const mulls_ransac_params *params, mulls_ransac_result *result, int32_t *inliers, uint32_t cap);
 
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 

@@ -319,6 +319,25 @@ def ncc_params(fixed_num_corr=0, corr_num=2000, reciprocal_on=1):
     return p
 
 
+class RansacParams(C.Structure):
+    """mulls_ransac_params: coarse_reg_ransac's arguments behind the clouds (cregistration.hpp:607), and upstream's setRefineModel(true)"""
+
+    _fields_ = [("noise_bound", C.c_float), ("min_inlier_num", C.c_int32), ("max_iter_num", C.c_int32), ("refine", C.c_int32)]
+
+
+class RansacResult(C.Structure):
+    """mulls_ransac_result"""
+
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("best_iteration", C.c_int32), ("refine_iterations", C.c_int32),
+                ("n_inliers", C.c_uint32), ("T", C.c_double * 16)]
+
+
+def ransac_params(noise_bound=0.2, min_inlier_num=8, max_iter_num=20000, refine=1):
+    p = RansacParams()
+    p.noise_bound, p.min_inlier_num, p.max_iter_num, p.refine = float(noise_bound), int(min_inlier_num), int(max_iter_num), int(refine)
+    return p
+
+
 def records(a):
     """Any point array (POINT_DTYPE records or raw (n, 48) bytes) as contiguous raw (n, 48) uint8 records, every byte kept."""
     a = np.asarray(a)

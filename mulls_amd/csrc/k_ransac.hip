@@ -1,0 +1,292 @@
+// k_ransac.hip — the RANSAC coarse-registration solver (CRegistration::coarse_reg_ransac, cregistration.hpp:605-661) for gfx950.
+//   k_ransac_gather  the four live floats of the pairs out of 48-byte records (optionally through an index list)
+//   k_ransac_models  one lane per hypothesis: float centroids and H of its three pairs, Horn's 4 x 4 by cyclic Jacobi in double
+//   k_ransac_score   one wave per four hypotheses: the lanes stride over the pairs, the models sit in scalar registers
+//   k_ransac_select  the inlier mask of one model
+//   k_ransac_refine  one workgroup: a round of PCL's refineModel — fit to the previous inliers, select, exact median by radix select
+// Every float / double expression is written in the order include/mulls_hip.h and DESIGN.md section 7 define (built with -ffp-contract=off):
+// tests/ransac_restated.py reproduces the bits.
+#include <hip/hip_runtime.h>
+
+#include "ransac_launch.h"
+#include "ransac_math.h"
+
+namespace
+{
+constexpr int WAVE = 64;
+constexpr int SCORE_THREADS = 256;
+constexpr int HYP_PER_WAVE = 4;
+constexpr int HYP_PER_BLOCK = (SCORE_THREADS / WAVE) * HYP_PER_WAVE;
+constexpr int RT = (int)MULLS_RANSAC_REFINE_THREADS;
+
+// squared distance of T (s, 1) to (t, 1), float
+__device__ __forceinline__ float resid2(const float *m, const float4 s, const float4 t)
+{
+	const float px = ((m[0] * s.x + m[1] * s.y) + m[2] * s.z) + m[3];
+	const float py = ((m[4] * s.x + m[5] * s.y) + m[6] * s.z) + m[7];
+	const float pz = ((m[8] * s.x + m[9] * s.y) + m[10] * s.z) + m[11];
+	const float dx = px - t.x, dy = py - t.y, dz = pz - t.z;
+	return (dx * dx + dy * dy) + dz * dz;
+}
+
+__global__ void __launch_bounds__(256) k_ransac_gather(const unsigned char *recs, const int32_t *idx, uint32_t n, float4 *out)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n)
+		return;
+	const size_t r = idx ? (size_t)idx[i] : (size_t)i; // (the host has checked the index lists against the clouds' sizes)
+	out[i] = *reinterpret_cast<const float4 *>(recs + r * 48u);
+}
+
+__global__ void __launch_bounds__(256) k_ransac_models(const float4 *src, const float4 *tgt, const int32_t *triples, uint32_t n_hyp, RansacModel *models)
+{
+	const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
+	if (h >= n_hyp)
+		return;
+	float s[3][3], t[3][3];
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+	{
+		const int32_t i = triples[3u * h + k];
+		const float4 a = src[i], b = tgt[i];
+		s[k][0] = a.x, s[k][1] = a.y, s[k][2] = a.z;
+		t[k][0] = b.x, t[k][1] = b.y, t[k][2] = b.z;
+	}
+	float cs[3], ct[3];
+#pragma unroll
+	for (int a = 0; a < 3; a++)
+	{
+		cs[a] = ((s[0][a] + s[1][a]) + s[2][a]) / 3.0f;
+		ct[a] = ((t[0][a] + t[1][a]) + t[2][a]) / 3.0f;
+	}
+	double H[9], csd[3], ctd[3];
+#pragma unroll
+	for (int a = 0; a < 3; a++)
+	{
+#pragma unroll
+		for (int b = 0; b < 3; b++)
+		{
+			const float h0 = (s[0][a] - cs[a]) * (t[0][b] - ct[b]), h1 = (s[1][a] - cs[a]) * (t[1][b] - ct[b]), h2 = (s[2][a] - cs[a]) * (t[2][b] - ct[b]);
+			H[a * 3 + b] = (double)((h0 + h1) + h2);
+		}
+		csd[a] = (double)cs[a], ctd[a] = (double)ct[a];
+	}
+	RansacModel M;
+	horn_fit(H, csd, ctd, M.m);
+	models[h] = M;
+}
+
+__global__ void __launch_bounds__(SCORE_THREADS) k_ransac_score(const float4 *__restrict__ src, const float4 *__restrict__ tgt, uint32_t n,
+																 const RansacModel *__restrict__ models, uint32_t n_hyp, double thresh, uint32_t *__restrict__ counts)
+{
+	// the wave's number, made scalar: the models' loads become scalar loads and the 48 coefficients live in SGPRs
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE;
+	const uint32_t h0 = blockIdx.x * HYP_PER_BLOCK + wave * HYP_PER_WAVE;
+	if (h0 >= n_hyp)
+		return;
+	float m[HYP_PER_WAVE][12];
+#pragma unroll
+	for (int j = 0; j < HYP_PER_WAVE; j++)
+	{
+		const uint32_t h = min(h0 + (uint32_t)j, n_hyp - 1u);
+#pragma unroll
+		for (int k = 0; k < 12; k++)
+			m[j][k] = models[h].m[k];
+	}
+	uint32_t c[HYP_PER_WAVE] = {0, 0, 0, 0};
+	for (uint32_t i = lane; i < n; i += WAVE)
+	{
+		const float4 s = src[i], t = tgt[i];
+#pragma unroll
+		for (int j = 0; j < HYP_PER_WAVE; j++)
+			c[j] += (double)resid2(m[j], s, t) < thresh ? 1u : 0u;
+	}
+#pragma unroll
+	for (int j = 0; j < HYP_PER_WAVE; j++)
+	{
+		uint32_t v = c[j];
+#pragma unroll
+		for (int off = WAVE / 2; off > 0; off >>= 1)
+			v += __shfl_xor(v, off, WAVE);
+		if (lane == 0 && h0 + (uint32_t)j < n_hyp)
+			counts[h0 + j] = v;
+	}
+}
+
+__global__ void __launch_bounds__(256) k_ransac_select(const float4 *src, const float4 *tgt, uint32_t n, const RansacModel *model, double thresh, uint8_t *mask,
+														uint32_t *count)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	float m[12];
+#pragma unroll
+	for (int k = 0; k < 12; k++)
+		m[k] = model->m[k];
+	bool in = false;
+	if (i < n)
+	{
+		in = (double)resid2(m, src[i], tgt[i]) < thresh;
+		mask[i] = in ? 1 : 0;
+	}
+	const unsigned long long b = __ballot(in);
+	if (threadIdx.x % WAVE == 0 && b)
+		atomicAdd(count, (uint32_t)__popcll(b));
+}
+
+// sum of v over the workgroup in the defined order: the RT per-thread values by a pairwise tree, p[t] += p[t + s] for s = RT / 2, ..., 1
+__device__ double block_tree_sum(double v, double *red)
+{
+	const int t = threadIdx.x;
+	__syncthreads(); // (red may still be read by the previous sum)
+	red[t] = v;
+	__syncthreads();
+	for (int s = RT / 2; s > 0; s >>= 1)
+	{
+		if (t < s)
+			red[t] = red[t] + red[t + s];
+		__syncthreads();
+	}
+	return red[0];
+}
+
+__global__ void __launch_bounds__(RT) k_ransac_refine(const float4 *src, const float4 *tgt, uint32_t n, const uint8_t *mask_prev, uint8_t *mask_new, float *d2,
+													   double thresh, RansacRound *out)
+{
+	__shared__ double red[RT];
+	__shared__ uint32_t hist[256];
+	__shared__ uint32_t sh_n_prev, sh_n_new, sh_changed, sh_prefix, sh_rank;
+	const uint32_t t = threadIdx.x;
+	if (t == 0)
+		sh_n_prev = 0, sh_n_new = 0, sh_changed = 0;
+	__syncthreads();
+	// centroids: thread t adds the pairs t, t + RT, ... of the previous inlier set in ascending order
+	double a[6] = {0, 0, 0, 0, 0, 0};
+	uint32_t cnt = 0;
+	for (uint32_t i = t; i < n; i += RT)
+		if (mask_prev[i])
+		{
+			const float4 s = src[i], g = tgt[i];
+			a[0] = a[0] + (double)s.x, a[1] = a[1] + (double)s.y, a[2] = a[2] + (double)s.z;
+			a[3] = a[3] + (double)g.x, a[4] = a[4] + (double)g.y, a[5] = a[5] + (double)g.z;
+			cnt++;
+		}
+	if (cnt)
+		atomicAdd(&sh_n_prev, cnt);
+	double cen[6];
+	for (int k = 0; k < 6; k++)
+		cen[k] = block_tree_sum(a[k], red);
+	const uint32_t n_prev = sh_n_prev; // (block_tree_sum's barriers order the atomics before this read)
+	const double nd = (double)n_prev;
+	for (int k = 0; k < 6; k++)
+		cen[k] = cen[k] / nd;
+	double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+	for (uint32_t i = t; i < n; i += RT)
+		if (mask_prev[i])
+		{
+			const float4 s = src[i], g = tgt[i];
+			const double sd[3] = {(double)s.x - cen[0], (double)s.y - cen[1], (double)s.z - cen[2]};
+			const double gd[3] = {(double)g.x - cen[3], (double)g.y - cen[4], (double)g.z - cen[5]};
+#pragma unroll
+			for (int r = 0; r < 3; r++)
+#pragma unroll
+				for (int c = 0; c < 3; c++)
+					h[r * 3 + c] = h[r * 3 + c] + sd[r] * gd[c];
+		}
+	double H[9];
+	for (int k = 0; k < 9; k++)
+		H[k] = block_tree_sum(h[k], red);
+	float m[12];
+	horn_fit(H, cen, cen + 3, m); // every thread the same arithmetic on the same numbers
+	// select
+	uint32_t n_in = 0, diff = 0;
+	for (uint32_t i = t; i < n; i += RT)
+	{
+		const float r2 = resid2(m, src[i], tgt[i]);
+		const bool in = (double)r2 < thresh;
+		d2[i] = r2;
+		mask_new[i] = in ? 1 : 0;
+		n_in += in ? 1u : 0u;
+		diff |= (in ? 1u : 0u) ^ (mask_prev[i] ? 1u : 0u);
+	}
+	if (n_in)
+		atomicAdd(&sh_n_new, n_in);
+	if (diff)
+		atomicOr(&sh_changed, 1u);
+	__syncthreads();
+	const uint32_t n_new = sh_n_new;
+	// the selected squared distances' element of rank n_new / 2: they are not negative, so their bit patterns order as they do; four 8-bit digits
+	if (t == 0)
+		sh_prefix = 0, sh_rank = n_new >> 1;
+	for (int level = 0; level < 4 && n_new; level++)
+	{
+		const int shift = 24 - 8 * level;
+		hist[t & 255u] = 0; // RT == 256
+		__syncthreads();
+		const uint32_t prefix = sh_prefix, himask = level ? 0xffffffffu << (shift + 8) : 0u;
+		for (uint32_t i = t; i < n; i += RT)
+			if (mask_new[i])
+			{
+				const uint32_t b = __float_as_uint(d2[i]);
+				if ((b & himask) == prefix)
+					atomicAdd(&hist[(b >> shift) & 255u], 1u);
+			}
+		__syncthreads();
+		if (t == 0)
+		{
+			uint32_t r = sh_rank, d = 0;
+			for (; d < 255u; d++)
+			{
+				if (r < hist[d])
+					break;
+				r -= hist[d];
+			}
+			sh_rank = r;
+			sh_prefix = prefix | (d << shift);
+		}
+		__syncthreads();
+	}
+	if (t == 0)
+	{
+		for (int k = 0; k < 12; k++)
+			out->T.m[k] = m[k];
+		out->n_new = n_new;
+		out->changed = sh_changed;
+		out->median = n_new ? __uint_as_float(sh_prefix) : 0.0f;
+		out->n_prev = n_prev;
+	}
+}
+} // namespace
+
+hipError_t launch_ransac_gather(hipStream_t st, const void *recs, const int32_t *idx, uint32_t n, float4 *out)
+{
+	if (!n)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_ransac_gather, dim3((n + 255u) / 256u), dim3(256), 0, st, static_cast<const unsigned char *>(recs), idx, n, out);
+	return hipGetLastError();
+}
+
+hipError_t launch_ransac_models(hipStream_t st, const float4 *src, const float4 *tgt, const int32_t *triples, uint32_t n_hyp, RansacModel *models)
+{
+	hipLaunchKernelGGL(k_ransac_models, dim3((n_hyp + 255u) / 256u), dim3(256), 0, st, src, tgt, triples, n_hyp, models);
+	return hipGetLastError();
+}
+
+hipError_t launch_ransac_score(hipStream_t st, const float4 *src, const float4 *tgt, uint32_t n, const RansacModel *models, uint32_t n_hyp, double thresh,
+							   uint32_t *counts)
+{
+	hipLaunchKernelGGL(k_ransac_score, dim3((n_hyp + HYP_PER_BLOCK - 1u) / HYP_PER_BLOCK), dim3(SCORE_THREADS), 0, st, src, tgt, n, models, n_hyp, thresh, counts);
+	return hipGetLastError();
+}
+
+hipError_t launch_ransac_select(hipStream_t st, const float4 *src, const float4 *tgt, uint32_t n, const RansacModel *model, double thresh, uint8_t *mask,
+								uint32_t *count)
+{
+	hipLaunchKernelGGL(k_ransac_select, dim3((n + 255u) / 256u), dim3(256), 0, st, src, tgt, n, model, thresh, mask, count);
+	return hipGetLastError();
+}
+
+hipError_t launch_ransac_refine(hipStream_t st, const float4 *src, const float4 *tgt, uint32_t n, const uint8_t *mask_prev, uint8_t *mask_new, float *d2,
+								double thresh, RansacRound *out)
+{
+	hipLaunchKernelGGL(k_ransac_refine, dim3(1), dim3(RT), 0, st, src, tgt, n, mask_prev, mask_new, d2, thresh, out);
+	return hipGetLastError();
+}

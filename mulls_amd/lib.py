@@ -104,6 +104,11 @@ def load():
     lib.mulls_ncc_default_params.argtypes = [C.POINTER(abi.NccParams)]
     lib.mulls_ncc_default_params.restype = None
     lib.mulls_ncc_correspond.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.NccParams), vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.mulls_ransac_default_params.argtypes = [C.POINTER(abi.RansacParams)]
+    lib.mulls_ransac_default_params.restype = None
+    lib.mulls_coarse_reg_ransac.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.RansacParams), C.POINTER(abi.RansacResult), vp, C.c_uint32]
+    lib.mulls_coarse_reg_ransac_indexed.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), vp, vp, C.c_uint32, C.POINTER(abi.RansacParams),
+                                                    C.POINTER(abi.RansacResult), vp, C.c_uint32]
     lib.mulls_io_read_kitti_bin.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_read_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_write_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_int]
@@ -124,6 +129,7 @@ EXPORTS = [
     "mulls_motion_compensate", "mulls_block_motion_compensate",
     "mulls_pack_results", "mulls_icp_batch_sharded", "mulls_pipe_create", "mulls_pipe_destroy", "mulls_pipe_depth", "mulls_pipe_ctx", "mulls_pipe_set_option", "mulls_icp_batch_begin", "mulls_icp_batch_end",
     "mulls_ncc_default_params", "mulls_ncc_correspond",
+    "mulls_ransac_default_params", "mulls_coarse_reg_ransac", "mulls_coarse_reg_ransac_indexed",
 ]
 
 
@@ -417,6 +423,44 @@ class Context:
         w = min(n.value, cap)
         assert ti[cap] == -1 and si[cap] == -1
         return bool(rc), ti[:w].copy(), si[:w].copy(), n.value
+
+    # --- RANSAC coarse registration --------------------------------------------------------------------------------
+    def coarse_reg_ransac(self, tgt_pts, src_pts, params=None, cap=None, tgt_idx=None, src_idx=None):
+        """coarse_reg_ransac (mulls_coarse_reg_ransac; with tgt_idx / src_idx, mulls_coarse_reg_ransac_indexed on the pairs those lists name).  The clouds
+        are host clouds or device-resident abi.Cloud objects, as for ncc_correspond.  Returns (result, inliers): the abi.RansacResult and the ascending
+        inlier indices actually written (min(n_inliers, cap) of them; cap defaults to the number of pairs)."""
+        keep = []
+
+        def cloud(k):
+            if isinstance(k, abi.Cloud):
+                return k
+            raw = abi.records(k)
+            keep.append(raw)
+            c = abi.Cloud()
+            c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+            return c
+
+        ct, cs = cloud(tgt_pts), cloud(src_pts)
+        p = params if params is not None else abi.ransac_params()
+        res = abi.RansacResult()
+        indexed = tgt_idx is not None
+        if indexed:
+            ti, si = np.ascontiguousarray(tgt_idx, np.int32), np.ascontiguousarray(src_idx, np.int32)
+            assert len(ti) == len(si)
+        n_pairs = len(ti) if indexed else ct.n
+        if cap is None:
+            cap = n_pairs
+        inl = np.full(cap + 1, -1, np.int32)  # one slot past cap: checked to be left alone
+        ip = inl.ctypes.data_as(C.c_void_p) if cap else None
+        if indexed:
+            rc = self.lib.mulls_coarse_reg_ransac_indexed(self.h, C.byref(ct), C.byref(cs), ti.ctypes.data_as(C.c_void_p), si.ctypes.data_as(C.c_void_p), len(ti),
+                                                          C.byref(p), C.byref(res), ip, cap)
+        else:
+            rc = self.lib.mulls_coarse_reg_ransac(self.h, C.byref(ct), C.byref(cs), C.byref(p), C.byref(res), ip, cap)
+        if rc != 0:
+            raise MullsError("mulls_coarse_reg_ransac failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        assert inl[cap] == -1
+        return res, inl[: min(res.n_inliers, cap)].copy()
 
     # --- stage-level entry points --------------------------------------------------------------------------------
     def motion_compensate(self, pts, Tran, s_ambiguous_thre=0.0):

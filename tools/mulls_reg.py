@@ -1,11 +1,13 @@
 """Pairwise registration of two point clouds with the library, stage for stage what test/mulls_reg.cpp does (script/run_mulls_reg.sh):
 read -> voxel_downsample (cloud_*_down_res, 0 = off as in run_mulls_reg.sh) -> fast_ground_filter -> classify_nground_pts per cloud -> the
-cloud with more down-sampled feature points is the target -> mm_lls_icp -> the source's pc_down, transformed, written out.  Flags carry the
-reference's names and defaults (test/mulls_reg.cpp:24-60).  Not here: the solver of the global coarse registration (TEASER++ / PCL RANSAC — the
-key-point correspondences it consumes are in the library, mulls_ncc_correspond, but have no consumer in this tool: --is_global_reg must be false, the initial
-guess is the identity), the viewers.
+cloud with more down-sampled feature points is the target -> with --is_global_reg (the reference's default: true) the global coarse registration,
+find_feature_correspondence_ncc on the two key-point clouds -> coarse_reg_ransac with noise_bound = 4 x keypoint_nms_radius (test/mulls_reg.cpp:170-179;
+mulls_ncc_correspond -> mulls_coarse_reg_ransac_indexed), whose transform is the initial guess (the identity when it fails, as upstream leaves init_mat)
+-> mm_lls_icp -> the source's pc_down, transformed, written out.  Flags carry the reference's names and defaults (test/mulls_reg.cpp:24-60).  Not here:
+TEASER++ (--teaser_on is accepted and answered with the RANSAC solver), the second non_max_suppress of the key points with keypoint_nms_radius
+(:145-149; the classification has already thinned them with the six times larger vertex_curvature_non_max_radius), the viewers.
 
-    python tools/mulls_reg.py --point_cloud_1_path a.pcd --point_cloud_2_path b.pcd --output_point_cloud_path b_reg.pcd --is_global_reg=false
+    python tools/mulls_reg.py --point_cloud_1_path a.pcd --point_cloud_2_path b.pcd --output_point_cloud_path b_reg.pcd
 """
 import argparse
 import sys
@@ -47,6 +49,10 @@ def flags(argv=None):
     p.add_argument("--converge_tran", type=float, default=0.001)
     p.add_argument("--converge_rot_d", type=float, default=0.01)
     p.add_argument("--is_global_reg", type=boolean, default=True)
+    p.add_argument("--teaser_on", type=boolean, default=False)
+    p.add_argument("--corr_num", type=int, default=3000)
+    p.add_argument("--reciprocal_corr_on", type=boolean, default=False)
+    p.add_argument("--fixed_num_corr_on", type=boolean, default=False)
     p.add_argument("--device", type=int, default=0)
     a, _ = p.parse_known_args(argv)  # glog / viewer flags of the reference's script are accepted and ignored
     return a
@@ -91,6 +97,18 @@ def extract_semantic_pts(ctx, scan, F, vf_downsample_resolution):
     return full, down, pc_down
 
 
+def global_registration(ctx, tgt_kpts, src_kpts, F):
+    """test/mulls_reg.cpp:170-179: key-point correspondences, then the RANSAC solver; returns init_mat"""
+    if F.teaser_on:
+        print("--teaser_on: TEASER++ is not part of the library; the RANSAC solver (coarse_reg_ransac) is used")
+    keypoint_nms_radius = 0.25 * F.pca_neighbor_radius  # :107
+    ok, ti, si, n = ctx.ncc_correspond(tgt_kpts, src_kpts, abi.ncc_params(int(F.fixed_num_corr_on), F.corr_num, int(F.reciprocal_corr_on)))
+    res, _ = ctx.coarse_reg_ransac(tgt_kpts, src_kpts, abi.ransac_params(noise_bound=4.0 * keypoint_nms_radius), cap=0, tgt_idx=ti, src_idx=si)
+    print("global registration: %d key-point pairs, RANSAC status %d after %d iterations, %d inliers" % (n, res.status, res.iterations, res.n_inliers))
+    # upstream writes init_mat only when the solver does not fail (cregistration.hpp:642-660)
+    return np.array(res.T[:], np.float64).reshape(4, 4).T.copy() if res.status >= 0 else np.eye(4)
+
+
 def register(ctx, scan1, scan2, F):
     """Returns (abi.Result, which scan is the source: 1 or 2, that scan's pc_down)."""
     # test/mulls_reg.cpp:80-81, :134-143: block 1 is down-sampled with cloud_2_down_res, block 2 with cloud_1_down_res
@@ -99,8 +117,11 @@ def register(ctx, scan1, scan2, F):
     n1, n2 = sum(len(x) for x in d1), sum(len(x) for x in d2)
     # determine_source_target_cloud (cregistration.hpp:857-870): block1 (target) = the one with more down-sampled feature points
     (tgt_full, src_down, source) = (f1, d2, 2) if n1 > n2 else (f2, d1, 1)
+    init_mat = np.eye(4)
+    if F.is_global_reg:
+        init_mat = global_registration(ctx, tgt_full[5], src_down[5], F)
     pair = abi.PairData([abi.points_of(t) for t in tgt_full], [abi.points_of(s) for s in src_down],
-                        tgt_bound=scan_bound(abi.as_points(scan1 if source == 2 else scan2)) if len(scan1) and len(scan2) else None)
+                        init_guess=init_mat, tgt_bound=scan_bound(abi.as_points(scan1 if source == 2 else scan2)) if len(scan1) and len(scan2) else None)
     # mm_lls_icp(reg_con, max_iter, thre, converge_tran, converge_rot_d, 0.25 * thre, 1.1, "111110", "1101", 1.0, 0.1, 0.1, 0.1, init_mat)
     P = abi.default_params(max_iter_num=F.reg_max_iter_num, dis_thre_unit=F.corr_dis_thre, converge_translation=F.converge_tran,
                            converge_rotation_d=F.converge_rot_d, dis_thre_min=0.25 * F.corr_dis_thre, dis_thre_update_rate=1.1,
@@ -111,8 +132,6 @@ def register(ctx, scan1, scan2, F):
 
 def main(argv=None):
     F = flags(argv)
-    if F.is_global_reg:
-        sys.exit("the global coarse registration is out of scope: pass --is_global_reg=false (the initial guess is the identity)")
     ctx = lib.Context(F.device)
     scans = [read_cloud(F.point_cloud_1_path), read_cloud(F.point_cloud_2_path)]
     res, source, source_down = register(ctx, scans[0], scans[1], F)
