@@ -698,6 +698,41 @@ inline int coarse_reg_ransac(const typename pcl::PointCloud<PointT>::Ptr &target
 	return R.status;
 }
 
+// CFilter<PointT>::sor_filter (include/common/cfilter.hpp:204-222 and :225-247), verbatim signatures (upstream gives no defaults): the statistical
+// outlier removal of the merged map mulls_slam exports (test/mulls_slam.cpp:1008-1009, `cf.sor_filter(pc_map_merged, 20, 2.0)` under --map_filter_on) in one
+// device call (mulls_sor_filter).  The binding is one early return at the top of each member function:
+//     #ifdef MULLS_USE_HIP
+//         return lo::hip::sor_filter<PointT>(cloud_in, cloud_out, mean_k, n_std);      // resp. (cloud_in_out, mean_k, n_std)
+//     #endif
+// cloud_out is overwritten, as pcl::Filter::filter does.  Upstream's body is pcl::StatisticalOutlierRemoval; include/mulls_hip.h says which lines of the
+// definition are PCL's (restated from memory, not compared) and which are the library's.  A cloud of 1 .. mean_k points, on which PCL reads past its
+// neighbour search's result, throws here, as do non-finite coordinates.
+template <typename PointT>
+inline bool sor_filter(typename pcl::PointCloud<PointT>::Ptr &cloud_in, typename pcl::PointCloud<PointT>::Ptr &cloud_out, int mean_k, double n_std)
+{
+	mulls_ctx *ctx = thread_context();
+	const mulls_cloud in = borrow(cloud_in);
+	mulls_sor_params P;
+	mulls_sor_default_params(&P);
+	P.mean_k = mean_k;
+	P.std_mul = n_std;
+	std::vector<unsigned char> raw((size_t)in.n * MULLS_POINT_BYTES);
+	uint32_t n_out = 0;
+	const int rc = mulls_sor_filter(ctx, &in, &P, raw.data(), in.n, &n_out, nullptr, 0, nullptr, nullptr);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_sor_filter failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	take_cloud<PointT>(cloud_out, raw, n_out, false);
+	return 1;
+}
+template <typename PointT>
+inline bool sor_filter(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out, int mean_k, double n_std)
+{
+	typename pcl::PointCloud<PointT>::Ptr cloud_temp(new pcl::PointCloud<PointT>());
+	sor_filter<PointT>(cloud_in_out, cloud_temp, mean_k, n_std);
+	cloud_temp->points.swap(cloud_in_out->points); // :239
+	return 1;
+}
+
 // CFilter<PointT>::extract_semantic_pts (include/common/cfilter.hpp:2295-2413), verbatim signature: the whole chain in one device call
 // (mulls_extract_features).  The binding is one early return at the top of the member function:
 //     #ifdef MULLS_USE_HIP

@@ -672,6 +672,51 @@ int mulls_coarse_reg_ransac(mulls_ctx *ctx, const mulls_cloud *tgt_pts, const mu
 int mulls_coarse_reg_ransac_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const int32_t *tgt_idx, const int32_t *src_idx,
 									uint32_t n_corr, const mulls_ransac_params *params, mulls_ransac_result *result, int32_t *inliers, uint32_t cap);
 
+/* ---- statistical outlier removal: CFilter<PointT>::sor_filter (include/common/cfilter.hpp:204-247) ----
+ * The filter of the merged map mulls_slam writes at the end of a run (test/mulls_slam.cpp:1009, sor_filter(pc_map_merged, 20, 2.0) under --map_filter_on).
+ * Upstream's body is pcl::StatisticalOutlierRemoval.  PCL is not available where this library is built and tested, so nothing below was checked
+ * against it: the lines marked [PCL] restate statistical_outlier_removal.hpp of PCL 1.8 - 1.10 from memory, the lines marked [LIB] are defined by this
+ * library.  tests/sor_restated.py restates all of it independently in numpy, bit for bit.  DESIGN.md section 7.2 has the same list with its reasons.
+ *   neighbours [PCL / FLANN] for point i the mean_k + 1 smallest squared distances to the points of the same cloud, itself included; float
+ *              d2 = (dx dx + dy dy) + dz dz, no contraction (L2_Simple).  Only the multiset of the values matters: no tie order is involved.  The
+ *              smallest value (0: the point itself or a coincident one) is dropped.
+ *   distance   [PCL] dist_i = (float)(sum over the mean_k remaining values, ascending, of sqrt((double)d2) / mean_k), the sum in double.
+ *              [LIB] the square root is the double one: PCL writes an unqualified sqrt(nn_dists[k]), and which overload that is depends on the headers in
+ *              scope.  (No committed expectation depends on the choice: tests/test_sor.py checks every fixture's keep mask under both readings.)
+ *   statistics [PCL] sum = sum of (double)dist_i, sq_sum = sum of (double)(dist_i * dist_i) (the product in float), mean = sum / n,
+ *              variance = (sq_sum - sum * sum / n) / (n - 1), stddev = sqrt(variance), threshold = mean + std_mul * stddev, all in double.  A variance
+ *              that rounding made negative gives a NaN threshold, and every point passes: the arithmetic is followed, not repaired.
+ *              [LIB] the order of the two sums (PCL: index order): 16384 strided partial sums (partial p adds i = p, p + 16384, ... in ascending i),
+ *              then a pairwise tree over the partials (half = 8192, 4096, ..., 1: s[p] += s[p + half] for p < half).
+ *   selection  [PCL] point i is removed iff (double)dist_i > threshold; the kept points stay in index order.  negative and keep_organized are not offered.
+ *   refused    [LIB] n == 0: MULLS_OK, nothing kept.  1 <= n <= mean_k: MULLS_E_INVALID (upstream reads past the k-NN result there).  mean_k < 1:
+ *              MULLS_E_INVALID; mean_k > 64: MULLS_E_UNSUPPORTED.  A non-finite coordinate or std_mul: MULLS_E_INVALID (PCL leaves non-finite points out of
+ *              the tree and passes them through: not reproduced).  More than 2^24 = 16777216 points: MULLS_E_UNSUPPORTED.
+ * The search is exact: a hash of occupied cells (cell edge from the data; part of the implementation, not of the result), Chebyshev rings with a
+ * conservative certificate, coarser levels and finally brute force for the queries the rings do not certify. */
+typedef struct mulls_sor_params
+{
+	int32_t mean_k; /* [20] */
+	int32_t reserved;
+	double std_mul; /* [2.0] */
+} mulls_sor_params;
+
+typedef struct mulls_sor_report
+{
+	uint32_t n_in, n_kept;
+	double mean, stddev, threshold;
+	float ms_total;		 /* wall time of the call */
+	uint32_t n_fallback; /* queries that left the grid walk and were answered by brute force */
+} mulls_sor_report;
+
+void mulls_sor_default_params(mulls_sor_params *p);
+/* returns MULLS_OK or MULLS_E_* (the list above; MULLS_E_INVALID also for a bad stride).  cloud: host memory (48-byte records at any stride that is a
+ * multiple of 4 and at least 48) or a device-resident cloud of 48-byte records (mulls_map_cloud, mulls_block_cloud).  All outputs are host memory.
+ * out: the kept records, byte for byte, in index order, at most cap of them (NULL with cap 0 allowed); *n_out: the full kept count.
+ * kept_idx: their ascending indices, at most idx_cap (NULL / 0 allowed).  mean_dist: NULL, or n floats: every point's dist_i.  report may be NULL. */
+int mulls_sor_filter(mulls_ctx *ctx, const mulls_cloud *cloud, const mulls_sor_params *params, void *out, uint32_t cap, uint32_t *n_out, int32_t *kept_idx,
+					 uint32_t idx_cap, float *mean_dist, mulls_sor_report *report);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

@@ -338,6 +338,25 @@ def ransac_params(noise_bound=0.2, min_inlier_num=8, max_iter_num=20000, refine=
     return p
 
 
+class SorParams(C.Structure):
+    """mulls_sor_params: sor_filter's arguments behind the cloud (cfilter.hpp:204)"""
+
+    _fields_ = [("mean_k", C.c_int32), ("reserved", C.c_int32), ("std_mul", C.c_double)]
+
+
+class SorReport(C.Structure):
+    """mulls_sor_report"""
+
+    _fields_ = [("n_in", C.c_uint32), ("n_kept", C.c_uint32), ("mean", C.c_double), ("stddev", C.c_double), ("threshold", C.c_double),
+                ("ms_total", C.c_float), ("n_fallback", C.c_uint32)]
+
+
+def sor_params(mean_k=20, std_mul=2.0):
+    p = SorParams()
+    p.mean_k, p.reserved, p.std_mul = int(mean_k), 0, float(std_mul)
+    return p
+
+
 def records(a):
     """Any point array (POINT_DTYPE records or raw (n, 48) bytes) as contiguous raw (n, 48) uint8 records, every byte kept."""
     a = np.asarray(a)

@@ -109,6 +109,10 @@ def load():
     lib.mulls_coarse_reg_ransac.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.RansacParams), C.POINTER(abi.RansacResult), vp, C.c_uint32]
     lib.mulls_coarse_reg_ransac_indexed.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), vp, vp, C.c_uint32, C.POINTER(abi.RansacParams),
                                                     C.POINTER(abi.RansacResult), vp, C.c_uint32]
+    lib.mulls_sor_default_params.argtypes = [C.POINTER(abi.SorParams)]
+    lib.mulls_sor_default_params.restype = None
+    lib.mulls_sor_filter.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.SorParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
+                                     C.POINTER(abi.SorReport)]
     lib.mulls_io_read_kitti_bin.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_read_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_write_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_int]
@@ -130,6 +134,7 @@ EXPORTS = [
     "mulls_pack_results", "mulls_icp_batch_sharded", "mulls_pipe_create", "mulls_pipe_destroy", "mulls_pipe_depth", "mulls_pipe_ctx", "mulls_pipe_set_option", "mulls_icp_batch_begin", "mulls_icp_batch_end",
     "mulls_ncc_default_params", "mulls_ncc_correspond",
     "mulls_ransac_default_params", "mulls_coarse_reg_ransac", "mulls_coarse_reg_ransac_indexed",
+    "mulls_sor_default_params", "mulls_sor_filter",
 ]
 
 
@@ -461,6 +466,31 @@ class Context:
             raise MullsError("mulls_coarse_reg_ransac failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
         assert inl[cap] == -1
         return res, inl[: min(res.n_inliers, cap)].copy()
+
+    # --- statistical outlier removal ---------------------------------------------------------------------------------
+    def sor_filter(self, pts, params=None, want_dist=False):
+        """CFilter::sor_filter (mulls_sor_filter).  pts: a host cloud (POINT_DTYPE records or raw (n, 48) bytes) or a device-resident abi.Cloud.
+        Returns (kept, kept_idx, report), with the (n,) float32 mean neighbour distances behind them when want_dist: kept are the kept records as raw
+        (n_kept, 48) bytes, kept_idx their ascending indices, report the abi.SorReport."""
+        if isinstance(pts, abi.Cloud):
+            c, raw = pts, None
+        else:
+            raw = abi.records(pts)
+            c = abi.Cloud()
+            c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+        n = c.n
+        p = params if params is not None else abi.sor_params()
+        out = np.zeros((n + 1, abi.POINT_BYTES), np.uint8)
+        idx = np.full(n + 1, -1, np.int32)  # one slot past n: checked to be left alone
+        dist = np.zeros(n, np.float32) if want_dist else None
+        rep, n_out = abi.SorReport(), C.c_uint32(0)
+        rc = self.lib.mulls_sor_filter(self.h, C.byref(c), C.byref(p), out.ctypes.data_as(C.c_void_p), n, C.byref(n_out), idx.ctypes.data_as(C.c_void_p), n,
+                                       dist.ctypes.data_as(C.c_void_p) if want_dist else None, C.byref(rep))
+        if rc != 0:
+            raise MullsError("mulls_sor_filter failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        assert idx[n] == -1 and n_out.value <= n
+        res = (out[: n_out.value].copy(), idx[: n_out.value].copy(), rep)
+        return res + (dist,) if want_dist else res
 
     # --- stage-level entry points --------------------------------------------------------------------------------
     def motion_compensate(self, pts, Tran, s_ambiguous_thre=0.0):
