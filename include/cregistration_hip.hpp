@@ -733,6 +733,67 @@ inline bool sor_filter(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out, int 
 	return 1;
 }
 
+// CFilter<PointT>::non_max_suppress (include/common/cfilter.hpp:1183-1240 and :1243-1312), verbatim signatures and defaults: the thinning of the key points
+// in front of the global registration (test/mulls_reg.cpp:147-148) and of loop closure (test/mulls_slam.cpp:462) in one device call
+// (mulls_non_max_suppress).  The binding is one early return at the top of each member function:
+//     #ifdef MULLS_USE_HIP
+//         return lo::hip::non_max_suppress<PointT>(cloud_in_out, non_max_radius, kd_tree_already_built, built_tree);
+//     #endif
+// In place: the cloud becomes the kept points, in visiting order.  Out of place: cloud_in is left sorted, as upstream's std::sort leaves it, and the kept
+// points are appended to cloud_out (upstream push_backs).  Both return false and touch nothing below 10 points.  distance_adaptive_on (set by no upstream
+// call site) and kd_tree_already_built (upstream would query a tree over the unsorted cloud with sorted indices; mulls_slam.cpp:462 passes false) throw.
+// A NaN key (normal[3]), on which upstream's sort is undefined, throws too, as do non-finite coordinates.
+template <typename PointT>
+inline bool non_max_suppress(typename pcl::PointCloud<PointT>::Ptr &cloud_in, typename pcl::PointCloud<PointT>::Ptr &cloud_out, float nms_radius,
+							 bool distance_adaptive_on = false, float unit_dist = 35.0, bool kd_tree_already_built = false,
+							 const typename pcl::search::KdTree<PointT>::Ptr &built_tree = NULL)
+{
+	(void)unit_dist, (void)built_tree;
+	if (distance_adaptive_on || kd_tree_already_built)
+		throw std::runtime_error("lo::hip::non_max_suppress: distance_adaptive_on and kd_tree_already_built are not supported");
+	if (cloud_in->points.size() < 10) // :1251-1253
+		return false;
+	mulls_ctx *ctx = thread_context();
+	const mulls_cloud in = borrow(cloud_in);
+	mulls_nms_params P;
+	mulls_nms_default_params(&P);
+	P.non_max_radius = nms_radius;
+	std::vector<unsigned char> raw((size_t)in.n * MULLS_POINT_BYTES);
+	std::vector<int32_t> order(in.n);
+	uint32_t n_out = 0;
+	const int rc = mulls_non_max_suppress(ctx, &in, &P, raw.data(), in.n, &n_out, nullptr, 0, order.data(), nullptr);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_non_max_suppress failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	typename std::remove_reference<decltype(cloud_in->points)>::type sorted(in.n);
+	for (uint32_t i = 0; i < in.n; i++)
+		sorted[i] = cloud_in->points[order[i]]; // :1255
+	cloud_in->points.swap(sorted);
+	take_cloud<PointT>(cloud_out, raw, n_out, true); // :1280
+	return true;
+}
+template <typename PointT>
+inline bool non_max_suppress(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out, float non_max_radius, bool kd_tree_already_built = false,
+							 const typename pcl::search::KdTree<PointT>::Ptr &built_tree = NULL)
+{
+	(void)built_tree;
+	if (kd_tree_already_built)
+		throw std::runtime_error("lo::hip::non_max_suppress: kd_tree_already_built is not supported");
+	if (cloud_in_out->points.size() < 10) // :1189-1191
+		return false;
+	mulls_ctx *ctx = thread_context();
+	const mulls_cloud in = borrow(cloud_in_out);
+	mulls_nms_params P;
+	mulls_nms_default_params(&P);
+	P.non_max_radius = non_max_radius;
+	std::vector<unsigned char> raw((size_t)in.n * MULLS_POINT_BYTES);
+	uint32_t n_out = 0;
+	const int rc = mulls_non_max_suppress(ctx, &in, &P, raw.data(), in.n, &n_out, nullptr, 0, nullptr, nullptr);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_non_max_suppress failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	take_cloud<PointT>(cloud_in_out, raw, n_out, false); // :1230
+	return true;
+}
+
 // CFilter<PointT>::extract_semantic_pts (include/common/cfilter.hpp:2295-2413), verbatim signature: the whole chain in one device call
 // (mulls_extract_features).  The binding is one early return at the top of the member function:
 //     #ifdef MULLS_USE_HIP

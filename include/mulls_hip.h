@@ -717,6 +717,58 @@ void mulls_sor_default_params(mulls_sor_params *p);
 int mulls_sor_filter(mulls_ctx *ctx, const mulls_cloud *cloud, const mulls_sor_params *params, void *out, uint32_t cap, uint32_t *n_out, int32_t *kept_idx,
 					 uint32_t idx_cap, float *mean_dist, mulls_sor_report *report);
 
+/* ---- key-point non-maximum suppression: CFilter<PointT>::non_max_suppress (include/common/cfilter.hpp:1183-1240 and :1243-1312) ----
+ * The thinning of the key points in front of the global registration (test/mulls_reg.cpp:145-149, both clouds, radius 0.25 * pca_neigh_r) and of every new
+ * submap's pc_vertex in front of loop closure (test/mulls_slam.cpp:462).  Lines marked [UP] are upstream's, [PCL] restate pcl::search::KdTree::radiusSearch
+ * (FLANN's L2_Simple) from memory — PCL is not available where this library is built and tested, nothing was compared with it —, [LIB] are this library's.
+ * tests/nms_restated.py restates all of it in numpy; DESIGN.md section 7.3 has the same list with its reasons.
+ *   gate     [UP :1189-1191] n < 10: nothing happens.  The cloud is returned unchanged and in input order (kept_idx and order are the identity),
+ *            report.ran = 0.
+ *   key      [UP :1193] normal[3], the float at byte 28 of the 48-byte record.
+ *   order    [UP + this toolchain] std::sort with the comparator a.key > b.key.  Equal keys fall as this toolchain's std::sort leaves them: the keys
+ *            are sorted on the host as (key, index) pairs by that std::sort (the lines mulls_classify_nground runs for its class clouds).  The
+ *            permutation depends on the keys and on n only.
+ *   walk     [UP :1211-1228] visit in that order; the first unvisited point is kept, every point within the radius of a kept point is erased: a point
+ *            is kept exactly when no earlier kept point lies within the radius.
+ *   radius   [PCL / FLANN] d2 < r2, strict; r2 = (float)((double)r * (double)r); d2 = (dx dx + dy dy) + dz dz in float, no contraction.  A negative
+ *            radius follows this arithmetic and so acts as |r|; radius 0 keeps everything, in sorted order.
+ *   output   [UP :1230] the kept records, byte for byte, in visiting order.
+ *   refused  [LIB] a NaN key: MULLS_E_INVALID (upstream's comparator is then no strict weak order and its sort undefined).  A non-finite coordinate or
+ *            radius, a bad stride: MULLS_E_INVALID.  More than MULLS_NMS_MAX_POINTS = 2^18 points: MULLS_E_UNSUPPORTED.  n == 0: MULLS_OK, nothing kept.
+ * Not offered: the distance_adaptive_on mode of the out-of-place overload (:1285-1295; no upstream call site sets it); kd_tree_already_built = true
+ * (upstream would query a tree built over the unsorted cloud with sorted indices; the one call site that names the argument passes false); the
+ * pca_feature_t overload (:1314; its only caller is the commented-out detect_key_pts).
+ * Two paths give the same bytes.  Path 1: the whole suppression in one workgroup with the cloud and a hashed cell grid in LDS, at most
+ * MULLS_NMS_LDS_MAX_POINTS = 4096 points (32 bytes of LDS per point and 4 per bucket: 144 KiB of the 160 KiB of a CU).  Path 2: the kernels of
+ * mulls_classify_nground's class-cloud suppression, any n up to the limit.  Path 0 takes path 2 at every size: path 1 measures slower (0.65 - 0.80 ms
+ * against 0.20 - 0.25 ms per call on the demo key points and at 4096 points, profiles/nms_kernel_stats.txt) and runs on request only. */
+#define MULLS_NMS_MAX_POINTS (1u << 18)
+#define MULLS_NMS_LDS_MAX_POINTS 4096u
+typedef struct mulls_nms_params
+{
+	float non_max_radius; /* [0.25] */
+	int32_t path;		  /* 0 = the library chooses, 1 = one workgroup, 2 = multi-launch.  The bytes of every output are the same on each path;
+							 1 beyond its size limit: MULLS_E_UNSUPPORTED */
+} mulls_nms_params;
+
+typedef struct mulls_nms_report
+{
+	uint32_t n_in, n_kept;
+	int32_t ran;	 /* 0: below the gate, nothing done */
+	int32_t path;	 /* the path taken (0 when ran == 0) */
+	uint32_t rounds; /* fixed-point rounds until every point was decided: at most the depth of the longest suppression chain */
+	float ms_total;	 /* wall time of the call */
+} mulls_nms_report;
+
+void mulls_nms_default_params(mulls_nms_params *p); /* radius 0.25, path 0 */
+/* returns MULLS_OK or MULLS_E_* (the list above).  cloud: host memory (48-byte records at any stride that is a multiple of 4 and at least 48) or a
+ * device-resident cloud of 48-byte records (mulls_map_cloud, mulls_block_cloud); it is never modified.  All outputs are host memory and any may be NULL
+ * (out with cap 0, kept_idx with idx_cap 0).  out: the kept records in visiting order, at most cap of them; *n_out: the full count of kept records;
+ * kept_idx: their indices into the input, in visiting order, at most idx_cap; order: n ints, the whole visiting permutation (order[i] = the input index
+ * of the point visited i-th: what the out-of-place overload leaves cloud_in sorted by). */
+int mulls_non_max_suppress(mulls_ctx *ctx, const mulls_cloud *cloud, const mulls_nms_params *params, void *out, uint32_t cap, uint32_t *n_out, int32_t *kept_idx,
+						   uint32_t idx_cap, int32_t *order, mulls_nms_report *report);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

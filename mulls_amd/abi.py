@@ -357,6 +357,28 @@ def sor_params(mean_k=20, std_mul=2.0):
     return p
 
 
+class NmsParams(C.Structure):
+    """mulls_nms_params: non_max_suppress' radius (cfilter.hpp:1183) and which path runs it"""
+
+    _fields_ = [("non_max_radius", C.c_float), ("path", C.c_int32)]
+
+
+class NmsReport(C.Structure):
+    """mulls_nms_report"""
+
+    _fields_ = [("n_in", C.c_uint32), ("n_kept", C.c_uint32), ("ran", C.c_int32), ("path", C.c_int32), ("rounds", C.c_uint32), ("ms_total", C.c_float)]
+
+
+NMS_MAX_POINTS = 1 << 18  # MULLS_NMS_MAX_POINTS
+NMS_LDS_MAX_POINTS = 4096  # MULLS_NMS_LDS_MAX_POINTS: the one-workgroup path's limit
+
+
+def nms_params(non_max_radius=0.25, path=0):
+    p = NmsParams()
+    p.non_max_radius, p.path = float(non_max_radius), int(path)
+    return p
+
+
 def records(a):
     """Any point array (POINT_DTYPE records or raw (n, 48) bytes) as contiguous raw (n, 48) uint8 records, every byte kept."""
     a = np.asarray(a)

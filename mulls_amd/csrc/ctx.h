@@ -23,6 +23,7 @@ struct mulls_block;
 struct mulls_ncc_scratch;
 struct mulls_ransac_scratch;
 struct mulls_sor_scratch;
+struct mulls_nms_scratch;
 
 // A few host threads that SLEEP between their jobs (condition variable), for the staging gather of mulls_icp_batch.  An OpenMP team keeps spinning after its
 // parallel region; 32 spinning threads inside a container with a CPU quota get the whole process throttled for the rest of the scheduler period: every fourth
@@ -82,6 +83,7 @@ struct mulls_ctx
 	mulls_ncc_scratch *ncc = nullptr; // mulls_ncc_correspond's device arena and pinned buffer (ncc.cpp; grow-only)
 	mulls_ransac_scratch *ransac = nullptr; // mulls_coarse_reg_ransac's (ransac.cpp; grow-only)
 	mulls_sor_scratch *sor = nullptr; // mulls_sor_filter's (sor.cpp; grow-only)
+	mulls_nms_scratch *nms = nullptr; // mulls_non_max_suppress's (nms.cpp; grow-only)
 	int nn_mode = 0;   // 0 auto, 1 LDS-tiled brute force, 2 uniform grid in global memory, 3 (and 4) uniform grid staged in LDS
 };
 
@@ -238,6 +240,7 @@ bool mulls_is_map_memory(const mulls_ctx *ctx, const void *p, size_t bytes);
 void mulls_ncc_release(mulls_ctx *ctx); // frees ctx->ncc (ncc.cpp)
 void mulls_ransac_release(mulls_ctx *ctx); // frees ctx->ransac (ransac.cpp)
 void mulls_sor_release(mulls_ctx *ctx); // frees ctx->sor (sor.cpp)
+void mulls_nms_release(mulls_ctx *ctx); // frees ctx->nms (nms.cpp)
 
 // device-resident feature clouds of one scan (mulls_extract_features_resident, ground.cpp): 48-byte records, one buffer
 struct mulls_block

@@ -263,6 +263,7 @@ extern "C"
 		mulls_ncc_release(ctx);
 		mulls_ransac_release(ctx);
 		mulls_sor_release(ctx);
+		mulls_nms_release(ctx);
 		while (!ctx->maps.empty()) // local maps die with their context (mulls_map_destroy unregisters them)
 			mulls_map_destroy(ctx, ctx->maps.back());
 		while (!ctx->blocks.empty()) // ... and so do feature blocks

@@ -113,6 +113,10 @@ def load():
     lib.mulls_sor_default_params.restype = None
     lib.mulls_sor_filter.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.SorParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
                                      C.POINTER(abi.SorReport)]
+    lib.mulls_nms_default_params.argtypes = [C.POINTER(abi.NmsParams)]
+    lib.mulls_nms_default_params.restype = None
+    lib.mulls_non_max_suppress.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.NmsParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
+                                           C.POINTER(abi.NmsReport)]
     lib.mulls_io_read_kitti_bin.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_read_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_write_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_int]
@@ -135,6 +139,7 @@ EXPORTS = [
     "mulls_ncc_default_params", "mulls_ncc_correspond",
     "mulls_ransac_default_params", "mulls_coarse_reg_ransac", "mulls_coarse_reg_ransac_indexed",
     "mulls_sor_default_params", "mulls_sor_filter",
+    "mulls_nms_default_params", "mulls_non_max_suppress",
 ]
 
 
@@ -491,6 +496,31 @@ class Context:
         assert idx[n] == -1 and n_out.value <= n
         res = (out[: n_out.value].copy(), idx[: n_out.value].copy(), rep)
         return res + (dist,) if want_dist else res
+
+    # --- key-point non-maximum suppression ---------------------------------------------------------------------------
+    def non_max_suppress(self, pts, radius=0.25, path=0):
+        """CFilter::non_max_suppress (mulls_non_max_suppress).  pts: a host cloud (POINT_DTYPE records or raw (n, 48) bytes) or a device-resident abi.Cloud.
+        Returns (kept, kept_idx, order, report): the kept records as raw (n_kept, 48) bytes in visiting order, their indices into the input, the whole
+        visiting permutation (the identity under the gate of 10 points), the abi.NmsReport.  path: 0 = the library chooses (the multi-launch path),
+        1 = one workgroup (at most abi.NMS_LDS_MAX_POINTS points), 2 = multi-launch; the outputs are the same bytes."""
+        if isinstance(pts, abi.Cloud):
+            c, raw = pts, None
+        else:
+            raw = abi.records(pts)
+            c = abi.Cloud()
+            c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+        n = c.n
+        p = abi.nms_params(radius, path)
+        out = np.zeros((n + 1, abi.POINT_BYTES), np.uint8)
+        idx = np.full(n + 1, -1, np.int32)  # one slot past n: checked to be left alone
+        order = np.full(n + 1, -1, np.int32)
+        rep, n_out = abi.NmsReport(), C.c_uint32(0)
+        rc = self.lib.mulls_non_max_suppress(self.h, C.byref(c), C.byref(p), out.ctypes.data_as(C.c_void_p), n, C.byref(n_out), idx.ctypes.data_as(C.c_void_p), n,
+                                             order.ctypes.data_as(C.c_void_p), C.byref(rep))
+        if rc != 0:
+            raise MullsError("mulls_non_max_suppress failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        assert idx[n] == -1 and order[n] == -1 and n_out.value <= n
+        return out[: n_out.value].copy(), idx[: n_out.value].copy(), order[:n].copy(), rep
 
     # --- stage-level entry points --------------------------------------------------------------------------------
     def motion_compensate(self, pts, Tran, s_ambiguous_thre=0.0):

@@ -1,11 +1,12 @@
 """Pairwise registration of two point clouds with the library, stage for stage what test/mulls_reg.cpp does (script/run_mulls_reg.sh):
 read -> voxel_downsample (cloud_*_down_res, 0 = off as in run_mulls_reg.sh) -> fast_ground_filter -> classify_nground_pts per cloud -> the
-cloud with more down-sampled feature points is the target -> with --is_global_reg (the reference's default: true) the global coarse registration,
-find_feature_correspondence_ncc on the two key-point clouds -> coarse_reg_ransac with noise_bound = 4 x keypoint_nms_radius (test/mulls_reg.cpp:170-179;
+cloud with more down-sampled feature points is the target -> with --is_global_reg (the reference's default: true) the global coarse registration:
+non_max_suppress of both key-point clouds with keypoint_nms_radius = 0.25 x pca_neighbor_radius (test/mulls_reg.cpp:145-149; mulls_non_max_suppress — the
+classification does not thin the key points: upstream's detect_key_pts is commented out and vertex_curvature_non_max_radius is unused),
+find_feature_correspondence_ncc on the two thinned clouds -> coarse_reg_ransac with noise_bound = 4 x keypoint_nms_radius (test/mulls_reg.cpp:170-179;
 mulls_ncc_correspond -> mulls_coarse_reg_ransac_indexed), whose transform is the initial guess (the identity when it fails, as upstream leaves init_mat)
 -> mm_lls_icp -> the source's pc_down, transformed, written out.  Flags carry the reference's names and defaults (test/mulls_reg.cpp:24-60).  Not here:
-TEASER++ (--teaser_on is accepted and answered with the RANSAC solver), the second non_max_suppress of the key points with keypoint_nms_radius
-(:145-149; the classification has already thinned them with the six times larger vertex_curvature_non_max_radius), the viewers.
+TEASER++ (--teaser_on is accepted and answered with the RANSAC solver), the viewers.
 
     python tools/mulls_reg.py --point_cloud_1_path a.pcd --point_cloud_2_path b.pcd --output_point_cloud_path b_reg.pcd
 """
@@ -119,6 +120,14 @@ def register(ctx, scan1, scan2, F):
     (tgt_full, src_down, source) = (f1, d2, 2) if n1 > n2 else (f2, d1, 1)
     init_mat = np.eye(4)
     if F.is_global_reg:
+        # test/mulls_reg.cpp:145-149: both blocks' pc_vertex, in place (the sizes above, which chose the target, were taken before)
+        keypoint_nms_radius = 0.25 * F.pca_neighbor_radius
+        kpts = []
+        for which, cloud in (("target", tgt_full[5]), ("source", src_down[5])):
+            kept = ctx.non_max_suppress(cloud, keypoint_nms_radius)[0]
+            print("non_max_suppress: %s key points %d -> %d" % (which, len(cloud), len(kept)))
+            kpts.append(kept)
+        tgt_full[5], src_down[5] = kpts
         init_mat = global_registration(ctx, tgt_full[5], src_down[5], F)
     pair = abi.PairData([abi.points_of(t) for t in tgt_full], [abi.points_of(s) for s in src_down],
                         init_guess=init_mat, tgt_bound=scan_bound(abi.as_points(scan1 if source == 2 else scan2)) if len(scan1) and len(scan2) else None)
