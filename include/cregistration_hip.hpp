@@ -640,7 +640,7 @@ inline bool voxel_downsample(const typename pcl::PointCloud<PointT>::Ptr &cloud_
 //     #endif
 // The matched key points are appended to target_corrs / source_corrs (upstream push_backs).  With fixed_num_corr, pairs at exactly equal descriptor distances
 // come in ascending (target index, source index) order — upstream's unstable std::sort leaves that order open (include/mulls_hip.h).  The solver behind it
-// is coarse_reg_ransac below; coarse_reg_teaser (TEASER++) stays the caller's.
+// is coarse_reg_teaser or coarse_reg_ransac below.
 template <typename PointT>
 inline bool find_feature_correspondence_ncc(const typename pcl::PointCloud<PointT>::Ptr &target_kpts, const typename pcl::PointCloud<PointT>::Ptr &source_kpts,
 											typename pcl::PointCloud<PointT>::Ptr &target_corrs, typename pcl::PointCloud<PointT>::Ptr &source_corrs,
@@ -674,8 +674,7 @@ inline bool find_feature_correspondence_ncc(const typename pcl::PointCloud<Point
 //         return lo::hip::coarse_reg_ransac<PointT>(target_pts, source_pts, tran_mat, noise_bound, min_inlier_num, max_iter_num);
 //     #endif
 // Returns upstream's 1 (reliable) / 0 (need check) / -1 (failed); tran_mat is written only when the result is not -1, as upstream.  Where PCL's result rests
-// on Eigen's decompositions this library defines its own (include/mulls_hip.h): the transform is the library's, not PCL's bits.  coarse_reg_teaser
-// (TEASER++) stays the caller's.
+// on Eigen's decompositions this library defines its own (include/mulls_hip.h): the transform is the library's, not PCL's bits.
 template <typename PointT>
 inline int coarse_reg_ransac(const typename pcl::PointCloud<PointT>::Ptr &target_pts, const typename pcl::PointCloud<PointT>::Ptr &source_pts,
 							 Eigen::Matrix4d &tran_mat, float noise_bound = 0.2, int min_inlier_num = 8, int max_iter_num = 20000)
@@ -691,6 +690,36 @@ inline int coarse_reg_ransac(const typename pcl::PointCloud<PointT>::Ptr &target
 	const int rc = mulls_coarse_reg_ransac(ctx, &tgt, &src, &P, &R, nullptr, 0);
 	if (rc != MULLS_OK)
 		throw std::runtime_error(std::string("mulls_coarse_reg_ransac failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	if (R.status >= 0)
+		for (int c = 0; c < 4; c++)
+			for (int r = 0; r < 4; r++)
+				tran_mat(r, c) = R.T[c * 4 + r];
+	return R.status;
+}
+
+// CRegistration<PointT>::coarse_reg_teaser (include/common/cregistration.hpp:664-759), verbatim signature and defaults: the TEASER solver of the global (coarse)
+// registration every shipped configuration selects (test/mulls_reg.cpp:177, test/mulls_slam.cpp:537) in one call (mulls_coarse_reg_teaser).  The binding is
+// one early return at the top of the member function, outside upstream's `#if TEASER_ON`: the bridge always solves, where upstream compiles the body out
+// and returns -1 without TEASER++:
+//     #ifdef MULLS_USE_HIP
+//         return lo::hip::coarse_reg_teaser<PointT>(target_pts, source_pts, tran_mat, noise_bound, min_inlier_num);
+//     #endif
+// Returns upstream's 1 (reliable) / 0 (need check) / -1 (failed; also unequal sizes and three pairs or fewer); tran_mat is untouched on -1, as upstream.
+// The maximum clique is the lexicographically smallest one and the rotation fit is the library's (include/mulls_hip.h): the transform is not TEASER++'s bits.
+template <typename PointT>
+inline int coarse_reg_teaser(const typename pcl::PointCloud<PointT>::Ptr &target_pts, const typename pcl::PointCloud<PointT>::Ptr &source_pts,
+							 Eigen::Matrix4d &tran_mat, float noise_bound = 0.2, int min_inlier_num = 8)
+{
+	mulls_ctx *ctx = thread_context();
+	const mulls_cloud tgt = borrow(target_pts), src = borrow(source_pts);
+	mulls_teaser_params P;
+	mulls_teaser_default_params(&P);
+	P.noise_bound = noise_bound;
+	P.min_inlier_num = min_inlier_num;
+	mulls_teaser_result R;
+	const int rc = mulls_coarse_reg_teaser(ctx, &tgt, &src, &P, &R, nullptr, 0);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_coarse_reg_teaser failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
 	if (R.status >= 0)
 		for (int c = 0; c < 4; c++)
 			for (int r = 0; r < 4; r++)

@@ -587,7 +587,7 @@ int mulls_voxel_downsample(mulls_ctx *ctx, const void *pts, uint32_t n, uint32_t
  * The correspondence stage of the reference's global (coarse) registration (test/mulls_reg.cpp:170-179, test/mulls_slam.cpp:532-540): the key points of two
  * scans (pc_vertex, MULLS_EX_VERTEX) are matched by the L1 distance of their 11-entry "neighbourhood category context" descriptors — the two packed codes
  * encode_stable_points left in normal[0] / normal[1], the intensity normalised by the TARGET's range, normal[3] (curvature) and data[3] (height above
- * ground).  mulls_coarse_reg_ransac(_indexed) below is the solver that consumes the pairs; TEASER++ is not part of this library.
+ * ground).  mulls_coarse_reg_ransac(_indexed) and mulls_coarse_reg_teaser(_indexed) below are the solvers that consume the pairs.
  *   not fixed_num_corr: every target key point i with the first source key point j* at the strictly smallest distance (a row without any distance below
  *     FLT_MAX yields j* = 0), in ascending i; with reciprocal_on only while no other target is strictly closer to j*.
  *   fixed_num_corr: the corr_num smallest of the Nt * Ns distances in ascending order, a pair being skipped once its target or its source point has been
@@ -671,6 +671,78 @@ int mulls_coarse_reg_ransac(mulls_ctx *ctx, const mulls_cloud *tgt_pts, const mu
  * index outside its cloud. */
 int mulls_coarse_reg_ransac_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const int32_t *tgt_idx, const int32_t *src_idx,
 									uint32_t n_corr, const mulls_ransac_params *params, mulls_ransac_result *result, int32_t *inliers, uint32_t cap);
+
+/* ---- TEASER coarse registration: CRegistration<PointT>::coarse_reg_teaser (include/common/cregistration.hpp:664-759) ----
+ * The solver every shipped configuration selects (--teaser_based_global_registration_on=true) between mulls_ncc_correspond's pairs and mulls_icp's initial
+ * guess.  Upstream's body is one call of TEASER++'s RobustRegistrationSolver (no scale estimation, maximum clique, GNC-TLS rotation).  TEASER++ is not
+ * available where this library is built and tested, so nothing below was checked against it: the lines marked [TEASER] restate TEASER++ as of the
+ * reference's date from memory (registration.cc, graph.cc), the lines marked [LIB] are this library's own arithmetic where TEASER++'s result rests on PMC's
+ * thread timing or on Eigen's decompositions, which cannot be pinned.  tests/teaser_restated.py restates all of it independently in numpy, bit for bit.
+ * DESIGN.md section 7.4 has the same list with its reasons.  Correspondence i pairs point i of each cloud (s_i: source, t_i: target).  All arithmetic is
+ * double on coordinates widened from float, only + - * / sqrt, no contraction, every sum in the stated order.
+ *   outcomes   [upstream] unequal sizes or N <= 3: MULLS_OK with status -1 (upstream returns -1 there).  [LIB] N > 8192: MULLS_E_UNSUPPORTED.
+ *   graph      [TEASER] vertices: the N pairs; edge {i, j} iff | |s_j - s_i| - |t_j - t_i| | <= beta, beta = 2 (double)noise_bound sqrt(cbar2), cbar2 = 1
+ *              (:703), |d| = sqrt((dx dx + dy dy) + dz dz).  A NaN comparison gives no edge.  n_edges counts them; max_core is the largest core number.
+ *   clique     [LIB] TEASER++ takes *a* maximum clique from PMC, which one depends on thread timing.  This library takes THE LEXICOGRAPHICALLY SMALLEST
+ *              MAXIMUM CLIQUE (ascending index lists compared), which no search order can change.  The search is exact up to clique_node_budget visited
+ *              nodes; beyond, the largest clique found so far by a deterministic single-threaded search is used and clique_exact = 0 (that clique does
+ *              depend on the search: teaser_host.h).  kcore_heuristic_threshold (:710) is not used: upstream leaves the mode at exact.  A graph without
+ *              an edge has the clique {0}; clique_size <= 1: status -1.  clique_nodes is the search's effort, not part of the definition.
+ *   measures   [TEASER] clique vertices c_0 < ... < c_(C-1); measurement k runs over the pairs a < b, a outer, b inner: a_k = s_cb - s_ca,
+ *              b_k = t_cb - t_ca; M = C (C - 1) / 2.
+ *   rotation   [TEASER] GNC-TLS: at most 100 iterations, factor 1.4, cost threshold 0.005 (:705-711); nb2 = noise_bound^2, 1e-2 when below 1e-16; weights 1,
+ *              prev_cost = +inf.  Iteration i: (1) R = fit of the weighted measurements; (2) r_k = |b_k - R a_k|^2, each row (R0 ax + R1 ay) + R2 az,
+ *              (dx dx + dy dy) + dz dz; (3) i = 0 only: mu = 1 / ((2 max r) / nb2 - 1), the loop ends if mu <= 0 (cost stays 0, the weights 1);
+ *              (4) cost = sum of w_k r_k with the weights before the update; (5) w_k = 0 if r_k >= ((mu + 1) / mu) nb2, 1 if r_k <= (mu / (mu + 1)) nb2,
+ *              else sqrt(((nb2 mu) (mu + 1)) / r_k) - mu; (6) the loop ends if |cost - prev_cost| < 0.005, else mu = 1.4 mu, prev_cost = cost.
+ *              gnc_iterations = fits made.  Rotation inliers: w_k >= 0.5.
+ *              [LIB] the fit: H[p][q] = sum of (w_k a_k[p]) b_k[q]; Horn's symmetric 4 x 4 of H, exactly 10 sweeps of cyclic Jacobi, the column of the
+ *              largest diagonal entry (the first among equals) as a unit quaternion, its rotation matrix — mulls_coarse_reg_ransac's steps, kept in double.
+ *              [LIB] H's nine sums and the cost: 4096 strided partial sums (partial p adds k = p, p + 4096, ... in ascending order, from 0), then the
+ *              pairwise tree p[t] += p[t + s], s = 2048, ..., 1.
+ *   translation [TEASER] per axis x_c = t_c - ((R0 sx + R1 sy) + R2 sz) over the C clique points and TEASER's scalar TLS estimator with range noise_bound:
+ *              the 2C endpoints x - range (opening), x + range (closing) sorted by (value, opening before closing, index); swept in that order with the
+ *              running sums sw, swx, swx2 (w = 1 / range^2; + w, + w x, + (w x) x when opening, - when closing) and the excluded ranges' sum (C times
+ *              range added up, - range when opening, + when closing); candidate xhat = swx / sw, cost ((sw xhat) xhat + swx2 - (2 swx) xhat) + excluded;
+ *              the first strictly smallest cost wins, a NaN never, none: 0.  Translation inliers: |x_c - that| <= range on all three axes.  Serial and at
+ *              most 8192 values: it runs on the host on one download of R and the clique's points.
+ *   outcome    [upstream] n = the number of rotation inliers — MEASUREMENTS, not pairs, as TEASER++'s getRotationInliers() of that date returns them: a
+ *              clique of 5 reaches min_inlier_num = 8.  A quirk, kept.  status 1 if n >= 2 min_inlier_num, 0 if n >= min_inlier_num, else -1. */
+#define MULLS_TEASER_DEFAULT_NODE_BUDGET (1ull << 28)
+typedef struct mulls_teaser_params
+{
+	float noise_bound;			 /* [0.2]  metres (cregistration.hpp:666) */
+	int32_t min_inlier_num;		 /* [8]    */
+	uint64_t clique_node_budget; /* [MULLS_TEASER_DEFAULT_NODE_BUDGET] nodes the exact clique search may visit */
+} mulls_teaser_params;
+
+typedef struct mulls_teaser_result
+{
+	int32_t status;		   /* upstream's return: 1 reliable, 0 need check, -1 failed */
+	int32_t max_core;	   /* largest core number of the graph */
+	uint64_t n_edges;
+	int32_t clique_size;
+	int32_t clique_exact;  /* 1: the search finished within the budget */
+	uint64_t clique_nodes; /* nodes the search visited */
+	int32_t gnc_iterations;
+	int32_t n_rotation_inliers; /* measurements with weight >= 0.5: upstream's inlier count */
+	int32_t n_translation_inliers;
+	int32_t reserved;
+	double cost;		   /* the last GNC iteration's */
+	double search_seconds; /* wall time of the host clique search: a measurement, not a result */
+	double T[16];		   /* column-major; written when status >= 0, the identity otherwise */
+} mulls_teaser_result;
+
+void mulls_teaser_default_params(mulls_teaser_params *p);
+/* returns MULLS_OK or MULLS_E_*: MULLS_E_INVALID for a non-finite or negative noise_bound or a bad stride (mulls_coarse_reg_ransac's rule);
+ * MULLS_E_UNSUPPORTED above 8192 pairs.  clique: the clique's pair indices, ascending, at most cap of them (NULL / 0 allowed).  The clouds are host memory
+ * (any stride that is a multiple of 4 and at least 16) or device-resident clouds of 48-byte records. */
+int mulls_coarse_reg_teaser(mulls_ctx *ctx, const mulls_cloud *tgt_pts, const mulls_cloud *src_pts, const mulls_teaser_params *params,
+							mulls_teaser_result *result, int32_t *clique, uint32_t cap);
+/* the same solver on tgt_kpts[tgt_idx[k]] <-> src_kpts[src_idx[k]], k < n_corr, gathered on the device as mulls_coarse_reg_ransac_indexed does (clique
+ * entries are positions k in the lists).  MULLS_E_INVALID for an index outside its cloud. */
+int mulls_coarse_reg_teaser_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const int32_t *tgt_idx, const int32_t *src_idx,
+									uint32_t n_corr, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique, uint32_t cap);
 
 /* ---- statistical outlier removal: CFilter<PointT>::sor_filter (include/common/cfilter.hpp:204-247) ----
  * The filter of the merged map mulls_slam writes at the end of a run (test/mulls_slam.cpp:1009, sor_filter(pc_map_merged, 20, 2.0) under --map_filter_on).

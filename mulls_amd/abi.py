@@ -338,6 +338,29 @@ def ransac_params(noise_bound=0.2, min_inlier_num=8, max_iter_num=20000, refine=
     return p
 
 
+class TeaserParams(C.Structure):
+    """mulls_teaser_params: coarse_reg_teaser's arguments behind the clouds (cregistration.hpp:666), and the clique search's node budget"""
+
+    _fields_ = [("noise_bound", C.c_float), ("min_inlier_num", C.c_int32), ("clique_node_budget", C.c_uint64)]
+
+
+class TeaserResult(C.Structure):
+    """mulls_teaser_result"""
+
+    _fields_ = [("status", C.c_int32), ("max_core", C.c_int32), ("n_edges", C.c_uint64), ("clique_size", C.c_int32), ("clique_exact", C.c_int32),
+                ("clique_nodes", C.c_uint64), ("gnc_iterations", C.c_int32), ("n_rotation_inliers", C.c_int32), ("n_translation_inliers", C.c_int32),
+                ("reserved", C.c_int32), ("cost", C.c_double), ("search_seconds", C.c_double), ("T", C.c_double * 16)]
+
+
+TEASER_DEFAULT_NODE_BUDGET = 1 << 28  # MULLS_TEASER_DEFAULT_NODE_BUDGET
+
+
+def teaser_params(noise_bound=0.2, min_inlier_num=8, clique_node_budget=TEASER_DEFAULT_NODE_BUDGET):
+    p = TeaserParams()
+    p.noise_bound, p.min_inlier_num, p.clique_node_budget = float(noise_bound), int(min_inlier_num), int(clique_node_budget)
+    return p
+
+
 class SorParams(C.Structure):
     """mulls_sor_params: sor_filter's arguments behind the cloud (cfilter.hpp:204)"""
 

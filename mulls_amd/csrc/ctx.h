@@ -22,6 +22,7 @@ struct mulls_map;
 struct mulls_block;
 struct mulls_ncc_scratch;
 struct mulls_ransac_scratch;
+struct mulls_teaser_scratch;
 struct mulls_sor_scratch;
 struct mulls_nms_scratch;
 
@@ -82,6 +83,7 @@ struct mulls_ctx
 	uint32_t cl_rounds_hint[2] = {4, 8}; // rounds the promotion loop / the suppression rounds needed in the previous call: this call's first batch
 	mulls_ncc_scratch *ncc = nullptr; // mulls_ncc_correspond's device arena and pinned buffer (ncc.cpp; grow-only)
 	mulls_ransac_scratch *ransac = nullptr; // mulls_coarse_reg_ransac's (ransac.cpp; grow-only)
+	mulls_teaser_scratch *teaser = nullptr; // mulls_coarse_reg_teaser's (teaser.cpp; grow-only)
 	mulls_sor_scratch *sor = nullptr; // mulls_sor_filter's (sor.cpp; grow-only)
 	mulls_nms_scratch *nms = nullptr; // mulls_non_max_suppress's (nms.cpp; grow-only)
 	int nn_mode = 0;   // 0 auto, 1 LDS-tiled brute force, 2 uniform grid in global memory, 3 (and 4) uniform grid staged in LDS
@@ -239,6 +241,7 @@ int grow_pinned(mulls_ctx *ctx, T **p, size_t *cap, size_t need, unsigned flags)
 bool mulls_is_map_memory(const mulls_ctx *ctx, const void *p, size_t bytes);
 void mulls_ncc_release(mulls_ctx *ctx); // frees ctx->ncc (ncc.cpp)
 void mulls_ransac_release(mulls_ctx *ctx); // frees ctx->ransac (ransac.cpp)
+void mulls_teaser_release(mulls_ctx *ctx); // frees ctx->teaser (teaser.cpp)
 void mulls_sor_release(mulls_ctx *ctx); // frees ctx->sor (sor.cpp)
 void mulls_nms_release(mulls_ctx *ctx); // frees ctx->nms (nms.cpp)
 

@@ -262,6 +262,7 @@ extern "C"
 			(void)hipHostFree(ctx->scan_pin);
 		mulls_ncc_release(ctx);
 		mulls_ransac_release(ctx);
+		mulls_teaser_release(ctx);
 		mulls_sor_release(ctx);
 		mulls_nms_release(ctx);
 		while (!ctx->maps.empty()) // local maps die with their context (mulls_map_destroy unregisters them)

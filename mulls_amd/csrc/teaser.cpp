@@ -1,0 +1,311 @@
+// teaser.cpp — mulls_coarse_reg_teaser: CRegistration<PointT>::coarse_reg_teaser (cregistration.hpp:664-759), the solver every shipped configuration
+// selects between the key-point matcher (ncc.cpp) and mulls_icp.  Host side: argument checks, staging, the order of the device steps (k_teaser.hip: graph,
+// core numbers, greedy lower bound, compaction, GNC-TLS rotation), the exact clique search on the one sub-matrix that comes down (teaser_host.h), and the
+// serial TLS translation estimate on the clique's points.  include/mulls_hip.h has the definition this file follows.
+#include <chrono>
+
+#include "ctx.h"
+#include "ransac_launch.h" // launch_ransac_gather: x, y, z, data[3] out of device records
+#include "teaser_host.h"
+#include "teaser_launch.h"
+
+// a context's scratch of this entry point: a device arena, the GNC weights (up to C (C - 1) / 2 doubles) and a pinned host buffer, grow-only
+struct mulls_teaser_scratch
+{
+	unsigned char *dev = nullptr, *pin = nullptr;
+	double *weights = nullptr;
+	size_t dev_cap = 0, pin_cap = 0, weights_cap = 0;
+};
+
+void mulls_teaser_release(mulls_ctx *ctx)
+{
+	if (!ctx->teaser)
+		return;
+	staggered_free(ctx->teaser->dev);
+	staggered_free(ctx->teaser->weights);
+	if (ctx->teaser->pin)
+		(void)hipHostFree(ctx->teaser->pin);
+	delete ctx->teaser;
+	ctx->teaser = nullptr;
+}
+
+namespace
+{
+size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+
+bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
+{
+	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * MULLS_POINT_BYTES))
+		return true;
+	hipPointerAttribute_t at;
+	std::memset(&at, 0, sizeof(at));
+	if (hipPointerGetAttributes(&at, c.pts) == hipSuccess)
+		return at.type == hipMemoryTypeDevice;
+	(void)hipGetLastError(); // (an ordinary host pointer: the query reports an error on some runtimes — cleared)
+	return false;
+}
+
+void pack_xyzw(const mulls_cloud &c, const int32_t *idx, uint32_t n, float *out)
+{
+	const unsigned char *p = static_cast<const unsigned char *>(c.pts);
+	for (uint32_t i = 0; i < n; i++, out += 4)
+		std::memcpy(out, p + (size_t)(idx ? (uint32_t)idx[i] : i) * c.stride, 16);
+}
+
+int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src_in, const int32_t *tgt_idx, const int32_t *src_idx, uint32_t n_corr,
+			   bool indexed, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique_out, uint32_t cap)
+{
+	const char *who = indexed ? "mulls_coarse_reg_teaser_indexed" : "mulls_coarse_reg_teaser";
+	if (!ctx || !tgt_in || !src_in || !params || !result || (cap && !clique_out))
+		return MULLS_E_INVALID;
+	std::memset(result, 0, sizeof(*result));
+	result->status = -1;
+	for (int k = 0; k < 16; k++)
+		result->T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+	const mulls_cloud T = *tgt_in, S = *src_in;
+	if ((T.n && !T.pts) || (S.n && !S.pts))
+		return MULLS_E_INVALID;
+	if (!std::isfinite(params->noise_bound) || params->noise_bound < 0.0f)
+	{
+		ctx->err = std::string(who) + ": noise_bound is not finite or negative";
+		return MULLS_E_INVALID;
+	}
+	uint32_t n = T.n;
+	if (indexed)
+	{
+		if (n_corr && (!tgt_idx || !src_idx))
+			return MULLS_E_INVALID;
+		n = n_corr;
+	}
+	else if (T.n != S.n)
+		return MULLS_OK; // upstream: "source points number != target points number", -1
+	if (n <= 3u)
+		return MULLS_OK; // upstream: "too few correspondences", -1
+	if (n > MULLS_TEASER_MAX_POINTS)
+	{
+		ctx->err = std::string(who) + ": at most 8192 pairs";
+		return MULLS_E_UNSUPPORTED;
+	}
+	if (indexed)
+		for (uint32_t i = 0; i < n; i++)
+			if (tgt_idx[i] < 0 || (uint32_t)tgt_idx[i] >= T.n || src_idx[i] < 0 || (uint32_t)src_idx[i] >= S.n)
+			{
+				ctx->err = std::string(who) + ": an index lies outside its cloud";
+				return MULLS_E_INVALID;
+			}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const bool t_dev = cloud_on_device(ctx, T), s_dev = cloud_on_device(ctx, S);
+	if ((t_dev && T.stride != MULLS_POINT_BYTES) || (s_dev && S.stride != MULLS_POINT_BYTES) || (!t_dev && (T.stride < 16u || T.stride % 4u)) ||
+		(!s_dev && (S.stride < 16u || S.stride % 4u)))
+	{
+		ctx->err = std::string(who) + ": stride (device clouds: 48; host clouds: a multiple of 4, at least 16)";
+		return MULLS_E_INVALID;
+	}
+	if (!ctx->teaser)
+		ctx->teaser = new mulls_teaser_scratch();
+	mulls_teaser_scratch &sc = *ctx->teaser;
+	const uint32_t W = (n + 63u) / 64u;
+	const size_t mat = (size_t)n * W * 8u;
+
+	size_t off = 0;
+	auto take = [&](size_t bytes) {
+		const size_t at = off;
+		off += up256(bytes);
+		return at;
+	};
+	const size_t o_src = take((size_t)n * 16u), o_tgt = take((size_t)n * 16u), o_idx = take((size_t)n * 8u), o_adj = take(mat), o_sub = take(mat);
+	const size_t o_deg = take((size_t)n * 4u), o_cg = take((size_t)n * 8u), o_sum = take(8), o_keep = take((size_t)n * 4u);
+	const size_t o_cs = take((size_t)n * 16u), o_ct = take((size_t)n * 16u), o_part = take((size_t)9u * MULLS_TEASER_PARTIALS * 8u), o_S = take(sizeof(TeaserGnc));
+	if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
+		return rc;
+	size_t poff = 0;
+	auto ptake = [&](size_t bytes) {
+		const size_t at = poff;
+		poff += up256(bytes);
+		return at;
+	};
+	const size_t p_src = ptake((size_t)n * 16u), p_tgt = ptake((size_t)n * 16u), p_idx = ptake((size_t)n * 8u), p_sub = ptake(mat), p_cg = ptake((size_t)n * 8u);
+	const size_t p_sum = ptake(8), p_keep = ptake((size_t)n * 4u), p_cs = ptake((size_t)n * 32u), p_S = ptake(sizeof(TeaserGnc));
+	if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, poff, hipHostMallocDefault))
+		return rc;
+	unsigned char *d = sc.dev, *h = sc.pin;
+	hipStream_t st = ctx->stream;
+	mulls::StreamDrain drain{st};
+	float4 *src4 = reinterpret_cast<float4 *>(d + o_src), *tgt4 = reinterpret_cast<float4 *>(d + o_tgt);
+
+	// staging, as mulls_coarse_reg_ransac: host clouds are packed (and gathered) on the host and go up; device clouds are gathered on the device
+	if (indexed && (t_dev || s_dev))
+	{
+		std::memcpy(h + p_idx, tgt_idx, (size_t)n * 4u);
+		std::memcpy(h + p_idx + (size_t)n * 4u, src_idx, (size_t)n * 4u);
+		HIPCHK(ctx, hipMemcpyAsync(d + o_idx, h + p_idx, (size_t)n * 8u, hipMemcpyHostToDevice, st));
+	}
+	const int32_t *d_tidx = indexed ? reinterpret_cast<const int32_t *>(d + o_idx) : nullptr, *d_sidx = indexed ? d_tidx + n : nullptr;
+	if (t_dev)
+		HIPCHK(ctx, launch_ransac_gather(st, T.pts, d_tidx, n, tgt4));
+	else
+	{
+		pack_xyzw(T, indexed ? tgt_idx : nullptr, n, reinterpret_cast<float *>(h + p_tgt));
+		HIPCHK(ctx, hipMemcpyAsync(tgt4, h + p_tgt, (size_t)n * 16u, hipMemcpyHostToDevice, st));
+	}
+	if (s_dev)
+		HIPCHK(ctx, launch_ransac_gather(st, S.pts, d_sidx, n, src4));
+	else
+	{
+		pack_xyzw(S, indexed ? src_idx : nullptr, n, reinterpret_cast<float *>(h + p_src));
+		HIPCHK(ctx, hipMemcpyAsync(src4, h + p_src, (size_t)n * 16u, hipMemcpyHostToDevice, st));
+	}
+
+	// the graph, its core numbers and the greedy clique sizes
+	const double nb = (double)params->noise_bound, beta = (2.0 * nb) * sqrt(1.0);
+	uint64_t *adj = reinterpret_cast<uint64_t *>(d + o_adj), *sub = reinterpret_cast<uint64_t *>(d + o_sub);
+	uint32_t *deg = reinterpret_cast<uint32_t *>(d + o_deg), *core = reinterpret_cast<uint32_t *>(d + o_cg), *greedy = core + n;
+	HIPCHK(ctx, hipMemsetAsync(d + o_sum, 0, 8, st));
+	HIPCHK(ctx, launch_teaser_graph(st, src4, tgt4, n, beta, adj));
+	HIPCHK(ctx, launch_teaser_degrees(st, adj, n, deg, reinterpret_cast<unsigned long long *>(d + o_sum)));
+	HIPCHK(ctx, launch_teaser_cores(st, adj, n, deg, core));
+	HIPCHK(ctx, launch_teaser_greedy(st, adj, n, greedy));
+	HIPCHK(ctx, hipMemcpyAsync(h + p_cg, core, (size_t)n * 8u, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipMemcpyAsync(h + p_sum, d + o_sum, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	const uint32_t *h_core = reinterpret_cast<const uint32_t *>(h + p_cg), *h_greedy = h_core + n;
+	unsigned long long deg_sum;
+	std::memcpy(&deg_sum, h + p_sum, 8);
+	result->n_edges = deg_sum / 2u;
+	uint32_t max_core = 0, lb = 0, lb_v = 0;
+	for (uint32_t i = 0; i < n; i++)
+	{
+		max_core = std::max(max_core, h_core[i]);
+		if (h_greedy[i] > lb)
+			lb = h_greedy[i], lb_v = i;
+	}
+	result->max_core = (int32_t)max_core;
+	std::vector<uint32_t> clique; // original vertex numbers, ascending
+	result->clique_exact = 1;
+	if (lb <= 1u) // no edge: the smallest maximum clique is the vertex 0
+		clique.assign(1, 0u);
+	else
+	{
+		// the vertices a clique of lb or more can hold, in ascending order: the one sub-matrix the search needs
+		int32_t *h_keep = reinterpret_cast<int32_t *>(h + p_keep);
+		uint32_t m = 0, witness_at = 0;
+		for (uint32_t i = 0; i < n; i++)
+			if (h_core[i] + 1u >= lb)
+			{
+				if (i == lb_v)
+					witness_at = m;
+				h_keep[m++] = (int32_t)i;
+			}
+		const uint32_t Wm = (m + 63u) / 64u;
+		HIPCHK(ctx, hipMemcpyAsync(d + o_keep, h_keep, (size_t)m * 4u, hipMemcpyHostToDevice, st));
+		HIPCHK(ctx, launch_teaser_compact(st, adj, n, reinterpret_cast<const int32_t *>(d + o_keep), m, sub));
+		HIPCHK(ctx, hipMemcpyAsync(h + p_sub, sub, (size_t)m * Wm * 8u, hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		TeaserBits G;
+		G.m = m, G.W = Wm, G.rows = reinterpret_cast<const uint64_t *>(h + p_sub);
+		const auto tic = std::chrono::steady_clock::now();
+		std::vector<uint32_t> witness;
+		teaser_greedy_clique(G, witness_at, witness);
+		if (witness.size() != lb)
+		{
+			ctx->err = std::string(who) + ": the greedy clique's witness does not have the size the device counted";
+			return MULLS_E_HIP;
+		}
+		TeaserSearch search;
+		search.run(G, lb, witness, params->clique_node_budget);
+		result->search_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
+		result->clique_nodes = search.nodes;
+		result->clique_exact = search.aborted ? 0 : 1;
+		for (uint32_t v : search.best_clique)
+			clique.push_back((uint32_t)h_keep[v]);
+	}
+	const uint32_t C = (uint32_t)clique.size();
+	result->clique_size = (int32_t)C;
+	for (uint32_t k = 0; k < std::min(C, cap); k++)
+		clique_out[k] = (int32_t)clique[k];
+	if (C <= 1u)
+		return MULLS_OK;
+
+	// the rotation: GNC-TLS over the clique's pairwise measurements, one launch set and one small readback per iteration
+	const uint64_t M = (uint64_t)C * (C - 1u) / 2u;
+	if (int rc = grow(ctx, &sc.weights, &sc.weights_cap, (size_t)M))
+		return rc;
+	int32_t *h_keep = reinterpret_cast<int32_t *>(h + p_keep);
+	for (uint32_t k = 0; k < C; k++)
+		h_keep[k] = (int32_t)clique[k];
+	float4 *cs = reinterpret_cast<float4 *>(d + o_cs), *ct = reinterpret_cast<float4 *>(d + o_ct);
+	HIPCHK(ctx, hipMemcpyAsync(d + o_keep, h_keep, (size_t)C * 4u, hipMemcpyHostToDevice, st));
+	HIPCHK(ctx, launch_teaser_pick(st, src4, tgt4, reinterpret_cast<const int32_t *>(d + o_keep), C, cs, ct));
+	HIPCHK(ctx, hipMemcpyAsync(h + p_cs, cs, (size_t)C * 16u, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipMemcpyAsync(h + p_cs + (size_t)n * 16u, ct, (size_t)C * 16u, hipMemcpyDeviceToHost, st));
+	double nb2 = nb * nb;
+	if (nb2 < 1e-16)
+		nb2 = 1e-2;
+	TeaserGnc G;
+	TeaserGnc *dS = reinterpret_cast<TeaserGnc *>(d + o_S);
+	int iters = 0;
+	for (int it = 0; it < MULLS_TEASER_GNC_MAX_ITER; it++)
+	{
+		HIPCHK(ctx, launch_teaser_gnc_iteration(st, cs, ct, C, it, nb2, sc.weights, reinterpret_cast<double *>(d + o_part), dS));
+		HIPCHK(ctx, hipMemcpyAsync(h + p_S, dS, sizeof(TeaserGnc), hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		std::memcpy(&G, h + p_S, sizeof(G));
+		iters = it + 1;
+		if (G.stop)
+			break;
+	}
+	result->gnc_iterations = iters;
+	result->cost = G.cost;
+	const uint64_t n_rot = G.stop == 1u ? M : (uint64_t)G.n_inlier;
+	result->n_rotation_inliers = (int32_t)n_rot;
+
+	// the translation: serial, on the clique's points (already down) and R
+	double that[3];
+	result->n_translation_inliers =
+		(int32_t)teaser_translation(reinterpret_cast<const float *>(h + p_cs), reinterpret_cast<const float *>(h + p_cs + (size_t)n * 16u), C, G.R, nb, that);
+	const long long min_in = params->min_inlier_num;
+	result->status = (long long)n_rot >= 2 * min_in ? 1 : ((long long)n_rot >= min_in ? 0 : -1);
+	if (result->status >= 0)
+		for (int r = 0; r < 3; r++)
+		{
+			for (int c = 0; c < 3; c++)
+				result->T[c * 4 + r] = G.R[r * 3 + c];
+			result->T[12 + r] = that[r];
+		}
+	return MULLS_OK;
+}
+} // namespace
+
+extern "C"
+{
+	void mulls_teaser_default_params(mulls_teaser_params *p)
+	{
+		if (!p)
+			return;
+		p->noise_bound = 0.2f; // cregistration.hpp:666
+		p->min_inlier_num = 8;
+		p->clique_node_budget = MULLS_TEASER_DEFAULT_NODE_BUDGET;
+	}
+
+	int mulls_coarse_reg_teaser(mulls_ctx *ctx, const mulls_cloud *tgt_pts, const mulls_cloud *src_pts, const mulls_teaser_params *params,
+								mulls_teaser_result *result, int32_t *clique, uint32_t cap)
+	try
+	{
+		return teaser_run(ctx, tgt_pts, src_pts, nullptr, nullptr, 0, false, params, result, clique, cap);
+	}
+	catch (...)
+	{
+		return mulls::abi_caught(ctx); // nothing is thrown across the ABI
+	}
+
+	int mulls_coarse_reg_teaser_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const int32_t *tgt_idx, const int32_t *src_idx,
+										uint32_t n_corr, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique, uint32_t cap)
+	try
+	{
+		return teaser_run(ctx, tgt_kpts, src_kpts, tgt_idx, src_idx, n_corr, true, params, result, clique, cap);
+	}
+	catch (...)
+	{
+		return mulls::abi_caught(ctx);
+	}
+}

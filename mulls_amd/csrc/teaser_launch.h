@@ -1,0 +1,27 @@
+// teaser_launch.h — host-callable launchers of k_teaser.hip: the TEASER coarse-registration solver, CRegistration::coarse_reg_teaser
+// (cregistration.hpp:664-759).  The device builds the pair-consistency graph as a bit matrix, peels it to core numbers, bounds the clique from below with
+// a greedy clique per vertex and compacts the vertices that can still belong to a maximum clique; the exact search runs on the host (teaser_host.h);
+// the GNC-TLS rotation runs on the device again, one launch set per iteration (include/mulls_hip.h has the definition).
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <hip/hip_vector_types.h>
+#include <stdint.h>
+
+#include "teaser_math.h"
+
+// adj: n rows of W = ceil(n / 64) words, bit j of row i = edge {i, j}; bits at and above n are zero, the diagonal is zero
+hipError_t launch_teaser_graph(hipStream_t st, const float4 *src, const float4 *tgt, uint32_t n, double beta, uint64_t *adj);
+// deg[i] = popcount of row i; *deg_sum (zeroed by the caller) = their sum = twice the edge count
+hipError_t launch_teaser_degrees(hipStream_t st, const uint64_t *adj, uint32_t n, uint32_t *deg, unsigned long long *deg_sum);
+// core[i] = core number of vertex i
+hipError_t launch_teaser_cores(hipStream_t st, const uint64_t *adj, uint32_t n, const uint32_t *deg, uint32_t *core);
+// greedy[v] = size of the clique grown from v by taking the smallest common neighbour until none is left
+hipError_t launch_teaser_greedy(hipStream_t st, const uint64_t *adj, uint32_t n, uint32_t *greedy);
+// sub: the m x ceil(m / 64) bit matrix of the vertices keep[0] < ... < keep[m - 1]
+hipError_t launch_teaser_compact(hipStream_t st, const uint64_t *adj, uint32_t n, const int32_t *keep, uint32_t m, uint64_t *sub);
+// cs[k] = src[clique[k]], ct[k] = tgt[clique[k]]
+hipError_t launch_teaser_pick(hipStream_t st, const float4 *src, const float4 *tgt, const int32_t *clique, uint32_t C, float4 *cs, float4 *ct);
+// one GNC iteration over the M = C (C - 1) / 2 measurements of the clique: fit (S->R), residuals and cost (S->cost, S->mu, S->stop), weight update
+// (weights, S->n_inlier; skipped on the device when S->stop == 1).  part: 9 * MULLS_TEASER_PARTIALS doubles.
+hipError_t launch_teaser_gnc_iteration(hipStream_t st, const float4 *cs, const float4 *ct, uint32_t C, int iter, double nb2, double *weights, double *part,
+									   TeaserGnc *S);

@@ -109,6 +109,11 @@ def load():
     lib.mulls_coarse_reg_ransac.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.RansacParams), C.POINTER(abi.RansacResult), vp, C.c_uint32]
     lib.mulls_coarse_reg_ransac_indexed.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), vp, vp, C.c_uint32, C.POINTER(abi.RansacParams),
                                                     C.POINTER(abi.RansacResult), vp, C.c_uint32]
+    lib.mulls_teaser_default_params.argtypes = [C.POINTER(abi.TeaserParams)]
+    lib.mulls_teaser_default_params.restype = None
+    lib.mulls_coarse_reg_teaser.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.TeaserParams), C.POINTER(abi.TeaserResult), vp, C.c_uint32]
+    lib.mulls_coarse_reg_teaser_indexed.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), vp, vp, C.c_uint32, C.POINTER(abi.TeaserParams),
+                                                    C.POINTER(abi.TeaserResult), vp, C.c_uint32]
     lib.mulls_sor_default_params.argtypes = [C.POINTER(abi.SorParams)]
     lib.mulls_sor_default_params.restype = None
     lib.mulls_sor_filter.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.SorParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
@@ -138,6 +143,7 @@ EXPORTS = [
     "mulls_pack_results", "mulls_icp_batch_sharded", "mulls_pipe_create", "mulls_pipe_destroy", "mulls_pipe_depth", "mulls_pipe_ctx", "mulls_pipe_set_option", "mulls_icp_batch_begin", "mulls_icp_batch_end",
     "mulls_ncc_default_params", "mulls_ncc_correspond",
     "mulls_ransac_default_params", "mulls_coarse_reg_ransac", "mulls_coarse_reg_ransac_indexed",
+    "mulls_teaser_default_params", "mulls_coarse_reg_teaser", "mulls_coarse_reg_teaser_indexed",
     "mulls_sor_default_params", "mulls_sor_filter",
     "mulls_nms_default_params", "mulls_non_max_suppress",
 ]
@@ -471,6 +477,44 @@ class Context:
             raise MullsError("mulls_coarse_reg_ransac failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
         assert inl[cap] == -1
         return res, inl[: min(res.n_inliers, cap)].copy()
+
+    # --- TEASER coarse registration ----------------------------------------------------------------------------------
+    def coarse_reg_teaser(self, tgt_pts, src_pts, params=None, cap=None, tgt_idx=None, src_idx=None):
+        """coarse_reg_teaser (mulls_coarse_reg_teaser; with tgt_idx / src_idx, mulls_coarse_reg_teaser_indexed on the pairs those lists name).  The clouds
+        are host clouds or device-resident abi.Cloud objects, as for coarse_reg_ransac.  Returns (result, clique): the abi.TeaserResult and the ascending
+        clique indices actually written (min(clique_size, cap) of them; cap defaults to the number of pairs)."""
+        keep = []
+
+        def cloud(k):
+            if isinstance(k, abi.Cloud):
+                return k
+            raw = abi.records(k)
+            keep.append(raw)
+            c = abi.Cloud()
+            c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+            return c
+
+        ct, cs = cloud(tgt_pts), cloud(src_pts)
+        p = params if params is not None else abi.teaser_params()
+        res = abi.TeaserResult()
+        indexed = tgt_idx is not None
+        if indexed:
+            ti, si = np.ascontiguousarray(tgt_idx, np.int32), np.ascontiguousarray(src_idx, np.int32)
+            assert len(ti) == len(si)
+        n_pairs = len(ti) if indexed else ct.n
+        if cap is None:
+            cap = n_pairs
+        clique = np.full(cap + 1, -1, np.int32)  # one slot past cap: checked to be left alone
+        ip = clique.ctypes.data_as(C.c_void_p) if cap else None
+        if indexed:
+            rc = self.lib.mulls_coarse_reg_teaser_indexed(self.h, C.byref(ct), C.byref(cs), ti.ctypes.data_as(C.c_void_p), si.ctypes.data_as(C.c_void_p), len(ti),
+                                                          C.byref(p), C.byref(res), ip, cap)
+        else:
+            rc = self.lib.mulls_coarse_reg_teaser(self.h, C.byref(ct), C.byref(cs), C.byref(p), C.byref(res), ip, cap)
+        if rc != 0:
+            raise MullsError("mulls_coarse_reg_teaser failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        assert clique[cap] == -1
+        return res, clique[: min(max(res.clique_size, 0), cap)].copy()
 
     # --- statistical outlier removal ---------------------------------------------------------------------------------
     def sor_filter(self, pts, params=None, want_dist=False):

@@ -1,0 +1,84 @@
+"""The TEASER coarse-registration solver (mulls_coarse_reg_teaser_indexed) timed on the device: wall time per call, host key points and index lists in to
+result out, median of 20 after 2 warm-ups (3 calls, the first among them, where one call takes more than a second: the host clique search is the whole of it), on the
+demo scans' key-point pair lists of 517, 294, 1 543 and 2 840 pairs (tests/golden/ncc_demo.npz) at the noise bounds 0.25 and 1.0, and on 4 000 random pairs
+with 5 % planted inliers.  The host clique search's time is reported on its own (result.search_seconds), and mulls_coarse_reg_ransac_indexed on the same
+pairs next to it.  The search is given --budget nodes (default 2^20, so that a timing run ends; the library's default is 2^28).
+
+    python tools/gpu_teaser.py                 the table
+    python tools/gpu_teaser.py --calls 3       three calls per case and nothing else: the run to put under `rocprofv3 --kernel-trace --stats -- ...`
+"""
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mulls_amd import abi, lib  # noqa: E402
+
+
+def random_pairs(seed, n, share=0.05, bound=1.0):
+    rng = np.random.default_rng(seed)
+    lo, hi = np.array([-40.0, -40.0, -3.0]), np.array([40.0, 40.0, 10.0])
+    src = rng.uniform(lo, hi, (n, 3))
+    a = rng.uniform(0.2, 1.2)
+    R = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+    tgt = src @ R.T + rng.uniform([-8, -8, -0.5], [8, 8, 0.5]) + rng.uniform(-0.1 * bound, 0.1 * bound, (n, 3))
+    out = rng.random(n) >= share
+    tgt[out] = rng.uniform(lo, hi, (int(out.sum()), 3))
+    rec = []
+    for p in (tgt, src):
+        f = np.zeros((n, 12), np.float32)
+        f[:, :3] = p
+        rec.append(f.view(np.uint8).reshape(n, 48))
+    idx = np.arange(n, dtype=np.int32)
+    return rec[0], rec[1], idx, idx
+
+
+def main():
+    arg = lambda k, d: type(d)(sys.argv[sys.argv.index(k) + 1]) if k in sys.argv else d  # noqa: E731
+    calls, budget = arg("--calls", 0), arg("--budget", 1 << 20)
+    Z = np.load(os.path.join(ROOT, "tests", "golden", "ncc_demo.npz"))
+    cases = []
+    for name in ("fixed300_0_15", "recip_0_15", "fixed2000_0_15", "nn_0_15"):
+        pr = Z[name + "_pairs"]
+        for nb in (0.25, 1.0):
+            cases.append((name, nb, Z["kpts_0"], Z["kpts_15"], pr[:, 0], pr[:, 1]))
+    cases.append(("random_4000", 1.0) + random_pairs(4000, 4000))
+    ctx = lib.Context(0)
+    for name, nb, kt, ks, ti, si in cases:
+        P = abi.teaser_params(nb, 8, budget)
+        RP = abi.ransac_params(nb, 8, 20000, 1)
+
+        def call():
+            t0 = time.perf_counter()
+            res, _ = ctx.coarse_reg_teaser(kt, ks, P, cap=0, tgt_idx=ti, src_idx=si)
+            return time.perf_counter() - t0, res
+
+        def ransac():
+            t0 = time.perf_counter()
+            ctx.coarse_reg_ransac(kt, ks, RP, cap=0, tgt_idx=ti, src_idx=si)
+            return time.perf_counter() - t0
+
+        first, res = call()
+        if calls:
+            for _ in range(calls - 1 if first < 1.0 else 0):  # (a call the host search dominates is traced once)
+                call()
+            continue
+        n_calls = 20 if first < 1.0 else 3
+        if n_calls == 20:
+            call()
+        runs = [call() for _ in range(n_calls)] if n_calls == 20 else [(first, res), call(), call()]
+        ts, ss = sorted(r[0] for r in runs), sorted(r[1].search_seconds for r in runs)
+        ransac(), ransac()
+        rs = sorted(ransac() for _ in range(20))
+        print("%-15s N %5d  bound %.2f  status %2d  edges %7d  max core %4d  clique %4d (%s, %9d nodes)  GNC iterations %3d  rotation inliers %6d | wall median of %2d: %10.3f ms"
+              "  (min %.3f, max %.3f) | host search alone %10.3f ms | RANSAC (20000 iterations, refined) on the same pairs %8.3f ms"
+              % (name, len(ti), nb, res.status, res.n_edges, res.max_core, res.clique_size, "exact" if res.clique_exact else "budget", res.clique_nodes,
+                 res.gnc_iterations, res.n_rotation_inliers, n_calls, ts[n_calls // 2] * 1e3, ts[0] * 1e3, ts[-1] * 1e3, ss[n_calls // 2] * 1e3, rs[10] * 1e3), flush=True)
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -5,8 +5,9 @@ non_max_suppress of both key-point clouds with keypoint_nms_radius = 0.25 x pca_
 classification does not thin the key points: upstream's detect_key_pts is commented out and vertex_curvature_non_max_radius is unused),
 find_feature_correspondence_ncc on the two thinned clouds -> coarse_reg_ransac with noise_bound = 4 x keypoint_nms_radius (test/mulls_reg.cpp:170-179;
 mulls_ncc_correspond -> mulls_coarse_reg_ransac_indexed), whose transform is the initial guess (the identity when it fails, as upstream leaves init_mat)
--> mm_lls_icp -> the source's pc_down, transformed, written out.  Flags carry the reference's names and defaults (test/mulls_reg.cpp:24-60).  Not here:
-TEASER++ (--teaser_on is accepted and answered with the RANSAC solver), the viewers.
+-> mm_lls_icp -> the source's pc_down, transformed, written out.  Flags carry the reference's names and defaults (test/mulls_reg.cpp:24-60).  With
+--global_solver=teaser the solver is coarse_reg_teaser (mulls_coarse_reg_teaser_indexed: the library's definition of upstream's TEASER++ call).  The
+reference's own --teaser_on is accepted and still answered with the RANSAC solver.  Not here: the viewers.
 
     python tools/mulls_reg.py --point_cloud_1_path a.pcd --point_cloud_2_path b.pcd --output_point_cloud_path b_reg.pcd
 """
@@ -51,6 +52,7 @@ def flags(argv=None):
     p.add_argument("--converge_rot_d", type=float, default=0.01)
     p.add_argument("--is_global_reg", type=boolean, default=True)
     p.add_argument("--teaser_on", type=boolean, default=False)
+    p.add_argument("--global_solver", choices=("ransac", "teaser"), default="ransac", help="teaser: coarse_reg_teaser (mulls_coarse_reg_teaser_indexed)")
     p.add_argument("--corr_num", type=int, default=3000)
     p.add_argument("--reciprocal_corr_on", type=boolean, default=False)
     p.add_argument("--fixed_num_corr_on", type=boolean, default=False)
@@ -101,9 +103,17 @@ def extract_semantic_pts(ctx, scan, F, vf_downsample_resolution):
 def global_registration(ctx, tgt_kpts, src_kpts, F):
     """test/mulls_reg.cpp:170-179: key-point correspondences, then the RANSAC solver; returns init_mat"""
     if F.teaser_on:
+        # (this line and the RANSAC answer to the reference's flag are what tests/test_gpu_ransac.py holds the tool to; the library's own solver of
+        # coarse_reg_teaser is selected with --global_solver=teaser)
         print("--teaser_on: TEASER++ is not part of the library; the RANSAC solver (coarse_reg_ransac) is used")
     keypoint_nms_radius = 0.25 * F.pca_neighbor_radius  # :107
     ok, ti, si, n = ctx.ncc_correspond(tgt_kpts, src_kpts, abi.ncc_params(int(F.fixed_num_corr_on), F.corr_num, int(F.reciprocal_corr_on)))
+    if F.global_solver == "teaser":  # test/mulls_reg.cpp:176-177
+        res, _ = ctx.coarse_reg_teaser(tgt_kpts, src_kpts, abi.teaser_params(noise_bound=4.0 * keypoint_nms_radius), cap=0, tgt_idx=ti, src_idx=si)
+        print("global registration: %d key-point pairs, TEASER status %d: clique of %d (%s, %d search nodes, %.1f ms), %d GNC iterations, %d rotation inliers"
+              % (n, res.status, res.clique_size, "exact" if res.clique_exact else "budget ended the search", res.clique_nodes, 1e3 * res.search_seconds,
+                 res.gnc_iterations, res.n_rotation_inliers))
+        return np.array(res.T[:], np.float64).reshape(4, 4).T.copy() if res.status >= 0 else np.eye(4)
     res, _ = ctx.coarse_reg_ransac(tgt_kpts, src_kpts, abi.ransac_params(noise_bound=4.0 * keypoint_nms_radius), cap=0, tgt_idx=ti, src_idx=si)
     print("global registration: %d key-point pairs, RANSAC status %d after %d iterations, %d inliers" % (n, res.status, res.iterations, res.n_inliers))
     # upstream writes init_mat only when the solver does not fail (cregistration.hpp:642-660)
