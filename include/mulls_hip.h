@@ -258,7 +258,11 @@ enum mulls_option
 	MULLS_OPT_SUM_STEP = 27,			  /* [1] lock-step loop stepped on the device, batches beyond STEP_LAUNCH_MAX_PAIRS: one wave per pair sums the pair's trip partials AND steps it
 											 (k_sum_step) instead of k_finish followed by k_step — one launch less per iteration; pairs with more than MULLS_SUM_STEP_TRIPS
 											 trips in a class keep the two kernels.  0 = k_finish + k_step.  Same bits */
-	MULLS_OPT_COUNT = 28
+	MULLS_OPT_TEASER_DEVICE_SEARCH = 28,  /* [0] 1: the exact maximum-clique search of mulls_coarse_reg_teaser / mulls_coarse_reg_teaser_indexed runs on the device (k_teaser_clique.hip: a
+											 chain of bounded launches, one wavefront per branch of the search tree) instead of on one host core.  Every result field is the same
+											 bits whenever the search completes; clique_nodes, the effort, is not (see the TEASER block below).  Values other than 0 and 1 are
+											 refused.  MULLS_TEASER_DEVICE_SEARCH=1 */
+	MULLS_OPT_COUNT = 29
 };
 int mulls_set_option(mulls_ctx *ctx, int option, double value);
 int mulls_get_option(const mulls_ctx *ctx, int option, double *value);
@@ -688,6 +692,18 @@ int mulls_coarse_reg_ransac_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts,
  *              nodes; beyond, the largest clique found so far by a deterministic single-threaded search is used and clique_exact = 0 (that clique does
  *              depend on the search: teaser_host.h).  kcore_heuristic_threshold (:710) is not used: upstream leaves the mode at exact.  A graph without
  *              an edge has the clique {0}; clique_size <= 1: status -1.  clique_nodes is the search's effort, not part of the definition.
+ *              With MULLS_OPT_TEASER_DEVICE_SEARCH = 1 the same clique comes from a search on the device (mulls_amd/csrc/teaser_search.h): clique
+ *              prefixes (a vertex, or a vertex and one later neighbour) are tasks in lexicographic rank order, one wavefront each; a first phase finds
+ *              the size (a shared incumbent, raised atomically), a second the list (every task looks for its first clique of that size in ascending
+ *              order; the task of the lowest rank that has one holds the smallest list).  Whenever the search completes, every field is the same bits
+ *              as the host search's, except: clique_nodes is the number of tree nodes all workers entered (every task that is started counts as one at
+ *              least); pruning depends on when a worker sees another's bound, so the number NEED NOT REPEAT from call to call.  clique_node_budget
+ *              bounds that total; the host checks it between launches, so the overshoot is at most one launch's quota (2048 workers x 256 nodes).
+ *              When the total exceeds the budget, clique_exact = 0 and the clique is THE GREEDY BOUND'S WITNESS (the clique grown from the first vertex
+ *              of the largest greedy clique by taking the smallest common neighbour again and again), not the largest clique found so far: an
+ *              abandoned search's result does not depend on scheduling either.  Whether a search whose effort lies within one launch of the budget is
+ *              abandoned at all may depend on timing, since the effort does.  search_seconds is then the wall time of the device search, from its first
+ *              launch to its last readback.
  *   measures   [TEASER] clique vertices c_0 < ... < c_(C-1); measurement k runs over the pairs a < b, a outer, b inner: a_k = s_cb - s_ca,
  *              b_k = t_cb - t_ca; M = C (C - 1) / 2.
  *   rotation   [TEASER] GNC-TLS: at most 100 iterations, factor 1.4, cost threshold 0.005 (:705-711); nb2 = noise_bound^2, 1e-2 when below 1e-16; weights 1,
@@ -723,13 +739,13 @@ typedef struct mulls_teaser_result
 	uint64_t n_edges;
 	int32_t clique_size;
 	int32_t clique_exact;  /* 1: the search finished within the budget */
-	uint64_t clique_nodes; /* nodes the search visited */
+	uint64_t clique_nodes; /* nodes the search visited (device search: by all workers together; need not repeat) */
 	int32_t gnc_iterations;
 	int32_t n_rotation_inliers; /* measurements with weight >= 0.5: upstream's inlier count */
 	int32_t n_translation_inliers;
 	int32_t reserved;
 	double cost;		   /* the last GNC iteration's */
-	double search_seconds; /* wall time of the host clique search: a measurement, not a result */
+	double search_seconds; /* wall time of the clique search, host or device: a measurement, not a result */
 	double T[16];		   /* column-major; written when status >= 0, the identity otherwise */
 } mulls_teaser_result;
 

@@ -1,6 +1,7 @@
 // teaser.cpp — mulls_coarse_reg_teaser: CRegistration<PointT>::coarse_reg_teaser (cregistration.hpp:664-759), the solver every shipped configuration
 // selects between the key-point matcher (ncc.cpp) and mulls_icp.  Host side: argument checks, staging, the order of the device steps (k_teaser.hip: graph,
-// core numbers, greedy lower bound, compaction, GNC-TLS rotation), the exact clique search on the one sub-matrix that comes down (teaser_host.h), and the
+// core numbers, greedy lower bound, compaction, GNC-TLS rotation), the exact clique search — on the one sub-matrix that comes down (teaser_host.h) or,
+// with MULLS_OPT_TEASER_DEVICE_SEARCH, as a chain of bounded launches on the sub-matrix where it lies (teaser_search.h, k_teaser_clique.hip) — and the
 // serial TLS translation estimate on the clique's points.  include/mulls_hip.h has the definition this file follows.
 #include <chrono>
 
@@ -9,12 +10,13 @@
 #include "teaser_host.h"
 #include "teaser_launch.h"
 
-// a context's scratch of this entry point: a device arena, the GNC weights (up to C (C - 1) / 2 doubles) and a pinned host buffer, grow-only
+// a context's scratch of this entry point: a device arena, the GNC weights (up to C (C - 1) / 2 doubles), a pinned host buffer and the device clique
+// search's workers (states, cliques so far, stacks: sized once the kept vertices and the largest core number are known), grow-only
 struct mulls_teaser_scratch
 {
-	unsigned char *dev = nullptr, *pin = nullptr;
+	unsigned char *dev = nullptr, *pin = nullptr, *search = nullptr;
 	double *weights = nullptr;
-	size_t dev_cap = 0, pin_cap = 0, weights_cap = 0;
+	size_t dev_cap = 0, pin_cap = 0, weights_cap = 0, search_cap = 0;
 };
 
 void mulls_teaser_release(mulls_ctx *ctx)
@@ -23,6 +25,7 @@ void mulls_teaser_release(mulls_ctx *ctx)
 		return;
 	staggered_free(ctx->teaser->dev);
 	staggered_free(ctx->teaser->weights);
+	staggered_free(ctx->teaser->search);
 	if (ctx->teaser->pin)
 		(void)hipHostFree(ctx->teaser->pin);
 	delete ctx->teaser;
@@ -51,6 +54,63 @@ void pack_xyzw(const mulls_cloud &c, const int32_t *idx, uint32_t n, float *out)
 	for (uint32_t i = 0; i < n; i++, out += 4)
 		std::memcpy(out, p + (size_t)(idx ? (uint32_t)idx[i] : i) * c.stride, 16);
 }
+
+// The executor of teaser_search_control on the device: one k_teaser_clique launch and one readback of the shared words per step.  Every word a phase reads
+// is written at its beginning (the shared words and the workers' states; stacks and cliques are written before they are read), so nothing of an earlier
+// call or phase is seen.
+struct DeviceSearch
+{
+	mulls_ctx *ctx;
+	hipStream_t st;
+	TeaserSearchArgs A;
+	TeaserSearchCtl *h_ctl;			   // pinned: [0] goes up, [1] comes down
+	TeaserWorkerState *h_init, *h_back; // pinned, A.workers each
+	uint32_t *h_list, *d_list;		   // m + 1 words each
+	uint32_t witness_at;
+
+	int begin(int phase, uint32_t bound)
+	{
+		A.phase = (uint32_t)phase, A.omega = bound;
+		std::memset(&h_ctl[0], 0, sizeof(TeaserSearchCtl));
+		h_ctl[0].bound = bound, h_ctl[0].best_rank = MULLS_TEASER_NO_RANK;
+		HIPCHK(ctx, hipMemcpyAsync(A.ctl, &h_ctl[0], sizeof(TeaserSearchCtl), hipMemcpyHostToDevice, st));
+		HIPCHK(ctx, hipMemcpyAsync(A.state, h_init, (size_t)A.workers * sizeof(TeaserWorkerState), hipMemcpyHostToDevice, st));
+		return MULLS_OK;
+	}
+	int launch(TeaserSearchCtl *out)
+	{
+		HIPCHK(ctx, launch_teaser_clique(st, A));
+		HIPCHK(ctx, hipMemcpyAsync(&h_ctl[1], A.ctl, sizeof(TeaserSearchCtl), hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		*out = h_ctl[1];
+		return MULLS_OK;
+	}
+	int clique(uint32_t rank, std::vector<uint32_t> *out)
+	{
+		HIPCHK(ctx, hipMemcpyAsync(h_back, A.state, (size_t)A.workers * sizeof(TeaserWorkerState), hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		for (uint32_t w = 0; w < A.workers; w++)
+			if (h_back[w].found == rank)
+			{
+				HIPCHK(ctx, hipMemcpyAsync(h_list, A.cur + (size_t)w * A.levels, (size_t)A.omega * 4u, hipMemcpyDeviceToHost, st)); // (omega < levels)
+				HIPCHK(ctx, hipStreamSynchronize(st));
+				out->assign(h_list, h_list + A.omega);
+				return MULLS_OK;
+			}
+		return MULLS_TEASER_SEARCH_FAILED;
+	}
+	int witness(std::vector<uint32_t> *out)
+	{
+		HIPCHK(ctx, launch_teaser_witness(st, A.sub, A.m, witness_at, d_list));
+		HIPCHK(ctx, hipMemcpyAsync(h_list, d_list, ((size_t)A.m + 1u) * 4u, hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		if (!h_list[0] || h_list[0] > A.m)
+			return MULLS_TEASER_SEARCH_FAILED;
+		out->assign(h_list + 1, h_list + 1 + h_list[0]);
+		std::sort(out->begin(), out->end());
+		return MULLS_OK;
+	}
+};
 
 int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src_in, const int32_t *tgt_idx, const int32_t *src_idx, uint32_t n_corr,
 			   bool indexed, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique_out, uint32_t cap)
@@ -116,6 +176,9 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 	const size_t o_src = take((size_t)n * 16u), o_tgt = take((size_t)n * 16u), o_idx = take((size_t)n * 8u), o_adj = take(mat), o_sub = take(mat);
 	const size_t o_deg = take((size_t)n * 4u), o_cg = take((size_t)n * 8u), o_sum = take(8), o_keep = take((size_t)n * 4u);
 	const size_t o_cs = take((size_t)n * 16u), o_ct = take((size_t)n * 16u), o_part = take((size_t)9u * MULLS_TEASER_PARTIALS * 8u), o_S = take(sizeof(TeaserGnc));
+	const bool device_search = ctx->opt[MULLS_OPT_TEASER_DEVICE_SEARCH] != 0.0;
+	const size_t o_later = take(device_search ? (size_t)n * 4u : 0u), o_first = take(device_search ? ((size_t)n + 1u) * 4u : 0u);
+	const size_t o_ctl = take(sizeof(TeaserSearchCtl)), o_list = take(device_search ? ((size_t)n + 1u) * 4u : 0u);
 	if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
 		return rc;
 	size_t poff = 0;
@@ -126,6 +189,9 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 	};
 	const size_t p_src = ptake((size_t)n * 16u), p_tgt = ptake((size_t)n * 16u), p_idx = ptake((size_t)n * 8u), p_sub = ptake(mat), p_cg = ptake((size_t)n * 8u);
 	const size_t p_sum = ptake(8), p_keep = ptake((size_t)n * 4u), p_cs = ptake((size_t)n * 32u), p_S = ptake(sizeof(TeaserGnc));
+	const size_t p_later = ptake(device_search ? ((size_t)n + 1u) * 4u : 0u), p_ctl = ptake(2u * sizeof(TeaserSearchCtl)), p_list = ptake(device_search ? ((size_t)n + 1u) * 4u : 0u);
+	const size_t p_init = ptake(device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u);
+	const size_t p_back = ptake(device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u);
 	if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, poff, hipHostMallocDefault))
 		return rc;
 	unsigned char *d = sc.dev, *h = sc.pin;
@@ -199,25 +265,83 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 		const uint32_t Wm = (m + 63u) / 64u;
 		HIPCHK(ctx, hipMemcpyAsync(d + o_keep, h_keep, (size_t)m * 4u, hipMemcpyHostToDevice, st));
 		HIPCHK(ctx, launch_teaser_compact(st, adj, n, reinterpret_cast<const int32_t *>(d + o_keep), m, sub));
-		HIPCHK(ctx, hipMemcpyAsync(h + p_sub, sub, (size_t)m * Wm * 8u, hipMemcpyDeviceToHost, st));
-		HIPCHK(ctx, hipStreamSynchronize(st));
-		TeaserBits G;
-		G.m = m, G.W = Wm, G.rows = reinterpret_cast<const uint64_t *>(h + p_sub);
-		const auto tic = std::chrono::steady_clock::now();
-		std::vector<uint32_t> witness;
-		teaser_greedy_clique(G, witness_at, witness);
-		if (witness.size() != lb)
+		if (device_search)
 		{
-			ctx->err = std::string(who) + ": the greedy clique's witness does not have the size the device counted";
-			return MULLS_E_HIP;
+			// the sub-matrix stays where it is: the plan needs one count per kept vertex, the control a few words per launch
+			const auto tic = std::chrono::steady_clock::now();
+			uint32_t *later = reinterpret_cast<uint32_t *>(d + o_later), *h_later = reinterpret_cast<uint32_t *>(h + p_later);
+			HIPCHK(ctx, launch_teaser_later(st, sub, m, later));
+			HIPCHK(ctx, hipMemcpyAsync(h_later, later, (size_t)m * 4u, hipMemcpyDeviceToHost, st));
+			HIPCHK(ctx, hipStreamSynchronize(st));
+			TeaserPlan plan;
+			teaser_plan(h_later, m, lb, max_core, plan);
+			DeviceSearch ex;
+			ex.ctx = ctx, ex.st = st, ex.witness_at = witness_at;
+			TeaserSearchArgs &A = ex.A;
+			A.sub = sub, A.first = reinterpret_cast<const uint32_t *>(d + o_first);
+			A.m = m, A.W = Wm, A.n_tasks = plan.n_tasks, A.levels = plan.levels;
+			A.phase = 0, A.omega = lb, A.quota = MULLS_TEASER_SEARCH_QUOTA, A.workers = teaser_plan_workers(plan);
+			size_t soff = 0;
+			auto stake = [&](size_t bytes) {
+				const size_t at = soff;
+				soff += up256(bytes);
+				return at;
+			};
+			const size_t s_state = stake((size_t)A.workers * sizeof(TeaserWorkerState)), s_cur = stake((size_t)A.workers * A.levels * 4u);
+			const size_t s_slab = stake((size_t)A.workers * A.levels * Wm * 8u);
+			if (int rc = grow(ctx, &sc.search, &sc.search_cap, soff))
+				return rc;
+			A.ctl = reinterpret_cast<TeaserSearchCtl *>(d + o_ctl);
+			A.state = reinterpret_cast<TeaserWorkerState *>(sc.search + s_state);
+			A.cur = reinterpret_cast<uint32_t *>(sc.search + s_cur), A.slab = reinterpret_cast<uint64_t *>(sc.search + s_slab);
+			ex.h_ctl = reinterpret_cast<TeaserSearchCtl *>(h + p_ctl);
+			ex.h_init = reinterpret_cast<TeaserWorkerState *>(h + p_init), ex.h_back = reinterpret_cast<TeaserWorkerState *>(h + p_back);
+			ex.h_list = reinterpret_cast<uint32_t *>(h + p_list), ex.d_list = reinterpret_cast<uint32_t *>(d + o_list);
+			for (uint32_t w = 0; w < A.workers; w++)
+				ex.h_init[w] = TeaserWorkerState{0, 0, 0, 0, MULLS_TEASER_NO_RANK, {0, 0, 0}};
+			std::memcpy(h_later, plan.first.data(), ((size_t)m + 1u) * 4u); // (the counts are in the plan now)
+			HIPCHK(ctx, hipMemcpyAsync(d + o_first, h_later, ((size_t)m + 1u) * 4u, hipMemcpyHostToDevice, st));
+			TeaserSearchOutcome found;
+			if (int rc = teaser_search_control(ex, plan, max_core, params->clique_node_budget, found))
+			{
+				if (rc != MULLS_TEASER_SEARCH_FAILED)
+					return rc;
+				ctx->err = std::string(who) + ": the device clique search left the states its plan allows";
+				return MULLS_E_HIP;
+			}
+			result->search_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
+			result->clique_nodes = found.nodes;
+			result->clique_exact = found.exact ? 1 : 0;
+			if (found.clique.size() != (found.exact ? found.omega : lb))
+			{
+				ctx->err = std::string(who) + ": the device clique search's list does not have the size it proved";
+				return MULLS_E_HIP;
+			}
+			for (uint32_t v : found.clique)
+				clique.push_back((uint32_t)h_keep[v]);
 		}
-		TeaserSearch search;
-		search.run(G, lb, witness, params->clique_node_budget);
-		result->search_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
-		result->clique_nodes = search.nodes;
-		result->clique_exact = search.aborted ? 0 : 1;
-		for (uint32_t v : search.best_clique)
-			clique.push_back((uint32_t)h_keep[v]);
+		else
+		{
+			HIPCHK(ctx, hipMemcpyAsync(h + p_sub, sub, (size_t)m * Wm * 8u, hipMemcpyDeviceToHost, st));
+			HIPCHK(ctx, hipStreamSynchronize(st));
+			TeaserBits G;
+			G.m = m, G.W = Wm, G.rows = reinterpret_cast<const uint64_t *>(h + p_sub);
+			const auto tic = std::chrono::steady_clock::now();
+			std::vector<uint32_t> witness;
+			teaser_greedy_clique(G, witness_at, witness);
+			if (witness.size() != lb)
+			{
+				ctx->err = std::string(who) + ": the greedy clique's witness does not have the size the device counted";
+				return MULLS_E_HIP;
+			}
+			TeaserSearch search;
+			search.run(G, lb, witness, params->clique_node_budget);
+			result->search_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
+			result->clique_nodes = search.nodes;
+			result->clique_exact = search.aborted ? 0 : 1;
+			for (uint32_t v : search.best_clique)
+				clique.push_back((uint32_t)h_keep[v]);
+		}
 	}
 	const uint32_t C = (uint32_t)clique.size();
 	result->clique_size = (int32_t)C;

@@ -1,13 +1,15 @@
 // teaser_launch.h — host-callable launchers of k_teaser.hip: the TEASER coarse-registration solver, CRegistration::coarse_reg_teaser
 // (cregistration.hpp:664-759).  The device builds the pair-consistency graph as a bit matrix, peels it to core numbers, bounds the clique from below with
-// a greedy clique per vertex and compacts the vertices that can still belong to a maximum clique; the exact search runs on the host (teaser_host.h);
-// the GNC-TLS rotation runs on the device again, one launch set per iteration (include/mulls_hip.h has the definition).
+// a greedy clique per vertex and compacts the vertices that can still belong to a maximum clique; the exact search runs on the host (teaser_host.h) or,
+// with MULLS_OPT_TEASER_DEVICE_SEARCH, on the device (k_teaser_clique.hip, the scheme of teaser_search.h); the GNC-TLS rotation runs on the device
+// again, one launch set per iteration (include/mulls_hip.h has the definition).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
 #include <stdint.h>
 
 #include "teaser_math.h"
+#include "teaser_search.h"
 
 // adj: n rows of W = ceil(n / 64) words, bit j of row i = edge {i, j}; bits at and above n are zero, the diagonal is zero
 hipError_t launch_teaser_graph(hipStream_t st, const float4 *src, const float4 *tgt, uint32_t n, double beta, uint64_t *adj);
@@ -25,3 +27,23 @@ hipError_t launch_teaser_pick(hipStream_t st, const float4 *src, const float4 *t
 // (weights, S->n_inlier; skipped on the device when S->stop == 1).  part: 9 * MULLS_TEASER_PARTIALS doubles.
 hipError_t launch_teaser_gnc_iteration(hipStream_t st, const float4 *cs, const float4 *ct, uint32_t C, int iter, double nb2, double *weights, double *part,
 									   TeaserGnc *S);
+
+// ---- k_teaser_clique.hip: the device clique search (teaser_search.h has the scheme)
+// later[v] = the neighbours of v above v in the m x ceil(m / 64) matrix sub
+hipError_t launch_teaser_later(hipStream_t st, const uint64_t *sub, uint32_t m, uint32_t *later);
+struct TeaserSearchArgs
+{
+	const uint64_t *sub;   // m x W
+	const uint32_t *first; // m + 1: TeaserPlan::first
+	uint32_t m, W, n_tasks, levels;
+	uint32_t phase, omega; // 0: the size (ctl->bound rises from lb); 1: the list of omega vertices
+	uint32_t quota, workers;
+	TeaserSearchCtl *ctl;
+	TeaserWorkerState *state; // workers
+	uint64_t *slab;			  // workers x levels x W: the stacks
+	uint32_t *cur;			  // workers x levels: the cliques so far
+};
+// one launch: every worker enters at most `quota` tree nodes
+hipError_t launch_teaser_clique(hipStream_t st, const TeaserSearchArgs &A);
+// out[0] = size, out[1 .. size] = the greedy clique of vertex v in the order taken; out: m + 1 words
+hipError_t launch_teaser_witness(hipStream_t st, const uint64_t *sub, uint32_t m, uint32_t v, uint32_t *out);

@@ -6,6 +6,9 @@ pairs next to it.  The search is given --budget nodes (default 2^20, so that a t
 
     python tools/gpu_teaser.py                 the table
     python tools/gpu_teaser.py --calls 3       three calls per case and nothing else: the run to put under `rocprofv3 --kernel-trace --stats -- ...`
+    python tools/gpu_teaser.py --search both   the clique search on the host, on the device (MULLS_OPT_TEASER_DEVICE_SEARCH) or both: with `both`, one call of
+                                               each per case, search_seconds and clique_nodes of either, and whether every result field agrees
+    --cases fixed2000_0_15:1.0,nn_15_0:0.25    only these rows (pair list of tests/golden/ncc_demo.npz : bound); with --search device --calls 1, the run to trace the search's kernels with
 """
 import os
 import sys
@@ -36,9 +39,29 @@ def random_pairs(seed, n, share=0.05, bound=1.0):
     return rec[0], rec[1], idx, idx
 
 
+FIELDS = ("status", "n_edges", "max_core", "clique_size", "clique_exact", "gnc_iterations", "n_rotation_inliers", "n_translation_inliers")
+
+
+def compare(ctx, name, nb, kt, ks, ti, si, P):
+    """one call with the host search and one with the device search on the same context: the two efforts, and whether every result field agrees"""
+    got = {}
+    for side, value in (("host", 0), ("device", 1)):
+        ctx.set_option(abi.OPT_TEASER_DEVICE_SEARCH, value)
+        t0 = time.perf_counter()
+        res, clique = ctx.coarse_reg_teaser(kt, ks, P, tgt_idx=ti, src_idx=si)
+        got[side] = (res, clique, time.perf_counter() - t0)
+    (a, ca, ta), (b, cb, tb) = got["host"], got["device"]
+    same = all(getattr(a, f) == getattr(b, f) for f in FIELDS) and np.array_equal(ca, cb) and bytes(a.T) == bytes(b.T) and np.float64(a.cost).tobytes() == np.float64(b.cost).tobytes()
+    print("%-15s N %5d  bound %.2f  clique %4d | host search %12.3f ms %10d nodes (%s), call %12.3f ms | device search %12.3f ms %10d nodes (%s), call %12.3f ms | every field %s"
+          % (name, len(ti), nb, a.clique_size, a.search_seconds * 1e3, a.clique_nodes, "exact" if a.clique_exact else "budget", ta * 1e3, b.search_seconds * 1e3, b.clique_nodes,
+             "exact" if b.clique_exact else "budget", tb * 1e3, "agrees" if same else "DIFFERS"), flush=True)
+
+
 def main():
     arg = lambda k, d: type(d)(sys.argv[sys.argv.index(k) + 1]) if k in sys.argv else d  # noqa: E731
-    calls, budget = arg("--calls", 0), arg("--budget", 1 << 20)
+    calls, budget, search, only = arg("--calls", 0), arg("--budget", 1 << 20), arg("--search", "host"), arg("--cases", "")
+    if search not in ("host", "device", "both"):
+        raise SystemExit("--search host|device|both")
     Z = np.load(os.path.join(ROOT, "tests", "golden", "ncc_demo.npz"))
     cases = []
     for name in ("fixed300_0_15", "recip_0_15", "fixed2000_0_15", "nn_0_15"):
@@ -46,9 +69,20 @@ def main():
         for nb in (0.25, 1.0):
             cases.append((name, nb, Z["kpts_0"], Z["kpts_15"], pr[:, 0], pr[:, 1]))
     cases.append(("random_4000", 1.0) + random_pairs(4000, 4000))
+    if only:  # any pair list of the file, either direction
+        cases = []
+        for c in only.split(","):
+            name, nb = c.split(":")[0], float(c.split(":")[1])
+            a, b = (0, 15) if name.endswith("0_15") else (15, 0)
+            pr = Z[name + "_pairs"]
+            cases.append((name, nb, Z["kpts_%d" % a], Z["kpts_%d" % b], pr[:, 0], pr[:, 1]))
     ctx = lib.Context(0)
+    ctx.set_option(abi.OPT_TEASER_DEVICE_SEARCH, 1 if search == "device" else 0)
     for name, nb, kt, ks, ti, si in cases:
         P = abi.teaser_params(nb, 8, budget)
+        if search == "both":
+            compare(ctx, name, nb, kt, ks, ti, si, P)
+            continue
         RP = abi.ransac_params(nb, 8, 20000, 1)
 
         def call():
