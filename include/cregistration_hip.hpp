@@ -27,6 +27,7 @@
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "mulls_hip.h"
 
@@ -725,6 +726,45 @@ inline int coarse_reg_teaser(const typename pcl::PointCloud<PointT>::Ptr &target
 			for (int r = 0; r < 4; r++)
 				tran_mat(r, c) = R.T[c * 4 + r];
 	return R.status;
+}
+
+// Many coarse_reg_teaser calls in one (mulls_coarse_reg_teaser_batch): the candidate edges of a loop-closure event (test/mulls_slam.cpp:517-557 solves them
+// one after another until one is accepted) or one scan against a list of submaps.  Pair k is targets[k] / sources[k] with trans[k]; the return value's
+// entry k and trans[k] are what coarse_reg_teaser<PointT>(targets[k], sources[k], trans[k], noise_bound, min_inlier_num) returns and writes (trans[k] is
+// untouched on -1).  The three vectors have one length.  INTEGRATION.md shows the loop restructured around it.
+template <typename PointT>
+inline std::vector<int> coarse_reg_teaser_batch(const std::vector<typename pcl::PointCloud<PointT>::Ptr> &targets,
+												const std::vector<typename pcl::PointCloud<PointT>::Ptr> &sources, std::vector<Eigen::Matrix4d> &trans,
+												float noise_bound = 0.2, int min_inlier_num = 8)
+{
+	if (targets.size() != sources.size() || targets.size() != trans.size())
+		throw std::invalid_argument("coarse_reg_teaser_batch: targets, sources and trans must have one length");
+	mulls_ctx *ctx = thread_context();
+	std::vector<mulls_teaser_problem> problems(targets.size());
+	for (size_t k = 0; k < targets.size(); k++)
+	{
+		problems[k] = mulls_teaser_problem();
+		problems[k].tgt = borrow(targets[k]);
+		problems[k].src = borrow(sources[k]);
+	}
+	mulls_teaser_params P;
+	mulls_teaser_default_params(&P);
+	P.noise_bound = noise_bound;
+	P.min_inlier_num = min_inlier_num;
+	std::vector<mulls_teaser_result> R(targets.size());
+	const int rc = mulls_coarse_reg_teaser_batch(ctx, problems.data(), (uint32_t)problems.size(), &P, 0, R.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_coarse_reg_teaser_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	std::vector<int> status(targets.size());
+	for (size_t k = 0; k < targets.size(); k++)
+	{
+		status[k] = R[k].status;
+		if (R[k].status >= 0)
+			for (int c = 0; c < 4; c++)
+				for (int r = 0; r < 4; r++)
+					trans[k](r, c) = R[k].T[c * 4 + r];
+	}
+	return status;
 }
 
 // CFilter<PointT>::sor_filter (include/common/cfilter.hpp:204-222 and :225-247), verbatim signatures (upstream gives no defaults): the statistical

@@ -760,6 +760,38 @@ int mulls_coarse_reg_teaser(mulls_ctx *ctx, const mulls_cloud *tgt_pts, const mu
 int mulls_coarse_reg_teaser_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const int32_t *tgt_idx, const int32_t *src_idx,
 									uint32_t n_corr, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique, uint32_t cap);
 
+/* ---- many TEASER problems per call: the candidate edges of one loop-closure event (test/mulls_slam.cpp:517-596 tries them one after another), or one
+ * scan against a list of submaps.  Until the first success the problems are independent: solve them all, then apply the sequential rule to the results.
+ * results[b] and problems[b].clique[] are THE BITS THE MATCHING SINGLE CALL RETURNS for problem b on the same context options (mulls_coarse_reg_teaser when
+ * both index lists are NULL, mulls_coarse_reg_teaser_indexed when both are set): status, max_core, n_edges, clique_size, clique_exact, gnc_iterations, both
+ * inlier counts, the clique list, every bit of cost and T.  No arithmetic is redefined; the summation orders hold per problem.  search_seconds is a
+ * measurement; clique_nodes equals the single call's when the host search runs and need not repeat under MULLS_OPT_TEASER_DEVICE_SEARCH, as above.
+ * The device steps run for all problems of a sub-batch per launch, and the GNC loop in lock-step: one launch set and one readback per iteration for all
+ * of them, a problem that has stopped is skipped on the device with its record and weights frozen.  The clique search and the
+ * translation run per problem, in index order, as in the single call.
+ *   per problem   upstream's early returns (unequal sizes, N <= 3): status -1, identity T, the clique buffer untouched; the rest of the batch runs.
+ *   whole call    checked for every problem before any device work: a problem the single call would refuse (a bad stride, an index outside its cloud,
+ *                 N > 8192, one index list without the other, a NULL it needs) and a non-finite or negative noise_bound make the call return the single
+ *                 call's code, name the first such problem's index in mulls_last_error, and leave every result at status -1 / identity.
+ *   scratch_limit_bytes  bounds each of the two device arenas the call holds: the graph phase's (the two bit matrices, 2 N ceil(N / 64) 8 bytes per
+ *                 problem, and the small per-problem arrays: 1.0 MB + 16.8 MB at N = 8192) and the GNC phase's weights (C (C - 1) / 2 doubles per
+ *                 problem, C known only after the search).  The batch is cut into consecutive sub-batches that fit, for each phase on its own; a problem
+ *                 larger than the limit runs alone.  0: MULLS_TEASER_BATCH_DEFAULT_SCRATCH_BYTES, a value chosen without a measurement.  The device clique search's workers (per problem, as in the
+ *                 single call) are not counted.
+ * n_problems = 0: MULLS_OK. */
+#define MULLS_TEASER_BATCH_DEFAULT_SCRATCH_BYTES (512ull << 20)
+typedef struct mulls_teaser_problem
+{
+	mulls_cloud tgt, src;			  /* host or device-resident clouds, by the single call's rules (strides included) */
+	const int32_t *tgt_idx, *src_idx; /* both NULL: pair i = point i of each cloud; both set: the n_corr pairs they name */
+	uint32_t n_corr;				  /* read only when the index lists are set */
+	uint32_t clique_cap;
+	int32_t *clique;				  /* clique_cap entries, or NULL with clique_cap = 0 */
+} mulls_teaser_problem;
+
+int mulls_coarse_reg_teaser_batch(mulls_ctx *ctx, const mulls_teaser_problem *problems, uint32_t n_problems, const mulls_teaser_params *params,
+								  uint64_t scratch_limit_bytes, mulls_teaser_result *results);
+
 /* ---- statistical outlier removal: CFilter<PointT>::sor_filter (include/common/cfilter.hpp:204-247) ----
  * The filter of the merged map mulls_slam writes at the end of a run (test/mulls_slam.cpp:1009, sor_filter(pc_map_merged, 20, 2.0) under --map_filter_on).
  * Upstream's body is pcl::StatisticalOutlierRemoval.  PCL is not available where this library is built and tested, so nothing below was checked

@@ -352,7 +352,15 @@ class TeaserResult(C.Structure):
                 ("reserved", C.c_int32), ("cost", C.c_double), ("search_seconds", C.c_double), ("T", C.c_double * 16)]
 
 
+class TeaserProblem(C.Structure):
+    """mulls_teaser_problem: one problem of mulls_coarse_reg_teaser_batch"""
+
+    _fields_ = [("tgt", Cloud), ("src", Cloud), ("tgt_idx", C.c_void_p), ("src_idx", C.c_void_p), ("n_corr", C.c_uint32), ("clique_cap", C.c_uint32),
+                ("clique", C.c_void_p)]
+
+
 TEASER_DEFAULT_NODE_BUDGET = 1 << 28  # MULLS_TEASER_DEFAULT_NODE_BUDGET
+TEASER_BATCH_DEFAULT_SCRATCH_BYTES = 512 << 20  # MULLS_TEASER_BATCH_DEFAULT_SCRATCH_BYTES
 
 
 def teaser_params(noise_bound=0.2, min_inlier_num=8, clique_node_budget=TEASER_DEFAULT_NODE_BUDGET):

@@ -3,10 +3,13 @@
 // core numbers, greedy lower bound, compaction, GNC-TLS rotation), the exact clique search — on the one sub-matrix that comes down (teaser_host.h) or,
 // with MULLS_OPT_TEASER_DEVICE_SEARCH, as a chain of bounded launches on the sub-matrix where it lies (teaser_search.h, k_teaser_clique.hip) — and the
 // serial TLS translation estimate on the clique's points.  include/mulls_hip.h has the definition this file follows.
+// mulls_coarse_reg_teaser_batch runs the same steps for many problems: the device steps per sub-batch (teaser_batch.h plans them, k_teaser_batch.hip runs
+// them, the GNC loop in lock-step), the search and the translation per problem with the code of the single call.
 #include <chrono>
 
 #include "ctx.h"
 #include "ransac_launch.h" // launch_ransac_gather: x, y, z, data[3] out of device records
+#include "teaser_batch_launch.h"
 #include "teaser_host.h"
 #include "teaser_launch.h"
 
@@ -111,6 +114,130 @@ struct DeviceSearch
 		return MULLS_OK;
 	}
 };
+
+// what the device clique search uses besides the workers' scratch: words per kept vertex and the control records, on the device and pinned
+struct DeviceSearchBuffers
+{
+	uint32_t *later, *first; // m and m + 1 words
+	TeaserSearchCtl *ctl;
+	uint32_t *list; // m + 1 words
+	uint32_t *h_later; // m + 1 words
+	TeaserSearchCtl *h_ctl; // two
+	uint32_t *h_list;
+	TeaserWorkerState *h_init, *h_back; // MULLS_TEASER_SEARCH_WORKERS each
+};
+
+// the exact search on the device, on the m x ceil(m / 64) sub-matrix where it lies; clique: original vertex numbers (h_keep maps the kept ones back)
+int device_clique_search(mulls_ctx *ctx, mulls_teaser_scratch &sc, hipStream_t st, const char *who, const uint64_t *sub, uint32_t m, uint32_t lb, uint32_t max_core,
+						 uint32_t witness_at, uint64_t node_budget, const DeviceSearchBuffers &B, const int32_t *h_keep, mulls_teaser_result *result,
+						 std::vector<uint32_t> *clique_out)
+{
+	std::vector<uint32_t> &clique = *clique_out;
+	const uint32_t Wm = (m + 63u) / 64u;
+	// the sub-matrix stays where it is: the plan needs one count per kept vertex, the control a few words per launch
+	const auto tic = std::chrono::steady_clock::now();
+	uint32_t *later = B.later, *h_later = B.h_later;
+	HIPCHK(ctx, launch_teaser_later(st, sub, m, later));
+	HIPCHK(ctx, hipMemcpyAsync(h_later, later, (size_t)m * 4u, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	TeaserPlan plan;
+	teaser_plan(h_later, m, lb, max_core, plan);
+	DeviceSearch ex;
+	ex.ctx = ctx, ex.st = st, ex.witness_at = witness_at;
+	TeaserSearchArgs &A = ex.A;
+	A.sub = sub, A.first = B.first;
+	A.m = m, A.W = Wm, A.n_tasks = plan.n_tasks, A.levels = plan.levels;
+	A.phase = 0, A.omega = lb, A.quota = MULLS_TEASER_SEARCH_QUOTA, A.workers = teaser_plan_workers(plan);
+	size_t soff = 0;
+	auto stake = [&](size_t bytes) {
+		const size_t at = soff;
+		soff += up256(bytes);
+		return at;
+	};
+	const size_t s_state = stake((size_t)A.workers * sizeof(TeaserWorkerState)), s_cur = stake((size_t)A.workers * A.levels * 4u);
+	const size_t s_slab = stake((size_t)A.workers * A.levels * Wm * 8u);
+	if (int rc = grow(ctx, &sc.search, &sc.search_cap, soff))
+		return rc;
+	A.ctl = B.ctl;
+	A.state = reinterpret_cast<TeaserWorkerState *>(sc.search + s_state);
+	A.cur = reinterpret_cast<uint32_t *>(sc.search + s_cur), A.slab = reinterpret_cast<uint64_t *>(sc.search + s_slab);
+	ex.h_ctl = B.h_ctl;
+	ex.h_init = B.h_init, ex.h_back = B.h_back;
+	ex.h_list = B.h_list, ex.d_list = B.list;
+	for (uint32_t w = 0; w < A.workers; w++)
+		ex.h_init[w] = TeaserWorkerState{0, 0, 0, 0, MULLS_TEASER_NO_RANK, {0, 0, 0}};
+	std::memcpy(h_later, plan.first.data(), ((size_t)m + 1u) * 4u); // (the counts are in the plan now)
+	HIPCHK(ctx, hipMemcpyAsync(B.first, h_later, ((size_t)m + 1u) * 4u, hipMemcpyHostToDevice, st));
+	TeaserSearchOutcome found;
+	if (int rc = teaser_search_control(ex, plan, max_core, node_budget, found))
+	{
+		if (rc != MULLS_TEASER_SEARCH_FAILED)
+			return rc;
+		ctx->err = std::string(who) + ": the device clique search left the states its plan allows";
+		return MULLS_E_HIP;
+	}
+	result->search_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
+	result->clique_nodes = found.nodes;
+	result->clique_exact = found.exact ? 1 : 0;
+	if (found.clique.size() != (found.exact ? found.omega : lb))
+	{
+		ctx->err = std::string(who) + ": the device clique search's list does not have the size it proved";
+		return MULLS_E_HIP;
+	}
+	for (uint32_t v : found.clique)
+		clique.push_back((uint32_t)h_keep[v]);
+	return MULLS_OK;
+}
+
+// the exact search on the host, on the downloaded sub-matrix
+int host_clique_search(mulls_ctx *ctx, const char *who, const uint64_t *h_sub, uint32_t m, uint32_t lb, uint32_t witness_at, uint64_t node_budget,
+					   const int32_t *h_keep, mulls_teaser_result *result, std::vector<uint32_t> *clique_out)
+{
+	std::vector<uint32_t> &clique = *clique_out;
+	const uint32_t Wm = (m + 63u) / 64u;
+	TeaserBits G;
+	G.m = m, G.W = Wm, G.rows = h_sub;
+	const auto tic = std::chrono::steady_clock::now();
+	std::vector<uint32_t> witness;
+	teaser_greedy_clique(G, witness_at, witness);
+	if (witness.size() != lb)
+	{
+		ctx->err = std::string(who) + ": the greedy clique's witness does not have the size the device counted";
+		return MULLS_E_HIP;
+	}
+	TeaserSearch search;
+	search.run(G, lb, witness, node_budget);
+	result->search_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
+	result->clique_nodes = search.nodes;
+	result->clique_exact = search.aborted ? 0 : 1;
+	for (uint32_t v : search.best_clique)
+		clique.push_back((uint32_t)h_keep[v]);
+	return MULLS_OK;
+}
+
+// what follows the GNC loop: the counts, the serial TLS translation on the clique's points (already down) and R, the outcome
+void teaser_finish(const TeaserGnc &G, int iters, const float *h_cs, const float *h_ct, uint32_t C, double nb, const mulls_teaser_params *params,
+				   mulls_teaser_result *result)
+{
+	const uint64_t M = (uint64_t)C * (C - 1u) / 2u;
+	result->gnc_iterations = iters;
+	result->cost = G.cost;
+	const uint64_t n_rot = G.stop == 1u ? M : (uint64_t)G.n_inlier;
+	result->n_rotation_inliers = (int32_t)n_rot;
+
+	// the translation: serial, on the clique's points (already down) and R
+	double that[3];
+	result->n_translation_inliers = (int32_t)teaser_translation(h_cs, h_ct, C, G.R, nb, that);
+	const long long min_in = params->min_inlier_num;
+	result->status = (long long)n_rot >= 2 * min_in ? 1 : ((long long)n_rot >= min_in ? 0 : -1);
+	if (result->status >= 0)
+		for (int r = 0; r < 3; r++)
+		{
+			for (int c = 0; c < 3; c++)
+				result->T[c * 4 + r] = G.R[r * 3 + c];
+			result->T[12 + r] = that[r];
+		}
+}
 
 int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src_in, const int32_t *tgt_idx, const int32_t *src_idx, uint32_t n_corr,
 			   bool indexed, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique_out, uint32_t cap)
@@ -267,80 +394,22 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 		HIPCHK(ctx, launch_teaser_compact(st, adj, n, reinterpret_cast<const int32_t *>(d + o_keep), m, sub));
 		if (device_search)
 		{
-			// the sub-matrix stays where it is: the plan needs one count per kept vertex, the control a few words per launch
-			const auto tic = std::chrono::steady_clock::now();
-			uint32_t *later = reinterpret_cast<uint32_t *>(d + o_later), *h_later = reinterpret_cast<uint32_t *>(h + p_later);
-			HIPCHK(ctx, launch_teaser_later(st, sub, m, later));
-			HIPCHK(ctx, hipMemcpyAsync(h_later, later, (size_t)m * 4u, hipMemcpyDeviceToHost, st));
-			HIPCHK(ctx, hipStreamSynchronize(st));
-			TeaserPlan plan;
-			teaser_plan(h_later, m, lb, max_core, plan);
-			DeviceSearch ex;
-			ex.ctx = ctx, ex.st = st, ex.witness_at = witness_at;
-			TeaserSearchArgs &A = ex.A;
-			A.sub = sub, A.first = reinterpret_cast<const uint32_t *>(d + o_first);
-			A.m = m, A.W = Wm, A.n_tasks = plan.n_tasks, A.levels = plan.levels;
-			A.phase = 0, A.omega = lb, A.quota = MULLS_TEASER_SEARCH_QUOTA, A.workers = teaser_plan_workers(plan);
-			size_t soff = 0;
-			auto stake = [&](size_t bytes) {
-				const size_t at = soff;
-				soff += up256(bytes);
-				return at;
-			};
-			const size_t s_state = stake((size_t)A.workers * sizeof(TeaserWorkerState)), s_cur = stake((size_t)A.workers * A.levels * 4u);
-			const size_t s_slab = stake((size_t)A.workers * A.levels * Wm * 8u);
-			if (int rc = grow(ctx, &sc.search, &sc.search_cap, soff))
+			DeviceSearchBuffers B;
+			B.later = reinterpret_cast<uint32_t *>(d + o_later), B.first = reinterpret_cast<uint32_t *>(d + o_first);
+			B.ctl = reinterpret_cast<TeaserSearchCtl *>(d + o_ctl), B.list = reinterpret_cast<uint32_t *>(d + o_list);
+			B.h_later = reinterpret_cast<uint32_t *>(h + p_later), B.h_ctl = reinterpret_cast<TeaserSearchCtl *>(h + p_ctl);
+			B.h_list = reinterpret_cast<uint32_t *>(h + p_list);
+			B.h_init = reinterpret_cast<TeaserWorkerState *>(h + p_init), B.h_back = reinterpret_cast<TeaserWorkerState *>(h + p_back);
+			if (int rc = device_clique_search(ctx, sc, st, who, sub, m, lb, max_core, witness_at, params->clique_node_budget, B, h_keep, result, &clique))
 				return rc;
-			A.ctl = reinterpret_cast<TeaserSearchCtl *>(d + o_ctl);
-			A.state = reinterpret_cast<TeaserWorkerState *>(sc.search + s_state);
-			A.cur = reinterpret_cast<uint32_t *>(sc.search + s_cur), A.slab = reinterpret_cast<uint64_t *>(sc.search + s_slab);
-			ex.h_ctl = reinterpret_cast<TeaserSearchCtl *>(h + p_ctl);
-			ex.h_init = reinterpret_cast<TeaserWorkerState *>(h + p_init), ex.h_back = reinterpret_cast<TeaserWorkerState *>(h + p_back);
-			ex.h_list = reinterpret_cast<uint32_t *>(h + p_list), ex.d_list = reinterpret_cast<uint32_t *>(d + o_list);
-			for (uint32_t w = 0; w < A.workers; w++)
-				ex.h_init[w] = TeaserWorkerState{0, 0, 0, 0, MULLS_TEASER_NO_RANK, {0, 0, 0}};
-			std::memcpy(h_later, plan.first.data(), ((size_t)m + 1u) * 4u); // (the counts are in the plan now)
-			HIPCHK(ctx, hipMemcpyAsync(d + o_first, h_later, ((size_t)m + 1u) * 4u, hipMemcpyHostToDevice, st));
-			TeaserSearchOutcome found;
-			if (int rc = teaser_search_control(ex, plan, max_core, params->clique_node_budget, found))
-			{
-				if (rc != MULLS_TEASER_SEARCH_FAILED)
-					return rc;
-				ctx->err = std::string(who) + ": the device clique search left the states its plan allows";
-				return MULLS_E_HIP;
-			}
-			result->search_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
-			result->clique_nodes = found.nodes;
-			result->clique_exact = found.exact ? 1 : 0;
-			if (found.clique.size() != (found.exact ? found.omega : lb))
-			{
-				ctx->err = std::string(who) + ": the device clique search's list does not have the size it proved";
-				return MULLS_E_HIP;
-			}
-			for (uint32_t v : found.clique)
-				clique.push_back((uint32_t)h_keep[v]);
 		}
 		else
 		{
 			HIPCHK(ctx, hipMemcpyAsync(h + p_sub, sub, (size_t)m * Wm * 8u, hipMemcpyDeviceToHost, st));
 			HIPCHK(ctx, hipStreamSynchronize(st));
-			TeaserBits G;
-			G.m = m, G.W = Wm, G.rows = reinterpret_cast<const uint64_t *>(h + p_sub);
-			const auto tic = std::chrono::steady_clock::now();
-			std::vector<uint32_t> witness;
-			teaser_greedy_clique(G, witness_at, witness);
-			if (witness.size() != lb)
-			{
-				ctx->err = std::string(who) + ": the greedy clique's witness does not have the size the device counted";
-				return MULLS_E_HIP;
-			}
-			TeaserSearch search;
-			search.run(G, lb, witness, params->clique_node_budget);
-			result->search_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - tic).count();
-			result->clique_nodes = search.nodes;
-			result->clique_exact = search.aborted ? 0 : 1;
-			for (uint32_t v : search.best_clique)
-				clique.push_back((uint32_t)h_keep[v]);
+			if (int rc = host_clique_search(ctx, who, reinterpret_cast<const uint64_t *>(h + p_sub), m, lb, witness_at, params->clique_node_budget, h_keep, result,
+											&clique))
+				return rc;
 		}
 	}
 	const uint32_t C = (uint32_t)clique.size();
@@ -378,23 +447,319 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 		if (G.stop)
 			break;
 	}
-	result->gnc_iterations = iters;
-	result->cost = G.cost;
-	const uint64_t n_rot = G.stop == 1u ? M : (uint64_t)G.n_inlier;
-	result->n_rotation_inliers = (int32_t)n_rot;
+	teaser_finish(G, iters, reinterpret_cast<const float *>(h + p_cs), reinterpret_cast<const float *>(h + p_cs + (size_t)n * 16u), C, nb, params, result);
+	return MULLS_OK;
+}
+// ---- mulls_coarse_reg_teaser_batch
+void reset_result(mulls_teaser_result *result)
+{
+	std::memset(result, 0, sizeof(*result));
+	result->status = -1;
+	for (int k = 0; k < 16; k++)
+		result->T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+}
 
-	// the translation: serial, on the clique's points (already down) and R
-	double that[3];
-	result->n_translation_inliers =
-		(int32_t)teaser_translation(reinterpret_cast<const float *>(h + p_cs), reinterpret_cast<const float *>(h + p_cs + (size_t)n * 16u), C, G.R, nb, that);
-	const long long min_in = params->min_inlier_num;
-	result->status = (long long)n_rot >= 2 * min_in ? 1 : ((long long)n_rot >= min_in ? 0 : -1);
-	if (result->status >= 0)
-		for (int r = 0; r < 3; r++)
+struct BatchProblem // a problem that reaches the device
+{
+	uint32_t index, n;
+	bool indexed, t_dev, s_dev;
+};
+
+const char *const BATCH = "mulls_coarse_reg_teaser_batch";
+
+// one graph-phase sub-batch: `count` problems whose arena fits the limit (or one that does not)
+int teaser_sub_batch(mulls_ctx *ctx, const mulls_teaser_problem *problems, const BatchProblem *act, uint32_t count, const mulls_teaser_params *params,
+					 uint64_t limit, mulls_teaser_result *results)
+{
+	mulls_teaser_scratch &sc = *ctx->teaser;
+	const bool device_search = ctx->opt[MULLS_OPT_TEASER_DEVICE_SEARCH] != 0.0;
+	std::vector<uint32_t> sizes(count);
+	uint32_t n_max = 0;
+	for (uint32_t k = 0; k < count; k++)
+		sizes[k] = act[k].n, n_max = std::max(n_max, act[k].n);
+	TeaserBatchLayout L;
+	teaser_batch_layout(sizes.data(), count, &L);
+	// behind the arena: what the device search needs besides its workers, once for the sub-batch (the problems are searched one after another)
+	size_t off = L.dev_bytes, poff = L.pin_bytes;
+	auto take = [&](size_t bytes) {
+		const size_t at = off;
+		off += up256(bytes);
+		return at;
+	};
+	auto ptake = [&](size_t bytes) {
+		const size_t at = poff;
+		poff += up256(bytes);
+		return at;
+	};
+	const size_t o_later = take(device_search ? (size_t)n_max * 4u : 0u), o_first = take(device_search ? ((size_t)n_max + 1u) * 4u : 0u);
+	const size_t o_ctl = take(sizeof(TeaserSearchCtl)), o_list = take(device_search ? ((size_t)n_max + 1u) * 4u : 0u);
+	const size_t p_later = ptake(device_search ? ((size_t)n_max + 1u) * 4u : 0u), p_ctl = ptake(2u * sizeof(TeaserSearchCtl));
+	const size_t p_list = ptake(device_search ? ((size_t)n_max + 1u) * 4u : 0u);
+	const size_t p_init = ptake(device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u);
+	const size_t p_back = ptake(device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u);
+	if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
+		return rc;
+	if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, poff, hipHostMallocDefault))
+		return rc;
+	unsigned char *d = sc.dev, *h = sc.pin;
+	hipStream_t st = ctx->stream;
+	mulls::StreamDrain drain{st};
+	const TeaserBatchDesc *d_desc = reinterpret_cast<const TeaserBatchDesc *>(d + L.o_desc);
+	auto put_desc = [&]() { // (the pinned copy is rewritten only behind a synchronisation)
+		std::memcpy(h + L.p_desc, L.desc.data(), sizeof(TeaserBatchDesc) * count);
+		return hipMemcpyAsync(d + L.o_desc, h + L.p_desc, sizeof(TeaserBatchDesc) * count, hipMemcpyHostToDevice, st);
+	};
+
+	// staging: the host clouds packed into the pinned mirror of the points and up in one copy; device clouds gathered by one launch
+	TeaserBatchGather *jobs = reinterpret_cast<TeaserBatchGather *>(h + L.p_jobs);
+	uint32_t n_jobs = 0;
+	bool any_host = false, any_idx = false;
+	for (uint32_t k = 0; k < count; k++)
+	{
+		const mulls_teaser_problem &P = problems[act[k].index];
+		const TeaserBatchDesc &D = L.desc[k];
+		const uint32_t n = D.n;
+		int32_t *h_idx = reinterpret_cast<int32_t *>(h + L.p_idx + (D.idx - L.o_idx));
+		if (act[k].indexed && (act[k].t_dev || act[k].s_dev))
 		{
-			for (int c = 0; c < 3; c++)
-				result->T[c * 4 + r] = G.R[r * 3 + c];
-			result->T[12 + r] = that[r];
+			std::memcpy(h_idx, P.tgt_idx, (size_t)n * 4u);
+			std::memcpy(h_idx + n, P.src_idx, (size_t)n * 4u);
+			any_idx = true;
+		}
+		if (act[k].t_dev)
+			jobs[n_jobs++] = TeaserBatchGather{static_cast<const unsigned char *>(P.tgt.pts), D.idx, D.tgt, n, act[k].indexed ? 1u : 0u};
+		else
+			pack_xyzw(P.tgt, act[k].indexed ? P.tgt_idx : nullptr, n, reinterpret_cast<float *>(h + L.p_pts + (D.tgt - L.o_pts))), any_host = true;
+		if (act[k].s_dev)
+			jobs[n_jobs++] = TeaserBatchGather{static_cast<const unsigned char *>(P.src.pts), D.idx + (uint64_t)n * 4u, D.src, n, act[k].indexed ? 1u : 0u};
+		else
+			pack_xyzw(P.src, act[k].indexed ? P.src_idx : nullptr, n, reinterpret_cast<float *>(h + L.p_pts + (D.src - L.o_pts))), any_host = true;
+	}
+	if (any_host) // (the places of device-resident clouds go up as they are and are gathered over below)
+		HIPCHK(ctx, hipMemcpyAsync(d + L.o_pts, h + L.p_pts, L.pts_bytes, hipMemcpyHostToDevice, st));
+	if (any_idx)
+		HIPCHK(ctx, hipMemcpyAsync(d + L.o_idx, h + L.p_idx, L.idx_bytes, hipMemcpyHostToDevice, st));
+	if (n_jobs)
+	{
+		HIPCHK(ctx, hipMemcpyAsync(d + L.o_jobs, jobs, sizeof(TeaserBatchGather) * n_jobs, hipMemcpyHostToDevice, st));
+		HIPCHK(ctx, launch_teaser_batch_gather(st, reinterpret_cast<const TeaserBatchGather *>(d + L.o_jobs), n_jobs, n_max, d));
+	}
+
+	// the graphs, their core numbers and the greedy clique sizes
+	const double nb = (double)params->noise_bound, beta = (2.0 * nb) * sqrt(1.0);
+	HIPCHK(ctx, put_desc());
+	HIPCHK(ctx, hipMemsetAsync(d + L.o_sum, 0, (size_t)8u * count, st));
+	HIPCHK(ctx, launch_teaser_batch_graph(st, d_desc, count, n_max, d, beta, reinterpret_cast<unsigned long long *>(d + L.o_sum)));
+	HIPCHK(ctx, hipMemcpyAsync(h + L.p_core, d + L.o_core, L.core_bytes, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipMemcpyAsync(h + L.p_sum, d + L.o_sum, (size_t)8u * count, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	std::vector<uint32_t> m(count, 0u), lbs(count), cores(count), witness_at(count, 0u), Cs(count, 0u);
+	uint64_t words_max = 0;
+	for (uint32_t k = 0; k < count; k++)
+	{
+		const TeaserBatchDesc &D = L.desc[k];
+		mulls_teaser_result *result = &results[act[k].index];
+		const uint32_t n = D.n;
+		const uint32_t *h_core = reinterpret_cast<const uint32_t *>(h + L.p_core + (D.core - L.o_core)), *h_greedy = h_core + n;
+		unsigned long long deg_sum;
+		std::memcpy(&deg_sum, h + L.p_sum + (size_t)8u * k, 8);
+		result->n_edges = deg_sum / 2u;
+		uint32_t max_core = 0, lb = 0, lb_v = 0;
+		for (uint32_t i = 0; i < n; i++)
+		{
+			max_core = std::max(max_core, h_core[i]);
+			if (h_greedy[i] > lb)
+				lb = h_greedy[i], lb_v = i;
+		}
+		result->max_core = (int32_t)max_core;
+		result->clique_exact = 1;
+		lbs[k] = lb, cores[k] = max_core;
+		if (lb <= 1u)
+			continue; // no edge: nothing to search
+		int32_t *h_keep = reinterpret_cast<int32_t *>(h + L.p_keep + (D.keep - L.o_keep));
+		for (uint32_t i = 0; i < n; i++)
+			if (h_core[i] + 1u >= lb)
+			{
+				if (i == lb_v)
+					witness_at[k] = m[k];
+				h_keep[m[k]++] = (int32_t)i;
+			}
+		words_max = std::max<uint64_t>(words_max, (uint64_t)m[k] * ((m[k] + 63u) / 64u));
+	}
+	const uint64_t sub_bytes = teaser_batch_pack_sub(&L, m.data());
+	HIPCHK(ctx, put_desc());
+	HIPCHK(ctx, hipMemcpyAsync(d + L.o_keep, h + L.p_keep, L.keep_bytes, hipMemcpyHostToDevice, st));
+	HIPCHK(ctx, launch_teaser_batch_compact(st, d_desc, count, words_max, d));
+	if (!device_search && sub_bytes)
+		HIPCHK(ctx, hipMemcpyAsync(h + L.p_sub, d + L.o_sub, sub_bytes, hipMemcpyDeviceToHost, st)); // every sub-matrix in one copy
+	HIPCHK(ctx, hipStreamSynchronize(st));
+
+	// the cliques: per problem, in index order, by the single call's searches
+	uint32_t C_max = 0;
+	for (uint32_t k = 0; k < count; k++)
+	{
+		const TeaserBatchDesc &D = L.desc[k];
+		const mulls_teaser_problem &P = problems[act[k].index];
+		mulls_teaser_result *result = &results[act[k].index];
+		int32_t *h_keep = reinterpret_cast<int32_t *>(h + L.p_keep + (D.keep - L.o_keep));
+		std::vector<uint32_t> clique; // original vertex numbers, ascending
+		if (lbs[k] <= 1u)
+			clique.assign(1, 0u);
+		else if (device_search)
+		{
+			DeviceSearchBuffers B;
+			B.later = reinterpret_cast<uint32_t *>(d + o_later), B.first = reinterpret_cast<uint32_t *>(d + o_first);
+			B.ctl = reinterpret_cast<TeaserSearchCtl *>(d + o_ctl), B.list = reinterpret_cast<uint32_t *>(d + o_list);
+			B.h_later = reinterpret_cast<uint32_t *>(h + p_later), B.h_ctl = reinterpret_cast<TeaserSearchCtl *>(h + p_ctl);
+			B.h_list = reinterpret_cast<uint32_t *>(h + p_list);
+			B.h_init = reinterpret_cast<TeaserWorkerState *>(h + p_init), B.h_back = reinterpret_cast<TeaserWorkerState *>(h + p_back);
+			if (int rc = device_clique_search(ctx, sc, st, BATCH, reinterpret_cast<const uint64_t *>(d + D.sub), m[k], lbs[k], cores[k], witness_at[k],
+											  params->clique_node_budget, B, h_keep, result, &clique))
+				return rc;
+		}
+		else if (int rc = host_clique_search(ctx, BATCH, reinterpret_cast<const uint64_t *>(h + L.p_sub + (D.sub - L.o_sub)), m[k], lbs[k], witness_at[k],
+											 params->clique_node_budget, h_keep, result, &clique))
+			return rc;
+		const uint32_t C = (uint32_t)clique.size();
+		result->clique_size = (int32_t)C;
+		for (uint32_t i = 0; i < std::min(C, P.clique_cap); i++)
+			P.clique[i] = (int32_t)clique[i];
+		for (uint32_t i = 0; i < C; i++) // (the kept vertices are not needed any more: the list goes up in their place)
+			h_keep[i] = (int32_t)clique[i];
+		Cs[k] = C, C_max = std::max(C_max, C);
+	}
+	if (C_max <= 1u)
+		return MULLS_OK;
+
+	// the cliques' points, down in one copy; the weights planned now that every C is known
+	const uint64_t cpts_bytes = teaser_batch_pack_clique(&L, Cs.data());
+	HIPCHK(ctx, hipStreamSynchronize(st)); // (the device search's last copies)
+	HIPCHK(ctx, put_desc());
+	HIPCHK(ctx, hipMemcpyAsync(d + L.o_keep, h + L.p_keep, L.keep_bytes, hipMemcpyHostToDevice, st));
+	HIPCHK(ctx, launch_teaser_batch_pick(st, d_desc, count, C_max, d));
+	HIPCHK(ctx, hipMemcpyAsync(h + L.p_cpts, d + L.o_cpts, cpts_bytes, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	std::vector<uint64_t> wbytes(count);
+	for (uint32_t k = 0; k < count; k++)
+		wbytes[k] = teaser_batch_weight_bytes(Cs[k]);
+	std::vector<uint32_t> cuts;
+	teaser_batch_cuts(wbytes.data(), count, limit, &cuts);
+	double nb2 = nb * nb;
+	if (nb2 < 1e-16)
+		nb2 = 1e-2;
+	TeaserGnc *d_gnc = reinterpret_cast<TeaserGnc *>(d + L.o_gnc);
+	uint32_t *d_frozen = reinterpret_cast<uint32_t *>(d + L.o_frozen);
+	std::vector<int> iters(count, 0);
+	std::vector<char> stopped(count);
+	for (size_t c = 0; c + 1 < cuts.size(); c++)
+	{
+		// the rotations of the problems g0 .. g1: GNC-TLS in lock-step, one launch set and one readback of the records per iteration
+		const uint32_t g0 = cuts[c], g1 = cuts[c + 1];
+		const uint64_t w_total = teaser_batch_place_weights(&L, g0, g1);
+		uint32_t running = 0;
+		uint64_t M_max = 0;
+		for (uint32_t k = g0; k < g1; k++)
+		{
+			stopped[k] = Cs[k] < 2u;
+			running += Cs[k] >= 2u;
+			M_max = std::max(M_max, L.desc[k].M);
+		}
+		if (!running)
+			continue;
+		if (int rc = grow(ctx, &sc.weights, &sc.weights_cap, (size_t)(w_total / 8u)))
+			return rc;
+		HIPCHK(ctx, put_desc());
+		HIPCHK(ctx, hipMemsetAsync(d_frozen, 0, (size_t)4u * count, st));
+		const TeaserGnc *h_gnc = reinterpret_cast<const TeaserGnc *>(h + L.p_gnc);
+		for (int it = 0; it < MULLS_TEASER_GNC_MAX_ITER && running; it++)
+		{
+			HIPCHK(ctx, launch_teaser_batch_gnc_iteration(st, d_desc, g0, g1 - g0, M_max, it, nb2, d, reinterpret_cast<unsigned char *>(sc.weights), d_gnc, d_frozen));
+			HIPCHK(ctx, hipMemcpyAsync(h + L.p_gnc + sizeof(TeaserGnc) * g0, d_gnc + g0, sizeof(TeaserGnc) * (g1 - g0), hipMemcpyDeviceToHost, st));
+			HIPCHK(ctx, hipStreamSynchronize(st));
+			for (uint32_t k = g0; k < g1; k++)
+				if (!stopped[k])
+				{
+					iters[k] = it + 1;
+					if (h_gnc[k].stop)
+						stopped[k] = 1, running--;
+				}
+		}
+		// the translations: serial, on the cliques' points (already down) and R (a stopped problem's record is as its last iteration left it)
+		for (uint32_t k = g0; k < g1; k++)
+			if (Cs[k] >= 2u)
+			{
+				TeaserGnc G;
+				std::memcpy(&G, &h_gnc[k], sizeof(G));
+				const TeaserBatchDesc &D = L.desc[k];
+				teaser_finish(G, iters[k], reinterpret_cast<const float *>(h + L.p_cpts + (D.cs - L.o_cpts)),
+							  reinterpret_cast<const float *>(h + L.p_cpts + (D.ct - L.o_cpts)), Cs[k], nb, params, &results[act[k].index]);
+			}
+	}
+	return MULLS_OK;
+}
+
+int teaser_batch_run(mulls_ctx *ctx, const mulls_teaser_problem *problems, uint32_t n_problems, const mulls_teaser_params *params, uint64_t limit,
+					 mulls_teaser_result *results)
+{
+	if (!ctx || !params || (n_problems && (!problems || !results)))
+		return MULLS_E_INVALID;
+	for (uint32_t b = 0; b < n_problems; b++)
+		reset_result(&results[b]);
+	if (!n_problems)
+		return MULLS_OK;
+	if (!std::isfinite(params->noise_bound) || params->noise_bound < 0.0f)
+	{
+		ctx->err = std::string(BATCH) + ": noise_bound is not finite or negative";
+		return MULLS_E_INVALID;
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	// every problem is checked before any device work: the single call's refusals, in its order, the first one found named
+	std::vector<BatchProblem> act;
+	for (uint32_t b = 0; b < n_problems; b++)
+	{
+		const mulls_teaser_problem &P = problems[b];
+		auto refuse = [&](int code, const char *why) {
+			ctx->err = std::string(BATCH) + ": problem " + std::to_string(b) + ": " + why;
+			return code;
+		};
+		const mulls_cloud &T = P.tgt, &S = P.src;
+		if ((T.n && !T.pts) || (S.n && !S.pts) || (P.clique_cap && !P.clique) || (P.tgt_idx == nullptr) != (P.src_idx == nullptr))
+			return refuse(MULLS_E_INVALID, "a NULL cloud, clique buffer or index list");
+		BatchProblem A;
+		A.index = b, A.indexed = P.tgt_idx != nullptr, A.n = A.indexed ? P.n_corr : T.n;
+		if (!A.indexed && T.n != S.n)
+			continue; // upstream: "source points number != target points number", -1
+		if (A.n <= 3u)
+			continue; // upstream: "too few correspondences", -1
+		if (A.n > MULLS_TEASER_MAX_POINTS)
+			return refuse(MULLS_E_UNSUPPORTED, "at most 8192 pairs");
+		if (A.indexed)
+			for (uint32_t i = 0; i < A.n; i++)
+				if (P.tgt_idx[i] < 0 || (uint32_t)P.tgt_idx[i] >= T.n || P.src_idx[i] < 0 || (uint32_t)P.src_idx[i] >= S.n)
+					return refuse(MULLS_E_INVALID, "an index lies outside its cloud");
+		A.t_dev = cloud_on_device(ctx, T), A.s_dev = cloud_on_device(ctx, S);
+		if ((A.t_dev && T.stride != MULLS_POINT_BYTES) || (A.s_dev && S.stride != MULLS_POINT_BYTES) || (!A.t_dev && (T.stride < 16u || T.stride % 4u)) ||
+			(!A.s_dev && (S.stride < 16u || S.stride % 4u)))
+			return refuse(MULLS_E_INVALID, "stride (device clouds: 48; host clouds: a multiple of 4, at least 16)");
+		act.push_back(A);
+	}
+	if (act.empty())
+		return MULLS_OK;
+	if (!ctx->teaser)
+		ctx->teaser = new mulls_teaser_scratch();
+	if (!limit)
+		limit = MULLS_TEASER_BATCH_DEFAULT_SCRATCH_BYTES;
+	std::vector<uint64_t> bytes(act.size());
+	for (size_t k = 0; k < act.size(); k++)
+		bytes[k] = teaser_batch_problem_bytes(act[k].n);
+	std::vector<uint32_t> cuts;
+	teaser_batch_cuts(bytes.data(), (uint32_t)act.size(), limit, &cuts);
+	for (size_t c = 0; c + 1 < cuts.size(); c++)
+		if (int rc = teaser_sub_batch(ctx, problems, &act[cuts[c]], cuts[c + 1] - cuts[c], params, limit, results))
+		{
+			for (uint32_t b = 0; b < n_problems; b++)
+				reset_result(&results[b]);
+			return rc;
 		}
 	return MULLS_OK;
 }
@@ -427,6 +792,17 @@ extern "C"
 	try
 	{
 		return teaser_run(ctx, tgt_kpts, src_kpts, tgt_idx, src_idx, n_corr, true, params, result, clique, cap);
+	}
+	catch (...)
+	{
+		return mulls::abi_caught(ctx);
+	}
+
+	int mulls_coarse_reg_teaser_batch(mulls_ctx *ctx, const mulls_teaser_problem *problems, uint32_t n_problems, const mulls_teaser_params *params,
+									  uint64_t scratch_limit_bytes, mulls_teaser_result *results)
+	try
+	{
+		return teaser_batch_run(ctx, problems, n_problems, params, scratch_limit_bytes, results);
 	}
 	catch (...)
 	{

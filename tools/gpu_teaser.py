@@ -8,6 +8,9 @@ pairs next to it.  The search is given --budget nodes (default 2^20, so that a t
     python tools/gpu_teaser.py --calls 3       three calls per case and nothing else: the run to put under `rocprofv3 --kernel-trace --stats -- ...`
     python tools/gpu_teaser.py --search both   the clique search on the host, on the device (MULLS_OPT_TEASER_DEVICE_SEARCH) or both: with `both`, one call of
                                                each per case, search_seconds and clique_nodes of either, and whether every result field agrees
+    python tools/gpu_teaser.py --batch 1,8,64  mulls_coarse_reg_teaser_batch: B copies of a demo pair list (recip_0_15 and fixed300_0_15 at the bound 0.25), and a
+                                               mixed list of B problems (the four small pair lists in turn), through the batch entry and as B single calls on the
+                                               same context: every result field compared, both wall times as the median of 20
     --cases fixed2000_0_15:1.0,nn_15_0:0.25    only these rows (pair list of tests/golden/ncc_demo.npz : bound); with --search device --calls 1, the run to trace the search's kernels with
 """
 import os
@@ -57,11 +60,64 @@ def compare(ctx, name, nb, kt, ks, ti, si, P):
              "exact" if b.clique_exact else "budget", tb * 1e3, "agrees" if same else "DIFFERS"), flush=True)
 
 
+def same_result_but_nodes(a, ca, b, cb):
+    """the device search's effort need not repeat: every field but clique_nodes"""
+    return (all(getattr(a, f) == getattr(b, f) for f in FIELDS) and np.array_equal(ca, cb) and bytes(a.T) == bytes(b.T)
+            and np.float64(a.cost).tobytes() == np.float64(b.cost).tobytes())
+
+
+def same_result(a, ca, b, cb):
+    return same_result_but_nodes(a, ca, b, cb) and a.clique_nodes == b.clique_nodes
+
+
+def batch_mode(sizes, budget, search, calls):
+    """B problems through mulls_coarse_reg_teaser_batch and as B calls of mulls_coarse_reg_teaser_indexed: equality of every field, and the two wall times"""
+    Z = np.load(os.path.join(ROOT, "tests", "golden", "ncc_demo.npz"))
+
+    def problem(name):
+        a, b = (0, 15) if name.endswith("0_15") else (15, 0)
+        pr = Z[name + "_pairs"]
+        return dict(tgt=Z["kpts_%d" % a], src=Z["kpts_%d" % b], tgt_idx=pr[:, 0], src_idx=pr[:, 1])
+
+    small = ("recip_0_15", "fixed300_0_15", "recip_15_0", "fixed300_15_0")
+    ctx = lib.Context(0)
+    ctx.set_option(abi.OPT_TEASER_DEVICE_SEARCH, 1 if search == "device" else 0)
+    P = abi.teaser_params(0.25, 8, budget)
+    for B in sizes:
+        for label, names in (("recip_0_15", ["recip_0_15"] * B), ("fixed300_0_15", ["fixed300_0_15"] * B), ("mixed", [small[k % 4] for k in range(B)])):
+            problems = [problem(n) for n in names]
+
+            def batch():
+                t0 = time.perf_counter()
+                out = ctx.coarse_reg_teaser_batch(problems, P)
+                return time.perf_counter() - t0, out
+
+            def singles():
+                t0 = time.perf_counter()
+                out = [ctx.coarse_reg_teaser(q["tgt"], q["src"], P, tgt_idx=q["tgt_idx"], src_idx=q["src_idx"]) for q in problems]
+                return time.perf_counter() - t0, out
+
+            (_, got), (_, want) = batch(), singles()
+            if calls:  # the run to trace: a few batch calls and nothing else
+                for _ in range(calls - 1):
+                    batch()
+                continue
+            eq = same_result_but_nodes if search == "device" else same_result
+            same = all(eq(a, ca, b, cb) for (a, ca), (b, cb) in zip(got, want))
+            tb, ts = sorted(batch()[0] for _ in range(20)), sorted(singles()[0] for _ in range(20))
+            print("%-14s B %3d  bound 0.25  GNC iterations %s | batch call, median of 20: %9.3f ms (min %.3f, max %.3f) | %d single calls: %9.3f ms (min %.3f, max %.3f)"
+                  " | ratio %.2f | every field %s" % (label, B, sorted(set(r.gnc_iterations for r, _ in got)), tb[10] * 1e3, tb[0] * 1e3, tb[-1] * 1e3, B, ts[10] * 1e3,
+                                                      ts[0] * 1e3, ts[-1] * 1e3, ts[10] / tb[10], "agrees" if same else "DIFFERS"), flush=True)
+    ctx.close()
+
+
 def main():
     arg = lambda k, d: type(d)(sys.argv[sys.argv.index(k) + 1]) if k in sys.argv else d  # noqa: E731
     calls, budget, search, only = arg("--calls", 0), arg("--budget", 1 << 20), arg("--search", "host"), arg("--cases", "")
     if search not in ("host", "device", "both"):
         raise SystemExit("--search host|device|both")
+    if "--batch" in sys.argv:
+        return batch_mode([int(b) for b in arg("--batch", "1").split(",")], budget, search, calls)
     Z = np.load(os.path.join(ROOT, "tests", "golden", "ncc_demo.npz"))
     cases = []
     for name in ("fixed300_0_15", "recip_0_15", "fixed2000_0_15", "nn_0_15"):
