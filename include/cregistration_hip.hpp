@@ -668,6 +668,54 @@ inline bool find_feature_correspondence_ncc(const typename pcl::PointCloud<Point
 	return rc != 0;
 }
 
+// Many find_feature_correspondence_ncc calls in one (mulls_ncc_correspond_batch): the candidate edges of a loop-closure event (test/mulls_slam.cpp:517-557
+// matches them one after another) or one scan against a list of submaps.  Pair k is target_kpts[k] / source_kpts[k]; target_corrs[k], source_corrs[k] and
+// ok[k] are what find_feature_correspondence_ncc<PointT>(target_kpts[k], source_kpts[k], target_corrs[k], source_corrs[k], fixed_num_corr, corr_num,
+// reciprocal_on) appends and returns.  The four cloud vectors have one length, the output clouds exist (they are appended to, as upstream push_backs); ok is
+// resized.  The same cloud pointer in several pairs is uploaded once.  INTEGRATION.md shows it chained into coarse_reg_teaser_batch.
+template <typename PointT>
+inline void find_feature_correspondence_ncc_batch(const std::vector<typename pcl::PointCloud<PointT>::Ptr> &target_kpts,
+												  const std::vector<typename pcl::PointCloud<PointT>::Ptr> &source_kpts,
+												  std::vector<typename pcl::PointCloud<PointT>::Ptr> &target_corrs,
+												  std::vector<typename pcl::PointCloud<PointT>::Ptr> &source_corrs, std::vector<bool> &ok, bool fixed_num_corr = false,
+												  int corr_num = 2000, bool reciprocal_on = true)
+{
+	const size_t B = target_kpts.size();
+	if (source_kpts.size() != B || target_corrs.size() != B || source_corrs.size() != B)
+		throw std::invalid_argument("find_feature_correspondence_ncc_batch: the four cloud vectors must have one length");
+	mulls_ctx *ctx = thread_context();
+	mulls_ncc_params P;
+	mulls_ncc_default_params(&P);
+	P.fixed_num_corr = fixed_num_corr ? 1 : 0;
+	P.corr_num = corr_num;
+	P.reciprocal_on = reciprocal_on ? 1 : 0;
+	std::vector<mulls_ncc_problem> problems(B);
+	std::vector<std::vector<int32_t>> ti(B), si(B);
+	for (size_t k = 0; k < B; k++)
+	{
+		problems[k] = mulls_ncc_problem();
+		problems[k].tgt = borrow(target_kpts[k]);
+		problems[k].src = borrow(source_kpts[k]);
+		const uint32_t cap = fixed_num_corr ? (uint32_t)(corr_num > 0 ? corr_num : 0) : problems[k].tgt.n;
+		ti[k].resize(cap ? cap : 1), si[k].resize(cap ? cap : 1);
+		problems[k].tgt_idx = ti[k].data(), problems[k].src_idx = si[k].data(), problems[k].cap = cap;
+	}
+	std::vector<mulls_ncc_result> R(B ? B : 1);
+	const int rc = mulls_ncc_correspond_batch(ctx, problems.data(), (uint32_t)B, &P, 0, R.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_ncc_correspond_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	ok.assign(B, false);
+	for (size_t k = 0; k < B; k++)
+	{
+		for (uint32_t c = 0; c < R[k].n_corr && c < problems[k].cap; c++)
+		{
+			target_corrs[k]->points.push_back(target_kpts[k]->points[ti[k][c]]); // :547-548, :584-585
+			source_corrs[k]->points.push_back(source_kpts[k]->points[si[k][c]]);
+		}
+		ok[k] = R[k].ret != 0;
+	}
+}
+
 // CRegistration<PointT>::coarse_reg_ransac (include/common/cregistration.hpp:605-661), verbatim signature and defaults: the RANSAC solver of the global (coarse)
 // registration (test/mulls_reg.cpp:179, test/mulls_slam.cpp:538) in one device call (mulls_coarse_reg_ransac).  The binding is one early return at the top of the
 // member function:

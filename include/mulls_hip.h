@@ -614,6 +614,45 @@ void mulls_ncc_default_params(mulls_ncc_params *p);
 int mulls_ncc_correspond(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const mulls_ncc_params *params, int32_t *tgt_idx,
 						 int32_t *src_idx, uint32_t cap, uint32_t *n_corr);
 
+/* ---- many key-point matching problems per call: the candidate edges of one loop-closure event (test/mulls_slam.cpp:517-596 matches them one after
+ * another), or one scan against a list of submaps; the stage in front of mulls_coarse_reg_teaser_batch, whose index lists are the ones written here.
+ * results[b] and the pairs written to problems[b].tgt_idx / src_idx are THE BITS mulls_ncc_correspond RETURNS for problem b with the same params: the return
+ * value (ret: 1 for the reference's `true`, 0 for its `false`), the full n_corr, the pairs in the reference's push_back order, at most cap of them written.
+ * No arithmetic or order is redefined; the fixed-number tie rule stays ascending flat index i * Ns + j.
+ * Every device step runs once per sub-batch for all its problems: a table pass is one launch whose workgroups each belong to one
+ * problem, the fixed-number selection's six digit levels run in lock-step (one histogram and one pick launch per level; a problem whose selection is settled
+ * is skipped on the device), the sub-batch has one upload and one download.  The ordering of the at most 65536 keys and upstream's seven-per-point walk
+ * run on the host per problem, as in the single call.
+ *   per problem   fewer than 10 key points on a side: ret 0, n_corr 0 (cregistration.hpp:421-425); fixed_num_corr with corr_num <= 0: ret 1, no pairs.
+ *                 The rest of the batch runs.
+ *   whole call    checked for every problem before any device work: a problem the single call would refuse (a bad stride, a NULL it needs,
+ *                 n > INT32_MAX, fixed_num_corr with Nt * Ns > INT32_MAX or corr_num > 65536) and a NULL params make the call return the single call's
+ *                 code, name the first such problem's index in mulls_last_error, and leave every result at ret 0 / n_corr 0.
+ *   shared clouds the same cloud may appear in several problems; a host cloud is staged once per distinct (pts, n, stride) of a sub-batch.  No result
+ *                 depends on it.
+ *   scratch_limit_bytes  bounds the call's device arena (per problem: 20 bytes per staged key point, 56 per key point of descriptors and keys, the
+ *                 output — 8 Nt bytes, or 8 (K + 1) in fixed-number mode — and in that mode 49 KB of selection state).  The batch is cut into consecutive
+ *                 sub-batches that fit; a problem larger than the limit runs alone.  0: MULLS_NCC_BATCH_DEFAULT_SCRATCH_BYTES, a value chosen without a
+ *                 measurement.  The arena belongs to the context, grows only, and is released with it.
+ * n_problems = 0: MULLS_OK. */
+#define MULLS_NCC_BATCH_DEFAULT_SCRATCH_BYTES (512ull << 20)
+typedef struct mulls_ncc_problem
+{
+	mulls_cloud tgt, src;		/* host or device-resident key-point clouds, by the single call's rules (strides included) */
+	int32_t *tgt_idx, *src_idx; /* cap entries each, or NULL with cap = 0 */
+	uint32_t cap;
+	uint32_t reserved;
+} mulls_ncc_problem;
+
+typedef struct mulls_ncc_result
+{
+	int32_t ret;	 /* mulls_ncc_correspond's return value for this problem: 1 or 0 */
+	uint32_t n_corr; /* the full count; min(n_corr, cap) pairs were written */
+} mulls_ncc_result;
+
+int mulls_ncc_correspond_batch(mulls_ctx *ctx, const mulls_ncc_problem *problems, uint32_t n_problems, const mulls_ncc_params *params,
+							   uint64_t scratch_limit_bytes, mulls_ncc_result *results);
+
 /* ---- RANSAC coarse registration: CRegistration<PointT>::coarse_reg_ransac (include/common/cregistration.hpp:605-661) ----
  * The solver that turns mulls_ncc_correspond's pairs into the initial guess of mulls_icp.  Upstream's body is one call of PCL's
  * CorrespondenceRejectorSampleConsensus (RANSAC over SampleConsensusModelRegistration, then refineModel).  PCL is not available where this library is

@@ -319,6 +319,21 @@ def ncc_params(fixed_num_corr=0, corr_num=2000, reciprocal_on=1):
     return p
 
 
+class NccProblem(C.Structure):
+    """mulls_ncc_problem: one problem of mulls_ncc_correspond_batch"""
+
+    _fields_ = [("tgt", Cloud), ("src", Cloud), ("tgt_idx", C.c_void_p), ("src_idx", C.c_void_p), ("cap", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class NccResult(C.Structure):
+    """mulls_ncc_result"""
+
+    _fields_ = [("ret", C.c_int32), ("n_corr", C.c_uint32)]
+
+
+NCC_BATCH_DEFAULT_SCRATCH_BYTES = 512 << 20  # MULLS_NCC_BATCH_DEFAULT_SCRATCH_BYTES
+
+
 class RansacParams(C.Structure):
     """mulls_ransac_params: coarse_reg_ransac's arguments behind the clouds (cregistration.hpp:607), and upstream's setRefineModel(true)"""
 

@@ -15,6 +15,8 @@ struct NccCloudIn
 	uint32_t n;
 	uint32_t packed;
 };
+#define MULLS_NCC_ROWS 256u // rows (= lanes) of a workgroup of the table passes
+#define MULLS_NCC_WGS 2048u // workgroups a table pass aims at: the column range is split until there are about this many
 #define MULLS_NCC_HIST_LEVELS 6u
 #define MULLS_NCC_HIST_BUCKETS 2048u
 #define MULLS_NCC_MAX_CORR 65536u

@@ -104,6 +104,7 @@ def load():
     lib.mulls_ncc_default_params.argtypes = [C.POINTER(abi.NccParams)]
     lib.mulls_ncc_default_params.restype = None
     lib.mulls_ncc_correspond.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.NccParams), vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.mulls_ncc_correspond_batch.argtypes = [vp, C.POINTER(abi.NccProblem), C.c_uint32, C.POINTER(abi.NccParams), C.c_uint64, C.POINTER(abi.NccResult)]
     lib.mulls_ransac_default_params.argtypes = [C.POINTER(abi.RansacParams)]
     lib.mulls_ransac_default_params.restype = None
     lib.mulls_coarse_reg_ransac.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.RansacParams), C.POINTER(abi.RansacResult), vp, C.c_uint32]
@@ -142,7 +143,7 @@ EXPORTS = [
     "mulls_set_option", "mulls_get_option", "mulls_block_create", "mulls_block_destroy", "mulls_extract_features_resident", "mulls_block_cloud", "mulls_block_download",
     "mulls_motion_compensate", "mulls_block_motion_compensate",
     "mulls_pack_results", "mulls_icp_batch_sharded", "mulls_pipe_create", "mulls_pipe_destroy", "mulls_pipe_depth", "mulls_pipe_ctx", "mulls_pipe_set_option", "mulls_icp_batch_begin", "mulls_icp_batch_end",
-    "mulls_ncc_default_params", "mulls_ncc_correspond",
+    "mulls_ncc_default_params", "mulls_ncc_correspond", "mulls_ncc_correspond_batch",
     "mulls_ransac_default_params", "mulls_coarse_reg_ransac", "mulls_coarse_reg_ransac_indexed",
     "mulls_teaser_default_params", "mulls_coarse_reg_teaser", "mulls_coarse_reg_teaser_indexed", "mulls_coarse_reg_teaser_batch",
     "mulls_sor_default_params", "mulls_sor_filter",
@@ -440,6 +441,49 @@ class Context:
         w = min(n.value, cap)
         assert ti[cap] == -1 and si[cap] == -1
         return bool(rc), ti[:w].copy(), si[:w].copy(), n.value
+
+    def ncc_correspond_batch(self, problems, params=None, scratch_limit=0):
+        """mulls_ncc_correspond_batch: many problems per call, each with the result of the matching ncc_correspond call.  problems: a list of
+        (tgt_kpts, src_kpts) or dicts with the keys tgt, src and optionally cap (the clouds are host clouds or device-resident abi.Cloud objects; a host
+        cloud may also be an abi.Cloud with a stride of its own; the same array object in several problems is the same cloud to the library).  One params
+        for the whole batch.  scratch_limit: scratch_limit_bytes (0: the library's default).  Returns [(ok, tgt_idx, src_idx, n_corr), ...] as
+        ncc_correspond does per problem."""
+        keep = {}
+
+        def cloud(k):
+            if isinstance(k, abi.Cloud):
+                return k
+            if id(k) not in keep:  # one conversion per array object: the same pointer wherever it appears
+                keep[id(k)] = (k, abi.records(k))
+            raw = keep[id(k)][1]
+            c = abi.Cloud()
+            c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+            return c
+
+        n = len(problems)
+        p = params if params is not None else abi.ncc_params()
+        arr, res, lists = (abi.NccProblem * max(n, 1))(), (abi.NccResult * max(n, 1))(), []
+        for b, prob in enumerate(problems):
+            if not isinstance(prob, dict):
+                prob = dict(zip(("tgt", "src"), prob))
+            P = arr[b]
+            P.tgt, P.src = cloud(prob["tgt"]), cloud(prob["src"])
+            cap = prob.get("cap")
+            if cap is None:
+                cap = max(0, min(p.corr_num, 65536)) if p.fixed_num_corr else P.tgt.n
+            ti, si = np.full(cap + 1, -1, np.int32), np.full(cap + 1, -1, np.int32)  # one slot past cap: checked to be left alone
+            lists.append((ti, si))
+            P.tgt_idx, P.src_idx, P.cap = ti.ctypes.data, si.ctypes.data, cap
+        rc = self.lib.mulls_ncc_correspond_batch(self.h, arr, n, C.byref(p), int(scratch_limit), res)
+        if rc != 0:
+            raise MullsError("mulls_ncc_correspond_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        out = []
+        for b in range(n):
+            (ti, si), cap = lists[b], arr[b].cap
+            assert ti[cap] == -1 and si[cap] == -1
+            w = min(res[b].n_corr, cap)
+            out.append((bool(res[b].ret), ti[:w].copy(), si[:w].copy(), int(res[b].n_corr)))
+        return out
 
     # --- RANSAC coarse registration --------------------------------------------------------------------------------
     def coarse_reg_ransac(self, tgt_pts, src_pts, params=None, cap=None, tgt_idx=None, src_idx=None):
