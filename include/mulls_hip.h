@@ -206,7 +206,10 @@ int mulls_get_profile(const mulls_ctx *ctx, mulls_profile *out);
 int mulls_set_nn_mode(mulls_ctx *ctx, int mode);
 /* Execution options of a context (none of them changes a result: every path returns the same bits).  mulls_create presets each from the environment
  * variable named after it (MULLS_OPT_HOST_STEP <- MULLS_HOST_STEP=1, ...: diagnostics and the A/B scripts under tools/); nothing reads the
- * environment after that. */
+ * environment after that.
+ * The tests that hold the options to "the same bits" (a form's every output field against the default form's, the default's against the oracle):
+ * tests/test_gpu_icp.py and tests/test_gpu_mixed.py (the launch forms, k-candidate certificates, fused target setup, tiers), tests/test_gpu_options.py
+ * (certificates and their slack, cell edges, LDS_DEDUP, FIRST_DIRECT, sub-batches and streams, the split window, LEAN_STAGING). */
 enum mulls_option
 {
 	MULLS_OPT_HOST_STEP = 0,			  /* [0] 1: the lock-step loop is stepped by the host (what per-iteration traces switch on anyway) */
@@ -256,8 +259,9 @@ enum mulls_option
 											 cloud unhinted against the grid in global memory: every called class cloud goes straight to the staged search.  0 = light pass
 											 first, as in every other iteration.  Same bits */
 	MULLS_OPT_SUM_STEP = 27,			  /* [1] lock-step loop stepped on the device, batches beyond STEP_LAUNCH_MAX_PAIRS: one wave per pair sums the pair's trip partials AND steps it
-											 (k_sum_step) instead of k_finish followed by k_step — one launch less per iteration; pairs with more than MULLS_SUM_STEP_TRIPS
-											 trips in a class keep the two kernels.  0 = k_finish + k_step.  Same bits */
+											 (k_sum_step) instead of k_finish followed by k_step — one launch less per iteration; a batch in which some class cloud has more than four
+											 1024-slot trips (run_device_step in loop.cpp checks the batch's job tables before the first launch set) keeps the
+											 two kernels.  0 = k_finish + k_step.  Same bits */
 	MULLS_OPT_TEASER_DEVICE_SEARCH = 28,  /* [0] 1: the exact maximum-clique search of mulls_coarse_reg_teaser / mulls_coarse_reg_teaser_indexed runs on the device (k_teaser_clique.hip: a
 											 chain of bounded launches, one wavefront per branch of the search tree) instead of on one host core.  Every result field is the same
 											 bits whenever the search completes; clique_nodes, the effort, is not (see the TEASER block below).  Values other than 0 and 1 are

@@ -7,51 +7,11 @@ import numpy as np
 import pytest
 
 from conftest import planes_scene, transformed_copy
+from icp_compare import compare
 from mulls_amd import abi, synth
 from oracle import pyoracle
 
 pytestmark = pytest.mark.gpu
-
-TOL_T, TOL_R = 1e-7, 1e-7
-
-
-def compare(ro, rg, check_trace=True, x_tol=1e-9):
-    assert ro.code == rg.code and ro.iters == rg.iters
-    assert list(ro.ncorr) == list(rg.ncorr)
-    assert list(ro.nsrc0) == list(rg.nsrc0) and list(ro.ntgt0) == list(rg.ntgt0)
-    assert ro.singular == rg.singular
-    assert ro.cropped == rg.cropped and list(ro.crop_box) == list(rg.crop_box)
-    if np.isnan(ro.T_matrix()).any():
-        # singular normal matrix: the reference lets inf/NaN propagate (SURVEY B-11); both must agree on where
-        assert np.array_equal(np.isnan(ro.T_matrix()), np.isnan(rg.T_matrix()))
-    else:
-        dt, dr = synth.pose_error(rg.T_matrix(), ro.T_matrix())
-        assert dt <= TOL_T and dr <= TOL_R, (dt, dr)
-    # sigma^2 = VTPV / (n - 6) goes negative / infinite with fewer than seven observations: NaN and inf propagate in both
-    assert (np.isnan(ro.sigma) and np.isnan(rg.sigma)) or ro.sigma == rg.sigma or abs(ro.sigma - rg.sigma) <= 1e-6 * max(1.0, abs(ro.sigma))
-    assert ro.confidence == rg.confidence or (np.isnan(ro.confidence) and np.isnan(rg.confidence))
-    io, ig = ro.info_matrix(), rg.info_matrix()
-    assert np.array_equal(np.isfinite(io), np.isfinite(ig))
-    if np.isfinite(io).all():
-        assert np.abs(io - ig).max() <= 1e-6 * np.abs(io).max()
-    if check_trace:
-        assert ro.trace_len == rg.trace_len
-        for k in range(ro.trace_len):
-            a, b = ro.trace[k], rg.trace[k]
-            assert list(a.ncorr) == list(b.ncorr) and list(a.nsrc) == list(b.nsrc), k
-            assert list(a.thr) == list(b.thr)
-            if any(a.atpa[:]):
-                A, Bm = np.array(a.atpa[:]), np.array(b.atpa[:])
-                assert np.array_equal(np.isfinite(A), np.isfinite(Bm))  # 0/0 weights etc. turn up in the same places
-                fin = np.isfinite(A)
-                if fin.any():
-                    assert np.abs(A[fin] - Bm[fin]).max() <= 1e-10 * np.abs(A[fin]).max()
-                if np.isfinite(np.array(a.x[:])).all():
-                    # the solve amplifies the 1e-12 differences of the sums by the condition number of the normal matrix
-                    assert np.abs(np.array(a.x[:]) - np.array(b.x[:])).max() <= x_tol * max(1.0, np.abs(np.array(a.x[:])).max())
-                else:
-                    assert not np.isfinite(np.array(b.x[:])).all()
-
 
 PARAM_SETS = {
     "kitti_s2s": dict(base="kitti", dis_thre_unit=2.4),

@@ -6,21 +6,11 @@ size: k_cert_big resolves the duplicate rule and the rejection chain itself) and
 import numpy as np
 import pytest
 
+from icp_compare import oracle_equal, same_bits
 from mulls_amd import abi, synth
 from oracle import pyoracle
 
 pytestmark = pytest.mark.gpu
-
-
-def same_bits(a, b):
-    return (a.code, a.iters, list(a.ncorr), list(a.nsrc0), list(a.ntgt0)) == (b.code, b.iters, list(b.ncorr), list(b.nsrc0), list(b.ntgt0)) and list(a.T[:]) == list(b.T[:]) and \
-        list(a.info[:]) == list(b.info[:]) and a.sigma == b.sigma
-
-
-def oracle_equal(ro, rg):
-    assert (ro.code, ro.iters, list(ro.ncorr), list(ro.nsrc0), list(ro.ntgt0)) == (rg.code, rg.iters, list(rg.ncorr), list(rg.nsrc0), list(rg.ntgt0))
-    dt, dr = synth.pose_error(rg.T_matrix(), ro.T_matrix())
-    assert dt <= 1e-7 and dr <= 1e-7, (dt, dr)
 
 
 @pytest.fixture(scope="module")
