@@ -795,11 +795,16 @@ typedef struct mulls_teaser_result
 void mulls_teaser_default_params(mulls_teaser_params *p);
 /* returns MULLS_OK or MULLS_E_*: MULLS_E_INVALID for a non-finite or negative noise_bound or a bad stride (mulls_coarse_reg_ransac's rule);
  * MULLS_E_UNSUPPORTED above 8192 pairs.  clique: the clique's pair indices, ascending, at most cap of them (NULL / 0 allowed).  The clouds are host memory
- * (any stride that is a multiple of 4 and at least 16) or device-resident clouds of 48-byte records. */
+ * (any stride that is a multiple of 4 and at least 16) or device-resident clouds of 48-byte records.
+ * The NULL checks of ctx, the clouds, params, result and clique (MULLS_E_INVALID, result untouched) come first, then a cloud with points and no address
+ * (MULLS_E_INVALID), noise_bound, and the refusals of the one checker mulls_coarse_reg_teaser_batch (below) uses per problem, with this entry point's name
+ * and no problem index in mulls_last_error.  The device steps are the text the batch compiles (k_teaser.hip), launched with arguments instead of a descriptor. */
 int mulls_coarse_reg_teaser(mulls_ctx *ctx, const mulls_cloud *tgt_pts, const mulls_cloud *src_pts, const mulls_teaser_params *params,
 							mulls_teaser_result *result, int32_t *clique, uint32_t cap);
 /* the same solver on tgt_kpts[tgt_idx[k]] <-> src_kpts[src_idx[k]], k < n_corr, gathered on the device as mulls_coarse_reg_ransac_indexed does (clique
- * entries are positions k in the lists).  MULLS_E_INVALID for an index outside its cloud. */
+ * entries are positions k in the lists).  MULLS_E_INVALID for an index outside its cloud, and for n_corr > 0 with a list that is NULL; n_corr = 0 reads no
+ * list and is upstream's "too few correspondences" (MULLS_OK, status -1): the call says that the problem is indexed, where the batch infers it from the
+ * lists. */
 int mulls_coarse_reg_teaser_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const int32_t *tgt_idx, const int32_t *src_idx,
 									uint32_t n_corr, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique, uint32_t cap);
 

@@ -1,15 +1,20 @@
 // teaser.cpp — mulls_coarse_reg_teaser: CRegistration<PointT>::coarse_reg_teaser (cregistration.hpp:664-759), the solver every shipped configuration
-// selects between the key-point matcher (ncc.cpp) and mulls_icp.  Host side: argument checks, staging, the order of the device steps (k_teaser.hip: graph,
-// core numbers, greedy lower bound, compaction, GNC-TLS rotation), the exact clique search — on the one sub-matrix that comes down (teaser_host.h) or,
-// with MULLS_OPT_TEASER_DEVICE_SEARCH, as a chain of bounded launches on the sub-matrix where it lies (teaser_search.h, k_teaser_clique.hip) — and the
-// serial TLS translation estimate on the clique's points.  include/mulls_hip.h has the definition this file follows.
-// mulls_coarse_reg_teaser_batch runs the same steps for many problems: the device steps per sub-batch (teaser_batch.h plans them, k_teaser_batch.hip runs
-// them, the GNC loop in lock-step), the search and the translation per problem with the code of the single call.
+// selects between the key-point matcher (ncc.cpp) and mulls_icp.  Host side: argument checks (one checker for the three entry points), staging, the order of
+// the device steps (k_teaser.hip: graph, core numbers, greedy lower bound, compaction, GNC-TLS rotation), the exact clique search — on the one sub-matrix that
+// comes down (teaser_host.h) or, with MULLS_OPT_TEASER_DEVICE_SEARCH, as a chain of bounded launches on the sub-matrix where it lies (teaser_search.h,
+// k_teaser_clique.hip) — and the serial TLS translation estimate on the clique's points.  include/mulls_hip.h has the definition this file follows.
+// mulls_coarse_reg_teaser_batch runs the same steps for many problems: the device steps per sub-batch (teaser_batch.h plans them, the k_tb_* kernels of
+// k_teaser.hip run them, the GNC loop in lock-step), the search and the translation per problem with the code of the single call.
+// WHY THE HOST SEQUENCE IS WRITTEN TWICE (teaser_run, teaser_sub_batch): a single call run as a batch of one was built and measured against teaser_run on one
+// MI355X and was 1.2 to 2.1 % slower on every launch-bound row (profiles/teaser_kernel_stats.txt, section 5).  The cause was not isolated.  Supposed: the kernels of a
+// sub-batch read their pointers and sizes from a descriptor in device memory before their own data, in a GNC loop of 22 to 42 iterations of five launches;
+// the batch path's descriptor uploads, its memset and its planner vectors may have a share.
+// So teaser_run keeps launch arguments; what the two share is one kernel text (the __device__ steps of k_teaser.hip), the argument checker, the searches
+// and teaser_finish.
 #include <chrono>
 
 #include "ctx.h"
 #include "ransac_launch.h" // launch_ransac_gather: x, y, z, data[3] out of device records
-#include "teaser_batch_launch.h"
 #include "teaser_host.h"
 #include "teaser_launch.h"
 
@@ -239,55 +244,138 @@ void teaser_finish(const TeaserGnc &G, int iters, const float *h_cs, const float
 		}
 }
 
-int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src_in, const int32_t *tgt_idx, const int32_t *src_idx, uint32_t n_corr,
-			   bool indexed, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique_out, uint32_t cap)
+void reset_result(mulls_teaser_result *result)
 {
-	const char *who = indexed ? "mulls_coarse_reg_teaser_indexed" : "mulls_coarse_reg_teaser";
-	if (!ctx || !tgt_in || !src_in || !params || !result || (cap && !clique_out))
-		return MULLS_E_INVALID;
 	std::memset(result, 0, sizeof(*result));
 	result->status = -1;
 	for (int k = 0; k < 16; k++)
 		result->T[k] = (k % 5 == 0) ? 1.0 : 0.0;
-	const mulls_cloud T = *tgt_in, S = *src_in;
-	if ((T.n && !T.pts) || (S.n && !S.pts))
-		return MULLS_E_INVALID;
-	if (!std::isfinite(params->noise_bound) || params->noise_bound < 0.0f)
+}
+
+struct BatchProblem // a problem that reaches the device
+{
+	uint32_t index, n;
+	bool indexed, t_dev, s_dev;
+};
+
+// who refuses: the entry point's name and, in a batch, the problem's index — mulls_last_error reads "<entry point>: [problem <b>: ]<why>"
+struct Refusal
+{
+	mulls_ctx *ctx;
+	const char *who;
+	int64_t problem; // -1: a single call
+
+	int operator()(int code, const char *why) const
 	{
-		ctx->err = std::string(who) + ": noise_bound is not finite or negative";
-		return MULLS_E_INVALID;
+		ctx->err = std::string(who) + (problem >= 0 ? ": problem " + std::to_string(problem) : std::string()) + ": " + why;
+		return code;
 	}
-	uint32_t n = T.n;
-	if (indexed)
-	{
-		if (n_corr && (!tgt_idx || !src_idx))
-			return MULLS_E_INVALID;
-		n = n_corr;
-	}
-	else if (T.n != S.n)
+};
+
+// one mulls_teaser_params for a call
+int check_params(const Refusal &refuse, const mulls_teaser_params *params)
+{
+	if (std::isfinite(params->noise_bound) && params->noise_bound >= 0.0f)
+		return MULLS_OK;
+	return refuse(MULLS_E_INVALID, "noise_bound is not finite or negative");
+}
+
+// A problem as it was handed in, before the device is touched: the refusals, upstream's early returns (*runs = false: the result stays at status -1), or
+// its number of pairs.  indexed: the batch ABI infers it from the lists and wants both or none; the indexed single call says so itself and reads no list
+// when n_corr = 0.
+int check_pairs(const Refusal &refuse, const mulls_teaser_problem &P, bool indexed, BatchProblem *A, bool *runs)
+{
+	*runs = false;
+	const mulls_cloud &T = P.tgt, &S = P.src;
+	const bool list_missing = indexed && (!P.tgt_idx || !P.src_idx) && (refuse.problem >= 0 || P.n_corr);
+	if ((T.n && !T.pts) || (S.n && !S.pts) || (P.clique_cap && !P.clique) || list_missing)
+		return refuse(MULLS_E_INVALID, "a NULL cloud, clique buffer or index list");
+	A->indexed = indexed, A->n = indexed ? P.n_corr : T.n;
+	if (!indexed && T.n != S.n)
 		return MULLS_OK; // upstream: "source points number != target points number", -1
-	if (n <= 3u)
+	if (A->n <= 3u)
 		return MULLS_OK; // upstream: "too few correspondences", -1
-	if (n > MULLS_TEASER_MAX_POINTS)
-	{
-		ctx->err = std::string(who) + ": at most 8192 pairs";
-		return MULLS_E_UNSUPPORTED;
-	}
+	if (A->n > MULLS_TEASER_MAX_POINTS)
+		return refuse(MULLS_E_UNSUPPORTED, "at most 8192 pairs");
 	if (indexed)
-		for (uint32_t i = 0; i < n; i++)
-			if (tgt_idx[i] < 0 || (uint32_t)tgt_idx[i] >= T.n || src_idx[i] < 0 || (uint32_t)src_idx[i] >= S.n)
-			{
-				ctx->err = std::string(who) + ": an index lies outside its cloud";
-				return MULLS_E_INVALID;
-			}
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const bool t_dev = cloud_on_device(ctx, T), s_dev = cloud_on_device(ctx, S);
-	if ((t_dev && T.stride != MULLS_POINT_BYTES) || (s_dev && S.stride != MULLS_POINT_BYTES) || (!t_dev && (T.stride < 16u || T.stride % 4u)) ||
-		(!s_dev && (S.stride < 16u || S.stride % 4u)))
+		for (uint32_t i = 0; i < A->n; i++)
+			if (P.tgt_idx[i] < 0 || (uint32_t)P.tgt_idx[i] >= T.n || P.src_idx[i] < 0 || (uint32_t)P.src_idx[i] >= S.n)
+				return refuse(MULLS_E_INVALID, "an index lies outside its cloud");
+	*runs = true;
+	return MULLS_OK;
+}
+
+// ... and once the device is set: where its clouds lie, and their strides
+int check_strides(const Refusal &refuse, const mulls_teaser_problem &P, BatchProblem *A)
+{
+	const mulls_cloud &T = P.tgt, &S = P.src;
+	A->t_dev = cloud_on_device(refuse.ctx, T), A->s_dev = cloud_on_device(refuse.ctx, S);
+	if ((A->t_dev && T.stride != MULLS_POINT_BYTES) || (A->s_dev && S.stride != MULLS_POINT_BYTES) || (!A->t_dev && (T.stride < 16u || T.stride % 4u)) ||
+		(!A->s_dev && (S.stride < 16u || S.stride % 4u)))
+		return refuse(MULLS_E_INVALID, "stride (device clouds: 48; host clouds: a multiple of 4, at least 16)");
+	return MULLS_OK;
+}
+
+// the device clique search's words behind an arena: taken once per call or sub-batch for its largest problem of n pairs (nothing when the host searches)
+struct SearchPlaces
+{
+	size_t o_later, o_first, o_ctl, o_list, p_later, p_ctl, p_list, p_init, p_back;
+
+	SearchPlaces(bool device_search, uint32_t n, size_t &off, size_t &poff) // off, poff: the arenas' ends so far, moved on
 	{
-		ctx->err = std::string(who) + ": stride (device clouds: 48; host clouds: a multiple of 4, at least 16)";
-		return MULLS_E_INVALID;
+		auto take = [&](size_t bytes) {
+			const size_t at = off;
+			off += up256(bytes);
+			return at;
+		};
+		auto ptake = [&](size_t bytes) {
+			const size_t at = poff;
+			poff += up256(bytes);
+			return at;
+		};
+		const size_t words = device_search ? ((size_t)n + 1u) * 4u : 0u, states = device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u;
+		o_later = take(device_search ? (size_t)n * 4u : 0u), o_first = take(words), o_ctl = take(sizeof(TeaserSearchCtl)), o_list = take(words);
+		p_later = ptake(words), p_ctl = ptake(2u * sizeof(TeaserSearchCtl)), p_list = ptake(words), p_init = ptake(states), p_back = ptake(states);
 	}
+	DeviceSearchBuffers at(unsigned char *d, unsigned char *h) const
+	{
+		DeviceSearchBuffers B;
+		B.later = reinterpret_cast<uint32_t *>(d + o_later), B.first = reinterpret_cast<uint32_t *>(d + o_first);
+		B.ctl = reinterpret_cast<TeaserSearchCtl *>(d + o_ctl), B.list = reinterpret_cast<uint32_t *>(d + o_list);
+		B.h_later = reinterpret_cast<uint32_t *>(h + p_later), B.h_ctl = reinterpret_cast<TeaserSearchCtl *>(h + p_ctl);
+		B.h_list = reinterpret_cast<uint32_t *>(h + p_list);
+		B.h_init = reinterpret_cast<TeaserWorkerState *>(h + p_init), B.h_back = reinterpret_cast<TeaserWorkerState *>(h + p_back);
+		return B;
+	}
+};
+
+int teaser_run(mulls_ctx *ctx, const char *who, bool indexed_call, const mulls_cloud *tgt_in, const mulls_cloud *src_in, const int32_t *tgt_idx,
+			   const int32_t *src_idx, uint32_t n_corr, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique_out, uint32_t cap)
+{
+	if (!ctx || !tgt_in || !src_in || !params || !result || (cap && !clique_out))
+		return MULLS_E_INVALID;
+	reset_result(result);
+	if ((tgt_in->n && !tgt_in->pts) || (src_in->n && !src_in->pts))
+		return MULLS_E_INVALID;
+	const Refusal refuse{ctx, who, -1};
+	if (int rc = check_params(refuse, params))
+		return rc;
+	mulls_teaser_problem P;
+	P.tgt = *tgt_in, P.src = *src_in;
+	P.tgt_idx = tgt_idx, P.src_idx = src_idx, P.n_corr = n_corr;
+	P.clique = clique_out, P.clique_cap = cap;
+	BatchProblem A;
+	bool runs;
+	if (int rc = check_pairs(refuse, P, indexed_call, &A, &runs))
+		return rc;
+	if (!runs)
+		return MULLS_OK; // upstream's early returns: -1
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	if (int rc = check_strides(refuse, P, &A))
+		return rc;
+	const mulls_cloud &T = P.tgt, &S = P.src;
+	const uint32_t n = A.n;
+	const bool indexed = A.indexed, t_dev = A.t_dev, s_dev = A.s_dev;
 	if (!ctx->teaser)
 		ctx->teaser = new mulls_teaser_scratch();
 	mulls_teaser_scratch &sc = *ctx->teaser;
@@ -303,11 +391,6 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 	const size_t o_src = take((size_t)n * 16u), o_tgt = take((size_t)n * 16u), o_idx = take((size_t)n * 8u), o_adj = take(mat), o_sub = take(mat);
 	const size_t o_deg = take((size_t)n * 4u), o_cg = take((size_t)n * 8u), o_sum = take(8), o_keep = take((size_t)n * 4u);
 	const size_t o_cs = take((size_t)n * 16u), o_ct = take((size_t)n * 16u), o_part = take((size_t)9u * MULLS_TEASER_PARTIALS * 8u), o_S = take(sizeof(TeaserGnc));
-	const bool device_search = ctx->opt[MULLS_OPT_TEASER_DEVICE_SEARCH] != 0.0;
-	const size_t o_later = take(device_search ? (size_t)n * 4u : 0u), o_first = take(device_search ? ((size_t)n + 1u) * 4u : 0u);
-	const size_t o_ctl = take(sizeof(TeaserSearchCtl)), o_list = take(device_search ? ((size_t)n + 1u) * 4u : 0u);
-	if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
-		return rc;
 	size_t poff = 0;
 	auto ptake = [&](size_t bytes) {
 		const size_t at = poff;
@@ -316,9 +399,10 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 	};
 	const size_t p_src = ptake((size_t)n * 16u), p_tgt = ptake((size_t)n * 16u), p_idx = ptake((size_t)n * 8u), p_sub = ptake(mat), p_cg = ptake((size_t)n * 8u);
 	const size_t p_sum = ptake(8), p_keep = ptake((size_t)n * 4u), p_cs = ptake((size_t)n * 32u), p_S = ptake(sizeof(TeaserGnc));
-	const size_t p_later = ptake(device_search ? ((size_t)n + 1u) * 4u : 0u), p_ctl = ptake(2u * sizeof(TeaserSearchCtl)), p_list = ptake(device_search ? ((size_t)n + 1u) * 4u : 0u);
-	const size_t p_init = ptake(device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u);
-	const size_t p_back = ptake(device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u);
+	const bool device_search = ctx->opt[MULLS_OPT_TEASER_DEVICE_SEARCH] != 0.0;
+	const SearchPlaces search(device_search, n, off, poff);
+	if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
+		return rc;
 	if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, poff, hipHostMallocDefault))
 		return rc;
 	unsigned char *d = sc.dev, *h = sc.pin;
@@ -394,13 +478,7 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 		HIPCHK(ctx, launch_teaser_compact(st, adj, n, reinterpret_cast<const int32_t *>(d + o_keep), m, sub));
 		if (device_search)
 		{
-			DeviceSearchBuffers B;
-			B.later = reinterpret_cast<uint32_t *>(d + o_later), B.first = reinterpret_cast<uint32_t *>(d + o_first);
-			B.ctl = reinterpret_cast<TeaserSearchCtl *>(d + o_ctl), B.list = reinterpret_cast<uint32_t *>(d + o_list);
-			B.h_later = reinterpret_cast<uint32_t *>(h + p_later), B.h_ctl = reinterpret_cast<TeaserSearchCtl *>(h + p_ctl);
-			B.h_list = reinterpret_cast<uint32_t *>(h + p_list);
-			B.h_init = reinterpret_cast<TeaserWorkerState *>(h + p_init), B.h_back = reinterpret_cast<TeaserWorkerState *>(h + p_back);
-			if (int rc = device_clique_search(ctx, sc, st, who, sub, m, lb, max_core, witness_at, params->clique_node_budget, B, h_keep, result, &clique))
+			if (int rc = device_clique_search(ctx, sc, st, who, sub, m, lb, max_core, witness_at, params->clique_node_budget, search.at(d, h), h_keep, result, &clique))
 				return rc;
 		}
 		else
@@ -451,20 +529,6 @@ int teaser_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 	return MULLS_OK;
 }
 // ---- mulls_coarse_reg_teaser_batch
-void reset_result(mulls_teaser_result *result)
-{
-	std::memset(result, 0, sizeof(*result));
-	result->status = -1;
-	for (int k = 0; k < 16; k++)
-		result->T[k] = (k % 5 == 0) ? 1.0 : 0.0;
-}
-
-struct BatchProblem // a problem that reaches the device
-{
-	uint32_t index, n;
-	bool indexed, t_dev, s_dev;
-};
-
 const char *const BATCH = "mulls_coarse_reg_teaser_batch";
 
 // one graph-phase sub-batch: `count` problems whose arena fits the limit (or one that does not)
@@ -481,22 +545,7 @@ int teaser_sub_batch(mulls_ctx *ctx, const mulls_teaser_problem *problems, const
 	teaser_batch_layout(sizes.data(), count, &L);
 	// behind the arena: what the device search needs besides its workers, once for the sub-batch (the problems are searched one after another)
 	size_t off = L.dev_bytes, poff = L.pin_bytes;
-	auto take = [&](size_t bytes) {
-		const size_t at = off;
-		off += up256(bytes);
-		return at;
-	};
-	auto ptake = [&](size_t bytes) {
-		const size_t at = poff;
-		poff += up256(bytes);
-		return at;
-	};
-	const size_t o_later = take(device_search ? (size_t)n_max * 4u : 0u), o_first = take(device_search ? ((size_t)n_max + 1u) * 4u : 0u);
-	const size_t o_ctl = take(sizeof(TeaserSearchCtl)), o_list = take(device_search ? ((size_t)n_max + 1u) * 4u : 0u);
-	const size_t p_later = ptake(device_search ? ((size_t)n_max + 1u) * 4u : 0u), p_ctl = ptake(2u * sizeof(TeaserSearchCtl));
-	const size_t p_list = ptake(device_search ? ((size_t)n_max + 1u) * 4u : 0u);
-	const size_t p_init = ptake(device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u);
-	const size_t p_back = ptake(device_search ? MULLS_TEASER_SEARCH_WORKERS * sizeof(TeaserWorkerState) : 0u);
+	const SearchPlaces search(device_search, n_max, off, poff);
 	if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
 		return rc;
 	if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, poff, hipHostMallocDefault))
@@ -607,14 +656,8 @@ int teaser_sub_batch(mulls_ctx *ctx, const mulls_teaser_problem *problems, const
 			clique.assign(1, 0u);
 		else if (device_search)
 		{
-			DeviceSearchBuffers B;
-			B.later = reinterpret_cast<uint32_t *>(d + o_later), B.first = reinterpret_cast<uint32_t *>(d + o_first);
-			B.ctl = reinterpret_cast<TeaserSearchCtl *>(d + o_ctl), B.list = reinterpret_cast<uint32_t *>(d + o_list);
-			B.h_later = reinterpret_cast<uint32_t *>(h + p_later), B.h_ctl = reinterpret_cast<TeaserSearchCtl *>(h + p_ctl);
-			B.h_list = reinterpret_cast<uint32_t *>(h + p_list);
-			B.h_init = reinterpret_cast<TeaserWorkerState *>(h + p_init), B.h_back = reinterpret_cast<TeaserWorkerState *>(h + p_back);
 			if (int rc = device_clique_search(ctx, sc, st, BATCH, reinterpret_cast<const uint64_t *>(d + D.sub), m[k], lbs[k], cores[k], witness_at[k],
-											  params->clique_node_budget, B, h_keep, result, &clique))
+											  params->clique_node_budget, search.at(d, h), h_keep, result, &clique))
 				return rc;
 		}
 		else if (int rc = host_clique_search(ctx, BATCH, reinterpret_cast<const uint64_t *>(h + L.p_sub + (D.sub - L.o_sub)), m[k], lbs[k], witness_at[k],
@@ -707,40 +750,24 @@ int teaser_batch_run(mulls_ctx *ctx, const mulls_teaser_problem *problems, uint3
 		reset_result(&results[b]);
 	if (!n_problems)
 		return MULLS_OK;
-	if (!std::isfinite(params->noise_bound) || params->noise_bound < 0.0f)
-	{
-		ctx->err = std::string(BATCH) + ": noise_bound is not finite or negative";
-		return MULLS_E_INVALID;
-	}
+	if (int rc = check_params(Refusal{ctx, BATCH, -1}, params))
+		return rc;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	// every problem is checked before any device work: the single call's refusals, in its order, the first one found named
+	// every problem is checked before any device work: the first refusal found ends the call
 	std::vector<BatchProblem> act;
 	for (uint32_t b = 0; b < n_problems; b++)
 	{
 		const mulls_teaser_problem &P = problems[b];
-		auto refuse = [&](int code, const char *why) {
-			ctx->err = std::string(BATCH) + ": problem " + std::to_string(b) + ": " + why;
-			return code;
-		};
-		const mulls_cloud &T = P.tgt, &S = P.src;
-		if ((T.n && !T.pts) || (S.n && !S.pts) || (P.clique_cap && !P.clique) || (P.tgt_idx == nullptr) != (P.src_idx == nullptr))
-			return refuse(MULLS_E_INVALID, "a NULL cloud, clique buffer or index list");
+		const Refusal refuse{ctx, BATCH, b};
 		BatchProblem A;
-		A.index = b, A.indexed = P.tgt_idx != nullptr, A.n = A.indexed ? P.n_corr : T.n;
-		if (!A.indexed && T.n != S.n)
-			continue; // upstream: "source points number != target points number", -1
-		if (A.n <= 3u)
-			continue; // upstream: "too few correspondences", -1
-		if (A.n > MULLS_TEASER_MAX_POINTS)
-			return refuse(MULLS_E_UNSUPPORTED, "at most 8192 pairs");
-		if (A.indexed)
-			for (uint32_t i = 0; i < A.n; i++)
-				if (P.tgt_idx[i] < 0 || (uint32_t)P.tgt_idx[i] >= T.n || P.src_idx[i] < 0 || (uint32_t)P.src_idx[i] >= S.n)
-					return refuse(MULLS_E_INVALID, "an index lies outside its cloud");
-		A.t_dev = cloud_on_device(ctx, T), A.s_dev = cloud_on_device(ctx, S);
-		if ((A.t_dev && T.stride != MULLS_POINT_BYTES) || (A.s_dev && S.stride != MULLS_POINT_BYTES) || (!A.t_dev && (T.stride < 16u || T.stride % 4u)) ||
-			(!A.s_dev && (S.stride < 16u || S.stride % 4u)))
-			return refuse(MULLS_E_INVALID, "stride (device clouds: 48; host clouds: a multiple of 4, at least 16)");
+		bool runs;
+		A.index = b;
+		if (int rc = check_pairs(refuse, P, P.tgt_idx || P.src_idx, &A, &runs))
+			return rc;
+		if (!runs)
+			continue;
+		if (int rc = check_strides(refuse, P, &A))
+			return rc;
 		act.push_back(A);
 	}
 	if (act.empty())
@@ -780,7 +807,7 @@ extern "C"
 								mulls_teaser_result *result, int32_t *clique, uint32_t cap)
 	try
 	{
-		return teaser_run(ctx, tgt_pts, src_pts, nullptr, nullptr, 0, false, params, result, clique, cap);
+		return teaser_run(ctx, "mulls_coarse_reg_teaser", false, tgt_pts, src_pts, nullptr, nullptr, 0, params, result, clique, cap);
 	}
 	catch (...)
 	{
@@ -791,7 +818,7 @@ extern "C"
 										uint32_t n_corr, const mulls_teaser_params *params, mulls_teaser_result *result, int32_t *clique, uint32_t cap)
 	try
 	{
-		return teaser_run(ctx, tgt_kpts, src_kpts, tgt_idx, src_idx, n_corr, true, params, result, clique, cap);
+		return teaser_run(ctx, "mulls_coarse_reg_teaser_indexed", true, tgt_kpts, src_kpts, tgt_idx, src_idx, n_corr, params, result, clique, cap);
 	}
 	catch (...)
 	{

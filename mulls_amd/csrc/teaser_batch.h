@@ -4,7 +4,7 @@
 //                bytes, are nearly all of it at large n) — the arena of a sub-batch stays at or below the limit;
 //   GNC phase    the weights, C (C - 1) / 2 doubles per problem, known only after the clique search — the problems of one graph sub-batch are cut
 //                again so that the weights of the problems that run the loop in lock-step stay at or below the limit.
-// A problem larger than the limit runs alone.  The descriptor table (one TeaserBatchDesc per problem) is what the kernels of k_teaser_batch.hip read.
+// A problem larger than the limit runs alone.  The descriptor table (one TeaserBatchDesc per problem) is what the k_tb_* kernels of k_teaser.hip read.
 #pragma once
 #include <stdint.h>
 

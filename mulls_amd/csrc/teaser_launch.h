@@ -1,4 +1,4 @@
-// teaser_launch.h — host-callable launchers of k_teaser.hip: the TEASER coarse-registration solver, CRegistration::coarse_reg_teaser
+// teaser_launch.h — host-callable launchers of k_teaser.hip and k_teaser_clique.hip: the TEASER coarse-registration solver, CRegistration::coarse_reg_teaser
 // (cregistration.hpp:664-759).  The device builds the pair-consistency graph as a bit matrix, peels it to core numbers, bounds the clique from below with
 // a greedy clique per vertex and compacts the vertices that can still belong to a maximum clique; the exact search runs on the host (teaser_host.h) or,
 // with MULLS_OPT_TEASER_DEVICE_SEARCH, on the device (k_teaser_clique.hip, the scheme of teaser_search.h); the GNC-TLS rotation runs on the device
@@ -8,6 +8,7 @@
 #include <hip/hip_vector_types.h>
 #include <stdint.h>
 
+#include "teaser_batch.h"
 #include "teaser_math.h"
 #include "teaser_search.h"
 
@@ -27,6 +28,22 @@ hipError_t launch_teaser_pick(hipStream_t st, const float4 *src, const float4 *t
 // (weights, S->n_inlier; skipped on the device when S->stop == 1).  part: 9 * MULLS_TEASER_PARTIALS doubles.
 hipError_t launch_teaser_gnc_iteration(hipStream_t st, const float4 *cs, const float4 *ct, uint32_t C, int iter, double nb2, double *weights, double *part,
 									   TeaserGnc *S);
+
+// ---- the same steps over the problems of one sub-batch of mulls_coarse_reg_teaser_batch per launch.  desc: the sub-batch's descriptor table in device memory
+// (teaser_batch.h), arena: the base its offsets count from.
+// the jobs' device-resident clouds into the points of their problems; n_max: the largest job
+hipError_t launch_teaser_batch_gather(hipStream_t st, const TeaserBatchGather *jobs, uint32_t n_jobs, uint32_t n_max, unsigned char *arena);
+// of every problem: the bit matrix, the degrees and deg_sum[b] (zeroed by the caller), the core numbers, the greedy clique sizes (behind the core numbers)
+hipError_t launch_teaser_batch_graph(hipStream_t st, const TeaserBatchDesc *desc, uint32_t B, uint32_t n_max, unsigned char *arena, double beta,
+									 unsigned long long *deg_sum);
+// of every problem with m > 0: the m x Wm sub-matrix of the vertices of its keep list; words_max: the largest m * Wm
+hipError_t launch_teaser_batch_compact(hipStream_t st, const TeaserBatchDesc *desc, uint32_t B, uint64_t words_max, unsigned char *arena);
+// of every problem: cs[k] = src[keep[k]], ct[k] = tgt[keep[k]], k < C
+hipError_t launch_teaser_batch_pick(hipStream_t st, const TeaserBatchDesc *desc, uint32_t B, uint32_t C_max, unsigned char *arena);
+// GNC iteration `iter` of the problems first .. first + count that still run (C >= 2, no stop word from an earlier iteration): launch_teaser_gnc_iteration's
+// five steps, one launch each for all of them.  gnc, frozen: one entry per problem of the sub-batch (frozen zeroed before iteration 0).
+hipError_t launch_teaser_batch_gnc_iteration(hipStream_t st, const TeaserBatchDesc *desc, uint32_t first, uint32_t count, uint64_t M_max, int iter, double nb2,
+											 unsigned char *arena, unsigned char *weights, TeaserGnc *gnc, uint32_t *frozen);
 
 // ---- k_teaser_clique.hip: the device clique search (teaser_search.h has the scheme)
 // later[v] = the neighbours of v above v in the m x ceil(m / 64) matrix sub

@@ -73,7 +73,7 @@ TEASER_HD inline double teaser_weight(double r, double mu, double nb2)
 TEASER_HD inline double teaser_mu0(double max_r, double nb2) { return 1.0 / ((2.0 * max_r) / nb2 - 1.0); }
 
 // the pairwise tree over the MULLS_TEASER_PARTIALS partial sums, in place: p[t] += p[t + s] for s = PARTIALS / 2, ..., 1 (the CPU form; the device runs the
-// same additions in k_teaser_fit / k_teaser_cost)
+// same additions in teaser_fit / teaser_cost of k_teaser.hip)
 inline double teaser_tree_host(double *p)
 {
 	for (uint32_t s = MULLS_TEASER_PARTIALS / 2u; s > 0; s >>= 1)

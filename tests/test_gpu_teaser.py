@@ -28,7 +28,10 @@ def device(ctx, t, s, nb, min_inlier=8, cap=None, budget=abi.TEASER_DEFAULT_NODE
     def rec(x):
         return tr.records(x) if isinstance(x, np.ndarray) and x.ndim == 2 and x.shape[1] == 4 and x.dtype == np.float32 else x
 
-    res, clique = ctx.coarse_reg_teaser(rec(t), rec(s), abi.teaser_params(nb, min_inlier, budget), cap, **kw)
+    return as_dict(*ctx.coarse_reg_teaser(rec(t), rec(s), abi.teaser_params(nb, min_inlier, budget), cap, **kw))
+
+
+def as_dict(res, clique):
     out = {k: int(getattr(res, k)) for k in INT_KEYS + ("clique_nodes",)}
     out.update(cost=float(res.cost), T=np.array(res.T[:], np.float64).reshape(4, 4).T.copy(), clique=clique.astype(np.int64))
     return out
@@ -100,6 +103,80 @@ def test_outcomes_and_refusals(ctx_auto):
     assert_same(device(ctx_auto, t, s, nb), fixture_case("size_64"), "after refusals")  # and the context goes on
     z = device(ctx_auto, t, s, 0.0)  # a zero bound is allowed: only exactly equal distances are consistent
     assert z["status"] == -1 and z["clique_size"] <= 2
+
+
+def test_single_entry_points_at_their_own_edges(ctx_auto):
+    """what only the single entry points define: the indexed call's early returns (no pairs and NULL lists, three pairs), one index list without the other,
+    a NULL result, a clique capacity without a buffer — and the message of every refusal that sets one names the entry point that was called"""
+    L = lib.load()
+    t, s, nb = input_sets()["size_64"]
+    rt, rs = tr.records(t), tr.records(s)
+    ct, cs = cloud_of(rt), cloud_of(rs)
+    good = abi.teaser_params(nb)
+    res, cl = abi.TeaserResult(), np.full(8, -7, np.int32)
+    ip = cl.ctypes.data_as(C.c_void_p)
+    idx = np.arange(64, dtype=np.int32)
+
+    def vp(a):
+        return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+    def plain(a, b, P=good, result=res, clique=ip, cap=4):
+        return L.mulls_coarse_reg_teaser(ctx_auto.h, C.byref(a), C.byref(b), C.byref(P), result, clique, cap)
+
+    def indexed(ti, si, n, a=ct, b=cs, P=good, result=res, clique=ip, cap=4):
+        return L.mulls_coarse_reg_teaser_indexed(ctx_auto.h, C.byref(a), C.byref(b), vp(ti), vp(si), n, C.byref(P), result, clique, cap)
+
+    for ti, si, n in ((None, None, 0), (idx, idx, 3)):  # upstream: "too few correspondences", -1
+        res.status, res.clique_size = 5, 9
+        assert indexed(ti, si, n) == abi.MULLS_OK
+        assert res.status == -1 and res.clique_size == 0 and np.array_equal(np.array(res.T[:]).reshape(4, 4), np.eye(4)) and (cl == -7).all()
+    assert indexed(idx, None, 64) == abi.MULLS_E_INVALID and indexed(None, idx, 64) == abi.MULLS_E_INVALID
+    assert plain(ct, cs, result=None) == abi.MULLS_E_INVALID and indexed(idx, idx, 64, result=None) == abi.MULLS_E_INVALID
+    assert plain(ct, cs, clique=None) == abi.MULLS_E_INVALID and indexed(idx, idx, 64, clique=None) == abi.MULLS_E_INVALID
+
+    def said(who):
+        msg = L.mulls_last_error(ctx_auto.h) or b""
+        assert msg.startswith(who + b":") and b"problem" not in msg, msg
+
+    big, odd = np.zeros((8193, 48), np.uint8), np.zeros((64, 18), np.uint8)
+    many, bad = np.zeros(8193, np.int32), idx.copy()
+    bad[10] = 64
+    nan = abi.teaser_params(float("nan"))
+    for refuse, who, code in ((lambda: plain(cloud_of(big), cloud_of(big)), b"mulls_coarse_reg_teaser", abi.MULLS_E_UNSUPPORTED),
+                              (lambda: plain(cloud_of(odd, 18), cs), b"mulls_coarse_reg_teaser", abi.MULLS_E_INVALID),
+                              (lambda: plain(ct, cs, P=nan), b"mulls_coarse_reg_teaser", abi.MULLS_E_INVALID),
+                              (lambda: indexed(many, many, 8193), b"mulls_coarse_reg_teaser_indexed", abi.MULLS_E_UNSUPPORTED),
+                              (lambda: indexed(idx, idx, 64, a=cloud_of(odd, 18)), b"mulls_coarse_reg_teaser_indexed", abi.MULLS_E_INVALID),
+                              (lambda: indexed(bad, idx, 64), b"mulls_coarse_reg_teaser_indexed", abi.MULLS_E_INVALID),
+                              (lambda: indexed(idx, idx, 64, P=nan), b"mulls_coarse_reg_teaser_indexed", abi.MULLS_E_INVALID)):
+        res.status = 5
+        assert refuse() == code
+        said(who)
+        assert res.status == -1 and (cl == -7).all()
+    assert_same(device(ctx_auto, t, s, nb, tgt_idx=idx, src_idx=idx), fixture_case("size_64"), "after refusals")
+
+
+def test_batch_and_single_calls_share_one_scratch():
+    """one context: a batch, a single call, a batch, a single call — the grow-only scratch carries nothing from one kind of call into the other"""
+    ctx = lib.Context(0)
+    try:
+        def batch(names):
+            sets = [input_sets()[name] for name in names]
+            assert all(nb == 0.2 for _, _, nb in sets)
+            got = ctx.coarse_reg_teaser_batch([(tr.records(t), tr.records(s)) for t, s, _ in sets], abi.teaser_params(0.2))
+            for (res, clique), name in zip(got, names):
+                assert_same(as_dict(res, clique), fixture_case(name), ("batch", name))
+
+        def single(name):
+            t, s, nb = input_sets()[name]
+            assert_same(device(ctx, t, s, nb), fixture_case(name), ("single", name))
+
+        batch(["size_1025", "complete_300", "no_edge"])
+        single("size_31")
+        batch(["exit_cost"])
+        single("size_1025")
+    finally:
+        ctx.close()
 
 
 def strided(raw, stride, seed):

@@ -1,10 +1,12 @@
-"""GPU tests of mulls_coarse_reg_teaser_batch through mulls_amd/lib.py: results[b] and the clique of problem b are the bits of the matching single call.
+"""GPU tests of mulls_coarse_reg_teaser_batch through mulls_amd/lib.py: results[b] and the clique of problem b are what the definition gives for problem b alone.
 
 Expected values are the fixture tests/golden/teaser_cases.npz (the numpy restatement, tests/test_teaser.py) where a set's own noise bound and min_inlier_num
-are the batch's, and the single call (mulls_coarse_reg_teaser / _indexed on the same context options) where they are not: a batch has ONE mulls_teaser_params,
-and the fixture's sets do not all share theirs (exit_limit: 1e6; the planted sets: min_inlier_num 3; the demo lists: 0.25 and 1.0).  So the mixed batch
-runs at 0.2 (the fixture's bound of all its sets but exit_limit) and again at 1e6 (exit_limit's: it runs all 100 GNC iterations beside problems that stop at
-iteration 0), and the demo lists run at 0.25 and at 1.0.  Nothing is ever compared with the batch path itself, except where a test is about repetition.
+are the batch's, and the same restatement (tests/teaser_restated.py: restate) run at the batch's parameters where they are not: a batch has ONE
+mulls_teaser_params, and the fixture's sets do not all share theirs (exit_limit: 1e6; the planted sets: min_inlier_num 3; the demo lists: 0.25 and 1.0).  So the
+mixed batch runs at 0.2 (the fixture's bound of all its sets but exit_limit) and again at 1e6 (exit_limit's: it runs all 100 GNC iterations beside problems that
+stop at iteration 0), and the demo lists run at 0.25 and at 1.0.  The single entry points compile the kernel text of the batch and share its argument checker, so no expectation comes
+from them: they appear only where the search's effort (clique_nodes, which the restatement does not define) must be the same through either entry form, and in
+test_one_problem_equals_the_single_call, which holds the two entry forms against each other.
 
 Every comparison is equality, as in tests/test_gpu_teaser.py: the integers, the clique list, every bit of cost and T; clique_nodes equals the single call's
 when the host search runs."""
@@ -15,8 +17,8 @@ import pytest
 
 import teaser_restated as tr
 from mulls_amd import abi, lib
-from test_gpu_teaser import assert_same, cloud_of, device, strided
-from test_teaser import INT_KEYS, demo, fixture_case, input_sets
+from test_gpu_teaser import as_dict, assert_same, cloud_of, device, strided
+from test_teaser import demo, fixture_case, input_sets
 
 pytestmark = pytest.mark.gpu
 
@@ -38,19 +40,15 @@ def clouds(name):
     return tr.records(t), tr.records(s)
 
 
-def as_dict(res, clique):
-    out = {k: int(getattr(res, k)) for k in INT_KEYS + ("clique_nodes",)}
-    out.update(cost=float(res.cost), T=np.array(res.T[:], np.float64).reshape(4, 4).T.copy(), clique=clique.astype(np.int64))
-    return out
-
-
 def run_batch(ctx, problems, nb, min_inlier=8, limit=0):
     return [as_dict(r, c) for r, c in ctx.coarse_reg_teaser_batch(problems, abi.teaser_params(nb, min_inlier), limit)]
 
 
 @pytest.fixture(scope="module")
 def expected(ctx_auto):
-    """what problem `name` must give at (nb, min_inlier): the fixture where its parameters are these, else the single call — computed once, left unchanged"""
+    """what problem `name` must give at (nb, min_inlier): the fixture where its parameters are these, else the numpy restatement run at them (every such set is
+    small: at most 0.3 s, complete_300 at 1e6) — computed once, left unchanged.  single=True: the single entry point, for its clique_nodes and for the
+    test of the two entry forms against each other."""
     cache, from_fixture = {}, set()
 
     def get(name, nb, min_inlier=8, single=False):
@@ -58,15 +56,19 @@ def expected(ctx_auto):
         if key not in cache:
             if name in ("three_pairs", "unequal"):
                 cache[key] = FAILED
-            elif not single and np.float32(input_sets()[name][2]) == np.float32(nb) and tr.min_inlier(name) == min_inlier:
+            elif single:
+                t, s = clouds(name)
+                cache[key] = device(ctx_auto, t, s, nb, min_inlier)
+            elif np.float32(input_sets()[name][2]) == np.float32(nb) and tr.min_inlier(name) == min_inlier:
                 cache[key] = fixture_case(name)
                 from_fixture.add(key[:3])
             else:
-                t, s = clouds(name)
-                cache[key] = device(ctx_auto, t, s, nb, min_inlier)
+                t, s, _ = input_sets()[name]
+                cache[key] = tr.restate(t, s, nb, min_inlier)
+                assert cache[key]["clique_exact"] == 1
         return cache[key]
 
-    get.from_fixture = from_fixture  # the (name, nb, min_inlier) whose expectation is the fixture's and not the single call's
+    get.from_fixture = from_fixture  # the (name, nb, min_inlier) whose expectation is the fixture's and not the restatement's run here
     return get
 
 

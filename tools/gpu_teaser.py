@@ -10,7 +10,9 @@ pairs next to it.  The search is given --budget nodes (default 2^20, so that a t
                                                each per case, search_seconds and clique_nodes of either, and whether every result field agrees
     python tools/gpu_teaser.py --batch 1,8,64  mulls_coarse_reg_teaser_batch: B copies of a demo pair list (recip_0_15 and fixed300_0_15 at the bound 0.25), and a
                                                mixed list of B problems (the four small pair lists in turn), through the batch entry and as B single calls on the
-                                               same context: every result field compared, both wall times as the median of 20
+                                               same context: every result field compared, both wall times as the median of 20.  The two paths compile one kernel
+                                               text; the single call passes launch arguments where the batch reads a descriptor, so the "B single calls" column
+                                               is B times the per-call cost (launches, copies, synchronisations) and the ratio what sharing them among B saves
     --cases fixed2000_0_15:1.0,nn_15_0:0.25    only these rows (pair list of tests/golden/ncc_demo.npz : bound); with --search device --calls 1, the run to trace the search's kernels with
 """
 import os
@@ -71,7 +73,8 @@ def same_result(a, ca, b, cb):
 
 
 def batch_mode(sizes, budget, search, calls):
-    """B problems through mulls_coarse_reg_teaser_batch and as B calls of mulls_coarse_reg_teaser_indexed: equality of every field, and the two wall times"""
+    """B problems through mulls_coarse_reg_teaser_batch and as B calls of mulls_coarse_reg_teaser_indexed (the same kernel text, one problem per call): equality of
+    every field, and the two wall times"""
     Z = np.load(os.path.join(ROOT, "tests", "golden", "ncc_demo.npz"))
 
     def problem(name):
