@@ -229,7 +229,8 @@ enum mulls_option
 	MULLS_OPT_LEAN_STAGING = 13,		  /* [0] mulls_icp / mulls_icp_batch stage only what the registration reads: the classes of used_feature_type (plus the
 											 source ground / pillar / facade clouds the intersection box is taken from).  mulls_result.nsrc0 / ntgt0 of the
 											 classes left out report 0; every output of the reference's interface is unchanged.  The C++ bridge switches it on. */
-	MULLS_OPT_DEBUG_STOP = 14,			  /* [0] kernel bring-up switches (tools/gpu_time_nn.py) */
+	MULLS_OPT_DEBUG_STOP = 14,			  /* [0] kernel bring-up switches (tools/gpu_time_nn.py; the values: tools/README.md).  30: the setup of a run in its
+											 former shape — k_clone_src + k_crop for every pair, one 19-trip k_tgt_grid workgroup per class cloud */
 	MULLS_OPT_DEBUG_TICK = 15,			  /* [0] tests: start a fresh batch's duplicate-table epoch counter here */
 	MULLS_OPT_SPLIT_MIN_PAIRS = 16,		  /* [96]    lock-step loop stepped on the device: batches of MIN .. MAX pairs iterate as two sub-batches on two streams, */
 	MULLS_OPT_SPLIT_MAX_PAIRS = 17,		  /* [2^30]  so that one half's kernels fill the gaps of the other's (MAX < MIN: never; not while profiling: +3 % at */

@@ -374,6 +374,41 @@ void build_jobs(mulls_batch *B, const mulls_params *P, int nsub, int mode)
 			B->ajob_split[k][3] = (uint32_t)B->ajobs_h.size();
 		}
 	}
+	// the setup's index tables
+	{
+		std::vector<uint32_t> &tab = B->setup_tab_h;
+		tab.clear();
+		const uint32_t *trips = tgt_grid_bucket_trips();
+		for (int k = 0; k < MULLS_TG_BUCKETS; k++)
+		{
+			// (an empty cloud goes to the smallest bucket: it still gets its empty grid descriptor and tgt_n = 0)
+			B->tg_split[k] = (uint32_t)tab.size();
+			for (uint32_t ci = 0; ci < (uint32_t)B->descs_h.size(); ci++)
+			{
+				const CloudDesc &d = B->descs_h[ci];
+				const uint32_t need = (d.tgt_n0 + 511u) / 512u;
+				if (d.tier == MULLS_TIER_LDS && need <= trips[k] && (k == 0 || need > trips[k - 1]))
+					tab.push_back(ci);
+			}
+		}
+		B->tg_split[MULLS_TG_BUCKETS] = (uint32_t)tab.size();
+		for (int seg = 0; seg < 3; seg++)
+		{
+			B->crop_split[seg] = (uint32_t)tab.size();
+			for (uint32_t ci = 0; ci < (uint32_t)B->descs_h.size(); ci++)
+			{
+				const bool lds = B->descs_h[ci].tier == MULLS_TIER_LDS;
+				if (seg == 0 ? !B->src_one_wg[ci / MULLS_NC] : (seg == 1 ? !lds : lds))
+					tab.push_back(ci * 2u + (seg ? 1u : 0u));
+			}
+		}
+		B->crop_split[3] = (uint32_t)tab.size();
+		B->srcp_split[0] = (uint32_t)tab.size();
+		for (int p = 0; p < B->n; p++)
+			if (B->src_one_wg[p])
+				tab.push_back((uint32_t)p);
+		B->srcp_split[1] = (uint32_t)tab.size();
+	}
 	B->njobs = (uint32_t)B->jobs_h.size();
 	B->jobs_key = key;
 }
@@ -531,6 +566,8 @@ int batch_fill(mulls_ctx *ctx, mulls_batch *B, const mulls_pair *pairs, int n, c
 	B->descs_h.assign((size_t)n * MULLS_NC, CloudDesc());
 	B->setup_h.assign(n, PairSetup());
 	B->setup_jobs_h.clear();
+	B->src_one_wg.assign(n, 0);
+	std::vector<Job> one_wg_jobs;
 	B->big_segs_h.clear();
 	B->big_clouds_h.clear();
 	B->n_big_tgt = 0;
@@ -594,12 +631,27 @@ int batch_fill(mulls_ctx *ctx, mulls_batch *B, const mulls_pair *pairs, int n, c
 					B->big_segs_h.push_back({(uint32_t)p, (uint32_t)c | MULLS_BIG_SRC_SIDE, k, slot});
 				B->big_clouds_h.push_back({(uint32_t)p, (uint32_t)c | MULLS_BIG_SRC_SIDE, first, (uint32_t)B->big_segs_h.size() - first});
 			}
+		}
+		{
+			uint64_t src_total = 0;
+			bool seg = false;
+			for (int c = 0; c < MULLS_NC; c++)
+			{
+				const CloudDesc &d = B->descs_h[p * MULLS_NC + c];
+				src_total += d.src_n0;
+				seg = seg || d.src_big_slot != 0u;
+			}
+			B->src_one_wg[p] = !seg && src_total <= MULLS_SRC_SETUP_CAP;
+		}
+		for (int c = 0; c < MULLS_NC; c++)
+		{
+			const CloudDesc &d = B->descs_h[p * MULLS_NC + c];
 			// clone jobs: 256 source points each; eight times that for a dense scan's clouds (k_clone_src: fewer atomics on the pair's box)
 			const uint32_t chunks = d.src_cap > 8192u ? 8u : 1u;
 			for (uint32_t k = 0; k < d.src_cap; k += MULLS_BLOCK * chunks)
 			{
 				Job j = {(uint32_t)p, (uint32_t)c, k, chunks};
-				B->setup_jobs_h.push_back(j);
+				(B->src_one_wg[p] ? one_wg_jobs : B->setup_jobs_h).push_back(j);
 			}
 		}
 		rows12(pairs[p].init_guess, B->setup_h[p].guess);
@@ -618,6 +670,8 @@ int batch_fill(mulls_ctx *ctx, mulls_batch *B, const mulls_pair *pairs, int n, c
 			B->setup_h[p].inv_t[3] = std::acos(std::min(1.0, std::fabs(B->setup_h[p].inv_q[0])));
 		}
 	}
+	B->n_setup_jobs_rest = (uint32_t)B->setup_jobs_h.size();
+	B->setup_jobs_h.insert(B->setup_jobs_h.end(), one_wg_jobs.begin(), one_wg_jobs.end());
 	if (stage_rec >= (1ull << 32) || so >= (1ull << 31) || to >= (1ull << 31))
 	{
 		ctx->err = "batch too large (>= 2^31 points)";
@@ -891,6 +945,8 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 	A(grow(ctx, &B->wl, &B->cap_wl, B->cjobs_h.size()));
 	A(grow(ctx, &B->ajobs, &B->cap_ajobs, B->ajobs_h.size(), &g2));
 	grew |= g2;
+	A(grow(ctx, &B->setup_tab, &B->cap_setup_tab, B->setup_tab_h.size(), &g2));
+	grew |= g2;
 	if (!B->wl_ctr)
 		A(dmalloc(ctx, &B->wl_ctr, 16));
 	if (rc == MULLS_OK)
@@ -927,6 +983,7 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 		up.add_host(B->ejobs, B->ejobs_h.data(), sizeof(Job) * B->ejobs_h.size());
 		up.add_host(B->lclouds, B->lclouds_h.data(), sizeof(uint32_t) * B->lclouds_h.size());
 		up.add_host(B->ajobs, B->ajobs_h.data(), sizeof(uint32_t) * B->ajobs_h.size());
+		up.add_host(B->setup_tab, B->setup_tab_h.data(), sizeof(uint32_t) * B->setup_tab_h.size());
 		up.add_host(B->descs_init, B->descs_h.data(), sizeof(CloudDesc) * B->descs_h.size());
 		up.add_host(B->bbox_init, B->bbox_h, sizeof(uint32_t) * 6 * n);
 		if (up.flush(st) != MULLS_OK)
@@ -950,10 +1007,29 @@ int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunP
 // ---- the launch sequences every entry point that runs a batch shares (mulls_batch_run, the 3-DOF variant, the stage-level entry points) ----------------------
 
 // clone + initial guess + intersection filter (cregistration.hpp:1180-1188)
+// MULLS_OPT_DEBUG_STOP = 30 (bring-up): the setup in its former shape — k_clone_src + k_crop for every pair, one full-reach k_tgt_grid workgroup per class cloud —
+// to set the shapes below against (tests/test_gpu_setup_forms.py, profiles/setup_forms.txt)
+bool setup_former_shape(const RunParams &rp) { return rp.debug_stop == 30u; }
+
+// A pair whose six source clouds fit one workgroup gets its clone, box and crop in one launch (k_src_setup; not while undistorting: the regenerated clouds take
+// k_clone_src's path); the other pairs go through k_clone_src + k_crop, whose workgroup list also holds the target sides that k_tgt_grid does not crop.
 void queue_clone_crop(hipStream_t st, const mulls_batch *B, const RunParams &rp)
 {
-	launch_clone_src(st, *B, rp, (uint32_t)B->setup_jobs_h.size());
-	launch_crop(st, *B, rp, (uint32_t)B->n, (uint32_t)B->big_segs_h.size(), (uint32_t)B->big_clouds_h.size());
+	const uint32_t nbig_segs = (uint32_t)B->big_segs_h.size(), nbig_clouds = (uint32_t)B->big_clouds_h.size();
+	if (setup_former_shape(rp))
+	{
+		launch_clone_src(st, *B, rp, (uint32_t)B->setup_jobs_h.size());
+		launch_crop(st, *B, rp, (uint32_t)B->n, nbig_segs, nbig_clouds);
+		return;
+	}
+	const bool one_wg = !rp.undistort;
+	launch_clone_src(st, *B, rp, one_wg ? B->n_setup_jobs_rest : (uint32_t)B->setup_jobs_h.size());
+	if (one_wg)
+		launch_src_setup(st, *B, rp, B->setup_tab + B->srcp_split[0], B->srcp_split[1] - B->srcp_split[0]);
+	if (one_wg) // (the target sides on the LDS tier only when no k_tgt_grid crops them)
+		launch_crop(st, *B, rp, (uint32_t)B->n, nbig_segs, nbig_clouds, B->setup_tab + B->crop_split[0], B->crop_split[rp.tgt_map ? 2 : 3] - B->crop_split[0]);
+	else
+		launch_crop(st, *B, rp, (uint32_t)B->n, nbig_segs, nbig_clouds);
 }
 
 // keep_less_source_points: thin the cropped clouds by the caller's keep masks (one byte per staged source / target point)
@@ -984,8 +1060,10 @@ int apply_keep_masks(mulls_ctx *ctx, const mulls_batch *B, const std::vector<uin
 // the target grids: the LDS tier's (fused_tgt: crop and grid in one pass, no cropped copy; else from the copies k_crop wrote), then the bitmap grids
 void queue_target_grids(hipStream_t st, const mulls_batch *B, const RunParams &rp, int tier, bool fused_tgt)
 {
-	if (fused_tgt)
+	if (fused_tgt && setup_former_shape(rp))
 		(void)launch_tgt_grid(st, *B, rp, (uint32_t)B->n);
+	else if (fused_tgt)
+		(void)launch_tgt_grid(st, *B, rp, (uint32_t)B->n, B->setup_tab, B->tg_split);
 	else if (tier == 2)
 		launch_grid_build_sort(st, *B, rp, (uint32_t)B->n);
 	launch_bm_build(st, *B, (uint32_t)B->lclouds_h.size(), (uint32_t)B->tjobs_h.size());

@@ -60,7 +60,16 @@ struct mulls_batch : BatchDev
 	size_t n_src = 0, n_tgt = 0; // staged points over all pairs and classes
 	std::vector<CloudDesc> descs_h;
 	std::vector<PairSetup> setup_h;
-	std::vector<Job> setup_jobs_h;
+	std::vector<Job> setup_jobs_h; // k_clone_src's jobs: those of the pairs that need them whatever the run is first (n_setup_jobs_rest), then those of the pairs
+								   // k_src_setup can take (src_one_wg)
+	uint32_t n_setup_jobs_rest = 0;
+	std::vector<uint8_t> src_one_wg; // per pair: no source cloud cropped segment-wise and at most MULLS_SRC_SETUP_CAP staged source points (batch_fill)
+	// the setup's index tables (build_jobs; device copy: setup_tab).  tg_split: k_tgt_grid's size buckets, LDS-tier class clouds as pair * MULLS_NC + class.
+	// crop_split: k_crop's workgroups, (pair * MULLS_NC + class) * 2 + side — [0, 1) source sides of the pairs outside src_one_wg, [1, 2) target sides off the LDS
+	// tier, [2, 3) target sides on it (k_tgt_grid crops those when the setup is fused).  srcp_split: the pairs of src_one_wg.
+	std::vector<uint32_t> setup_tab_h;
+	uint32_t tg_split[MULLS_TG_BUCKETS + 1] = {}, crop_split[4] = {}, srcp_split[2] = {};
+	size_t cap_setup_tab = 0;
 	std::vector<Job> big_segs_h, big_clouds_h; // class clouds cropped segment-wise (k_crop_big_*): segments, clouds (Job::cls carries MULLS_BIG_SRC_SIDE for a source cloud)
 	uint32_t n_big_tgt = 0;					   // ... how many of those clouds are targets
 	std::vector<Job> jobs_h;
@@ -161,6 +170,7 @@ int batch_fill(mulls_ctx *ctx, mulls_batch *B, const mulls_pair *pairs, int n, c
 int prepare_run(mulls_ctx *ctx, mulls_batch *B, const mulls_params *P_jobs, RunParams &rp, uint32_t *lds_cap_out, int *tier_out, int nsub = 0, bool allow_mixed = false);
 // the launch sequences the entry points share (batch.cpp, behind prepare_run); st: where the set-up goes, ctx->stream otherwise
 void queue_clone_crop(hipStream_t st, const mulls_batch *B, const RunParams &rp);
+bool setup_former_shape(const RunParams &rp);
 int apply_keep_masks(mulls_ctx *ctx, const mulls_batch *B, const std::vector<uint8_t> &skeep, const std::vector<uint8_t> &tkeep, const char *what);
 void queue_target_grids(hipStream_t st, const mulls_batch *B, const RunParams &rp, int tier, bool fused_tgt);
 int queue_tier_search(mulls_ctx *ctx, const mulls_batch *B, const RunParams &rp, int tier, uint32_t lds_cap, uint32_t parity);

@@ -7,20 +7,25 @@
 // (ordered keys from k_clone_src) against block1->local_bound, padded by 1 m
 namespace
 {
-__device__ __forceinline__ void crop_box(uint32_t pair, const uint32_t *__restrict__ bbox, const PairSetup *__restrict__ setup, double lo[3],
-										  double hi[3])
+// keys: the six ordered keys of the pair's source box (global memory, or a workgroup's own reduction of them)
+__device__ __forceinline__ void crop_box_keys(const uint32_t *keys, const PairSetup &su, double lo[3], double hi[3])
 {
 	for (int k = 0; k < 3; k++)
 	{
-		uint32_t kmin = bbox[pair * 6 + k], kmax = bbox[pair * 6 + 3 + k];
+		uint32_t kmin = keys[k], kmax = keys[3 + k];
 		// an empty union keeps (+DBL_MAX, -DBL_MAX) like CloudUtility::merge_bbx (utility.hpp:867-884)
 		double mmin = (kmin == 0xffffffffu && kmax == 0u) ? 1.7976931348623157e308 : (double)ord2f(kmin);
 		double mmax = (kmin == 0xffffffffu && kmax == 0u) ? -1.7976931348623157e308 : (double)ord2f(kmax);
-		double b1min = setup[pair].tgt_bound[k], b1max = setup[pair].tgt_bound[3 + k];
+		double b1min = su.tgt_bound[k], b1max = su.tgt_bound[3 + k];
 		const float pad = 1.0f;
 		lo[k] = ((b1min > mmin) ? b1min : mmin) - pad; // get_intersection_bbx, utility.hpp:857-865
 		hi[k] = ((b1max < mmax) ? b1max : mmax) + pad;
 	}
+}
+__device__ __forceinline__ void crop_box(uint32_t pair, const uint32_t *__restrict__ bbox, const PairSetup *__restrict__ setup, double lo[3],
+										  double hi[3])
+{
+	crop_box_keys(bbox + pair * 6, setup[pair], lo, hi);
 }
 // strict inequalities, float coordinate promoted to double (cfilter.hpp:959-961)
 __device__ __forceinline__ bool crop_keep(const float4 &p, const double lo[3], const double hi[3])

@@ -28,6 +28,8 @@
 #ifndef MULLS_LDS_GROUP // (4u / 16u: A/B builds, tools/build_variant.sh)
 #define MULLS_LDS_GROUP 8u	   // lanes that cooperate on one query in the LDS grid tier (DPP reductions stay inside a 16-lane row)
 #endif
+#define MULLS_TG_BUCKETS 4	   // size buckets of the LDS tier's fused target setup (k_tgt_grid by trip count; launch_tgt_grid names the trips)
+#define MULLS_SRC_SETUP_CAP 4096u // most staged source points of a pair (its six clouds together) whose clone, box and crop run in one workgroup (k_src_setup)
 #define MULLS_BIG_CLOUD 16384u // class clouds above this size (target or source) are cropped segment-wise (k_crop_big_*): one workgroup walking a 100 k-point
 							   // cloud alone took 290 us (profiles/r04_large_base.txt)
 #define MULLS_BIG_SRC_SIDE 0x100u // Job::cls flag in the segment tables: the segment belongs to the pair's SOURCE cloud of that class
@@ -183,7 +185,8 @@ struct RunParams
 	float class_w_value;
 	double cos_bearing; // cos(normal_bearing / 180.0 * M_PI) in double, computed on the host
 	int32_t resid_from_iter; // residual weighting applies when iter_num > this (2 for mm_lls_icp, cregistration.hpp:1905-1907; -1 for the 3-DoF variant)
-	uint32_t debug_stop;	// diagnostics only (env MULLS_DEBUG_STOP): 1 = k_nn_lds returns after the transform, 2 = after staging
+	uint32_t debug_stop;	// diagnostics only (env MULLS_DEBUG_STOP): 1 = k_nn_lds returns after the transform, 2 = after staging; 30 = the host queues the setup in its
+							// former shape (setup_former_shape, batch.cpp): k_clone_src + k_crop for every pair, one 19-trip k_tgt_grid workgroup per class cloud
 	uint32_t cell_stride;	// entries reserved per cloud in the cell tables (multiple of 4: uint4-aligned), >= grid_maxcells + 1
 	uint32_t grid_maxcells; // cell budget of the target grids built by k_crop (MULLS_MAXCELLS, or what fits in LDS for the LDS tier)
 	float grid_h0;		// LDS tier: preferred cell edge (MULLS_GRID_H0; grows until the cloud's box fits grid_maxcells)

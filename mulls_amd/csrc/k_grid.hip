@@ -357,22 +357,40 @@ __global__ __launch_bounds__(MULLS_LDS_BLOCK) void k_grid_build_sort(const Cloud
 // crop, the cell count and the scatter; it writes the map rank in the cropped cloud -> staged index (2 B: the consumers gather the few target
 // records they need — a correspondence's position and direction when it changes — from the staged cloud through it, tgt_record()) and the
 // cell-sorted positions (16 B): 34 B per point.  Same cropped order (stable), grid descriptor, cell table and tsorted records (w = rank in the
-// cropped cloud) as the two kernels give.  LDS: the cell counters (two 16-bit counters per word) or the sort keys — 64 KiB; registers capped at 128: two workgroups per CU
-// (1.21 ms per 4096 pairs as one 1024-lane workgroup per CU, 0.88 ms like this; the phases by MULLS_DEBUG_STOP 11 - 15: DESIGN.md section 12.3).
+// cropped cloud) as the two kernels give.  LDS: the cell counters (two 16-bit counters per word) or the sort keys.  The 19-trip form with 64 KiB of them and registers
+// capped at 128 holds two workgroups per CU (1.21 ms per 4096 pairs as one 1024-lane workgroup per CU, 0.88 ms like this; the phases by MULLS_DEBUG_STOP 11 - 15:
+// DESIGN.md section 12.3).
 #define MULLS_TG_LANES 512u
 #define MULLS_TG_WAVES (MULLS_TG_LANES / 64u)
 #define MULLS_TG_TRIPS ((MULLS_LDS_MAXPTS + MULLS_TG_LANES - 1u) / MULLS_TG_LANES)
-__global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__restrict__ descs, const PairSetup *__restrict__ setup, const uint32_t *__restrict__ bbox,
-															   const float4 *__restrict__ stage, RunParams rp, GridDesc *__restrict__ grids, uint16_t *__restrict__ tmap,
-															   uint32_t *__restrict__ cell_start, float4 *__restrict__ tsorted)
+// The kernel by trip count.  TRIPS x 512 points is what a workgroup covers: every loop over the trips runs TRIPS times whatever the cloud holds, and TRIPS
+// positions stay in registers, so the host sorts the class clouds into size buckets (build_jobs, by tgt_grid_bucket_trips()) and launches one instantiation per
+// bucket over its table `clouds` (pair * MULLS_NC + class each; null: every class cloud of the batch, workgroup = cloud).  K is dynamic LDS: the cell
+// counters of rp.grid_maxcells cells for the bucketed form; the SORT form keeps its static 64 KiB.
+// SORT: the bitonic branch for grids of 32768 cells and more exists.  It needs 16384 words of K.  The run's cell budget decides whether a grid can get that
+// large (make_grid stops growing the cell edge once nx * ny * nz <= rp.grid_maxcells), and the device-stepped loop caps the budget of a fused setup at 32767
+// (run_setup), so the bucketed instantiations are built without the branch and launch_tgt_grid takes them only under that cap.
+//
+// tg_waves_per_eu: the waves per SIMD the register cap is set for.  A workgroup puts two waves on every SIMD, so only even numbers buy a workgroup: 6 (80 registers, three workgroups
+// per CU) holds the 4-trip form without scratch, 8 (64 registers) does not; the 8- and 12-trip forms need more than 80.
+constexpr uint32_t tg_waves_per_eu(uint32_t trips) { return trips <= 4u ? 6u : 4u; }
+template <uint32_t TRIPS, bool SORT>
+__global__ __launch_bounds__(MULLS_TG_LANES, tg_waves_per_eu(TRIPS)) void k_tgt_grid(const uint32_t *__restrict__ clouds, CloudDesc *__restrict__ descs, const PairSetup *__restrict__ setup,
+																				   const uint32_t *__restrict__ bbox, const float4 *__restrict__ stage, RunParams rp, GridDesc *__restrict__ grids,
+																				   uint16_t *__restrict__ tmap, uint32_t *__restrict__ cell_start, float4 *__restrict__ tsorted)
 {
-	__shared__ uint32_t K[16384];						  // counting path: cell counters, two per word; sort path: (cell id, rank) keys
-	__shared__ uint32_t wcnt[MULLS_TG_TRIPS * MULLS_TG_WAVES + 32u]; // survivors per (trip, wave), then their exclusive prefix: the stable order of the points
+	// counting path: cell counters, two per word; sort path: (cell id, rank) keys
+	extern __shared__ uint32_t K_dyn[];
+	__shared__ uint32_t K_sort[SORT ? 16384u : 1u];
+	uint32_t *const K = SORT ? K_sort : K_dyn;
+	constexpr uint32_t WC_PER = (TRIPS * MULLS_TG_WAVES + 1u + 63u) / 64u, WC = WC_PER * 64u; // one wave scans the (trip, wave) counts, WC_PER per lane
+	__shared__ uint32_t wcnt[WC]; // survivors per (trip, wave), then their exclusive prefix: the stable order of the points
 	__shared__ float box_red[MULLS_TG_LANES / 64][6];
 	__shared__ uint32_t wave_tot[MULLS_TG_LANES / 64];
 	__shared__ GridDesc g_sh;
-	const uint32_t pair = blockIdx.x / MULLS_NC, cls = blockIdx.x % MULLS_NC;
-	CloudDesc &d = descs[blockIdx.x];
+	const uint32_t ci = clouds ? clouds[blockIdx.x] : blockIdx.x;
+	const uint32_t pair = ci / MULLS_NC, cls = ci % MULLS_NC;
+	CloudDesc &d = descs[ci];
 	if (d.tier != MULLS_TIER_LDS)
 		return; // a cloud of another tier (mixed batch): k_crop writes its cropped copy, the bitmap kernels build its grid
 	const uint32_t n0 = d.tgt_n0, fmt = (d.stage_fmt >> 2) & 3u;
@@ -385,7 +403,7 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 		if (threadIdx.x == 0)                                          \
 		{                                                              \
 			const float inf3[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, ninf3[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()}; \
-			grids[blockIdx.x] = make_grid(inf3, ninf3, 0u, rp, d, cls); \
+			grids[ci] = make_grid(inf3, ninf3, 0u, rp, d, cls); \
 			d.tgt_n = 0u;                                              \
 		}                                                              \
 		return;                                                        \
@@ -393,7 +411,7 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 	double lo[3], hi[3];
 	if (rp.crop)
 		crop_box(pair, bbox, setup, lo, hi);
-	float px[MULLS_TG_TRIPS], py[MULLS_TG_TRIPS], pz[MULLS_TG_TRIPS];
+	float px[TRIPS], py[TRIPS], pz[TRIPS];
 	{
 		// x y z of load_staged_pos's records, 12-byte loads (ten float4 results in flight would not fit the register budget of a 1024-lane workgroup),
 		// all of them unconditional at clamped indices: no control flow between them, every load in flight before the first is consumed.  An empty
@@ -401,7 +419,7 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 		const float4 *base = n0 ? stage + (size_t)d.tgt_stage : reinterpret_cast<const float4 *>(setup + pair);
 		const uint32_t last = n0 ? n0 - 1u : 0u, stride = fmt == MULLS_STAGE_AOS48 ? 3u : 1u;
 #pragma unroll
-		for (uint32_t t = 0; t < MULLS_TG_TRIPS; t++)
+		for (uint32_t t = 0; t < TRIPS; t++)
 		{
 			const float *q = reinterpret_cast<const float *>(base + (size_t)min(t * MULLS_TG_LANES + threadIdx.x, last) * stride);
 			px[t] = q[0], py[t] = q[1], pz[t] = q[2];
@@ -410,7 +428,7 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 	__builtin_amdgcn_sched_barrier(0); // every load is issued before the first one is consumed
 	uint32_t keepmask = 0;
 #pragma unroll
-	for (uint32_t t = 0; t < MULLS_TG_TRIPS; t++)
+	for (uint32_t t = 0; t < TRIPS; t++)
 	{
 		const uint32_t i = t * MULLS_TG_LANES + threadIdx.x;
 		__builtin_amdgcn_sched_barrier(0); // one trip at a time: interleaving the ten trips' arithmetic spills
@@ -420,15 +438,16 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 		if (lane == 0)
 			wcnt[t * MULLS_TG_WAVES + (uint32_t)wave] = (uint32_t)__popcll(bal);
 	}
-	if (threadIdx.x < 32u)
-		wcnt[MULLS_TG_TRIPS * MULLS_TG_WAVES + threadIdx.x] = 0u;
+	if (threadIdx.x < WC - TRIPS * MULLS_TG_WAVES)
+		wcnt[TRIPS * MULLS_TG_WAVES + threadIdx.x] = 0u;
 	__syncthreads();
 	TG_STOP(11u)
 	if (wave == 0)
 	{
-		// exclusive scan of the (trip, wave) counts, three per lane
-		const uint32_t c0 = wcnt[3 * lane], c1 = wcnt[3 * lane + 1], c2 = wcnt[3 * lane + 2];
-		const uint32_t sum = c0 + c1 + c2;
+		// exclusive scan of the (trip, wave) counts, WC_PER per lane
+		uint32_t c[WC_PER], sum = 0;
+		for (uint32_t k = 0; k < WC_PER; k++)
+			sum += c[k] = wcnt[WC_PER * lane + k];
 		uint32_t incl = sum;
 		for (int off = 1; off < 64; off <<= 1)
 		{
@@ -436,19 +455,20 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 			if (lane >= off)
 				incl += o;
 		}
-		const uint32_t before = incl - sum;
-		wcnt[3 * lane] = before;
-		wcnt[3 * lane + 1] = before + c0;
-		wcnt[3 * lane + 2] = before + c0 + c1;
+		uint32_t before = incl - sum;
+		for (uint32_t k = 0; k < WC_PER; k++)
+		{
+			wcnt[WC_PER * lane + k] = before;
+			before += c[k];
+		}
 	}
-	static_assert(MULLS_TG_TRIPS * MULLS_TG_WAVES + 1u <= 3u * 64u, "one wave scans the (trip, wave) counts, three per lane");
 	__syncthreads();
-	const uint32_t n = wcnt[MULLS_TG_TRIPS * MULLS_TG_WAVES]; // the prefix of the first padding entry = the number of survivors
+	const uint32_t n = wcnt[TRIPS * MULLS_TG_WAVES]; // the prefix of the first padding entry = the number of survivors
 	// rank of this lane's trip-t point in the cropped cloud (every lane of the wave calls it: ballot)
 	auto rank_of = [&](uint32_t t, bool keep) { return wcnt[t * MULLS_TG_WAVES + (uint32_t)wave] + (uint32_t)__popcll(__ballot(keep) & ((1ull << lane) - 1ull)); };
 	float bmin[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, bmax[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
 #pragma unroll
-	for (uint32_t t = 0; t < MULLS_TG_TRIPS; t++)
+	for (uint32_t t = 0; t < TRIPS; t++)
 	{
 		__builtin_amdgcn_sched_barrier(0);
 		const bool keep = (keepmask >> t) & 1u;
@@ -488,7 +508,7 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 				lo3[k] = fminf(lo3[k], box_red[w][k]), hi3[k] = fmaxf(hi3[k], box_red[w][3 + k]);
 		}
 		const GridDesc gd = make_grid(lo3, hi3, n, rp, d, cls);
-		grids[blockIdx.x] = gd;
+		grids[ci] = gd;
 		g_sh = gd;
 		d.tgt_n = n;
 	}
@@ -507,7 +527,7 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 			K[w] = 0u;
 		__syncthreads();
 #pragma unroll
-		for (uint32_t t = 0; t < MULLS_TG_TRIPS; t++)
+		for (uint32_t t = 0; t < TRIPS; t++)
 		{
 			__builtin_amdgcn_sched_barrier(0);
 			if ((keepmask >> t) & 1u)
@@ -549,7 +569,7 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 		__syncthreads();
 		TG_STOP(15u)
 #pragma unroll
-		for (uint32_t t = 0; t < MULLS_TG_TRIPS; t++)
+		for (uint32_t t = 0; t < TRIPS; t++)
 		{
 			__builtin_amdgcn_sched_barrier(0);
 			const bool keep = (keepmask >> t) & 1u;
@@ -564,6 +584,8 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 		}
 		return;
 	}
+	if (!SORT)
+		return; // (unreachable: see SORT above)
 	// many cells (small clouds only: the cell budget shrinks as the staged cloud grows): sort (cell id, rank) keys with a bitonic network in LDS
 	uint32_t npow = 64;
 	while (npow < n)
@@ -571,7 +593,7 @@ __global__ __launch_bounds__(MULLS_TG_LANES, 4) void k_tgt_grid(CloudDesc *__res
 	for (uint32_t i = n + threadIdx.x; i < npow; i += MULLS_TG_LANES)
 		K[i] = 0xffffffffu;
 #pragma unroll
-	for (uint32_t t = 0; t < MULLS_TG_TRIPS; t++)
+	for (uint32_t t = 0; t < TRIPS; t++)
 	{
 		const bool keep = (keepmask >> t) & 1u;
 		const uint32_t rank = rank_of(t, keep);
@@ -645,9 +667,35 @@ void launch_bm_build(hipStream_t st, const BatchDev &b, uint32_t nl, uint32_t nt
 		hipLaunchKernelGGL(k_bm_scatter, dim3((ntjobs + MULLS_BM_CH - 1) / MULLS_BM_CH), dim3(MULLS_BLOCK), 0, st, b.tjobs, ntjobs, b.descs, b.tpos, b.bm_rank, b.bm_cs, b.tsorted);
 }
 
-int launch_tgt_grid(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs)
+// trips of the size buckets (x MULLS_TG_LANES points); the last one is the kernel's full reach.  build_jobs sorts the LDS-tier class clouds into them.
+const uint32_t *tgt_grid_bucket_trips()
 {
-	if (npairs)
-		hipLaunchKernelGGL(k_tgt_grid, dim3(npairs * MULLS_NC), dim3(MULLS_TG_LANES), 0, st, b.descs, b.setup, b.bbox, b.stage, rp, b.grids, b.tmap, b.cell_start, b.tsorted);
+	static const uint32_t trips[MULLS_TG_BUCKETS] = {4u, 8u, 12u, MULLS_TG_TRIPS};
+	return trips;
+}
+static_assert(MULLS_TG_BUCKETS == 4, "launch_tgt_grid names one instantiation per bucket");
+
+// clouds / split: the bucket tables (device) and their bounds — bucket k is clouds[split[k] .. split[k + 1]).  clouds == nullptr, or a cell budget beyond what the
+// bucketed instantiations are built for: the former shape, one 19-trip workgroup per class cloud of the batch.
+int launch_tgt_grid(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs, const uint32_t *clouds, const uint32_t *split)
+{
+	if (!npairs)
+		return 0;
+	if (!clouds || rp.grid_maxcells > 32767u)
+	{
+		hipLaunchKernelGGL((k_tgt_grid<MULLS_TG_TRIPS, true>), dim3(npairs * MULLS_NC), dim3(MULLS_TG_LANES), 0, st, (const uint32_t *)nullptr, b.descs, b.setup, b.bbox, b.stage, rp,
+						   b.grids, b.tmap, b.cell_start, b.tsorted);
+		return 0;
+	}
+	const uint32_t lds = (((rp.grid_maxcells >> 1) + 1u + 3u) & ~3u) * 4u; // counters 0 .. grid_maxcells, two per word
+#define TG_LAUNCH(k, T)                                                                                                                                                              \
+	if (split[k + 1] > split[k])                                                                                                                                                     \
+		hipLaunchKernelGGL((k_tgt_grid<T, false>), dim3(split[k + 1] - split[k]), dim3(MULLS_TG_LANES), lds, st, clouds + split[k], b.descs, b.setup, b.bbox, b.stage, rp, b.grids, \
+						   b.tmap, b.cell_start, b.tsorted);
+	TG_LAUNCH(0, 4u)
+	TG_LAUNCH(1, 8u)
+	TG_LAUNCH(2, 12u)
+	TG_LAUNCH(3, MULLS_TG_TRIPS)
+#undef TG_LAUNCH
 	return 0;
 }

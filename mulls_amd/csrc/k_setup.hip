@@ -116,7 +116,9 @@ __global__ __launch_bounds__(MULLS_BLOCK) void k_clone_src(const Job *__restrict
 
 // Setup 2: order-preserving compaction of one cloud by the intersection box.  One workgroup per (pair, class, side);
 // side 0 = source (reads the SoA written by k_clone_src), side 1 = target (reads the staged AoS records).
-__global__ __launch_bounds__(MULLS_BLOCK) void k_crop(CloudDesc *__restrict__ descs, const PairSetup *__restrict__ setup,
+// wgs: the (pair, class, side) codes of the workgroups, (pair * MULLS_NC + class) * 2 + side each — the sides that have work here (build_jobs); null: every
+// side of the batch, code = workgroup.
+__global__ __launch_bounds__(MULLS_BLOCK) void k_crop(const uint32_t *__restrict__ wgs, CloudDesc *__restrict__ descs, const PairSetup *__restrict__ setup,
 													   const uint32_t *__restrict__ bbox, const float4 *__restrict__ stage,
 													   const float4 *__restrict__ tmp_pos, const float4 *__restrict__ tmp_nrm,
 													   float4 *__restrict__ spos, float4 *__restrict__ snrm, float4 *__restrict__ tpos,
@@ -126,9 +128,10 @@ __global__ __launch_bounds__(MULLS_BLOCK) void k_crop(CloudDesc *__restrict__ de
 	const int crop = rp.crop;
 	__shared__ uint32_t wave_cnt[4];
 	__shared__ float box_red[4][6];
-	const uint32_t pair = blockIdx.x / (MULLS_NC * 2);
-	const uint32_t cls = (blockIdx.x / 2) % MULLS_NC;
-	const uint32_t side = blockIdx.x & 1;
+	const uint32_t code = wgs ? wgs[blockIdx.x] : blockIdx.x;
+	const uint32_t pair = code / (MULLS_NC * 2);
+	const uint32_t cls = (code / 2) % MULLS_NC;
+	const uint32_t side = code & 1;
 	CloudDesc &d = descs[pair * MULLS_NC + cls];
 	const uint32_t n0 = side ? d.tgt_n0 : ((rp.undistort && cls != 5) ? d.sd_n0 : d.src_n0);
 	const uint32_t off = side ? d.tgt_off : d.src_off;
@@ -248,6 +251,181 @@ __global__ __launch_bounds__(MULLS_BLOCK) void k_crop(CloudDesc *__restrict__ de
 			d.valid_next = 0;
 			d.n_valid = 0;
 		}
+	}
+}
+
+// Setups 1 + 2 of a pair's source side in one workgroup: a down-sampled scan's six source clouds together hold a few thousand points, which fit the registers of
+// 512 lanes (MULLS_SRC_SETUP_CAP = 512 x 8 points).  The clouds are laid end to end over the workgroup's slots (slot = trip * 512 + lane); every lane loads its
+// staged records (all loads in flight together), applies the guess with k_clone_src's arithmetic, the workgroup reduces the ground / pillar / facade box in LDS and
+// stores it with plain stores (nobody else writes this pair's six words), derives the intersection box from it and compacts every class stably to its own
+// d.src_off — k_crop's source side without the round trip through tmp_pos / tmp_nrm (32 B out + 32 B in per point) and without two of the three launches.
+// Only for runs that do not undistort, and for the pairs the host lists (build_jobs): no source cloud cropped segment-wise, staged source total within the capacity.
+// Every other pair goes through k_clone_src + k_crop.  Same values at the same addresses as those two write.
+#define MULLS_SS_LANES 512u
+#define MULLS_SS_WAVES (MULLS_SS_LANES / 64u)
+#define MULLS_SS_TRIPS (MULLS_SRC_SETUP_CAP / MULLS_SS_LANES)
+static_assert(MULLS_SS_TRIPS * MULLS_SS_WAVES == 64u, "one wave scans the (trip, wave) counts, one per lane");
+__global__ __launch_bounds__(MULLS_SS_LANES, 4) void k_src_setup(const uint32_t *__restrict__ pairs, CloudDesc *__restrict__ descs, const PairSetup *__restrict__ setup,
+																	const float4 *__restrict__ stage, float4 *__restrict__ spos, float4 *__restrict__ snrm, uint8_t *__restrict__ flag,
+																	int32_t *__restrict__ match, float *__restrict__ wd, uint32_t *__restrict__ bbox, RunParams rp)
+{
+	__shared__ uint32_t first[MULLS_NC + 1]; // first slot of every class; [MULLS_NC] = the pair's staged source points
+	__shared__ uint32_t c_stage[MULLS_NC], c_fmt[MULLS_NC], c_off[MULLS_NC];
+	__shared__ uint32_t ucnt[MULLS_SS_TRIPS * MULLS_SS_WAVES]; // survivors per (trip, wave), then their exclusive prefix
+	__shared__ uint32_t box_red[MULLS_SS_WAVES][6];
+	__shared__ uint32_t box_keys[6];
+	__shared__ uint32_t cls_base[MULLS_NC + 1]; // survivors in front of every class
+	const uint32_t pair = pairs[blockIdx.x];
+	CloudDesc *pd = descs + (size_t)pair * MULLS_NC;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	if (threadIdx.x == 0)
+	{
+		uint32_t at = 0;
+		for (int c = 0; c < MULLS_NC; c++)
+		{
+			first[c] = at;
+			at += pd[c].src_n0;
+			c_stage[c] = pd[c].src_stage, c_fmt[c] = pd[c].stage_fmt & 3u, c_off[c] = pd[c].src_off;
+		}
+		first[MULLS_NC] = at;
+	}
+	__syncthreads();
+	uint32_t st_[MULLS_NC + 1];
+	for (int c = 0; c <= MULLS_NC; c++)
+		st_[c] = first[c];
+	const uint32_t total = st_[MULLS_NC];
+	const PairSetup &su = setup[pair];
+	const double *G = su.guess;
+	float4 a[MULLS_SS_TRIPS], b[MULLS_SS_TRIPS]; // a = x y z intensity, b = nx ny nz curvature
+	uint32_t clsmask = 0;						  // 3 bits per trip: the class of this lane's slot
+#pragma unroll
+	for (uint32_t t = 0; t < MULLS_SS_TRIPS; t++)
+	{
+		const uint32_t s = t * MULLS_SS_LANES + threadIdx.x;
+		uint32_t c = 0;
+		for (int k = 1; k < MULLS_NC; k++)
+			c += s >= st_[k] ? 1u : 0u; // (the start slots grow with the class: the last class that starts at or before s)
+		clsmask |= c << (3u * t);
+		a[t] = b[t] = make_float4(0, 0, 0, 0);
+		if (s < total)
+			load_staged(stage, c_stage[c], c_fmt[c], first[c + 1] - first[c], s - first[c], a[t], b[t]);
+	}
+	__builtin_amdgcn_sched_barrier(0); // every load is issued before the first one is consumed
+	uint32_t k6[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
+#pragma unroll
+	for (uint32_t t = 0; t < MULLS_SS_TRIPS; t++)
+	{
+		const uint32_t s = t * MULLS_SS_LANES + threadIdx.x, c = (clsmask >> (3u * t)) & 7u;
+		if (s < total)
+		{
+			// k_clone_src's expressions (double math, float store)
+			const double px = a[t].x, py = a[t].y, pz = a[t].z, nx = b[t].x, ny = b[t].y, nz = b[t].z;
+			const float x = (float)(G[0] * px + G[1] * py + G[2] * pz + G[3]);
+			const float y = (float)(G[4] * px + G[5] * py + G[6] * pz + G[7]);
+			const float z = (float)(G[8] * px + G[9] * py + G[10] * pz + G[11]);
+			const float onx = (float)(G[0] * nx + G[1] * ny + G[2] * nz);
+			const float ony = (float)(G[4] * nx + G[5] * ny + G[6] * nz);
+			const float onz = (float)(G[8] * nx + G[9] * ny + G[10] * nz);
+			a[t] = make_float4(x, y, z, a[t].w);
+			b[t] = make_float4(onx, ony, onz, b[t].w);
+			if (c <= 2u) // the bounding box of the transformed ground / pillar / facade source clouds (cregistration.hpp:2912-2915)
+			{
+				k6[0] = min(k6[0], f2ord(x)), k6[1] = min(k6[1], f2ord(y)), k6[2] = min(k6[2], f2ord(z));
+				k6[3] = max(k6[3], f2ord(x)), k6[4] = max(k6[4], f2ord(y)), k6[5] = max(k6[5], f2ord(z));
+			}
+		}
+	}
+	for (int off = 32; off > 0; off >>= 1)
+		for (int j = 0; j < 3; j++)
+		{
+			k6[j] = min(k6[j], (uint32_t)__shfl_down(k6[j], off));
+			k6[3 + j] = max(k6[3 + j], (uint32_t)__shfl_down(k6[3 + j], off));
+		}
+	if (lane == 0)
+		for (int j = 0; j < 6; j++)
+			box_red[wave][j] = k6[j];
+	__syncthreads();
+	if (threadIdx.x < 6)
+	{
+		uint32_t v = box_red[0][threadIdx.x];
+		for (uint32_t w = 1; w < MULLS_SS_WAVES; w++)
+			v = threadIdx.x < 3 ? min(v, box_red[w][threadIdx.x]) : max(v, box_red[w][threadIdx.x]);
+		box_keys[threadIdx.x] = v;
+		bbox[pair * 6 + threadIdx.x] = v; // (0xffffffff / 0 when the three clouds are empty: what the run's reset left there)
+	}
+	__syncthreads();
+	double lo[3], hi[3];
+	if (rp.crop)
+		crop_box_keys(box_keys, su, lo, hi);
+	uint32_t keepmask = 0;
+#pragma unroll
+	for (uint32_t t = 0; t < MULLS_SS_TRIPS; t++)
+	{
+		const uint32_t s = t * MULLS_SS_LANES + threadIdx.x;
+		const bool keep = s < total && (!rp.crop || crop_keep(a[t], lo, hi));
+		const unsigned long long bal = __ballot(keep);
+		keepmask |= keep ? (1u << t) : 0u;
+		if (lane == 0)
+			ucnt[t * MULLS_SS_WAVES + (uint32_t)wave] = (uint32_t)__popcll(bal);
+	}
+	__syncthreads();
+	if (wave == 0)
+	{
+		const uint32_t v = ucnt[lane];
+		uint32_t incl = v;
+		for (int off = 1; off < 64; off <<= 1)
+		{
+			const uint32_t o = __shfl_up(incl, off);
+			if (lane >= off)
+				incl += o;
+		}
+		ucnt[lane] = incl - v;
+		if (lane == 63)
+		{
+			// classes that start behind the last staged point (empty tails) and the end: every survivor lies in front of them
+			for (int c = 0; c <= MULLS_NC; c++)
+				if (st_[c] >= total)
+					cls_base[c] = incl;
+		}
+	}
+	__syncthreads();
+	uint32_t rank[MULLS_SS_TRIPS]; // survivors in front of this lane's slot, over the whole pair
+#pragma unroll
+	for (uint32_t t = 0; t < MULLS_SS_TRIPS; t++)
+	{
+		const uint32_t s = t * MULLS_SS_LANES + threadIdx.x;
+		const bool keep = (keepmask >> t) & 1u;
+		rank[t] = ucnt[t * MULLS_SS_WAVES + (uint32_t)wave] + (uint32_t)__popcll(__ballot(keep) & ((1ull << lane) - 1ull));
+		if (s < total)
+			for (int c = 0; c < MULLS_NC; c++)
+				if (s == st_[c])
+					cls_base[c] = rank[t]; // (an empty class shares its start slot with the next one: the same value)
+	}
+	__syncthreads();
+#pragma unroll
+	for (uint32_t t = 0; t < MULLS_SS_TRIPS; t++)
+		if ((keepmask >> t) & 1u)
+		{
+			const uint32_t c = (clsmask >> (3u * t)) & 7u;
+			const uint32_t dst = c_off[c] + rank[t] - cls_base[c];
+			float4 p = a[t], q = b[t];
+			identity_step(p, q); // (as k_crop)
+			spos[dst] = p;
+			snrm[dst] = q;
+			flag[dst] = MULLS_F_ALIVE;
+			match[dst] = -1;
+			wd[dst] = 0.0f;
+		}
+	if (threadIdx.x < MULLS_NC)
+	{
+		CloudDesc &d = pd[threadIdx.x];
+		const uint32_t n = cls_base[threadIdx.x + 1] - cls_base[threadIdx.x];
+		d.src_n = n;
+		d.alive_cur = n;
+		d.alive_next = 0;
+		d.n_matched = 0;
+		d.valid_next = 0;
+		d.n_valid = 0;
 	}
 }
 
@@ -608,12 +786,21 @@ void launch_clone_src(hipStream_t st, const BatchDev &b, const RunParams &rp, ui
 		hipLaunchKernelGGL(k_clone_src, dim3(njobs), dim3(MULLS_BLOCK), 0, st, b.setup_jobs, b.descs, b.setup, b.stage, b.tmp_pos, b.tmp_nrm, b.bbox, rp);
 }
 
-void launch_crop(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs, uint32_t nbig_segs, uint32_t nbig_clouds)
+void launch_src_setup(hipStream_t st, const BatchDev &b, const RunParams &rp, const uint32_t *pairs, uint32_t npairs)
+{
+	if (npairs)
+		hipLaunchKernelGGL(k_src_setup, dim3(npairs), dim3(MULLS_SS_LANES), 0, st, pairs, b.descs, b.setup, b.stage, b.spos, b.snrm, b.flag, b.match, b.wd, b.bbox, rp);
+}
+
+void launch_crop(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs, uint32_t nbig_segs, uint32_t nbig_clouds, const uint32_t *wgs, uint32_t nwgs)
 {
 	if (!npairs)
 		return;
-	hipLaunchKernelGGL(k_crop, dim3(npairs * MULLS_NC * 2), dim3(MULLS_BLOCK), 0, st, b.descs, b.setup, b.bbox, b.stage, b.tmp_pos, b.tmp_nrm, b.spos, b.snrm, b.tpos,
-					   b.tnrm, b.flag, b.match, b.wd, rp, b.grids, b.big_box);
+	if (!wgs)
+		nwgs = npairs * MULLS_NC * 2;
+	if (nwgs)
+		hipLaunchKernelGGL(k_crop, dim3(nwgs), dim3(MULLS_BLOCK), 0, st, wgs, b.descs, b.setup, b.bbox, b.stage, b.tmp_pos, b.tmp_nrm, b.spos, b.snrm, b.tpos, b.tnrm, b.flag,
+						   b.match, b.wd, rp, b.grids, b.big_box);
 	if (nbig_clouds)
 	{
 		hipLaunchKernelGGL(k_crop_big_count, dim3(nbig_segs), dim3(MULLS_BLOCK), 0, st, b.big_segs, b.descs, b.setup, b.bbox, b.stage, b.tmp_pos, rp, b.seg_cnt, b.big_box + (size_t)nbig_clouds * 6u);

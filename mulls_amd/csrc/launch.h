@@ -62,6 +62,7 @@ struct BatchDev
 	PairOut *outs_pin = nullptr;	 // device address of the pinned host array outs_h (packed records, k_pull_outs)
 	uint32_t *bbox = nullptr;
 	Job *setup_jobs = nullptr;
+	uint32_t *setup_tab = nullptr; // the setup's index tables, one array (mulls_batch::setup_tab_h): k_tgt_grid's buckets, k_crop's workgroups, k_src_setup's pairs
 	Job *big_segs = nullptr, *big_clouds = nullptr;
 	uint32_t *seg_cnt = nullptr, *big_box = nullptr;
 	Job *jobs = nullptr;
@@ -89,14 +90,19 @@ struct BatchDev
 // clone + initial guess of the `njobs` setup jobs (b.setup_jobs)
 void launch_clone_src(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t njobs);
 // nbig_segs / nbig_clouds: entries of b.big_segs / b.big_clouds (class clouds cropped segment-wise)
-void launch_crop(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs, uint32_t nbig_segs, uint32_t nbig_clouds);
+// wgs / nwgs: the (pair, class, side) workgroups k_crop starts (device table; null: every side of the `npairs` pairs)
+void launch_crop(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs, uint32_t nbig_segs, uint32_t nbig_clouds, const uint32_t *wgs = nullptr, uint32_t nwgs = 0);
+// clone + box + crop of the source side of the `npairs` pairs listed in `pairs` (device), one workgroup each (k_src_setup: runs that do not undistort)
+void launch_src_setup(hipStream_t st, const BatchDev &b, const RunParams &rp, const uint32_t *pairs, uint32_t npairs);
 // n byte ranges in one launch per MULLS_COPY_SEGS of them (device_types.h: CopySeg)
 void launch_copy_segs(hipStream_t st, const CopySeg *segs, uint32_t n);
 // CFilter::apply_motion_compensation on `n` 48-byte records in device memory (q: w x y z of Tran's rotation, t: its translation)
 void launch_motion_comp(hipStream_t st, float4 *recs, uint32_t n, const double q[4], const double t[3], float thre);
 void launch_thin(hipStream_t st, const BatchDev &b, uint32_t npairs, const uint8_t *src_keep, const uint8_t *tgt_keep);
 // LDS tier with rp.tgt_map: crop + grid build of every target class cloud (<= MULLS_LDS_MAXPTS points) in one pass, no working copy (k_grid.hip)
-int launch_tgt_grid(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs);
+// clouds / split: size-bucket tables of the LDS-tier class clouds (device) and their MULLS_TG_BUCKETS + 1 bounds; null: one full-reach workgroup per class cloud
+int launch_tgt_grid(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs, const uint32_t *clouds = nullptr, const uint32_t *split = nullptr);
+const uint32_t *tgt_grid_bucket_trips(); // [MULLS_TG_BUCKETS]: x 512 points = the largest cloud of each bucket
 // LDS tier without the fused setup (k_crop wrote the cropped copies)
 void launch_grid_build_sort(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t npairs);
 // bitmap grids of the `nl` class clouds b.lclouds[] (pair * MULLS_NC + class each); ntjobs: their 256-point chunks (b.tjobs)

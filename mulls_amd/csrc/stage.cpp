@@ -172,6 +172,8 @@ extern "C"
 		ctx->opt[MULLS_OPT_LDS_DEDUP] = dedup_opt;
 		if (rc != MULLS_OK)
 			return rc;
+		if (ctx->opt[MULLS_OPT_DEBUG_STOP] == 30.0) // (the one bring-up value that is the host's: the setup's former shape)
+			rp->debug_stop = 30u;
 		queue_clone_crop(st, B, *rp);
 		queue_target_grids(st, B, *rp, tier, false);
 		return MULLS_OK;

@@ -48,6 +48,8 @@ extern "C"
 		rc = prepare_run(ctx, B, &Pj, rp, &lds_cap, &tier);
 		if (rc != MULLS_OK)
 			return rc;
+		if (ctx->opt[MULLS_OPT_DEBUG_STOP] == 30.0) // (the one bring-up value that is the host's: the setup's former shape)
+			rp.debug_stop = 30u;
 		queue_clone_crop(st, B, rp);
 		if (P->keep_less_source_points)
 		{
