@@ -341,7 +341,11 @@ int mulls_icp_4dof_global(mulls_ctx *ctx, const mulls_pair *pair, float heading_
  * MapManager::update_local_map (src/map_manager.cpp:18-140) with the six undown class clouds of `local_map` kept in HBM
  * between frames: the scan-to-map target is never re-uploaded (mulls_map_cloud() yields device clouds that mulls_pair.tgt
  * accepts), and map-based dynamic-object removal (map_manager.cpp:149-256) runs as an exact nearest-neighbour pass on the
- * device instead of querying the kd-trees mm_lls_icp left on block1. */
+ * device instead of querying the kd-trees mm_lls_icp left on block1.
+ * Held to the oracle bit for bit on every record and report figure: tests/test_map.py and tests/test_gpu_map.py (update sequences),
+ * tests/test_map_edges.py and tests/test_gpu_map_edges.py (inputs of tests/map_edges.py: clouds of many compaction segments, trees of
+ * one to four search chunks with queries exactly on the removal's thresholds, neighbourhoods with ties at rank K, empty and non-finite
+ * clouds, and these entry points by raw calls: packed strides, short downloads, NULL arguments, device-resident sources). */
 typedef struct mulls_map mulls_map;
 
 typedef struct mulls_map_params

@@ -2546,7 +2546,10 @@ int classify_nground_impl(Cloud &cloud_in, const mulls_classify_params &P, Cloud
 }
 
 // MapManager::update_cloud_vectors (src/map_manager.cpp:258-292), the PCA refresh of the local map's linear features
-// (recalculate_feature_on, :98-118)
+// (recalculate_feature_on, :98-118).  A limit of this restatement, not of the operation: the radius filter before it lets any finite height
+// through, and the radius index below (pcl_restated.h) sizes its grid by the cloud's extent over the search radius -- a pillar or beam at
+// z = 1e20 or 3e38 makes that count overflow and the index ask for more memory than there is (std::bad_alloc).  Keep such heights out of
+// the linear classes when the refresh is on; everywhere else in update_local_map they are fine.
 void update_cloud_vectors(Cloud &pts, float pca_radius, int pca_k, int k_min, float sin_low, float sin_high, float min_linearity)
 {
 	if (pts.size() == 0)
