@@ -911,6 +911,108 @@ inline bool non_max_suppress(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out
 	return true;
 }
 
+// The raw-scan steps of CFilter<PointT> in front of extract_semantic_pts and of the map export (test/mulls_slam.cpp:359-362, :404-412, :966-974), verbatim
+// signatures and defaults, each one device call on the cloud's records in place (mulls_scan_prepare with one step switched on; a caller that owns the
+// sequence fills mulls_scan_prep_params itself and runs all of them in one call).  include/mulls_hip.h has the definition.  The binding is one early
+// return at the top of each member function.
+template <typename PointT>
+inline uint32_t scan_prepare(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out, const mulls_scan_prep_params &P)
+{
+	static_assert(sizeof(PointT) == MULLS_POINT_BYTES, "the scan preparation expects 48-byte pcl::PointXYZINormal records");
+	mulls_ctx *ctx = thread_context();
+	uint32_t n_out = 0;
+	const int rc = mulls_scan_prepare(ctx, cloud_in_out->points.data(), static_cast<uint32_t>(cloud_in_out->points.size()), MULLS_POINT_BYTES, &P, &n_out, nullptr);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_scan_prepare failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	cloud_in_out->points.resize(n_out);
+	return n_out;
+}
+// cfilter.hpp:250-291
+template <typename PointT>
+inline bool vertical_intrinsic_calibration(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out, double var_vertical_ang_d = 0.0, bool inverse_z = false)
+{
+	if (var_vertical_ang_d == 0)
+		return false;
+	if (var_vertical_ang_d >= 180.0)
+		inverse_z = true;
+	mulls_scan_prep_params P;
+	mulls_scan_prep_default_params(&P);
+	P.calib_on = 1;
+	P.vertical_ang_correction_deg = inverse_z ? 180.0 : var_vertical_ang_d; // (180: the library's spelling of "negate z")
+	scan_prepare<PointT>(cloud_in_out, P);
+	return !inverse_z;
+}
+// cfilter.hpp:412-467
+template <typename PointT>
+inline bool get_pts_timestamp_ratio_in_frame(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out, bool timestamp_availiable = true,
+											 double scan_begin_ang_anticlock_x_positive_deg = 180.0, float scan_duration_ms = 100)
+{
+	mulls_scan_prep_params P;
+	mulls_scan_prep_default_params(&P);
+	P.timestamp_mode = timestamp_availiable ? 1 : 2;
+	P.scan_begin_ang_deg = scan_begin_ang_anticlock_x_positive_deg;
+	P.scan_duration_ms = scan_duration_ms;
+	scan_prepare<PointT>(cloud_in_out, P);
+	return true;
+}
+// cfilter.hpp:730-747 and :713-728
+template <typename PointT>
+inline bool random_downsample(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out, int downsample_ratio)
+{
+	if (downsample_ratio <= 1)
+		return 0;
+	mulls_scan_prep_params P;
+	mulls_scan_prep_default_params(&P);
+	P.downsample_ratio = downsample_ratio;
+	scan_prepare<PointT>(cloud_in_out, P);
+	return 1;
+}
+template <typename PointT>
+inline bool random_downsample(const typename pcl::PointCloud<PointT>::Ptr &cloud_in, typename pcl::PointCloud<PointT>::Ptr &cloud_out, int downsample_ratio)
+{
+	if (downsample_ratio <= 1)
+		return 0;
+	cloud_out->points = cloud_in->points; // (:718-723 clears cloud_out and pushes the kept points)
+	return random_downsample<PointT>(cloud_out, downsample_ratio);
+}
+// cfilter.hpp:806-831
+template <typename PointT>
+inline bool dist_filter(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out, double xy_dist_min, double xy_dist_max)
+{
+	mulls_scan_prep_params P;
+	mulls_scan_prep_default_params(&P);
+	P.dist_filter_on = 1;
+	P.min_dist = xy_dist_min;
+	P.max_dist = xy_dist_max;
+	scan_prepare<PointT>(cloud_in_out, P);
+	return 1;
+}
+// One frame of the merged map mulls_slam exports (test/mulls_slam.cpp:963-990) into a mapper (mulls_mapper_create): pc_raw as read from the file, its
+// pose_optimized, and the pose of the frame before it — NULL for the first frame, which upstream does not compensate (:977 `i > 0`).  prep carries the
+// flags of :966-974; compensated when prep.timestamp_mode > 0 (FLAGS_motion_compensation_method > 0) and there is a frame before.
+template <typename PointT>
+inline uint32_t merged_map_add(mulls_mapper *mapper, const typename pcl::PointCloud<PointT>::Ptr &pc_raw, const Eigen::Matrix4d &pose_optimized,
+							   const Eigen::Matrix4d *pose_of_frame_before, const mulls_scan_prep_params &prep)
+{
+	static_assert(sizeof(PointT) == MULLS_POINT_BYTES, "the merged map expects 48-byte pcl::PointXYZINormal records");
+	mulls_ctx *ctx = thread_context();
+	mulls_mapper_frame F;
+	std::memset(&F, 0, sizeof(F));
+	F.scan = borrow(pc_raw);
+	std::memcpy(F.pose, pose_optimized.data(), sizeof(F.pose));
+	if (prep.timestamp_mode > 0 && pose_of_frame_before)
+	{
+		const Eigen::Matrix4d adjacent_tran = pose_optimized.inverse() * *pose_of_frame_before; // :979
+		std::memcpy(F.adjacent_tran, adjacent_tran.data(), sizeof(F.adjacent_tran));
+		F.compensate = 1;
+	}
+	uint32_t n_out = 0;
+	const int rc = mulls_mapper_add(ctx, mapper, &F, 1, &prep, &n_out, nullptr);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_mapper_add failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	return n_out;
+}
+
 // CFilter<PointT>::extract_semantic_pts (include/common/cfilter.hpp:2295-2413), verbatim signature: the whole chain in one device call
 // (mulls_extract_features).  The binding is one early return at the top of the member function:
 //     #ifdef MULLS_USE_HIP

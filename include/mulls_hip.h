@@ -942,6 +942,109 @@ void mulls_nms_default_params(mulls_nms_params *p); /* radius 0.25, path 0 */
 int mulls_non_max_suppress(mulls_ctx *ctx, const mulls_cloud *cloud, const mulls_nms_params *params, void *out, uint32_t cap, uint32_t *n_out, int32_t *kept_idx,
 						   uint32_t idx_cap, int32_t *order, mulls_nms_report *report);
 
+/* ---- scan preparation: the raw-scan steps of CFilter in front of extract_semantic_pts and of the map export (include/common/cfilter.hpp) ----
+ * What test/mulls_slam.cpp runs on pc_raw before the feature extraction (:359-362 and :404-412: dist_filter, vertical_intrinsic_calibration,
+ * get_pts_timestamp_ratio_in_frame) and per frame of the merged map (:966-974: calibration, dist_filter, random_downsample, time ratio), on the device and
+ * in place.  Lines marked [UP] are upstream's, [LIB] this library's.  tests/scanprep_restated.py restates all of it with Python's math functions per
+ * element; DESIGN.md section 7.5 has the same list with its reasons.  PCL is not available where this library is built and tested: nothing below (the
+ * mapper's pcl::transformPointCloud included) was compared with it.
+ *   order        [UP] calib_first = 0: dist filter, calibration (the frame loop, :404-407); 1: calibration, dist filter (the export, :966-969).  Then
+ *                random_downsample, then the time ratio, in both.  Each step sees the cloud as the steps before it left it.
+ *   calibration  [UP :250-291] angle == 0 (or calib_on = 0): nothing.  angle >= 180.0: every z is negated, nothing else.  Otherwise per point
+ *                dist = (double)sqrtf((x x + y y) + z z), products, sum and root in float; v = asin((double)z / dist); vc = v + angle / 180.0 * M_PI;
+ *                hs = cos(vc) / cos(v); x = (float)((double)x hs), y likewise, z = (float)(dist sin(vc)).  A point at the origin becomes NaN: the
+ *                arithmetic is followed, not repaired.
+ *                [LIB] asin, cos and sin are detmath.h's asin_cr, cos_cr, sin_cr (double-double evaluation rounded to double: the correctly rounded
+ *                value, the same bits on the host and on the device) where upstream calls the C library; no device math library is involved.
+ *   dist filter  [UP :806-831] a point stays iff d2 < max max && d2 > min min with d2 = (double)(x x + y y), products and sum in float, the limits'
+ *                squares in double.  (The lines mulls_extract_features runs under apply_dist_filter.)
+ *   thinning     [UP :730-747] downsample_ratio > 1: the points whose index i in the cloud as it stands then has i % ratio == 0 stay.
+ *   time ratio   [UP :424-441] mode 1: last / first = the max_ / min_ folds (utility.hpp:31-32, seeded with -DBL_MAX / DBL_MAX) of (double)curvature over
+ *                the cloud as it stands then (after thinning); last - first < scan_duration_ms * 0.75 replaces the duration by (float)(last - first);
+ *                curvature = (float)min_(1.0, max_(0.0, (last - curvature) / duration)).  Equal stamps give 0 / 0: the NaN is stored.
+ *                [LIB] a NaN time stamp among the points that stay: MULLS_E_INVALID, the cloud untouched (upstream's folds then depend on the order).
+ *                [UP :443-466] mode 2: ang = atan2(y, x), + 2 pi if negative, + begin angle / 180.0 * M_PI, - 2 pi if >= 2 pi;
+ *                curvature = (float)((2 pi - ang) / (2 pi)), on the coordinates as they stand then.
+ *                [LIB] atan2 is detmath.h's atan2_cr on the coordinates widened to double.  (Upstream writes std::atan2 on two floats, which C++ resolves
+ *                to the float overload; the double evaluation is this library's definition and differs from a float atan2 by that function's rounding.)
+ *   refused      [LIB] a stride other than 48, min_dist / max_dist / the angles / scan_duration_ms not finite, timestamp_mode outside 0..2:
+ *                MULLS_E_INVALID.  More than 2^24 points: MULLS_E_UNSUPPORTED.  n == 0: MULLS_OK.
+ * The work runs in chunks of MULLS_SCAN_CHUNK points, one workgroup each; nothing in the result depends on the chunk size or on which workgroup runs first. */
+#define MULLS_SCAN_CHUNK 256u
+#define MULLS_SCAN_MAX_POINTS (1u << 24)
+typedef struct mulls_scan_prep_params
+{
+	uint8_t calib_on, dist_filter_on;	/* [0, 0] */
+	uint8_t calib_first;				/* 0: dist filter -> calibration (frame loop, :404-407); 1: calibration -> dist filter (export, :966-969) */
+	uint8_t reserved_;
+	int32_t downsample_ratio;			/* [1] random_downsample(ratio), <= 1: off; always after both steps above */
+	int32_t timestamp_mode;				/* [0] 0 off, 1 from time stamps, 2 from azimuth; always last */
+	float scan_duration_ms;				/* [100] */
+	double vertical_ang_correction_deg; /* [0.0] */
+	double min_dist, max_dist;			/* [1.0, 120.0] */
+	double scan_begin_ang_deg;			/* [180.0]; mulls_slam passes 90.0 */
+} mulls_scan_prep_params;
+
+typedef struct mulls_scan_prep_report
+{
+	uint32_t n_in, n_after_dist, n_out;
+	uint32_t reserved;
+	double first_timestamp, last_timestamp; /* mode 1; DBL_MAX / -DBL_MAX (the folds' seeds) when nothing stays */
+	float scan_duration_used;				/* mode 1: what the ratios were divided by */
+	float ms_total;							/* wall time of the call */
+} mulls_scan_prep_report;
+
+void mulls_scan_prep_default_params(mulls_scan_prep_params *p);
+/* returns MULLS_OK or MULLS_E_* (the list above).  pts: n 48-byte records in host memory (one upload, one download of the records that stay) or in device
+ * memory (a cloud of the library's or any device allocation of the caller's: in place, nothing crosses PCIe), told apart as mulls_motion_compensate
+ * does.  The records that stay are left packed at the front, in input order, every field but x, y, z and curvature as it was; the records behind
+ * *n_out keep what they held.  report may be NULL. */
+int mulls_scan_prepare(mulls_ctx *ctx, void *pts, uint32_t n, uint32_t stride, const mulls_scan_prep_params *params, uint32_t *n_out,
+					   mulls_scan_prep_report *report);
+
+/* ---- the merged map mulls_slam exports (test/mulls_slam.cpp:959-1015), kept in device memory ----
+ * Per frame, in this order: the scan preparation above with calib_first taken as 1 (:966-974); when compensate is set,
+ * apply_motion_compensation(pc_raw, adjacent_tran) with threshold 0 (:977-981; mulls_motion_compensate's arithmetic, theta = acos(|q.w|) by the host's
+ * C library once per frame); pcl::transformPointCloud by pose (:982: positions in double, stored as float, every other field copied); appended in frame
+ * order (:990).  mulls_mapper_cloud hands the result to mulls_sor_filter (:1009).  Many frames per call run in lock step: one launch per pass for all of
+ * them.  The viewer's thinning (:991), write_map_each_frame and generate_2d_map are not part of this; the ground-truth map (:996-1005) is a second
+ * mapper fed pose_gt.
+ *   capacity [LIB] frames are appended while they fit.  If frame k does not fit, frames 0 .. k-1 of the call stay appended, frames k onward are not, and
+ *            the call returns MULLS_E_UNSUPPORTED with report.frames_added = k and report.n_needed = the size the map would have had with every frame.
+ *   refused  [LIB] what mulls_scan_prepare refuses, for any frame: MULLS_E_INVALID and nothing is appended.  A mapper of another context: MULLS_E_INVALID.
+ * A mapper belongs to its context: mulls_destroy(ctx) also destroys the mappers still alive. */
+typedef struct mulls_mapper mulls_mapper;
+typedef struct mulls_mapper_frame
+{
+	mulls_cloud scan;		 /* host or device, 48-byte records; never modified */
+	double pose[16];		 /* pose_optimized, column-major */
+	double adjacent_tran[16]; /* pose_i^-1 * pose_{i-1} (:979); read only when compensate is set */
+	int32_t compensate;		 /* 1: apply_motion_compensation(pc_raw, adjacent_tran), threshold 0 (:977-981) */
+	int32_t reserved;
+} mulls_mapper_frame;
+
+typedef struct mulls_mapper_report
+{
+	uint32_t frames_added; /* frames of this call that were appended */
+	uint32_t n_before;	   /* the map's size before the call */
+	uint32_t n_after;	   /* ... and after it */
+	uint32_t reserved;
+	uint64_t n_needed;	   /* the size the map has (or would have had) with every frame of the call appended */
+	float ms_total;		   /* wall time of the call */
+	uint32_t reserved2;
+} mulls_mapper_report;
+
+int mulls_mapper_create(mulls_ctx *ctx, uint32_t capacity_points /* <= 2^24, what mulls_sor_filter takes */, mulls_mapper **out);
+void mulls_mapper_destroy(mulls_ctx *ctx, mulls_mapper *mapper);
+/* frame_n_out: NULL, or n_frames counts: what each frame contributed (frames that were not appended: what they would have).  report may be NULL. */
+int mulls_mapper_add(mulls_ctx *ctx, mulls_mapper *mapper, const mulls_mapper_frame *frames, uint32_t n_frames, const mulls_scan_prep_params *prep,
+					 uint32_t *frame_n_out, mulls_mapper_report *report);
+/* the map as a device-resident cloud (stride 48), valid until the next add / clear / destroy: for mulls_sor_filter, mulls_non_max_suppress, ... */
+int mulls_mapper_cloud(mulls_ctx *ctx, const mulls_mapper *mapper, mulls_cloud *out);
+/* records first .. of the map to host memory, at most cap of them; *n: the map's size minus first (pts NULL with cap 0: the size query) */
+int mulls_mapper_download(mulls_ctx *ctx, const mulls_mapper *mapper, uint32_t first, void *pts, uint32_t cap, uint32_t *n);
+int mulls_mapper_clear(mulls_ctx *ctx, mulls_mapper *mapper);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

@@ -425,6 +425,48 @@ def nms_params(non_max_radius=0.25, path=0):
     return p
 
 
+class ScanPrepParams(C.Structure):
+    """mulls_scan_prep_params: the raw-scan steps of CFilter in front of the feature extraction and of the map export"""
+
+    _fields_ = [("calib_on", C.c_uint8), ("dist_filter_on", C.c_uint8), ("calib_first", C.c_uint8), ("reserved_", C.c_uint8), ("downsample_ratio", C.c_int32),
+                ("timestamp_mode", C.c_int32), ("scan_duration_ms", C.c_float), ("vertical_ang_correction_deg", C.c_double), ("min_dist", C.c_double),
+                ("max_dist", C.c_double), ("scan_begin_ang_deg", C.c_double)]
+
+
+class ScanPrepReport(C.Structure):
+    """mulls_scan_prep_report"""
+
+    _fields_ = [("n_in", C.c_uint32), ("n_after_dist", C.c_uint32), ("n_out", C.c_uint32), ("reserved", C.c_uint32), ("first_timestamp", C.c_double),
+                ("last_timestamp", C.c_double), ("scan_duration_used", C.c_float), ("ms_total", C.c_float)]
+
+
+class MapperFrame(C.Structure):
+    """mulls_mapper_frame: one frame of the merged map (test/mulls_slam.cpp:963-990)"""
+
+    _fields_ = [("scan", Cloud), ("pose", C.c_double * 16), ("adjacent_tran", C.c_double * 16), ("compensate", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapperReport(C.Structure):
+    """mulls_mapper_report"""
+
+    _fields_ = [("frames_added", C.c_uint32), ("n_before", C.c_uint32), ("n_after", C.c_uint32), ("reserved", C.c_uint32), ("n_needed", C.c_uint64),
+                ("ms_total", C.c_float), ("reserved2", C.c_uint32)]
+
+
+SCAN_CHUNK = 256  # MULLS_SCAN_CHUNK
+SCAN_MAX_POINTS = 1 << 24  # MULLS_SCAN_MAX_POINTS
+
+
+def scan_prep_params(calib_on=0, dist_filter_on=0, calib_first=0, downsample_ratio=1, timestamp_mode=0, scan_duration_ms=100.0, vertical_ang_correction_deg=0.0,
+                     min_dist=1.0, max_dist=120.0, scan_begin_ang_deg=180.0):
+    """upstream's defaults (cfilter.hpp:250, :414; test/mulls_slam.cpp:52-53)"""
+    p = ScanPrepParams()
+    p.calib_on, p.dist_filter_on, p.calib_first, p.reserved_ = int(calib_on), int(dist_filter_on), int(calib_first), 0
+    p.downsample_ratio, p.timestamp_mode, p.scan_duration_ms = int(downsample_ratio), int(timestamp_mode), float(scan_duration_ms)
+    p.vertical_ang_correction_deg, p.min_dist, p.max_dist, p.scan_begin_ang_deg = float(vertical_ang_correction_deg), float(min_dist), float(max_dist), float(scan_begin_ang_deg)
+    return p
+
+
 def records(a):
     """Any point array (POINT_DTYPE records or raw (n, 48) bytes) as contiguous raw (n, 48) uint8 records, every byte kept."""
     a = np.asarray(a)

@@ -1,4 +1,4 @@
-// detmath.h — the three transcendental functions of the per-iteration algebra (sin, cos, atan2), written out so that the
+// detmath.h — the transcendental functions of the per-iteration algebra (sin, cos, atan2) and of the scan preparation (asin), written out so that the
 // host driver and the device step of the ICP loop compute THE SAME BITS: plain IEEE-754 double operations in a fixed order
 // (the library is built -ffp-contract=off; the only fused operation is the explicit fma of the exact product), no libm.
 //
@@ -247,6 +247,35 @@ MULLS_HD inline double trig(double x, int which)
 MULLS_HD inline double sin_cr(double x) { return trig(x, 0); }
 MULLS_HD inline double cos_cr(double x) { return trig(x, 1); }
 
+// atan z for a double-double z in [0, 1]: halve the angle until tan is small, the series, double back
+MULLS_HD inline dd atan_dd(dd z)
+{
+	// halve the angle until tan is small: atan z = 2 atan(z / (1 + sqrt(1 + z^2)))
+	int m = 0;
+	while (z.hi > 0.1 && m < 4)
+	{
+		z = div(z, add(sqrt_dd(add(mul(z, z), 1.0)), 1.0));
+		m++;
+	}
+	dd a;
+	if (z.hi < 1e-150)
+		a = z; // atan z = z to every bit we keep (and z^2 would underflow)
+	else
+	{
+		int e;
+		(void)std::frexp(z.hi, &e);
+		const int n = e <= -20 ? 3 : (e <= -10 ? 6 : (e <= -5 ? 12 : 20));
+		const dd z2 = mul(z, z);
+		dd p = inv_odd(n);
+		for (int k = n - 1; k >= 1; k--)
+			p = add(mul(p, z2), inv_odd(k));
+		a = add(mul(mul(p, z2), z), z); // z - z^3/3 + ...
+	}
+	for (int i = 0; i < m; i++)
+		a = dd{2.0 * a.hi, 2.0 * a.lo};
+	return a;
+}
+
 // atan2(y, x) with the IEEE special cases of the C library function
 MULLS_HD inline double atan2_cr(double y, double x)
 {
@@ -292,30 +321,7 @@ MULLS_HD inline double atan2_cr(double y, double x)
 		}
 #endif
 		const bool swap = ay > ax;
-		dd z = div(dd{swap ? ax : ay, 0.0}, dd{swap ? ay : ax, 0.0}); // in [0, 1]
-		// halve the angle until tan is small: atan z = 2 atan(z / (1 + sqrt(1 + z^2)))
-		int m = 0;
-		while (z.hi > 0.1 && m < 4)
-		{
-			z = div(z, add(sqrt_dd(add(mul(z, z), 1.0)), 1.0));
-			m++;
-		}
-		dd a;
-		if (z.hi < 1e-150)
-			a = z; // atan z = z to every bit we keep (and z^2 would underflow)
-		else
-		{
-			int e;
-			(void)std::frexp(z.hi, &e);
-			const int n = e <= -20 ? 3 : (e <= -10 ? 6 : (e <= -5 ? 12 : 20));
-			const dd z2 = mul(z, z);
-			dd p = inv_odd(n);
-			for (int k = n - 1; k >= 1; k--)
-				p = add(mul(p, z2), inv_odd(k));
-			a = add(mul(mul(p, z2), z), z); // z - z^3/3 + ...
-		}
-		for (int i = 0; i < m; i++)
-			a = dd{2.0 * a.hi, 2.0 * a.lo};
+		dd a = atan_dd(div(dd{swap ? ax : ay, 0.0}, dd{swap ? ay : ax, 0.0})); // of a quotient in [0, 1]
 		const dd pio2 = {0x1.921fb54442d18p+0, 0x1.1a62633145c07p-54}, pi = {0x1.921fb54442d18p+1, 0x1.1a62633145c07p-53};
 		if (swap)
 			a = add(pio2, neg(a));
@@ -324,6 +330,32 @@ MULLS_HD inline double atan2_cr(double y, double x)
 		res = a.hi + a.lo;
 	}
 	return std::signbit(y) ? -res : res;
+}
+// asin(u) with the special cases of the C library function (NaN for |u| > 1 and for NaN, +-pi/2 at +-1, the sign of zero kept): the angle of the point
+// (sqrt((1 - u)(1 + u)), u) on the unit circle, with 1 - u and 1 + u exact and everything after them in double-double (vertical_intrinsic_calibration,
+// cfilter.hpp:278, calls glibc's asin)
+MULLS_HD inline double asin_cr(double u)
+{
+	const double au = std::fabs(u);
+	if (!(au <= 1.0))
+		return (u - u) / (u - u); // NaN
+	if (au < 0x1p-28)
+		return u; // u + u^3 / 6 + ... rounds to u
+	double res;
+	if (au == 1.0)
+		res = 0x1.921fb54442d18p+0;
+	else
+	{
+		const dd c = sqrt_dd(mul(two_sum(1.0, -au), two_sum(1.0, au))); // cos of the angle, > 0
+		const dd s = {au, 0.0};
+		dd a;
+		if (au <= c.hi)
+			a = atan_dd(div(s, c));
+		else
+			a = add(dd{0x1.921fb54442d18p+0, 0x1.1a62633145c07p-54}, neg(atan_dd(div(c, s))));
+		res = a.hi + a.lo;
+	}
+	return std::signbit(u) ? -res : res;
 }
 } // namespace det
 } // namespace mulls

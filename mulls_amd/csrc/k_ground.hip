@@ -28,6 +28,7 @@
 #include "device_util.h"
 #include "ground_launch.h"
 #include "pca_device.h"
+#include "scan_math.h"
 
 #define MULLS_GF_BLOCK 256
 #define MULLS_GF_SEG 1024u // points per segment (one wave walks a segment in 16 steps of 64)
@@ -970,7 +971,7 @@ __global__ __launch_bounds__(256) void k_raw_mask(const float4 *__restrict__ pts
 	const float dis_square = p.x * p.x + p.y * p.y;
 	bool keep = true;
 	if (a.dist_on)
-		keep = (double)dis_square < a.dist_max_sq && (double)dis_square > a.dist_min_sq;
+		keep = mulls::scan::dist_keep(p.x, p.y, a.dist_min_sq, a.dist_max_sq); // (the lines mulls_scan_prepare runs)
 	if (a.scanner_on)
 	{
 		bool k2 = false;

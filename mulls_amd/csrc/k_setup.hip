@@ -3,6 +3,7 @@
 #include "device_util.h"
 #include "crop_grid.h"
 #include "detmath.h"
+#include "scan_math.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // Setup 1: clone the staged source clouds into SoA and apply the initial guess (double math, float store); reduce
@@ -687,13 +688,8 @@ __global__ __launch_bounds__(MULLS_BLOCK) void k_thin(CloudDesc *__restrict__ de
 // with time stamp t = curvature in [thre, 1 - thre] moves by the fraction t of Tran — slerp from the identity quaternion (Eigen's
 // QuaternionBase::slerp), linear translation — in double, stored as float; directions, intensities and time stamps stay.  What mulls_slam applies to a
 // frame's clouds after its registration (test/mulls_slam.cpp:703-712); k_clone_src does the same inside a registration (cregistration.hpp:1251-1253).
-struct MotionComp
-{
-	double q[4]; // Eigen::Quaterniond(Tran.block<3,3>(0,0)): w x y z
-	double t[3]; // Tran.block<3,1>(0,3)
-	double theta, sin_theta; // acos(|q.w|) — one value per transform, by the HOST's libm, the reference's own (launch_motion_comp) — and its sine (detmath.h)
-	float thre;
-};
+// The arithmetic is scan_math.h's motion_comp_point: the merged-map builder (k_scan.hip) applies the same lines.
+using mulls::scan::MotionComp;
 __global__ __launch_bounds__(MULLS_BLOCK) void k_motion_comp(float4 *__restrict__ recs, uint32_t n, MotionComp M)
 {
 	const uint32_t i = blockIdx.x * MULLS_BLOCK + threadIdx.x;
@@ -701,36 +697,8 @@ __global__ __launch_bounds__(MULLS_BLOCK) void k_motion_comp(float4 *__restrict_
 		return;
 	float4 a = recs[(size_t)i * 3];
 	const float sc = recs[(size_t)i * 3 + 2].y; // curvature
-	if (sc < M.thre || (double)sc > 1.0 - M.thre)
-		return;
-	const double t = (double)sc, one = 1.0 - 2.220446049250313e-16;
-	const double dq = M.q[0], absD = fabs(dq);
-	double s0, s1;
-	if (absD >= one)
-	{
-		s0 = 1.0 - t;
-		s1 = t;
-	}
-	else
-	{
-		// (the two sines per point by detmath.h's correctly rounded sine: the same bits on every ROCm version and on the host, like the rest of the library's
-		// trigonometry; the device library's acos / sin were the one place where a result depended on the toolchain — advisor, round 4)
-		const double theta = M.theta, sinTheta = M.sin_theta;
-		s0 = mulls::det::sin_cr((1.0 - t) * theta) / sinTheta;
-		s1 = mulls::det::sin_cr((t * theta)) / sinTheta;
-	}
-	if (dq < 0)
-		s1 = -s1;
-	const double qw = s0 + s1 * M.q[0], qx = s1 * M.q[1], qy = s1 * M.q[2], qz = s1 * M.q[3];
-	const double vx = a.x, vy = a.y, vz = a.z;
-	const double uvx = 2.0 * (qy * vz - qz * vy), uvy = 2.0 * (qz * vx - qx * vz), uvz = 2.0 * (qx * vy - qy * vx);
-	const double rx = vx + qw * uvx + (qy * uvz - qz * uvy);
-	const double ry = vy + qw * uvy + (qz * uvx - qx * uvz);
-	const double rz = vz + qw * uvz + (qx * uvy - qy * uvx);
-	a.x = (float)(rx + t * M.t[0]);
-	a.y = (float)(ry + t * M.t[1]);
-	a.z = (float)(rz + t * M.t[2]);
-	recs[(size_t)i * 3] = a;
+	if (mulls::scan::motion_comp_point(a.x, a.y, a.z, sc, M))
+		recs[(size_t)i * 3] = a;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -769,14 +737,7 @@ void launch_motion_comp(hipStream_t st, float4 *recs, uint32_t n, const double q
 {
 	if (!n)
 		return;
-	MotionComp M;
-	for (int k = 0; k < 4; k++)
-		M.q[k] = q[k];
-	for (int k = 0; k < 3; k++)
-		M.t[k] = t[k];
-	M.thre = thre;
-	M.theta = std::acos(std::fabs(q[0]) < 1.0 ? std::fabs(q[0]) : 1.0);
-	M.sin_theta = mulls::det::sin_cr(M.theta);
+	const MotionComp M = mulls::scan::motion_comp_of(q, t, thre);
 	hipLaunchKernelGGL(k_motion_comp, dim3((n + MULLS_BLOCK - 1) / MULLS_BLOCK), dim3(MULLS_BLOCK), 0, st, recs, n, M);
 }
 

@@ -124,6 +124,16 @@ def load():
     lib.mulls_nms_default_params.restype = None
     lib.mulls_non_max_suppress.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.NmsParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
                                            C.POINTER(abi.NmsReport)]
+    lib.mulls_scan_prep_default_params.argtypes = [C.POINTER(abi.ScanPrepParams)]
+    lib.mulls_scan_prep_default_params.restype = None
+    lib.mulls_scan_prepare.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(abi.ScanPrepParams), C.POINTER(C.c_uint32), C.POINTER(abi.ScanPrepReport)]
+    lib.mulls_mapper_create.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+    lib.mulls_mapper_destroy.argtypes = [vp, vp]
+    lib.mulls_mapper_destroy.restype = None
+    lib.mulls_mapper_add.argtypes = [vp, vp, C.POINTER(abi.MapperFrame), C.c_uint32, C.POINTER(abi.ScanPrepParams), C.POINTER(C.c_uint32), C.POINTER(abi.MapperReport)]
+    lib.mulls_mapper_cloud.argtypes = [vp, vp, C.POINTER(abi.Cloud)]
+    lib.mulls_mapper_download.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.mulls_mapper_clear.argtypes = [vp, vp]
     lib.mulls_io_read_kitti_bin.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_read_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_write_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_int]
@@ -148,6 +158,8 @@ EXPORTS = [
     "mulls_teaser_default_params", "mulls_coarse_reg_teaser", "mulls_coarse_reg_teaser_indexed", "mulls_coarse_reg_teaser_batch",
     "mulls_sor_default_params", "mulls_sor_filter",
     "mulls_nms_default_params", "mulls_non_max_suppress",
+    "mulls_scan_prep_default_params", "mulls_scan_prepare",
+    "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
 ]
 
 
@@ -660,6 +672,20 @@ class Context:
         assert idx[n] == -1 and order[n] == -1 and n_out.value <= n
         return out[: n_out.value].copy(), idx[: n_out.value].copy(), order[:n].copy(), rep
 
+    # --- scan preparation ----------------------------------------------------------------------------------------------
+    def scan_prepare(self, pts, params):
+        """The raw-scan steps of CFilter (mulls_scan_prepare: calibration, dist filter, thinning, time ratio) on a copy of a host cloud.  Returns (kept, report):
+        the records that stay as raw (n_out, 48) bytes in input order, the abi.ScanPrepReport.  (A device buffer is prepared in place by the C call itself.)"""
+        raw = abi.records(pts).copy()
+        rep, n_out = abi.ScanPrepReport(), C.c_uint32(0)
+        rc = self.lib.mulls_scan_prepare(self.h, C.c_void_p(raw.ctypes.data) if len(raw) else None, len(raw), abi.POINT_BYTES, C.byref(params), C.byref(n_out), C.byref(rep))
+        if rc != 0:
+            raise MullsError("mulls_scan_prepare failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return raw[: n_out.value].copy(), rep
+
+    def mapper(self, capacity_points):
+        return Mapper(self, capacity_points)
+
     # --- stage-level entry points --------------------------------------------------------------------------------
     def motion_compensate(self, pts, Tran, s_ambiguous_thre=0.0):
         """CFilter::apply_motion_compensation on a copy of a host cloud (structured array of 48-byte records)."""
@@ -776,6 +802,79 @@ class Block:
         P = abi.EX_PILLAR
         which = [abi.EX_GROUND_DOWN, P + 4, P + 6, P + 5, P + 7, abi.EX_VERTEX] if down else [abi.EX_GROUND, P, P + 2, P + 1, P + 3, abi.EX_VERTEX]
         return [self.cloud(k) for k in which]
+
+
+class Mapper:
+    """mulls_mapper: the merged map mulls_slam exports (test/mulls_slam.cpp:959-1015), device-resident."""
+
+    def __init__(self, ctx, capacity_points):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self.last_report, self.last_counts = None, None
+        rc = ctx.lib.mulls_mapper_create(ctx.h, int(capacity_points), C.byref(self.h))
+        if rc != 0:
+            raise MullsError("mulls_mapper_create failed with %d: %s" % (rc, ctx.lib.mulls_last_error(ctx.h).decode()), rc)
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.mulls_mapper_destroy(self.ctx.h, self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def adjacent_tran(pose, pose_before):
+        """pose_i^-1 * pose_{i-1} (test/mulls_slam.cpp:979)"""
+        return np.linalg.inv(np.asarray(pose, np.float64)) @ np.asarray(pose_before, np.float64)
+
+    @staticmethod
+    def marshal(frames):
+        """frames as add() takes them -> (mulls_mapper_frame array, what it borrows from)"""
+        keep, arr = [], (abi.MapperFrame * max(len(frames), 1))()
+        for k, fr in enumerate(frames):
+            scan, pose, adj = (tuple(fr) + (None,))[:3]
+            if isinstance(scan, abi.Cloud):
+                arr[k].scan = scan
+            else:
+                raw = abi.records(scan)
+                keep.append(raw)
+                arr[k].scan.pts, arr[k].scan.n, arr[k].scan.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+            arr[k].pose = abi.colmajor16(pose)
+            if adj is not None:
+                arr[k].adjacent_tran, arr[k].compensate = abi.colmajor16(adj), 1
+        return arr, keep
+
+    def add(self, frames, prep):
+        """mulls_mapper_add.  frames: a list of (scan, pose) or (scan, pose, adjacent_tran): scan a host cloud or a device-resident abi.Cloud, adjacent_tran None
+        for a frame that is not compensated.  Returns (frame_n_out, report), also kept in last_counts / last_report when the call is refused."""
+        arr, keep = self.marshal(frames)
+        counts, rep = (C.c_uint32 * max(len(frames), 1))(), abi.MapperReport()
+        rc = self.ctx.lib.mulls_mapper_add(self.ctx.h, self.h, arr, len(frames), C.byref(prep), counts, C.byref(rep))
+        self.last_counts, self.last_report = list(counts)[: len(frames)], rep
+        if rc != 0:
+            raise MullsError("mulls_mapper_add failed with %d: %s" % (rc, self.ctx.lib.mulls_last_error(self.ctx.h).decode()), rc)
+        return self.last_counts, rep
+
+    def cloud(self):
+        """the map as a device-resident mulls_cloud (valid until the next add / clear)"""
+        c = abi.Cloud()
+        self.ctx._check(self.ctx.lib.mulls_mapper_cloud(self.ctx.h, self.h, C.byref(c)), "mulls_mapper_cloud")
+        return c
+
+    def download(self, first=0):
+        n = C.c_uint32(0)
+        self.ctx._check(self.ctx.lib.mulls_mapper_download(self.ctx.h, self.h, first, None, 0, C.byref(n)), "mulls_mapper_download")
+        out = np.zeros((n.value, abi.POINT_BYTES), np.uint8)
+        if n.value:
+            self.ctx._check(self.ctx.lib.mulls_mapper_download(self.ctx.h, self.h, first, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "mulls_mapper_download")
+        return out
+
+    def clear(self):
+        self.ctx._check(self.ctx.lib.mulls_mapper_clear(self.ctx.h, self.h), "mulls_mapper_clear")
 
 
 class LocalMap:
