@@ -27,6 +27,7 @@
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mulls_hip.h"
@@ -813,6 +814,130 @@ inline std::vector<int> coarse_reg_teaser_batch(const std::vector<typename pcl::
 					trans[k](r, c) = R[k].T[c * 4 + r];
 	}
 	return status;
+}
+
+// GlobalOptimize::optimize_pose_graph_ceres (src/graph_optimizer.cpp:385-417) in one device call (mulls_pgo_optimize): the nodes are the blocks in
+// their order (a constraint's ends are found by block1 / block2 ->id_in_strip, as upstream's set_pgo_problem_ceres does), pose_init goes in, pose_optimized
+// comes out.  t_limit / r_limit are upstream's moving_threshold_tran / _rot; params carries what upstream sets through GlobalOptimize's setters
+// (set_robust_function, set_equal_weight, set_max_iter_num, set_diagonal_information_matrix, set_free_node; set_problem_size has no counterpart: there is one
+// linear solver).  Returns upstream's bool: false — with pose_optimized untouched — when there are too few edges or the initial cost is not finite; with
+// update_edge_or_not, false also when the edge check fails (update_optimized_edges, :713-776).  The consequences upstream draws there are applied here,
+// since the library changes no edge: a wrong REGISTRATION edge's con_type becomes NONE, and when the check passes every ADJACENT edge's
+// information_matrix takes the covariance ratio (first_time_updating_ratio the first time, life_long_updating_ratio afterwards; both 1.0 upstream).
+// update_optimized_edges' second argument, fixed_reg_edge, which gates that ratio, is taken at its default true: upstream's only call passes none.
+// include/mulls_hip.h says which lines of the definition are upstream's, which restate Ceres (from its documentation, not compared) and which are the library's.
+namespace detail
+{
+template <typename Constraints>
+inline void pgo_fill(const cloudblock_Ptrs &blocks, const Constraints &cons, std::vector<mulls_pgo_node> &nodes, std::vector<mulls_pgo_edge> &edges)
+{
+	nodes.assign(blocks.size(), mulls_pgo_node());
+	for (size_t i = 0; i < blocks.size(); i++)
+	{
+		std::memcpy(nodes[i].pose_init, blocks[i]->pose_init.data(), sizeof(nodes[i].pose_init));
+		nodes[i].fixed = blocks[i]->pose_fixed ? 1 : 0;
+		nodes[i].stable = blocks[i]->pose_stable ? 1 : 0;
+	}
+	edges.assign(cons.size(), mulls_pgo_edge());
+	for (size_t k = 0; k < cons.size(); k++)
+	{
+		edges[k].a = cons[k].block1->id_in_strip;
+		edges[k].b = cons[k].block2->id_in_strip;
+		edges[k].type = (int32_t)cons[k].con_type;
+		std::memcpy(edges[k].T, cons[k].Trans1_2.data(), sizeof(edges[k].T));
+		for (int c = 0; c < 6; c++)
+			for (int r = 0; r < 6; r++)
+				edges[k].info[r + 6 * c] = cons[k].information_matrix(r, c);
+	}
+}
+template <typename Constraints>
+inline bool pgo_take(const mulls_pgo_result &R, const double *poses, const uint8_t *wrong, cloudblock_Ptrs &blocks, Constraints &cons, bool update_edge_or_not,
+					 float first_time_updating_ratio, float life_long_updating_ratio)
+{
+	if (R.status != 1)
+		return false;
+	for (size_t i = 0; i < blocks.size(); i++)
+		for (int c = 0; c < 4; c++)
+			for (int r = 0; r < 4; r++)
+				blocks[i]->pose_optimized(r, c) = poses[16 * i + 4 * c + r];
+	if (!update_edge_or_not)
+		return true;
+	for (size_t k = 0; k < cons.size(); k++)
+		if (wrong[k] && cons[k].con_type == REGISTRATION)
+			cons[k].con_type = NONE;
+	if (!R.edges_ok)
+		return false;
+	for (size_t k = 0; k < cons.size(); k++)
+		if (cons[k].con_type == ADJACENT)
+		{
+			const double ratio = cons[k].cov_updated ? life_long_updating_ratio : first_time_updating_ratio;
+			for (int c = 0; c < 6; c++)
+				for (int r = 0; r < 6; r++)
+					cons[k].information_matrix(r, c) = ratio * cons[k].information_matrix(r, c);
+			cons[k].cov_updated = true;
+		}
+	return true;
+}
+} // namespace detail
+
+inline mulls_pgo_params pgo_params()
+{
+	mulls_pgo_params P;
+	mulls_pgo_default_params(&P);
+	return P;
+}
+
+// (Constraints: upstream's `constraints`, the aligned vector of constraint_t; a template parameter because that typedef follows the types this header is included behind)
+template <typename Constraints>
+inline bool optimize_pose_graph(mulls_ctx *ctx, cloudblock_Ptrs &all_blocks, Constraints &all_cons, double t_limit, double r_limit,
+								bool update_edge_or_not = true, mulls_pgo_params params = pgo_params(), float first_time_updating_ratio = 1.0f,
+								float life_long_updating_ratio = 1.0f)
+{
+	std::vector<mulls_pgo_node> nodes;
+	std::vector<mulls_pgo_edge> edges;
+	detail::pgo_fill(all_blocks, all_cons, nodes, edges);
+	params.t_limit = t_limit, params.r_limit = r_limit;
+	std::vector<double> poses(16 * nodes.size() + 1);
+	std::vector<uint8_t> wrong(edges.size() + 1);
+	mulls_pgo_result R;
+	const int rc = mulls_pgo_optimize(ctx, nodes.data(), (uint32_t)nodes.size(), edges.data(), (uint32_t)edges.size(), &params, poses.data(), wrong.data(), &R);
+	if (rc != MULLS_OK) // infrastructure failure or refused arguments: the reference has no channel for it
+		throw std::runtime_error(std::string("mulls_pgo_optimize failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	return detail::pgo_take(R, poses.data(), wrong.data(), all_blocks, all_cons, update_edge_or_not, first_time_updating_ratio, life_long_updating_ratio);
+}
+
+// The inner-submap loop of test/mulls_slam.cpp:885-926 in one call (mulls_pgo_optimize_batch): problem k is (*graphs[k].first, *graphs[k].second), one
+// chain of frames per submap.  Entry k of the return value is what optimize_pose_graph returns for it; the blocks and constraints are written as there.
+template <typename Constraints>
+inline std::vector<bool> optimize_pose_graph_batch(mulls_ctx *ctx, std::vector<std::pair<cloudblock_Ptrs *, Constraints *>> &graphs, double t_limit,
+												   double r_limit, bool update_edge_or_not = false, mulls_pgo_params params = pgo_params(),
+												   float first_time_updating_ratio = 1.0f, float life_long_updating_ratio = 1.0f)
+{
+	const size_t B = graphs.size();
+	std::vector<std::vector<mulls_pgo_node>> nodes(B);
+	std::vector<std::vector<mulls_pgo_edge>> edges(B);
+	std::vector<std::vector<double>> poses(B);
+	std::vector<std::vector<uint8_t>> wrong(B);
+	std::vector<mulls_pgo_problem> problems(B);
+	for (size_t k = 0; k < B; k++)
+	{
+		detail::pgo_fill(*graphs[k].first, *graphs[k].second, nodes[k], edges[k]);
+		poses[k].resize(16 * nodes[k].size() + 1);
+		wrong[k].resize(edges[k].size() + 1);
+		problems[k].nodes = nodes[k].data(), problems[k].n_nodes = (uint32_t)nodes[k].size();
+		problems[k].edges = edges[k].data(), problems[k].n_edges = (uint32_t)edges[k].size();
+		problems[k].poses_out = poses[k].data(), problems[k].edge_wrong = wrong[k].data();
+	}
+	params.t_limit = t_limit, params.r_limit = r_limit;
+	std::vector<mulls_pgo_result> R(B);
+	const int rc = mulls_pgo_optimize_batch(ctx, problems.data(), (uint32_t)B, &params, 0, R.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_pgo_optimize_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	std::vector<bool> ok(B);
+	for (size_t k = 0; k < B; k++)
+		ok[k] = detail::pgo_take(R[k], poses[k].data(), wrong[k].data(), *graphs[k].first, *graphs[k].second, update_edge_or_not, first_time_updating_ratio,
+								 life_long_updating_ratio);
+	return ok;
 }
 
 // CFilter<PointT>::sor_filter (include/common/cfilter.hpp:204-222 and :225-247), verbatim signatures (upstream gives no defaults): the statistical

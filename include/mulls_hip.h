@@ -1045,6 +1045,176 @@ int mulls_mapper_cloud(mulls_ctx *ctx, const mulls_mapper *mapper, mulls_cloud *
 int mulls_mapper_download(mulls_ctx *ctx, const mulls_mapper *mapper, uint32_t first, void *pts, uint32_t cap, uint32_t *n);
 int mulls_mapper_clear(mulls_ctx *ctx, mulls_mapper *mapper);
 
+/* ---- pose graph optimisation: GlobalOptimize::optimize_pose_graph_ceres (src/graph_optimizer.cpp:385-417, with set_pgo_problem_ceres :481-636) and update_optimized_edges (:713-776) ----
+ * The step behind a closed loop: registration edges (mulls_result.T / .info) and the odometry chain in, one pose per node out — the poses
+ * mulls_mapper_add takes.  Upstream hands the problem to Ceres.  Ceres is not available where this library is built and tested, so NOTHING BELOW WAS CHECKED
+ * AGAINST CERES: lines marked [upstream] follow the reference's own code, lines marked [Ceres] restate Ceres's documented defaults (trust-region
+ * Levenberg-Marquardt), lines marked [LIB] are this library's own choices where upstream's result rests on Ceres internals that cannot be pinned.
+ * tests/pgo_restated.py restates all of it independently in numpy, bit for bit: every operation is + - * / sqrt in double, in the order written here
+ * (the library is built without FMA contraction).  Matrices are column-major 4 x 4 / 6 x 6, quaternions are (x, y, z, w).
+ *
+ *   edges used [upstream] an edge is used iff its type is neither NONE nor HISTORY (:493, :540); an edge with a > b is taken as it comes; several edges
+ *              between one pair are all summed.  "Edge index" below counts the used edges in input order.
+ *   early return [upstream :513] (n_nodes - nodes with `fixed` set) > used edges: status -1, poses_out = pose_init verbatim, no device work; the rest of a
+ *              batch still runs.
+ *   classes    [upstream :533-629, quirks kept] with_reg = a used REGISTRATION edge exists, m = the smallest `a` among them; stable_index = m when
+ *              with_reg, else 0.  For i ascending, the first rule that matches: (1) with_reg && i <= m: fixed; (2) `fixed` set: fixed; (3) `stable` set:
+ *              unless free_all_nodes, box (t_limit, r_limit) and stable_index = i (with free_all_nodes neither); (4) otherwise: unless free_all_nodes,
+ *              box ((i - stable_index) t_limit, (i - stable_index) r_limit), the factor converted to double first.  [LIB] fixed nodes are constants of
+ *              the problem (upstream holds them inside +-1e-10); a box of width 0 is a box: the node stays an unknown and is projected onto its start.
+ *              n_fixed / n_boxed / n_free count the three classes; the unknowns are the non-fixed nodes in ascending index, six each (dt, dtheta).
+ *   state      [upstream / LIB] per node t and a unit quaternion from pose_init: Eigen's matrix -> quaternion (trace t = m00 + m11 + m22 summed left to
+ *              right; t > 0: r = sqrt(t + 1), w = 0.5 r, r = 0.5 / r, x = (m21 - m12) r, y = (m02 - m20) r, z = (m10 - m01) r; else i = 0, i = 1 if
+ *              m11 > m00, i = 2 if m22 > m_ii, j = (i + 1) % 3, k = (j + 1) % 3, r = sqrt(((m_ii - m_jj) - m_kk) + 1), q_i = 0.5 r, r = 0.5 / r,
+ *              w = (m_kj - m_jk) r, q_j = (m_ji + m_ij) r, q_k = (m_ki + m_ik) r), then normalisation: q / sqrt(((x x + y y) + z z) + w w), four
+ *              divisions.  Per edge (t^, q^) from T by the same rule.  The product p (x) q is Eigen's: x = ((pw qx + px qw) + py qz) - pz qy,
+ *              y = ((pw qy + py qw) + pz qx) - px qz, z = ((pw qz + pz qw) + px qy) - py qx, w = ((pw qw - px qx) - py qy) - pz qz.  R(q) is Eigen's
+ *              toRotationMatrix (utility.hpp:199-212): tx = 2x, ty = 2y, tz = 2z, twx = tx w, twy = ty w, twz = tz w, txx = tx x, txy = ty x,
+ *              txz = tz x, tyy = ty y, tyz = tz y, tzz = tz z; R = [1 - (tyy + tzz), txy - twz, txz + twy; txy + twz, 1 - (txx + tzz), tyz - twx;
+ *              txz - twy, tyz + twx, 1 - (txx + tyy)].  poses_out = [R(normalise(q)), t; 0 0 0 1] for every node, fixed ones included.
+ *   residual   [upstream graph_optimizer.h:87-136] d = t_b - t_a, v_r = (R_0r d_0 + R_1r d_1) + R_2r d_2 with R = R(q_a) (v = R^T d), e_p = v - t^;
+ *              P = q^ (x) conj(conj(q_a) (x) q_b), e_r = 2 vec(P); e = [e_p; e_r].
+ *   weight W   [upstream / LIB] use_equal_weight: diag(1, 1, 1, r2, r2, r2), r2 = (double)quat_tran_ratio squared; else
+ *              use_diagonal_information_matrix: diag(info_jj); else W_kl = 0.5 (info_kl + info_lk).  Upstream multiplies the residual by a matrix square
+ *              root; only s = e^T W e enters the objective, so none is taken and a singular info stays legal.  u = W e (u_k = sum_l W_kl e_l),
+ *              s = sum_k e_k u_k.  EVERY 6-TERM SUM HERE AND BELOW STARTS FROM 0.0 AND ADDS ITS PRODUCTS IN ASCENDING INNER INDEX.
+ *   cost       [LIB] cost = 0.5 sum_edges rho(s).  robustify: d = (double)robust_delta, rho = s and w = 1 for s <= d d, else rho = (2 d) sqrt(s) - d d
+ *              and w = d / sqrt(s) (Huber; no second-order correction).  Without robustify rho = s, w = 1.
+ *   update     [LIB] t <- t + dt; q <- normalise(q (x) (0.5 dtheta, 1)): a retraction with the exponential map's first-order Jacobian and no
+ *              transcendental function.
+ *   Jacobians  [LIB] analytic, 6 x 6 per end, rows = residual, columns = (dt, dtheta): Ja = [-R^T, [v]x; 0, A], Jb = [R^T, 0; 0, B] with
+ *              [v]x = [0, -v2, v1; v2, 0, -v0; -v1, v0, 0], column c of A = vec(P (x) (e_c, 0)), column c of B = -vec((q^ (x) (e_c, 0)) (x) Q),
+ *              Q = conj(conj(q_a) (x) q_b).
+ *   per edge   [LIB] WJa = w (W Ja), WJb = w (W Jb), wu = w u (the sum first, then times w); Haa = Ja^T WJa, Hab = Ja^T WJb, Hbb = Jb^T WJb,
+ *              ga = Ja^T wu, gb = Jb^T wu (inner index = the residual row).  The block of (b, a) is Hab transposed.
+ *   assembly   [LIB] H's block (i, j) and g_i: 0.0 plus the contributions of the used edges that touch them, in ascending edge index.  Only block rows
+ *              i >= j are kept, and of a diagonal block only the lower triangle is read.
+ *   damped step [Ceres] radius starts at 1e4, nu at 2.  D_jj = min(max(H_jj, 1e-6), 1e32) / radius; solve (H + D) delta = -g;
+ *              model decrease md = -0.5 sum_j delta_j (g_j - D_jj delta_j)  ([LIB] this is -delta^T (g + H delta / 2) with H delta replaced by
+ *              -g - D delta, the solved system's identity, so that no second matrix product is taken).  The step succeeds iff cost+ is finite, md > 0 and
+ *              rr = (cost - cost+) / md > 1e-3; then radius = min(radius / max(1.0 / 3.0, 1 - (u u) u), 1e16) with u = 2 rr - 1, nu = 2; else
+ *              radius = radius / nu, nu = 2 nu.  [LIB] a non-positive or non-finite pivot counts as a failed step.
+ *   projection [LIB] applied to the candidate before its cost is taken.  A boxed node's t is clamped per component to pose_init's t -+ its limit (lo = t0 - l,
+ *              hi = t0 + l; t < lo ? lo : t, then > hi ? hi).  Unless only_limit_translation its quaternion is (1) negated when
+ *              ((x x0 + y y0) + z z0) + w w0 < 0, (2) clamped per component to q0 -+ its limit, (3) normalised again.  Upstream's bound is on the raw
+ *              4-vector: the clamped 4-vector before the last normalisation is what this contract speaks of.
+ *   iteration  [Ceres / LIB] in this order: no unknown -> stop NO_FREE (before anything else); iterations == num_iterations -> stop MAX_ITERATIONS
+ *              (successful and failed steps both count); linearise at the state; max |g_j| <= 1e-10 -> stop GRADIENT; iterations += 1; factor and solve
+ *              (failure: failed step); max |delta_j| <= 1e-8 -> stop STEP; candidate, projection, cost+, md; success: the state and cost move, and
+ *              |cost - cost+| <= function_tolerance * cost (the cost before the step) -> stop FUNCTION_TOLERANCE; failure: radius < 1e-32 -> stop RADIUS.
+ *              status 1 covers every stop (Ceres's "usable"); status -2: the initial cost is not finite (poses_out = pose_init verbatim).
+ *   linear solve [LIB] H is stored as a block skyline: block row i runs from first_i (its smallest unknown neighbour, or i) to i.  Cholesky L L^T:
+ *              block (i, j), j <= i: S = (H + D)_ij; for k = max(first_i, first_j) .. j - 1 ascending: S_rc -= (sum_m L_ik[r][m] L_jk[c][m]);
+ *              j < i: L_ij[r][c] = (S_rc - L_ij[r][0] L_jj[c][0] - ... - L_ij[r][c-1] L_jj[c][c-1]) / L_jj[c][c], one subtraction per product, c ascending;
+ *              j = i: the scalar Cholesky of the lower triangle, column c ascending: x = S_rc - L[r][0] L[c][0] - ... - L[r][c-1] L[c][c-1];
+ *              r = c: the pivot x must be finite and > 0, L[c][c] = sqrt(x); r > c: L[r][c] = x / L[c][c].  Forward, y = -g: for j ascending:
+ *              y_j[r] = (y_j[r] - L_jj[r][0] y_j[0] - ... ) / L_jj[r][r], r ascending; then y_i[r] -= (sum_m L_ij[r][m] y_j[m]) for every row i > j that
+ *              holds block (i, j).  Backward: for k descending: x_k[r] = (y_k[r] - L_kk[r+1][r] x_k[r+1] - ... - L_kk[5][r] x_k[5]) / L_kk[r][r],
+ *              r descending; then y_j[c] -= (sum_m L_kj[m][c] x_k[m]) for j = first_k .. k - 1.  THE VALUE OF EVERY ENTRY IS FIXED, NOT THE SCHEDULE:
+ *              the device factors column by column and updates the trailing rows of a column in parallel, with these bits.
+ *   sums       [LIB] the cost and md: 256 strided partials (partial l = 0.0 + the terms l, l + 256, ... ascending), then the tree
+ *              p[l] += p[l + w] for w = 128, 64, ..., 1; maxima are exact in any order.
+ *   edge check [upstream :713-776, :1041-1050] on the host after the solve, per used REGISTRATION / ADJACENT edge (SMOOTH edges enter the solve but not
+ *              the check): with the output poses, R = Ra^T Rb, t = Ra^T (tb - ta), Rd = R^T R^, td = R^T (t^ - t)  ([LIB] rigid inverses and 3-term
+ *              sums left to right instead of Eigen's general 4 x 4 inverse); wrong iff sqrt((tdx tdx + tdy tdy) + tdz tdz) > (double)translation_thre or
+ *              2 atan2(|vec|, |w|) of Rd's normalised quaternion > (double)rotation_thre / 180.0 * pi, atan2 from detmath.h.  edge_wrong[e] (per
+ *              input edge, 0 for edges not checked), wrong_edges, correct_reg_edges (REGISTRATION edges not wrong),
+ *              edges_ok = !((double)wrong / (double)checked > (double)ratio_thre || correct_reg == 0) (0 checked edges: the quotient is NaN, as upstream's).
+ *              The library changes no edge: the bridge (cregistration_hip.hpp) applies upstream's consequences.
+ * Capacity: MULLS_PGO_MAX_NODES nodes, MULLS_PGO_MAX_EDGES edges and MULLS_PGO_MAX_BLOCKS skyline blocks per problem (a 4096-node chain has 4095 edges and 8189 blocks, a
+ * 512-node graph with every edge 130816 edges and 131328 blocks); above them MULLS_E_UNSUPPORTED. */
+#define MULLS_PGO_MAX_NODES 4096u
+#define MULLS_PGO_MAX_EDGES 131072u
+#define MULLS_PGO_MAX_BLOCKS 262144u
+#define MULLS_PGO_BATCH_DEFAULT_SCRATCH_BYTES (256ull << 20) /* a value chosen without a measurement */
+enum mulls_pgo_edge_type /* upstream's constraint_type (utility.hpp) */
+{
+	MULLS_PGO_REGISTRATION = 0,
+	MULLS_PGO_ADJACENT = 1,
+	MULLS_PGO_HISTORY = 2,
+	MULLS_PGO_SMOOTH = 3,
+	MULLS_PGO_NONE = 4
+};
+enum mulls_pgo_termination
+{
+	MULLS_PGO_TERM_NOT_RUN = 0, /* status -1 / -2 */
+	MULLS_PGO_TERM_MAX_ITERATIONS = 1,
+	MULLS_PGO_TERM_FUNCTION_TOLERANCE = 2,
+	MULLS_PGO_TERM_GRADIENT = 3,
+	MULLS_PGO_TERM_STEP = 4,
+	MULLS_PGO_TERM_RADIUS = 5,
+	MULLS_PGO_TERM_NO_FREE = 6
+};
+typedef struct mulls_pgo_node
+{
+	double pose_init[16];	/* cloudblock_t::pose_init, column-major */
+	uint8_t fixed, stable;	/* pose_fixed, pose_stable */
+	uint8_t reserved[6];
+} mulls_pgo_node;
+typedef struct mulls_pgo_edge
+{
+	int32_t a, b;	  /* block1 / block2 ->id_in_strip: indices into the nodes */
+	int32_t type;	  /* con_type, enum mulls_pgo_edge_type */
+	int32_t reserved;
+	double T[16];	  /* Trans1_2, column-major */
+	double info[36]; /* information_matrix, column-major */
+} mulls_pgo_edge;
+typedef struct mulls_pgo_params
+{
+	int32_t num_iterations;	 /* [100] mulls_slam.cpp:181-182 (max_iter_inter_submap / max_iter_inner_submap; pgo_param_t's own 50, utility.hpp:771, is overwritten at :601) */
+	uint8_t robustify;		 /* [0] mulls_slam.cpp:190 robust_kernel_on, set at :599 (utility.hpp:760 says true) */
+	uint8_t use_equal_weight; /* [0] utility.hpp:761, mulls_slam.cpp:170 */
+	uint8_t use_diagonal_information_matrix; /* [0] utility.hpp:763, mulls_slam.cpp:185 */
+	uint8_t free_all_nodes;	 /* [0] utility.hpp:764, mulls_slam.cpp:191 */
+	uint8_t only_limit_translation; /* [0] utility.hpp:762 */
+	uint8_t reserved0[3];
+	float robust_delta;		 /* [1.0] utility.hpp:766 */
+	float quat_tran_ratio;	 /* [1000.0] utility.hpp:773 */
+	int32_t reserved1;
+	double t_limit;			 /* [2.0] mulls_slam.cpp:177 inter_submap_t_limit (the inner-submap loop passes 0.1, :179) */
+	double r_limit;			 /* [0.05] mulls_slam.cpp:178 inter_submap_r_limit (inner-submap: 0.01, :180) */
+	double function_tolerance; /* [1e-16] graph_optimizer.cpp:445 */
+	float wrong_edge_translation_thre; /* [5.0] utility.hpp:776, mulls_slam.cpp:186 */
+	float wrong_edge_rotation_thre;	   /* [25.0] degrees; mulls_slam.cpp:187 (utility.hpp:777 says 20) */
+	float wrong_edge_ratio_thre;	   /* [0.1] utility.hpp:778 */
+	uint32_t reserved2;
+} mulls_pgo_params;
+typedef struct mulls_pgo_result
+{
+	int32_t status;		 /* 1: solved (every stop); -1: too few edges; -2: the initial cost is not finite */
+	int32_t termination; /* enum mulls_pgo_termination */
+	int32_t iterations, successful_steps;
+	uint32_t n_free, n_boxed, n_fixed, n_edges_used;
+	double initial_cost, final_cost;
+	int32_t wrong_edges, correct_reg_edges, edges_ok;
+	int32_t reserved;
+} mulls_pgo_result;
+typedef struct mulls_pgo_problem
+{
+	const mulls_pgo_node *nodes;
+	uint32_t n_nodes;
+	const mulls_pgo_edge *edges;
+	uint32_t n_edges;
+	double *poses_out;	 /* 16 n_nodes, column-major */
+	uint8_t *edge_wrong; /* n_edges, or NULL */
+} mulls_pgo_problem;
+
+void mulls_pgo_default_params(mulls_pgo_params *p);
+/* One problem; a batch of one.  NULL ctx / params / result, NULL nodes with n_nodes > 0, NULL edges with n_edges > 0 or NULL poses_out with n_nodes > 0:
+ * MULLS_E_INVALID with the result untouched.  MULLS_E_INVALID for a non-finite pose, T or info, an edge index outside the nodes, a == b, an edge type outside enum mulls_pgo_edge_type, num_iterations
+ * outside 0 .. 1000, a negative or non-finite limit, tolerance, delta, ratio or threshold; MULLS_E_UNSUPPORTED above the capacity.  On either nothing is written to the
+ * result, poses_out or edge_wrong.  n_nodes = 0: MULLS_OK, a zeroed result with status 1 and termination NO_FREE. */
+int mulls_pgo_optimize(mulls_ctx *ctx, const mulls_pgo_node *nodes, uint32_t n_nodes, const mulls_pgo_edge *edges, uint32_t n_edges,
+					   const mulls_pgo_params *params, double *poses_out, uint8_t *edge_wrong, mulls_pgo_result *result);
+/* Many independent problems per call: the inner-submap loop of mulls_slam.cpp:876-926.  results[b], problems[b].poses_out and .edge_wrong are THE BITS THE
+ * SINGLE CALL RETURNS for problem b, whatever its neighbours, its position and the sub-batches.  Every problem is checked before any device work; the first
+ * offending problem's index is named in mulls_last_error and nothing is written for any problem.  The problems iterate in lock step, one launch set and
+ * one 4-byte readback (the number of problems still running) per iteration; a stopped problem is skipped with its record frozen.
+ * scratch_limit_bytes: the device memory one sub-batch may take; a problem larger than the limit runs alone.  0: MULLS_PGO_BATCH_DEFAULT_SCRATCH_BYTES.
+ * n_problems = 0: MULLS_OK. */
+int mulls_pgo_optimize_batch(mulls_ctx *ctx, const mulls_pgo_problem *problems, uint32_t n_problems, const mulls_pgo_params *params,
+							 uint64_t scratch_limit_bytes, mulls_pgo_result *results);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

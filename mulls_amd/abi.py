@@ -403,6 +403,81 @@ def sor_params(mean_k=20, std_mul=2.0):
     return p
 
 
+class PgoNode(C.Structure):
+    """mulls_pgo_node: cloudblock_t's pose_init (column-major), pose_fixed, pose_stable"""
+
+    _fields_ = [("pose_init", C.c_double * 16), ("fixed", C.c_uint8), ("stable", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+class PgoEdge(C.Structure):
+    """mulls_pgo_edge: constraint_t's block ids, con_type, Trans1_2 and information_matrix (column-major)"""
+
+    _fields_ = [("a", C.c_int32), ("b", C.c_int32), ("type", C.c_int32), ("reserved", C.c_int32), ("T", C.c_double * 16), ("info", C.c_double * 36)]
+
+
+class PgoParams(C.Structure):
+    """mulls_pgo_params"""
+
+    _fields_ = [("num_iterations", C.c_int32), ("robustify", C.c_uint8), ("use_equal_weight", C.c_uint8), ("use_diagonal_information_matrix", C.c_uint8),
+                ("free_all_nodes", C.c_uint8), ("only_limit_translation", C.c_uint8), ("reserved0", C.c_uint8 * 3), ("robust_delta", C.c_float),
+                ("quat_tran_ratio", C.c_float), ("reserved1", C.c_int32), ("t_limit", C.c_double), ("r_limit", C.c_double), ("function_tolerance", C.c_double),
+                ("wrong_edge_translation_thre", C.c_float), ("wrong_edge_rotation_thre", C.c_float), ("wrong_edge_ratio_thre", C.c_float),
+                ("reserved2", C.c_uint32)]
+
+
+class PgoResult(C.Structure):
+    """mulls_pgo_result"""
+
+    _fields_ = [("status", C.c_int32), ("termination", C.c_int32), ("iterations", C.c_int32), ("successful_steps", C.c_int32), ("n_free", C.c_uint32),
+                ("n_boxed", C.c_uint32), ("n_fixed", C.c_uint32), ("n_edges_used", C.c_uint32), ("initial_cost", C.c_double), ("final_cost", C.c_double),
+                ("wrong_edges", C.c_int32), ("correct_reg_edges", C.c_int32), ("edges_ok", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PgoProblem(C.Structure):
+    """mulls_pgo_problem: one problem of mulls_pgo_optimize_batch"""
+
+    _fields_ = [("nodes", C.c_void_p), ("n_nodes", C.c_uint32), ("edges", C.c_void_p), ("n_edges", C.c_uint32), ("poses_out", C.c_void_p),
+                ("edge_wrong", C.c_void_p)]
+
+
+PGO_REGISTRATION, PGO_ADJACENT, PGO_HISTORY, PGO_SMOOTH, PGO_NONE = range(5)  # enum mulls_pgo_edge_type
+(PGO_TERM_NOT_RUN, PGO_TERM_MAX_ITERATIONS, PGO_TERM_FUNCTION_TOLERANCE, PGO_TERM_GRADIENT, PGO_TERM_STEP, PGO_TERM_RADIUS,
+ PGO_TERM_NO_FREE) = range(7)  # enum mulls_pgo_termination
+PGO_MAX_NODES, PGO_MAX_EDGES, PGO_MAX_BLOCKS = 4096, 131072, 262144
+PGO_BATCH_DEFAULT_SCRATCH_BYTES = 256 << 20  # MULLS_PGO_BATCH_DEFAULT_SCRATCH_BYTES
+
+
+def pgo_params(**kw):
+    """mulls_pgo_default_params' values, then the keyword arguments"""
+    p = PgoParams()
+    p.num_iterations, p.robust_delta, p.quat_tran_ratio, p.t_limit, p.r_limit, p.function_tolerance = 100, 1.0, 1000.0, 2.0, 0.05, 1e-16
+    p.wrong_edge_translation_thre, p.wrong_edge_rotation_thre, p.wrong_edge_ratio_thre = 5.0, 25.0, 0.1
+    for k, v in kw.items():
+        getattr(p, k)
+        setattr(p, k, v)
+    return p
+
+
+def pgo_nodes(poses, fixed, stable):
+    """poses (n, 4, 4) row-major numpy matrices -> an array of mulls_pgo_node"""
+    poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+    arr = (PgoNode * max(len(poses), 1))()
+    for i, T in enumerate(poses):
+        arr[i].pose_init[:] = T.T.reshape(-1).tolist()
+        arr[i].fixed, arr[i].stable = int(bool(fixed[i])), int(bool(stable[i]))
+    return arr
+
+
+def pgo_edges(edges):
+    """a list of (a, b, type, T (4, 4), info (6, 6)) -> an array of mulls_pgo_edge"""
+    arr = (PgoEdge * max(len(edges), 1))()
+    for k, (a, b, typ, T, info) in enumerate(edges):
+        arr[k].a, arr[k].b, arr[k].type = int(a), int(b), int(typ)
+        arr[k].T[:] = np.asarray(T, np.float64).reshape(4, 4).T.reshape(-1).tolist()
+        arr[k].info[:] = np.asarray(info, np.float64).reshape(6, 6).T.reshape(-1).tolist()
+    return arr
+
+
 class NmsParams(C.Structure):
     """mulls_nms_params: non_max_suppress' radius (cfilter.hpp:1183) and which path runs it"""
 

@@ -26,6 +26,7 @@ struct mulls_teaser_scratch;
 struct mulls_sor_scratch;
 struct mulls_nms_scratch;
 struct mulls_scan_scratch;
+struct mulls_pgo_scratch;
 struct mulls_mapper;
 
 // A few host threads that SLEEP between their jobs (condition variable), for the staging gather of mulls_icp_batch.  An OpenMP team keeps spinning after its
@@ -89,6 +90,7 @@ struct mulls_ctx
 	mulls_sor_scratch *sor = nullptr; // mulls_sor_filter's (sor.cpp; grow-only)
 	mulls_nms_scratch *nms = nullptr; // mulls_non_max_suppress's (nms.cpp; grow-only)
 	mulls_scan_scratch *scanprep = nullptr; // mulls_scan_prepare's and mulls_mapper_add's (scan.cpp; grow-only)
+	mulls_pgo_scratch *pgo = nullptr; // mulls_pgo_optimize's (pgo.cpp; grow-only)
 	std::vector<mulls_mapper *> mappers; // live merged maps (scan.cpp)
 	int nn_mode = 0;   // 0 auto, 1 LDS-tiled brute force, 2 uniform grid in global memory, 3 (and 4) uniform grid staged in LDS
 };
@@ -248,6 +250,7 @@ void mulls_ransac_release(mulls_ctx *ctx); // frees ctx->ransac (ransac.cpp)
 void mulls_teaser_release(mulls_ctx *ctx); // frees ctx->teaser (teaser.cpp)
 void mulls_sor_release(mulls_ctx *ctx); // frees ctx->sor (sor.cpp)
 void mulls_nms_release(mulls_ctx *ctx); // frees ctx->nms (nms.cpp)
+void mulls_pgo_release(mulls_ctx *ctx); // frees ctx->pgo (pgo.cpp)
 void mulls_scan_release(mulls_ctx *ctx); // frees ctx->scanprep and destroys the mappers still alive (scan.cpp)
 
 // device-resident feature clouds of one scan (mulls_extract_features_resident, ground.cpp): 48-byte records, one buffer

@@ -264,6 +264,7 @@ extern "C"
 		mulls_ransac_release(ctx);
 		mulls_teaser_release(ctx);
 		mulls_sor_release(ctx);
+		mulls_pgo_release(ctx);
 		mulls_nms_release(ctx);
 		mulls_scan_release(ctx); // (merged maps die with their context, like local maps and feature blocks)
 		while (!ctx->maps.empty()) // local maps die with their context (mulls_map_destroy unregisters them)

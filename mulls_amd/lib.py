@@ -116,6 +116,10 @@ def load():
     lib.mulls_coarse_reg_teaser_indexed.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), vp, vp, C.c_uint32, C.POINTER(abi.TeaserParams),
                                                     C.POINTER(abi.TeaserResult), vp, C.c_uint32]
     lib.mulls_coarse_reg_teaser_batch.argtypes = [vp, C.POINTER(abi.TeaserProblem), C.c_uint32, C.POINTER(abi.TeaserParams), C.c_uint64, C.POINTER(abi.TeaserResult)]
+    lib.mulls_pgo_default_params.argtypes = [C.POINTER(abi.PgoParams)]
+    lib.mulls_pgo_default_params.restype = None
+    lib.mulls_pgo_optimize.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(abi.PgoParams), vp, vp, C.POINTER(abi.PgoResult)]
+    lib.mulls_pgo_optimize_batch.argtypes = [vp, C.POINTER(abi.PgoProblem), C.c_uint32, C.POINTER(abi.PgoParams), C.c_uint64, C.POINTER(abi.PgoResult)]
     lib.mulls_sor_default_params.argtypes = [C.POINTER(abi.SorParams)]
     lib.mulls_sor_default_params.restype = None
     lib.mulls_sor_filter.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.SorParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
@@ -157,6 +161,7 @@ EXPORTS = [
     "mulls_ransac_default_params", "mulls_coarse_reg_ransac", "mulls_coarse_reg_ransac_indexed",
     "mulls_teaser_default_params", "mulls_coarse_reg_teaser", "mulls_coarse_reg_teaser_indexed", "mulls_coarse_reg_teaser_batch",
     "mulls_sor_default_params", "mulls_sor_filter",
+    "mulls_pgo_default_params", "mulls_pgo_optimize", "mulls_pgo_optimize_batch",
     "mulls_nms_default_params", "mulls_non_max_suppress",
     "mulls_scan_prep_default_params", "mulls_scan_prepare",
     "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
@@ -621,6 +626,43 @@ class Context:
             r = abi.TeaserResult.from_buffer_copy(res[b])
             out.append((r, cliques[b][: min(max(r.clique_size, 0), cap)].copy()))
         return out
+
+    # --- pose graph optimisation --------------------------------------------------------------------------------------
+    def pgo_optimize(self, poses, fixed, stable, edges, params=None):
+        """optimize_pose_graph_ceres (mulls_pgo_optimize).  poses: (n, 4, 4) pose_init; fixed, stable: (n,) flags; edges: a list of
+        (a, b, type, T (4, 4), info (6, 6)).  Returns (result, poses_out (n, 4, 4), edge_wrong (n_edges,) uint8)."""
+        poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+        n, m = len(poses), len(edges)
+        p = params if params is not None else abi.pgo_params()
+        nodes, earr = abi.pgo_nodes(poses, fixed, stable), abi.pgo_edges(edges)
+        out, wrong, res = np.zeros((max(n, 1), 16)), np.zeros(max(m, 1), np.uint8), abi.PgoResult()
+        rc = self.lib.mulls_pgo_optimize(self.h, C.addressof(nodes) if n else None, n, C.addressof(earr) if m else None, m, C.byref(p),
+                                         out.ctypes.data if n else None, wrong.ctypes.data, C.byref(res))
+        if rc != 0:
+            raise MullsError("mulls_pgo_optimize failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return res, out[:n].reshape(n, 4, 4).transpose(0, 2, 1).copy(), wrong[:m].copy()
+
+    def pgo_optimize_batch(self, problems, params=None, scratch_limit=0):
+        """mulls_pgo_optimize_batch: many independent problems per call, each with the bits of its pgo_optimize call.  problems: a list of
+        (poses, fixed, stable, edges) as pgo_optimize takes them.  One params for the whole batch.  scratch_limit: scratch_limit_bytes (0: the
+        library's default).  Returns [(result, poses_out, edge_wrong), ...]."""
+        B = len(problems)
+        p = params if params is not None else abi.pgo_params()
+        arr, res, keep = (abi.PgoProblem * max(B, 1))(), (abi.PgoResult * max(B, 1))(), []
+        for b, (poses, fixed, stable, edges) in enumerate(problems):
+            poses = np.asarray(poses, np.float64).reshape(-1, 4, 4)
+            n, m = len(poses), len(edges)
+            nodes, earr = abi.pgo_nodes(poses, fixed, stable), abi.pgo_edges(edges)
+            out, wrong = np.zeros((max(n, 1), 16)), np.zeros(max(m, 1), np.uint8)
+            keep.append((nodes, earr, out, wrong, n, m))
+            arr[b].nodes, arr[b].n_nodes = (C.addressof(nodes) if n else None), n
+            arr[b].edges, arr[b].n_edges = (C.addressof(earr) if m else None), m
+            arr[b].poses_out, arr[b].edge_wrong = (out.ctypes.data if n else None), wrong.ctypes.data
+        rc = self.lib.mulls_pgo_optimize_batch(self.h, arr, B, C.byref(p), int(scratch_limit), res)
+        if rc != 0:
+            raise MullsError("mulls_pgo_optimize_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return [(abi.PgoResult.from_buffer_copy(res[b]), out[:n].reshape(n, 4, 4).transpose(0, 2, 1).copy(), wrong[:m].copy())
+                for b, (_, _, out, wrong, n, m) in enumerate(keep)]
 
     # --- statistical outlier removal ---------------------------------------------------------------------------------
     def sor_filter(self, pts, params=None, want_dist=False):
