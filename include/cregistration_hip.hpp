@@ -23,6 +23,7 @@
 #ifndef MULLS_CREGISTRATION_HIP_HPP
 #define MULLS_CREGISTRATION_HIP_HPP
 
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <stdexcept>
@@ -938,6 +939,84 @@ inline std::vector<bool> optimize_pose_graph_batch(mulls_ctx *ctx, std::vector<s
 		ok[k] = detail::pgo_take(R[k], poses[k].data(), wrong[k].data(), *graphs[k].first, *graphs[k].second, update_edge_or_not, first_time_updating_ratio,
 								 life_long_updating_ratio);
 	return ok;
+}
+
+// The submap archive (mulls_submaps_*): cblock_submaps[i] is submap i of `store`, pushed in that order.
+// submaps_push is the deep copy of test/mulls_slam.cpp:454 (and, with vertex_nms_radius > 0, the non_max_suppress of :462) into the store: the block's six
+// class clouds, pose_lo and id_in_strip go to the device once; later registrations take them from mulls_submaps_cloud / mulls_submaps_pairs.  The block's
+// local_bound and bound are set to what the store holds.  update_optimized_nodes (src/graph_optimizer.cpp:778-798) and
+// find_overlap_registration_constraint (src/build_pose_graph.cpp:123-209) keep upstream's remaining arguments and write the blocks and constraints as upstream
+// does; the bounds come from the device and the overlap search reads the store's poses and bounds, which these functions keep equal to the blocks'.
+// include/mulls_hip.h says which lines of the definition are upstream's and which are the library's.
+inline mulls_submap_info submaps_push(mulls_ctx *ctx, mulls_submaps *store, const cloudblock_Ptr &block, float vertex_nms_radius = 0.0f)
+{
+	const mulls_cloud clouds[MULLS_NCLASS] = {borrow(block->pc_ground), borrow(block->pc_pillar), borrow(block->pc_facade),
+											  borrow(block->pc_beam),	borrow(block->pc_roof),	  borrow(block->pc_vertex)};
+	mulls_submap_info info;
+	const int rc = mulls_submaps_push(ctx, store, clouds, block->pose_lo.data(), block->id_in_strip, vertex_nms_radius, &info);
+	if (rc != MULLS_OK) // a full store included: the reference has no channel for it
+		throw std::runtime_error(std::string("mulls_submaps_push failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	block->local_bound.min_x = info.local_bound[0], block->local_bound.min_y = info.local_bound[1], block->local_bound.min_z = info.local_bound[2];
+	block->local_bound.max_x = info.local_bound[3], block->local_bound.max_y = info.local_bound[4], block->local_bound.max_z = info.local_bound[5];
+	block->bound.min_x = info.bound[0], block->bound.min_y = info.bound[1], block->bound.min_z = info.bound[2];
+	block->bound.max_x = info.bound[3], block->bound.max_y = info.bound[4], block->bound.max_z = info.bound[5];
+	return info;
+}
+
+inline bool update_optimized_nodes(mulls_ctx *ctx, mulls_submaps *store, cloudblock_Ptrs &all_blocks, bool update_init_pose = false, bool update_bbx = false)
+{
+	std::vector<double> poses(16 * all_blocks.size() + 1);
+	for (size_t i = 0; i < all_blocks.size(); i++)
+	{
+		all_blocks[i]->pose_lo = all_blocks[i]->pose_optimized;
+		if (update_init_pose)
+			all_blocks[i]->pose_init = all_blocks[i]->pose_lo;
+		std::memcpy(&poses[16 * i], all_blocks[i]->pose_lo.data(), 16 * sizeof(double));
+	}
+	const int rc = mulls_submaps_set_poses(ctx, store, 0, (uint32_t)all_blocks.size(), poses.data(), update_bbx ? 1 : 0);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_submaps_set_poses failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (size_t i = 0; update_bbx && i < all_blocks.size(); i++)
+	{
+		mulls_submap_info info;
+		if (mulls_submaps_info(ctx, store, (uint32_t)i, &info) != MULLS_OK)
+			throw std::runtime_error(std::string("mulls_submaps_info failed: ") + mulls_last_error(ctx));
+		all_blocks[i]->bound.min_x = info.bound[0], all_blocks[i]->bound.min_y = info.bound[1], all_blocks[i]->bound.min_z = info.bound[2];
+		all_blocks[i]->bound.max_x = info.bound[3], all_blocks[i]->bound.max_y = info.bound[4], all_blocks[i]->bound.max_z = info.bound[5];
+	}
+	return true;
+}
+
+// (Constraints: upstream's `constraints`, as for optimize_pose_graph.)  The new edges are appended to cons and cons is sorted as a whole, as upstream does;
+// equal ratios keep their order.
+template <typename Constraints>
+inline int find_overlap_registration_constraint(mulls_ctx *ctx, mulls_submaps *store, cloudblock_Ptrs &blocks, Constraints &cons, float neighbor_radius = 50.0,
+												float min_iou_thre = 0.25, int adjacent_id_thre = 3, bool search_neighbor_2d = true, int max_neighbor = 10)
+{
+	if (blocks.empty())
+		return 0;
+	mulls_overlap_params P;
+	mulls_overlap_default_params(&P);
+	P.neighbor_search_dist = neighbor_radius, P.min_iou_thre = min_iou_thre, P.adjacent_id_thre = adjacent_id_thre;
+	P.search_2d = search_neighbor_2d ? 1 : 0, P.max_neighbor = max_neighbor;
+	const uint32_t cur = (uint32_t)blocks.size() - 1u;
+	std::vector<mulls_submap_edge> edges(blocks.size());
+	uint32_t n = 0;
+	const int rc = mulls_submaps_find_overlap(ctx, store, cur, &P, edges.data(), (uint32_t)edges.size(), &n);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_submaps_find_overlap failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (uint32_t k = 0; k < n; k++)
+	{
+		typename Constraints::value_type registration_con;
+		registration_con.block1 = blocks[(size_t)edges[k].tgt_id]; // history map (target)
+		registration_con.block2 = blocks[(size_t)edges[k].src_id]; // current map (source)
+		registration_con.con_type = REGISTRATION;
+		std::memcpy(registration_con.Trans1_2.data(), edges[k].Trans1_2, 16 * sizeof(double));
+		registration_con.overlapping_ratio = edges[k].overlapping_ratio;
+		cons.push_back(registration_con);
+	}
+	std::stable_sort(cons.begin(), cons.end(), [](const typename Constraints::value_type &a, const typename Constraints::value_type &b) { return a.overlapping_ratio > b.overlapping_ratio; });
+	return (int)n;
 }
 
 // CFilter<PointT>::sor_filter (include/common/cfilter.hpp:204-222 and :225-247), verbatim signatures (upstream gives no defaults): the statistical

@@ -1215,6 +1215,106 @@ int mulls_pgo_optimize(mulls_ctx *ctx, const mulls_pgo_node *nodes, uint32_t n_n
 int mulls_pgo_optimize_batch(mulls_ctx *ctx, const mulls_pgo_problem *problems, uint32_t n_problems, const mulls_pgo_params *params,
 							 uint64_t scratch_limit_bytes, mulls_pgo_result *results);
 
+/* ---- the submap archive: cloudblock_t submaps kept in device memory, their bounds, and loop closure's candidate edges ----
+ * What test/mulls_slam.cpp does with cblock_submaps between judge_new_submap and the registration of a loop-closure edge: the deep copy of the local map
+ * into a new submap (:454, utility.hpp:327-345), update_optimized_nodes (src/graph_optimizer.cpp:778-798) after a pose graph optimisation, and
+ * Constraint_Finder::find_overlap_registration_constraint (src/build_pose_graph.cpp:123-209).  Lines marked [upstream] follow the reference's code, [LIB]
+ * are this library's; PCL and FLANN are not available where this library is built and tested, and what is said of them is restated from memory and was
+ * compared with neither.  tests/submaps_restated.py restates the bounds, the overlap search and the pairs in numpy; DESIGN.md section 7.7 has the reasons.
+ *   storage    [LIB] one arena of capacity_points 48-byte records, allocated by mulls_submaps_create and never moved: a mulls_cloud handed out by
+ *              mulls_submaps_cloud stays valid until mulls_submaps_clear or mulls_submaps_destroy.  A submap's records are contiguous, in the order of
+ *              cloudblock_t::merge_feature_points(pc, false) (utility.hpp:471-482): ground, facade, pillar, beam, roof, vertex.  The six class clouds, the
+ *              merged cloud and the merged cloud without ground are slices of that one range.
+ *   capacity   [LIB] mulls_mapper_add's rule: a push that does not fit, in points or in submaps, returns MULLS_E_UNSUPPORTED, leaves the store as it was,
+ *              and info reports n[], points_needed and submaps_needed (what the store would have held).
+ *   bounds     [upstream utility.hpp:817-847] CloudUtility::get_cloud_bbx: min starts at DBL_MAX and is replaced when min > v, max starts at -DBL_MAX and
+ *              is replaced when max < v, v the float coordinate widened to double.  So a NaN never wins, +inf never becomes a minimum, -inf never a
+ *              maximum, and an axis nothing wins keeps (DBL_MAX, -DBL_MAX).  Both bounds are {min_x, min_y, min_z, max_x, max_y, max_z}.
+ *              local_bound: over the submap's records as stored.  bound: over the same points moved by pose_lo as pcl::transformPointCloud with a
+ *              Matrix4d does: (float)(((m00 x + m01 y) + m02 z) + m03) in double, no contraction, per row.  A minimum and a maximum are exact in any order:
+ *              nothing depends on the job size or on which workgroup runs first, and a batched call returns the bits of single calls.
+ *   vertex NMS [upstream mulls_slam.cpp:462] vertex_nms_radius > 0: the stored vertex cloud is, byte for byte, mulls_non_max_suppress's output for the given
+ *              cloud at that radius on its default path (below its gate of 10 points: the cloud as given).  [LIB] that entry point runs inside the push
+ *              and its refusals are the push's; its kept records pass through host memory on their way into the arena.  0: stored as given.
+ *              A negative or non-finite radius: MULLS_E_INVALID.
+ *   overlap    mulls_submaps_find_overlap, blocks = submaps 0 .. query_id, cur = query_id.
+ *              [upstream :127] query_id + 1 < adjacent_id_thre + 2: no edges.
+ *              [upstream :139-152] centres: pose_lo's translation cast to float; x, y (search_2d) or x, y, z.
+ *              [LIB / FLANN L2_Simple from memory] d2 = 0.0f + dx dx + dy dy (+ dz dz), float, left to right, dx = query - history; a neighbour needs
+ *              d2 < r2 strictly with r2 = (float)((double)r * (double)r) (mulls_non_max_suppress's rule); neighbours are ordered by (d2, id) ascending; the first max_neighbor are
+ *              kept, max_neighbor <= 0 keeps all.  A NaN d2 is no neighbour.
+ *              [upstream :571-590] iou = calculate_iou(bound of cur, bound of the neighbour), literally in double with max_(a, b) = a > b ? a : b and
+ *              min_(a, b) = a < b ? a : b; an empty box gives NaN or 0 under IEEE rules and passes no threshold >= 0.
+ *              [upstream :560-569] adjacent iff id_cur <= id_nb + thre && id_cur >= id_nb - thre on id_in_strip.
+ *              [upstream :190] kept iff !adjacent && iou > (double)min_iou_thre.
+ *              [upstream :204 / LIB] sorted by iou descending; ties keep the neighbour order (upstream's std::sort leaves them unspecified).
+ *              [LIB] Trans1_2 = inverse(pose_tgt) * pose_src with the general 4 x 4 inverse of this library's host algebra (row-pivoted LU, hostmath.h) and
+ *              its 4 x 4 product (each entry 0.0 + four products in ascending inner index); upstream's Eigen inverse cannot be pinned here.
+ *   refused    [LIB] NULL arguments, a store of another context, a cloud with points and no address, a stride under 48 or not a multiple of 4, an id or
+ *              `which` out of range, a non-finite search radius or IoU threshold: MULLS_E_INVALID, checked on the host before anything is launched.
+ * A store belongs to its context: mulls_destroy(ctx) also destroys the stores still alive. */
+#define MULLS_SUBMAP_CHUNK 1024u /* records of one submap per bounds job (one workgroup) */
+#define MULLS_SUBMAP_MERGED 6	 /* `which` of mulls_submaps_cloud / _download: all six classes in merge order */
+#define MULLS_SUBMAP_MERGED_NO_GROUND 7 /* ... facade, pillar, beam, roof, vertex */
+typedef struct mulls_submaps mulls_submaps;
+typedef struct mulls_submap_info
+{
+	uint32_t n[MULLS_NCLASS]; /* class sizes as stored, in the ABI's class order (enum mulls_class) */
+	int32_t id_in_strip;
+	uint32_t submaps_needed;  /* submaps the store holds after the push (or would have held) */
+	uint64_t offset;		  /* the submap's first record in the arena */
+	uint64_t points_needed;	  /* records the store holds after the push (or would have held) */
+	double pose_lo[16];		  /* column-major */
+	double local_bound[6];
+	double bound[6];
+} mulls_submap_info;
+typedef struct mulls_overlap_params /* build_pose_graph.h:43-44 */
+{
+	float neighbor_search_dist; /* [50.0] */
+	float min_iou_thre;			/* [0.25] */
+	int32_t adjacent_id_thre;	/* [3] */
+	int32_t search_2d;			/* [1] */
+	int32_t max_neighbor;		/* [10] */
+	int32_t reserved;
+} mulls_overlap_params;
+typedef struct mulls_submap_edge /* constraint_t as find_overlap_registration_constraint fills it; con_type is REGISTRATION */
+{
+	int32_t tgt_id; /* block1: the history submap */
+	int32_t src_id; /* block2: the query submap */
+	double overlapping_ratio;
+	double Trans1_2[16]; /* column-major */
+} mulls_submap_edge;
+
+void mulls_overlap_default_params(mulls_overlap_params *p);
+int mulls_submaps_create(mulls_ctx *ctx, uint32_t capacity_points /* <= 2^30 */, uint32_t capacity_submaps /* <= 2^16 */, mulls_submaps **out);
+void mulls_submaps_destroy(mulls_ctx *ctx, mulls_submaps *store);
+/* clouds: the six class clouds in the ABI's class order; each host memory or device memory (a cloud of the library's or any device allocation of the
+ * caller's, told apart as mulls_scan_prepare does), at any stride that is a multiple of 4 and at least 48.  Returns MULLS_OK, the new submap's id being
+ * info->submaps_needed - 1. */
+int mulls_submaps_push(mulls_ctx *ctx, mulls_submaps *store, const mulls_cloud clouds[MULLS_NCLASS], const double pose_lo[16], int32_t id_in_strip,
+					   float vertex_nms_radius, mulls_submap_info *info);
+/* the local map's six clouds and pose_lo, device to device: the bytes mulls_map_download returns.  local_bound and bound are the last mulls_map_update's
+ * report; a map that was set and never updated has none, and with vertex_nms_radius > 0 the report no longer describes what is stored: they are then taken
+ * from the stored records. */
+int mulls_submaps_push_map(mulls_ctx *ctx, mulls_submaps *store, const mulls_map *map, int32_t id_in_strip, float vertex_nms_radius, mulls_submap_info *info);
+int mulls_submaps_count(mulls_ctx *ctx, const mulls_submaps *store, uint32_t *n_submaps, uint64_t *n_points);
+int mulls_submaps_info(mulls_ctx *ctx, const mulls_submaps *store, uint32_t id, mulls_submap_info *info);
+/* which: enum mulls_class, MULLS_SUBMAP_MERGED or MULLS_SUBMAP_MERGED_NO_GROUND; a device-resident cloud (stride 48) for every entry point that takes one */
+int mulls_submaps_cloud(mulls_ctx *ctx, const mulls_submaps *store, uint32_t id, int which, mulls_cloud *out);
+/* at most cap records to host memory; *n: the cloud's size (pts NULL with cap 0: the size query) */
+int mulls_submaps_download(mulls_ctx *ctx, const mulls_submaps *store, uint32_t id, int which, void *pts, uint32_t cap, uint32_t *n);
+int mulls_submaps_clear(mulls_ctx *ctx, mulls_submaps *store);
+/* update_optimized_nodes (graph_optimizer.cpp:778-798): pose_lo of submaps first .. first + n - 1 becomes poses[16 k ..], column-major; with update_bbx
+ * their `bound` is taken again.  One upload of the poses, one launch set over jobs of MULLS_SUBMAP_CHUNK records for all n submaps, one download of 6 n
+ * doubles.  first + n beyond the count: MULLS_E_INVALID, nothing changed.  n = 0: MULLS_OK. */
+int mulls_submaps_set_poses(mulls_ctx *ctx, mulls_submaps *store, uint32_t first, uint32_t n, const double *poses, int update_bbx);
+/* edges: at most cap of them, in output order; *n_edges: the full count */
+int mulls_submaps_find_overlap(mulls_ctx *ctx, const mulls_submaps *store, uint32_t query_id, const mulls_overlap_params *params, mulls_submap_edge *edges,
+							   uint32_t cap, uint32_t *n_edges);
+/* pairs[k] for mulls_icp_batch from edges[k]: tgt = the history submap's class clouds, src = the query's (use_more_points), src_down zero,
+ * tgt_bound = the history submap's local_bound, init_guess = Trans1_2 */
+int mulls_submaps_pairs(mulls_ctx *ctx, const mulls_submaps *store, const mulls_submap_edge *edges, uint32_t n, mulls_pair *pairs);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

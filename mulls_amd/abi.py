@@ -542,6 +542,40 @@ def scan_prep_params(calib_on=0, dist_filter_on=0, calib_first=0, downsample_rat
     return p
 
 
+class SubmapInfo(C.Structure):
+    """mulls_submap_info: one submap of the device-resident archive (n in the ABI's class order; bounds as {min xyz, max xyz})"""
+
+    _fields_ = [("n", C.c_uint32 * NCLASS), ("id_in_strip", C.c_int32), ("submaps_needed", C.c_uint32), ("offset", C.c_uint64), ("points_needed", C.c_uint64),
+                ("pose_lo", C.c_double * 16), ("local_bound", C.c_double * 6), ("bound", C.c_double * 6)]
+
+
+class OverlapParams(C.Structure):
+    """mulls_overlap_params: find_overlap_registration_constraint's arguments (build_pose_graph.h:43-44)"""
+
+    _fields_ = [("neighbor_search_dist", C.c_float), ("min_iou_thre", C.c_float), ("adjacent_id_thre", C.c_int32), ("search_2d", C.c_int32),
+                ("max_neighbor", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SubmapEdge(C.Structure):
+    """mulls_submap_edge: a candidate registration edge (tgt = the history submap, src = the query)"""
+
+    _fields_ = [("tgt_id", C.c_int32), ("src_id", C.c_int32), ("overlapping_ratio", C.c_double), ("Trans1_2", C.c_double * 16)]
+
+
+SUBMAP_CHUNK = 1024  # MULLS_SUBMAP_CHUNK
+SUBMAP_MERGED = 6  # MULLS_SUBMAP_MERGED
+SUBMAP_MERGED_NO_GROUND = 7  # MULLS_SUBMAP_MERGED_NO_GROUND
+SUBMAP_MERGE_ORDER = (0, 2, 1, 3, 4, 5)  # cloudblock_t::merge_feature_points: ground, facade, pillar, beam, roof, vertex
+
+
+def overlap_params(neighbor_search_dist=50.0, min_iou_thre=0.25, adjacent_id_thre=3, search_2d=1, max_neighbor=10):
+    """upstream's defaults (build_pose_graph.h:43-44)"""
+    p = OverlapParams()
+    p.neighbor_search_dist, p.min_iou_thre = float(neighbor_search_dist), float(min_iou_thre)
+    p.adjacent_id_thre, p.search_2d, p.max_neighbor, p.reserved = int(adjacent_id_thre), int(search_2d), int(max_neighbor), 0
+    return p
+
+
 def records(a):
     """Any point array (POINT_DTYPE records or raw (n, 48) bytes) as contiguous raw (n, 48) uint8 records, every byte kept."""
     a = np.asarray(a)

@@ -92,6 +92,7 @@ struct mulls_ctx
 	mulls_scan_scratch *scanprep = nullptr; // mulls_scan_prepare's and mulls_mapper_add's (scan.cpp; grow-only)
 	mulls_pgo_scratch *pgo = nullptr; // mulls_pgo_optimize's (pgo.cpp; grow-only)
 	std::vector<mulls_mapper *> mappers; // live merged maps (scan.cpp)
+	std::vector<mulls_submaps *> submap_stores; // live submap archives (submaps.cpp): their arenas are device clouds mulls_pair may point to
 	int nn_mode = 0;   // 0 auto, 1 LDS-tiled brute force, 2 uniform grid in global memory, 3 (and 4) uniform grid staged in LDS
 };
 
@@ -252,6 +253,19 @@ void mulls_sor_release(mulls_ctx *ctx); // frees ctx->sor (sor.cpp)
 void mulls_nms_release(mulls_ctx *ctx); // frees ctx->nms (nms.cpp)
 void mulls_pgo_release(mulls_ctx *ctx); // frees ctx->pgo (pgo.cpp)
 void mulls_scan_release(mulls_ctx *ctx); // frees ctx->scanprep and destroys the mappers still alive (scan.cpp)
+void mulls_submaps_release(mulls_ctx *ctx); // destroys the submap archives still alive (submaps.cpp)
+bool mulls_submaps_memory(const mulls_ctx *ctx, const void *p, size_t bytes); // is [p, p + bytes) inside a live archive's arena? (submaps.cpp)
+
+// a local map as mulls_submaps_push_map reads it (map.cpp); false: the map is not this context's
+struct MapSnapshot
+{
+	const void *rec[MULLS_NCLASS]; // device, 48-byte records
+	uint32_t n[MULLS_NCLASS];
+	double pose[16];
+	bool has_bounds; // local_bound / bound: the last mulls_map_update's report (none after mulls_map_set)
+	double local_bound[6], bound[6];
+};
+bool mulls_map_snapshot(const mulls_ctx *ctx, const mulls_map *m, MapSnapshot *out);
 
 // device-resident feature clouds of one scan (mulls_extract_features_resident, ground.cpp): 48-byte records, one buffer
 struct mulls_block

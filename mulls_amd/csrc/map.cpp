@@ -37,6 +37,8 @@ struct mulls_map
 	size_t cap_dmask = 0;
 	uint32_t *seg = nullptr; // per-segment counters of the stable compactions
 	size_t cap_seg = 0;
+	bool has_bounds = false; // the last update's report (what a submap snapshot carries on: mulls_submaps_push_map)
+	double local_bound[6] = {}, bound[6] = {};
 };
 
 bool mulls_is_map_memory(const mulls_ctx *ctx, const void *p, size_t bytes)
@@ -52,7 +54,23 @@ bool mulls_is_map_memory(const mulls_ctx *ctx, const void *p, size_t bytes)
 	for (const mulls_block *b : ctx->blocks)
 		if (b->buf && q >= (const char *)b->buf && q + bytes <= (const char *)b->buf + b->cap)
 			return true;
-	return false;
+	return mulls_submaps_memory(ctx, p, bytes);
+}
+
+bool mulls_map_snapshot(const mulls_ctx *ctx, const mulls_map *m, MapSnapshot *out)
+{
+	if (std::find(ctx->maps.begin(), ctx->maps.end(), m) == ctx->maps.end())
+		return false;
+	for (int c = 0; c < MULLS_NC; c++)
+	{
+		out->rec[c] = m->rec[c];
+		out->n[c] = m->n[c];
+	}
+	std::memcpy(out->pose, m->pose, sizeof(m->pose));
+	out->has_bounds = m->has_bounds;
+	std::memcpy(out->local_bound, m->local_bound, sizeof(m->local_bound));
+	std::memcpy(out->bound, m->bound, sizeof(m->bound));
+	return true;
 }
 
 namespace
@@ -235,6 +253,7 @@ extern "C"
 			m->frame_n[c] = 0;
 		}
 		std::memcpy(m->pose, pose_lo, sizeof(m->pose));
+		m->has_bounds = false;
 		return MULLS_OK;
 	}
 	catch (...)
@@ -257,6 +276,7 @@ extern "C"
 		const auto wall0 = std::chrono::steady_clock::now();
 		hipStream_t st = ctx->stream;
 		std::memset(rep, 0, sizeof(*rep));
+		m->has_bounds = false; // (until step 8 of this update)
 
 		// 1. the frame's clouds on the device
 		const int rc_up = upload_clouds(ctx, frame_down, m->frame, m->cap_frame);
@@ -483,6 +503,9 @@ extern "C"
 			rep->local_bound[k] = key_to_double(keys[k], k < 3);
 			rep->bound[k] = key_to_double(keys[6 + k], k < 3);
 		}
+		std::memcpy(m->local_bound, rep->local_bound, sizeof(m->local_bound));
+		std::memcpy(m->bound, rep->bound, sizeof(m->bound));
+		m->has_bounds = true;
 		// 9. recalculate_feature_on (:98-118): principal directions of the pillar and beam clouds from their own neighbourhoods
 		//    (pca_radius 1.8, pca_max_k 20, pca_min_k 6, min_linearity 0.65), pillars kept above sin 0.80, beams below sin 0.25
 		if (P->recalculate_feature_on)

@@ -138,6 +138,21 @@ def load():
     lib.mulls_mapper_cloud.argtypes = [vp, vp, C.POINTER(abi.Cloud)]
     lib.mulls_mapper_download.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_mapper_clear.argtypes = [vp, vp]
+    lib.mulls_overlap_default_params.argtypes = [C.POINTER(abi.OverlapParams)]
+    lib.mulls_overlap_default_params.restype = None
+    lib.mulls_submaps_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+    lib.mulls_submaps_destroy.argtypes = [vp, vp]
+    lib.mulls_submaps_destroy.restype = None
+    lib.mulls_submaps_push.argtypes = [vp, vp, C.POINTER(abi.Cloud), C.POINTER(C.c_double), C.c_int32, C.c_float, C.POINTER(abi.SubmapInfo)]
+    lib.mulls_submaps_push_map.argtypes = [vp, vp, vp, C.c_int32, C.c_float, C.POINTER(abi.SubmapInfo)]
+    lib.mulls_submaps_count.argtypes = [vp, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.mulls_submaps_info.argtypes = [vp, vp, C.c_uint32, C.POINTER(abi.SubmapInfo)]
+    lib.mulls_submaps_cloud.argtypes = [vp, vp, C.c_uint32, C.c_int, C.POINTER(abi.Cloud)]
+    lib.mulls_submaps_download.argtypes = [vp, vp, C.c_uint32, C.c_int, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.mulls_submaps_clear.argtypes = [vp, vp]
+    lib.mulls_submaps_set_poses.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_int]
+    lib.mulls_submaps_find_overlap.argtypes = [vp, vp, C.c_uint32, C.POINTER(abi.OverlapParams), C.POINTER(abi.SubmapEdge), C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.mulls_submaps_pairs.argtypes = [vp, vp, C.POINTER(abi.SubmapEdge), C.c_uint32, C.POINTER(abi.Pair)]
     lib.mulls_io_read_kitti_bin.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_read_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_io_write_pcd.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_int]
@@ -165,6 +180,9 @@ EXPORTS = [
     "mulls_nms_default_params", "mulls_non_max_suppress",
     "mulls_scan_prep_default_params", "mulls_scan_prepare",
     "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
+    "mulls_overlap_default_params", "mulls_submaps_create", "mulls_submaps_destroy", "mulls_submaps_push", "mulls_submaps_push_map", "mulls_submaps_count",
+    "mulls_submaps_info", "mulls_submaps_cloud", "mulls_submaps_download", "mulls_submaps_clear", "mulls_submaps_set_poses", "mulls_submaps_find_overlap",
+    "mulls_submaps_pairs",
 ]
 
 
@@ -728,6 +746,10 @@ class Context:
     def mapper(self, capacity_points):
         return Mapper(self, capacity_points)
 
+    def submaps(self, capacity_points, capacity_submaps):
+        """a device-resident submap archive (mulls_submaps_*)"""
+        return Submaps(self, capacity_points, capacity_submaps)
+
     # --- stage-level entry points --------------------------------------------------------------------------------
     def motion_compensate(self, pts, Tran, s_ambiguous_thre=0.0):
         """CFilter::apply_motion_compensation on a copy of a host cloud (structured array of 48-byte records)."""
@@ -917,6 +939,112 @@ class Mapper:
 
     def clear(self):
         self.ctx._check(self.ctx.lib.mulls_mapper_clear(self.ctx.h, self.h), "mulls_mapper_clear")
+
+
+class Submaps:
+    """mulls_submaps: the submaps of the back end in one device arena, their bounds and loop closure's candidate edges."""
+
+    def __init__(self, ctx, capacity_points, capacity_submaps):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        self.last_info = None
+        rc = ctx.lib.mulls_submaps_create(ctx.h, int(capacity_points), int(capacity_submaps), C.byref(self.h))
+        if rc != 0:
+            raise MullsError("mulls_submaps_create failed with %d: %s" % (rc, ctx.lib.mulls_last_error(ctx.h).decode()), rc)
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.mulls_submaps_destroy(self.ctx.h, self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _raise(self, rc, what):
+        if rc != 0:
+            raise MullsError("%s failed with %d: %s" % (what, rc, self.ctx.lib.mulls_last_error(self.ctx.h).decode()), rc)
+
+    def push(self, clouds, pose_lo, id_in_strip=0, vertex_nms_radius=0.0):
+        """mulls_submaps_push.  clouds: six class clouds in the ABI's order, each a point array, raw (n, 48) records or a device-resident abi.Cloud.
+        Returns the abi.SubmapInfo, also kept in last_info when the push is refused."""
+        arr, keep = (abi.Cloud * abi.NCLASS)(), []
+        for c in range(abi.NCLASS):
+            if isinstance(clouds[c], abi.Cloud):
+                arr[c] = clouds[c]
+            else:
+                raw = abi.records(clouds[c] if clouds[c] is not None else np.zeros(0, abi.POINT_DTYPE))
+                keep.append(raw)
+                arr[c].pts, arr[c].n, arr[c].stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+        info = abi.SubmapInfo()
+        rc = self.ctx.lib.mulls_submaps_push(self.ctx.h, self.h, arr, abi.colmajor16(pose_lo), int(id_in_strip), float(vertex_nms_radius), C.byref(info))
+        self.last_info = info
+        self._raise(rc, "mulls_submaps_push")
+        return info
+
+    def push_map(self, local_map, id_in_strip=0, vertex_nms_radius=0.0):
+        """mulls_submaps_push_map: a LocalMap's clouds and pose, device to device"""
+        info = abi.SubmapInfo()
+        rc = self.ctx.lib.mulls_submaps_push_map(self.ctx.h, self.h, local_map.h, int(id_in_strip), float(vertex_nms_radius), C.byref(info))
+        self.last_info = info
+        self._raise(rc, "mulls_submaps_push_map")
+        return info
+
+    def count(self):
+        """-> (submaps, points)"""
+        n, p = C.c_uint32(0), C.c_uint64(0)
+        self._raise(self.ctx.lib.mulls_submaps_count(self.ctx.h, self.h, C.byref(n), C.byref(p)), "mulls_submaps_count")
+        return n.value, p.value
+
+    def info(self, sid):
+        info = abi.SubmapInfo()
+        self._raise(self.ctx.lib.mulls_submaps_info(self.ctx.h, self.h, int(sid), C.byref(info)), "mulls_submaps_info")
+        return info
+
+    def cloud(self, sid, which):
+        """device-resident mulls_cloud: which = a class (0..5), abi.SUBMAP_MERGED or abi.SUBMAP_MERGED_NO_GROUND; valid until clear / close"""
+        c = abi.Cloud()
+        self._raise(self.ctx.lib.mulls_submaps_cloud(self.ctx.h, self.h, int(sid), int(which), C.byref(c)), "mulls_submaps_cloud")
+        return c
+
+    def download(self, sid, which):
+        """raw (n, 48) records of one view"""
+        n = C.c_uint32(0)
+        self._raise(self.ctx.lib.mulls_submaps_download(self.ctx.h, self.h, int(sid), int(which), None, 0, C.byref(n)), "mulls_submaps_download")
+        out = np.zeros((n.value, abi.POINT_BYTES), np.uint8)
+        if n.value:
+            self._raise(self.ctx.lib.mulls_submaps_download(self.ctx.h, self.h, int(sid), int(which), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "mulls_submaps_download")
+        return out
+
+    def clear(self):
+        self._raise(self.ctx.lib.mulls_submaps_clear(self.ctx.h, self.h), "mulls_submaps_clear")
+
+    def set_poses(self, first, poses, update_bbx=True):
+        """mulls_submaps_set_poses (update_optimized_nodes): poses a sequence of 4 x 4 matrices for submaps first, first + 1, ..."""
+        poses = [np.asarray(P, np.float64) for P in poses]
+        flat = np.ascontiguousarray(np.concatenate([P.T.reshape(-1) for P in poses]) if poses else np.zeros(0), np.float64)
+        self._raise(self.ctx.lib.mulls_submaps_set_poses(self.ctx.h, self.h, int(first), len(poses), flat.ctypes.data_as(C.POINTER(C.c_double)), int(bool(update_bbx))),
+                    "mulls_submaps_set_poses")
+
+    def find_overlap(self, query_id, params=None, cap=None):
+        """mulls_submaps_find_overlap -> (the first `cap` edges as a list of abi.SubmapEdge, the full count); cap None: all of them"""
+        params = abi.overlap_params() if params is None else params
+        n = C.c_uint32(0)
+        if cap is None:
+            self._raise(self.ctx.lib.mulls_submaps_find_overlap(self.ctx.h, self.h, int(query_id), C.byref(params), None, 0, C.byref(n)), "mulls_submaps_find_overlap")
+            cap = n.value
+        arr = (abi.SubmapEdge * max(int(cap), 1))()
+        self._raise(self.ctx.lib.mulls_submaps_find_overlap(self.ctx.h, self.h, int(query_id), C.byref(params), arr, int(cap), C.byref(n)), "mulls_submaps_find_overlap")
+        return [arr[k] for k in range(min(int(cap), n.value))], n.value
+
+    def pairs(self, edges):
+        """mulls_submaps_pairs: a mulls_pair array for mulls_icp_batch (Context.icp_batch(..., marshalled=(pairs, results)))"""
+        arr = (abi.SubmapEdge * max(len(edges), 1))(*edges)
+        out = (abi.Pair * max(len(edges), 1))()
+        self._raise(self.ctx.lib.mulls_submaps_pairs(self.ctx.h, self.h, arr, len(edges), out), "mulls_submaps_pairs")
+        return out
 
 
 class LocalMap:
