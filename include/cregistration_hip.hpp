@@ -1360,6 +1360,81 @@ inline bool extract_semantic_pts(cloudblock_Ptr in_block, float vf_downsample_re
 	return true;
 }
 
+// CRegistration<PointT>::omp_ndt (include/common/cregistration.hpp:945-1021), verbatim signature and defaults: the NDT baseline that
+// test/mulls_slam.cpp:633-647 and :669-684 select with --baseline_reg_method=omp_ndt, in one device call (mulls_ndt).  The binding is one early return
+// at the top of the member function:
+//     #ifdef MULLS_USE_HIP
+//         return lo::hip::omp_ndt<PointT>(registration_cons, ndt_resolution, use_direct_search, initial_guess, apply_intersection_filter, fitness_score_thre);
+//     #endif
+// block1->pc_down is the target, block2->pc_down the source; Trans1_2 receives the pose, the return value is upstream's process code (1 or -3).
+// use_direct_search = false (the kd-tree over leaf centroids) is not built: the call throws with MULLS_E_UNSUPPORTED's message.
+namespace detail
+{
+template <typename Constraint>
+inline void ndt_fill(const Constraint &con, const Eigen::Matrix4d &initial_guess, mulls_ndt_problem &P)
+{
+	P.tgt = borrow(con.block1->pc_down), P.src = borrow(con.block2->pc_down);
+	const bounds_t &a = con.block1->local_bound, &b = con.block2->local_bound;
+	const double tb[6] = {a.min_x, a.min_y, a.min_z, a.max_x, a.max_y, a.max_z}, sb[6] = {b.min_x, b.min_y, b.min_z, b.max_x, b.max_y, b.max_z};
+	for (int k = 0; k < 6; k++)
+		P.tgt_bound[k] = tb[k], P.src_bound[k] = sb[k];
+	for (int k = 0; k < 16; k++)
+		P.init_guess[k] = initial_guess.data()[k]; // (column-major)
+}
+} // namespace detail
+inline mulls_ndt_params ndt_params(float ndt_resolution = 1.0, bool use_direct_search = true, bool apply_intersection_filter = true, float fitness_score_thre = 10.0)
+{
+	mulls_ndt_params P;
+	mulls_ndt_default_params(&P);
+	P.resolution = ndt_resolution, P.search_method = use_direct_search ? MULLS_NDT_DIRECT7 : MULLS_NDT_KDTREE;
+	P.apply_intersection_filter = apply_intersection_filter ? 1 : 0, P.fitness_score_thre = fitness_score_thre;
+	return P;
+}
+template <typename PointT>
+inline int omp_ndt(constraint_t &registration_cons, float ndt_resolution = 1.0, bool use_direct_search = true,
+				   Eigen::Matrix4d initial_guess = Eigen::Matrix4d::Identity(), bool apply_intersection_filter = true, float fitness_score_thre = 10.0)
+{
+	mulls_ctx *ctx = thread_context();
+	mulls_ndt_problem P;
+	detail::ndt_fill(registration_cons, initial_guess, P);
+	const mulls_ndt_params prm = ndt_params(ndt_resolution, use_direct_search, apply_intersection_filter, fitness_score_thre);
+	mulls_ndt_result R;
+	const int rc = mulls_ndt(ctx, &P, &prm, &R);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_ndt failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (int k = 0; k < 16; k++)
+		registration_cons.Trans1_2.data()[k] = R.T[k];
+	return R.code;
+}
+// many constraints in one call (mulls_ndt_batch): every constraint with the bits of its omp_ndt call; initial_guesses is empty (identity for all) or
+// one matrix per constraint.  Returns the process codes.
+template <typename PointT>
+inline std::vector<int> omp_ndt_batch(std::vector<constraint_t> &registration_cons, float ndt_resolution = 1.0, bool use_direct_search = true,
+									  const std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>> &initial_guesses = {},
+									  bool apply_intersection_filter = true, float fitness_score_thre = 10.0)
+{
+	const size_t B = registration_cons.size();
+	if (!initial_guesses.empty() && initial_guesses.size() != B)
+		throw std::runtime_error("lo::hip::omp_ndt_batch: one initial guess per constraint, or none");
+	mulls_ctx *ctx = thread_context();
+	std::vector<mulls_ndt_problem> problems(B);
+	for (size_t k = 0; k < B; k++)
+		detail::ndt_fill(registration_cons[k], initial_guesses.empty() ? Eigen::Matrix4d(Eigen::Matrix4d::Identity()) : initial_guesses[k], problems[k]);
+	const mulls_ndt_params prm = ndt_params(ndt_resolution, use_direct_search, apply_intersection_filter, fitness_score_thre);
+	std::vector<mulls_ndt_result> R(B);
+	const int rc = mulls_ndt_batch(ctx, problems.data(), (uint32_t)B, &prm, R.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_ndt_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	std::vector<int> codes(B);
+	for (size_t k = 0; k < B; k++)
+	{
+		for (int e = 0; e < 16; e++)
+			registration_cons[k].Trans1_2.data()[e] = R[k].T[e];
+		codes[k] = R[k].code;
+	}
+	return codes;
+}
+
 } // namespace hip
 } // namespace lo
 

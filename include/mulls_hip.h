@@ -1315,6 +1315,109 @@ int mulls_submaps_find_overlap(mulls_ctx *ctx, const mulls_submaps *store, uint3
  * tgt_bound = the history submap's local_bound, init_guess = Trans1_2 */
 int mulls_submaps_pairs(mulls_ctx *ctx, const mulls_submaps *store, const mulls_submap_edge *edges, uint32_t n, mulls_pair *pairs);
 
+/* ---- NDT registration: CRegistration::omp_ndt (cregistration.hpp:945-1021) with base_align (:762-785), koide_reg::NormalDistributionsTransform
+ * (baseline_reg/ndt_omp_impl.hpp), koide_reg::VoxelGridCovariance::applyFilter and getNeighborhoodAtPoint{1,7,} (voxel_grid_covariance_omp_impl.hpp:44-443)
+ * and pcl::Registration::getFitnessScore.  The yardstick is a numpy restatement written from reading those files (tests/ndt_restated.py); NOTHING WAS
+ * COMPARED WITH ndt_omp OR PCL THEMSELVES (PCL is not a dependency of this repository).  [upstream]: kept as upstream has it; [LIB]: defined here.
+ *
+ * Pre-steps [upstream, omp_ndt]  tgt = block1->pc_down, src = block2->pc_down.  The guess counts as identity when Eigen's isIdentity(1e-6) says so
+ *   (|g_ii - 1| <= 1e-6 min(|g_ii|, 1), |g_ij| <= 1e-6).  Otherwise every source point becomes float(((g00 x + g01 y) + g02 z) + g03), .. in double
+ *   (pcl::transformPointCloudWithNormals with a Matrix4d), src_bound is replaced by the box of the moved source, and T = T_ndt * guess at the end.
+ *   box = {max(tgt_bound.min, src_bound.min) - 2, min(tgt_bound.max, src_bound.max) + 2} (get_intersection_bbx); with apply_intersection_filter both
+ *   clouds keep, in order, the points with min < (double)coordinate < max on the three axes.  NDT itself starts from p = 0.
+ *   [LIB] a cloud that is empty after the crop: no registration runs, T = guess (or identity), fitness = DBL_MAX, code = -3, converged = 0.
+ * Grid [upstream]  inv = 1.0f / resolution (float); min_p, max_p: float minimum and maximum of the cropped target; min_b = (int)floorf(min_p * inv),
+ *   max_b likewise, div_b = max_b - min_b + 1; cell of a point: (int)(floorf(x * inv) - (float)min_b.x), ..; index = i + j div_b.x + k div_b.x div_b.y.
+ *   ((int64)((max_p.x - min_p.x) * inv) + 1) (..y) (..z) > INT32_MAX: MULLS_E_UNSUPPORTED (upstream warns and leaves an empty grid); [LIB] the same
+ *   when div_b.x div_b.y div_b.z > INT32_MAX (upstream's int index overflows).  Per leaf, in double, points added in input order: n, the sum s of the
+ *   points, the sum q of their outer products.  mean = s / n.  n >= min_points_per_voxel: the lower triangle of the covariance, element (b, a) =
+ *   ((q_ab - 2 (s_b mean_a)) / n + mean_b mean_a) * ((n - 1.0) / n); eigenvalues e0 <= e1 <= e2 and vectors [LIB] by the cyclic Jacobi rotations of
+ *   csrc/jacobi_rot.h (pairs (0,1) (0,2) (1,2), at most 60 sweeps, until the squared off-diagonal sum is below 1e-300); e0 < 0 or e1 < 0 or e2 <= 0:
+ *   the leaf is disabled (n = -1).  e0 < m = min_covar_eigvalue_mult e2: e0 = m, then e1 = m if e1 < m, and the covariance becomes [LIB] V diag(e) V^T,
+ *   element (a, b) = ((v_a0 e0) v_b0 + (v_a1 e1) v_b1) + (v_a2 e2) v_b2.  icov [LIB] by cofactors over the determinant ((c00 k00 + c01 k01) + c02 k02);
+ *   an infinite element disables the leaf.  The leaves are found through a hash table keyed by the cell index; no dense table of the grid exists.
+ * Score constants [upstream]  c1 = 10 (1 - outlier_ratio), c2 = outlier_ratio / pow(resolution, 3), d3 = -log(c2), d1 = -log(c1 + c2) - d3,
+ *   d2 = -2 log((-log(c1 exp(-0.5) + c2) - d3) / d1), by the host's C library.
+ * Neighbourhood [upstream] of a transformed point (a float): ijk = (int)floorf(x / resolution) (a division); the offsets in order — DIRECT1: (0,0,0);
+ *   DIRECT7: (0,0,0) (1,0,0) (-1,0,0) (0,1,0) (0,-1,0) (0,0,1) (0,0,-1); DIRECT26: pcl::getAllNeighborCellIndices' 26 columns, i.e. the 13 of
+ *   (i, j, -1) for i, j in -1 .. 1 (i outer), (i, -1, 0) for i in -1 .. 1, (-1, 0, 0), then their negatives in the same order (the centre is not among
+ *   them).  An offset counts when min_b <= ijk + offset <= max_b on every axis and the cell has a leaf with n >= min_points_per_voxel.
+ *   [LIB] a transformed coordinate that is not finite or beyond 2^30 cells has no neighbours.  MULLS_NDT_KDTREE (use_direct_search = false): MULLS_E_UNSUPPORTED.
+ * One (point, leaf) term [LIB: in double throughout; upstream's float Matrix<float,4,6> intermediates and float exp are not reproduced]
+ *   R, t of T(p) = Translation(p0 p1 p2) Rx(p3) Ry(p4) Rz(p5) in double with detmath.h's correctly rounded sin and cos; x' = float(((R_r0 x + R_r1 y)
+ *   + R_r2 z) + t_r) (upstream stores the moved cloud in float), X = (double)x' - mean.  The vectors a .. h of equation 6.19 and a2 .. f3 of 6.21 as
+ *   upstream writes them, with upstream's rule that an angle below 10e-5 counts as 0 there (not in T(p)).  Every 3-term dot product is (u0 v0 + u1 v1) + u2 v2.
+ *   cX = C X, q = X . cX, e = exp_cr((-d2 q) / 2), score term -d1 e; E = d2 e; E > 1, E < 0 or NaN: the pair adds nothing; E = E d1.  J_k: the columns
+ *   of the point Jacobian (unit vectors, then (0, x.a, x.b), (x.c, x.d, x.e), (x.f, x.g, x.h)); cJ_k = C J_k (column k of C for k < 3); g_k = X . cJ_k;
+ *   gradient_k += E g_k; for i <= k: H_ik += E (((-d2 g_i) g_k + cX . h_ik) + J_k . cJ_i), the middle term only for i >= 3, J_k . cJ_i = (cJ_i)_k for k < 3.
+ *   Only the upper triangle is accumulated; the Hessian is that triangle mirrored.
+ * Sums [LIB]  a point's terms are added in offset order into 28 per-point sums starting from 0; the 28 sums over points: partial[l] = the sum over
+ *   points l, l + MULLS_NDT_TREE, .. in that order, then for w = MULLS_NDT_TREE / 2 .. 1: partial[l] += partial[l + w], l < w.  The fitness sum likewise.
+ * Newton loop [upstream :119-171]  with its quirks: converged when nr_iterations > max_iterations or (nr_iterations and |step| < transformation_epsilon);
+ *   the return on a zero or NaN ||delta|| with converged = (norm == norm).  delta [LIB]: cyclic Jacobi eigen-decomposition of the Hessian in double
+ *   (12 sweeps over the pairs (0,1) (0,2) .. (4,5); rotation as jacobi_rot.h's, the annihilated element set to 0), delta = -V diag(1/lambda) V^T g over
+ *   the eigenvalues with |lambda| > 6 2^-52 max|lambda|; ||delta|| = sqrt of the squares added in order; direction = delta / ||delta||.
+ * Line search [upstream :757-916, whole]  mu 1e-4, nu 0.9, at most max_step_iterations inner steps, step_max = step_size, step_min =
+ *   transformation_epsilon / 2, the reversed direction, interval_converged = (step_max - step_min) > 0 as written (so with upstream's constants the inner
+ *   loop never runs; it does with transformation_epsilon = 2 step_size), updateIntervalMT, trialValueSelectionMT, the extra Hessian only when the inner
+ *   loop ran ([LIB] over the same direct neighbourhood: upstream's computeHessian searches its kd-tree of leaf centroids).
+ * Results  T [LIB] = T(p) in double (upstream keeps a float matrix) times the guess; trans_probability = score / n_src [upstream]; fitness [upstream] =
+ *   the mean over the cropped source of the float squared distance ((dx dx + dy dy) + dz dz) from x' under the final p to its nearest cropped target
+ *   point; code = fitness > fitness_score_thre ? -3 : 1.  evaluations: evaluation passes, the Hessian-only ones included. */
+enum mulls_ndt_search
+{
+	MULLS_NDT_KDTREE = 0, /* not built: MULLS_E_UNSUPPORTED */
+	MULLS_NDT_DIRECT26 = 1,
+	MULLS_NDT_DIRECT7 = 2,
+	MULLS_NDT_DIRECT1 = 3
+};
+#define MULLS_NDT_TREE 4096u									/* width of the strided partial sums */
+#define MULLS_NDT_BATCH_DEFAULT_SCRATCH_BYTES (1024ull << 20) /* a value chosen without a measurement */
+#define MULLS_NDT_MAX_POINTS (1u << 24)						/* per cloud */
+typedef struct mulls_ndt_params
+{
+	float resolution;				   /* 1.0 */
+	int32_t search_method;			   /* MULLS_NDT_DIRECT7 */
+	int32_t apply_intersection_filter; /* 1 */
+	float fitness_score_thre;		   /* 10.0 */
+	uint64_t scratch_limit_bytes;	   /* of one sub-batch of mulls_ndt_batch; 0: MULLS_NDT_BATCH_DEFAULT_SCRATCH_BYTES */
+	/* upstream's constants */
+	double step_size;				/* 0.1 */
+	double transformation_epsilon; /* 0.1 */
+	double outlier_ratio;			/* 0.55 */
+	double min_covar_eigvalue_mult; /* 0.01 */
+	int32_t max_iterations;			/* 35 */
+	int32_t max_step_iterations;	/* 10 */
+	int32_t min_points_per_voxel;	/* 6 */
+	int32_t reserved;
+} mulls_ndt_params;
+typedef struct mulls_ndt_problem
+{
+	mulls_cloud tgt, src;	/* host or device memory, told apart as mulls_scan_prepare does; stride a multiple of 4, at least 12 */
+	double tgt_bound[6];	/* block1->local_bound: min x y z, max x y z */
+	double src_bound[6];	/* block2->local_bound (read only when the guess is identity) */
+	double init_guess[16];	/* column-major */
+} mulls_ndt_problem;
+typedef struct mulls_ndt_result
+{
+	int32_t code; /* 1 or -3 */
+	int32_t iterations, evaluations, converged;
+	uint32_t n_leaves, n_leaves_used; /* cells with a point; leaves with n >= min_points_per_voxel that are not disabled */
+	uint32_t n_src, n_tgt;			  /* after the crop */
+	double T[16];					  /* column-major */
+	double fitness, trans_probability;
+	double gauss_d1, gauss_d2, gauss_d3;
+	int32_t line_search_reversals, inner_steps; /* directions reversed; inner steps of all line searches */
+} mulls_ndt_result;
+void mulls_ndt_default_params(mulls_ndt_params *p);
+/* MULLS_OK, or MULLS_E_INVALID (an empty cloud, a NULL pointer, a non-finite coordinate, bound or guess, a bad stride or parameter), MULLS_E_UNSUPPORTED
+ * (MULLS_NDT_KDTREE, the grid refusals above, a cloud above MULLS_NDT_MAX_POINTS); the results are then not written. */
+int mulls_ndt(mulls_ctx *ctx, const mulls_ndt_problem *problem, const mulls_ndt_params *params, mulls_ndt_result *result);
+/* the bits of n_problems mulls_ndt calls.  The problems of a sub-batch run in lock step: a tick is one evaluation launch over the problems that still
+ * run, one launch that advances every problem's Newton / line-search state, and one 4-byte readback; at most (max_iterations + 2) (max_step_iterations + 2)
+ * + 1 ticks (the first evaluation, then per Newton iteration one trial, the inner steps and the Hessian pass).  Sub-batches are sized by params->scratch_limit_bytes; a problem larger than the limit runs alone.  n_problems = 0: MULLS_OK. */
+int mulls_ndt_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, uint32_t n_problems, const mulls_ndt_params *params, mulls_ndt_result *results);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

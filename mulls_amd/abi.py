@@ -478,6 +478,46 @@ def pgo_edges(edges):
     return arr
 
 
+class NdtParams(C.Structure):
+    """mulls_ndt_params"""
+
+    _fields_ = [("resolution", C.c_float), ("search_method", C.c_int32), ("apply_intersection_filter", C.c_int32), ("fitness_score_thre", C.c_float),
+                ("scratch_limit_bytes", C.c_uint64), ("step_size", C.c_double), ("transformation_epsilon", C.c_double), ("outlier_ratio", C.c_double),
+                ("min_covar_eigvalue_mult", C.c_double), ("max_iterations", C.c_int32), ("max_step_iterations", C.c_int32),
+                ("min_points_per_voxel", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NdtProblem(C.Structure):
+    """mulls_ndt_problem"""
+
+    _fields_ = [("tgt", Cloud), ("src", Cloud), ("tgt_bound", C.c_double * 6), ("src_bound", C.c_double * 6), ("init_guess", C.c_double * 16)]
+
+
+class NdtResult(C.Structure):
+    """mulls_ndt_result"""
+
+    _fields_ = [("code", C.c_int32), ("iterations", C.c_int32), ("evaluations", C.c_int32), ("converged", C.c_int32), ("n_leaves", C.c_uint32),
+                ("n_leaves_used", C.c_uint32), ("n_src", C.c_uint32), ("n_tgt", C.c_uint32), ("T", C.c_double * 16), ("fitness", C.c_double),
+                ("trans_probability", C.c_double), ("gauss_d1", C.c_double), ("gauss_d2", C.c_double), ("gauss_d3", C.c_double),
+                ("line_search_reversals", C.c_int32), ("inner_steps", C.c_int32)]
+
+
+NDT_KDTREE, NDT_DIRECT26, NDT_DIRECT7, NDT_DIRECT1 = range(4)  # enum mulls_ndt_search
+NDT_TREE = 4096  # MULLS_NDT_TREE
+
+
+def ndt_params(**kw):
+    """mulls_ndt_default_params' values, then the keyword arguments"""
+    p = NdtParams()
+    p.resolution, p.search_method, p.apply_intersection_filter, p.fitness_score_thre = 1.0, NDT_DIRECT7, 1, 10.0
+    p.step_size, p.transformation_epsilon, p.outlier_ratio, p.min_covar_eigvalue_mult = 0.1, 0.1, 0.55, 0.01
+    p.max_iterations, p.max_step_iterations, p.min_points_per_voxel = 35, 10, 6
+    for k, v in kw.items():
+        getattr(p, k)
+        setattr(p, k, v)
+    return p
+
+
 class NmsParams(C.Structure):
     """mulls_nms_params: non_max_suppress' radius (cfilter.hpp:1183) and which path runs it"""
 

@@ -357,5 +357,58 @@ MULLS_HD inline double asin_cr(double u)
 	}
 	return std::signbit(u) ? -res : res;
 }
+
+// exp(x) for the NDT score (ndt_math.h; upstream calls glibc's exp and expf, ndt_omp_impl.hpp:497, :606): correctly rounded for x in [-700, 0] (the
+// result is a normal number there, so the scaling by 2^k is exact), 0 below -700, +infinity above 700, NaN for NaN.  x = k ln 2 + r with ln 2 in three
+// parts (32 + 53 + 53 bits: k L1 is exact), |r| <= 0.35.  Quick phase as in trig: 1 + r + r^2 / 2 + r^3 / 6 in double-double, the rest of the series
+// in double, the value returned only when the bound on what that leaves out does not move its rounding; otherwise the series to r^27 / 27! in
+// double-double.
+MULLS_HD inline double exp_cr(double x)
+{
+	if (x != x)
+		return x;
+	if (x < -700.0)
+		return 0.0;
+	if (x > 700.0)
+		return 1.0 / 0.0;
+	const double k = std::nearbyint(x * 0x1.71547652b82fep+0);
+	dd r = two_sum(x, -(k * 0x1.62e42fee00000p-1));
+	r = add(r, neg(two_prod(k, 0x1.a39ef35793c76p-33)));
+	r = add(r, -(k * 0x1.cc01f97b57a08p-87));
+	const unsigned long long bits = (unsigned long long)((long long)k + 1023ll) << 52; // 2^k, a normal number for |x| <= 700
+	double scale;
+	__builtin_memcpy(&scale, &bits, 8);
+#ifndef MULLS_DETMATH_NO_QUICK
+	{
+		const double q = r.hi;
+		const dd s = two_prod(q, q);
+		dd t3 = two_prod(q, s.hi); // q^3
+		t3.lo += q * s.lo;
+		dd c3 = two_prod(t3.hi, 0x1.5555555555555p-3); // q^3 / 6
+		c3.lo += t3.hi * 0x1.5555555555555p-57 + t3.lo * 0x1.5555555555555p-3;
+		const double p = 0x1.5555555555555p-5 + q * (0x1.1111111111111p-7 + q * (0x1.6c16c16c16c17p-10 + q * (0x1.a01a01a01a01ap-13 + q * (0x1.a01a01a01a01ap-16 + q * (0x1.71de3a556c734p-19 + q * (0x1.27e4fb7789f5cp-22 + q * (0x1.ae64567f544e4p-26 + q * (0x1.1eed8eff8d898p-29 + q * (0x1.6124613a86d09p-33 + q * (0x1.93974a8c07c9dp-37 + q * (0x1.ae7f3e733b81fp-41 + q * (0x1.ae7f3e733b81fp-45 + q * (0x1.952c77030ad4ap-49 + q * 0x1.6827863b97d97p-53)))))))))))));
+		const double c4 = (s.hi * s.hi) * p; // q^4 / 4! + ... + q^18 / 18!
+		dd v = add(fast_two_sum(1.0, q), dd{0.5 * s.hi, 0.5 * s.lo});
+		v = add(v, c3);
+		const double lo = v.lo + (c4 + r.lo * ((1.0 + q) + 0.5 * s.hi)); // e^(q + l) = e^q (1 + l) up to l^2, l q^3 / 6 < 2^-61
+		const double err = std::fabs(c4) * 0x1p-48 + 0x1p-60;
+		const double out = v.hi + lo;
+		if (out == v.hi + (lo + err) && out == v.hi + (lo - err))
+			return out * scale;
+	}
+#endif
+	dd p = inv_fact(27);
+	if ((27 >> 1) & 1)
+		p = neg(p);
+	for (int j = 26; j >= 1; j--)
+	{
+		dd c = inv_fact(j); // the table carries the signs of the sine and cosine series
+		if ((j >> 1) & 1)
+			c = neg(c);
+		p = add(mul(p, r), c);
+	}
+	const dd v = add(mul(p, r), 1.0);
+	return (v.hi + v.lo) * scale;
+}
 } // namespace det
 } // namespace mulls

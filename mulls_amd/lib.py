@@ -120,6 +120,10 @@ def load():
     lib.mulls_pgo_default_params.restype = None
     lib.mulls_pgo_optimize.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(abi.PgoParams), vp, vp, C.POINTER(abi.PgoResult)]
     lib.mulls_pgo_optimize_batch.argtypes = [vp, C.POINTER(abi.PgoProblem), C.c_uint32, C.POINTER(abi.PgoParams), C.c_uint64, C.POINTER(abi.PgoResult)]
+    lib.mulls_ndt_default_params.argtypes = [C.POINTER(abi.NdtParams)]
+    lib.mulls_ndt_default_params.restype = None
+    lib.mulls_ndt.argtypes = [vp, C.POINTER(abi.NdtProblem), C.POINTER(abi.NdtParams), C.POINTER(abi.NdtResult)]
+    lib.mulls_ndt_batch.argtypes = [vp, C.POINTER(abi.NdtProblem), C.c_uint32, C.POINTER(abi.NdtParams), C.POINTER(abi.NdtResult)]
     lib.mulls_sor_default_params.argtypes = [C.POINTER(abi.SorParams)]
     lib.mulls_sor_default_params.restype = None
     lib.mulls_sor_filter.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.SorParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
@@ -177,6 +181,7 @@ EXPORTS = [
     "mulls_teaser_default_params", "mulls_coarse_reg_teaser", "mulls_coarse_reg_teaser_indexed", "mulls_coarse_reg_teaser_batch",
     "mulls_sor_default_params", "mulls_sor_filter",
     "mulls_pgo_default_params", "mulls_pgo_optimize", "mulls_pgo_optimize_batch",
+    "mulls_ndt_default_params", "mulls_ndt", "mulls_ndt_batch",
     "mulls_nms_default_params", "mulls_non_max_suppress",
     "mulls_scan_prep_default_params", "mulls_scan_prepare",
     "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
@@ -644,6 +649,57 @@ class Context:
             r = abi.TeaserResult.from_buffer_copy(res[b])
             out.append((r, cliques[b][: min(max(r.clique_size, 0), cap)].copy()))
         return out
+
+    # --- NDT registration ---------------------------------------------------------------------------------------------
+    @staticmethod
+    def _ndt_problem(prob, keep):
+        """prob: (tgt, src, tgt_bound, src_bound, init_guess) or a dict with those keys; a cloud is an (n, 3) float32 array, a POINT_DTYPE array or an
+        abi.Cloud (host or device memory); init_guess a row-major (4, 4) or None"""
+        if not isinstance(prob, dict):
+            prob = dict(zip(("tgt", "src", "tgt_bound", "src_bound", "init_guess"), prob))
+
+        def cloud(k):
+            if isinstance(k, abi.Cloud):
+                return k
+            k = np.asarray(k)
+            raw = k if k.dtype == abi.POINT_DTYPE else np.ascontiguousarray(k, np.float32).reshape(-1, 3)
+            raw = np.ascontiguousarray(raw)
+            keep.append(raw)
+            c = abi.Cloud()
+            c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), (abi.POINT_BYTES if raw.dtype == abi.POINT_DTYPE else 12)
+            return c
+
+        P = abi.NdtProblem()
+        P.tgt, P.src = cloud(prob["tgt"]), cloud(prob["src"])
+        P.tgt_bound[:] = [float(v) for v in prob["tgt_bound"]]
+        P.src_bound[:] = [float(v) for v in prob["src_bound"]]
+        G = np.eye(4) if prob.get("init_guess") is None else np.asarray(prob["init_guess"], np.float64).reshape(4, 4)
+        P.init_guess[:] = G.T.reshape(-1).tolist()
+        return P
+
+    def ndt(self, tgt, src, tgt_bound, src_bound, init_guess=None, params=None):
+        """CRegistration::omp_ndt (mulls_ndt).  Returns the mulls_ndt_result; np.array(res.T).reshape(4, 4).T is the pose."""
+        keep = []
+        P = self._ndt_problem((tgt, src, tgt_bound, src_bound, init_guess), keep)
+        p = params if params is not None else abi.ndt_params()
+        res = abi.NdtResult()
+        rc = self.lib.mulls_ndt(self.h, C.byref(P), C.byref(p), C.byref(res))
+        if rc != 0:
+            raise MullsError("mulls_ndt failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return res
+
+    def ndt_batch(self, problems, params=None):
+        """mulls_ndt_batch: many problems per call in lock step, each with the bits of its ndt call.  problems: as _ndt_problem takes them.  One params
+        for the whole batch (its scratch_limit_bytes sizes the sub-batches).  Returns [mulls_ndt_result, ...]."""
+        keep, B = [], len(problems)
+        arr, res = (abi.NdtProblem * max(B, 1))(), (abi.NdtResult * max(B, 1))()
+        for b, prob in enumerate(problems):
+            arr[b] = self._ndt_problem(prob, keep)
+        p = params if params is not None else abi.ndt_params()
+        rc = self.lib.mulls_ndt_batch(self.h, arr, B, C.byref(p), res)
+        if rc != 0:
+            raise MullsError("mulls_ndt_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return [abi.NdtResult.from_buffer_copy(res[b]) for b in range(B)]
 
     # --- pose graph optimisation --------------------------------------------------------------------------------------
     def pgo_optimize(self, poses, fixed, stable, edges, params=None):

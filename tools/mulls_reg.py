@@ -57,6 +57,9 @@ def flags(argv=None):
     p.add_argument("--reciprocal_corr_on", type=boolean, default=False)
     p.add_argument("--fixed_num_corr_on", type=boolean, default=False)
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--baseline_reg_method", choices=("", "ndt"), default="",
+                   help="ndt: CRegistration::omp_ndt (mulls_ndt) on the two pc_down clouds in place of mm_lls_icp, as test/mulls_slam.cpp's omp_ndt baseline")
+    p.add_argument("--reg_voxel_size", type=float, default=1.0, help="the NDT leaf size (test/mulls_slam.cpp's reg_voxel_size)")
     a, _ = p.parse_known_args(argv)  # glog / viewer flags of the reference's script are accepted and ignored
     return a
 
@@ -120,6 +123,16 @@ def global_registration(ctx, tgt_kpts, src_kpts, F):
     return np.array(res.T[:], np.float64).reshape(4, 4).T.copy() if res.status >= 0 else np.eye(4)
 
 
+class NdtOutcome:
+    """mulls_ndt_result with the three members main() reads of an abi.Result"""
+
+    def __init__(self, r):
+        self.ndt, self.code, self.iters = r, r.code, r.iterations
+
+    def T_matrix(self):
+        return np.array(self.ndt.T[:], np.float64).reshape(4, 4).T.copy()
+
+
 def register(ctx, scan1, scan2, F):
     """Returns (abi.Result, which scan is the source: 1 or 2, that scan's pc_down)."""
     # test/mulls_reg.cpp:80-81, :134-143: block 1 is down-sampled with cloud_2_down_res, block 2 with cloud_1_down_res
@@ -139,6 +152,13 @@ def register(ctx, scan1, scan2, F):
             kpts.append(kept)
         tgt_full[5], src_down[5] = kpts
         init_mat = global_registration(ctx, tgt_full[5], src_down[5], F)
+    if F.baseline_reg_method == "ndt":
+        # omp_ndt(reg_con, reg_voxel_size, ndt_searching_method = true, init_mat) (test/mulls_slam.cpp:635): block1 / block2 ->pc_down and their local_bound
+        tgt_scan, src_scan = (scan1, scan2) if source == 2 else (scan2, scan1)
+        r = ctx.ndt((p1, p2)[2 - source], (p1, p2)[source - 1], scan_bound(abi.as_points(tgt_scan)), scan_bound(abi.as_points(src_scan)), init_mat,
+                    abi.ndt_params(resolution=F.reg_voxel_size))
+        print("omp_ndt: %d iterations, %d evaluations, fitness %.4f, %d of %d leaves used" % (r.iterations, r.evaluations, r.fitness, r.n_leaves_used, r.n_leaves))
+        return NdtOutcome(r), source, (p1, p2)[source - 1]
     pair = abi.PairData([abi.points_of(t) for t in tgt_full], [abi.points_of(s) for s in src_down],
                         init_guess=init_mat, tgt_bound=scan_bound(abi.as_points(scan1 if source == 2 else scan2)) if len(scan1) and len(scan2) else None)
     # mm_lls_icp(reg_con, max_iter, thre, converge_tran, converge_rot_d, 0.25 * thre, 1.1, "111110", "1101", 1.0, 0.1, 0.1, 0.1, init_mat)
