@@ -1435,6 +1435,69 @@ inline std::vector<int> omp_ndt_batch(std::vector<constraint_t> &registration_co
 	return codes;
 }
 
+// CRegistration<PointT>::omp_gicp (include/common/cregistration.hpp:1024-1098), verbatim signature and defaults: the GICP baseline that
+// test/mulls_slam.cpp:637-639 and :674-676 select with --baseline_reg_method=gicp, in one device call (mulls_gicp).  The binding is one early return
+// at the top of the member function:
+//     #ifdef MULLS_USE_HIP
+//         return lo::hip::omp_gicp<PointT>(registration_cons, max_iter_num, dis_thre_unit, using_voxel_gicp, voxel_size, initial_guess, apply_intersection_filter, fitness_score_thre);
+//     #endif
+// block1->pc_down is the target, block2->pc_down the source; Trans1_2 receives the pose, the return value is upstream's process code (1 or -3).
+// max_iter_num and dis_thre_unit are accepted and not read, as upstream does not read them with using_voxel_gicp = true.  using_voxel_gicp = false
+// (PCL's BFGS GICP) is not built: the call throws with MULLS_E_UNSUPPORTED's message.
+inline mulls_gicp_params gicp_params(bool using_voxel_gicp = true, float voxel_size = 1.0, bool apply_intersection_filter = false, float fitness_score_thre = 10.0)
+{
+	mulls_gicp_params P;
+	mulls_gicp_default_params(&P);
+	P.voxel_resolution = voxel_size, P.using_voxel_gicp = using_voxel_gicp ? 1 : 0;
+	P.apply_intersection_filter = apply_intersection_filter ? 1 : 0, P.fitness_score_thre = fitness_score_thre;
+	return P;
+}
+template <typename PointT>
+inline int omp_gicp(constraint_t &registration_cons, int max_iter_num = 20, float dis_thre_unit = 1.5, bool using_voxel_gicp = true, float voxel_size = 1.0,
+					Eigen::Matrix4d initial_guess = Eigen::Matrix4d::Identity(), bool apply_intersection_filter = false, float fitness_score_thre = 10.0)
+{
+	(void)max_iter_num, (void)dis_thre_unit;
+	mulls_ctx *ctx = thread_context();
+	mulls_gicp_problem P;
+	detail::ndt_fill(registration_cons, initial_guess, P);
+	const mulls_gicp_params prm = gicp_params(using_voxel_gicp, voxel_size, apply_intersection_filter, fitness_score_thre);
+	mulls_gicp_result R;
+	const int rc = mulls_gicp(ctx, &P, &prm, &R);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_gicp failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (int k = 0; k < 16; k++)
+		registration_cons.Trans1_2.data()[k] = R.T[k];
+	return R.code;
+}
+// many constraints in one call (mulls_gicp_batch): every constraint with the bits of its omp_gicp call; initial_guesses is empty (identity for all) or
+// one matrix per constraint.  Returns the process codes.
+template <typename PointT>
+inline std::vector<int> omp_gicp_batch(std::vector<constraint_t> &registration_cons, float voxel_size = 1.0,
+									   const std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>> &initial_guesses = {},
+									   bool apply_intersection_filter = false, float fitness_score_thre = 10.0, bool using_voxel_gicp = true)
+{
+	const size_t B = registration_cons.size();
+	if (!initial_guesses.empty() && initial_guesses.size() != B)
+		throw std::runtime_error("lo::hip::omp_gicp_batch: one initial guess per constraint, or none");
+	mulls_ctx *ctx = thread_context();
+	std::vector<mulls_gicp_problem> problems(B);
+	for (size_t k = 0; k < B; k++)
+		detail::ndt_fill(registration_cons[k], initial_guesses.empty() ? Eigen::Matrix4d(Eigen::Matrix4d::Identity()) : initial_guesses[k], problems[k]);
+	const mulls_gicp_params prm = gicp_params(using_voxel_gicp, voxel_size, apply_intersection_filter, fitness_score_thre);
+	std::vector<mulls_gicp_result> R(B);
+	const int rc = mulls_gicp_batch(ctx, problems.data(), (uint32_t)B, &prm, R.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_gicp_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	std::vector<int> codes(B);
+	for (size_t k = 0; k < B; k++)
+	{
+		for (int e = 0; e < 16; e++)
+			registration_cons[k].Trans1_2.data()[e] = R[k].T[e];
+		codes[k] = R[k].code;
+	}
+	return codes;
+}
+
 } // namespace hip
 } // namespace lo
 

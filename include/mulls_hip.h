@@ -1418,6 +1418,95 @@ int mulls_ndt(mulls_ctx *ctx, const mulls_ndt_problem *problem, const mulls_ndt_
  * + 1 ticks (the first evaluation, then per Newton iteration one trial, the inner steps and the Hessian pass).  Sub-batches are sized by params->scratch_limit_bytes; a problem larger than the limit runs alone.  n_problems = 0: MULLS_OK. */
 int mulls_ndt_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, uint32_t n_problems, const mulls_ndt_params *params, mulls_ndt_result *results);
 
+/* ---- Voxelised GICP registration: CRegistration::omp_gicp (cregistration.hpp:1024-1098) with using_voxel_gicp = true, the second base_align overload
+ * (:788-815), koide_reg::FastVGICP (baseline_reg/fast_vgicp_impl.hpp, fast_vgicp_voxel.h, fast_gicp_utility.h) as upstream configures it
+ * (k_correspondences 20, PLANE regularisation, ADDITIVE voxels, DIRECT1, the Sophus branch of computeTransformation) and
+ * pcl::Registration::getFitnessScore.  The yardstick is a numpy restatement written from reading those files (tests/gicp_restated.py); NOTHING WAS
+ * COMPARED WITH fast_gicp, Sophus, Eigen OR PCL THEMSELVES (none is a dependency of this repository).  [upstream]: kept as upstream has it; [LIB]:
+ * defined here.  Every 3-term dot product is (u0 v0 + u1 v1) + u2 v2; sin and atan2 are detmath.h's correctly rounded ones; no contraction.
+ *
+ * Pre-steps [upstream, omp_gicp]  exactly mulls_ndt's (the same code runs): pc_down clouds, the isIdentity(1e-6) rule, the guess applied to the source
+ *   in double and stored as float, get_intersection_bbx, the crop, T = T_gicp * guess at the end.  apply_intersection_filter defaults to 0 here (:1026).
+ *   Quirk kept: with using_voxel_gicp = true upstream never reads max_iter_num and dis_thre_unit (:1071 is commented out, corr_dist_threshold_ is
+ *   unused); the loop runs max_iterations = 64.  using_voxel_gicp = 0 (PCL's BFGS GICP): MULLS_E_UNSUPPORTED.
+ *   [LIB] a cloud with fewer than k_correspondences points after the crop: no registration runs, T = guess (or identity), fitness = DBL_MAX,
+ *   code = -3, converged = 0, stop = MULLS_GICP_STOP_NONE (upstream would read uninitialised columns of the neighbour matrix).
+ * Neighbours [LIB order, upstream set]  of every point i of a cropped cloud: the k points of the same cloud, i itself among them, that are smallest by
+ *   (float squared distance ((dx dx + dy dy) + dz dz), index) in lexicographic order.  FLANN's tie order is unknown and not claimed.
+ * Point covariance [upstream shape, LIB arithmetic]  in double: m = the sum of the k neighbours in that order, divided by k; S = the sum, in that order,
+ *   of the outer products of (p - m) (a scatter matrix: not divided); S is decomposed by the cyclic Jacobi rotations of csrc/jacobi_rot.h (pairs (0,1)
+ *   (0,2) (1,2), at most 60 sweeps, until the squared off-diagonal sum is below 1e-300); eigenvalues descending, ties by column index ascending;
+ *   C_ab = (v0_a v0_b + v1_a v1_b) + 0.01 (v2_a v2_b): PLANE, U diag(1, 1, 1e-2) V^T.  Upstream's JacobiSVD signs for a symmetric matrix are not
+ *   reproduced.  Six doubles per point (xx xy xz yy yz zz).
+ * Voxel map [upstream]  the coordinate of a float point is floorf(x / resolution - 0.5f) per axis, computed in float and cast to int (the -0.5 is
+ *   upstream's and is kept).  [LIB] the key is three 21-bit fields of coordinate + 2^20; a coordinate of a cropped point outside [-2^20, 2^20), of the
+ *   voxel map or of the neighbour search's cells of the same edge: MULLS_E_UNSUPPORTED.  Per occupied voxel, in ascending point index and in
+ *   double: n, the sum of the points, the sum of their C; mean = sum / n, cov = sum / n.  A voxel of one point is a voxel (upstream has no minimum).
+ *   The map is an open-addressing hash table; no dense grid exists.
+ * State and start [upstream]  x = (r, t), rotation vector and translation, from 0 (omp_gicp has applied the guess to the cloud).  Since |r| < 1e-2
+ *   upstream sets r = Vector3f::Random().normalized() * 1e-2, an unseeded rand(); [LIB] r = params->start_rotvec.
+ * Rotation [LIB]  in double.  exp(w): th = sqrt((w0^2 + w1^2) + w2^2); th == 0: I; else R_ij = (I_ij + a K_ij) + b K2_ij, K = skew(w), K2 = K K written
+ *   out (diagonal -(w1 w1 + w2 w2), -(w0 w0 + w2 w2), -(w0 w0 + w1 w1); off-diagonal w_i w_j), a = sin_cr(th) / th, s = sin_cr(th / 2),
+ *   b = ((2 s) s) / (th th).  log(R): w = ((R21 - R12) / 2, (R02 - R20) / 2, (R10 - R01) / 2), c = (((R00 + R11) + R22) - 1) / 2, n = |w| as above,
+ *   th = atan2_cr(n, c); the result is w (th / n), or 0 when n == 0.  Rotations near pi are outside the definition.  csrc/gicp_math.h is this text.
+ * One source point per iteration [upstream loss_ls, LIB double]  T = (exp(r), t); a'_r = ((R_r0 x + R_r1 y) + R_r2 z) + t_r, kept in double (upstream
+ *   is float throughout; not reproduced).  The voxel of float(a') is looked up; with no voxel (or a coordinate out of range) the point adds nothing.
+ *   RC = R C_A; the upper triangle of M = cov_B + RC R^T, mirrored; W = M^-1 by cofactors over the determinant ((m00 k00 + m01 k01) + m02 k02), as
+ *   the NDT leaf's icov; d = mean_B - a', e = W d, J = [W skew(a'), -W] (3 x 6; column 0 of W skew(a') is W_i1 a'_2 - W_i2 a'_1, and cyclically).
+ *   The point's 28 sums: the upper triangle of J^T J row by row (21), J^T e (6), e . e (1).  Over points: MULLS_NDT_TREE's strided-partial rule
+ *   (lane l adds points l, l + MULLS_NDT_TREE, .. in order, then the halving tree).  n_corr = the points with a voxel.
+ * Step [upstream GaussNewton::delta, LIB solve]  delta = (J^T J)^-1 J^T e by a 6 x 6 Cholesky in double, L by columns, every sum subtracted term by
+ *   term in ascending index, then the two triangular solves.  [LIB] a pivot that is <= 0 or not finite, a non-finite delta or n_corr == 0 ends the
+ *   loop: converged = 0, stop = MULLS_GICP_STOP_SINGULAR, the current x is kept (upstream takes a random step instead).  Update, a quirk kept:
+ *   r = log(exp(-delta_r) exp(r)), t -= delta_t.  Converged, with iterations = i, when max(max|exp(delta_r) - I| / rotation_epsilon,
+ *   max|delta_t| / transformation_epsilon) < 1.  After max_iterations steps without that: converged = 0, iterations = max_iterations - 1
+ *   (upstream's nr_iterations_ = i), stop = MULLS_GICP_STOP_MAX_ITERATIONS.
+ * Results  T = (exp(r), t) * guess in double.  fitness and code are mulls_ndt's fitness pass (the same kernels): the mean over the cropped source of
+ *   the float squared distance from float(a') under the final x to the nearest cropped target point; code = fitness > fitness_score_thre ? -3 : 1.
+ *   loss = the last evaluation's e . e sum, n_corr its count.
+ * Not built: plain GICP (using_voxel_gicp = false); FastVGICP's DIRECT7 / DIRECT27, MULTIPLICATIVE / ADDITIVE_WEIGHTED voxels and the other
+ *   regularisations (omp_gicp cannot select them); keeping a cloud's covariances between calls; pcl_icp. */
+enum mulls_gicp_stop
+{
+	MULLS_GICP_STOP_NONE = 0, /* no registration ran */
+	MULLS_GICP_STOP_CONVERGED = 1,
+	MULLS_GICP_STOP_MAX_ITERATIONS = 2,
+	MULLS_GICP_STOP_SINGULAR = 3
+};
+#define MULLS_GICP_BATCH_DEFAULT_SCRATCH_BYTES (1024ull << 20) /* a value chosen without a measurement */
+typedef struct mulls_gicp_params
+{
+	float voxel_resolution;			   /* 1.0 */
+	int32_t k_correspondences;		   /* 20; 3 .. 32 */
+	int32_t max_iterations;			   /* 64 */
+	int32_t apply_intersection_filter; /* 0 */
+	double rotation_epsilon;		   /* 2e-3 */
+	double transformation_epsilon;	   /* 5e-4 */
+	float fitness_score_thre;		   /* 10.0 */
+	int32_t using_voxel_gicp;		   /* 1; 0: MULLS_E_UNSUPPORTED */
+	float start_rotvec[3];			   /* 3 x 0.005773503f: the rotation vector the loop starts from */
+	int32_t reserved;
+	uint64_t scratch_limit_bytes; /* of one sub-batch of mulls_gicp_batch; 0: MULLS_GICP_BATCH_DEFAULT_SCRATCH_BYTES */
+} mulls_gicp_params;
+typedef mulls_ndt_problem mulls_gicp_problem; /* tgt, src, tgt_bound, src_bound, init_guess */
+typedef struct mulls_gicp_result
+{
+	int32_t code; /* 1 or -3 */
+	int32_t iterations, converged, stop; /* enum mulls_gicp_stop */
+	uint32_t n_src, n_tgt; /* after the crop */
+	uint32_t n_voxels, n_corr; /* occupied voxels; source points with a voxel at the last evaluation */
+	double T[16];			   /* column-major */
+	double fitness, loss;
+} mulls_gicp_result;
+void mulls_gicp_default_params(mulls_gicp_params *p);
+/* MULLS_OK, or MULLS_E_INVALID (an empty cloud, a NULL pointer, a non-finite coordinate, bound or guess, a bad stride or parameter), MULLS_E_UNSUPPORTED
+ * (using_voxel_gicp = 0, a coordinate beyond 2^20 voxels, a cloud above MULLS_NDT_MAX_POINTS); the results are then not written. */
+int mulls_gicp(mulls_ctx *ctx, const mulls_gicp_problem *problem, const mulls_gicp_params *params, mulls_gicp_result *result);
+/* the bits of n_problems mulls_gicp calls.  The covariances and voxel maps of a sub-batch are built in one launch set; then its problems run in lock
+ * step: a tick is one evaluation launch over the problems that still run, one launch that solves and updates every problem, and one 4-byte readback;
+ * at most max_iterations ticks.  Sub-batches are sized by params->scratch_limit_bytes; a problem larger than the limit runs alone.  n_problems = 0: MULLS_OK. */
+int mulls_gicp_batch(mulls_ctx *ctx, const mulls_gicp_problem *problems, uint32_t n_problems, const mulls_gicp_params *params, mulls_gicp_result *results);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

@@ -518,6 +518,42 @@ def ndt_params(**kw):
     return p
 
 
+class GicpParams(C.Structure):
+    """mulls_gicp_params"""
+
+    _fields_ = [("voxel_resolution", C.c_float), ("k_correspondences", C.c_int32), ("max_iterations", C.c_int32), ("apply_intersection_filter", C.c_int32),
+                ("rotation_epsilon", C.c_double), ("transformation_epsilon", C.c_double), ("fitness_score_thre", C.c_float), ("using_voxel_gicp", C.c_int32),
+                ("start_rotvec", C.c_float * 3), ("reserved", C.c_int32), ("scratch_limit_bytes", C.c_uint64)]
+
+
+GicpProblem = NdtProblem  # mulls_gicp_problem is mulls_ndt_problem
+
+
+class GicpResult(C.Structure):
+    """mulls_gicp_result"""
+
+    _fields_ = [("code", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("stop", C.c_int32), ("n_src", C.c_uint32), ("n_tgt", C.c_uint32),
+                ("n_voxels", C.c_uint32), ("n_corr", C.c_uint32), ("T", C.c_double * 16), ("fitness", C.c_double), ("loss", C.c_double)]
+
+
+GICP_STOP_NONE, GICP_STOP_CONVERGED, GICP_STOP_MAX_ITERATIONS, GICP_STOP_SINGULAR = range(4)  # enum mulls_gicp_stop
+
+
+def gicp_params(**kw):
+    """mulls_gicp_default_params' values, then the keyword arguments (start_rotvec: three numbers)"""
+    p = GicpParams()
+    p.voxel_resolution, p.k_correspondences, p.max_iterations, p.apply_intersection_filter = 1.0, 20, 64, 0
+    p.rotation_epsilon, p.transformation_epsilon, p.fitness_score_thre, p.using_voxel_gicp = 2e-3, 5e-4, 10.0, 1
+    p.start_rotvec[:] = [0.005773503] * 3
+    for k, v in kw.items():
+        getattr(p, k)
+        if k == "start_rotvec":
+            p.start_rotvec[:] = [float(x) for x in v]
+        else:
+            setattr(p, k, v)
+    return p
+
+
 class NmsParams(C.Structure):
     """mulls_nms_params: non_max_suppress' radius (cfilter.hpp:1183) and which path runs it"""
 

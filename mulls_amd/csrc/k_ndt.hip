@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ndt_launch.h"
+#include "ndt_tree.h"
 
 namespace
 {
@@ -429,27 +430,6 @@ __global__ void __launch_bounds__(256) k_ndt_eval(const NdtDesc *__restrict__ de
 		partial[(uint32_t)k * MULLS_NDT_TREE + lane] = acc[k];
 }
 
-// the pairwise tree over MULLS_NDT_TREE partials held as r[16] per thread of a 256-thread workgroup (r[m] = partial[t + 256 m]); the sum in every thread
-__device__ inline double tree_of_partials(double *r, double *s_p)
-{
-	const uint32_t t = threadIdx.x;
-#pragma unroll
-	for (int h = 8; h >= 1; h >>= 1) // the levels w = 2048 .. 256: partner l + w of l = t + 256 m is held by the same thread
-#pragma unroll
-		for (int m = 0; m < h; m++)
-			r[m] += r[m + h];
-	__syncthreads();
-	s_p[t] = r[0];
-	__syncthreads();
-	for (uint32_t w = 128; w >= 1; w >>= 1)
-	{
-		if (t < w)
-			s_p[t] += s_p[t + w];
-		__syncthreads();
-	}
-	return s_p[0];
-}
-
 __global__ void __launch_bounds__(256) k_ndt_decide(const NdtDesc *__restrict__ desc, unsigned char *arena, NdtOpts opt, NdtRec *rec, uint32_t *running)
 {
 	__shared__ double s_p[256];
@@ -495,7 +475,7 @@ __global__ void __launch_bounds__(256) k_ndt_decide(const NdtDesc *__restrict__ 
 }
 
 // the float squared distance from every cropped source point under T(p) to its nearest cropped target point: tiles of the target through LDS
-__global__ void __launch_bounds__(256) k_ndt_nearest(const NdtDesc *__restrict__ desc, unsigned char *arena, NdtRec *rec)
+__global__ void __launch_bounds__(256) k_ndt_nearest(const NdtDesc *__restrict__ desc, unsigned char *arena, NdtRec *rec, const double *__restrict__ frames)
 {
 	__shared__ ndt::Frame s_F;
 	__shared__ float s_t[256][3];
@@ -507,7 +487,12 @@ __global__ void __launch_bounds__(256) k_ndt_nearest(const NdtDesc *__restrict__
 	const uint32_t ns = R.n_src < D.n_src_in ? R.n_src : D.n_src_in, nt = R.n_tgt < D.n_tgt_in ? R.n_tgt : D.n_tgt_in;
 	if (blockIdx.x * 256u >= ns)
 		return;
-	if (threadIdx.x == 0)
+	if (frames) // (mulls_gicp: the rotation and translation as given, 12 doubles a problem)
+	{
+		if (threadIdx.x < 12)
+			reinterpret_cast<double *>(&s_F)[threadIdx.x] = frames[12u * p + threadIdx.x];
+	}
+	else if (threadIdx.x == 0)
 		ndt::make_frame(R.S.p, &s_F);
 	__syncthreads();
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -600,9 +585,9 @@ hipError_t launch_ndt_decide(hipStream_t st, const NdtDesc *desc, uint32_t P, un
 	hipLaunchKernelGGL(k_ndt_decide, dim3(P), dim3(256), 0, st, desc, arena, opt, rec, running);
 	return hipGetLastError();
 }
-hipError_t launch_ndt_fitness(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, NdtRec *rec)
+hipError_t launch_ndt_fitness(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, NdtRec *rec, const double *frames)
 {
-	hipLaunchKernelGGL(k_ndt_nearest, dim3(blocks_of(n_src_max, 256), P), dim3(256), 0, st, desc, arena, rec);
+	hipLaunchKernelGGL(k_ndt_nearest, dim3(blocks_of(n_src_max, 256), P), dim3(256), 0, st, desc, arena, rec, frames);
 	hipLaunchKernelGGL(k_ndt_fitness, dim3(P), dim3(256), 0, st, desc, arena, rec);
 	return hipGetLastError();
 }

@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "ctx.h"
+#include "ndt_host.h"
 #include "ndt_launch.h"
 
 // a context's scratch of this entry point: one device arena, one pinned host buffer; grow-only
@@ -25,12 +26,9 @@ void mulls_ndt_release(mulls_ctx *ctx)
 	ctx->ndt = nullptr;
 }
 
-namespace
+// what mulls_gicp shares with this file (ndt_host.h): the pre-steps of omp_ndt and omp_gicp are the same text upstream
+namespace ndt_host
 {
-constexpr uint32_t MAX_SUB_BATCH = 4096u; // problems of one sub-batch (one grid dimension of the per-point launches)
-
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
-
 bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
 {
 	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * c.stride))
@@ -59,32 +57,6 @@ bool is_identity(const double *G, double prec)
 				return false;
 		}
 	return true;
-}
-
-struct Plan
-{
-	bool apply_guess = false;
-	size_t bytes = 0;
-	NdtDesc D{};
-};
-
-const char *check_params(const mulls_ndt_params &p)
-{
-	if (!(p.resolution > 0.f) || !std::isfinite(p.resolution))
-		return "resolution is not a positive number";
-	if (p.search_method < MULLS_NDT_KDTREE || p.search_method > MULLS_NDT_DIRECT1)
-		return "an unknown search_method";
-	if (p.max_iterations < 0 || p.max_iterations > 1000 || p.max_step_iterations < 0 || p.max_step_iterations > 1000)
-		return "max_iterations or max_step_iterations outside 0 .. 1000";
-	if (p.min_points_per_voxel < 1)
-		return "min_points_per_voxel below 1";
-	const double v[] = {p.step_size, p.transformation_epsilon, p.outlier_ratio, p.min_covar_eigvalue_mult, (double)p.fitness_score_thre};
-	for (double x : v)
-		if (!(x >= 0.0) || !std::isfinite(x))
-			return "a negative or non-finite step_size, transformation_epsilon, outlier_ratio, min_covar_eigvalue_mult or fitness_score_thre";
-	if (!(p.outlier_ratio > 0.0 && p.outlier_ratio < 1.0))
-		return "outlier_ratio outside (0, 1)";
-	return nullptr;
 }
 
 int check_problem(const mulls_ndt_problem &P, std::string &msg)
@@ -127,6 +99,70 @@ int check_problem(const mulls_ndt_problem &P, std::string &msg)
 			return MULLS_E_INVALID;
 		}
 	return MULLS_OK;
+}
+
+// the coordinates of a cloud, packed to 12 bytes a point, into the arena (a host cloud through the pinned buffer, a device cloud by a strided copy)
+int upload_cloud(mulls_ctx *ctx, const mulls_cloud &c, unsigned char *dst, unsigned char *pinned)
+{
+	hipStream_t st = ctx->stream;
+	if (cloud_on_device(ctx, c))
+		HIPCHK(ctx, hipMemcpy2DAsync(dst, 12, c.pts, c.stride, 12, c.n, hipMemcpyDeviceToDevice, st));
+	else
+	{
+		const unsigned char *src = static_cast<const unsigned char *>(c.pts);
+		for (uint32_t i = 0; i < c.n; i++)
+			std::memcpy(pinned + 12ull * i, src + (size_t)i * c.stride, 12);
+		HIPCHK(ctx, hipMemcpyAsync(dst, pinned, 12ull * c.n, hipMemcpyHostToDevice, st));
+		HIPCHK(ctx, hipStreamSynchronize(st)); // (the pinned buffer is reused)
+	}
+	return MULLS_OK;
+}
+
+// T = Tn * G (column-major 4 x 4, G = NULL: the identity)
+void pose_times_guess(const double *Tn, const double *G, double *T)
+{
+	if (!G)
+	{
+		std::memcpy(T, Tn, 16 * sizeof(double));
+		return;
+	}
+	for (int r = 0; r < 4; r++)
+		for (int c = 0; c < 4; c++)
+			T[r + 4 * c] = ((Tn[r] * G[4 * c] + Tn[r + 4] * G[1 + 4 * c]) + Tn[r + 8] * G[2 + 4 * c]) + Tn[r + 12] * G[3 + 4 * c];
+}
+} // namespace ndt_host
+
+namespace
+{
+using namespace ndt_host;
+constexpr uint32_t MAX_SUB_BATCH = 4096u; // problems of one sub-batch (one grid dimension of the per-point launches)
+
+size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
+
+struct Plan
+{
+	bool apply_guess = false;
+	size_t bytes = 0;
+	NdtDesc D{};
+};
+
+const char *check_params(const mulls_ndt_params &p)
+{
+	if (!(p.resolution > 0.f) || !std::isfinite(p.resolution))
+		return "resolution is not a positive number";
+	if (p.search_method < MULLS_NDT_KDTREE || p.search_method > MULLS_NDT_DIRECT1)
+		return "an unknown search_method";
+	if (p.max_iterations < 0 || p.max_iterations > 1000 || p.max_step_iterations < 0 || p.max_step_iterations > 1000)
+		return "max_iterations or max_step_iterations outside 0 .. 1000";
+	if (p.min_points_per_voxel < 1)
+		return "min_points_per_voxel below 1";
+	const double v[] = {p.step_size, p.transformation_epsilon, p.outlier_ratio, p.min_covar_eigvalue_mult, (double)p.fitness_score_thre};
+	for (double x : v)
+		if (!(x >= 0.0) || !std::isfinite(x))
+			return "a negative or non-finite step_size, transformation_epsilon, outlier_ratio, min_covar_eigvalue_mult or fitness_score_thre";
+	if (!(p.outlier_ratio > 0.0 && p.outlier_ratio < 1.0))
+		return "outlier_ratio outside (0, 1)";
+	return nullptr;
 }
 
 void lay_out(Plan &L, const mulls_ndt_problem &P, size_t &off)
@@ -193,21 +229,10 @@ int run_sub_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, std::vector
 	{
 		const mulls_ndt_problem &P = problems[idx[k]];
 		const NdtDesc &D = plans[idx[k]].D;
-		const mulls_cloud *cl[2] = {&P.src, &P.tgt};
-		const uint64_t dst[2] = {D.o_src_in, D.o_tgt_in};
-		for (int c = 0; c < 2; c++)
-		{
-			if (cloud_on_device(ctx, *cl[c]))
-				HIPCHK(ctx, hipMemcpy2DAsync(d + dst[c], 12, cl[c]->pts, cl[c]->stride, 12, cl[c]->n, hipMemcpyDeviceToDevice, st));
-			else
-			{
-				const unsigned char *src = static_cast<const unsigned char *>(cl[c]->pts);
-				for (uint32_t i = 0; i < cl[c]->n; i++)
-					std::memcpy(h + 12ull * i, src + (size_t)i * cl[c]->stride, 12);
-				HIPCHK(ctx, hipMemcpyAsync(d + dst[c], h, 12ull * cl[c]->n, hipMemcpyHostToDevice, st));
-				HIPCHK(ctx, hipStreamSynchronize(st)); // (the pinned buffer is reused)
-			}
-		}
+		if (int rc = ndt_host::upload_cloud(ctx, P.src, d + D.o_src_in, h))
+			return rc;
+		if (int rc = ndt_host::upload_cloud(ctx, P.tgt, d + D.o_tgt_in, h))
+			return rc;
 		HIPCHK(ctx, hipMemsetAsync(d + D.o_keys, 0xff, 4ull * D.table_size, st));
 		HIPCHK(ctx, hipMemsetAsync(d + D.o_count, 0, D.o_leaves - D.o_count, st)); // count, start, fill
 	}
@@ -239,7 +264,7 @@ int run_sub_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, std::vector
 		if (*h_running == 0)
 			break;
 	}
-	HIPCHK(ctx, launch_ndt_fitness(st, desc, B, ns_max, d, rec));
+	HIPCHK(ctx, launch_ndt_fitness(st, desc, B, ns_max, d, rec, nullptr));
 	std::vector<NdtRec> recs(B);
 	HIPCHK(ctx, hipMemcpyAsync(h, rec, sizeof(NdtRec) * (size_t)B, hipMemcpyDeviceToHost, st));
 	HIPCHK(ctx, hipStreamSynchronize(st));
@@ -280,15 +305,7 @@ int run_sub_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, std::vector
 			Tn[r + 12] = F.t[r];
 		}
 		Tn[15] = 1.0;
-		if (!L.apply_guess)
-			std::memcpy(res.T, Tn, sizeof(Tn));
-		else
-			for (int r = 0; r < 4; r++)
-				for (int c = 0; c < 4; c++)
-				{
-					const double *G = P.init_guess;
-					res.T[r + 4 * c] = ((Tn[r] * G[4 * c] + Tn[r + 4] * G[1 + 4 * c]) + Tn[r + 8] * G[2 + 4 * c]) + Tn[r + 12] * G[3 + 4 * c];
-				}
+		ndt_host::pose_times_guess(Tn, L.apply_guess ? P.init_guess : nullptr, res.T);
 	}
 	return MULLS_OK;
 }

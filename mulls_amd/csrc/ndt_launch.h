@@ -56,4 +56,5 @@ hipError_t launch_ndt_leaves(hipStream_t st, const NdtDesc *desc, uint32_t P, ui
 hipError_t launch_ndt_begin(hipStream_t st, uint32_t P, NdtRec *rec);
 hipError_t launch_ndt_eval(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, const NdtRec *rec);
 hipError_t launch_ndt_decide(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, NdtRec *rec, uint32_t *running);
-hipError_t launch_ndt_fitness(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, NdtRec *rec);
+// frames: NULL (the pose is T(rec[p].S.p)), or 12 doubles a problem: the rotation row-major, the translation (mulls_gicp)
+hipError_t launch_ndt_fitness(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, NdtRec *rec, const double *frames);

@@ -57,9 +57,10 @@ def flags(argv=None):
     p.add_argument("--reciprocal_corr_on", type=boolean, default=False)
     p.add_argument("--fixed_num_corr_on", type=boolean, default=False)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--baseline_reg_method", choices=("", "ndt"), default="",
-                   help="ndt: CRegistration::omp_ndt (mulls_ndt) on the two pc_down clouds in place of mm_lls_icp, as test/mulls_slam.cpp's omp_ndt baseline")
-    p.add_argument("--reg_voxel_size", type=float, default=1.0, help="the NDT leaf size (test/mulls_slam.cpp's reg_voxel_size)")
+    p.add_argument("--baseline_reg_method", choices=("", "ndt", "gicp"), default="",
+                   help="ndt: CRegistration::omp_ndt (mulls_ndt), gicp: CRegistration::omp_gicp with voxelised GICP (mulls_gicp), on the two pc_down clouds "
+                        "in place of mm_lls_icp, as test/mulls_slam.cpp's baselines")
+    p.add_argument("--reg_voxel_size", type=float, default=1.0, help="the NDT leaf size or the VGICP voxel size (test/mulls_slam.cpp's reg_voxel_size)")
     a, _ = p.parse_known_args(argv)  # glog / viewer flags of the reference's script are accepted and ignored
     return a
 
@@ -124,7 +125,7 @@ def global_registration(ctx, tgt_kpts, src_kpts, F):
 
 
 class NdtOutcome:
-    """mulls_ndt_result with the three members main() reads of an abi.Result"""
+    """mulls_ndt_result or mulls_gicp_result with the three members main() reads of an abi.Result"""
 
     def __init__(self, r):
         self.ndt, self.code, self.iters = r, r.code, r.iterations
@@ -158,6 +159,13 @@ def register(ctx, scan1, scan2, F):
         r = ctx.ndt((p1, p2)[2 - source], (p1, p2)[source - 1], scan_bound(abi.as_points(tgt_scan)), scan_bound(abi.as_points(src_scan)), init_mat,
                     abi.ndt_params(resolution=F.reg_voxel_size))
         print("omp_ndt: %d iterations, %d evaluations, fitness %.4f, %d of %d leaves used" % (r.iterations, r.evaluations, r.fitness, r.n_leaves_used, r.n_leaves))
+        return NdtOutcome(r), source, (p1, p2)[source - 1]
+    if F.baseline_reg_method == "gicp":
+        # omp_gicp(reg_con, max_iter, thre, voxel_gicp_on = true, reg_voxel_size, init_mat) (test/mulls_slam.cpp:638): the same clouds and bounds
+        tgt_scan, src_scan = (scan1, scan2) if source == 2 else (scan2, scan1)
+        r = ctx.gicp((p1, p2)[2 - source], (p1, p2)[source - 1], scan_bound(abi.as_points(tgt_scan)), scan_bound(abi.as_points(src_scan)), init_mat,
+                     abi.gicp_params(voxel_resolution=F.reg_voxel_size))
+        print("omp_gicp: %d iterations, stop %d, fitness %.4f, %d voxels, %d of %d source points with a voxel" % (r.iterations + 1, r.stop, r.fitness, r.n_voxels, r.n_corr, r.n_src))
         return NdtOutcome(r), source, (p1, p2)[source - 1]
     pair = abi.PairData([abi.points_of(t) for t in tgt_full], [abi.points_of(s) for s in src_down],
                         init_guess=init_mat, tgt_bound=scan_bound(abi.as_points(scan1 if source == 2 else scan2)) if len(scan1) and len(scan2) else None)
