@@ -1217,47 +1217,34 @@ inline uint32_t merged_map_add(mulls_mapper *mapper, const typename pcl::PointCl
 	return n_out;
 }
 
-// CFilter<PointT>::extract_semantic_pts (include/common/cfilter.hpp:2295-2413), verbatim signature: the whole chain in one device call
-// (mulls_extract_features).  The binding is one early return at the top of the member function:
-//     #ifdef MULLS_USE_HIP
-//         return lo::hip::extract_semantic_pts<PointT>(in_block, vf_downsample_resolution, gf_grid_resolution, ...);
-//     #endif
-// semantic_assisted (deprecated upstream, off in every shipped configuration; round 5): the pre-filter filter_with_dynamic_object_mask_pre (cfilter.hpp:2487-2504 —
-// Semantic-KITTI labels in the curvature field: moving objects, labels >= 250, and outliers, label 1, leave pc_raw) runs here on the host, in place on pc_raw as
-// upstream does, INSTEAD of the scanner filter (upstream's `else if`, :2331-2345); the post-filter filter_with_semantic_mask(in_block) is called with its default mask
-// "000000" (:2396), with which it touches nothing.  apply_roi_filtering is dead code upstream ("#if 0") and ignored here too.  use_adpative_parameters runs upstream's update (:2416-2444) on the host; where upstream would divide by zero (no facade and
-// no pillar point left) this throws instead.
-// One side effect is not reproduced: upstream's ground filter writes (0,0,1) normals and data[3] heights into the points of pc_down (= pc_raw)
-// it classifies; here pc_raw / pc_down / pc_sketch keep the scan's records (the clouds handed out carry those values).
-template <typename PointT>
-inline bool extract_semantic_pts(cloudblock_Ptr in_block, float vf_downsample_resolution, float gf_grid_resolution, float gf_max_grid_height_diff,
+// the pieces lo::hip::extract_semantic_pts and lo::hip::extract_semantic_pts_batch share
+namespace detail
+{
+struct ExtractSetup
+{
+	mulls_extract_params X;
+	bool scanner_stage, voxels;
+};
+// extract_semantic_pts' arguments as mulls_extract_params (two seeds of the feature stage's sequence are taken)
+inline ExtractSetup extract_setup(float vf_downsample_resolution, float gf_grid_resolution, float gf_max_grid_height_diff,
 								 float gf_neighbor_height_diff, float gf_max_ground_height, int &gf_down_rate_ground, int &gf_downsample_rate_nonground,
 								 float pca_neighbor_radius, int pca_neighbor_k, float edge_thre, float planar_thre, float curvature_thre, float edge_thre_down,
-								 float planar_thre_down, bool use_distance_adaptive_pca = false, int distance_inverse_sampling_method = 0,
-								 float standard_distance = 15.0, int estimate_ground_normal_method = 3, float normal_estimation_radius = 2.0,
-								 bool use_adpative_parameters = false, bool apply_scanner_filter = false, bool extract_curb_or_not = false,
-								 int extract_vertex_points_method = 2, int gf_grid_pt_num_thre = 8, int gf_reliable_neighbor_grid_thre = 0,
-								 int gf_down_down_rate_ground = 2, int pca_neighbor_k_min = 8, int pca_down_rate = 1, float intensity_thre = FLT_MAX,
-								 float linear_vertical_sin_high_thre = 0.94, float linear_vertical_sin_low_thre = 0.17, float planar_vertical_sin_high_thre = 0.98,
-								 float planar_vertical_sin_low_thre = 0.34, bool sharpen_with_nms_on = true, bool fixed_num_downsampling = false,
-								 int ground_down_fixed_num = 500, int pillar_down_fixed_num = 200, int facade_down_fixed_num = 800, int beam_down_fixed_num = 200,
-								 int roof_down_fixed_num = 200, int unground_down_fixed_num = 20000, float beam_height_max = FLT_MAX, float roof_height_min = 0.0,
-								 float approx_scanner_height = 2.0, float underground_thre = -7.0, float feature_pts_ratio_guess = 0.3, bool semantic_assisted = false,
-								 bool apply_roi_filtering = false, float roi_min_y = 0.0, float roi_max_y = 0.0)
+								 float planar_thre_down, bool use_distance_adaptive_pca, int distance_inverse_sampling_method,
+								 float standard_distance, int estimate_ground_normal_method, float normal_estimation_radius,
+								 bool use_adpative_parameters, bool apply_scanner_filter, bool extract_curb_or_not,
+								 int extract_vertex_points_method, int gf_grid_pt_num_thre, int gf_reliable_neighbor_grid_thre,
+								 int gf_down_down_rate_ground, int pca_neighbor_k_min, int pca_down_rate, float intensity_thre,
+								 float linear_vertical_sin_high_thre, float linear_vertical_sin_low_thre, float planar_vertical_sin_high_thre,
+								 float planar_vertical_sin_low_thre, bool sharpen_with_nms_on, bool fixed_num_downsampling,
+								 int ground_down_fixed_num, int pillar_down_fixed_num, int facade_down_fixed_num, int beam_down_fixed_num,
+								 int roof_down_fixed_num, int unground_down_fixed_num, float beam_height_max, float roof_height_min,
+								 float approx_scanner_height, float underground_thre, float feature_pts_ratio_guess, bool semantic_assisted,
+								 bool apply_roi_filtering, float roi_min_y, float roi_max_y)
 {
-	(void)extract_curb_or_not, (void)apply_roi_filtering, (void)roi_min_y, (void)roi_max_y;
-	if (semantic_assisted)
-	{
-		// filter_with_dynamic_object_mask_pre(in_block->pc_raw), cfilter.hpp:2487-2504: the float comparisons as written there
-		typename pcl::PointCloud<PointT>::Ptr kept(new pcl::PointCloud<PointT>());
-		for (size_t i = 0; i < in_block->pc_raw->points.size(); i++)
-			if (in_block->pc_raw->points[i].curvature < 250 && in_block->pc_raw->points[i].curvature != 1)
-				kept->points.push_back(in_block->pc_raw->points[i]);
-		kept->points.swap(in_block->pc_raw->points);
-	}
+	(void)extract_curb_or_not, (void)apply_roi_filtering, (void)roi_min_y, (void)roi_max_y, (void)use_adpative_parameters;
 	const bool scanner_stage = apply_scanner_filter && !semantic_assisted; // upstream: `if (semantic_assisted) ... else if (apply_scanner_filter) scanner_filter(...)`
-	mulls_ctx *ctx = thread_context();
-	mulls_extract_params X;
+	ExtractSetup S;
+	mulls_extract_params &X = S.X;
 	mulls_extract_default_params(&X);
 	mulls_ground_params &G = X.ground;
 	G.min_grid_pt_num = gf_grid_pt_num_thre;
@@ -1303,7 +1290,86 @@ inline bool extract_semantic_pts(cloudblock_Ptr in_block, float vf_downsample_re
 	X.z_min = -approx_scanner_height - 4.0;
 	X.z_min_min = -approx_scanner_height + underground_thre;
 	X.vf_downsample_resolution = vf_downsample_resolution;
-	const bool voxels = !(vf_downsample_resolution < 0.001);
+	S.scanner_stage = scanner_stage;
+	S.voxels = !(vf_downsample_resolution < 0.001);
+	return S;
+}
+// filter_with_dynamic_object_mask_pre(in_block->pc_raw), cfilter.hpp:2487-2504: the float comparisons as written there
+template <typename PointT>
+inline void extract_semantic_prefilter(cloudblock_t &blk)
+{
+	typename pcl::PointCloud<PointT>::Ptr kept(new pcl::PointCloud<PointT>());
+	for (size_t i = 0; i < blk.pc_raw->points.size(); i++)
+		if (blk.pc_raw->points[i].curvature < 250 && blk.pc_raw->points[i].curvature != 1)
+			kept->points.push_back(blk.pc_raw->points[i]);
+	kept->points.swap(blk.pc_raw->points);
+}
+// pc_sketch from pc_down: random_downsample(pc_down, pc_sketch, size / 1024 + 1) (:2351, :713-728)
+inline void extract_sketch(cloudblock_t &b)
+{
+	const int ratio = (int)(b.pc_down->points.size() / 1024 + 1);
+	if (ratio > 1)
+	{
+		b.pc_sketch->points.clear();
+		for (size_t i = 0; i < b.pc_down->points.size(); i++)
+			if ((int)i % ratio == 0)
+				b.pc_sketch->points.push_back(b.pc_down->points[i]);
+	}
+}
+// what extract_semantic_pts does on the host once the clouds are in the block: the feature count and the adaptive parameter update, with its exception
+inline void extract_finish(cloudblock_t &b, bool use_adpative_parameters, int &gf_downsample_rate_nonground)
+{
+	b.down_feature_point_num = b.pc_ground_down->points.size() + b.pc_pillar_down->points.size() + b.pc_beam_down->points.size() + b.pc_facade_down->points.size() +
+							   b.pc_roof_down->points.size() + b.pc_vertex->points.size(); // :2397-2398
+	if (use_adpative_parameters)
+	{
+		// update_parameters_self_adaptive (:2416-2444): the one live rule lowers the non-ground down-sampling rate when few facade / pillar points came out
+		const int non_ground_num_min_expected = 200;
+		const int non_ground_feature_num = (int)b.pc_facade_down->points.size() + (int)b.pc_pillar_down->points.size();
+		if (non_ground_feature_num < non_ground_num_min_expected)
+		{
+			if (non_ground_feature_num == 0)
+				throw std::runtime_error("lo::hip::extract_semantic_pts: adaptive parameters with no facade / pillar point (upstream divides by zero here)");
+			gf_downsample_rate_nonground = std::max(1, gf_downsample_rate_nonground - non_ground_num_min_expected / non_ground_feature_num);
+		}
+	}
+}
+} // namespace detail
+
+// CFilter<PointT>::extract_semantic_pts (include/common/cfilter.hpp:2295-2413), verbatim signature: the whole chain in one device call
+// (mulls_extract_features).  The binding is one early return at the top of the member function:
+//     #ifdef MULLS_USE_HIP
+//         return lo::hip::extract_semantic_pts<PointT>(in_block, vf_downsample_resolution, gf_grid_resolution, ...);
+//     #endif
+// semantic_assisted (deprecated upstream, off in every shipped configuration; round 5): the pre-filter filter_with_dynamic_object_mask_pre (cfilter.hpp:2487-2504 —
+// Semantic-KITTI labels in the curvature field: moving objects, labels >= 250, and outliers, label 1, leave pc_raw) runs here on the host, in place on pc_raw as
+// upstream does, INSTEAD of the scanner filter (upstream's `else if`, :2331-2345); the post-filter filter_with_semantic_mask(in_block) is called with its default mask
+// "000000" (:2396), with which it touches nothing.  apply_roi_filtering is dead code upstream ("#if 0") and ignored here too.  use_adpative_parameters runs upstream's update (:2416-2444) on the host; where upstream would divide by zero (no facade and
+// no pillar point left) this throws instead.
+// One side effect is not reproduced: upstream's ground filter writes (0,0,1) normals and data[3] heights into the points of pc_down (= pc_raw)
+// it classifies; here pc_raw / pc_down / pc_sketch keep the scan's records (the clouds handed out carry those values).
+template <typename PointT>
+inline bool extract_semantic_pts(cloudblock_Ptr in_block, float vf_downsample_resolution, float gf_grid_resolution, float gf_max_grid_height_diff,
+								 float gf_neighbor_height_diff, float gf_max_ground_height, int &gf_down_rate_ground, int &gf_downsample_rate_nonground,
+								 float pca_neighbor_radius, int pca_neighbor_k, float edge_thre, float planar_thre, float curvature_thre, float edge_thre_down,
+								 float planar_thre_down, bool use_distance_adaptive_pca = false, int distance_inverse_sampling_method = 0,
+								 float standard_distance = 15.0, int estimate_ground_normal_method = 3, float normal_estimation_radius = 2.0,
+								 bool use_adpative_parameters = false, bool apply_scanner_filter = false, bool extract_curb_or_not = false,
+								 int extract_vertex_points_method = 2, int gf_grid_pt_num_thre = 8, int gf_reliable_neighbor_grid_thre = 0,
+								 int gf_down_down_rate_ground = 2, int pca_neighbor_k_min = 8, int pca_down_rate = 1, float intensity_thre = FLT_MAX,
+								 float linear_vertical_sin_high_thre = 0.94, float linear_vertical_sin_low_thre = 0.17, float planar_vertical_sin_high_thre = 0.98,
+								 float planar_vertical_sin_low_thre = 0.34, bool sharpen_with_nms_on = true, bool fixed_num_downsampling = false,
+								 int ground_down_fixed_num = 500, int pillar_down_fixed_num = 200, int facade_down_fixed_num = 800, int beam_down_fixed_num = 200,
+								 int roof_down_fixed_num = 200, int unground_down_fixed_num = 20000, float beam_height_max = FLT_MAX, float roof_height_min = 0.0,
+								 float approx_scanner_height = 2.0, float underground_thre = -7.0, float feature_pts_ratio_guess = 0.3, bool semantic_assisted = false,
+								 bool apply_roi_filtering = false, float roi_min_y = 0.0, float roi_max_y = 0.0)
+{
+	if (semantic_assisted)
+		detail::extract_semantic_prefilter<PointT>(*in_block);
+	const detail::ExtractSetup S = detail::extract_setup(vf_downsample_resolution, gf_grid_resolution, gf_max_grid_height_diff, gf_neighbor_height_diff, gf_max_ground_height, gf_down_rate_ground, gf_downsample_rate_nonground, pca_neighbor_radius, pca_neighbor_k, edge_thre, planar_thre, curvature_thre, edge_thre_down, planar_thre_down, use_distance_adaptive_pca, distance_inverse_sampling_method, standard_distance, estimate_ground_normal_method, normal_estimation_radius, use_adpative_parameters, apply_scanner_filter, extract_curb_or_not, extract_vertex_points_method, gf_grid_pt_num_thre, gf_reliable_neighbor_grid_thre, gf_down_down_rate_ground, pca_neighbor_k_min, pca_down_rate, intensity_thre, linear_vertical_sin_high_thre, linear_vertical_sin_low_thre, planar_vertical_sin_high_thre, planar_vertical_sin_low_thre, sharpen_with_nms_on, fixed_num_downsampling, ground_down_fixed_num, pillar_down_fixed_num, facade_down_fixed_num, beam_down_fixed_num, roof_down_fixed_num, unground_down_fixed_num, beam_height_max, roof_height_min, approx_scanner_height, underground_thre, feature_pts_ratio_guess, semantic_assisted, apply_roi_filtering, roi_min_y, roi_max_y);
+	const mulls_extract_params &X = S.X;
+	const bool scanner_stage = S.scanner_stage, voxels = S.voxels;
+	mulls_ctx *ctx = thread_context();
 
 	cloudblock_t &b = *in_block;
 	const mulls_cloud in = borrow(b.pc_raw);
@@ -1326,37 +1392,116 @@ inline bool extract_semantic_pts(cloudblock_Ptr in_block, float vf_downsample_re
 		take_cloud<PointT>(b.pc_down, raw[MULLS_EX_DOWN], n_out[MULLS_EX_DOWN], true); // `cloud_out->push_back(...)` (:147)
 	else
 		b.pc_down = b.pc_raw; // voxel_downsample below 0.001 m: `cloud_out = cloud_in` (:92)
-	{
-		// random_downsample(pc_down, pc_sketch, size / 1024 + 1) (:2351, :713-728)
-		const int ratio = (int)(b.pc_down->points.size() / 1024 + 1);
-		if (ratio > 1)
-		{
-			b.pc_sketch->points.clear();
-			for (size_t i = 0; i < b.pc_down->points.size(); i++)
-				if ((int)i % ratio == 0)
-					b.pc_sketch->points.push_back(b.pc_down->points[i]);
-		}
-	}
+	detail::extract_sketch(b);
 	take_cloud<PointT>(b.pc_ground, raw[MULLS_EX_GROUND], n_out[MULLS_EX_GROUND], true);
 	take_cloud<PointT>(b.pc_ground_down, raw[MULLS_EX_GROUND_DOWN], n_out[MULLS_EX_GROUND_DOWN], true);
 	take_cloud<PointT>(b.pc_unground, raw[MULLS_EX_UNGROUND], n_out[MULLS_EX_UNGROUND], false); // the filter appends to an empty cloud, the classification works on it in place
 	typename pcl::PointCloud<PointT>::Ptr *dst[9] = {&b.pc_pillar, &b.pc_beam, &b.pc_facade, &b.pc_roof, &b.pc_pillar_down, &b.pc_beam_down, &b.pc_facade_down, &b.pc_roof_down, &b.pc_vertex};
 	for (int k = 0; k < 9; k++)
 		take_cloud<PointT>(*dst[k], raw[MULLS_EX_PILLAR + k], n_out[MULLS_EX_PILLAR + k], true);
-	b.down_feature_point_num = b.pc_ground_down->points.size() + b.pc_pillar_down->points.size() + b.pc_beam_down->points.size() + b.pc_facade_down->points.size() +
-							   b.pc_roof_down->points.size() + b.pc_vertex->points.size(); // :2397-2398
-	if (use_adpative_parameters)
+	detail::extract_finish(b, use_adpative_parameters, gf_downsample_rate_nonground);
+	return true;
+}
+
+// extract_semantic_pts for many blocks in one device call (mulls_extract_features_batch): every block's pc_raw is one scan, all scans take the same arguments
+// (one pair of seeds: every scan's fixed-number selections are those of a single call with these seeds), and every block leaves as extract_semantic_pts leaves
+// it — the clouds come back from the device-resident feature blocks, one download per cloud, and the host-side remainder is the single call's
+// (detail::extract_sketch, detail::extract_finish: the adaptive update lowers gf_downsample_rate_nonground once per block, in order, as a loop of single calls
+// would).  A scan the library refuses throws, naming it, after the others' blocks have been filled.  With the scanner filter on, pc_raw is filtered here on the
+// host (cfilter.hpp:914-929, the comparisons as written there): a feature block does not keep pc_raw, and the size is checked against the device's.
+template <typename PointT>
+inline bool extract_semantic_pts_batch(std::vector<cloudblock_Ptr> &in_blocks, float vf_downsample_resolution, float gf_grid_resolution, float gf_max_grid_height_diff,
+								 float gf_neighbor_height_diff, float gf_max_ground_height, int &gf_down_rate_ground, int &gf_downsample_rate_nonground,
+								 float pca_neighbor_radius, int pca_neighbor_k, float edge_thre, float planar_thre, float curvature_thre, float edge_thre_down,
+								 float planar_thre_down, bool use_distance_adaptive_pca = false, int distance_inverse_sampling_method = 0,
+								 float standard_distance = 15.0, int estimate_ground_normal_method = 3, float normal_estimation_radius = 2.0,
+								 bool use_adpative_parameters = false, bool apply_scanner_filter = false, bool extract_curb_or_not = false,
+								 int extract_vertex_points_method = 2, int gf_grid_pt_num_thre = 8, int gf_reliable_neighbor_grid_thre = 0,
+								 int gf_down_down_rate_ground = 2, int pca_neighbor_k_min = 8, int pca_down_rate = 1, float intensity_thre = FLT_MAX,
+								 float linear_vertical_sin_high_thre = 0.94, float linear_vertical_sin_low_thre = 0.17, float planar_vertical_sin_high_thre = 0.98,
+								 float planar_vertical_sin_low_thre = 0.34, bool sharpen_with_nms_on = true, bool fixed_num_downsampling = false,
+								 int ground_down_fixed_num = 500, int pillar_down_fixed_num = 200, int facade_down_fixed_num = 800, int beam_down_fixed_num = 200,
+								 int roof_down_fixed_num = 200, int unground_down_fixed_num = 20000, float beam_height_max = FLT_MAX, float roof_height_min = 0.0,
+								 float approx_scanner_height = 2.0, float underground_thre = -7.0, float feature_pts_ratio_guess = 0.3, bool semantic_assisted = false,
+								 bool apply_roi_filtering = false, float roi_min_y = 0.0, float roi_max_y = 0.0)
+{
+	static_assert(sizeof(PointT) == MULLS_POINT_BYTES, "the feature stage expects 48-byte pcl::PointXYZINormal records");
+	if (semantic_assisted)
+		for (cloudblock_Ptr &blk : in_blocks)
+			detail::extract_semantic_prefilter<PointT>(*blk);
+	const detail::ExtractSetup S = detail::extract_setup(vf_downsample_resolution, gf_grid_resolution, gf_max_grid_height_diff, gf_neighbor_height_diff, gf_max_ground_height, gf_down_rate_ground, gf_downsample_rate_nonground, pca_neighbor_radius, pca_neighbor_k, edge_thre, planar_thre, curvature_thre, edge_thre_down, planar_thre_down, use_distance_adaptive_pca, distance_inverse_sampling_method, standard_distance, estimate_ground_normal_method, normal_estimation_radius, use_adpative_parameters, apply_scanner_filter, extract_curb_or_not, extract_vertex_points_method, gf_grid_pt_num_thre, gf_reliable_neighbor_grid_thre, gf_down_down_rate_ground, pca_neighbor_k_min, pca_down_rate, intensity_thre, linear_vertical_sin_high_thre, linear_vertical_sin_low_thre, planar_vertical_sin_high_thre, planar_vertical_sin_low_thre, sharpen_with_nms_on, fixed_num_downsampling, ground_down_fixed_num, pillar_down_fixed_num, facade_down_fixed_num, beam_down_fixed_num, roof_down_fixed_num, unground_down_fixed_num, beam_height_max, roof_height_min, approx_scanner_height, underground_thre, feature_pts_ratio_guess, semantic_assisted, apply_roi_filtering, roi_min_y, roi_max_y);
+	mulls_ctx *ctx = thread_context();
+	const uint32_t count = static_cast<uint32_t>(in_blocks.size());
+	std::vector<mulls_cloud> scans(count);
+	std::vector<mulls_block *> dev(count, nullptr);
+	std::vector<mulls_extract_batch_result> results(count);
+	struct Release
 	{
-		// update_parameters_self_adaptive (:2416-2444): the one live rule lowers the non-ground down-sampling rate when few facade / pillar points came out
-		const int non_ground_num_min_expected = 200;
-		const int non_ground_feature_num = (int)b.pc_facade_down->points.size() + (int)b.pc_pillar_down->points.size();
-		if (non_ground_feature_num < non_ground_num_min_expected)
+		mulls_ctx *ctx;
+		std::vector<mulls_block *> &dev;
+		~Release()
 		{
-			if (non_ground_feature_num == 0)
-				throw std::runtime_error("lo::hip::extract_semantic_pts: adaptive parameters with no facade / pillar point (upstream divides by zero here)");
-			gf_downsample_rate_nonground = std::max(1, gf_downsample_rate_nonground - non_ground_num_min_expected / non_ground_feature_num);
+			for (mulls_block *d : dev)
+				mulls_block_destroy(ctx, d);
 		}
+	} release{ctx, dev};
+	for (uint32_t k = 0; k < count; k++)
+	{
+		scans[k] = borrow(in_blocks[k]->pc_raw);
+		if (mulls_block_create(ctx, &dev[k]) != MULLS_OK)
+			throw std::runtime_error(std::string("mulls_block_create failed: ") + mulls_last_error(ctx));
 	}
+	const int rc = mulls_extract_features_batch(ctx, scans.data(), count, &S.X, dev.data(), 0, results.data(), nullptr);
+	const std::string why = rc != MULLS_OK ? mulls_last_error(ctx) : "";
+	std::vector<unsigned char> raw;
+	for (uint32_t k = 0; k < count; k++)
+	{
+		if (results[k].status != MULLS_OK)
+			continue;
+		cloudblock_t &b = *in_blocks[k];
+		const uint32_t *n_out = results[k].n_out;
+		if (S.scanner_stage)
+		{
+			typename pcl::PointCloud<PointT>::Ptr kept(new pcl::PointCloud<PointT>());
+			const float self_ring_radius = S.X.self_ring_radius, ghost_radius = S.X.ghost_radius, z_min = S.X.z_min, z_min_min = S.X.z_min_min;
+			for (size_t i = 0; i < b.pc_raw->points.size(); i++)
+			{
+				const PointT &pt = b.pc_raw->points[i];
+				const float dis_square = pt.x * pt.x + pt.y * pt.y;
+				if (dis_square > self_ring_radius * self_ring_radius && pt.z > z_min_min && (dis_square > ghost_radius * ghost_radius || pt.z > z_min))
+					kept->points.push_back(pt);
+			}
+			if (kept->points.size() != n_out[MULLS_EX_RAW])
+				throw std::runtime_error("lo::hip::extract_semantic_pts_batch: the host's scanner filter kept " + std::to_string(kept->points.size()) + " points of block " +
+										 std::to_string(k) + ", the device " + std::to_string(n_out[MULLS_EX_RAW]));
+			kept->points.swap(b.pc_raw->points);
+		}
+		typename pcl::PointCloud<PointT>::Ptr *dst[MULLS_EX_COUNT] = {nullptr, &b.pc_ground, &b.pc_ground_down, &b.pc_unground, &b.pc_pillar, &b.pc_beam, &b.pc_facade, &b.pc_roof,
+																	  &b.pc_pillar_down, &b.pc_beam_down, &b.pc_facade_down, &b.pc_roof_down, &b.pc_vertex, nullptr};
+		if (S.voxels)
+		{
+			// (the single-scan path inside the call does not keep pc_down either: voxel_downsample once more, the same device code on the same records)
+			b.pc_down->points.clear();
+			voxel_downsample<PointT>(b.pc_raw, b.pc_down, S.X.vf_downsample_resolution);
+		}
+		else
+			b.pc_down = b.pc_raw; // voxel_downsample below 0.001 m: `cloud_out = cloud_in` (:92)
+		detail::extract_sketch(b);
+		for (int c = 0; c < MULLS_EX_COUNT; c++)
+		{
+			if (!dst[c])
+				continue;
+			uint32_t got = 0;
+			raw.resize((size_t)n_out[c] * MULLS_POINT_BYTES);
+			const int rd = mulls_block_download(ctx, dev[k], c, raw.data(), n_out[c], &got);
+			if (rd != MULLS_OK || got != n_out[c])
+				throw std::runtime_error(std::string("mulls_block_download failed (") + std::to_string(rd) + "): " + mulls_last_error(ctx));
+			take_cloud<PointT>(*dst[c], raw, got, c != MULLS_EX_UNGROUND); // (the filter appends to an empty pc_unground, the classification works on it in place)
+		}
+		detail::extract_finish(b, use_adpative_parameters, gf_downsample_rate_nonground);
+	}
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_extract_features_batch failed (") + std::to_string(rc) + "): " + why);
 	return true;
 }
 

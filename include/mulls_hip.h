@@ -579,6 +579,39 @@ int mulls_block_cloud(mulls_ctx *ctx, const mulls_block *block, int which, mulls
 /* copy cloud `which` back to the host (48-byte records); *n receives its size, at most cap records are written */
 int mulls_block_download(mulls_ctx *ctx, const mulls_block *block, int which, void *pts, uint32_t cap, uint32_t *n);
 
+/* ---- many scans per call: mulls_extract_features_resident in lock step ----
+ * mulls_extract_features_batch runs extract_semantic_pts' chain (dist_filter -> scanner_filter -> voxel_downsample -> fast_ground_filter -> classify_nground_pts)
+ * on n_scans scans with one `params` (rng_seed included: every scan's fixed-number selections are its single call's) and leaves the feature clouds of scan i
+ * in blocks[i].  Every scan gets the bytes of its own mulls_extract_features_resident call — the fourteen n_out counts, every record of the twelve clouds a
+ * block holds, the return code — whatever the batch size, the scan's position, the other scans and the cuts into sub-batches are.
+ *   scans[i]   48-byte records `stride` bytes apart in host memory or in a device cloud of this context (detected as the single call detects it)
+ *   blocks[i]  live blocks of this context, all different, overwritten; a null or repeated block: MULLS_E_INVALID before anything is written
+ *   scratch_limit_bytes  bound of one sub-batch's device arena (0: MULLS_EXTRACT_BATCH_DEFAULT_SCRATCH_BYTES, which holds 64 scans of 121 k returns under the
+ *              KITTI parameters); consecutive scans share a sub-batch while they fit, a scan larger than the limit runs alone
+ *   results[i] status: what the scan's single call returns (a refused scan — a grid of more than 65 536 cells, non-finite coordinates reaching the
+ *              classification, more than 500 000 points — leaves its block with all sizes zero and disturbs no other scan); path; n_out
+ *   stats      optional (may be NULL)
+ * Within a sub-batch every device step runs once for all scans (one launch whose workgroups find their scan in a table in device memory) and every host
+ * wait of the single path happens once; both fixed-point loops run in lock step until no scan has an undecided point.  Two parameter points are handed scan
+ * by scan to the single-scan path inside the call (path = 1, the same bits): vf_downsample_resolution >= 0.001 (its cost is a host sort per scan either way)
+ * and estimate_ground_normal_method 1 / 2 (their own neighbour grid and error word).  Everything else runs in lock step (path = 0).
+ * Returns the status of the lowest-index scan whose status is not MULLS_OK (mulls_last_error names it), else MULLS_OK; n_scans == 0: MULLS_OK. */
+typedef struct mulls_extract_batch_result
+{
+	int32_t status;					/* this scan's code: what its single call returns */
+	uint32_t path;					/* 0 = ran in lock step, 1 = handed to the single-scan path */
+	uint32_t n_out[MULLS_EX_COUNT];
+} mulls_extract_batch_result;
+typedef struct mulls_extract_batch_stats
+{
+	uint32_t n_subbatches, n_lockstep, n_single_path;
+	uint32_t n_kernel_launches, n_syncs; /* of the lock-step part: kernels enqueued, host waits on the stream */
+	uint32_t promote_rounds, nms_rounds; /* rounds launched, summed over sub-batches */
+} mulls_extract_batch_stats;
+#define MULLS_EXTRACT_BATCH_DEFAULT_SCRATCH_BYTES (12ull << 30)
+int mulls_extract_features_batch(mulls_ctx *ctx, const mulls_cloud *scans, uint32_t n_scans, const mulls_extract_params *params, mulls_block *const *blocks,
+								 uint64_t scratch_limit_bytes, mulls_extract_batch_result *results, mulls_extract_batch_stats *stats);
+
 /* ---- motion compensation of a frame after its registration (test/mulls_slam.cpp:703-712, on in the 32- and 128-beam configurations) ----
  * mulls_motion_compensate = CFilter::apply_motion_compensation(pc_in_out, Tran, s_ambigous_thre) (cfilter.hpp:470-491), in place on `n` 48-byte records: every
  * point whose time stamp t (the curvature field, pts time-stamp ratio in the frame) lies in [thre, 1 - thre] is moved by the fraction t of Tran — slerp of the

@@ -290,6 +290,22 @@ class ExtractParams(C.Structure):
 EX_RAW, EX_GROUND, EX_GROUND_DOWN, EX_UNGROUND, EX_PILLAR, EX_VERTEX, EX_DOWN, EX_COUNT = 0, 1, 2, 3, 4, 12, 13, 14
 
 
+class ExtractBatchResult(C.Structure):
+    """mulls_extract_batch_result: one scan of mulls_extract_features_batch"""
+
+    _fields_ = [("status", C.c_int32), ("path", C.c_uint32), ("n_out", C.c_uint32 * EX_COUNT)]
+
+
+class ExtractBatchStats(C.Structure):
+    """mulls_extract_batch_stats"""
+
+    _fields_ = [("n_subbatches", C.c_uint32), ("n_lockstep", C.c_uint32), ("n_single_path", C.c_uint32), ("n_kernel_launches", C.c_uint32), ("n_syncs", C.c_uint32),
+                ("promote_rounds", C.c_uint32), ("nms_rounds", C.c_uint32)]
+
+
+EXTRACT_BATCH_DEFAULT_SCRATCH_BYTES = 12 << 30  # MULLS_EXTRACT_BATCH_DEFAULT_SCRATCH_BYTES
+
+
 def extract_params(ground=None, classify=None, apply_scanner_filter=0, approx_scanner_height=2.0, underground_thre=-7.0, apply_dist_filter=0,
                    min_dist_used=1.0, max_dist_used=120.0, vf_downsample_resolution=0.0):
     """The frame front end: dist_filter (test/mulls_slam.cpp:359-360) -> scanner filter (cfilter.hpp:2338-2346) -> voxel_downsample ->

@@ -15,6 +15,8 @@
 #include "../../include/mulls_hip.h"
 #include "classify_launch.h"
 #include "ctx.h"
+#include "extract_batch.h"
+#include "extract_internal.h"
 #include "map_launch.h"
 #include "nms_host.h"
 #include "rounds.h"
@@ -24,92 +26,8 @@ namespace
 const size_t REC = MULLS_POINT_BYTES;
 typedef std::vector<unsigned char> Bytes;
 
-struct Bump // carve device arrays out of one arena
-{
-	unsigned char *base;
-	size_t off;
-	template <typename T>
-	T *take(size_t count)
-	{
-		off = (off + 255u) & ~(size_t)255u;
-		T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
-		off += count * sizeof(T);
-		return p;
-	}
-};
-
-struct Layout
-{
-	ClArrays A;
-	float4 *cls_a[6];	  // pillar, pillar (promoted), beam, beam (promoted), facade, roof: compaction targets, pillar / beam become the class clouds
-	float4 *cls_sorted[4]; // class clouds in visiting order
-	float4 *down[4], *vertex;
-	uint32_t *nms_list[4], *nms_cnt[4], *nms_off[4], *nms_wcur[4], *nms_pool;
-	unsigned long long *nms_pool_used;
-	uint32_t nms_pool_cap;
-	uint8_t *keep[4];
-	float *keys;	// [4][n]
-	uint32_t *perm; // [4][n]
-	uint32_t *counts; // [16]
-	uint32_t *seg;	  // compaction scratch
-	size_t seg_cap;
-	size_t total;
-};
-
-// n: points the passes work on; n_in >= n: points of the cloud as handed in (the device-side thinning needs a mask and compaction scratch of that size)
-Layout carve(unsigned char *base, uint32_t n, uint32_t K, uint32_t n_in)
-{
-	Layout L;
-	Bump b{base, 0};
-	ClArrays &A = L.A;
-	A.recs = b.take<float4>((size_t)n * 3);
-	A.sorted = b.take<float4>(n);
-	A.cellof = b.take<uint32_t>(n);
-	A.cell_start = b.take<uint32_t>((size_t)MULLS_CL_MAX_CELLS + 1u);
-	A.cell_fill = b.take<uint32_t>((size_t)MULLS_CL_MAX_CELLS + 1u);
-	A.seg_sum = b.take<uint32_t>(1032);
-	A.nbr = b.take<uint32_t>((size_t)n * K);
-	A.closebits = b.take<unsigned long long>(n);
-	A.f_cnt = b.take<int32_t>(n);
-	A.cov = b.take<float>((size_t)n * 6);
-	A.f_curv = b.take<double>(n);
-	A.f_lin = b.take<double>(n);
-	A.f_pla = b.take<double>(n);
-	A.f_pd = b.take<float4>(n);
-	A.f_nd = b.take<float4>(n);
-	A.lab = b.take<uint8_t>(n);
-	A.plab = b.take<uint8_t>(n);
-	A.cstate = b.take<uint8_t>(n);
-	A.cand = b.take<uint8_t>(n);
-	A.down = b.take<uint8_t>(n);
-	A.mask = b.take<uint8_t>(std::max<size_t>((size_t)n * 11, n_in));
-	A.vtx = b.take<float4>((size_t)n * 3);
-	A.round_cnt = b.take<uint32_t>(64);
-	A.grid = b.take<ClGrid>(1);
-	for (int k = 0; k < 6; k++)
-		L.cls_a[k] = b.take<float4>((size_t)n * 3);
-	for (int k = 0; k < 4; k++)
-	{
-		L.cls_sorted[k] = b.take<float4>((size_t)n * 3);
-		L.down[k] = b.take<float4>((size_t)n * 3);
-		L.nms_list[k] = b.take<uint32_t>((size_t)n * MULLS_CL_NMS_CAP);
-		L.nms_cnt[k] = b.take<uint32_t>(n);
-		L.nms_off[k] = b.take<uint32_t>(n);
-		L.nms_wcur[k] = b.take<uint32_t>(n);
-		L.keep[k] = b.take<uint8_t>(n);
-	}
-	L.vertex = b.take<float4>((size_t)n * 3);
-	L.nms_pool_cap = (uint32_t)std::min<size_t>((size_t)n * 64u, 0x7fffffffu);
-	L.nms_pool = b.take<uint32_t>(L.nms_pool_cap);
-	L.nms_pool_used = b.take<unsigned long long>(1);
-	L.keys = b.take<float>((size_t)n * 4);
-	L.perm = b.take<uint32_t>((size_t)n * 4);
-	L.counts = b.take<uint32_t>(16);
-	L.seg_cap = (size_t)6 * ((std::max(n, n_in) + 4095u) / 4096u + 1u) + 16;
-	L.seg = b.take<uint32_t>(L.seg_cap);
-	L.total = b.off + 256;
-	return L;
-}
+using mulls_ex::carve;
+using mulls_ex::Layout;
 
 // random_downsample_pcl (cfilter.hpp:606-628) on raw records, with the ABI's seeded selection
 void random_downsample(Bytes &c, int keep_number, uint64_t seed, int cloud_id)
@@ -196,6 +114,47 @@ extern "C"
 		p->feature_pts_ratio_guess = 0.3f;
 	}
 
+	// the fixed-number thinning of the four *_down clouds (:2247-2257) on host records, host[MULLS_CL_*_DOWN]
+	__attribute__((visibility("hidden"))) void mulls_classify_thin_down(std::vector<unsigned char> *host, const mulls_classify_params *P)
+	{
+		random_downsample(host[MULLS_CL_PILLAR_DOWN], P->pillar_down_fixed_num, P->rng_seed, 31);
+		const int sector_num = 4;
+		xy_normal_balanced_downsample(host[MULLS_CL_FACADE_DOWN], (int)(P->facade_down_fixed_num / sector_num), sector_num, P->rng_seed, 32);
+		xy_normal_balanced_downsample(host[MULLS_CL_BEAM_DOWN], (int)(P->beam_down_fixed_num / sector_num), sector_num, P->rng_seed, 36);
+		random_downsample(host[MULLS_CL_ROOF_DOWN], P->roof_down_fixed_num, P->rng_seed, 40);
+	}
+	// what mulls_classify_impl refuses before it looks at the cloud
+	__attribute__((visibility("hidden"))) int mulls_classify_check(mulls_ctx *ctx, const mulls_classify_params *P)
+	{
+		if (P->pca_down_rate < 1 || P->neighbor_k < 1 || P->neighbor_k > (int)MULLS_CL_MAX_K || !(P->neighbor_searching_radius > 0.0f))
+		{
+			ctx->err = "mulls_classify_nground: pca_down_rate >= 1, 1 <= neighbor_k <= 64 and a positive radius are required";
+			return MULLS_E_INVALID;
+		}
+		return MULLS_OK;
+	}
+	// the parameters as the kernels use them (n left 0)
+	__attribute__((visibility("hidden"))) void mulls_classify_kernel_params(const mulls_classify_params *P, ClParams *out)
+	{
+		ClParams &Q = *out;
+		std::memset(&Q, 0, sizeof(Q));
+		Q.K = (uint32_t)P->neighbor_k;
+		Q.down_rate = P->pca_down_rate, Q.k_min = P->neigh_k_min;
+		Q.radius = P->neighbor_searching_radius;
+		Q.adaptive = P->use_distance_adaptive_pca ? 1 : 0;
+		Q.unit_distance = 30.0f; // :2098
+		Q.edge_thre = P->edge_thre, Q.planar_thre = P->planar_thre, Q.edge_thre_down = P->edge_thre_down, Q.planar_thre_down = P->planar_thre_down;
+		Q.lin_high = P->linear_vertical_sin_high_thre, Q.lin_low = P->linear_vertical_sin_low_thre;
+		Q.pla_high = P->planar_vertical_sin_high_thre, Q.pla_low = P->planar_vertical_sin_low_thre;
+		Q.beam_height_max = P->beam_height_max, Q.roof_height_min = P->roof_height_min;
+		Q.nms = P->sharpen_with_nms ? 1 : 0;
+		Q.vertex_method = (P->curvature_thre < 1e-8) ? 0 : P->extract_vertex_points_method; // :2161-2162
+		Q.curvature_thre = P->curvature_thre;
+		Q.vertex_ratio_thre = P->feature_pts_ratio_guess / P->pca_down_rate;									  // :2167
+		Q.min_curvature = (float)(0.3 * P->curvature_thre);													  // :2210
+		Q.min_neighbor_feature_pts = (int)(P->feature_pts_ratio_guess / P->pca_down_rate * P->neighbor_k) - 1; // :2206
+	}
+
 	// pts_on_device: `pts` is device memory of this context's device holding packed 48-byte records (mulls_extract_features)
 	// dev_out: leave the clouds on the device (ClassifyDev, ctx.h) instead of copying them to out[] (which may then hold nulls)
 	__attribute__((visibility("hidden"))) int mulls_classify_impl(mulls_ctx *ctx, const void *pts, bool pts_on_device, uint32_t n_in, uint32_t stride, const mulls_classify_params *P,
@@ -210,11 +169,8 @@ extern "C"
 			if (cap[k] && !out[k])
 				return MULLS_E_INVALID;
 		}
-		if (P->pca_down_rate < 1 || P->neighbor_k < 1 || P->neighbor_k > (int)MULLS_CL_MAX_K || !(P->neighbor_searching_radius > 0.0f))
-		{
-			ctx->err = "mulls_classify_nground: pca_down_rate >= 1, 1 <= neighbor_k <= 64 and a positive radius are required";
+		if (mulls_classify_check(ctx, P) != MULLS_OK)
 			return MULLS_E_INVALID;
-		}
 		if (n_in > 2000000u)
 		{
 			ctx->err = "mulls_classify_nground: more than 2000000 points in one cloud";
@@ -283,22 +239,8 @@ extern "C"
 		HIPCHK(ctx, hipMemsetAsync(A.round_cnt, 0, 64 * 4, st));
 
 		ClParams Q;
-		std::memset(&Q, 0, sizeof(Q));
-		Q.n = n, Q.K = K;
-		Q.down_rate = P->pca_down_rate, Q.k_min = P->neigh_k_min;
-		Q.radius = P->neighbor_searching_radius;
-		Q.adaptive = P->use_distance_adaptive_pca ? 1 : 0;
-		Q.unit_distance = 30.0f; // :2098
-		Q.edge_thre = P->edge_thre, Q.planar_thre = P->planar_thre, Q.edge_thre_down = P->edge_thre_down, Q.planar_thre_down = P->planar_thre_down;
-		Q.lin_high = P->linear_vertical_sin_high_thre, Q.lin_low = P->linear_vertical_sin_low_thre;
-		Q.pla_high = P->planar_vertical_sin_high_thre, Q.pla_low = P->planar_vertical_sin_low_thre;
-		Q.beam_height_max = P->beam_height_max, Q.roof_height_min = P->roof_height_min;
-		Q.nms = P->sharpen_with_nms ? 1 : 0;
-		Q.vertex_method = (P->curvature_thre < 1e-8) ? 0 : P->extract_vertex_points_method; // :2161-2162
-		Q.curvature_thre = P->curvature_thre;
-		Q.vertex_ratio_thre = P->feature_pts_ratio_guess / P->pca_down_rate;									  // :2167
-		Q.min_curvature = (float)(0.3 * P->curvature_thre);													  // :2210
-		Q.min_neighbor_feature_pts = (int)(P->feature_pts_ratio_guess / P->pca_down_rate * P->neighbor_k) - 1; // :2206
+		mulls_classify_kernel_params(P, &Q);
+		Q.n = n;
 
 		launch_cl_grid(st, A, Q);
 		launch_cl_pca(st, A, Q);
@@ -464,11 +406,7 @@ extern "C"
 		HIPCHK(ctx, hipStreamSynchronize(st));
 		if (P->fixed_num_downsampling) // :2247-2257
 		{
-			random_downsample(host[MULLS_CL_PILLAR_DOWN], P->pillar_down_fixed_num, P->rng_seed, 31);
-			const int sector_num = 4;
-			xy_normal_balanced_downsample(host[MULLS_CL_FACADE_DOWN], (int)(P->facade_down_fixed_num / sector_num), sector_num, P->rng_seed, 32);
-			xy_normal_balanced_downsample(host[MULLS_CL_BEAM_DOWN], (int)(P->beam_down_fixed_num / sector_num), sector_num, P->rng_seed, 36);
-			random_downsample(host[MULLS_CL_ROOF_DOWN], P->roof_down_fixed_num, P->rng_seed, 40);
+			mulls_classify_thin_down(host, P);
 			for (int k = MULLS_CL_PILLAR_DOWN; k <= MULLS_CL_ROOF_DOWN; k++)
 			{
 				n_out[k] = (uint32_t)(host[k].size() / REC);

@@ -83,3 +83,30 @@ void launch_cl_nms_round(hipStream_t st, const ClNmsArgs &a, uint32_t *round_cnt
 void launch_cl_keys(hipStream_t st, const float4 *recs, uint32_t n, float *keys);
 // out[i] = in[perm[i]], whole 48-byte records
 void launch_cl_gather(hipStream_t st, const float4 *in, const uint32_t *perm, float4 *out, uint32_t n);
+
+// ---- mulls_extract_features_batch: the same kernels for many scans per launch -------------------------------------------------------------------
+// One scan of a lock-step launch (a table entry in device memory, found at blockIdx.y); n == 0: the scan takes no part.
+struct ClScan
+{
+	ClArrays A;
+	uint32_t n, pad_;
+};
+struct ClRecJob // one class cloud of launch_cl_keys_batch / launch_cl_gather_batch
+{
+	const float4 *in;
+	const uint32_t *perm;
+	float4 *out;
+	float *keys;
+	uint32_t n, pad_;
+};
+// (P.n is not read: every scan's own n comes from the table.  The grid's start keys and zeroed cell counters are the caller's.)  Each returns the kernels launched.
+int launch_cl_grid_batch(hipStream_t st, const ClScan *tab_dev, uint32_t count, uint32_t n_max, const ClParams &P);
+int launch_cl_pca_batch(hipStream_t st, const ClScan *tab_dev, uint32_t count, uint32_t n_max, const ClParams &P);
+int launch_cl_label_batch(hipStream_t st, const ClScan *tab_dev, uint32_t count, uint32_t n_max, const ClParams &P);
+int launch_cl_promote_round_batch(hipStream_t st, const ClScan *tab_dev, uint32_t count, uint32_t n_max, const ClParams &P, uint32_t *round_cnt); // *round_cnt += undecided, all scans
+int launch_cl_encode_batch(hipStream_t st, const ClScan *tab_dev, uint32_t count, uint32_t n_max, const ClParams &P);
+// tab_dev: one ClNmsArgs per scan (blockIdx.z); nmax: the largest class cloud of any scan
+int launch_cl_nms_lists_batch(hipStream_t st, const ClNmsArgs *tab_dev, uint32_t count, uint32_t nmax, uint32_t *round_cnt); // round_cnt: 64 counters shared by the scans, zeroed here
+int launch_cl_nms_round_batch(hipStream_t st, const ClNmsArgs *tab_dev, uint32_t count, uint32_t nmax, uint32_t *round_cnt);
+int launch_cl_keys_batch(hipStream_t st, const ClRecJob *tab_dev, uint32_t count, uint32_t n_max);
+int launch_cl_gather_batch(hipStream_t st, const ClRecJob *tab_dev, uint32_t count, uint32_t n_max);

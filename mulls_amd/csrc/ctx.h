@@ -85,6 +85,11 @@ struct mulls_ctx
 	size_t mail_cap = 0;
 	unsigned char *cl_pin = nullptr, *scan_pin = nullptr; // pinned host scratch of the feature stage: the visiting orders' keys and permutations; the raw scan on its way up
 	size_t cl_pin_cap = 0, scan_pin_cap = 0;
+	void *exb_buf = nullptr; // mulls_extract_features_batch's device arena of one sub-batch (grow-only; gf_buf and cl_buf stay the single calls')
+	size_t exb_cap = 0;
+	unsigned char *exb_tab_pin = nullptr, *exb_pin = nullptr; // ... its pinned scratch: the tables on their way up; the words, keys, orders and records that cross (host-mapped)
+	size_t exb_tab_pin_cap = 0, exb_pin_cap = 0;
+	uint32_t exb_rounds_hint[2] = {4, 8}; // ... and its two round loops' lengths in the previous call
 	uint32_t cl_rounds_hint[2] = {4, 8}; // rounds the promotion loop / the suppression rounds needed in the previous call: this call's first batch
 	mulls_ncc_scratch *ncc = nullptr; // mulls_ncc_correspond's device arena and pinned buffer (ncc.cpp; grow-only)
 	mulls_ransac_scratch *ransac = nullptr; // mulls_coarse_reg_ransac's (ransac.cpp; grow-only)

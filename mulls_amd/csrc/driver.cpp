@@ -256,6 +256,12 @@ extern "C"
 			mulls_batch_destroy(ctx, ctx->scratch);
 		if (ctx->mail_h)
 			(void)hipHostFree(ctx->mail_h);
+		if (ctx->exb_buf)
+			(void)hipFree(ctx->exb_buf);
+		if (ctx->exb_tab_pin)
+			(void)hipHostFree(ctx->exb_tab_pin);
+		if (ctx->exb_pin)
+			(void)hipHostFree(ctx->exb_pin);
 		if (ctx->cl_pin)
 			(void)hipHostFree(ctx->cl_pin);
 		if (ctx->scan_pin)

@@ -17,11 +17,12 @@
 #include "map_launch.h"
 
 #include "classify_launch.h"
+#include "extract_batch.h"
+#include "extract_internal.h"
 #include "ground_launch.h"
 
-extern "C" __attribute__((visibility("hidden"))) int mulls_classify_impl(mulls_ctx *ctx, const void *pts, bool pts_on_device, uint32_t n_in, uint32_t stride, const mulls_classify_params *P,
-								   void *const out[MULLS_CL_COUNT], const uint32_t cap[MULLS_CL_COUNT], uint32_t n_out[MULLS_CL_COUNT], void *cloud_in_after,
-								   uint32_t *n_cloud_in_after, ClassifyDev *dev_out);
+using mulls_ex::GfArena;
+using mulls_ex::gf_layout;
 
 extern "C"
 {
@@ -54,30 +55,7 @@ extern "C"
 	}
 
 	// ---- shared by mulls_ground_filter and mulls_extract_features -------------------------------------------------------------------
-	struct GfArena // one device arena: scan | ground | unground | ids | d3v | cellof | code | state, counters, per-cell tables | (filters / voxels ahead:) scan copy, mask, scratch, voxel keys, order
-	{
-		size_t o_ground, o_unground, o_ids, o_d3, o_cell, o_code, o_aux, o_alt, o_mask, o_seg, o_keys, o_perm, o_ransac, o_normals, total;
-	};
-	// prefilter: dist_filter / scanner_filter ahead of the ground filter; voxels: voxel_downsample ahead of it (either needs a second scan-sized buffer)
-	static GfArena gf_layout(uint32_t n, bool prefilter, bool voxels, int normal_method = 0)
-	{
-		GfArena a;
-		const size_t rec = (size_t)n * MULLS_POINT_BYTES;
-		a.o_ground = rec, a.o_unground = 2 * rec, a.o_ids = 3 * rec, a.o_d3 = a.o_ids + (size_t)n * 4, a.o_cell = a.o_d3 + (size_t)n * 4;
-		a.o_code = a.o_cell + (size_t)n * 2;
-		a.o_aux = (a.o_code + n + 255) & ~(size_t)255;
-		a.o_alt = (a.o_aux + ground_filter_aux_bytes(n) + 255) & ~(size_t)255;
-		a.o_mask = a.o_alt + (prefilter || voxels ? rec : 0);
-		a.o_seg = (a.o_mask + (prefilter ? n : 0) + 255) & ~(size_t)255;
-		a.o_keys = (a.o_seg + (prefilter ? ((size_t)n / 4096 + 32) * 4 * 8 : 0) + 255) & ~(size_t)255;
-		a.o_perm = a.o_keys + (voxels ? (size_t)n * 8 + 256 : 0);
-		// normal method 3: gg | perm | inl (uint32 each) | gxyz (float4) | cell_nrm (float4 per cell); methods 1 / 2: the neighbour grid of the ground cloud
-		a.o_ransac = (a.o_perm + (voxels ? (size_t)n * 4 : 0) + 255) & ~(size_t)255;
-		a.o_normals = a.o_ransac + (normal_method == 3 ? (size_t)n * 28 + (size_t)MULLS_GF_MAXCELLS * 16 + 256 : 0);
-		a.total = a.o_normals + ((normal_method == 1 || normal_method == 2) ? ground_normals_bytes(n) : 0);
-		return a;
-	}
-	static int gf_check(mulls_ctx *ctx, const mulls_ground_params *P, uint32_t n)
+	MULLS_HIDDEN int gf_check(mulls_ctx *ctx, const mulls_ground_params *P, uint32_t n)
 	{
 		if (P->estimate_ground_normal_method < 0 || P->estimate_ground_normal_method > 3)
 		{
@@ -122,7 +100,7 @@ extern "C"
 	}
 	// PCL's sample sequence for the plane RANSAC of normal method 3: SACSegmentation(random = false) seeds boost::mt19937 with 12345u for every
 	// model and draws through boost::uniform_int<>(0, INT_MAX), i.e. output / 2 — the same draws for every grid cell, so one table serves all
-	static int gf_rnd_table(mulls_ctx *ctx)
+	MULLS_HIDDEN int gf_rnd_table(mulls_ctx *ctx)
 	{
 		if (ctx->gf_rnd)
 			return MULLS_OK;
@@ -144,13 +122,7 @@ extern "C"
 		{
 			if (gf_rnd_table(ctx) != MULLS_OK)
 				return MULLS_E_HIP;
-			unsigned char *r = base + a.o_ransac;
-			R.gg = reinterpret_cast<uint32_t *>(r);
-			R.perm = R.gg + n;
-			R.inl = R.perm + n;
-			R.gxyz = reinterpret_cast<float4 *>((reinterpret_cast<uintptr_t>(R.inl + n) + 15) & ~(uintptr_t)15);
-			R.cell_nrm = R.gxyz + n;
-			R.rnd = static_cast<const uint32_t *>(ctx->gf_rnd);
+			R = mulls_ex::gf_ransac_at(base, a, n, ctx->gf_rnd);
 		}
 		if (launch_ground_filter(st, scan, n, *P, reinterpret_cast<uint32_t *>(base + a.o_ids), reinterpret_cast<uint16_t *>(base + a.o_cell), base + a.o_code,
 								 reinterpret_cast<float *>(base + a.o_d3), reinterpret_cast<float4 *>(base + a.o_ground), reinterpret_cast<float4 *>(base + a.o_unground),
@@ -259,7 +231,7 @@ extern "C"
 		return MULLS_OK;
 	}
 	// which points of cloud_ground make cloud_ground_down (cfilter.hpp:1955-1968): every ground_random_down_down_rate-th, or the seeded fixed-number selection
-	static void gf_ground_down_indices(const mulls_ground_params *P, uint32_t n_ground, std::vector<uint32_t> &idx)
+	MULLS_HIDDEN void gf_ground_down_indices(const mulls_ground_params *P, uint32_t n_ground, std::vector<uint32_t> &idx)
 	{
 		idx.clear();
 		if (!P->fixed_num_downsampling)
@@ -406,7 +378,7 @@ extern "C"
 	}
 
 	// blk: keep the feature clouds on the device (mulls_extract_features_resident) instead of copying them to out[]
-	static int extract_impl(mulls_ctx *ctx, const void *scan, uint32_t n_in, uint32_t stride, const mulls_extract_params *X, void *const out[MULLS_EX_COUNT],
+	MULLS_HIDDEN int extract_impl(mulls_ctx *ctx, const void *scan, uint32_t n_in, uint32_t stride, const mulls_extract_params *X, void *const out[MULLS_EX_COUNT],
 							const uint32_t cap[MULLS_EX_COUNT], uint32_t n_out[MULLS_EX_COUNT], mulls_block *blk)
 	{
 		if (!ctx || !X || !out || !cap || !n_out || (n_in && !scan) || stride < MULLS_POINT_BYTES)

@@ -12,6 +12,8 @@
 //   k_cl_promote    fixed-point rounds of the one loop upstream that reads labels it has just written (:2166-2197)
 //   k_cl_encode     key points and their neighbourhood descriptors; masks for the stable compactions (map_kernels.hip)
 //   k_cl_nms_*      greedy suppression in visiting order as earlier-neighbour lists + fixed-point rounds
+// Each of them is written once as a __device__ body (d_cl_*) and launched in two forms, see "The kernels" below: k_cl_* for one cloud (arguments by value) and
+// k_cl_*_b for the scans of a table in device memory (mulls_extract_features_batch).
 #include <hip/hip_runtime.h>
 
 #include "classify_launch.h"
@@ -41,7 +43,7 @@ __device__ __forceinline__ int cell_axis(double v, double lo, double cell, uint3
 }
 } // namespace
 
-__global__ __launch_bounds__(256) void k_cl_bbox(const float4 *__restrict__ recs, uint32_t n, ClGrid *g)
+__device__ __forceinline__ void d_cl_bbox(const float4 *__restrict__ recs, uint32_t n, ClGrid *g)
 {
 	__shared__ uint32_t s[7][4];
 	uint32_t k[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u}, bad = 0;
@@ -85,7 +87,7 @@ __global__ __launch_bounds__(256) void k_cl_bbox(const float4 *__restrict__ recs
 	}
 }
 
-__global__ void k_cl_setup(ClGrid *g, float cell_hint)
+__device__ __forceinline__ void d_cl_setup(ClGrid *g, float cell_hint)
 {
 	if (threadIdx.x || blockIdx.x)
 		return;
@@ -114,7 +116,7 @@ __global__ void k_cl_setup(ClGrid *g, float cell_hint)
 	g->ncell = g->dim[0] * g->dim[1] * g->dim[2];
 }
 
-__global__ __launch_bounds__(256) void k_cl_count(const float4 *__restrict__ recs, uint32_t n, const ClGrid *__restrict__ g, uint32_t *__restrict__ cellof,
+__device__ __forceinline__ void d_cl_count(const float4 *__restrict__ recs, uint32_t n, const ClGrid *__restrict__ g, uint32_t *__restrict__ cellof,
 												  uint32_t *__restrict__ cnt)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(256) void k_cl_count(const float4 *__restrict__ rec
 
 // exclusive prefix sum of v[0 .. ncell] (ncell + 1 entries, v[ncell] = 0 on entry) in three steps over 4096-entry segments
 #define CL_SEG 4096u
-__global__ __launch_bounds__(256) void k_cl_scan_seg(const uint32_t *__restrict__ v, const ClGrid *__restrict__ g, uint32_t *__restrict__ seg_sum)
+__device__ __forceinline__ void d_cl_scan_seg(const uint32_t *__restrict__ v, const ClGrid *__restrict__ g, uint32_t *__restrict__ seg_sum)
 {
 	__shared__ uint32_t s[4];
 	const uint32_t total = g->ncell + 1u, base = blockIdx.x * CL_SEG;
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(256) void k_cl_scan_seg(const uint32_t *__restrict_
 	if (threadIdx.x == 0)
 		seg_sum[blockIdx.x] = s[0] + s[1] + s[2] + s[3];
 }
-__global__ __launch_bounds__(1024) void k_cl_scan_top(uint32_t *__restrict__ seg_sum, const ClGrid *__restrict__ g)
+__device__ __forceinline__ void d_cl_scan_top(uint32_t *__restrict__ seg_sum, const ClGrid *__restrict__ g)
 {
 	__shared__ uint32_t s[1025];
 	const uint32_t nseg = (g->ncell + 1u + CL_SEG - 1u) / CL_SEG; // <= 1025
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(1024) void k_cl_scan_top(uint32_t *__restrict__ seg
 	for (uint32_t j = threadIdx.x; j < nseg; j += 1024u)
 		seg_sum[j] = s[j];
 }
-__global__ __launch_bounds__(256) void k_cl_scan_apply(uint32_t *__restrict__ v, const ClGrid *__restrict__ g, const uint32_t *__restrict__ seg_sum, uint32_t *__restrict__ copy)
+__device__ __forceinline__ void d_cl_scan_apply(uint32_t *__restrict__ v, const ClGrid *__restrict__ g, const uint32_t *__restrict__ seg_sum, uint32_t *__restrict__ copy)
 {
 	__shared__ uint32_t wsum[4];
 	const uint32_t total = g->ncell + 1u, base = blockIdx.x * CL_SEG;
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(256) void k_cl_scan_apply(uint32_t *__restrict__ v,
 			run += loc[k];
 		}
 }
-__global__ __launch_bounds__(256) void k_cl_scatter(const float4 *__restrict__ recs, uint32_t n, const uint32_t *__restrict__ cellof, uint32_t *__restrict__ fill,
+__device__ __forceinline__ void d_cl_scatter(const float4 *__restrict__ recs, uint32_t n, const uint32_t *__restrict__ cellof, uint32_t *__restrict__ fill,
 													float4 *__restrict__ sorted)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -276,7 +278,7 @@ __device__ __forceinline__ uint32_t knn_select(KnnLds &L, uint32_t lane, uint32_
 }
 } // namespace
 
-__global__ __launch_bounds__(256) void k_cl_knn(ClArrays A, ClParams P)
+__device__ __forceinline__ void d_cl_knn(ClArrays A, ClParams P)
 {
 	__shared__ KnnLds Lw[4];
 	const uint32_t t = threadIdx.x, w = t >> 6, lane = t & 63u;
@@ -404,7 +406,7 @@ __global__ __launch_bounds__(256) void k_cl_knn(ClArrays A, ClParams P)
 	}
 }
 
-__global__ __launch_bounds__(256) void k_cl_eig(ClArrays A, ClParams P)
+__device__ __forceinline__ void d_cl_eig(ClArrays A, ClParams P)
 {
 	const uint32_t q = blockIdx.x * 256u + threadIdx.x;
 	const uint64_t i64 = (uint64_t)q * (uint64_t)P.down_rate;
@@ -441,7 +443,7 @@ __global__ __launch_bounds__(256) void k_cl_eig(ClArrays A, ClParams P)
 // ---------------------------------------------------------------------------------------------------------------------
 // the class decision (cfilter.hpp:2105-2158).  lab: 0 none, 1 pillar, 2 beam, 3 facade, 4 roof; down: the same codes for the *_down clouds
 // of sharpen_with_nms = false; cand: bit 0 = candidate of the promotion loop (:2170), bit 1 / 2 = would become a pillar / beam there
-__global__ __launch_bounds__(256) void k_cl_label(ClArrays A, ClParams P)
+__device__ __forceinline__ void d_cl_label(ClArrays A, ClParams P)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= P.n)
@@ -489,7 +491,7 @@ __global__ __launch_bounds__(256) void k_cl_label(ClArrays A, ClParams P)
 // One round of the promotion loop (:2166-2197).  Upstream walks the points in order and counts, for a candidate, the neighbours that carry
 // a label at that moment — labels of the first pass plus those the loop itself gave to candidates of lower index.  A candidate is decided as
 // soon as the undecided lower-index candidates in its neighbourhood cannot change its verdict; the lowest undecided one always is.
-__global__ __launch_bounds__(256) void k_cl_promote(ClArrays A, ClParams P, uint32_t round)
+__device__ __forceinline__ void d_cl_promote(ClArrays A, ClParams P, uint32_t *round_cnt)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= P.n)
@@ -535,12 +537,12 @@ __global__ __launch_bounds__(256) void k_cl_promote(ClArrays A, ClParams P, uint
 		}
 		__threadfence();
 	}
-	atomicAdd(&A.round_cnt[round], 1u);
+	atomicAdd(round_cnt, 1u);
 }
 
 // encode_stable_points (:1071-1181) into vtx[i] + the eleven masks of the stable compactions:
 // 0 pillar (first pass), 1 pillar (promoted), 2 beam, 3 beam (promoted), 4 facade, 5 roof, 6 key point, 7..10 pillar / beam / facade / roof down
-__global__ __launch_bounds__(256) void k_cl_encode(ClArrays A, ClParams P)
+__device__ __forceinline__ void d_cl_encode(ClArrays A, ClParams P)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x, n = P.n;
 	if (i >= n)
@@ -607,7 +609,7 @@ __global__ __launch_bounds__(256) void k_cl_encode(ClArrays A, ClParams P)
 //                    all suppressed is kept, the others wait — the first undecided point of the order never waits, so every round decides
 // state: 0 suppressed, 1 kept, 2 undecided (so that the settled array is the compaction's keep mask)
 #define CL_NMS_CAP MULLS_CL_NMS_CAP // list slots; a point with more earlier neighbours scans its predecessors directly in every round
-__global__ __launch_bounds__(256) void k_cl_nms_lists(ClNmsArgs a)
+__device__ __forceinline__ void d_cl_nms_lists(const ClNmsArgs &a)
 {
 	// one workgroup per pair of 256-point tiles (bi >= bj) of one class: lane t's point p of tile bi against the points q < p of tile bj
 	__shared__ float sx[256], sy[256], sz[256];
@@ -650,7 +652,7 @@ __global__ __launch_bounds__(256) void k_cl_nms_lists(ClNmsArgs a)
 // shared pool and the tile pairs are walked once more for them; only a cloud that exhausts the pool (pathological: everything within the
 // radius of everything) leaves points to the direct scan of k_cl_nms_round
 // before the lists: every point undecided, no earlier neighbours counted, the pool empty, the round counters zero (one launch instead of a fill command per array)
-__global__ __launch_bounds__(256) void k_cl_nms_init(ClNmsArgs a, uint32_t *round_cnt)
+__device__ __forceinline__ void d_cl_nms_init(const ClNmsArgs &a, uint32_t *round_cnt)
 {
 	const uint32_t c = blockIdx.y, n = a.n[c], p = blockIdx.x * 256u + threadIdx.x;
 	if (c == 0 && blockIdx.x == 0)
@@ -666,7 +668,7 @@ __global__ __launch_bounds__(256) void k_cl_nms_init(ClNmsArgs a, uint32_t *roun
 		a.keep[c][p] = 2;
 	}
 }
-__global__ __launch_bounds__(256) void k_cl_nms_reserve(ClNmsArgs a)
+__device__ __forceinline__ void d_cl_nms_reserve(const ClNmsArgs &a)
 {
 	const uint32_t c = blockIdx.y, n = a.n[c], p = blockIdx.x * 256u + threadIdx.x;
 	if (p >= n)
@@ -682,7 +684,7 @@ __global__ __launch_bounds__(256) void k_cl_nms_reserve(ClNmsArgs a)
 	a.off[c][p] = off;
 	a.wcur[c][p] = 0;
 }
-__global__ __launch_bounds__(256) void k_cl_nms_lists_long(ClNmsArgs a)
+__device__ __forceinline__ void d_cl_nms_lists_long(const ClNmsArgs &a)
 {
 	__shared__ float sx[256], sy[256], sz[256];
 	const uint32_t c = blockIdx.y, n = a.n[c], t = threadIdx.x, nb = (n + 255u) / 256u;
@@ -718,7 +720,7 @@ __global__ __launch_bounds__(256) void k_cl_nms_lists_long(ClNmsArgs a)
 			a.pool[off + atomicAdd(&a.wcur[c][p], 1u)] = q0 + j;
 	}
 }
-__global__ __launch_bounds__(256) void k_cl_nms_round(ClNmsArgs a, uint32_t *round_cnt)
+__device__ __forceinline__ void d_cl_nms_round(const ClNmsArgs &a, uint32_t *round_cnt)
 {
 	const uint32_t c = blockIdx.y, n = a.n[c], p = blockIdx.x * 256u + threadIdx.x;
 	if (p >= n)
@@ -785,13 +787,13 @@ __global__ __launch_bounds__(256) void k_cl_nms_round(ClNmsArgs a, uint32_t *rou
 	atomicAdd(round_cnt, 1u);
 }
 
-__global__ __launch_bounds__(256) void k_cl_keys(const float4 *__restrict__ recs, uint32_t n, float *__restrict__ keys)
+__device__ __forceinline__ void d_cl_keys(const float4 *__restrict__ recs, uint32_t n, float *__restrict__ keys)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i < n)
 		keys[i] = recs[(size_t)i * 3 + 1].w;
 }
-__global__ __launch_bounds__(256) void k_cl_gather(const float4 *__restrict__ in, const uint32_t *__restrict__ perm, float4 *__restrict__ out, uint32_t n)
+__device__ __forceinline__ void d_cl_gather(const float4 *__restrict__ in, const uint32_t *__restrict__ perm, float4 *__restrict__ out, uint32_t n)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= n)
@@ -802,6 +804,85 @@ __global__ __launch_bounds__(256) void k_cl_gather(const float4 *__restrict__ in
 	out[(size_t)i * 3 + 2] = in[(size_t)s * 3 + 2];
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The kernels: every body above once with its arguments by value (one cloud: mulls_classify_nground) and once with the arguments of the scan at
+// blockIdx.y (the suppression kernels, whose blockIdx.y is the class: blockIdx.z) of a table in device memory (mulls_extract_features_batch).
+// The table entry is wave-uniform: scalar loads.  A workgroup past its scan's size leaves through the body's own bound check.
+__global__ __launch_bounds__(256) void k_cl_bbox(const float4 *__restrict__ recs, uint32_t n, ClGrid *g) { d_cl_bbox(recs, n, g); }
+__global__ void k_cl_setup(ClGrid *g, float cell_hint) { d_cl_setup(g, cell_hint); }
+__global__ __launch_bounds__(256) void k_cl_count(const float4 *__restrict__ recs, uint32_t n, const ClGrid *__restrict__ g, uint32_t *__restrict__ cellof, uint32_t *__restrict__ cnt) { d_cl_count(recs, n, g, cellof, cnt); }
+__global__ __launch_bounds__(256) void k_cl_scan_seg(const uint32_t *__restrict__ v, const ClGrid *__restrict__ g, uint32_t *__restrict__ seg_sum) { d_cl_scan_seg(v, g, seg_sum); }
+__global__ __launch_bounds__(1024) void k_cl_scan_top(uint32_t *__restrict__ seg_sum, const ClGrid *__restrict__ g) { d_cl_scan_top(seg_sum, g); }
+__global__ __launch_bounds__(256) void k_cl_scan_apply(uint32_t *__restrict__ v, const ClGrid *__restrict__ g, const uint32_t *__restrict__ seg_sum, uint32_t *__restrict__ copy) { d_cl_scan_apply(v, g, seg_sum, copy); }
+__global__ __launch_bounds__(256) void k_cl_scatter(const float4 *__restrict__ recs, uint32_t n, const uint32_t *__restrict__ cellof, uint32_t *__restrict__ fill, float4 *__restrict__ sorted) { d_cl_scatter(recs, n, cellof, fill, sorted); }
+__global__ __launch_bounds__(256) void k_cl_knn(ClArrays A, ClParams P) { d_cl_knn(A, P); }
+__global__ __launch_bounds__(256) void k_cl_eig(ClArrays A, ClParams P) { d_cl_eig(A, P); }
+__global__ __launch_bounds__(256) void k_cl_label(ClArrays A, ClParams P) { d_cl_label(A, P); }
+__global__ __launch_bounds__(256) void k_cl_promote(ClArrays A, ClParams P, uint32_t round) { d_cl_promote(A, P, A.round_cnt + round); }
+__global__ __launch_bounds__(256) void k_cl_encode(ClArrays A, ClParams P) { d_cl_encode(A, P); }
+__global__ __launch_bounds__(256) void k_cl_nms_lists(ClNmsArgs a) { d_cl_nms_lists(a); }
+__global__ __launch_bounds__(256) void k_cl_nms_init(ClNmsArgs a, uint32_t *round_cnt) { d_cl_nms_init(a, round_cnt); }
+__global__ __launch_bounds__(256) void k_cl_nms_reserve(ClNmsArgs a) { d_cl_nms_reserve(a); }
+__global__ __launch_bounds__(256) void k_cl_nms_lists_long(ClNmsArgs a) { d_cl_nms_lists_long(a); }
+__global__ __launch_bounds__(256) void k_cl_nms_round(ClNmsArgs a, uint32_t *round_cnt) { d_cl_nms_round(a, round_cnt); }
+__global__ __launch_bounds__(256) void k_cl_keys(const float4 *__restrict__ recs, uint32_t n, float *__restrict__ keys) { d_cl_keys(recs, n, keys); }
+__global__ __launch_bounds__(256) void k_cl_gather(const float4 *__restrict__ in, const uint32_t *__restrict__ perm, float4 *__restrict__ out, uint32_t n) { d_cl_gather(in, perm, out, n); }
+
+#define CL_BATCH(name, bounds, extra, call)                                          \
+	__global__ __launch_bounds__(bounds) void name(const ClScan *__restrict__ tab extra) \
+	{                                                                                \
+		const ClScan e = tab[blockIdx.y];                                            \
+		if (!e.n)                                                                    \
+			return;                                                                  \
+		call;                                                                        \
+	}
+#define CL_COMMA ,
+#define CL_P(e) cl_params_of(P, e.n)
+namespace
+{
+__device__ __forceinline__ ClParams cl_params_of(ClParams P, uint32_t n)
+{
+	P.n = n;
+	return P;
+}
+} // namespace
+CL_BATCH(k_cl_bbox_b, 256, , if (blockIdx.x < min((e.n + 255u) / 256u, 256u)) d_cl_bbox(e.A.recs, e.n, e.A.grid))
+CL_BATCH(k_cl_setup_b, 64, CL_COMMA float cell_hint, d_cl_setup(e.A.grid, cell_hint))
+CL_BATCH(k_cl_count_b, 256, , d_cl_count(e.A.recs, e.n, e.A.grid, e.A.cellof, e.A.cell_start))
+CL_BATCH(k_cl_scan_seg_b, 256, , d_cl_scan_seg(e.A.cell_start, e.A.grid, e.A.seg_sum))
+CL_BATCH(k_cl_scan_top_b, 1024, , d_cl_scan_top(e.A.seg_sum, e.A.grid))
+CL_BATCH(k_cl_scan_apply_b, 256, , d_cl_scan_apply(e.A.cell_start, e.A.grid, e.A.seg_sum, e.A.cell_fill))
+CL_BATCH(k_cl_scatter_b, 256, , d_cl_scatter(e.A.recs, e.n, e.A.cellof, e.A.cell_fill, e.A.sorted))
+CL_BATCH(k_cl_knn_b, 256, CL_COMMA ClParams P, d_cl_knn(e.A, CL_P(e)))
+CL_BATCH(k_cl_eig_b, 256, CL_COMMA ClParams P, d_cl_eig(e.A, CL_P(e)))
+CL_BATCH(k_cl_label_b, 256, CL_COMMA ClParams P, d_cl_label(e.A, CL_P(e)))
+CL_BATCH(k_cl_promote_b, 256, CL_COMMA ClParams P CL_COMMA uint32_t *round_cnt, d_cl_promote(e.A, CL_P(e), round_cnt))
+CL_BATCH(k_cl_encode_b, 256, CL_COMMA ClParams P, d_cl_encode(e.A, CL_P(e)))
+#define CL_NMS_BATCH(name, call)                                                        \
+	__global__ __launch_bounds__(256) void name(const ClNmsArgs *__restrict__ tab, uint32_t *round_cnt) \
+	{                                                                                   \
+		const ClNmsArgs &a = tab[blockIdx.z];                                            \
+		if (!a.n[blockIdx.y])                                                            \
+			return;                                                                      \
+		call;                                                                            \
+	}
+CL_NMS_BATCH(k_cl_nms_lists_b, d_cl_nms_lists(a))
+CL_NMS_BATCH(k_cl_nms_reserve_b, d_cl_nms_reserve(a))
+CL_NMS_BATCH(k_cl_nms_lists_long_b, d_cl_nms_lists_long(a))
+CL_NMS_BATCH(k_cl_nms_round_b, d_cl_nms_round(a, round_cnt))
+// (no early leave: the first workgroup of every scan resets its pool cursor whatever its classes hold)
+__global__ __launch_bounds__(256) void k_cl_nms_init_b(const ClNmsArgs *__restrict__ tab, uint32_t *round_cnt) { d_cl_nms_init(tab[blockIdx.z], round_cnt); }
+__global__ __launch_bounds__(256) void k_cl_keys_b(const ClRecJob *__restrict__ tab)
+{
+	const ClRecJob e = tab[blockIdx.y];
+	d_cl_keys(e.in, e.n, e.keys);
+}
+__global__ __launch_bounds__(256) void k_cl_gather_b(const ClRecJob *__restrict__ tab)
+{
+	const ClRecJob e = tab[blockIdx.y];
+	d_cl_gather(e.in, e.perm, e.out, e.n);
+}
 // ---------------------------------------------------------------------------------------------------------------------
 void launch_cl_grid(hipStream_t st, const ClArrays &A, const ClParams &P)
 {
@@ -867,4 +948,83 @@ void launch_cl_gather(hipStream_t st, const float4 *in, const uint32_t *perm, fl
 {
 	if (n)
 		hipLaunchKernelGGL(k_cl_gather, dim3((n + 255u) / 256u), dim3(256), 0, st, in, perm, out, n);
+}
+
+// ---- the same launch sequences for the scans of a table; each returns the kernels it launched ------------------------------------------
+#define CL_GO(...)                       \
+	do                                   \
+	{                                    \
+		hipLaunchKernelGGL(__VA_ARGS__); \
+		k++;                             \
+	} while (0)
+int launch_cl_grid_batch(hipStream_t st, const ClScan *tab, uint32_t count, uint32_t n_max, const ClParams &P)
+{
+	// (the grid's start keys and the zeroed cell counters are the caller's: one fill for all scans)
+	const uint32_t nb = (n_max + 255u) / 256u, max_seg = (MULLS_CL_MAX_CELLS + 1u + CL_SEG - 1u) / CL_SEG;
+	int k = 0;
+	CL_GO(k_cl_bbox_b, dim3(min(nb, 256u), count), dim3(256), 0, st, tab);
+	CL_GO(k_cl_setup_b, dim3(1, count), dim3(1), 0, st, tab, P.radius);
+	CL_GO(k_cl_count_b, dim3(nb, count), dim3(256), 0, st, tab);
+	CL_GO(k_cl_scan_seg_b, dim3(max_seg, count), dim3(256), 0, st, tab);
+	CL_GO(k_cl_scan_top_b, dim3(1, count), dim3(1024), 0, st, tab);
+	CL_GO(k_cl_scan_apply_b, dim3(max_seg, count), dim3(256), 0, st, tab);
+	CL_GO(k_cl_scatter_b, dim3(nb, count), dim3(256), 0, st, tab);
+	return k;
+}
+int launch_cl_pca_batch(hipStream_t st, const ClScan *tab, uint32_t count, uint32_t n_max, const ClParams &P)
+{
+	const uint32_t nq = (n_max + (uint32_t)P.down_rate - 1u) / (uint32_t)P.down_rate;
+	int k = 0;
+	CL_GO(k_cl_knn_b, dim3((nq + 3u) / 4u, count), dim3(256), 0, st, tab, P);
+	CL_GO(k_cl_eig_b, dim3((nq + 255u) / 256u, count), dim3(256), 0, st, tab, P);
+	return k;
+}
+int launch_cl_label_batch(hipStream_t st, const ClScan *tab, uint32_t count, uint32_t n_max, const ClParams &P)
+{
+	hipLaunchKernelGGL(k_cl_label_b, dim3((n_max + 255u) / 256u, count), dim3(256), 0, st, tab, P);
+	return 1;
+}
+int launch_cl_promote_round_batch(hipStream_t st, const ClScan *tab, uint32_t count, uint32_t n_max, const ClParams &P, uint32_t *round_cnt)
+{
+	hipLaunchKernelGGL(k_cl_promote_b, dim3((n_max + 255u) / 256u, count), dim3(256), 0, st, tab, P, round_cnt);
+	return 1;
+}
+int launch_cl_encode_batch(hipStream_t st, const ClScan *tab, uint32_t count, uint32_t n_max, const ClParams &P)
+{
+	hipLaunchKernelGGL(k_cl_encode_b, dim3((n_max + 255u) / 256u, count), dim3(256), 0, st, tab, P);
+	return 1;
+}
+int launch_cl_nms_lists_batch(hipStream_t st, const ClNmsArgs *tab, uint32_t count, uint32_t nmax, uint32_t *round_cnt)
+{
+	const uint32_t nb = nmax ? (nmax + 255u) / 256u : 1u;
+	int k = 0;
+	CL_GO(k_cl_nms_init_b, dim3(nb, 4, count), dim3(256), 0, st, tab, round_cnt);
+	if (nmax)
+	{
+		CL_GO(k_cl_nms_lists_b, dim3(nb * (nb + 1u) / 2u, 4, count), dim3(256), 0, st, tab, round_cnt);
+		CL_GO(k_cl_nms_reserve_b, dim3(nb, 4, count), dim3(256), 0, st, tab, round_cnt);
+		CL_GO(k_cl_nms_lists_long_b, dim3(nb * (nb + 1u) / 2u, 4, count), dim3(256), 0, st, tab, round_cnt);
+	}
+	return k;
+}
+int launch_cl_nms_round_batch(hipStream_t st, const ClNmsArgs *tab, uint32_t count, uint32_t nmax, uint32_t *round_cnt)
+{
+	if (!nmax)
+		return 0;
+	hipLaunchKernelGGL(k_cl_nms_round_b, dim3((nmax + 255u) / 256u, 4, count), dim3(256), 0, st, tab, round_cnt);
+	return 1;
+}
+int launch_cl_keys_batch(hipStream_t st, const ClRecJob *tab, uint32_t count, uint32_t n_max)
+{
+	if (!count || !n_max)
+		return 0;
+	hipLaunchKernelGGL(k_cl_keys_b, dim3((n_max + 255u) / 256u, count), dim3(256), 0, st, tab);
+	return 1;
+}
+int launch_cl_gather_batch(hipStream_t st, const ClRecJob *tab, uint32_t count, uint32_t n_max)
+{
+	if (!count || !n_max)
+		return 0;
+	hipLaunchKernelGGL(k_cl_gather_b, dim3((n_max + 255u) / 256u, count), dim3(256), 0, st, tab);
+	return 1;
 }

@@ -22,6 +22,8 @@
 //   k_gf_normals   normal methods 1 / 2 (:1943-1954 -> pca.hpp:66-119, :462-475), k_ground_normals.hip
 //   k_gf_scan      prefix sums over the blocks and the segments' high points
 //   k_gf_write     stable compaction into the output clouds; the kept high points first (input order) in the non-ground cloud
+// Each of them is written once as a __device__ body (d_gf_*) and launched in two forms, see "The kernels" below: k_gf_* for one scan (arguments by value) and
+// k_gf_*_b for the scans of a table in device memory (mulls_extract_features_batch).
 #include <algorithm>
 
 #include "../../include/mulls_hip.h"
@@ -30,22 +32,7 @@
 #include "pca_device.h"
 #include "scan_math.h"
 
-#define MULLS_GF_BLOCK 256
-#define MULLS_GF_SEG 1024u // points per segment (one wave walks a segment in 16 steps of 64)
 #define MULLS_GF_STAGE 4096u // z samples staged per round (k_gf_setup)
-
-struct GfState // device-resident state of one call; the head (GfOut) is read back by the host
-{
-	uint32_t n_ground, n_unground, n_high, error; // error: 1 = grid too large
-	uint32_t row, col;
-	float mean_height;
-	uint32_t n_cand;
-	// ---- device only
-	uint32_t box[4]; // ordered keys: min x, min y, max x, max y
-	float thre;		 // non_ground_height_thre
-	int num_grid;
-	double min_x, min_y;
-};
 
 namespace
 {
@@ -128,7 +115,7 @@ __device__ __forceinline__ GfTables gf_tables(uint32_t *arena, uint32_t nc, uint
 }
 } // namespace
 
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_bbox(const float4 *__restrict__ pts, uint32_t n, GfState *S)
+__device__ __forceinline__ void d_gf_bbox(const float4 *__restrict__ pts, uint32_t n, GfState *S)
 {
 	float mnx = __builtin_inff(), mny = __builtin_inff(), mxx = -__builtin_inff(), mxy = -__builtin_inff();
 	for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < n; j += gridDim.x * blockDim.x)
@@ -171,7 +158,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_bbox(const float4 *__rest
 	}
 }
 
-__global__ __launch_bounds__(512) void k_gf_setup(const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, GfState *S, uint32_t max_cells)
+__device__ __forceinline__ void d_gf_setup(const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, GfState *S, uint32_t max_cells)
 {
 	__shared__ float s_stage[MULLS_GF_STAGE];
 	__shared__ float s_sum;
@@ -225,7 +212,7 @@ __global__ __launch_bounds__(512) void k_gf_setup(const float4 *__restrict__ pts
 	}
 }
 
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_init(const GfState *S, uint32_t *arena, uint32_t ns)
+__device__ __forceinline__ void d_gf_init(const GfState *S, uint32_t *arena, uint32_t ns)
 {
 	const uint32_t nc = (uint32_t)S->num_grid;
 	const GfTables t = gf_tables(arena, nc, ns);
@@ -241,7 +228,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_init(const GfState *S, ui
 
 // one wave per segment; mode 0: counts (k_gf_count), mode 1: stable scatter + kept high points per segment (k_gf_scatter)
 template <int MODE>
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_walk(const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, const GfState *S, uint32_t *arena,
+__device__ __forceinline__ void d_gf_walk(const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, const GfState *S, uint32_t *arena,
 															 uint32_t ns, uint32_t *__restrict__ ids, uint16_t *__restrict__ cellof, uint32_t *__restrict__ seg_high)
 {
 	const uint32_t nc = (uint32_t)S->num_grid;
@@ -331,7 +318,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_walk(const float4 *__rest
 }
 
 // per cell: counts of the segments -> candidates in the segments before; cell starts.  One workgroup of 1024 lanes.
-__global__ __launch_bounds__(1024) void k_gf_prefix(GfState *S, uint32_t *arena, uint32_t ns)
+__device__ __forceinline__ void d_gf_prefix(GfState *S, uint32_t *arena, uint32_t ns)
 {
 	__shared__ uint32_t s_scan[16];
 	const uint32_t nc = (uint32_t)S->num_grid;
@@ -388,7 +375,7 @@ __global__ __launch_bounds__(1024) void k_gf_prefix(GfState *S, uint32_t *arena,
 }
 
 // per cell: min_z; no outlier threshold yet
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_cells1(const GfState *S, uint32_t *arena, uint32_t ns)
+__device__ __forceinline__ void d_gf_cells1(const GfState *S, uint32_t *arena, uint32_t ns)
 {
 	const uint32_t nc = (uint32_t)S->num_grid;
 	const GfTables t = gf_tables(arena, nc, ns);
@@ -401,7 +388,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_cells1(const GfState *S, 
 
 // the optional grid-wise outlier threshold (:1770-1790): mean and standard deviation of the cell's z in double, summed in the list's
 // order.  One wave per cell: 64 values are gathered at once, lane 0 adds them one after the other (readlane) — the reference's order.
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_outlier(const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns,
+__device__ __forceinline__ void d_gf_outlier(const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns,
 																 const uint32_t *__restrict__ ids)
 {
 	const uint32_t nc = (uint32_t)S->num_grid;
@@ -452,7 +439,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_outlier(const float4 *__r
 }
 
 // per cell: 3x3 neighbourhood minimum, reliable neighbours, verdict (:1795-1812, :1834, :1853)
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_cells2(mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns)
+__device__ __forceinline__ void d_gf_cells2(mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns)
 {
 	const uint32_t nc = (uint32_t)S->num_grid;
 	const GfTables t = gf_tables(arena, nc, ns);
@@ -480,7 +467,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_cells2(mulls_ground_param
 }
 
 // per sorted entry: verdict (:1853-1907); per-block counts of ground / non-ground entries
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_verdict(const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns,
+__device__ __forceinline__ void d_gf_verdict(const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns,
 																 const uint32_t *__restrict__ ids, const uint16_t *__restrict__ cellof, uint8_t *__restrict__ code,
 																 float *__restrict__ d3v, uint32_t *__restrict__ blk_cnt)
 {
@@ -557,7 +544,7 @@ namespace
 __device__ __forceinline__ float plane_dot(float c0, float c1, float c2, float c3, float x, float y, float z, float w) { return (c0 * x + c2 * z) + (c1 * y + c3 * w); }
 __device__ __forceinline__ float rl_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 } // namespace
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_ransac(const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns,
+__device__ __forceinline__ void d_gf_ransac(const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns,
 															   const uint32_t *__restrict__ ids, uint8_t *__restrict__ code, GfRansac X)
 {
 	__shared__ uint32_t s_sel[MULLS_GF_BLOCK / 64][8];
@@ -749,7 +736,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_ransac(const float4 *__re
 		X.cell_nrm[c] = make_float4(r0, r1, r2, 0.0f);
 }
 // ... and the per-block count of ground entries once more (k_gf_verdict counted none of them)
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_recount(const GfState *S, const uint8_t *__restrict__ code, uint32_t *__restrict__ blk_cnt)
+__device__ __forceinline__ void d_gf_recount(const GfState *S, const uint8_t *__restrict__ code, uint32_t *__restrict__ blk_cnt)
 {
 	__shared__ uint32_t s_cnt;
 	const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -765,7 +752,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_recount(const GfState *S,
 }
 
 // exclusive prefix sums: blk_cnt[nblk][2] and seg_high[ns] in place; totals into the state.  One workgroup of 1024 lanes.
-__global__ __launch_bounds__(1024) void k_gf_scan(GfState *S, uint32_t *__restrict__ blk_cnt, uint32_t nblk, uint32_t *__restrict__ seg_high, uint32_t ns)
+__device__ __forceinline__ void d_gf_scan(GfState *S, uint32_t *__restrict__ blk_cnt, uint32_t nblk, uint32_t *__restrict__ seg_high, uint32_t ns)
 {
 	__shared__ uint32_t s_scan[16];
 	__shared__ uint32_t s_tot[3];
@@ -817,7 +804,7 @@ __global__ __launch_bounds__(1024) void k_gf_scan(GfState *S, uint32_t *__restri
 }
 
 // stable compaction of the sorted entries into the two output clouds (positions: block base + rank inside the block)
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_write(const float4 *__restrict__ pts, const GfState *S, const uint32_t *__restrict__ ids,
+__device__ __forceinline__ void d_gf_write(const float4 *__restrict__ pts, const GfState *S, const uint32_t *__restrict__ ids,
 															   const uint8_t *__restrict__ code, const float *__restrict__ d3v, const uint32_t *__restrict__ blk_base,
 															   float4 *__restrict__ ground, float4 *__restrict__ unground, int normal_method,
 															   const uint16_t *__restrict__ cellof, const float4 *__restrict__ cell_nrm)
@@ -866,7 +853,7 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_write(const float4 *__res
 }
 
 // the kept high points, in input order, at the head of the non-ground cloud: one wave per segment from its base
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_write_high(const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, const GfState *S, uint32_t *arena,
+__device__ __forceinline__ void d_gf_write_high(const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, const GfState *S, uint32_t *arena,
 																	uint32_t ns, const uint32_t *__restrict__ seg_base, float4 *__restrict__ unground)
 {
 	const uint32_t nc = (uint32_t)S->num_grid;
@@ -909,19 +896,110 @@ __global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_write_high(const float4 *
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Arena of uint32 words behind the scan-sized arrays: state | seg_high[ns] | blk_cnt[2 * nblk] | tables (8 * MAXCELLS + 1 + ns * MAXCELLS ... bounded below)
-static size_t gf_cell_room(uint32_t n)
+
+// ---------------------------------------------------------------------------------------------------------------
+// The kernels: every body above once with its arguments by value (one scan: launch_ground_filter) and once with the arguments of the scan at
+// blockIdx.y of a table in device memory (mulls_extract_features_batch: launch_ground_filter_batch).  The table entry is wave-uniform: scalar loads.
+namespace
 {
-	// the per-segment tables take ns * nc words; nc is only known on the device: room for min(MAXCELLS, 64 M words / ns) cells
-	const size_t ns = (n + MULLS_GF_SEG - 1) / MULLS_GF_SEG;
-	return std::min<size_t>(MULLS_GF_MAXCELLS, ((size_t)64 << 20) / std::max<size_t>(ns, 1));
-}
-size_t ground_filter_aux_bytes(uint32_t n)
+struct GfView // where the pieces of a scan's aux arena are (launch_ground_filter's arithmetic)
 {
-	const size_t ns = (n + MULLS_GF_SEG - 1) / MULLS_GF_SEG, nblk = (n + MULLS_GF_BLOCK - 1) / MULLS_GF_BLOCK;
-	const size_t nc_room = gf_cell_room(n);
-	return sizeof(GfState) + 64 + (ns + 2 * nblk + 16 + 8 * (size_t)MULLS_GF_MAXCELLS + ns * nc_room) * sizeof(uint32_t);
+	GfState *S;
+	uint32_t *seg_high, *blk_cnt, *arena;
+	uint32_t ns, nblk;
+};
+__host__ __device__ __forceinline__ GfView gf_view(void *aux, uint32_t n)
+{
+	GfView v;
+	v.ns = (n + MULLS_GF_SEG - 1) / MULLS_GF_SEG, v.nblk = (n + MULLS_GF_BLOCK - 1) / MULLS_GF_BLOCK;
+	v.S = static_cast<GfState *>(aux);
+	v.seg_high = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(aux) + ((sizeof(GfState) + 63) & ~(size_t)63));
+	v.blk_cnt = v.seg_high + v.ns;
+	v.arena = v.blk_cnt + 2 * v.nblk + 16;
+	return v;
 }
+} // namespace
+__device__ __forceinline__ uint32_t gf_cell_room_dev(uint32_t ns) // gf_cell_room (ground_launch.h)
+{
+	const uint32_t room = (64u << 20) / (ns ? ns : 1u);
+	return room < MULLS_GF_MAXCELLS ? room : MULLS_GF_MAXCELLS;
+}
+#define GF_ONE(name, bounds, params, args) \
+	__global__ __launch_bounds__(bounds) void name params { args; }
+// a lock-step kernel: `limit` workgroups of the launch belong to the scan (the launch is as wide as the widest scan needs)
+#define GF_BATCH(name, bounds, extra, limit, call)                                 \
+	__global__ __launch_bounds__(bounds) void name(const GfScan *__restrict__ tab extra) \
+	{                                                                              \
+		const GfScan e = tab[blockIdx.y];                                          \
+		if (!e.n)                                                                  \
+			return;                                                                \
+		const GfView v = gf_view(e.aux, e.n);                                      \
+		if (blockIdx.x >= (limit))                                                 \
+			return;                                                                \
+		call;                                                                      \
+	}
+#define GF_COMMA ,
+#define GF_SEGB ((v.ns + MULLS_GF_BLOCK / 64 - 1) / (MULLS_GF_BLOCK / 64))
+GF_ONE(k_gf_bbox, MULLS_GF_BLOCK, (const float4 *__restrict__ pts, uint32_t n, GfState *S), d_gf_bbox(pts, n, S))
+GF_ONE(k_gf_setup, 512, (const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, GfState *S, uint32_t max_cells), d_gf_setup(pts, n, P, S, max_cells))
+GF_ONE(k_gf_init, MULLS_GF_BLOCK, (const GfState *S, uint32_t *arena, uint32_t ns), d_gf_init(S, arena, ns))
+template <int MODE>
+__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_walk(const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns,
+															 uint32_t *__restrict__ ids, uint16_t *__restrict__ cellof, uint32_t *__restrict__ seg_high)
+{
+	d_gf_walk<MODE>(pts, n, P, S, arena, ns, ids, cellof, seg_high);
+}
+GF_ONE(k_gf_prefix, 1024, (GfState * S, uint32_t *arena, uint32_t ns), d_gf_prefix(S, arena, ns))
+GF_ONE(k_gf_cells1, MULLS_GF_BLOCK, (const GfState *S, uint32_t *arena, uint32_t ns), d_gf_cells1(S, arena, ns))
+GF_ONE(k_gf_outlier, MULLS_GF_BLOCK, (const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns, const uint32_t *__restrict__ ids),
+	   d_gf_outlier(pts, P, S, arena, ns, ids))
+GF_ONE(k_gf_cells2, MULLS_GF_BLOCK, (mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns), d_gf_cells2(P, S, arena, ns))
+GF_ONE(k_gf_verdict, MULLS_GF_BLOCK,
+	   (const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns, const uint32_t *__restrict__ ids,
+		const uint16_t *__restrict__ cellof, uint8_t *__restrict__ code, float *__restrict__ d3v, uint32_t *__restrict__ blk_cnt),
+	   d_gf_verdict(pts, P, S, arena, ns, ids, cellof, code, d3v, blk_cnt))
+GF_ONE(k_gf_ransac, MULLS_GF_BLOCK,
+	   (const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns, const uint32_t *__restrict__ ids, uint8_t *__restrict__ code,
+		GfRansac X),
+	   d_gf_ransac(pts, P, S, arena, ns, ids, code, X))
+GF_ONE(k_gf_recount, MULLS_GF_BLOCK, (const GfState *S, const uint8_t *__restrict__ code, uint32_t *__restrict__ blk_cnt), d_gf_recount(S, code, blk_cnt))
+GF_ONE(k_gf_scan, 1024, (GfState * S, uint32_t *__restrict__ blk_cnt, uint32_t nblk, uint32_t *__restrict__ seg_high, uint32_t ns), d_gf_scan(S, blk_cnt, nblk, seg_high, ns))
+GF_ONE(k_gf_write, MULLS_GF_BLOCK,
+	   (const float4 *__restrict__ pts, const GfState *S, const uint32_t *__restrict__ ids, const uint8_t *__restrict__ code, const float *__restrict__ d3v,
+		const uint32_t *__restrict__ blk_base, float4 *__restrict__ ground, float4 *__restrict__ unground, int normal_method, const uint16_t *__restrict__ cellof,
+		const float4 *__restrict__ cell_nrm),
+	   d_gf_write(pts, S, ids, code, d3v, blk_base, ground, unground, normal_method, cellof, cell_nrm))
+GF_ONE(k_gf_write_high, MULLS_GF_BLOCK,
+	   (const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns, const uint32_t *__restrict__ seg_base,
+		float4 *__restrict__ unground),
+	   d_gf_write_high(pts, n, P, S, arena, ns, seg_base, unground))
+
+// the bounding box's start values, which the single call copies from the host
+__global__ void k_gf_box0_b(const GfScan *__restrict__ tab, uint32_t count)
+{
+	const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+	if (b >= count || !tab[b].n)
+		return;
+	GfState *S = static_cast<GfState *>(tab[b].aux);
+	S->box[0] = S->box[1] = 0xffffffffu;
+	S->box[2] = S->box[3] = 0u;
+}
+GF_BATCH(k_gf_bbox_b, MULLS_GF_BLOCK, , min(v.nblk, 64u), d_gf_bbox(e.pts, e.n, v.S))
+GF_BATCH(k_gf_setup_b, 512, GF_COMMA mulls_ground_params P, 1u, d_gf_setup(e.pts, e.n, P, v.S, gf_cell_room_dev(v.ns)))
+GF_BATCH(k_gf_init_b, MULLS_GF_BLOCK, , 512u, d_gf_init(v.S, v.arena, v.ns))
+template <int MODE>
+GF_BATCH(k_gf_walk_b, MULLS_GF_BLOCK, GF_COMMA mulls_ground_params P, GF_SEGB, d_gf_walk<MODE>(e.pts, e.n, P, v.S, v.arena, v.ns, e.ids, e.cellof, v.seg_high))
+GF_BATCH(k_gf_prefix_b, 1024, , 1u, d_gf_prefix(v.S, v.arena, v.ns))
+GF_BATCH(k_gf_cells1_b, MULLS_GF_BLOCK, , MULLS_GF_MAXCELLS / MULLS_GF_BLOCK, d_gf_cells1(v.S, v.arena, v.ns))
+GF_BATCH(k_gf_outlier_b, MULLS_GF_BLOCK, GF_COMMA mulls_ground_params P, MULLS_GF_MAXCELLS / (MULLS_GF_BLOCK / 64), d_gf_outlier(e.pts, P, v.S, v.arena, v.ns, e.ids))
+GF_BATCH(k_gf_cells2_b, MULLS_GF_BLOCK, GF_COMMA mulls_ground_params P, MULLS_GF_MAXCELLS / MULLS_GF_BLOCK, d_gf_cells2(P, v.S, v.arena, v.ns))
+GF_BATCH(k_gf_verdict_b, MULLS_GF_BLOCK, GF_COMMA mulls_ground_params P, v.nblk, d_gf_verdict(e.pts, P, v.S, v.arena, v.ns, e.ids, e.cellof, e.code, e.d3v, v.blk_cnt))
+GF_BATCH(k_gf_ransac_b, MULLS_GF_BLOCK, GF_COMMA mulls_ground_params P, MULLS_GF_MAXCELLS / (MULLS_GF_BLOCK / 64), d_gf_ransac(e.pts, P, v.S, v.arena, v.ns, e.ids, e.code, e.R))
+GF_BATCH(k_gf_recount_b, MULLS_GF_BLOCK, , v.nblk, d_gf_recount(v.S, e.code, v.blk_cnt))
+GF_BATCH(k_gf_scan_b, 1024, , 1u, d_gf_scan(v.S, v.blk_cnt, v.nblk, v.seg_high, v.ns))
+GF_BATCH(k_gf_write_b, MULLS_GF_BLOCK, GF_COMMA int normal_method, v.nblk,
+		 d_gf_write(e.pts, v.S, e.ids, e.code, e.d3v, v.blk_cnt, e.ground, e.unground, normal_method, e.cellof, e.R.cell_nrm))
+GF_BATCH(k_gf_write_high_b, MULLS_GF_BLOCK, GF_COMMA mulls_ground_params P, GF_SEGB, d_gf_write_high(e.pts, e.n, P, v.S, v.arena, v.ns, v.seg_high, e.unground))
 
 int launch_ground_filter(hipStream_t st, const float4 *pts, uint32_t n, const mulls_ground_params &P, uint32_t *ids, uint16_t *cellof, uint8_t *code, float *d3v,
 						 float4 *ground, float4 *unground, void *aux, const GfRansac &R)
@@ -958,11 +1036,51 @@ int launch_ground_filter(hipStream_t st, const float4 *pts, uint32_t n, const mu
 	return 0;
 }
 
+#define GF_GO(...)                      \
+	do                                  \
+	{                                   \
+		hipLaunchKernelGGL(__VA_ARGS__); \
+		k++;                            \
+	} while (0)
+int launch_ground_filter_batch(hipStream_t st, const GfScan *tab, const GfScan *tab_host, uint32_t count, const mulls_ground_params &P)
+{
+	uint32_t n_max = 0;
+	for (uint32_t b = 0; b < count; b++)
+		n_max = std::max(n_max, tab_host[b].n);
+	if (!n_max)
+		return 0;
+	const uint32_t ns = (n_max + MULLS_GF_SEG - 1) / MULLS_GF_SEG, nblk = (n_max + MULLS_GF_BLOCK - 1) / MULLS_GF_BLOCK;
+	const uint32_t seg_blocks = (ns + MULLS_GF_BLOCK / 64 - 1) / (MULLS_GF_BLOCK / 64);
+	const dim3 B(MULLS_GF_BLOCK);
+	int k = 0;
+	GF_GO(k_gf_box0_b, dim3((count + 63u) / 64u), dim3(64), 0, st, tab, count);
+	GF_GO(k_gf_bbox_b, dim3(std::min<uint32_t>(nblk, 64u), count), B, 0, st, tab);
+	GF_GO(k_gf_setup_b, dim3(1, count), dim3(512), 0, st, tab, P);
+	GF_GO(k_gf_init_b, dim3(512, count), B, 0, st, tab);
+	GF_GO(k_gf_walk_b<0>, dim3(seg_blocks, count), B, 0, st, tab, P);
+	GF_GO(k_gf_prefix_b, dim3(1, count), dim3(1024), 0, st, tab);
+	GF_GO(k_gf_walk_b<1>, dim3(seg_blocks, count), B, 0, st, tab, P);
+	GF_GO(k_gf_cells1_b, dim3(MULLS_GF_MAXCELLS / MULLS_GF_BLOCK, count), B, 0, st, tab);
+	if (P.apply_grid_wise_outlier_filter)
+		GF_GO(k_gf_outlier_b, dim3(MULLS_GF_MAXCELLS / (MULLS_GF_BLOCK / 64), count), B, 0, st, tab, P);
+	GF_GO(k_gf_cells2_b, dim3(MULLS_GF_MAXCELLS / MULLS_GF_BLOCK, count), B, 0, st, tab, P);
+	GF_GO(k_gf_verdict_b, dim3(nblk, count), B, 0, st, tab, P);
+	if (P.estimate_ground_normal_method == 3)
+	{
+		GF_GO(k_gf_ransac_b, dim3(MULLS_GF_MAXCELLS / (MULLS_GF_BLOCK / 64), count), B, 0, st, tab, P);
+		GF_GO(k_gf_recount_b, dim3(nblk, count), B, 0, st, tab);
+	}
+	GF_GO(k_gf_scan_b, dim3(1, count), dim3(1024), 0, st, tab);
+	GF_GO(k_gf_write_b, dim3(nblk, count), B, 0, st, tab, (int)P.estimate_ground_normal_method);
+	GF_GO(k_gf_write_high_b, dim3(seg_blocks, count), B, 0, st, tab, P);
+	return k;
+}
+
 // The per-point filters ahead of the ground filter as one keep mask (both keep the order, so their sequence is the AND of their tests):
 // CFilter::dist_filter(cloud, xy_dist_min, xy_dist_max) (cfilter.hpp:806-832: float range expression widened to double, double limits) and
 // CFilter::scanner_filter (cfilter.hpp:914-929: the ego vehicle's ring and the underground ghost points near the scanner).
 // mask[i] = 1 keeps point i; the stable compaction is map_kernels.hip's.
-__global__ __launch_bounds__(256) void k_raw_mask(const float4 *__restrict__ pts, uint32_t n, RawMaskArgs a, uint8_t *__restrict__ mask)
+__device__ __forceinline__ void d_raw_mask(const float4 *__restrict__ pts, uint32_t n, RawMaskArgs a, uint8_t *__restrict__ mask)
 {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= n)
@@ -980,6 +1098,17 @@ __global__ __launch_bounds__(256) void k_raw_mask(const float4 *__restrict__ pts
 		keep = keep && k2;
 	}
 	mask[i] = keep ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void k_raw_mask(const float4 *__restrict__ pts, uint32_t n, RawMaskArgs a, uint8_t *__restrict__ mask) { d_raw_mask(pts, n, a, mask); }
+__global__ __launch_bounds__(256) void k_raw_mask_b(const RawMaskJob *__restrict__ tab, RawMaskArgs a)
+{
+	const RawMaskJob e = tab[blockIdx.y];
+	d_raw_mask(e.pts, e.n, a, e.mask); // (returns past e.n)
+}
+void launch_raw_mask_batch(hipStream_t st, const RawMaskJob *tab, uint32_t count, uint32_t n_max, const RawMaskArgs &a)
+{
+	if (n_max && count)
+		hipLaunchKernelGGL(k_raw_mask_b, dim3((n_max + 255u) / 256u, count), dim3(256), 0, st, tab, a);
 }
 void launch_raw_mask(hipStream_t st, const float4 *pts, uint32_t n, const RawMaskArgs &a, uint8_t *mask)
 {

@@ -212,10 +212,7 @@ __global__ __launch_bounds__(256) void k_gf_normals(float4 *__restrict__ ground,
 }
 
 // scratch layout: ClGrid | seg_sum | cellof[n] | cell_start | cell_fill | sorted[n]
-size_t ground_normals_bytes(uint32_t n)
-{
-	return 256 + 1040 * 4 + (size_t)n * 4 + 2 * ((size_t)MULLS_CL_MAX_CELLS + 2) * 4 + 64 + (size_t)n * 16 + 256;
-}
+static_assert(MULLS_CL_MAX_CELLS == (1u << 22), "ground_normals_bytes (ground_launch.h) spells the cell limit out");
 void launch_ground_normals(hipStream_t st, float4 *ground, uint32_t n, float radius, int k, void *grid_mem, uint32_t *error)
 {
 	if (!n)

@@ -31,6 +31,14 @@ struct MapBoxArgs
 // seg_scratch: device array of at least map_compact_segments(a) uint32 (one counter per 4096-record segment)
 uint32_t map_compact_segments(const MapCompactArgs &a);
 void launch_map_compact(hipStream_t st, const MapCompactArgs &a, uint32_t *seg_scratch);
+// the same three steps for `count` sets of clouds in one launch each (mulls_extract_features_batch): a table in device memory, one entry per set (blockIdx.y),
+// every set with its own segment scratch; tab_host: the table's host copy.  Returns the kernels launched.
+struct MapCompactJob
+{
+	MapCompactArgs a;
+	uint32_t *seg;
+};
+int launch_map_compact_batch(hipStream_t st, const MapCompactJob *tab_dev, const MapCompactJob *tab_host, uint32_t count);
 void launch_map_bbox(hipStream_t st, const MapBoxArgs &a);
 // nearest tree point of every frame point: best[i] = float bits of the smallest squared distance (0x7f800000 if the tree
 // is empty); tree = map class cloud, optionally restricted to the open box (strict inequalities, float vs double)

@@ -8,9 +8,9 @@ namespace
 // Rounds of a settle-until-nothing-is-undecided loop: launch(slot) runs one round that adds the points it leaves undecided to round_cnt[slot].  A round over
 // a settled state changes nothing, so rounds are launched in batches and the counters read once per batch — the first batch as long as the previous call's
 // loop turned out to be (+ 2: consecutive frames need about the same), further ones `step` rounds: one wait per loop instead of one per `step` rounds (28 us
-// each on the frame path).  All 64 counters come down, so the round that settled is known and the hint follows the data both ways.
+// each on the frame path).  n_waits counts the waits (the statistics of mulls_extract_features_batch).  All 64 counters come down, so the round that settled is known and the hint follows the data both ways.
 template <class Launch>
-int run_rounds(mulls_ctx *ctx, hipStream_t st, uint32_t *round_cnt, uint32_t step, uint32_t *hint, const Launch &launch, const char *what)
+int run_rounds(mulls_ctx *ctx, hipStream_t st, uint32_t *round_cnt, uint32_t step, uint32_t *hint, const Launch &launch, const char *what, uint32_t *n_waits = nullptr)
 {
 	uint32_t h[64];
 	// a multiple of `step` (4 or 8; 32 is one of both), so that `round` stays one and the reset below meets every multiple of 64
@@ -22,6 +22,8 @@ int run_rounds(mulls_ctx *ctx, hipStream_t st, uint32_t *round_cnt, uint32_t ste
 			launch(round & 63u);
 		HIPCHK(ctx, hipMemcpyAsync(h, round_cnt, sizeof(h), hipMemcpyDeviceToHost, st));
 		HIPCHK(ctx, hipStreamSynchronize(st));
+		if (n_waits)
+			++*n_waits;
 		if (h[(round - 1u) & 63u] == 0)
 		{
 			uint32_t needed = round;

@@ -96,6 +96,8 @@ def load():
     lib.mulls_block_destroy.argtypes = [vp, vp]
     lib.mulls_block_destroy.restype = None
     lib.mulls_extract_features_resident.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(abi.ExtractParams), vp, C.POINTER(C.c_uint32)]
+    lib.mulls_extract_features_batch.argtypes = [vp, C.POINTER(abi.Cloud), C.c_uint32, C.POINTER(abi.ExtractParams), C.POINTER(vp), C.c_uint64,
+                                                 C.POINTER(abi.ExtractBatchResult), C.POINTER(abi.ExtractBatchStats)]
     lib.mulls_block_cloud.argtypes = [vp, vp, C.c_int, C.POINTER(abi.Cloud)]
     lib.mulls_block_download.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_motion_compensate.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.c_float]
@@ -177,7 +179,7 @@ EXPORTS = [
     "mulls_map_cloud", "mulls_map_pose", "mulls_map_download", "mulls_map_frame_download", "mulls_io_read_kitti_bin", "mulls_io_read_pcd",
     "mulls_io_write_pcd", "mulls_io_write_pose", "mulls_ground_default_params", "mulls_ground_filter",
     "mulls_classify_default_params", "mulls_classify_nground", "mulls_extract_default_params", "mulls_extract_features", "mulls_voxel_downsample",
-    "mulls_set_option", "mulls_get_option", "mulls_block_create", "mulls_block_destroy", "mulls_extract_features_resident", "mulls_block_cloud", "mulls_block_download",
+    "mulls_set_option", "mulls_get_option", "mulls_block_create", "mulls_block_destroy", "mulls_extract_features_resident", "mulls_extract_features_batch", "mulls_block_cloud", "mulls_block_download",
     "mulls_motion_compensate", "mulls_block_motion_compensate",
     "mulls_pack_results", "mulls_icp_batch_sharded", "mulls_pipe_create", "mulls_pipe_destroy", "mulls_pipe_depth", "mulls_pipe_ctx", "mulls_pipe_set_option", "mulls_icp_batch_begin", "mulls_icp_batch_end",
     "mulls_ncc_default_params", "mulls_ncc_correspond", "mulls_ncc_correspond_batch",
@@ -446,6 +448,32 @@ class Context:
         if not voxels:
             res[abi.EX_DOWN] = res[abi.EX_RAW]
         return res
+
+    def extract_features_batch(self, scans, params, blocks=None, scratch_limit_bytes=0, check=True):
+        """mulls_extract_features_batch: extract_semantic_pts' chain on many scans per call, in lock step on the device, the feature clouds left in one Block per scan.
+        scans: record arrays (abi.records takes them) or abi.Cloud structures (device-resident clouds, strided host records).  Returns (blocks, results, stats):
+        the Blocks (created here when none are given), one abi.ExtractBatchResult per scan, the abi.ExtractBatchStats.  check=False: a refused scan does not raise;
+        the call's code is left in self.last_batch_rc."""
+        n = len(scans)
+        keep, clouds = [], (abi.Cloud * max(n, 1))()
+        for i, sc in enumerate(scans):
+            if isinstance(sc, abi.Cloud):
+                clouds[i] = sc
+                continue
+            raw = abi.records(sc)
+            keep.append(raw)
+            clouds[i].pts, clouds[i].n, clouds[i].stride = raw.ctypes.data if len(raw) else None, len(raw), abi.POINT_BYTES
+        if blocks is None:
+            blocks = [Block(self) for _ in range(n)]
+        handles = (C.c_void_p * max(n, 1))(*[b.h for b in blocks])
+        results = (abi.ExtractBatchResult * max(n, 1))()
+        stats = abi.ExtractBatchStats()
+        self.last_batch_rc = self.lib.mulls_extract_features_batch(self.h, clouds, n, C.byref(params), handles, int(scratch_limit_bytes), results, C.byref(stats))
+        for b, r in zip(blocks, results):
+            b.n = list(r.n_out)
+        if check:
+            self._check(self.last_batch_rc, "mulls_extract_features_batch")
+        return blocks, [results[i] for i in range(n)], stats
 
     def voxel_downsample(self, pts, voxel_size):
         """CFilter::voxel_downsample (cfilter.hpp:83-160).  Returns pc_down as (n, 48) uint8 records."""
