@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <array>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -392,17 +393,11 @@ inline uint64_t &map_rng_seed()
 	static uint64_t seed = 0;
 	return seed;
 }
-inline bool update_local_map(cloudblock_Ptr local_map, cloudblock_Ptr last_target_cblock, float local_map_radius = 80, int max_num_pts = 20000,
-							 int kept_vertex_num = 800, float last_frame_reliable_radius = 60, bool map_based_dynamic_removal_on = false,
-							 std::string used_feature_type = "111110", float dynamic_removal_center_radius = 30.0,
-							 float dynamic_dist_thre_min = 0.3, float dynamic_dist_thre_max = 3.0, float near_dist_thre = 0.03,
-							 bool recalculate_feature_on = false)
+// (the two halves of an update the single call and the batch share: the parameters of one map's update, and what goes back into the two blocks)
+inline mulls_map_params map_update_params(const MapMirror &mir, float local_map_radius, int max_num_pts, int kept_vertex_num, float last_frame_reliable_radius,
+										  bool map_based_dynamic_removal_on, const std::string &used_feature_type, float dynamic_removal_center_radius,
+										  float dynamic_dist_thre_min, float dynamic_dist_thre_max, float near_dist_thre, bool recalculate_feature_on)
 {
-	mulls_ctx *ctx = thread_context();
-	MapMirror &mir = attach_local_map(local_map);
-	cloudblock_t &f = *last_target_cblock;
-	const mulls_cloud frame[6] = {borrow(f.pc_ground_down), borrow(f.pc_pillar_down), borrow(f.pc_facade_down),
-								  borrow(f.pc_beam_down),	borrow(f.pc_roof_down),	  borrow(f.pc_vertex)};
 	mulls_map_params P;
 	mulls_map_default_params(&P);
 	P.local_map_radius = local_map_radius;
@@ -421,11 +416,10 @@ inline bool update_local_map(cloudblock_Ptr local_map, cloudblock_Ptr last_targe
 	P.tree_mode = mir.tree_mode;
 	std::memcpy(P.tree_used, mir.tree_used, sizeof(P.tree_used));
 	std::memcpy(P.tree_box, mir.tree_box, sizeof(P.tree_box));
-	mulls_map_report rep;
-	const int rc = mulls_map_update(ctx, mir.map, frame, f.pose_lo.data(), &P, &rep);
-	if (rc != MULLS_OK)
-		throw std::runtime_error(std::string("mulls_map_update failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
-
+	return P;
+}
+inline void map_update_take(mulls_ctx *ctx, MapMirror &mir, const mulls_map_report &rep, cloudblock_t &m, cloudblock_t &f)
+{
 	typedef typename std::remove_reference<decltype(*f.pc_ground_down)>::type Cloud;
 	auto fetch = [&](int (*fn)(mulls_ctx *, const mulls_map *, int, void *, uint32_t, uint32_t *), int cls, Cloud &dst, uint32_t n) {
 		dst.points.resize(n);
@@ -438,7 +432,6 @@ inline bool update_local_map(cloudblock_Ptr local_map, cloudblock_Ptr last_targe
 	Cloud *fd[5] = {f.pc_ground_down.get(), f.pc_pillar_down.get(), f.pc_facade_down.get(), f.pc_beam_down.get(), f.pc_roof_down.get()};
 	for (int c = 0; c < 5; c++)
 		fetch(mulls_map_frame_download, c, *fd[c], rep.frame_n[c]);
-	cloudblock_t &m = *local_map;
 	if (sync_host_map())
 	{
 		Cloud *mc[6] = {m.pc_ground.get(), m.pc_pillar.get(), m.pc_facade.get(), m.pc_beam.get(), m.pc_roof.get(), m.pc_vertex.get()};
@@ -455,6 +448,67 @@ inline bool update_local_map(cloudblock_Ptr local_map, cloudblock_Ptr last_targe
 	m.free_tree();								 // :132-133
 	m.free_raw_cloud();
 	mir.tree_mode = 0; // the kd-trees are gone until the next registration against this map
+}
+inline bool update_local_map(cloudblock_Ptr local_map, cloudblock_Ptr last_target_cblock, float local_map_radius = 80, int max_num_pts = 20000,
+							 int kept_vertex_num = 800, float last_frame_reliable_radius = 60, bool map_based_dynamic_removal_on = false,
+							 std::string used_feature_type = "111110", float dynamic_removal_center_radius = 30.0,
+							 float dynamic_dist_thre_min = 0.3, float dynamic_dist_thre_max = 3.0, float near_dist_thre = 0.03,
+							 bool recalculate_feature_on = false)
+{
+	mulls_ctx *ctx = thread_context();
+	MapMirror &mir = attach_local_map(local_map);
+	cloudblock_t &f = *last_target_cblock;
+	const mulls_cloud frame[6] = {borrow(f.pc_ground_down), borrow(f.pc_pillar_down), borrow(f.pc_facade_down),
+								  borrow(f.pc_beam_down),	borrow(f.pc_roof_down),	  borrow(f.pc_vertex)};
+	const mulls_map_params P = map_update_params(mir, local_map_radius, max_num_pts, kept_vertex_num, last_frame_reliable_radius, map_based_dynamic_removal_on,
+												 used_feature_type, dynamic_removal_center_radius, dynamic_dist_thre_min, dynamic_dist_thre_max, near_dist_thre,
+												 recalculate_feature_on);
+	mulls_map_report rep;
+	const int rc = mulls_map_update(ctx, mir.map, frame, f.pose_lo.data(), &P, &rep);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_map_update failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	map_update_take(ctx, mir, rep, *local_map, f);
+	return true;
+}
+
+// update_local_map for several streams at once (several drives replayed side by side, several vehicles): one (local map block, last target block) pair per
+// stream and update_local_map's trailing arguments, shared by all.  One mulls_map_update_batch call, every device step once for all streams (mulls_hip.h);
+// each stream gets what its own lo::hip::update_local_map call would have left in its two blocks, a seed of map_rng_seed()'s sequence in the streams' order
+// included.  The blocks must be distinct.
+inline bool update_local_map_batch(const std::vector<std::pair<cloudblock_Ptr, cloudblock_Ptr>> &streams, float local_map_radius = 80, int max_num_pts = 20000,
+								   int kept_vertex_num = 800, float last_frame_reliable_radius = 60, bool map_based_dynamic_removal_on = false,
+								   std::string used_feature_type = "111110", float dynamic_removal_center_radius = 30.0,
+								   float dynamic_dist_thre_min = 0.3, float dynamic_dist_thre_max = 3.0, float near_dist_thre = 0.03,
+								   bool recalculate_feature_on = false)
+{
+	mulls_ctx *ctx = thread_context();
+	const size_t n = streams.size();
+	std::vector<MapMirror *> mirs(n);
+	std::vector<std::array<mulls_cloud, 6>> frames(n);
+	std::vector<mulls_map_params> params(n);
+	std::vector<mulls_map_update_item> items(n);
+	std::vector<mulls_map_batch_result> results(n);
+	for (size_t i = 0; i < n; i++)
+	{
+		mirs[i] = &attach_local_map(streams[i].first); // (std::map: a reference stays valid while others are inserted)
+		cloudblock_t &f = *streams[i].second;
+		frames[i] = {borrow(f.pc_ground_down), borrow(f.pc_pillar_down), borrow(f.pc_facade_down), borrow(f.pc_beam_down), borrow(f.pc_roof_down), borrow(f.pc_vertex)};
+		params[i] = map_update_params(*mirs[i], local_map_radius, max_num_pts, kept_vertex_num, last_frame_reliable_radius, map_based_dynamic_removal_on,
+									  used_feature_type, dynamic_removal_center_radius, dynamic_dist_thre_min, dynamic_dist_thre_max, near_dist_thre,
+									  recalculate_feature_on);
+	}
+	for (size_t i = 0; i < n; i++)
+	{
+		items[i].map = mirs[i]->map;
+		items[i].frame_down = frames[i].data();
+		std::memcpy(items[i].frame_pose_lo, streams[i].second->pose_lo.data(), sizeof(items[i].frame_pose_lo));
+		items[i].params = &params[i];
+	}
+	const int rc = mulls_map_update_batch(ctx, items.data(), (uint32_t)n, nullptr, 0, results.data(), nullptr);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_map_update_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (size_t i = 0; i < n; i++)
+		map_update_take(ctx, *mirs[i], results[i].report, *streams[i].first, *streams[i].second);
 	return true;
 }
 

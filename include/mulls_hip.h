@@ -394,6 +394,46 @@ int mulls_map_set(mulls_ctx *ctx, mulls_map *map, const mulls_cloud clouds[6], c
  * filters last_target_cblock->pc_*_down in place: mulls_map_frame_download returns that state). */
 int mulls_map_update(mulls_ctx *ctx, mulls_map *map, const mulls_cloud frame_down[6], const double frame_pose_lo[16],
 					 const mulls_map_params *params, mulls_map_report *report);
+/* Many maps, one update each, in lock step (map_batch.cpp): whoever drives several sequences side by side — a dataset's drives replayed together, several
+ * vehicles, a parameter sweep over one drive — runs mulls_extract_features_batch and mulls_icp_batch for all streams and then this.
+ *
+ * What every item gets: the bytes of its own mulls_map_update call — every record of the six class clouds, the six frame clouds mulls_map_frame_download
+ * returns, the pose, the status and every field of the report except ms_total (here: the wall time of the item's group) — whatever the batch size, the item's
+ * position, the other items and the cuts into groups are.  Parameters are per item (params; NULL: shared_params); nothing assumes they are shared.
+ *
+ * Lock step: the items are cut into groups of max_lockstep (0: 64, which keeps the pinned staging of KITTI-sized frames near 20 MB).  Within a group every
+ * device step of the update runs once for all items — one launch, or one fixed launch set, whose workgroups find their map, class and block in a table in
+ * device memory, the grid being the sum of the items' work — and every host wait of the single path happens at most once: behind the dynamic removal (only if
+ * some item's removal runs), behind dist_filter, and behind the bounds and the pillar / beam refresh together.  The thinning masks of all maps are computed
+ * on the host after the one read of dist_filter's counts and go up in one copy.  Each map keeps its own buffers; a buffer that has to grow is replaced at once
+ * and the old one freed behind the phase's wait, so growth costs no wait.  stats->n_syncs and n_kernel_launches do not depend on the number of items in a group.
+ *
+ * Refused before anything is written (MULLS_E_INVALID; maps and results untouched): NULL items or results, a NULL or repeated map, a map of another context,
+ * a frame_down cloud that lies in the memory of a map this batch updates, an item without params while shared_params is NULL.
+ * Refused per item: a NULL frame_down, a used_feature_type / tree_used of fewer than 6 characters, a cloud with points but no pointer or a stride below 48 give
+ * that item the status of its single call (results[i].status, report zeroed) and leave its map untouched to the byte; every other item is undisturbed.
+ * Returns the status of the lowest-index item that is not MULLS_OK (mulls_last_error names it); n_items == 0: MULLS_OK.  After MULLS_E_HIP the maps of the
+ * running group are unspecified until mulls_map_set, as after a failed mulls_map_update; the items of later groups are not run and report MULLS_E_HIP too.
+ * results[i].path: 0 = lock step; 1 = handed to the single-map path inside the call — never taken: no input is known that the lock-step path cannot serve. */
+typedef struct mulls_map_update_item
+{
+	mulls_map *map;
+	const mulls_cloud *frame_down; /* [6], as mulls_map_update takes them: host or device clouds */
+	double frame_pose_lo[16];	   /* column-major */
+	const mulls_map_params *params; /* NULL: the call's shared params */
+} mulls_map_update_item;
+typedef struct mulls_map_batch_result
+{
+	int32_t status;
+	uint32_t path;
+	mulls_map_report report;
+} mulls_map_batch_result;
+typedef struct mulls_map_batch_stats
+{
+	uint32_t n_groups, n_lockstep, n_single_path, n_kernel_launches, n_syncs;
+} mulls_map_batch_stats;
+int mulls_map_update_batch(mulls_ctx *ctx, const mulls_map_update_item *items, uint32_t n_items, const mulls_map_params *shared_params,
+						   uint32_t max_lockstep, mulls_map_batch_result *results, mulls_map_batch_stats *stats /* may be NULL */);
 /* class cloud c of the map as a device cloud (48-B records); valid until the next mulls_map_set / _update / _destroy */
 int mulls_map_cloud(mulls_ctx *ctx, const mulls_map *map, int cls, mulls_cloud *out);
 int mulls_map_pose(mulls_ctx *ctx, const mulls_map *map, double pose_lo[16]);

@@ -155,6 +155,24 @@ class MapReport(C.Structure):
     ]
 
 
+class MapUpdateItem(C.Structure):
+    """mulls_map_update_item: one map's update inside mulls_map_update_batch"""
+
+    _fields_ = [("map", C.c_void_p), ("frame_down", C.POINTER(Cloud)), ("frame_pose_lo", C.c_double * 16), ("params", C.POINTER(MapParams))]
+
+
+class MapBatchResult(C.Structure):
+    """mulls_map_batch_result"""
+
+    _fields_ = [("status", C.c_int32), ("path", C.c_uint32), ("report", MapReport)]
+
+
+class MapBatchStats(C.Structure):
+    """mulls_map_batch_stats"""
+
+    _fields_ = [("n_groups", C.c_uint32), ("n_lockstep", C.c_uint32), ("n_single_path", C.c_uint32), ("n_kernel_launches", C.c_uint32), ("n_syncs", C.c_uint32)]
+
+
 def map_params(**kw):
     """update_local_map defaults (map_manager.h:21-31), overridden by keyword."""
     p = MapParams()

@@ -30,6 +30,7 @@ struct mulls_pgo_scratch;
 struct mulls_ndt_scratch;
 struct mulls_gicp_scratch;
 struct mulls_mapper;
+struct mulls_mapb_scratch;
 
 // A few host threads that SLEEP between their jobs (condition variable), for the staging gather of mulls_icp_batch.  An OpenMP team keeps spinning after its
 // parallel region; 32 spinning threads inside a container with a CPU quota get the whole process throttled for the rest of the scheduler period: every fourth
@@ -100,6 +101,7 @@ struct mulls_ctx
 	mulls_pgo_scratch *pgo = nullptr; // mulls_pgo_optimize's (pgo.cpp; grow-only)
 	mulls_ndt_scratch *ndt = nullptr; // mulls_ndt's (ndt.cpp; grow-only)
 	mulls_gicp_scratch *gicp = nullptr; // mulls_gicp's (gicp.cpp; grow-only)
+	mulls_mapb_scratch *mapb = nullptr; // mulls_map_update_batch's staging: tables up, counts and keys down (map_batch.cpp; grow-only)
 	std::vector<mulls_mapper *> mappers; // live merged maps (scan.cpp)
 	std::vector<mulls_submaps *> submap_stores; // live submap archives (submaps.cpp): their arenas are device clouds mulls_pair may point to
 	int nn_mode = 0;   // 0 auto, 1 LDS-tiled brute force, 2 uniform grid in global memory, 3 (and 4) uniform grid staged in LDS
@@ -263,6 +265,7 @@ void mulls_nms_release(mulls_ctx *ctx); // frees ctx->nms (nms.cpp)
 void mulls_pgo_release(mulls_ctx *ctx); // frees ctx->pgo (pgo.cpp)
 void mulls_ndt_release(mulls_ctx *ctx); // frees ctx->ndt (ndt.cpp)
 void mulls_gicp_release(mulls_ctx *ctx); // frees ctx->gicp (gicp.cpp)
+void mulls_mapb_release(mulls_ctx *ctx); // frees ctx->mapb (map_batch.cpp)
 void mulls_scan_release(mulls_ctx *ctx); // frees ctx->scanprep and destroys the mappers still alive (scan.cpp)
 void mulls_submaps_release(mulls_ctx *ctx); // destroys the submap archives still alive (submaps.cpp)
 bool mulls_submaps_memory(const mulls_ctx *ctx, const void *p, size_t bytes); // is [p, p + bytes) inside a live archive's arena? (submaps.cpp)

@@ -4,6 +4,7 @@
 #include "device_util.h"
 #include "accum.h"
 #include "solve_wave.h"
+#include "map_bodies.h"
 
 // Normal-equation accumulation (active pairs) or posterior residual (pairs flagged want_residual), lock-step path.  The job
 // table is the one of the search (512 source slots per job); one workgroup per job that starts a trip of MULLS_ACC_LANES slots
@@ -870,18 +871,7 @@ __global__ void k_transform_clouds(TransformArgs A)
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= A.n[blockIdx.y])
 		return;
-	float4 *__restrict__ recs = A.recs[blockIdx.y];
-	const double *T = A.T;
-	float4 a = recs[(size_t)i * 3], b = recs[(size_t)i * 3 + 1];
-	double x = a.x, y = a.y, z = a.z, nx = b.x, ny = b.y, nz = b.z;
-	a.x = (float)(T[0] * x + T[1] * y + T[2] * z + T[3]);
-	a.y = (float)(T[4] * x + T[5] * y + T[6] * z + T[7]);
-	a.z = (float)(T[8] * x + T[9] * y + T[10] * z + T[11]);
-	b.x = (float)(T[0] * nx + T[1] * ny + T[2] * nz);
-	b.y = (float)(T[4] * nx + T[5] * ny + T[6] * nz);
-	b.z = (float)(T[8] * nx + T[9] * ny + T[10] * nz);
-	recs[(size_t)i * 3] = a;
-	recs[(size_t)i * 3 + 1] = b;
+	map_body::transform(A.recs[blockIdx.y], i, A.T); // (map_bodies.h: the text mulls_map_update_batch's launches share)
 }
 
 // force a given correspondence list into the flag/match/wd arrays (mulls_stage_accumulate)

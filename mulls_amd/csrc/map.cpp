@@ -13,33 +13,10 @@
 #include "device_types.h"
 #include "hostmath.h"
 #include "launch.h"
+#include "map_internal.h"
 #include "map_launch.h"
 
-using mulls::Mat4;
-
-struct mulls_map
-{
-	float4 *rec[MULLS_NC] = {}; // class clouds, 48-B records
-	float4 *alt[MULLS_NC] = {}; // compaction target (ping-pong)
-	size_t cap[MULLS_NC] = {}, cap_alt[MULLS_NC] = {};
-	uint32_t n[MULLS_NC] = {};
-	float4 *frame[MULLS_NC] = {}, *frame_alt[MULLS_NC] = {};
-	size_t cap_frame[MULLS_NC] = {}, cap_frame_alt[MULLS_NC] = {};
-	uint32_t frame_n[MULLS_NC] = {};
-	double pose[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; // pose_lo, column-major
-	uint32_t *counts = nullptr; // [6] device
-	uint32_t *keys = nullptr;	// [12] device
-	double *T12 = nullptr;		// [12] device
-	uint32_t *best = nullptr;
-	uint8_t *keep = nullptr;
-	size_t cap_best = 0, cap_keep = 0;
-	uint8_t *dmask = nullptr; // the thinning masks of a frame's update
-	size_t cap_dmask = 0;
-	uint32_t *seg = nullptr; // per-segment counters of the stable compactions
-	size_t cap_seg = 0;
-	bool has_bounds = false; // the last update's report (what a submap snapshot carries on: mulls_submaps_push_map)
-	double local_bound[6] = {}, bound[6] = {};
-};
+using namespace mulls_mapi; // (the map and the per-phase host arithmetic: map_internal.h, shared with map_batch.cpp)
 
 bool mulls_is_map_memory(const mulls_ctx *ctx, const void *p, size_t bytes)
 {
@@ -75,15 +52,6 @@ bool mulls_map_snapshot(const mulls_ctx *ctx, const mulls_map *m, MapSnapshot *o
 
 namespace
 {
-const size_t REC = MULLS_POINT_BYTES;
-
-void rows12_of(const Mat4 &M, double out[12])
-{
-	for (int r = 0; r < 3; r++)
-		for (int c = 0; c < 4; c++)
-			out[r * 4 + c] = M.at(r, c);
-}
-
 // capacity in records; keeps the contents when `keep_n` > 0
 int reserve(mulls_ctx *ctx, float4 **p, size_t *cap, size_t need, size_t keep_n)
 {
@@ -163,16 +131,6 @@ int compact(mulls_ctx *ctx, mulls_map *m, const MapCompactArgs &a)
 	return MULLS_OK;
 }
 
-double key_to_double(uint32_t k, bool is_min)
-{
-	const bool none = is_min ? k == 0xffffffffu : k == 0u;
-	if (none)
-		return is_min ? 1.7976931348623157e308 : -1.7976931348623157e308;
-	const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-	float f;
-	std::memcpy(&f, &u, sizeof(f));
-	return (double)f;
-}
 } // namespace
 
 extern "C"
@@ -285,37 +243,20 @@ extern "C"
 		for (int c = 0; c < MULLS_NC; c++)
 			m->frame_n[c] = frame_down[c].n;
 		// 2. tran_target_map = last_target.pose_lo^-1 * local_map.pose_lo (:28); the five *_down clouds go to the map frame (:32)
-		Mat4 map_T, frame_T;
-		std::memcpy(map_T.v, m->pose, sizeof(map_T.v));
-		std::memcpy(frame_T.v, frame_pose_lo, sizeof(frame_T.v));
-		const Mat4 tran_target_map = mulls::invert4(frame_T) * map_T;
-		const Mat4 inv = mulls::invert4(tran_target_map);
-		double t12[12];
-		rows12_of(inv, t12);
-		launch_transform_clouds(st, m->frame, m->frame_n, 5, t12); // (the transform travels with the launch)
+		UpdatePoses poses;
+		update_poses(m->pose, frame_pose_lo, &poses);
+		launch_transform_clouds(st, m->frame, m->frame_n, 5, poses.frame_to_map); // (the transform travels with the launch)
 
 		// 3. map-based dynamic-object removal on the frame's pillar, beam and facade clouds (:37-47, :149-268)
-		float dmax = P->dynamic_dist_thre_max;
-		{
-			const double lo = P->dynamic_dist_thre_min + 0.1;
-			dmax = (float)(((double)dmax > lo) ? (double)dmax : lo);
-		}
-		const int fpn0 = (int)(m->n[MULLS_GROUND] + m->n[MULLS_FACADE] + m->n[MULLS_ROOF] + m->n[MULLS_PILLAR] + m->n[MULLS_BEAM]);
-		if (P->map_based_dynamic_removal_on && fpn0 > P->max_num_pts / 5 && P->tree_mode != 0)
+		const float dmax = removal_dmax(P);
+		const RemovalPlan plan = removal_plan(m, P);
+		if (plan.ran)
 		{
 			rep->dynamic_removal_ran = 1;
 			// the three classes side by side (nearest tree point, verdict), then ONE compaction and one read of the counts
-			static const int order[3] = {MULLS_PILLAR, MULLS_BEAM, MULLS_FACADE};
-			uint32_t first[3] = {0, 0, 0}, total = 0;
-			bool run[3];
-			for (int k = 0; k < 3; k++)
-			{
-				const int c = order[k];
-				run[k] = !(P->used_feature_type[c] != '1' || P->tree_used[c] != '1' || m->frame_n[c] <= 10 || m->n[c] == 0);
-				first[k] = total;
-				if (run[k])
-					total += (m->frame_n[c] + 3u) & ~3u;
-			}
+			const int *order = removal_order();
+			const bool *run = plan.run;
+			const uint32_t *first = plan.first, total = plan.total;
 			if (total)
 			{
 				if (m->cap_best < total)
@@ -386,8 +327,7 @@ extern "C"
 				return MULLS_E_HIP;
 		}
 		// 5. the map moves to the frame's coordinates (:57-59)
-		rows12_of(tran_target_map, t12);
-		launch_transform_clouds(st, m->rec, m->n, MULLS_NC, t12);
+		launch_transform_clouds(st, m->rec, m->n, MULLS_NC, poses.map_to_frame);
 		std::memcpy(m->pose, frame_pose_lo, sizeof(m->pose));
 		// 6. dist_filter(cloud, local_map_radius) on all six (:62-67)
 		MapCompactArgs a;
@@ -416,19 +356,9 @@ extern "C"
 			m->n[c] = cnt[c];
 		}
 		// 7. random_downsample_pcl to the per-class share of max_num_pts (:70-86), seeded selection sampling
-		const int cur = (int)(m->n[MULLS_GROUND] + m->n[MULLS_FACADE] + m->n[MULLS_ROOF] + m->n[MULLS_PILLAR] + m->n[MULLS_BEAM]);
 		int kept[MULLS_NC];
-		for (int c = 0; c < 5; c++)
-			kept[c] = cur > 0 ? (int)(1.0 * P->max_num_pts / cur * m->n[c] + 1) : 1;
-		kept[MULLS_VERTEX] = P->kept_vertex_num;
-		bool any_thin = false;
-		size_t mask_total = 0;
-		for (int c = 0; c < MULLS_NC; c++)
-			if ((long)m->n[c] > (long)kept[c])
-			{
-				any_thin = true;
-				mask_total += m->n[c];
-			}
+		const size_t mask_total = thinning_plan(m->n, P, kept);
+		const bool any_thin = mask_total != 0;
 		if (any_thin)
 		{
 			std::vector<uint8_t> mask(mask_total);
@@ -483,8 +413,7 @@ extern "C"
 		}
 		// 8. bounds of the merged cloud, local and posed (:88-94)
 		uint32_t keys[12];
-		for (int k = 0; k < 12; k++)
-			keys[k] = (k % 6) < 3 ? 0xffffffffu : 0u;
+		bound_keys_init(keys);
 		HIPCHK(ctx, hipMemcpyAsync(m->keys, keys, sizeof(keys), hipMemcpyHostToDevice, st));
 		MapBoxArgs b;
 		std::memset(&b, 0, sizeof(b));
@@ -493,30 +422,21 @@ extern "C"
 			b.recs[c] = m->rec[c];
 			b.n[c] = m->n[c];
 		}
-		rows12_of(frame_T, b.pose);
+		std::memcpy(b.pose, poses.frame_pose, sizeof(b.pose));
 		b.keys = m->keys;
 		launch_map_bbox(st, b);
 		HIPCHK(ctx, hipMemcpyAsync(keys, m->keys, sizeof(keys), hipMemcpyDeviceToHost, st));
 		HIPCHK(ctx, hipStreamSynchronize(st));
-		for (int k = 0; k < 6; k++)
-		{
-			rep->local_bound[k] = key_to_double(keys[k], k < 3);
-			rep->bound[k] = key_to_double(keys[6 + k], k < 3);
-		}
-		std::memcpy(m->local_bound, rep->local_bound, sizeof(m->local_bound));
-		std::memcpy(m->bound, rep->bound, sizeof(m->bound));
-		m->has_bounds = true;
+		bound_keys_decode(keys, m, rep);
 		// 9. recalculate_feature_on (:98-118): principal directions of the pillar and beam clouds from their own neighbourhoods
 		//    (pca_radius 1.8, pca_max_k 20, pca_min_k 6, min_linearity 0.65), pillars kept above sin 0.80, beams below sin 0.25
-		if (P->recalculate_feature_on)
 		{
-			static const int cls[2] = {MULLS_PILLAR, MULLS_BEAM};
-			static const float sin_low[2] = {0.0f, 0.25f}, sin_high[2] = {0.80f, 1.0f};
+			const int *cls = refresh_classes();
 			for (int k = 0; k < 2; k++)
 			{
 				const int c = cls[k];
 				const uint32_t nc = m->n[c];
-				if (P->used_feature_type[c] != '1' || nc == 0)
+				if (!refresh_runs(m, P, k))
 					continue;
 				if (m->cap_best < nc)
 				{
@@ -531,15 +451,7 @@ extern "C"
 					m->cap_best = (size_t)nc * 2;
 				}
 				MapPcaArgs pa;
-				pa.recs = m->rec[c];
-				pa.n = nc;
-				pa.radius = 1.8f;
-				pa.max_k = 20;
-				pa.min_k = 6;
-				pa.sin_low = sin_low[k];
-				pa.sin_high = sin_high[k];
-				pa.min_linearity = 0.65f;
-				pa.keep = m->keep;
+				refresh_args(k, m->rec[c], nc, m->keep, &pa);
 				launch_map_pca(st, pa);
 				const int rc = reserve(ctx, &m->alt[c], &m->cap_alt[c], nc, 0);
 				if (rc != MULLS_OK)
@@ -560,9 +472,7 @@ extern "C"
 				m->n[c] = cnt[0];
 			}
 		}
-		for (int c = 0; c < MULLS_NC; c++)
-			rep->n[c] = m->n[c];
-		rep->feature_point_num = (int)(m->n[MULLS_GROUND] + m->n[MULLS_FACADE] + m->n[MULLS_ROOF] + m->n[MULLS_PILLAR] + m->n[MULLS_BEAM]);
+		report_sizes(m, rep);
 		rep->ms_total = (float)(std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3);
 		return MULLS_OK;
 	}

@@ -40,6 +40,7 @@ struct MapCompactJob
 };
 int launch_map_compact_batch(hipStream_t st, const MapCompactJob *tab_dev, const MapCompactJob *tab_host, uint32_t count);
 void launch_map_bbox(hipStream_t st, const MapBoxArgs &a);
+#define MAP_NN_CHUNK 2048u // tree points per workgroup (a down-sampled frame against a 20 000-point map: 16384 made 8 workgroups of it, 284 us; 2048: ~40 workgroups)
 // nearest tree point of every frame point: best[i] = float bits of the smallest squared distance (0x7f800000 if the tree
 // is empty); tree = map class cloud, optionally restricted to the open box (strict inequalities, float vs double)
 void launch_map_nn(hipStream_t st, const float4 *frame, uint32_t n_frame, const float4 *tree, uint32_t n_tree, int use_box, const double box[6],
@@ -59,3 +60,50 @@ struct MapPcaArgs
 	uint8_t *keep;
 };
 void launch_map_pca(hipStream_t st, const MapPcaArgs &a);
+
+// ---- table-driven forms (k_map_batch.hip) for mulls_map_update_batch: one launch per step for every map of a lock-step group -----------------------------
+// A launch reads an entry table (one entry per cloud taking part) and a flat job list (one job per workgroup: which entry, which block of it), both in device
+// memory and both built on the host from the sizes it knows at every phase; the grid is the job list's length, whatever the largest cloud is.
+struct MapbCopyEnt // byte range to copy; bytes a multiple of 4; job = 16 KiB block of it
+{
+	unsigned long long dst, src;
+	uint32_t bytes, pad_;
+};
+struct MapbXformEnt // job = 256 records
+{
+	float4 *recs;
+	uint32_t n, pad_;
+	double T[12]; // rows of [R|t]
+};
+struct MapbRemEnt // one frame class cloud against its tree (dynamic removal); jobs: (frame block of 256, tree chunk of MAP_NN_CHUNK) and (frame block of 256)
+{
+	const float4 *frame, *tree;
+	uint32_t *best;
+	uint8_t *keep;
+	uint32_t n_frame, n_tree;
+	int use_box;
+	float center_radius, dmin, dmax, near_;
+	uint32_t pad_;
+	double box[6];
+};
+struct MapbBoxEnt // job = MAPB_BOX_TILE records
+{
+	const float4 *recs;
+	uint32_t *keys; // the map's 12-word block
+	uint32_t n, pad_;
+	double pose[12];
+};
+#define MAPB_BOX_TILE 2048u
+#define MAPB_COPY_BLOCK 16384u
+struct MapbJob
+{
+	uint32_t ent, block, chunk, pad_;
+};
+// every launcher: nothing is launched for an empty job list; returns the kernels launched
+int launch_mapb_copy(hipStream_t st, const MapbCopyEnt *ent, const MapbJob *jobs, uint32_t n_jobs);
+int launch_mapb_transform(hipStream_t st, const MapbXformEnt *ent, const MapbJob *jobs, uint32_t n_jobs);
+int launch_mapb_fill_best(hipStream_t st, const MapbRemEnt *ent, const MapbJob *jobs, uint32_t n_jobs); // best[q] = 0x7f800000
+int launch_mapb_nn(hipStream_t st, const MapbRemEnt *ent, const MapbJob *jobs, uint32_t n_jobs);
+int launch_mapb_keep(hipStream_t st, const MapbRemEnt *ent, const MapbJob *jobs, uint32_t n_jobs);
+int launch_mapb_bbox(hipStream_t st, const MapbBoxEnt *ent, const MapbJob *jobs, uint32_t n_jobs);
+int launch_mapb_pca(hipStream_t st, const MapPcaArgs *ent, const MapbJob *jobs, uint32_t n_jobs); // job = tile of 256 points

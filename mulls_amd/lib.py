@@ -77,6 +77,8 @@ def load():
     lib.mulls_map_destroy.restype = None
     lib.mulls_map_set.argtypes = [vp, vp, C.POINTER(abi.Cloud), C.POINTER(C.c_double)]
     lib.mulls_map_update.argtypes = [vp, vp, C.POINTER(abi.Cloud), C.POINTER(C.c_double), C.POINTER(abi.MapParams), C.POINTER(abi.MapReport)]
+    lib.mulls_map_update_batch.argtypes = [vp, C.POINTER(abi.MapUpdateItem), C.c_uint32, C.POINTER(abi.MapParams), C.c_uint32, C.POINTER(abi.MapBatchResult),
+                                           C.POINTER(abi.MapBatchStats)]
     lib.mulls_map_cloud.argtypes = [vp, vp, C.c_int, C.POINTER(abi.Cloud)]
     lib.mulls_map_pose.argtypes = [vp, vp, C.POINTER(C.c_double)]
     lib.mulls_map_download.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -175,7 +177,7 @@ EXPORTS = [
     "mulls_default_params", "mulls_create", "mulls_destroy", "mulls_last_error", "mulls_set_profiling", "mulls_get_profile",
     "mulls_stream", "mulls_set_nn_mode", "mulls_icp", "mulls_icp_batch", "mulls_batch_create", "mulls_batch_run", "mulls_batch_destroy",
     "mulls_stage_transform", "mulls_stage_correspond", "mulls_stage_accumulate", "mulls_icp_3dof_ground", "mulls_icp_3dof_ground_batch",
-    "mulls_icp_4dof_global", "mulls_map_default_params", "mulls_map_create", "mulls_map_destroy", "mulls_map_set", "mulls_map_update",
+    "mulls_icp_4dof_global", "mulls_map_default_params", "mulls_map_create", "mulls_map_destroy", "mulls_map_set", "mulls_map_update", "mulls_map_update_batch",
     "mulls_map_cloud", "mulls_map_pose", "mulls_map_download", "mulls_map_frame_download", "mulls_io_read_kitti_bin", "mulls_io_read_pcd",
     "mulls_io_write_pcd", "mulls_io_write_pose", "mulls_ground_default_params", "mulls_ground_filter",
     "mulls_classify_default_params", "mulls_classify_nground", "mulls_extract_default_params", "mulls_extract_features", "mulls_voxel_downsample",
@@ -448,6 +450,31 @@ class Context:
         if not voxels:
             res[abi.EX_DOWN] = res[abi.EX_RAW]
         return res
+
+    def map_update_batch(self, maps, frames, poses, params, max_lockstep=0, check=True, shared_params=None):
+        """mulls_map_update_batch: one update_local_map per LocalMap, in lock step on the device.  frames[i]: the six clouds LocalMap.update takes (point arrays or
+        abi.Cloud device clouds), poses[i]: the frame's pose_lo, params: one abi.MapParams for all or a list with one per map
+        (a None entry takes shared_params).  Returns (reports, stats): one abi.MapReport per map and the abi.MapBatchStats; check=False returns
+        (results, stats, rc) with the abi.MapBatchResult records instead and does not raise on a refused item."""
+        n = len(maps)
+        per_item = isinstance(params, (list, tuple))
+        shared = shared_params if per_item else params
+        items, keep = (abi.MapUpdateItem * max(n, 1))(), []
+        for i in range(n):
+            items[i].map = maps[i].h if isinstance(maps[i], LocalMap) else maps[i]
+            if frames[i] is not None:
+                arr, held = LocalMap._clouds(frames[i])
+                keep.append((arr, held))
+                items[i].frame_down = arr
+            items[i].frame_pose_lo = abi.colmajor16(poses[i])
+            if per_item and params[i] is not None:
+                items[i].params = C.pointer(params[i])
+        results, stats = (abi.MapBatchResult * max(n, 1))(), abi.MapBatchStats()
+        rc = self.lib.mulls_map_update_batch(self.h, items, n, C.byref(shared) if shared is not None else None, int(max_lockstep), results, C.byref(stats))
+        if not check:
+            return [results[i] for i in range(n)], stats, rc
+        self._check(rc, "mulls_map_update_batch")
+        return [results[i].report for i in range(n)], stats
 
     def extract_features_batch(self, scans, params, blocks=None, scratch_limit_bytes=0, check=True):
         """mulls_extract_features_batch: extract_semantic_pts' chain on many scans per call, in lock step on the device, the feature clouds left in one Block per scan.
