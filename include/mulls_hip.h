@@ -391,7 +391,9 @@ void mulls_map_destroy(mulls_ctx *ctx, mulls_map *map);
 int mulls_map_set(mulls_ctx *ctx, mulls_map *map, const mulls_cloud clouds[6], const double pose_lo[16]);
 /* update_local_map(local_map = map, last_target_cblock = {frame_down, frame_pose_lo}).  frame_down[0..4] = pc_*_down,
  * frame_down[5] = pc_vertex, all in the frame's own coordinates; they are not modified (the reference transforms and
- * filters last_target_cblock->pc_*_down in place: mulls_map_frame_download returns that state). */
+ * filters last_target_cblock->pc_*_down in place: mulls_map_frame_download returns that state).  The call is mulls_map_update_batch (below) with one item,
+ * without the batch's own refusals: a frame cloud may be a device cloud of any map or block of the context, this map's included.  Refused for a cloud with
+ * points but no pointer or a stride below 48 (MULLS_E_INVALID), it has zeroed `report` and left the map untouched. */
 int mulls_map_update(mulls_ctx *ctx, mulls_map *map, const mulls_cloud frame_down[6], const double frame_pose_lo[16],
 					 const mulls_map_params *params, mulls_map_report *report);
 /* Many maps, one update each, in lock step (map_batch.cpp): whoever drives several sequences side by side — a dataset's drives replayed together, several
@@ -403,7 +405,7 @@ int mulls_map_update(mulls_ctx *ctx, mulls_map *map, const mulls_cloud frame_dow
  *
  * Lock step: the items are cut into groups of max_lockstep (0: 64, which keeps the pinned staging of KITTI-sized frames near 20 MB).  Within a group every
  * device step of the update runs once for all items — one launch, or one fixed launch set, whose workgroups find their map, class and block in a table in
- * device memory, the grid being the sum of the items' work — and every host wait of the single path happens at most once: behind the dynamic removal (only if
+ * device memory, the grid being the sum of the items' work — and every host wait of an update happens at most once: behind the dynamic removal (only if
  * some item's removal runs), behind dist_filter, and behind the bounds and the pillar / beam refresh together.  The thinning masks of all maps are computed
  * on the host after the one read of dist_filter's counts and go up in one copy.  Each map keeps its own buffers; a buffer that has to grow is replaced at once
  * and the old one freed behind the phase's wait, so growth costs no wait.  stats->n_syncs and n_kernel_launches do not depend on the number of items in a group.

@@ -4,7 +4,6 @@
 #include "device_util.h"
 #include "accum.h"
 #include "solve_wave.h"
-#include "map_bodies.h"
 
 // Normal-equation accumulation (active pairs) or posterior residual (pairs flagged want_residual), lock-step path.  The job
 // table is the one of the search (512 source slots per job); one workgroup per job that starts a trip of MULLS_ACC_LANES slots
@@ -858,22 +857,6 @@ __global__ void k_transform_aos(float4 *__restrict__ recs, uint32_t n, const dou
 	recs[(size_t)i * 3 + 1] = b;
 }
 
-// ... on up to six clouds in one launch (blockIdx.y), the transform travelling with the launch: the local map's update moves the frame's clouds and then the
-// whole map (map.cpp) — eleven launches and two uploads otherwise
-struct TransformArgs
-{
-	float4 *recs[6];
-	uint32_t n[6];
-	double T[12];
-};
-__global__ void k_transform_clouds(TransformArgs A)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= A.n[blockIdx.y])
-		return;
-	map_body::transform(A.recs[blockIdx.y], i, A.T); // (map_bodies.h: the text mulls_map_update_batch's launches share)
-}
-
 // force a given correspondence list into the flag/match/wd arrays (mulls_stage_accumulate)
 __global__ void k_set_corr(uint32_t src_off, const int32_t *__restrict__ cs, const int32_t *__restrict__ ct, const float *__restrict__ cd,
 						   uint32_t n, uint8_t *__restrict__ flag, int32_t *__restrict__ match, float *__restrict__ wd, uint32_t tgt_off,
@@ -982,22 +965,6 @@ void launch_push_states(hipStream_t st, const BatchDev &b, uint32_t pair_base, u
 	if (nwords)
 		hipLaunchKernelGGL(k_push_states, dim3((nwords + 255) / 256), dim3(256), 0, st, reinterpret_cast<const uint4 *>(host_states),
 						   reinterpret_cast<uint4 *>(dev_states), nwords);
-}
-
-void launch_transform_clouds(hipStream_t st, float4 *const recs[], const uint32_t n[], int count, const double T12[12])
-{
-	TransformArgs a;
-	uint32_t most = 0;
-	for (int c = 0; c < 6; c++)
-	{
-		a.recs[c] = c < count ? recs[c] : nullptr;
-		a.n[c] = c < count ? n[c] : 0u;
-		most = a.n[c] > most ? a.n[c] : most;
-	}
-	for (int k = 0; k < 12; k++)
-		a.T[k] = T12[k];
-	if (most)
-		hipLaunchKernelGGL(k_transform_clouds, dim3((most + 255) / 256, 6), dim3(256), 0, st, a);
 }
 
 void launch_transform_aos(hipStream_t st, float4 *recs, uint32_t n, const double *T12)

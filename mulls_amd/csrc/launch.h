@@ -130,7 +130,5 @@ void launch_finish_step(hipStream_t st, const BatchDev &b, const RunParams &rp, 
 						int brute, uint32_t *ticket = nullptr, bool sum_step = false); // ticket: two zeroed device words -> finish, step and publication in one launch (small batches);
 						// sum_step (large batches): one wave per pair sums and steps (k_sum_step) instead of k_finish + k_step
 void launch_transform_aos(hipStream_t st, float4 *recs, uint32_t n, const double *T12);
-// the same on `count` (<= 6) clouds in one launch, T12 (host) by value
-void launch_transform_clouds(hipStream_t st, float4 *const recs[], const uint32_t n[], int count, const double T12[12]);
 // cs, ct, cd: the caller's correspondence list (device copies), forced into the batch's flag / match / wd / mq arrays
 void launch_set_corr(hipStream_t st, const BatchDev &b, uint32_t src_off, const int32_t *cs, const int32_t *ct, const float *cd, uint32_t n, uint32_t tgt_off);

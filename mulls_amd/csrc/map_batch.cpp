@@ -1,6 +1,8 @@
-// map_batch.cpp — mulls_map_update_batch (include/mulls_hip.h): the nine steps of mulls_map_update (map.cpp) for a group of maps in lock step.  Every device
-// step is one table-driven launch (k_map_batch.hip; the compactions: launch_map_compact_batch) over a flat job list the host builds from the sizes it knows at
-// every phase, every wait of the single path happens once per group, and the host arithmetic between the waits is map_internal.h's, the single call's text.
+// map_batch.cpp — mulls_map_update and mulls_map_update_batch (include/mulls_hip.h): MapManager::update_local_map (src/map_manager.cpp:18-140) and map-based
+// dynamic-object removal (:149-268) in nine steps, for a group of maps in lock step; mulls_map_update is a group of one.  Every device step is one table-driven
+// launch (k_map_batch.hip; the compactions: launch_map_compact_batch) over a flat job list the host builds from the sizes it knows at every phase, every wait
+// happens once per group, and the host arithmetic between the waits is map_internal.h's.  As everywhere in this library there is no CPU fallback: the only
+// host-side arithmetic is the pose algebra, the kept-point counts and the seeded selection masks.
 //
 //   phase A  steps 1-2   the frames' clouds into the maps' frame buffers (host sources wait in the pinned staging, read by the copy launch), moved to the map frame
 //   phase B  step 3      dynamic removal of the items whose gate opens: fill `best`, nearest tree point, verdict, ONE compaction           -> wait (counts)
@@ -155,7 +157,8 @@ struct Group
 		return MULLS_OK;
 	}
 
-	// map.cpp's reserve(): capacity in records.  The old buffer (returned through `old` when its contents are to be kept) is freed behind the next wait.
+	// capacity in records, grown by half as map.cpp's reserve() does.  The old buffer (returned through `old` when its contents are to be kept) is freed behind
+	// the next wait.
 	int reserve_rec(float4 **p, size_t *cap, size_t need, float4 **old = nullptr)
 	{
 		if (old)
@@ -697,8 +700,7 @@ struct Group
 	}
 };
 
-// the status a single mulls_map_update would give this item before it touched the map (NULL frame, short strings, a cloud with points but no pointer or a
-// stride below a record)
+// why an item is refused before its map is touched (NULL frame, short strings, a cloud with points but no pointer or a stride below a record)
 int precheck(const mulls_map_update_item &I, const mulls_map_params *P, std::string *why)
 {
 	if (!I.frame_down)
@@ -719,7 +721,108 @@ int precheck(const mulls_map_update_item &I, const mulls_map_params *P, std::str
 		}
 	return MULLS_OK;
 }
+
+// The items as lock-step groups of at most `max_lockstep` (0: 64).  An item precheck refuses gets its status and stays out of its group; results[i].status and
+// errs[i] say how item i fared.  Returns MULLS_E_HIP only where nothing was written (the device could not be selected).
+int run_items(mulls_ctx *ctx, const mulls_map_update_item *items, uint32_t n_items, const mulls_map_params *shared_params, uint32_t max_lockstep,
+			  mulls_map_batch_result *results, mulls_map_batch_stats *stats, std::vector<std::string> &errs)
+{
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	if (!ctx->mapb)
+		ctx->mapb = new mulls_mapb_scratch();
+	const uint32_t per_group = max_lockstep ? max_lockstep : 64u;
+	errs.assign(n_items, std::string());
+	const auto fail = [&](uint32_t i, int rc, const std::string &why) {
+		results[i].status = rc;
+		errs[i] = why;
+	};
+	std::vector<Item> group;
+	for (uint32_t g0 = 0; g0 < n_items; g0 += per_group)
+	{
+		const uint32_t g1 = std::min<uint64_t>((uint64_t)g0 + per_group, n_items);
+		group.clear();
+		for (uint32_t i = g0; i < g1; i++)
+		{
+			std::memset(&results[i], 0, sizeof(results[i]));
+			const mulls_map_params *P = items[i].params ? items[i].params : shared_params;
+			std::string why;
+			const int rc = precheck(items[i], P, &why);
+			if (rc != MULLS_OK)
+			{
+				fail(i, rc, why);
+				continue;
+			}
+			Item I;
+			std::memset(&I, 0, sizeof(I));
+			I.idx = i, I.m = items[i].map, I.fd = items[i].frame_down, I.pose = items[i].frame_pose_lo, I.P = P, I.rep = &results[i].report;
+			group.push_back(I);
+		}
+		stats->n_groups++;
+		if (group.empty())
+			continue;
+		const auto wall0 = std::chrono::steady_clock::now();
+		Group G{ctx, ctx->mapb, ctx->stream, stats, group};
+		const int rc = G.run();
+		const float ms = (float)(std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3);
+		const std::string why = rc == MULLS_OK ? std::string() : ctx->err;
+		for (const Item &I : group)
+		{
+			results[I.idx].report.ms_total = ms; // (the group's wall time: the items ran together)
+			if (rc != MULLS_OK)
+				fail(I.idx, rc, why);
+		}
+		stats->n_lockstep += (uint32_t)group.size();
+		if (rc == MULLS_E_HIP)
+		{
+			for (uint32_t i = g1; i < n_items; i++) // (the device is not asked again)
+			{
+				std::memset(&results[i], 0, sizeof(results[i]));
+				fail(i, MULLS_E_HIP, "not run: an earlier group failed on the device");
+			}
+			break;
+		}
+	}
+	return MULLS_OK;
+}
 } // namespace
+
+// One map: a batch of one, without the batch's own refusals (a frame cloud may lie in device memory of this or another map, the map is taken as given).
+// Refused for a bad cloud, the call has zeroed `rep` and left the map as it was.
+extern "C" int mulls_map_update(mulls_ctx *ctx, mulls_map *m, const mulls_cloud frame_down[6], const double frame_pose_lo[16], const mulls_map_params *P,
+								mulls_map_report *rep)
+try
+{
+	if (!ctx || !m || !frame_down || !frame_pose_lo || !P || !rep)
+		return MULLS_E_INVALID;
+	if (std::strlen(P->used_feature_type) < 6 || std::strlen(P->tree_used) < 6)
+	{
+		ctx->err = "used_feature_type and tree_used need 6 characters";
+		return MULLS_E_INVALID;
+	}
+	const auto wall0 = std::chrono::steady_clock::now();
+	mulls_map_update_item item;
+	item.map = m, item.frame_down = frame_down, item.params = P;
+	std::memcpy(item.frame_pose_lo, frame_pose_lo, sizeof(item.frame_pose_lo));
+	mulls_map_batch_result res;
+	mulls_map_batch_stats stats;
+	std::memset(&stats, 0, sizeof(stats));
+	std::vector<std::string> errs;
+	const int rc = run_items(ctx, &item, 1, nullptr, 1, &res, &stats, errs);
+	if (rc != MULLS_OK)
+		return rc;
+	*rep = res.report;
+	if (res.status != MULLS_OK)
+	{
+		ctx->err = errs[0];
+		return res.status;
+	}
+	rep->ms_total = (float)(std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3);
+	return MULLS_OK;
+}
+catch (...)
+{
+	return mulls::abi_caught(const_cast<mulls_ctx *>(ctx)); // nothing is thrown across the ABI
+}
 
 extern "C" int mulls_map_update_batch(mulls_ctx *ctx, const mulls_map_update_item *items, uint32_t n_items, const mulls_map_params *shared_params,
 									  uint32_t max_lockstep, mulls_map_batch_result *results, mulls_map_batch_stats *stats)
@@ -784,61 +887,10 @@ try
 				}
 		}
 	}
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	if (!ctx->mapb)
-		ctx->mapb = new mulls_mapb_scratch();
-	const uint32_t per_group = max_lockstep ? max_lockstep : 64u;
-	std::vector<std::string> errs(n_items);
-	const auto fail = [&](uint32_t i, int rc, const std::string &why) {
-		results[i].status = rc;
-		errs[i] = why;
-	};
-	std::vector<Item> group;
-	for (uint32_t g0 = 0; g0 < n_items; g0 += per_group)
-	{
-		const uint32_t g1 = std::min<uint64_t>((uint64_t)g0 + per_group, n_items);
-		group.clear();
-		for (uint32_t i = g0; i < g1; i++)
-		{
-			std::memset(&results[i], 0, sizeof(results[i]));
-			const mulls_map_params *P = items[i].params ? items[i].params : shared_params;
-			std::string why;
-			const int rc = precheck(items[i], P, &why);
-			if (rc != MULLS_OK)
-			{
-				fail(i, rc, why);
-				continue;
-			}
-			Item I;
-			std::memset(&I, 0, sizeof(I));
-			I.idx = i, I.m = items[i].map, I.fd = items[i].frame_down, I.pose = items[i].frame_pose_lo, I.P = P, I.rep = &results[i].report;
-			group.push_back(I);
-		}
-		local.n_groups++;
-		if (group.empty())
-			continue;
-		const auto wall0 = std::chrono::steady_clock::now();
-		Group G{ctx, ctx->mapb, ctx->stream, &local, group};
-		const int rc = G.run();
-		const float ms = (float)(std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count() * 1e3);
-		const std::string why = rc == MULLS_OK ? std::string() : ctx->err;
-		for (const Item &I : group)
-		{
-			results[I.idx].report.ms_total = ms; // (the group's wall time: the items ran together)
-			if (rc != MULLS_OK)
-				fail(I.idx, rc, why);
-		}
-		local.n_lockstep += (uint32_t)group.size();
-		if (rc == MULLS_E_HIP)
-		{
-			for (uint32_t i = g1; i < n_items; i++) // (the device is not asked again)
-			{
-				std::memset(&results[i], 0, sizeof(results[i]));
-				fail(i, MULLS_E_HIP, "not run: an earlier group failed on the device");
-			}
-			break;
-		}
-	}
+	std::vector<std::string> errs;
+	const int rc = run_items(ctx, items, n_items, shared_params, max_lockstep, results, &local, errs);
+	if (rc != MULLS_OK)
+		return rc;
 	if (stats)
 		*stats = local;
 	for (uint32_t i = 0; i < n_items; i++) // the lowest-index item that is not MULLS_OK

@@ -1,5 +1,5 @@
-// map_internal.h — what map.cpp (mulls_map_update, one map) and map_batch.cpp (mulls_map_update_batch, a lock-step group of maps) share: the map itself and
-// the host arithmetic of every phase of an update, written once so that the batch decides what the single call decides.  Nothing here is ABI.
+// map_internal.h — what map.cpp (a map's life, mulls_map_set, the downloads) and map_batch.cpp (mulls_map_update and mulls_map_update_batch: lock-step groups
+// of maps) share: the map itself, and the host arithmetic of every phase of an update.  Nothing here is ABI.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>

@@ -1,9 +1,9 @@
-// map_kernels.hip — device side of the local map (MapManager::update_local_map, src/map_manager.cpp:18-140; dynamic
-// object removal :149-268).  Clouds stay 48-B PointXYZINormal records (3 float4: x y z -, nx ny nz -, intensity
-// curvature - -) so that a map class cloud can be handed to mulls_icp as a device-resident target unchanged.
+// map_kernels.hip — the stable segmented compaction of 48-B record clouds: the local map's radius filter, thinning, dynamic removal and refresh
+// (map_batch.cpp), and the ground filter, classifier, non-maximum suppression and feature-extraction batch.  Clouds stay 48-B PointXYZINormal records
+// (3 float4: x y z -, nx ny nz -, intensity curvature - -) so that a map class cloud can be handed to mulls_icp as a device-resident target unchanged.
+// (the local map's other kernels: k_map_batch.hip)
 #include <hip/hip_runtime.h>
 
-#include "map_bodies.h"
 #include "map_launch.h"
 
 // Stable compaction of up to six clouds in three steps, so that a 400 k-point class cloud is not left to one CU's memory
@@ -167,60 +167,6 @@ __global__ __launch_bounds__(256) void k_map_seg_scatter_b(const MapCompactJob *
 	MAP_SEG_SCATTER_BODY
 }
 
-// get_cloud_bbx (utility.hpp:817-848) over the six class clouds, and over the same points moved by pose_lo
-// (pcl::transformPointCloud: double arithmetic, float store) — ordered-uint atomics; NaN coordinates never win a
-// comparison in the reference and are skipped here.
-__global__ __launch_bounds__(256) void k_map_bbox(MapBoxArgs a)
-{
-	const uint32_t cls = blockIdx.y;
-	map_body::bbox(a.recs[cls], blockIdx.x * blockDim.x + threadIdx.x, a.n[cls], gridDim.x * blockDim.x, a.pose, a.keys);
-}
-
-// Exact nearest tree point (FLANN L2_Simple<float> distance) of every frame point, brute force: blockIdx.y splits the tree
-// into chunks of MAP_NN_CHUNK points staged through LDS, atomicMin on the float bits combines the chunks (distances are >= 0).
-// (the body, MAP_NN_CHUNK and MAP_NN_TILE: map_bodies.h)
-__global__ __launch_bounds__(256) void k_map_nn(const float4 *__restrict__ frame, uint32_t n_frame, const float4 *__restrict__ tree, uint32_t n_tree,
-												 int use_box, double b0, double b1, double b2, double b3, double b4, double b5,
-												 uint32_t *__restrict__ best)
-{
-	__shared__ float4 tile[MAP_NN_TILE];
-	map_body::nn(frame, n_frame, tree, n_tree, use_box, b0, b1, b2, b3, b4, b5, best, blockIdx.x, blockIdx.y, tile);
-}
-
-// map_scan_feature_pts_distance_removal's keep rule (map_manager.cpp:246-256), all in float as written there
-__global__ void k_map_keep(const float4 *__restrict__ frame, uint32_t n_frame, const uint32_t *__restrict__ best, float center_radius, float dmin,
-						   float dmax, float near, uint8_t *__restrict__ keep)
-{
-	const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-	if (q >= n_frame)
-		return;
-	map_body::keep(frame, q, best, center_radius, dmin, dmax, near, keep);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// MapManager::update_cloud_vectors (src/map_manager.cpp:258-292): every point of a linear-feature cloud gets the principal direction
-// of its radius-limited k-neighbourhood (pca.hpp:209-290, :392-437) and survives only if the neighbourhood is linear enough and its
-// direction steep (pillars) or flat (beams) enough.  One lane per point; the cloud streams through LDS in 256-point tiles and every
-// lane keeps its `max_k` nearest neighbours as a sorted list in LDS (slot-major, so that neighbouring lanes touch neighbouring banks).
-// A cloud of a few thousand points is all this ever sees (the map's pillar / beam share of max_num_pts): n^2 distances is microseconds.
-//   neighbourhood   squared L2_Simple distance (((dx*dx)+dy*dy)+dz*dz, float) < radius^2, the max_k nearest in (distance, index) order,
-//                   the point itself included — pcl::KdTreeFLANN::radiusSearch with max_nn
-//   pcl::PCA        float centroid and float demeaned covariance summed in the neighbours' order, scaled by 1/(n-1); the
-//                   eigen-decomposition of that float matrix in double (cyclic Jacobi), eigenvalues rounded to float
-// (the body and MAP_PCA_K, the list slots per lane: map_bodies.h)
-__global__ __launch_bounds__(256) void k_map_pca(MapPcaArgs a)
-{
-	__shared__ float tx[256], ty[256], tz[256];
-	__shared__ float ld[MAP_PCA_K * 256];
-	__shared__ uint32_t li[MAP_PCA_K * 256];
-	map_body::pca(a, blockIdx.x, tx, ty, tz, ld, li);
-}
-void launch_map_pca(hipStream_t st, const MapPcaArgs &a)
-{
-	if (a.n)
-		hipLaunchKernelGGL(k_map_pca, dim3((a.n + 255u) / 256u), dim3(256), 0, st, a);
-}
-
 uint32_t map_compact_segments(const MapCompactArgs &a)
 {
 	uint32_t ns = 0;
@@ -250,19 +196,4 @@ int launch_map_compact_batch(hipStream_t st, const MapCompactJob *tab_dev, const
 	if (ns)
 		hipLaunchKernelGGL(k_map_seg_scatter_b, dim3(ns, count), dim3(256), 0, st, tab_dev);
 	return ns ? 3 : 1;
-}
-void launch_map_bbox(hipStream_t st, const MapBoxArgs &a) { hipLaunchKernelGGL(k_map_bbox, dim3(64, 6), dim3(256), 0, st, a); }
-void launch_map_nn(hipStream_t st, const float4 *frame, uint32_t n_frame, const float4 *tree, uint32_t n_tree, int use_box, const double box[6],
-				   uint32_t *best)
-{
-	if (!n_frame || !n_tree)
-		return;
-	hipLaunchKernelGGL(k_map_nn, dim3((n_frame + 255) / 256, (n_tree + MAP_NN_CHUNK - 1) / MAP_NN_CHUNK), dim3(256), 0, st, frame, n_frame, tree,
-					   n_tree, use_box, box[0], box[1], box[2], box[3], box[4], box[5], best);
-}
-void launch_map_keep(hipStream_t st, const float4 *frame, uint32_t n_frame, const uint32_t *best, float center_radius, float dmin, float dmax,
-					 float near, uint8_t *keep)
-{
-	if (n_frame)
-		hipLaunchKernelGGL(k_map_keep, dim3((n_frame + 255) / 256), dim3(256), 0, st, frame, n_frame, best, center_radius, dmin, dmax, near, keep);
 }

@@ -1,4 +1,4 @@
-// map_launch.h — host-callable launchers of map_kernels.hip (device-resident local map)
+// map_launch.h — host-callable launchers of map_kernels.hip (the segmented compaction) and k_map_batch.hip (device-resident local map)
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
@@ -20,13 +20,6 @@ struct MapCompactArgs
 	int mode;		 // 0 = keep where mask != 0; 1 = CFilter::dist_filter(cloud, radius) (cfilter.hpp:834-871)
 	double radius;
 };
-struct MapBoxArgs
-{
-	const float4 *recs[6];
-	uint32_t n[6];
-	double pose[12]; // rows of [R|t] (local_map->pose_lo)
-	uint32_t *keys;	 // [12] ordered-uint min xyz / max xyz of the points, then of the posed points
-};
 
 // seg_scratch: device array of at least map_compact_segments(a) uint32 (one counter per 4096-record segment)
 uint32_t map_compact_segments(const MapCompactArgs &a);
@@ -39,17 +32,10 @@ struct MapCompactJob
 	uint32_t *seg;
 };
 int launch_map_compact_batch(hipStream_t st, const MapCompactJob *tab_dev, const MapCompactJob *tab_host, uint32_t count);
-void launch_map_bbox(hipStream_t st, const MapBoxArgs &a);
 #define MAP_NN_CHUNK 2048u // tree points per workgroup (a down-sampled frame against a 20 000-point map: 16384 made 8 workgroups of it, 284 us; 2048: ~40 workgroups)
-// nearest tree point of every frame point: best[i] = float bits of the smallest squared distance (0x7f800000 if the tree
-// is empty); tree = map class cloud, optionally restricted to the open box (strict inequalities, float vs double)
-void launch_map_nn(hipStream_t st, const float4 *frame, uint32_t n_frame, const float4 *tree, uint32_t n_tree, int use_box, const double box[6],
-				   uint32_t *best);
-void launch_map_keep(hipStream_t st, const float4 *frame, uint32_t n_frame, const uint32_t *best, float center_radius, float dmin, float dmax,
-					 float near, uint8_t *keep);
 
 // PCA refresh of a linear-feature cloud (MapManager::update_cloud_vectors): writes direction / linearity into the records of
-// the points it keeps and keep[i] = 0/1 for every point; max_k <= 24
+// the points it keeps and keep[i] = 0/1 for every point; max_k <= 24.  An entry of launch_mapb_pca's table.
 struct MapPcaArgs
 {
 	float4 *recs;
@@ -59,9 +45,8 @@ struct MapPcaArgs
 	float sin_low, sin_high, min_linearity;
 	uint8_t *keep;
 };
-void launch_map_pca(hipStream_t st, const MapPcaArgs &a);
 
-// ---- table-driven forms (k_map_batch.hip) for mulls_map_update_batch: one launch per step for every map of a lock-step group -----------------------------
+// ---- the local map's kernels (k_map_batch.hip), table-driven: one launch per step for every map of a lock-step group (mulls_map_update: a group of one) ----
 // A launch reads an entry table (one entry per cloud taking part) and a flat job list (one job per workgroup: which entry, which block of it), both in device
 // memory and both built on the host from the sizes it knows at every phase; the grid is the job list's length, whatever the largest cloud is.
 struct MapbCopyEnt // byte range to copy; bytes a multiple of 4; job = 16 KiB block of it
@@ -75,7 +60,10 @@ struct MapbXformEnt // job = 256 records
 	uint32_t n, pad_;
 	double T[12]; // rows of [R|t]
 };
-struct MapbRemEnt // one frame class cloud against its tree (dynamic removal); jobs: (frame block of 256, tree chunk of MAP_NN_CHUNK) and (frame block of 256)
+// one frame class cloud against its tree (dynamic removal); jobs: (frame block of 256, tree chunk of MAP_NN_CHUNK) and (frame block of 256).  best[i] = float
+// bits of the smallest squared distance to a tree point (0x7f800000 if there is none); tree = map class cloud, with use_box restricted to the open box (strict
+// inequalities, float vs double)
+struct MapbRemEnt
 {
 	const float4 *frame, *tree;
 	uint32_t *best;

@@ -1,4 +1,4 @@
-// pca_device.h — the neighbourhood PCA of the feature-extraction kernels (k_map_pca of map_kernels.hip, k_cl_pca of k_classify.hip):
+// pca_device.h — the neighbourhood PCA of the feature-extraction kernels (k_mapb_pca of k_map_batch.hip, k_cl_pca of k_classify.hip):
 // what pcl::PCA computes for pca.hpp:392-437, as the ABI defines it (include/mulls_hip.h) —
 //   float centroid and float demeaned covariance summed in the neighbours' order, scaled by 1 / (n - 1),
 //   eigen-decomposition of that float matrix by cyclic Jacobi rotations in double (upper triangle), eigenvalues descending,

@@ -13,10 +13,10 @@ from mulls_amd import abi, synth
 # the sizes the inputs aim at (map_kernels.hip, map.cpp)
 MAP_SEG = 4096  # records per workgroup of k_map_seg_count / k_map_seg_scatter
 MAP_SCAN_TRIP = 64  # segments per trip of k_map_seg_scan
-MAP_NN_CHUNK = 2048  # tree points per blockIdx.y of k_map_nn
+MAP_NN_CHUNK = 2048  # tree points per job of k_mapb_nn
 MAP_NN_TILE = 1024  # tree points per LDS tile
-MAP_PCA_K = 24  # list slots per lane of k_map_pca
-MAP_BBOX_SPAN = 64 * 256  # records one trip of k_map_bbox's grid covers per class
+MAP_PCA_K = 24  # list slots per lane of k_mapb_pca
+MAP_BBOX_SPAN = 64 * 256  # records of a class cloud beyond which the bounds take many 2048-record tiles of k_mapb_bbox (eight)
 PCA_RADIUS = np.float32(1.8)
 PCA_MAX_K = 20
 PCA_MIN_K = 6

@@ -1,7 +1,14 @@
 """mulls_map_update_batch against mulls_map_update: every case drives twin maps with single calls and asks for the same bytes — all six class clouds, the six
 frame clouds, the pose and the report without ms_total — after every batched update, and holds at least one item per case to the oracle as test_gpu_map.drive
-does.  Inputs are the generators that exist: test_map.small_frames / linear_frames and the scenes of tests/map_edges.py.  No tolerance anywhere."""
+does.  mulls_map_update runs as a batch of one, so the twin comparison states "a batch of N equals N batches of one"; what holds both to the bytes the
+separate single path left behind is tests/golden/map_update_digests.json: a SHA-256 per stream and step over state(map) and the report up to ms_total, pad
+words included, recorded from single calls before that path was removed (record_digests, run by hand: see the end of this module).
+Inputs are the generators that exist: test_map.small_frames / linear_frames and the scenes of tests/map_edges.py.  No tolerance anywhere."""
 import ctypes as C
+import hashlib
+import json
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -53,6 +60,28 @@ def state(m):
     return [m.download(c).tobytes() for c in range(6)], [m.frame_download(c).tobytes() for c in range(6)], m.pose().tobytes()
 
 
+def digest(m, rep):
+    """SHA-256 over everything state() returns (each part behind its length) and the report up to ms_total"""
+    clouds, frames, pose = state(m)
+    h = hashlib.sha256()
+    for part in clouds + frames + [pose, bytes(rep)[:REPORT_BYTES]]:
+        h.update(len(part).to_bytes(8, "little"))
+        h.update(part)
+    return h.hexdigest()
+
+
+DIGEST_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "map_update_digests.json")
+_recorded = {}
+
+
+def recorded(key):
+    """the digests of stream `key` ("case/index"), one per step"""
+    if not _recorded:
+        with open(DIGEST_FILE) as f:
+            _recorded.update(json.load(f))
+    return _recorded[key]
+
+
 def same_report(a, b):
     assert bytes(a)[:REPORT_BYTES] == bytes(b)[:REPORT_BYTES]
 
@@ -69,9 +98,16 @@ def against_oracle(m, rep, clouds, appended, ro, P, pose):
     assert np.array_equal(m.pose(), pose)
 
 
-def lockstep(ctx, streams, oracle=(0,), max_lockstep=0, shared=None):
+# the streams of each case held to the oracle: every one
+ORACLE = {"mixed": range(5), "removal": range(9), "refresh": range(7), "capacity": range(11), "seven": range(7), "random": range(4)}
+
+
+def lockstep(ctx, streams, oracle=(0,), max_lockstep=0, shared=None, digests=None):
     """Every stream's k-th update as ONE batch per k; twins by single calls; the streams named in `oracle` also against pyoracle.map_update.
-    shared: (index, params) — that stream passes no params of its own.  Returns the per-step list of (reports, stats) and the maps."""
+    shared: (index, params) — that stream passes no params of its own.  digests: a case of DIGEST_CASES (its streams in order) or one key of the recorded
+    digests per stream — the batched map and the twin both have the recorded digest after every step.  Returns the per-step list of (reports, stats) and the maps."""
+    if isinstance(digests, str):
+        digests = ["%s/%d" % (digests, i) for i in range(len(streams))]
     maps = [ctx.local_map(s.clouds, s.pose) for s in streams]
     twins = [ctx.local_map(s.clouds, s.pose) for s in streams]
     host = {i: ([c.copy() for c in streams[i].clouds], streams[i].pose) for i in oracle}
@@ -89,6 +125,8 @@ def lockstep(ctx, streams, oracle=(0,), max_lockstep=0, shared=None):
             rt = twins[i].update(fc, fp, P)
             same_report(reps[j], rt)
             assert state(maps[i]) == state(twins[i]), (k, i)
+            if digests is not None:
+                assert digest(maps[i], reps[j]) == digest(twins[i], rt) == recorded(digests[i])[k], (k, i, digests[i])
             if i in host:
                 clouds, appended, ro = pyoracle.map_update(host[i][0], host[i][1], fc, fp, P)
                 host[i] = (clouds, fp)
@@ -104,7 +142,8 @@ def close(*groups):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------- parameters
-def test_mixed_parameters_three_updates_five_maps(ctx_auto):
+def mixed_streams():
+    """(the last stream passes no params of its own: its steps' params are the batch's shared ones)"""
     wide = dict(max_num_pts=10**7, kept_vertex_num=10**6)
     per_stream = [
         lambda k: abi.map_params(used_feature_type="111110", local_map_radius=45.0, **wide),
@@ -115,16 +154,21 @@ def test_mixed_parameters_three_updates_five_maps(ctx_auto):
     shared = abi.map_params(max_num_pts=2500, kept_vertex_num=10**6, local_map_radius=80.0, rng_seed=5)
     streams = [of_frames(small_frames(40 + 10 * i, n_frames=4), per_stream[i]) for i in range(4)]
     streams.append(of_frames(small_frames(95, n_frames=4), lambda k: shared))
-    out, maps, twins = lockstep(ctx_auto, streams, oracle=(1, 4), shared=(4, shared))
+    return streams
+
+
+def test_mixed_parameters_three_updates_five_maps(ctx_auto):
+    streams = mixed_streams()
+    out, maps, twins = lockstep(ctx_auto, streams, oracle=ORACLE["mixed"], shared=(4, streams[4].steps[0][2]), digests="mixed")
     assert len(out) == 3 and out[-1][0][1].n[5] == 130 and out[-1][0][4].feature_point_num <= 2505
     close(maps, twins)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------- dynamic removal
-def test_dynamic_removal_in_one_batch(ctx_auto):
+def removal_streams():
     n0 = E.scene_n(0)
     no_pillars = E.Case("N(0) without map pillars", [E.empty() if c == abi.PILLAR else n0.map_clouds[c] for c in range(6)], n0.map_pose, n0.frames, n0.params)
-    streams = [
+    return [
         of_case(n0),  # tree_mode 1; frame classes of 11, 257 and 1001 points
         of_case(E.scene_n(1)),  # a facade of 10 points: not searched
         of_case(E.scene_n(2)),  # tree_mode 2
@@ -135,7 +179,12 @@ def test_dynamic_removal_in_one_batch(ctx_auto):
         of_case(no_pillars),  # an empty map class
         of_case(E.scene_n(7), tree_box=[-8.0, -8.0, -0.5, 8.0, 8.0, 20.0]),
     ]
-    out, maps, twins = lockstep(ctx_auto, streams, oracle=(0, 2, 7))
+
+
+def test_dynamic_removal_in_one_batch(ctx_auto):
+    n0 = E.scene_n(0)
+    streams = removal_streams()
+    out, maps, twins = lockstep(ctx_auto, streams, oracle=ORACLE["removal"], digests="removal")
     reps = out[0][0]
     assert [r.dynamic_removal_ran for r in reps] == [1, 1, 1, 1, 1, 0, 0, 1, 1]
     assert reps[1].frame_n[abi.FACADE] == 10 and reps[7].frame_n[abi.PILLAR] == len(n0.frames[0][0][abi.PILLAR])
@@ -149,9 +198,9 @@ def test_dynamic_removal_in_one_batch(ctx_auto):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------- PCA refresh
-def test_pca_refresh_mixed_on_and_off(ctx_auto):
+def refresh_streams():
     kw = dict(max_num_pts=10**7, kept_vertex_num=10**6, local_map_radius=60.0)
-    streams = [
+    return [
         of_frames(linear_frames(310, n_frames=3), lambda k: abi.map_params(recalculate_feature_on=1, used_feature_type="111110" if k != 2 else "110010", **kw)),
         of_frames(linear_frames(320, n_frames=3), lambda k: abi.map_params(recalculate_feature_on=0, **kw)),
         of_frames(linear_frames(330, n_frames=3), lambda k: abi.map_params(recalculate_feature_on=k % 2, max_num_pts=2500, kept_vertex_num=60, rng_seed=77,
@@ -161,9 +210,13 @@ def test_pca_refresh_mixed_on_and_off(ctx_auto):
         of_case(E.scene_p(257, "descending")),
         of_case(E.scene_p(257, "random"), recalculate_feature_on=0),
     ]
+
+
+def test_pca_refresh_mixed_on_and_off(ctx_auto):
+    streams = refresh_streams()
     ties = E.neighbour_lists(E.scene_p(256, "ascending").pillar_xyz)
     assert np.any(ties["tie_at_k"])  # neighbourhoods whose rank-K candidate has an equal
-    out, maps, twins = lockstep(ctx_auto, streams, oracle=(0, 3, 4, 5))
+    out, maps, twins = lockstep(ctx_auto, streams, oracle=ORACLE["refresh"], digests="refresh")
     reps = out[0][0]
     for j, n in ((3, 255), (4, 256), (5, 257)):
         assert 0 < reps[j].n[abi.PILLAR] < n and 0 < reps[j].n[abi.BEAM] < n
@@ -188,10 +241,10 @@ def segment_edges():
     return Stream(m, E.S_POSES[0], [(f, E.S_POSES[1], P)])
 
 
-def test_capacity_edges_side_by_side(ctx_auto):
+def capacity_streams():
     n0 = E.scene_n(0)
     none = [E.empty() for _ in range(6)]
-    streams = [
+    return [
         of_case(E.scene_s_removal()),  # class clouds of 4095, 4096, 4097 and 8192 records, a frame pillar cloud of 8193, a facade of 4097
         of_case(E.scene_n(0)),  # trees of 1, 1023, 1024; frames of 11, 257, 1001
         of_case(E.scene_n(1)),  # trees of 1025, 2047, 2048; frames of 255, 256, 10
@@ -204,9 +257,13 @@ def test_capacity_edges_side_by_side(ctx_auto):
         of_case(E.scene_s_pca()),  # the refresh's compaction across a segment edge
         segment_edges(),
     ]
+
+
+def test_capacity_edges_side_by_side(ctx_auto):
+    streams = capacity_streams()
     assert sorted(len(c) for c in streams[0].clouds)[:4] == [4095, 4096, 4097, 8192] and len(streams[0].steps[0][0][abi.PILLAR]) == 8193
     assert [len(c) for c in streams[10].clouds] == [4095, 8193, 4096, 4097, 1, 0]
-    out, maps, twins = lockstep(ctx_auto, streams, oracle=(1, 4, 5, 8, 10))
+    out, maps, twins = lockstep(ctx_auto, streams, oracle=ORACLE["capacity"], digests="capacity")
     big = np.finfo(np.float64).max
     assert list(out[0][0][5].local_bound) == [big] * 3 + [-big] * 3
     close(maps, twins)
@@ -230,14 +287,14 @@ def seven_streams():
 def test_an_item_is_independent_of_its_batch(ctx_auto):
     S = seven_streams()
     X = 3
-    alone, m1, t1 = lockstep(ctx_auto, [S[X]], oracle=(0,))
+    alone, m1, t1 = lockstep(ctx_auto, [S[X]], oracle=(0,), digests=["seven/%d" % X])
     want, want_rep = state(m1[0]), bytes(alone[0][0][0])[:REPORT_BYTES]
     assert alone[0][0][0].dynamic_removal_ran == 1 and alone[0][1].n_groups == 1
-    cut, m2, t2 = lockstep(ctx_auto, S, oracle=(), max_lockstep=3)
+    cut, m2, t2 = lockstep(ctx_auto, S, oracle=ORACLE["seven"], max_lockstep=3, digests="seven")
     assert cut[0][1].n_groups == 3  # cuts after 3 and 6
     assert state(m2[X]) == want and bytes(cut[0][0][X])[:REPORT_BYTES] == want_rep
     order = [5, 2, 6, 0, 4, 1, 3]
-    mixed, m3, t3 = lockstep(ctx_auto, [S[i] for i in order], oracle=(), max_lockstep=0)
+    mixed, m3, t3 = lockstep(ctx_auto, [S[i] for i in order], oracle=(), max_lockstep=0, digests=["seven/%d" % i for i in order])
     assert mixed[0][1].n_groups == 1
     for pos, i in enumerate(order):
         assert state(m3[pos]) == state(m2[i]) and bytes(mixed[0][0][pos])[:REPORT_BYTES] == bytes(cut[0][0][i])[:REPORT_BYTES]
@@ -447,8 +504,40 @@ def random_stream(block):
     return of_frames([(mutate(fc), fp) for fc, fp in frames], params)
 
 
+def random_streams():
+    return [random_stream(b) for b in range(4)]
+
+
 def test_random_sequences_in_lock_step(ctx_auto):
-    streams = [random_stream(b) for b in range(4)]
-    out, maps, twins = lockstep(ctx_auto, streams, oracle=(0, 1, 2, 3))
+    out, maps, twins = lockstep(ctx_auto, random_streams(), oracle=ORACLE["random"], digests="random")
     assert len(out) == 3
     close(maps, twins)
+
+
+# ------------------------------------------------------------------------------------------------------------------------- recorded digests
+DIGEST_CASES = {"mixed": mixed_streams, "removal": removal_streams, "refresh": refresh_streams, "capacity": capacity_streams, "seven": seven_streams,
+                "random": random_streams}
+
+
+def record_digests(ctx):
+    """what mulls_map_update (LocalMap.update) leaves behind, per stream and step of DIGEST_CASES.  The file in tests/golden/ was written by this function from
+    the commit before mulls_map_update became a batch of one; it is not a fixture to refresh when a test fails.
+        PYTHONPATH=. python tests/test_gpu_map_batch.py --record-digests [file]"""
+    out = {}
+    for name, make in DIGEST_CASES.items():
+        for i, s in enumerate(make()):
+            m = ctx.local_map(s.clouds, s.pose)
+            out["%s/%d" % (name, i)] = [digest(m, m.update(fc, fp, P)) for fc, fp, P in s.steps]
+            m.close()
+    return out
+
+
+if __name__ == "__main__" and "--record-digests" in sys.argv:
+    from mulls_amd import lib
+
+    context = lib.Context(0)
+    target = sys.argv[sys.argv.index("--record-digests") + 1] if len(sys.argv) > sys.argv.index("--record-digests") + 1 else DIGEST_FILE
+    with open(target, "w") as f:
+        json.dump(record_digests(context), f, indent=0, sort_keys=True)
+        f.write("\n")
+    context.close()

@@ -12,7 +12,8 @@ import map_edges as E
 from mulls_amd import abi, synth
 from oracle import pyoracle
 from test_gpu_map import drive
-from test_map import same_cloud
+from test_gpu_map_batch import against_oracle, same_report, state
+from test_map import same_cloud, small_frames
 
 pytestmark = pytest.mark.gpu
 
@@ -241,3 +242,86 @@ def test_abi_device_resident_sources_mixed_with_host_strides(ctx_auto):
         same_cloud(third.download(c), abi.as_points(fc[c]))  # lending its clouds changed nothing in the third map
     for m in (first, second, third):
         m.close()
+
+
+# ------------------------------------------------------------------------------------------- the single call: refusals and lent device clouds
+def refused_for_a_bad_cloud(ctx):
+    """A map updated once, then an update whose class 3 has four points and no pointer behind three valid classes of 1, 257 and 0 records: the status, the
+    text, the zeroed report, and map clouds, counts and pose as they were.  Returns what the caller may ask beyond that.
+    The first update refreshes the pillars, whose cloud holds one point far from every other: it sets the report's upper x bound (the bounds are taken before
+    the refresh) and the refresh drops it, so bounds carried by has_bounds differ from bounds taken from the records."""
+    lib = ctx.lib
+    frames = small_frames(90, n_frames=3)
+    start = [abi.as_points(c) for c in frames[0][0]]
+    start[abi.PILLAR] = np.concatenate([start[abi.PILLAR], E.records(np.array([[75.0, 0.0, 1.0]]), 90)])
+    m = ctx.local_map(start, frames[0][1])
+    P = abi.map_params(recalculate_feature_on=1, max_num_pts=10**7, kept_vertex_num=10**6, local_map_radius=80.0)
+    rep0 = m.update(frames[1][0], frames[1][1], P)
+    store = ctx.submaps(40000, 4)
+    info = store.push_map(m, id_in_strip=0)
+    kept_x = np.concatenate([E.xyz_of(m.download(c))[:, 0] for c in range(6)])
+    assert list(info.local_bound) == list(rep0.local_bound) and rep0.local_bound[3] > float(kept_x.max()) + 1.0
+    before = state(m)
+    sizes = [m.cloud(c).n for c in range(6)]
+    fc = [abi.as_points(c) for c in frames[2][0]]
+    held = [fc[0][:1], fc[abi.FACADE][:257], fc[2][:0]]  # (any records do: the call is refused before it looks at them)
+    assert [len(h) for h in held] == [1, 257, 0]
+    nowhere = abi.Cloud()
+    nowhere.pts, nowhere.n, nowhere.stride = None, 4, 48
+    arr = (abi.Cloud * 6)(*([abi.as_cloud(h) for h in held] + [nowhere, abi.as_cloud(None), abi.as_cloud(None)]))
+    rep = abi.MapReport()
+    C.memset(C.byref(rep), 0x5A, C.sizeof(rep))
+    rc = lib.mulls_map_update(ctx.h, m.h, arr, abi.colmajor16(frames[2][1]), C.byref(P), C.byref(rep))
+    assert rc == abi.MULLS_E_INVALID
+    assert lib.mulls_last_error(ctx.h) == b"cloud with points but null pointer or stride < 48"
+    assert bytes(rep) == bytes(C.sizeof(rep))
+    after = state(m)
+    assert after[0] == before[0] and after[2] == before[2] and [m.cloud(c).n for c in range(6)] == sizes
+    return m, store, before, after, rep0
+
+
+def test_single_call_refused_for_a_bad_cloud_leaves_the_map_untouched(ctx_auto):
+    m, store, before, after, rep0 = refused_for_a_bad_cloud(ctx_auto)
+    assert after[1] == before[1]  # the frame clouds of the update before it
+    info = store.push_map(m, id_in_strip=1)  # has_bounds still set: the archive carries the report's bounds, not the records'
+    assert list(info.local_bound) == list(rep0.local_bound) and list(info.bound) == list(rep0.bound)
+    store.close()
+    m.close()
+
+
+def test_single_call_with_another_maps_device_clouds_as_the_frame(ctx_auto):
+    """all six frame clouds lent by another map of the context == the same update from host copies == the oracle"""
+    ctx = ctx_auto
+    frames = small_frames(110, n_frames=2)
+    (mc, mp), (fc, fp) = frames
+    P = abi.map_params(max_num_pts=1800, kept_vertex_num=130, local_map_radius=35.0, rng_seed=12, map_based_dynamic_removal_on=1, tree_mode=1,
+                       tree_used="111110")
+    lender = ctx.local_map(fc, fp)
+    lent, hosted = ctx.local_map(mc, mp), ctx.local_map(mc, mp)
+    r_lent = lent.update([lender.cloud(c) for c in range(6)], fp, P)
+    r_host = hosted.update(fc, fp, P)
+    same_report(r_lent, r_host)
+    assert state(lent) == state(hosted) and r_lent.dynamic_removal_ran == 1
+    clouds, appended, ro = pyoracle.map_update(mc, mp, fc, fp, P)
+    against_oracle(lent, r_lent, clouds, appended, ro, P, fp)
+    for c in range(6):
+        same_cloud(lender.download(c), abi.as_points(fc[c]))
+    for m in (lender, lent, hosted):
+        m.close()
+
+
+def test_single_call_with_the_maps_own_vertex_cloud_as_the_frame(ctx_auto):
+    """the vertex frame cloud is mulls_map_cloud(map, VERTEX) of the map being updated: accepted, and the bytes of the update from a host copy of it"""
+    ctx = ctx_auto
+    frames = small_frames(120, n_frames=2)
+    (mc, mp), (fc, fp) = frames
+    P = abi.map_params(max_num_pts=10**7, kept_vertex_num=10**6, local_map_radius=60.0)
+    own, hosted = ctx.local_map(mc, mp), ctx.local_map(mc, mp)
+    vertex = hosted.download(abi.VERTEX)
+    assert len(vertex) == own.cloud(abi.VERTEX).n > 0
+    r_own = own.update(list(fc[:5]) + [own.cloud(abi.VERTEX)], fp, P)
+    r_host = hosted.update(list(fc[:5]) + [vertex], fp, P)
+    same_report(r_own, r_host)
+    assert state(own) == state(hosted) and r_own.n[abi.VERTEX] > 0
+    own.close()
+    hosted.close()

@@ -1,11 +1,12 @@
 """mulls_map_update_batch against as many mulls_map_update calls, in one process on one GPU.
-usage: gpu_map_batch.py [--batch 1,8,64] [--removal] [--resident] [--updates 20] [--out profiles/map_batch.txt]
+usage: gpu_map_batch.py [--batch 1,8,64] [--removal] [--resident] [--updates 20] [--map-points 20000] [--out profiles/map_batch.txt]
 
-B streams, each a map of about 20 000 feature points (max_num_pts = 20000, so it stays there) and a drive of frames of the KITTI fixed-number sizes
-(synth.R_SOURCE).  Every update runs twice: as one batched call on the maps and as B single calls on twin maps; after every update all twelve clouds, the pose
-and the report of every stream are compared byte for byte, and only then is a time printed.  Times are medians of the C calls alone (arguments marshalled
-beforehand) over `--updates` updates after one warm-up update.  --removal: map-based dynamic removal on (tree_mode 1).  --resident: the frames are device
-clouds (lent by maps that hold them), as a feature block's would be."""
+B streams, each a map of about --map-points feature points (max_num_pts = that, so it stays there) and a drive of frames of the KITTI fixed-number sizes
+(synth.R_SOURCE).  Every update runs twice: as one batched call on the maps and as B single calls on twin maps.  A single call is a batch of one, so the
+"single calls" column is B groups of one against one group of B: what lock step saves, and at B = 1 the cost of the single entry point itself.  After every
+update all twelve clouds, the pose and the report of every stream are compared byte for byte, and only then is a time printed.  Times are medians of the C
+calls alone (arguments marshalled beforehand) over `--updates` updates after one warm-up update.  --removal: map-based dynamic removal on (tree_mode 1).
+--resident: the frames are device clouds (lent by maps that hold them), as a feature block's would be."""
 import argparse
 import ctypes as C
 import os
@@ -21,10 +22,12 @@ MAP_COUNTS = {abi.GROUND: 7000, abi.PILLAR: 2500, abi.FACADE: 8500, abi.BEAM: 12
 N_SCENES, N_FRAMES = 4, 6
 
 
-def scenes():
+def scenes(map_points):
     out = []
+    scale = map_points / 20000.0  # (a scan of 64 beams has about 120 000 returns: more beams for a larger map)
+    counts = {c: int(n * scale) for c, n in MAP_COUNTS.items()}
     for s in range(N_SCENES):
-        pair, _ = synth.make_pair(500 + s, tgt_counts=MAP_COUNTS, vertex_count=800)
+        pair, _ = synth.make_pair(500 + s, n_beams=64 * max(1, round(scale / 5)), tgt_counts=counts, vertex_count=800)
         drive = synth.drive(500 + s, N_FRAMES + 1, n_beams=64, n_az=1900, counts=synth.R_SOURCE, vertex_count=300)[1:]
         out.append(([pair.tgt[c] for c in range(6)], drive))
     return out
@@ -34,8 +37,8 @@ def state(m):
     return [m.download(c).tobytes() for c in range(6)], [m.frame_download(c).tobytes() for c in range(6)], m.pose().tobytes()
 
 
-def run(ctx, world, B, updates, removal, resident):
-    P = abi.map_params(max_num_pts=20000, kept_vertex_num=800, local_map_radius=80.0, rng_seed=1, map_based_dynamic_removal_on=int(removal),
+def run(ctx, world, B, updates, removal, resident, map_points):
+    P = abi.map_params(max_num_pts=map_points, kept_vertex_num=800, local_map_radius=80.0, rng_seed=1, map_based_dynamic_removal_on=int(removal),
                        tree_mode=1 if removal else 0, tree_used="111110" if removal else "000000")
     maps = [ctx.local_map(world[i % N_SCENES][0], np.eye(4)) for i in range(B)]
     twins = [ctx.local_map(world[i % N_SCENES][0], np.eye(4)) for i in range(B)]
@@ -84,12 +87,13 @@ def main():
     ap.add_argument("--removal", action="store_true")
     ap.add_argument("--resident", action="store_true")
     ap.add_argument("--updates", type=int, default=20)
+    ap.add_argument("--map-points", type=int, default=20000)
     ap.add_argument("--out", default=os.path.join("profiles", "map_batch.txt"))
     a = ap.parse_args()
     assert a.updates >= 20, "medians of at least 20 updates"
-    world = scenes()
+    world = scenes(a.map_points)
     ctx = lib.Context(0)
-    lines = [run(ctx, world, int(b), a.updates, a.removal, a.resident) for b in a.batch.split(",")]
+    lines = [run(ctx, world, int(b), a.updates, a.removal, a.resident, a.map_points) for b in a.batch.split(",")]
     ctx.close()
     with open(a.out, "a") as f:
         for line in lines:
