@@ -802,6 +802,47 @@ inline int coarse_reg_ransac(const typename pcl::PointCloud<PointT>::Ptr &target
 	return R.status;
 }
 
+// Many coarse_reg_ransac calls in one (mulls_coarse_reg_ransac_batch): the candidate edges of a loop-closure event under
+// --teaser_based_global_registration_on=false (test/mulls_slam.cpp:517-557 solves them one after another until one is accepted).  Pair k is targets[k] /
+// sources[k] with trans[k]; the return value's entry k and trans[k] are what coarse_reg_ransac<PointT>(targets[k], sources[k], trans[k], noise_bound,
+// min_inlier_num, max_iter_num) returns and writes (trans[k] is untouched on -1).  The three vectors have one length.  INTEGRATION.md shows the loop
+// restructured around it.
+template <typename PointT>
+inline std::vector<int> coarse_reg_ransac_batch(const std::vector<typename pcl::PointCloud<PointT>::Ptr> &targets,
+												const std::vector<typename pcl::PointCloud<PointT>::Ptr> &sources, std::vector<Eigen::Matrix4d> &trans,
+												float noise_bound = 0.2, int min_inlier_num = 8, int max_iter_num = 20000)
+{
+	if (targets.size() != sources.size() || targets.size() != trans.size())
+		throw std::invalid_argument("coarse_reg_ransac_batch: targets, sources and trans must have one length");
+	mulls_ctx *ctx = thread_context();
+	std::vector<mulls_ransac_problem> problems(targets.size());
+	for (size_t k = 0; k < targets.size(); k++)
+	{
+		problems[k] = mulls_ransac_problem();
+		problems[k].tgt = borrow(targets[k]);
+		problems[k].src = borrow(sources[k]);
+	}
+	mulls_ransac_params P;
+	mulls_ransac_default_params(&P);
+	P.noise_bound = noise_bound;
+	P.min_inlier_num = min_inlier_num;
+	P.max_iter_num = max_iter_num;
+	std::vector<mulls_ransac_result> R(targets.size());
+	const int rc = mulls_coarse_reg_ransac_batch(ctx, problems.data(), (uint32_t)problems.size(), &P, 0, R.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_coarse_reg_ransac_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	std::vector<int> status(targets.size());
+	for (size_t k = 0; k < targets.size(); k++)
+	{
+		status[k] = R[k].status;
+		if (R[k].status >= 0)
+			for (int c = 0; c < 4; c++)
+				for (int r = 0; r < 4; r++)
+					trans[k](r, c) = R[k].T[c * 4 + r];
+	}
+	return status;
+}
+
 // CRegistration<PointT>::coarse_reg_teaser (include/common/cregistration.hpp:664-759), verbatim signature and defaults: the TEASER solver of the global (coarse)
 // registration every shipped configuration selects (test/mulls_reg.cpp:177, test/mulls_slam.cpp:537) in one call (mulls_coarse_reg_teaser).  The binding is
 // one early return at the top of the member function, outside upstream's `#if TEASER_ON`: the bridge always solves, where upstream compiles the body out

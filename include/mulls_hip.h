@@ -799,6 +799,38 @@ int mulls_coarse_reg_ransac(mulls_ctx *ctx, const mulls_cloud *tgt_pts, const mu
 int mulls_coarse_reg_ransac_indexed(mulls_ctx *ctx, const mulls_cloud *tgt_kpts, const mulls_cloud *src_kpts, const int32_t *tgt_idx, const int32_t *src_idx,
 									uint32_t n_corr, const mulls_ransac_params *params, mulls_ransac_result *result, int32_t *inliers, uint32_t cap);
 
+/* ---- many RANSAC problems per call: the candidate edges of one loop-closure event under --teaser_based_global_registration_on=false
+ * (test/mulls_slam.cpp:517-596 tries them one after another), behind mulls_ncc_correspond_batch and in front of mulls_icp_batch.
+ * results[b] and problems[b].inliers[] are THE BYTES THE MATCHING SINGLE CALL RETURNS for problem b on the same context (mulls_coarse_reg_ransac when both
+ * index lists are NULL, mulls_coarse_reg_ransac_indexed when both are set): every field of the result, every bit of T, the inlier list, the slot behind
+ * inlier_cap left alone.  No arithmetic is redefined; every order of summation holds per problem (the float models, the 256 strided partial sums and
+ * pairwise tree of the refinement fit, the radix-select median).  The device steps run for all problems of a sub-batch per launch: one launch for all
+ * models, one for all counts, one for all winners' masks, and the refinement in lock step, one launch per round with one workgroup per problem that still
+ * refines; a problem that has ended is not launched again, so its masks and model are frozen (addendum).  The draws run per
+ * problem on the host, the problems side by side.
+ *   per problem   PCL's pass-through outcomes (fewer than 3 pairs, no good first sample, fewer than 3 inliers) give the single call's result; the rest of
+ *                 the batch runs.
+ *   whole call    checked for every problem before any device work and before any result is written: a problem the single call would refuse (a bad
+ *                 stride, sizes that differ, an index outside its cloud, more than 65536 pairs, one index list without the other, a NULL it needs),
+ *                 max_iter_num > 2^20 and a non-finite noise_bound make the call return the single call's code, name the first such problem's index in
+ *                 mulls_last_error (a refused parameter refuses problem 0), and leave every result at status -1, best_iteration -1, identity T.
+ *   scratch_limit_bytes  bounds the device arena: per problem the two packed float4 pair arrays, the index lists, max_iter_num + 1 triples, models and
+ *                 counts, three masks, the squared distances and one round record.  The batch is cut into consecutive sub-batches that fit; a problem
+ *                 larger than the limit runs alone.  0: MULLS_RANSAC_BATCH_DEFAULT_SCRATCH_BYTES, a value chosen without a measurement.
+ * n_problems = 0: MULLS_OK. */
+#define MULLS_RANSAC_BATCH_DEFAULT_SCRATCH_BYTES (512ull << 20)
+typedef struct mulls_ransac_problem
+{
+	mulls_cloud tgt, src;			  /* host or device-resident clouds, by the single call's rules (strides included) */
+	const int32_t *tgt_idx, *src_idx; /* both NULL: pair i = point i of each cloud; both set: the n_corr pairs they name */
+	uint32_t n_corr;				  /* read only when the index lists are set */
+	uint32_t inlier_cap;
+	int32_t *inliers;				  /* inlier_cap entries, or NULL with inlier_cap = 0 */
+} mulls_ransac_problem;
+
+int mulls_coarse_reg_ransac_batch(mulls_ctx *ctx, const mulls_ransac_problem *problems, uint32_t n_problems, const mulls_ransac_params *params,
+								  uint64_t scratch_limit_bytes, mulls_ransac_result *results);
+
 /* ---- TEASER coarse registration: CRegistration<PointT>::coarse_reg_teaser (include/common/cregistration.hpp:664-759) ----
  * The solver every shipped configuration selects (--teaser_based_global_registration_on=true) between mulls_ncc_correspond's pairs and mulls_icp's initial
  * guess.  Upstream's body is one call of TEASER++'s RobustRegistrationSolver (no scale estimation, maximum clique, GNC-TLS rotation).  TEASER++ is not

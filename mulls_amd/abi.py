@@ -387,6 +387,16 @@ def ransac_params(noise_bound=0.2, min_inlier_num=8, max_iter_num=20000, refine=
     return p
 
 
+class RansacProblem(C.Structure):
+    """mulls_ransac_problem: one problem of mulls_coarse_reg_ransac_batch"""
+
+    _fields_ = [("tgt", Cloud), ("src", Cloud), ("tgt_idx", C.c_void_p), ("src_idx", C.c_void_p), ("n_corr", C.c_uint32), ("inlier_cap", C.c_uint32),
+                ("inliers", C.c_void_p)]
+
+
+RANSAC_BATCH_DEFAULT_SCRATCH_BYTES = 512 << 20  # MULLS_RANSAC_BATCH_DEFAULT_SCRATCH_BYTES
+
+
 class TeaserParams(C.Structure):
     """mulls_teaser_params: coarse_reg_teaser's arguments behind the clouds (cregistration.hpp:666), and the clique search's node budget"""
 

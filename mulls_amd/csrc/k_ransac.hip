@@ -4,6 +4,8 @@
 //   k_ransac_score   one wave per four hypotheses: the lanes stride over the pairs, the models sit in scalar registers
 //   k_ransac_select  the inlier mask of one model
 //   k_ransac_refine  one workgroup: a round of PCL's refineModel — fit to the previous inliers, select, exact median by radix select
+//   k_rb_*           the same five steps for the problems of a sub-batch of mulls_coarse_reg_ransac_batch, read from a descriptor table (ransac_batch.h):
+//                    the second grid axis is the problem (refine: a job list), the arithmetic is the __device__ functions the kernels above call
 // Every float / double expression is written in the order include/mulls_hip.h and DESIGN.md section 7 define (built with -ffp-contract=off):
 // tests/ransac_restated.py reproduces the bits.
 #include <hip/hip_runtime.h>
@@ -38,16 +40,14 @@ __global__ void __launch_bounds__(256) k_ransac_gather(const unsigned char *recs
 	out[i] = *reinterpret_cast<const float4 *>(recs + r * 48u);
 }
 
-__global__ void __launch_bounds__(256) k_ransac_models(const float4 *src, const float4 *tgt, const int32_t *triples, uint32_t n_hyp, RansacModel *models)
+// the rigid transform of the three pairs tri[0 .. 2]
+__device__ __forceinline__ RansacModel sample_model(const float4 *src, const float4 *tgt, const int32_t *tri)
 {
-	const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
-	if (h >= n_hyp)
-		return;
 	float s[3][3], t[3][3];
 #pragma unroll
 	for (int k = 0; k < 3; k++)
 	{
-		const int32_t i = triples[3u * h + k];
+		const int32_t i = tri[k];
 		const float4 a = src[i], b = tgt[i];
 		s[k][0] = a.x, s[k][1] = a.y, s[k][2] = a.z;
 		t[k][0] = b.x, t[k][1] = b.y, t[k][2] = b.z;
@@ -73,7 +73,15 @@ __global__ void __launch_bounds__(256) k_ransac_models(const float4 *src, const 
 	}
 	RansacModel M;
 	horn_fit(H, csd, ctd, M.m);
-	models[h] = M;
+	return M;
+}
+
+__global__ void __launch_bounds__(256) k_ransac_models(const float4 *src, const float4 *tgt, const int32_t *triples, uint32_t n_hyp, RansacModel *models)
+{
+	const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
+	if (h >= n_hyp)
+		return;
+	models[h] = sample_model(src, tgt, triples + 3u * h);
 }
 
 __global__ void __launch_bounds__(SCORE_THREADS) k_ransac_score(const float4 *__restrict__ src, const float4 *__restrict__ tgt, uint32_t n,
@@ -113,10 +121,10 @@ __global__ void __launch_bounds__(SCORE_THREADS) k_ransac_score(const float4 *__
 	}
 }
 
-__global__ void __launch_bounds__(256) k_ransac_select(const float4 *src, const float4 *tgt, uint32_t n, const RansacModel *model, double thresh, uint8_t *mask,
-														uint32_t *count)
+// pair i's entry of the inlier mask of *model, and the wave's share of their count
+__device__ __forceinline__ void select_pair(const float4 *src, const float4 *tgt, uint32_t n, const RansacModel *model, double thresh, uint8_t *mask, uint32_t *count,
+											 uint32_t i)
 {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	float m[12];
 #pragma unroll
 	for (int k = 0; k < 12; k++)
@@ -130,6 +138,12 @@ __global__ void __launch_bounds__(256) k_ransac_select(const float4 *src, const 
 	const unsigned long long b = __ballot(in);
 	if (threadIdx.x % WAVE == 0 && b)
 		atomicAdd(count, (uint32_t)__popcll(b));
+}
+
+__global__ void __launch_bounds__(256) k_ransac_select(const float4 *src, const float4 *tgt, uint32_t n, const RansacModel *model, double thresh, uint8_t *mask,
+														uint32_t *count)
+{
+	select_pair(src, tgt, n, model, thresh, mask, count, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // sum of v over the workgroup in the defined order: the RT per-thread values by a pairwise tree, p[t] += p[t + s] for s = RT / 2, ..., 1
@@ -148,8 +162,9 @@ __device__ double block_tree_sum(double v, double *red)
 	return red[0];
 }
 
-__global__ void __launch_bounds__(RT) k_ransac_refine(const float4 *src, const float4 *tgt, uint32_t n, const uint8_t *mask_prev, uint8_t *mask_new, float *d2,
-													   double thresh, RansacRound *out)
+// one round of refineModel by one workgroup of RT threads (its shared state is the block's): fit, select, radix-select median
+__device__ __forceinline__ void refine_round(const float4 *src, const float4 *tgt, uint32_t n, const uint8_t *mask_prev, uint8_t *mask_new, float *d2, double thresh,
+											  RansacRound *out)
 {
 	__shared__ double red[RT];
 	__shared__ uint32_t hist[256];
@@ -254,6 +269,101 @@ __global__ void __launch_bounds__(RT) k_ransac_refine(const float4 *src, const f
 		out->n_prev = n_prev;
 	}
 }
+
+__global__ void __launch_bounds__(RT) k_ransac_refine(const float4 *src, const float4 *tgt, uint32_t n, const uint8_t *mask_prev, uint8_t *mask_new, float *d2,
+													   double thresh, RansacRound *out)
+{
+	refine_round(src, tgt, n, mask_prev, mask_new, d2, thresh, out);
+}
+
+// ---- the steps for a sub-batch: blockIdx.y (refine: a job) names the problem, its descriptor the places in the arena
+template <typename T>
+__device__ __forceinline__ T *at(unsigned char *arena, uint64_t off)
+{
+	return reinterpret_cast<T *>(arena + off);
+}
+
+__global__ void __launch_bounds__(256) k_rb_gather(const RansacBatchGather *jobs, unsigned char *arena)
+{
+	const RansacBatchGather J = jobs[blockIdx.y];
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= J.n)
+		return;
+	const size_t r = J.indexed ? (size_t)at<const int32_t>(arena, J.idx)[i] : (size_t)i; // (the host has checked the index lists against the clouds' sizes)
+	at<float4>(arena, J.out)[i] = *reinterpret_cast<const float4 *>(J.recs + r * 48u);
+}
+
+__global__ void __launch_bounds__(256) k_rb_models(const RansacBatchDesc *desc, unsigned char *arena)
+{
+	const RansacBatchDesc &D = desc[blockIdx.y];
+	const uint32_t h = blockIdx.x * blockDim.x + threadIdx.x;
+	if (h >= D.n_hyp)
+		return;
+	at<RansacModel>(arena, D.models)[h] = sample_model(at<const float4>(arena, D.src), at<const float4>(arena, D.tgt), at<const int32_t>(arena, D.tri) + 3u * h);
+}
+
+// k_ransac_score's body on a problem's arrays.  A workgroup belongs to one problem (blockIdx.y): its 16 hypotheses are the problem's, the 4-per-wave and
+// 16-per-block tails are the problem's own n_hyp; the problem's and the wave's numbers are made scalar, so the descriptor and the models arrive by scalar loads
+__global__ void __launch_bounds__(SCORE_THREADS) k_rb_score(const RansacBatchDesc *__restrict__ desc, unsigned char *arena, double thresh)
+{
+	const uint32_t b = __builtin_amdgcn_readfirstlane(blockIdx.y);
+	const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE;
+	const uint32_t n = desc[b].n, n_hyp = desc[b].n_hyp, h0 = blockIdx.x * HYP_PER_BLOCK + wave * HYP_PER_WAVE;
+	if (h0 >= n_hyp)
+		return;
+	const float4 *__restrict__ src = at<const float4>(arena, desc[b].src), *__restrict__ tgt = at<const float4>(arena, desc[b].tgt);
+	const RansacModel *__restrict__ models = at<const RansacModel>(arena, desc[b].models);
+	uint32_t *__restrict__ counts = at<uint32_t>(arena, desc[b].counts);
+	float m[HYP_PER_WAVE][12];
+#pragma unroll
+	for (int j = 0; j < HYP_PER_WAVE; j++)
+	{
+		const uint32_t h = min(h0 + (uint32_t)j, n_hyp - 1u);
+#pragma unroll
+		for (int k = 0; k < 12; k++)
+			m[j][k] = models[h].m[k];
+	}
+	uint32_t c[HYP_PER_WAVE] = {0, 0, 0, 0};
+	for (uint32_t i = lane; i < n; i += WAVE)
+	{
+		const float4 s = src[i], t = tgt[i];
+#pragma unroll
+		for (int j = 0; j < HYP_PER_WAVE; j++)
+			c[j] += (double)resid2(m[j], s, t) < thresh ? 1u : 0u;
+	}
+#pragma unroll
+	for (int j = 0; j < HYP_PER_WAVE; j++)
+	{
+		uint32_t v = c[j];
+#pragma unroll
+		for (int off = WAVE / 2; off > 0; off >>= 1)
+			v += __shfl_xor(v, off, WAVE);
+		if (lane == 0 && h0 + (uint32_t)j < n_hyp)
+			counts[h0 + j] = v;
+	}
+}
+
+// the winner's mask (buffer 0) and, in the problem's winner record, its model and count (the host has zeroed the records)
+__global__ void __launch_bounds__(256) k_rb_select(const RansacBatchDesc *desc, unsigned char *arena, double thresh, RansacRound *win)
+{
+	const RansacBatchDesc &D = desc[blockIdx.y];
+	if (!D.n_hyp || blockIdx.x * blockDim.x >= D.n)
+		return;
+	const RansacModel *model = at<const RansacModel>(arena, D.models) + D.best;
+	select_pair(at<const float4>(arena, D.src), at<const float4>(arena, D.tgt), D.n, model, thresh, at<uint8_t>(arena, D.mask), &win[blockIdx.y].n_new,
+				blockIdx.x * blockDim.x + threadIdx.x);
+	if (blockIdx.x == 0 && threadIdx.x < 12u)
+		win[blockIdx.y].T.m[threadIdx.x] = model->m[threadIdx.x];
+}
+
+__global__ void __launch_bounds__(RT) k_rb_refine(const RansacBatchDesc *desc, const RansacBatchJob *jobs, unsigned char *arena)
+{
+	const RansacBatchJob J = jobs[blockIdx.x];
+	const RansacBatchDesc &D = desc[J.problem];
+	uint8_t *mask = at<uint8_t>(arena, D.mask);
+	refine_round(at<const float4>(arena, D.src), at<const float4>(arena, D.tgt), D.n, mask + (size_t)J.prev * D.mask_stride, mask + (size_t)J.next * D.mask_stride,
+				 at<float>(arena, D.d2), J.thresh, at<RansacRound>(arena, D.round));
+}
 } // namespace
 
 hipError_t launch_ransac_gather(hipStream_t st, const void *recs, const int32_t *idx, uint32_t n, float4 *out)
@@ -288,5 +398,38 @@ hipError_t launch_ransac_refine(hipStream_t st, const float4 *src, const float4 
 								double thresh, RansacRound *out)
 {
 	hipLaunchKernelGGL(k_ransac_refine, dim3(1), dim3(RT), 0, st, src, tgt, n, mask_prev, mask_new, d2, thresh, out);
+	return hipGetLastError();
+}
+
+// ---- the sub-batch: grids of (blocks of the largest problem) x (problems); a block past its problem's end returns
+hipError_t launch_ransac_batch_gather(hipStream_t st, const RansacBatchGather *jobs, uint32_t n_jobs, uint32_t n_max, unsigned char *arena)
+{
+	if (!n_jobs || !n_max)
+		return hipSuccess;
+	hipLaunchKernelGGL(k_rb_gather, dim3((n_max + 255u) / 256u, n_jobs), dim3(256), 0, st, jobs, arena);
+	return hipGetLastError();
+}
+
+hipError_t launch_ransac_batch_models(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_hyp_max, unsigned char *arena)
+{
+	hipLaunchKernelGGL(k_rb_models, dim3((n_hyp_max + 255u) / 256u, count), dim3(256), 0, st, desc, arena);
+	return hipGetLastError();
+}
+
+hipError_t launch_ransac_batch_score(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_hyp_max, unsigned char *arena, double thresh)
+{
+	hipLaunchKernelGGL(k_rb_score, dim3((n_hyp_max + HYP_PER_BLOCK - 1u) / HYP_PER_BLOCK, count), dim3(SCORE_THREADS), 0, st, desc, arena, thresh);
+	return hipGetLastError();
+}
+
+hipError_t launch_ransac_batch_select(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_max, unsigned char *arena, double thresh, RansacRound *win)
+{
+	hipLaunchKernelGGL(k_rb_select, dim3((n_max + 255u) / 256u, count), dim3(256), 0, st, desc, arena, thresh, win);
+	return hipGetLastError();
+}
+
+hipError_t launch_ransac_batch_refine(hipStream_t st, const RansacBatchDesc *desc, const RansacBatchJob *jobs, uint32_t n_jobs, unsigned char *arena)
+{
+	hipLaunchKernelGGL(k_rb_refine, dim3(n_jobs), dim3(RT), 0, st, desc, jobs, arena);
 	return hipGetLastError();
 }

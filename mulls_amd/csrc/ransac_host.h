@@ -153,52 +153,77 @@ struct RefineOutcome
 	int final_mask = 0;		  // the buffer that holds the final inlier set (not oscillating, not failed)
 	uint32_t n_inliers = 0;
 };
-// RandomSampleConsensus::refineModel(3.0, 1000) (sac.h).  Inlier sets live in three buffers: 0 holds the unrefined model's and is never written, 1 and 2 take the
-// rounds' sets in turn.  round(prev, next, thresh, step): fit the set in buffer prev, select within the squared threshold into buffer next; non-zero = error.
+// RandomSampleConsensus::refineModel(3.0, 1000) (sac.h), as a state that is fed one round at a time: the one statement of its control flow.  Inlier sets live
+// in three buffers: 0 holds the unrefined model's and is never written, 1 and 2 take the rounds' sets in turn.  refine_begin, then per round: fit the set in
+// buffer prev, select within refine_threshold() (squared) into buffer next, and refine_feed what the round reports; it answers whether another round runs
+// (prev / next / the threshold are then the next round's) or the refinement has ended (o is complete).  mulls_coarse_reg_ransac_batch keeps one state per
+// problem, as its problems stand at different rounds.
+struct RefineState
+{
+	double thr_sqr = 0, error_threshold = 0;
+	int prev = 0, next = 1;
+	uint32_t prev_size = 0;
+	std::vector<uint32_t> sizes;
+	RefineOutcome o;
+};
+inline void refine_begin(RefineState &s, double noise_bound, uint32_t n_in)
+{
+	s.thr_sqr = noise_bound * noise_bound;
+	s.error_threshold = noise_bound;
+	s.prev = 0, s.next = 1;
+	s.prev_size = n_in;
+	s.sizes.clear();
+	s.o = RefineOutcome();
+}
+inline double refine_threshold(const RefineState &s) { return s.error_threshold * s.error_threshold; }
+inline bool refine_feed(RefineState &s, const RefineStep &step)
+{
+	const double sigma_sqr = 3.0 * 3.0;
+	s.o.rounds++;
+	s.sizes.push_back(s.prev_size);
+	uint32_t new_size = step.n_new;
+	if (!new_size) // PCL fits the same set again until its round limit, and fails: the outcome without the rounds
+	{
+		s.o.failed = true;
+		return false;
+	}
+	const double variance = 2.1981 * (double)step.median; // computeVariance
+	s.error_threshold = std::sqrt(std::min(s.thr_sqr, sigma_sqr * variance));
+	std::swap(s.prev_size, new_size);
+	s.prev = s.next;
+	s.next = s.prev == 1 ? 2 : 1;
+	bool inlier_changed = step.changed;
+	if (new_size != s.prev_size)
+	{
+		const size_t m = s.sizes.size();
+		if (m >= 4 && s.sizes[m - 1] == s.sizes[m - 3] && s.sizes[m - 2] == s.sizes[m - 4])
+		{
+			s.o.oscillating = true;
+			return false;
+		}
+		inlier_changed = true;
+	}
+	if (inlier_changed && s.o.rounds < 1000)
+		return true;
+	s.o.failed = inlier_changed;
+	s.o.final_mask = s.prev;
+	s.o.n_inliers = s.prev_size;
+	return false;
+}
+// the same as a loop around round(prev, next, thresh, step): one launch and one wait per round in the single call; non-zero = error
 template <typename Round>
 int refine_control(double noise_bound, uint32_t n_in, RefineOutcome &o, Round &&round)
 {
-	const double thr_sqr = noise_bound * noise_bound, sigma_sqr = 3.0 * 3.0;
-	double error_threshold = noise_bound;
-	int prev = 0;
-	uint32_t prev_size = n_in, new_size = 0;
-	bool inlier_changed = false;
-	std::vector<uint32_t> sizes;
-	o = RefineOutcome();
-	do
+	RefineState s;
+	refine_begin(s, noise_bound, n_in);
+	for (bool more = true; more;)
 	{
-		const int next = prev == 1 ? 2 : 1;
 		RefineStep step;
-		if (int rc = round(prev, next, error_threshold * error_threshold, step))
+		o = s.o;
+		if (int rc = round(s.prev, s.next, refine_threshold(s), step))
 			return rc;
-		o.rounds++;
-		sizes.push_back(prev_size);
-		new_size = step.n_new;
-		if (!new_size) // PCL fits the same set again until its round limit, and fails: the outcome without the rounds
-		{
-			o.failed = true;
-			return 0;
-		}
-		const double variance = 2.1981 * (double)step.median; // computeVariance
-		error_threshold = std::sqrt(std::min(thr_sqr, sigma_sqr * variance));
-		inlier_changed = false;
-		std::swap(prev_size, new_size);
-		prev = next;
-		if (new_size != prev_size)
-		{
-			const size_t m = sizes.size();
-			if (m >= 4 && sizes[m - 1] == sizes[m - 3] && sizes[m - 2] == sizes[m - 4])
-			{
-				o.oscillating = true;
-				return 0;
-			}
-			inlier_changed = true;
-			continue;
-		}
-		inlier_changed = step.changed;
-	} while (inlier_changed && o.rounds < 1000);
-	o.failed = inlier_changed;
-	o.final_mask = prev;
-	o.n_inliers = prev_size;
+		more = refine_feed(s, step);
+	}
+	o = s.o;
 	return 0;
 }

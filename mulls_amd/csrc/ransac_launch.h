@@ -6,6 +6,8 @@
 #include <hip/hip_vector_types.h>
 #include <stdint.h>
 
+#include "ransac_batch.h"
+
 #define MULLS_RANSAC_MAX_POINTS 65536u
 #define MULLS_RANSAC_MAX_ITER (1 << 20)
 #define MULLS_RANSAC_REFINE_THREADS 256u // the partial sums of a refinement fit: part of the definition, not a tuning knob
@@ -38,3 +40,13 @@ hipError_t launch_ransac_select(hipStream_t st, const float4 *src, const float4 
 // one round of refineModel: fit to the pairs of mask_prev, select within thresh into mask_new, the median for the next threshold
 hipError_t launch_ransac_refine(hipStream_t st, const float4 *src, const float4 *tgt, uint32_t n, const uint8_t *mask_prev, uint8_t *mask_new, float *d2,
 								double thresh, RansacRound *out);
+
+// ---- mulls_coarse_reg_ransac_batch: the same steps for the `count` problems of a sub-batch, read from their descriptors (ransac_batch.h; device memory);
+// arena: the base the descriptors' offsets count from.  n_max / n_hyp_max: the largest problem's pairs / hypotheses (both above 0: a zero-sized grid is an error)
+hipError_t launch_ransac_batch_gather(hipStream_t st, const RansacBatchGather *jobs, uint32_t n_jobs, uint32_t n_max, unsigned char *arena);
+hipError_t launch_ransac_batch_models(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_hyp_max, unsigned char *arena);
+hipError_t launch_ransac_batch_score(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_hyp_max, unsigned char *arena, double thresh);
+// every problem's winner (desc[b].best): its mask into buffer 0, its model and count into win[b] (T, n_new; zeroed by the caller)
+hipError_t launch_ransac_batch_select(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_max, unsigned char *arena, double thresh, RansacRound *win);
+// one refinement round of the n_jobs problems the jobs name, one workgroup each; a problem without a job is not touched
+hipError_t launch_ransac_batch_refine(hipStream_t st, const RansacBatchDesc *desc, const RansacBatchJob *jobs, uint32_t n_jobs, unsigned char *arena);

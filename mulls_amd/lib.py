@@ -114,6 +114,7 @@ def load():
     lib.mulls_coarse_reg_ransac.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.RansacParams), C.POINTER(abi.RansacResult), vp, C.c_uint32]
     lib.mulls_coarse_reg_ransac_indexed.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), vp, vp, C.c_uint32, C.POINTER(abi.RansacParams),
                                                     C.POINTER(abi.RansacResult), vp, C.c_uint32]
+    lib.mulls_coarse_reg_ransac_batch.argtypes = [vp, C.POINTER(abi.RansacProblem), C.c_uint32, C.POINTER(abi.RansacParams), C.c_uint64, C.POINTER(abi.RansacResult)]
     lib.mulls_teaser_default_params.argtypes = [C.POINTER(abi.TeaserParams)]
     lib.mulls_teaser_default_params.restype = None
     lib.mulls_coarse_reg_teaser.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.TeaserParams), C.POINTER(abi.TeaserResult), vp, C.c_uint32]
@@ -185,7 +186,7 @@ EXPORTS = [
     "mulls_motion_compensate", "mulls_block_motion_compensate",
     "mulls_pack_results", "mulls_icp_batch_sharded", "mulls_pipe_create", "mulls_pipe_destroy", "mulls_pipe_depth", "mulls_pipe_ctx", "mulls_pipe_set_option", "mulls_icp_batch_begin", "mulls_icp_batch_end",
     "mulls_ncc_default_params", "mulls_ncc_correspond", "mulls_ncc_correspond_batch",
-    "mulls_ransac_default_params", "mulls_coarse_reg_ransac", "mulls_coarse_reg_ransac_indexed",
+    "mulls_ransac_default_params", "mulls_coarse_reg_ransac", "mulls_coarse_reg_ransac_indexed", "mulls_coarse_reg_ransac_batch",
     "mulls_teaser_default_params", "mulls_coarse_reg_teaser", "mulls_coarse_reg_teaser_indexed", "mulls_coarse_reg_teaser_batch",
     "mulls_sor_default_params", "mulls_sor_filter",
     "mulls_pgo_default_params", "mulls_pgo_optimize", "mulls_pgo_optimize_batch",
@@ -621,6 +622,55 @@ class Context:
             raise MullsError("mulls_coarse_reg_ransac failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
         assert inl[cap] == -1
         return res, inl[: min(res.n_inliers, cap)].copy()
+
+    def coarse_reg_ransac_batch(self, problems, params=None, scratch_limit=0):
+        """mulls_coarse_reg_ransac_batch: many problems per call, each with the result of the matching coarse_reg_ransac call.  problems: a list of
+        (tgt_pts, src_pts) or (tgt_pts, src_pts, tgt_idx, src_idx) or dicts with the keys tgt, src and optionally tgt_idx, src_idx, cap (the clouds are host
+        clouds or device-resident abi.Cloud objects; a host cloud may also be an abi.Cloud with a stride of its own).  One params for the whole batch.
+        scratch_limit: scratch_limit_bytes (0: the library's default).  Returns [(result, inliers), ...] as coarse_reg_ransac does per problem."""
+        keep = []
+
+        def cloud(k):
+            if isinstance(k, abi.Cloud):
+                return k
+            raw = abi.records(k)
+            keep.append(raw)
+            c = abi.Cloud()
+            c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+            return c
+
+        n = len(problems)
+        p = params if params is not None else abi.ransac_params()
+        arr, res, lists = (abi.RansacProblem * max(n, 1))(), (abi.RansacResult * max(n, 1))(), []
+        for b, prob in enumerate(problems):
+            if not isinstance(prob, dict):
+                prob = dict(zip(("tgt", "src", "tgt_idx", "src_idx"), prob))
+            P = arr[b]
+            P.tgt, P.src = cloud(prob["tgt"]), cloud(prob["src"])
+            n_pairs = P.tgt.n
+            if prob.get("tgt_idx") is not None:
+                ti, si = np.ascontiguousarray(prob["tgt_idx"], np.int32), np.ascontiguousarray(prob["src_idx"], np.int32)
+                assert len(ti) == len(si)
+                keep.extend((ti, si))
+                P.tgt_idx, P.src_idx, P.n_corr = ti.ctypes.data, si.ctypes.data, len(ti)
+                if not len(ti):  # (an empty array has no address to speak of: the lists stay set)
+                    P.tgt_idx = P.src_idx = C.addressof(arr)
+                n_pairs = len(ti)
+            cap = prob.get("cap")
+            cap = n_pairs if cap is None else cap
+            inl = np.full(cap + 1, -1, np.int32)  # one slot past cap: checked to be left alone
+            lists.append(inl)
+            P.inlier_cap, P.inliers = cap, (inl.ctypes.data if cap else None)
+        rc = self.lib.mulls_coarse_reg_ransac_batch(self.h, arr, n, C.byref(p), int(scratch_limit), res)
+        if rc != 0:
+            raise MullsError("mulls_coarse_reg_ransac_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        out = []
+        for b in range(n):
+            cap = arr[b].inlier_cap
+            assert lists[b][cap] == -1
+            r = abi.RansacResult.from_buffer_copy(res[b])
+            out.append((r, lists[b][: min(r.n_inliers, cap)].copy()))
+        return out
 
     # --- TEASER coarse registration ----------------------------------------------------------------------------------
     def coarse_reg_teaser(self, tgt_pts, src_pts, params=None, cap=None, tgt_idx=None, src_idx=None):

@@ -6,6 +6,11 @@ after tens of iterations, the device has scored max_iter_num + 1 all the same). 
 
     python tools/gpu_ransac.py                 the table
     python tools/gpu_ransac.py --calls 5       five calls per case and nothing else: the run to put under `rocprofv3 --kernel-trace --stats -- ...`
+    python tools/gpu_ransac.py --batch 1,8,64  mulls_coarse_reg_ransac_batch: per B, one batch call of B problems against B single calls in this process, on
+                                               the demo scans' four key-point pair lists (indexed, noise_bound 1.0, cycled to B problems) and on B synthetic
+                                               sets of 2 840 pairs (40 % inliers with 12 cm of noise, noise_bound 0.3: refinements of several rounds); the
+                                               defaults otherwise (max_iter_num 20000, refinement on); median of 20 after a warm-up call of each
+    python tools/gpu_ransac.py --batch 64 --batch-only --calls 3    the batch calls alone: the run for `rocprofv3 --kernel-trace --stats`
 """
 import ctypes as C
 import os
@@ -43,8 +48,67 @@ def cloud(raw):
     return c
 
 
+def batch_table(sizes, calls, batch_only):
+    ctx = lib.Context(0)
+    L = ctx.lib
+    Z = np.load(os.path.join(ROOT, "tests", "golden", "ncc_demo.npz"))
+    kt, ks = np.ascontiguousarray(Z["kpts_0"]), np.ascontiguousarray(Z["kpts_15"])
+    lists = [np.ascontiguousarray(Z[name + "_pairs"], np.int32) for name in ("recip_0_15", "nn_0_15", "fixed2000_0_15", "fixed300_0_15")]
+    lists = [(np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])) for pr in lists]
+    synth = [planted(200 + k, 2840, 0.4, sigma=0.12) for k in range(max(sizes))]
+    inl = np.zeros((max(sizes), 4096), np.int32)
+    print("mulls_coarse_reg_ransac_batch against B single calls: max_iter_num 20000, refine 1, wall time host clouds in to results out, median of %d" % (calls or 20))
+    for what, bound in (("demo pair lists (indexed)", 1.0), ("synthetic 2840 pairs", 0.3)):
+        P = abi.ransac_params(bound, 8, 20000, 1)
+        for B in sizes:
+            arr, res, single = (abi.RansacProblem * B)(), (abi.RansacResult * B)(), (abi.RansacResult * B)()
+            for b in range(B):
+                if bound == 1.0:
+                    ti, si = lists[b % len(lists)]
+                    arr[b].tgt, arr[b].src, arr[b].tgt_idx, arr[b].src_idx, arr[b].n_corr = cloud(kt), cloud(ks), ti.ctypes.data, si.ctypes.data, len(ti)
+                else:
+                    arr[b].tgt, arr[b].src = cloud(synth[b][0]), cloud(synth[b][1])
+                arr[b].inlier_cap, arr[b].inliers = inl.shape[1], inl[b].ctypes.data
+
+            def batch_call():
+                t0 = time.perf_counter()
+                rc = L.mulls_coarse_reg_ransac_batch(ctx.h, arr, B, C.byref(P), 0, res)
+                dt = time.perf_counter() - t0
+                assert rc == 0, (rc, L.mulls_last_error(ctx.h))
+                return dt
+
+            def single_calls():
+                t0 = time.perf_counter()
+                for b in range(B):
+                    A = arr[b]
+                    ip = C.c_void_p(A.inliers)
+                    if A.tgt_idx:
+                        rc = L.mulls_coarse_reg_ransac_indexed(ctx.h, C.byref(A.tgt), C.byref(A.src), C.c_void_p(A.tgt_idx), C.c_void_p(A.src_idx), A.n_corr, C.byref(P),
+                                                               C.byref(single[b]), ip, A.inlier_cap)
+                    else:
+                        rc = L.mulls_coarse_reg_ransac(ctx.h, C.byref(A.tgt), C.byref(A.src), C.byref(P), C.byref(single[b]), ip, A.inlier_cap)
+                    assert rc == 0, (rc, L.mulls_last_error(ctx.h))
+                return time.perf_counter() - t0
+
+            batch_call()
+            tb = sorted(batch_call() for _ in range(calls or 20))
+            rounds = max(r.refine_iterations for r in res)
+            if batch_only:
+                print("%-26s B %3d  batch %9.3f ms  longest refinement %d rounds" % (what, B, tb[len(tb) // 2] * 1e3, rounds))
+                continue
+            single_calls()
+            ts = sorted(single_calls() for _ in range(calls or 20))
+            assert all(bytes(res[b]) == bytes(single[b]) for b in range(B))  # the same bytes, or the times compare nothing
+            mb, ms = tb[len(tb) // 2], ts[len(ts) // 2]
+            print("%-26s B %3d  batch %9.3f ms (min %.3f, max %.3f)  %3d single calls %9.3f ms (min %.3f, max %.3f)  single / batch %5.2f  longest refinement %d rounds"
+                  % (what, B, mb * 1e3, tb[0] * 1e3, tb[-1] * 1e3, B, ms * 1e3, ts[0] * 1e3, ts[-1] * 1e3, ms / mb, rounds))
+    ctx.close()
+
+
 def main():
     calls = int(sys.argv[sys.argv.index("--calls") + 1]) if "--calls" in sys.argv else 0
+    if "--batch" in sys.argv:
+        return batch_table([int(v) for v in sys.argv[sys.argv.index("--batch") + 1].split(",")], calls, "--batch-only" in sys.argv)
     ctx = lib.Context(0)
     L = ctx.lib
     res = abi.RansacResult()
