@@ -180,7 +180,8 @@ typedef struct mulls_profile
 							   its workgroups ([0..4], ms) and the workgroup count ([5]); = 21: the global-memory tier's leftover queries ([0]) and
 							   its workgroup time ([1], ms) */
 	double icp_search_ms[24]; /* ... MULLS_OPT_DEBUG_STOP = 20: k_cert's k-candidate certificates — points the plain certificate left over, points
-							   given the second chance, points it certified, points searched ([0..3]); 0 otherwise */
+							   given the second chance, points it certified, points searched ([0..3]); [4]: slots the live-point compaction took out of the
+						   later searches' walks (0: nothing was compacted); 0 otherwise */
 	double icp_phase_ms[6]; /* ... MULLS_OPT_DEBUG_STOP = 20: k_nn_lds's phase clocks summed over its class clouds ([0..3], ms) and the class cloud
 							   count ([4]); 0 otherwise, and [5] always */
 	double ms_stage;		/* mulls_icp / mulls_icp_batch: wall time of staging the caller's clouds (host gather into pinned memory + upload), */
@@ -230,7 +231,8 @@ enum mulls_option
 											 source ground / pillar / facade clouds the intersection box is taken from).  mulls_result.nsrc0 / ntgt0 of the
 											 classes left out report 0; every output of the reference's interface is unchanged.  The C++ bridge switches it on. */
 	MULLS_OPT_DEBUG_STOP = 14,			  /* [0] kernel bring-up switches (tools/gpu_time_nn.py; the values: tools/README.md).  30: the setup of a run in its
-											 former shape — k_clone_src + k_crop for every pair, one 19-trip k_tgt_grid workgroup per class cloud */
+											 former shape — k_clone_src + k_crop for every pair, one 19-trip k_tgt_grid workgroup per class cloud.  31: no live-point
+										 compaction after iteration 0's staged search (the searches walk every slot of every class cloud, as they did before it) */
 	MULLS_OPT_DEBUG_TICK = 15,			  /* [0] tests: start a fresh batch's duplicate-table epoch counter here */
 	MULLS_OPT_SPLIT_MIN_PAIRS = 16,		  /* [96]    lock-step loop stepped on the device: batches of MIN .. MAX pairs iterate as two sub-batches on two streams, */
 	MULLS_OPT_SPLIT_MAX_PAIRS = 17,		  /* [2^30]  so that one half's kernels fill the gaps of the other's (MAX < MIN: never; not while profiling: +3 % at */

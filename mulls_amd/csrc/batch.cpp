@@ -697,6 +697,7 @@ int batch_fill(mulls_ctx *ctx, mulls_batch *B, const mulls_pair *pairs, int n, c
 	A(grow(ctx, &B->nn_hint, &B->cap_src[9], 2 * so, nullptr, 8 * SG)); // LDS tier: (hint word, bound) records
 	A(grow(ctx, &B->mq, &B->cap_src[10], 2 * so, nullptr, 9 * SG));
 	A(grow(ctx, &B->nn_cand, &B->cap_src[11], so, &cand_grew, 14 * SG)); // k-candidate certificates: 16-byte candidate records
+	A(grow(ctx, &B->live_mask, &B->cap_live, (so >> 6) + (size_t)n * MULLS_NC + 1u)); // live-point compaction: word (src_off >> 6) + cloud + w (device_types.h: LiveWord)
 	A(grow(ctx, &B->tpos, &B->cap_tgt[0], to));
 	A(grow(ctx, &B->tnrm, &B->cap_tgt[1], to));
 	A(grow(ctx, &B->tsorted, &B->cap_tgt[2], to, nullptr, 10 * SG));

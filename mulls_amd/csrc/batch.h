@@ -91,6 +91,8 @@ struct mulls_batch : BatchDev
 	uint32_t njobs = 0;
 	// device (besides BatchDev's)
 	uint4 *nn_cand = nullptr; // per source point: candidate record of the k-candidate certificates (RunParams::cand)
+	LiveWord *live_mask = nullptr; // live-point compaction: one word per 64 source slots and one more per class cloud (RunParams::live_mask, device_types.h)
+	size_t cap_live = 0;
 	uint32_t tick = 1; // duplicate-table epoch counter of THIS batch's winner table, monotone between resets (take_epochs)
 	size_t cap_outs = 0;
 	size_t cap_big[4] = {};

@@ -78,6 +78,19 @@ struct CloudDesc
 	uint32_t tier;		// search tier of this cloud pair (MULLS_TIER_*), assigned per run by the host (assign_tiers): decides which setup kernels build its target
 						// grid and which search kernel's job table holds it
 	uint32_t grid_slot; // its slot in that tier's cell tables (LDS tier: x RunParams::cell_stride entries; bitmap tier: x RunParams::bm_stride words)
+	// live-point compaction (RunParams::live_mask): the tail of iteration 0's staged search moves a class cloud's live points, in slot order, to the front of its
+	// range.  src_c: the slots the searches walk from then on — the live count at the compaction, src_n before it and for a cloud that is never compacted (the setup
+	// writes both); compacted: 1 once the move has happened (0 in the pristine descriptors every run starts from).  src_n keeps its meaning.
+	uint32_t src_c;
+	uint32_t compacted;
+};
+// One 64-slot word of a compacted class cloud, by ORIGINAL slot: which slots were live at the compaction and how many live slots lie below the word — the live
+// slot s of the cloud sits at src_off + below + popcount(alive & ((1 << (s & 63)) - 1)).  Word w of cloud ci (= pair * MULLS_NC + class) is entry
+// (src_off >> 6) + ci + w of the batch's array: the clouds' ranges are disjoint because their slot ranges are (live_word_base).
+struct LiveWord
+{
+	unsigned long long alive;
+	uint32_t below, pad_;
 };
 // staged layouts of one cloud of n points (load_staged, device_util.h)
 #define MULLS_STAGE_AOS48 0u  // n x 3 float4: the caller's 48-byte PointXYZINormal records (device-resident map clouds, copied device to device)
@@ -187,6 +200,7 @@ struct RunParams
 	int32_t resid_from_iter; // residual weighting applies when iter_num > this (2 for mm_lls_icp, cregistration.hpp:1905-1907; -1 for the 3-DoF variant)
 	uint32_t debug_stop;	// diagnostics only (env MULLS_DEBUG_STOP): 1 = k_nn_lds returns after the transform, 2 = after staging; 30 = the host queues the setup in its
 							// former shape (setup_former_shape, batch.cpp): k_clone_src + k_crop for every pair, one 19-trip k_tgt_grid workgroup per class cloud
+							// 31 = the device-stepped loop does not compact the live source points (live_mask stays null)
 	uint32_t cell_stride;	// entries reserved per cloud in the cell tables (multiple of 4: uint4-aligned), >= grid_maxcells + 1
 	uint32_t grid_maxcells; // cell budget of the target grids built by k_crop (MULLS_MAXCELLS, or what fits in LDS for the LDS tier)
 	float grid_h0;		// LDS tier: preferred cell edge (MULLS_GRID_H0; grows until the cloud's box fits grid_maxcells)
@@ -216,4 +230,9 @@ struct RunParams
 	const float4 *tgt_stage;
 	const uint16_t *tgt_map;
 	unsigned long long *dbg_ticks; // diagnostics (MULLS_OPT_DEBUG_STOP = 20): k_cert's one-pass walk adds its phase times here (10-ns ticks; [6] = workgroups)
+	// Live-point compaction (null: off).  Set by the device-stepped loop when every class cloud's accumulation goes through k_accum_wave, the one accumulation
+	// kernel that maps original slots to compacted records (wave_trip); then the tail of iteration 0's staged search (class_tail_flat) compacts every class cloud
+	// the one-pass walk takes (MULLS_COMPACT_MAX slots) and leaves its LiveWords here.
+	LiveWord *live_mask;
 };
+#define MULLS_COMPACT_MAX (3u * MULLS_CERT_BLOCK) // largest class cloud that is compacted: what every form of the one-pass walk (cert_class_flat) takes

@@ -18,7 +18,8 @@
 // Launch geometry: 256-thread workgroups (4 wave64) unless a kernel says otherwise (k_nn_lds: 1024 lanes per class cloud,
 // k_accum: 1024 / 512 / 256 by trip length, k_step: one wave per pair).  The search / filter / accumulate kernels share one static job table (one job = 512 consecutive source
 // points of one feature class of one pair; the LDS tier's class-level jobs are whole class clouds); dead source points keep
-// their slot and are masked by a flag byte instead of being physically compacted, which makes the job tables iteration-
+// their slot and are masked by a flag byte instead of being physically compacted (but for one move inside a small class cloud's own
+// range at the end of iteration 0's staged search: lds_tier.h, class_tail_flat<COMPACT>), which makes the job tables iteration-
 // invariant and the whole batch advance with a handful of launches per ICP iteration (search (+ rejection chain), accumulate,
 // finish, step, publish; host-stepped loop: push states, ..., finish (+ pull)).
 
@@ -113,6 +114,10 @@ __device__ __forceinline__ float4 tgt_point(const float4 *__restrict__ tgt_stage
 {
 	return tgt_map ? load_staged_pos(tgt_stage, d.tgt_stage, (d.stage_fmt >> 2) & 3u, tgt_map[d.tgt_off + m]) : tpos[d.tgt_off + m];
 }
+
+// first LiveWord of class cloud `cloud` (= pair * MULLS_NC + class) in RunParams::live_mask: one word per 64 slots of a cloud.  Source ranges are laid out in cloud
+// order, so floor(src_off / 64) + cloud leaves every cloud the ceil(src_n / 64) words it needs below the next cloud's first one.
+__device__ __forceinline__ uint32_t live_word_base(const CloudDesc &d, uint32_t cloud) { return (d.src_off >> 6) + cloud; }
 
 __device__ __forceinline__ bool class_called(const RunParams &rp, const CloudDesc &d, int cls)
 {

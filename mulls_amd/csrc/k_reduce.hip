@@ -77,15 +77,30 @@ __device__ __forceinline__ void add_windows(const AccumCtx &A, const double *x, 
 // next slot's records in flight and a fifth wave per SIMD)
 template <typename TS, int NT, int MODE, int METRIC, int T0, int NTW>
 __device__ __forceinline__ void wave_trip(const AccumCtx &A, const double *x, const CloudDesc &d, uint32_t trip0, const float4 *__restrict__ spos, const float4 *__restrict__ mq,
-										   const uint8_t *__restrict__ flag, float *__restrict__ wd, double *__restrict__ out, bool owner)
+										   const uint8_t *__restrict__ flag, float *__restrict__ wd, double *__restrict__ out, bool owner, const LiveWord *__restrict__ live,
+										   uint32_t cloud)
 {
 	const uint32_t lane = threadIdx.x & 63u;
 	const uint32_t src_n = d.src_n, src_off = d.src_off;
 	const uint32_t n_here = min(src_n - trip0, (uint32_t)MULLS_ACC_LANES), iters = (n_here + 63u) >> 6; // (uniform)
-	const uint32_t last = src_off + src_n - 1u;
+	// A compacted class cloud (lds_tier.h: class_tail_flat): the summation order stays the one by ORIGINAL slot — lane j still visits the slots trip0 + j + 64 i in
+	// that order — but a slot's records sit at its compact index, which the cloud's LiveWords give: word (trip0 >> 6) + i for the trip's i-th round.  Lane i fetches
+	// word i once, in front of the walk (a trip has at most sixteen), and every round reads its word out of that lane: no round trip is added to a round.  A slot
+	// that was dead at the compaction requests nothing of its own: it re-reads the records of the next live slot, which a neighbouring lane fetches anyway.
+	const bool compacted = d.compacted != 0u; // (uniform)
+	const uint32_t last = src_off + (compacted ? max(d.src_c, 1u) : src_n) - 1u;
+	const unsigned long long below_me = (1ull << lane) - 1ull;
+	static_assert(MULLS_ACC_LANES / 64 <= 64, "one LiveWord per lane covers a trip");
+	uint32_t lw_lo = 0u, lw_hi = 0u, lw_below = 0u;
+	if (compacted)
+	{
+		const LiveWord w = live[live_word_base(d, cloud) + (trip0 >> 6) + min(lane, iters - 1u)];
+		lw_lo = (uint32_t)w.alive, lw_hi = (uint32_t)(w.alive >> 32), lw_below = w.below;
+	}
 	struct Rec
 	{
-		uint32_t f;
+		uint32_t f, g; // flag; where the slot's records are (its own index, or its compact one)
+		bool live;	   // (compacted cloud) the slot was live at the compaction
 		float4 P, Q;
 		float3 N;
 		float w;
@@ -96,7 +111,17 @@ __device__ __forceinline__ void wave_trip(const AccumCtx &A, const double *x, co
 	const bool need_w = A.residual_pass, writes_w = !A.residual_pass && (METRIC != 2 || !A.faithful); // (uniform)
 	auto load = [&](uint32_t i) {
 		Rec r;
-		const uint32_t g = min(src_off + trip0 + lane + 64u * i, last); // (slots beyond the cloud re-read its last point: no branch between the loads)
+		uint32_t g = src_off + trip0 + lane + 64u * i;
+		r.live = true;
+		if (compacted)
+		{
+			// (i is uniform: the round counter)
+			const unsigned long long alive = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)lw_hi, (int)i) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)lw_lo, (int)i);
+			g = src_off + (uint32_t)__builtin_amdgcn_readlane((int)lw_below, (int)i) + (uint32_t)__popcll(alive & below_me);
+			r.live = ((alive >> lane) & 1ull) != 0ull;
+		}
+		g = min(g, last); // (slots beyond the cloud re-read its last point: no branch between the loads)
+		r.g = g;
 		r.f = flag[g];
 		r.P = spos[g], r.Q = mq[2u * g], r.N = *reinterpret_cast<const float3 *>(mq + 2u * g + 1u);
 		r.w = need_w ? wd[g] : 0.0f;
@@ -124,7 +149,7 @@ __device__ __forceinline__ void wave_trip(const AccumCtx &A, const double *x, co
 		MULLS_PIN_REC(cur);
 #endif
 		const uint32_t s = trip0 + lane + 64u * i;
-		const bool valid = s < src_n && (cur.f & (MULLS_F_ALIVE | MULLS_F_VALID)) == (MULLS_F_ALIVE | MULLS_F_VALID);
+		const bool valid = s < src_n && cur.live && (cur.f & (MULLS_F_ALIVE | MULLS_F_VALID)) == (MULLS_F_ALIVE | MULLS_F_VALID);
 		// A dead or unmatched slot's terms are +0.0: adding them changes a running sum only from -0.0 to +0.0, which k_finish's `0.0 + partial` does anyway (the 512- and
 		// 256-lane forms of k_accum leave the slots beyond their lanes out the same way) — so such a slot is skipped altogether.
 		// The terms in windows: a window's terms are added to their running sums before the next window's are evaluated (the windows share the row vector through
@@ -141,7 +166,7 @@ __device__ __forceinline__ void wave_trip(const AccumCtx &A, const double *x, co
 			const float wpre = A.residual_pass ? 0.0f : corr_weight(A, METRIC, cur.P, cur.Q, N4, wi);
 			add_windows<TS, T0, NTW, MODE, METRIC, T0>(A, x, cur.P, cur.Q, N4, wi, w, acc, A.residual_pass ? nullptr : &wpre);
 			if (owner && writes_w)
-				wd[src_off + s] = w; // pcl::Correspondence::weight (the wave that holds the form's first terms writes it: the weight does not depend on the terms)
+				wd[cur.g] = w; // pcl::Correspondence::weight (the wave that holds the form's first terms writes it: the weight does not depend on the terms)
 		}
 #if MULLS_ACCW_PREFETCH
 		cur = nxt;
@@ -210,6 +235,7 @@ __global__ __launch_bounds__(64 * MULLS_ACCW_WAVES, MULLS_ACCW_OCC) void k_accum
 		cnt[c] = (int)(class_called(rp, pd[c], c) ? pd[c].valid_next : pd[c].n_valid);
 	const AccumCtx A = accum_ctx(rp, job.cls, ps.iter, residual_pass, class_weight(rp, job.cls, residual_pass, cnt));
 	const CloudDesc &d = pd[job.cls];
+	const uint32_t ci = job.pair * MULLS_NC + job.cls;
 	double *out = partial + (size_t)job_idx * MULLS_NTERM;
 	if (d.src_n <= job.start) // (a trip starts inside its cloud; an emptied descriptor must not turn into a wild index)
 	{
@@ -223,34 +249,34 @@ __global__ __launch_bounds__(64 * MULLS_ACCW_WAVES, MULLS_ACCW_OCC) void k_accum
 		if (part) // two sums, or the twelve of the faithful point-to-line system: one wave
 			return;
 		if (!residual_pass)
-			wave_trip<double, 12, 1, 1, 0, 12>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true); // (li_diag: launch_accum keeps other point-to-line sums away)
+			wave_trip<double, 12, 1, 1, 0, 12>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true, rp.live_mask, ci); // (li_diag: launch_accum keeps other point-to-line sums away)
 		else if (A.metric == 0)
-			wave_trip<double, 2, 0, 0, 0, 2>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true);
+			wave_trip<double, 2, 0, 0, 0, 2>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true, rp.live_mask, ci);
 		else if (A.metric == 1)
-			wave_trip<double, 2, 0, 1, 0, 2>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true);
+			wave_trip<double, 2, 0, 1, 0, 2>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true, rp.live_mask, ci);
 		else
-			wave_trip<double, 2, 0, 2, 0, 2>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true);
+			wave_trip<double, 2, 0, 2, 0, 2>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true, rp.live_mask, ci);
 	}
 #if MULLS_ACCW_SPLIT == 2
 	else if (A.metric == 0)
 	{
 		if (part == 0u)
-			wave_trip<float, 27, 0, 0, 0, 14>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true);
+			wave_trip<float, 27, 0, 0, 0, 14>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true, rp.live_mask, ci);
 		else
-			wave_trip<float, 27, 0, 0, 14, 13>(A, ps.x, d, job.start, spos, mq, flag, wd, out, false);
+			wave_trip<float, 27, 0, 0, 14, 13>(A, ps.x, d, job.start, spos, mq, flag, wd, out, false, rp.live_mask, ci);
 	}
 	else
 	{
 		if (part == 0u)
-			wave_trip<float, 27, 0, 2, 0, 14>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true);
+			wave_trip<float, 27, 0, 2, 0, 14>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true, rp.live_mask, ci);
 		else
-			wave_trip<float, 27, 0, 2, 14, 13>(A, ps.x, d, job.start, spos, mq, flag, wd, out, false);
+			wave_trip<float, 27, 0, 2, 14, 13>(A, ps.x, d, job.start, spos, mq, flag, wd, out, false, rp.live_mask, ci);
 	}
 #else
 	else if (A.metric == 0)
-		wave_trip<float, 27, 0, 0, 0, 27>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true);
+		wave_trip<float, 27, 0, 0, 0, 27>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true, rp.live_mask, ci);
 	else
-		wave_trip<float, 27, 0, 2, 0, 27>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true);
+		wave_trip<float, 27, 0, 2, 0, 27>(A, ps.x, d, job.start, spos, mq, flag, wd, out, true, rp.live_mask, ci);
 #endif
 }
 
@@ -877,6 +903,12 @@ __global__ void k_set_corr(uint32_t src_off, const int32_t *__restrict__ cs, con
 // host-callable launch wrappers (the driver is plain C++ and never sees <<< >>>)
 #include "launch.h"
 
+bool accum_takes_waves(const RunParams &rp, const uint32_t split[4], uint32_t wave_min_trips)
+{
+	const uint32_t n_trips = split[3] - split[0];
+	return wave_min_trips && n_trips >= wave_min_trips && rp.faithful && rp.pull_comb;
+}
+
 void launch_accum(hipStream_t st, const BatchDev &b, const RunParams &rp, const uint32_t split[4], bool single, uint32_t wave_min_trips)
 {
 	(void)dev_launch<3>([](DevLaunch &) { // per device (launch.h)
@@ -885,7 +917,7 @@ void launch_accum(hipStream_t st, const BatchDev &b, const RunParams &rp, const 
 	// One wave per trip once the launch has trips enough to fill the chip with waves (k_accum_wave; below that a trip's sixteen slots per lane in sequence are the launch's
 	// latency).  Its point-to-line form is the faithful combined system's (diagonal + right-hand side); other point-to-line sums stay with k_accum.
 	const uint32_t n_trips = split[3] - split[0];
-	if (wave_min_trips && n_trips >= wave_min_trips && rp.faithful && rp.pull_comb)
+	if (accum_takes_waves(rp, split, wave_min_trips))
 	{
 		hipLaunchKernelGGL(k_accum_wave, dim3((n_trips + MULLS_ACCW_WAVES / MULLS_ACCW_SPLIT - 1u) / (MULLS_ACCW_WAVES / MULLS_ACCW_SPLIT)), dim3(64 * MULLS_ACCW_WAVES), 0, st, b.ajobs + split[0], n_trips, b.jobs, b.descs, b.states, rp, b.spos,
 						   b.mq, b.flag, b.wd, b.partial);

@@ -406,8 +406,8 @@ __global__ __launch_bounds__(MULLS_LDS_BLOCK) void k_cert_mixed(uint32_t n_lds, 
 }
 
 __global__ __launch_bounds__(MULLS_LDS_BLOCK) void k_nn_lds(const Job *__restrict__ cjobs, CloudDesc *__restrict__ descs,
-															 const PairState *__restrict__ states, RunParams rp, const float4 *__restrict__ spos,
-															 const float4 *__restrict__ snrm, const GridDesc *__restrict__ grids,
+															 const PairState *__restrict__ states, RunParams rp, float4 *spos,
+															 float4 *snrm, const GridDesc *__restrict__ grids,
 															 const uint32_t *__restrict__ cell_start, const float4 *__restrict__ tsorted,
 															 uint8_t *flag, int32_t *__restrict__ nn_idx, float *__restrict__ nn_d2,
 															 unsigned long long *__restrict__ winner, const float4 *__restrict__ tnrm, int32_t *__restrict__ match,

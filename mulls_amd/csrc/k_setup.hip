@@ -245,7 +245,7 @@ __global__ __launch_bounds__(MULLS_BLOCK) void k_crop(const uint32_t *__restrict
 			d.tgt_n = running;
 		else
 		{
-			d.src_n = running;
+			d.src_n = d.src_c = running; // (src_c: not compacted yet, lds_tier.h)
 			d.alive_cur = running;
 			d.alive_next = 0;
 			d.n_matched = 0;
@@ -421,7 +421,7 @@ __global__ __launch_bounds__(MULLS_SS_LANES, 4) void k_src_setup(const uint32_t 
 	{
 		CloudDesc &d = pd[threadIdx.x];
 		const uint32_t n = cls_base[threadIdx.x + 1] - cls_base[threadIdx.x];
-		d.src_n = n;
+		d.src_n = d.src_c = n; // (src_c: not compacted yet, lds_tier.h)
 		d.alive_cur = n;
 		d.alive_next = 0;
 		d.n_matched = 0;
@@ -534,7 +534,7 @@ __global__ __launch_bounds__(64) void k_crop_big_scan(const Job *__restrict__ cl
 	if (threadIdx.x == 0 && (bc.cls & MULLS_BIG_SRC_SIDE))
 	{
 		CloudDesc &d = descs[bc.pair * MULLS_NC + (bc.cls & 0xffu)];
-		d.src_n = running;
+		d.src_n = d.src_c = running; // (src_c: not compacted yet, lds_tier.h)
 		d.alive_cur = running;
 		d.alive_next = 0;
 		d.n_matched = 0;
@@ -677,7 +677,7 @@ __global__ __launch_bounds__(MULLS_BLOCK) void k_thin(CloudDesc *__restrict__ de
 			d.tgt_n = running;
 		else
 		{
-			d.src_n = running;
+			d.src_n = d.src_c = running; // (src_c: not compacted yet, lds_tier.h)
 			d.alive_cur = running;
 		}
 	}

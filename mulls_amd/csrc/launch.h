@@ -122,6 +122,8 @@ void launch_nn_shoot(hipStream_t st, const BatchDev &b, const RunParams &rp, con
 void launch_filter(hipStream_t st, const BatchDev &b, const RunParams &rp, const Job *jobs, uint32_t njobs, bool big = false);
 // b.ajobs: job indices of the trip starts, grouped by trip length (split[0..3]: see k_reduce.hip)
 void launch_accum(hipStream_t st, const BatchDev &b, const RunParams &rp, const uint32_t split[4], bool single = false, uint32_t wave_min_trips = 0);
+// whether launch_accum sums these trips by one wave each (k_accum_wave) — the accumulation that reads a compacted class cloud (RunParams::live_mask)
+bool accum_takes_waves(const RunParams &rp, const uint32_t split[4], uint32_t wave_min_trips);
 void launch_finish(hipStream_t st, const BatchDev &b, const RunParams &rp, uint32_t pair_base, uint32_t npairs, uint32_t *ticket, volatile uint32_t *host_epoch, uint32_t epoch);
 void launch_push_states(hipStream_t st, const BatchDev &b, uint32_t pair_base, uint32_t npairs);
 // lock-step loop with the O(1) half of the iteration on the device: initial per-pair state and first PairState; k_finish followed by the step (k_step)

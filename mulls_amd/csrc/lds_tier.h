@@ -691,11 +691,21 @@ __device__ __forceinline__ void class_tail(const RunParams &rp, const PairState 
 // tests that need them (k_nn_lds runs one workgroup per CU: each dependent round trip is exposed; the tail took as long as the search,
 // profiles/r03_cert_phases_4096.txt).  Same decisions and outputs as class_tail (losers of the duplicate rule keep their nn_idx in memory: nothing
 // reads it after this).
-template <int BLK, int TRIPS, bool W16>
+//
+// COMPACT (iteration 0 of a run with rp.live_mask, lds_search_class(first)): the live points move, in slot order, to the front of the cloud's range, and the
+// searches of the later iterations walk d.src_c slots instead of d.src_n.  Points that lose the duplicate rule or find no target under the gate vanish for good
+// (cregistration.hpp:1762-1789), a fifth of a class cloud after iteration 0, and a walk requests every record of every slot before it looks at the flag.
+// Nothing depends on a point's slot number but the duplicate rule, which compares them (a stable move keeps their order), and the accumulation's summation
+// order, which k_accum_wave keeps through the LiveWords written here (wave_trip).  What moves: position, direction (x y z), hint, flag; the correspondence (match, record,
+// distance word) is written at the compact index in the first place — in iteration 0 every correspondence is new (the setup left match = -1), so a point without
+// a new record keeps that -1 and a record nobody reads.  nn_idx / nn_d2 stay behind: the next walk rewrites them for every point a search has to see.  The move is
+// in place: every lane has its loads of the cloud back (named by a volatile asm) before a barrier, and nothing of the cloud is stored before that barrier.
+template <int BLK, int TRIPS, bool W16, bool COMPACT = false>
 __device__ __forceinline__ void class_tail_flat(const RunParams &rp, const PairState &ps, const ClassCtx &C, CloudDesc &d, const Job &job, uint32_t q_end,
-												 uint32_t matched_cnt, uint32_t searched, const uint32_t *W, uint32_t *red, const float4 *__restrict__ snrm,
+												 uint32_t matched_cnt, uint32_t searched, const uint32_t *W, uint32_t *red, float4 *snrm,
 												 const float4 *__restrict__ tnrm, uint8_t *flag, const int32_t *__restrict__ nn_idx, const float *__restrict__ nn_d2,
-												 int32_t *__restrict__ match, float *__restrict__ wd, const float4 *__restrict__ tpos, float4 *__restrict__ mq)
+												 int32_t *__restrict__ match, float *__restrict__ wd, const float4 *__restrict__ tpos, float4 *__restrict__ mq,
+												 float4 *spos = nullptr, int2 *hint2 = nullptr)
 {
 	__threadfence_block(); // the searched points' nn_idx / nn_d2 (commit_search, other lanes)
 	__syncthreads();	   // ... and the duplicate table is complete
@@ -703,6 +713,13 @@ __device__ __forceinline__ void class_tail_flat(const RunParams &rp, const PairS
 	int32_t M[TRIPS], PM[TRIPS];
 	float D[TRIPS];
 	float3 N1[TRIPS], T2[TRIPS];
+	// COMPACT: what travels with a live point, and what the decisions below leave for the stores behind the last barrier
+	float4 P4[COMPACT ? TRIPS : 1], Q2[COMPACT ? TRIPS : 1], N2[COMPACT ? TRIPS : 1];
+	int2 H[COMPACT ? TRIPS : 1];
+	uint32_t NF[COMPACT ? TRIPS : 1]; // the new flag bits, and 8: the point has a new record
+#if MULLS_LDS_KCERT
+	uint4 CR[COMPACT ? TRIPS : 1];
+#endif
 	const uint32_t last = d.src_off + (q_end ? q_end - 1u : 0u);
 #pragma unroll
 	for (int k = 0; k < TRIPS; k++)
@@ -711,9 +728,35 @@ __device__ __forceinline__ void class_tail_flat(const RunParams &rp, const PairS
 		FL[k] = flag[gi];
 		M[k] = nn_idx[gi];
 		D[k] = nn_d2[gi];
-		PM[k] = match[gi];
 		N1[k] = *reinterpret_cast<const float3 *>(snrm + gi);
-		T2[k] = *reinterpret_cast<const float3 *>(mq + 2u * gi + 1u);
+		if (COMPACT)
+		{
+			// (iteration 0: the setup left every slot match = -1 and no slot MULLS_F_VALID, so neither the standing match nor its target direction is fetched)
+			PM[k] = -1, T2[k] = make_float3(0.0f, 0.0f, 0.0f);
+			P4[COMPACT ? k : 0] = spos[gi];
+			H[COMPACT ? k : 0] = hint2[gi];
+#if MULLS_LDS_KCERT
+			CR[COMPACT ? k : 0] = C.cand ? C.cand[gi] : make_uint4(0u, 0u, 0u, 0u);
+#endif
+		}
+		else
+		{
+			PM[k] = match[gi];
+			T2[k] = *reinterpret_cast<const float3 *>(mq + 2u * gi + 1u);
+		}
+	}
+	if (COMPACT)
+	{
+		// the move is in place: no lane may still wait for a record of the cloud when the first compacted store is issued (behind the barriers below)
+#pragma unroll
+		for (int k = 0; k < TRIPS; k++)
+		{
+			// (one word of every load, as inputs: an asm that also wrote a vector's member would keep the vector's array in scratch memory)
+			asm volatile("" ::"v"(FL[k]), "v"(M[k]), "v"(D[k]), "v"(N1[k].x), "v"(P4[COMPACT ? k : 0].x), "v"(H[COMPACT ? k : 0].x));
+#if MULLS_LDS_KCERT
+			asm volatile("" ::"v"(CR[COMPACT ? k : 0].x));
+#endif
+		}
 	}
 	for (int off = 32; off > 0; off >>= 1)
 		matched_cnt += __shfl_down(matched_cnt, off);
@@ -730,13 +773,15 @@ __device__ __forceinline__ void class_tail_flat(const RunParams &rp, const PairS
 	for (int k = 0; k < TRIPS; k++)
 	{
 		const uint32_t s = threadIdx.x + (uint32_t)k * BLK, gi = d.src_off + s;
+		if (COMPACT)
+			NF[COMPACT ? k : 0] = 0u;
 		if (s >= q_end || !(FL[k] & MULLS_F_ALIVE))
 			continue;
 		int32_t m = M[k];
 		// first source (lowest index) matched to a target keeps it (cregistration.hpp:1762-1789); the others become unmatched
 		if (C.dedup && m >= 0 && !dedup_holds<W16>(W, (uint32_t)m, s))
 			m = -1;
-		bool alive = true, valid;
+		bool alive = true, valid, newrec = false;
 		float3 n2 = T2[k]; // the standing correspondence's target direction
 		if (any_match)
 		{
@@ -752,14 +797,20 @@ __device__ __forceinline__ void class_tail_flat(const RunParams &rp, const PairS
 				valid = strict ? dist < max_sqr : !(dist > max_sqr); // CorrespondenceRejectorDistance (see mulls_params.rejector_strict)
 				if (valid)
 				{
-					wd[gi] = dist; // pcl::Correspondence::distance (shares storage with ::weight)
+					if (!COMPACT)
+						wd[gi] = dist; // pcl::Correspondence::distance (shares storage with ::weight)
 					if (PM[k] != m)
 					{
-						match[gi] = m;
 						float4 q2, n4;
 						tgt_record(rp.tgt_stage, rp.tgt_map, d, (uint32_t)m, tpos, tnrm, q2, n4);
-						mq[2u * gi] = q2;
-						mq[2u * gi + 1u] = n4;
+						if (COMPACT)
+							Q2[COMPACT ? k : 0] = q2, N2[COMPACT ? k : 0] = n4, newrec = true;
+						else
+						{
+							match[gi] = m;
+							mq[2u * gi] = q2;
+							mq[2u * gi + 1u] = n4;
+						}
 						n2 = make_float3(n4.x, n4.y, n4.z);
 					}
 				}
@@ -780,10 +831,28 @@ __device__ __forceinline__ void class_tail_flat(const RunParams &rp, const PairS
 				valid = false;
 		}
 		const uint32_t nf = (alive ? MULLS_F_ALIVE : 0u) | (valid ? MULLS_F_VALID : 0u);
-		if (nf != FL[k])
+		if (COMPACT)
+		{
+			NF[COMPACT ? k : 0] = nf | (newrec ? 8u : 0u);
+			M[k] = newrec ? m : PM[k]; // the correspondence on record: a new one, or the one that was (iteration 0: the setup's -1)
+		}
+		else if (nf != FL[k])
 			flag[gi] = (uint8_t)nf;
 		n_alive += alive ? 1u : 0u;
 		n_valid += valid ? 1u : 0u;
+	}
+	// COMPACT: live slots per 64-slot word, in slot order (word k * BLK / 64 + wave is this wave's ballot of trip k) — next to the counters, behind the same barrier
+	uint32_t *words = red + 3 * (BLK / 64);
+	unsigned long long bal[COMPACT ? TRIPS : 1];
+	if (COMPACT)
+	{
+#pragma unroll
+		for (int k = 0; k < TRIPS; k++)
+		{
+			bal[COMPACT ? k : 0] = __ballot((NF[COMPACT ? k : 0] & MULLS_F_ALIVE) != 0u);
+			if ((threadIdx.x & 63) == 0)
+				words[k * (BLK / 64) + (threadIdx.x >> 6)] = (uint32_t)__popcll(bal[COMPACT ? k : 0]);
+		}
 	}
 	for (int off = 32; off > 0; off >>= 1)
 	{
@@ -796,6 +865,68 @@ __device__ __forceinline__ void class_tail_flat(const RunParams &rp, const PairS
 		red[2 * (BLK / 64) + (threadIdx.x >> 6)] = n_valid;
 	}
 	__syncthreads();
+	if (COMPACT)
+	{
+		const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, src_off = d.src_off;
+		const unsigned long long below_me = (1ull << lane) - 1ull;
+		LiveWord *lw = rp.live_mask + live_word_base(d, job.pair * MULLS_NC + job.cls);
+		const uint32_t n_words = (q_end + 63u) >> 6;
+		uint32_t run = 0; // live slots below the trip's first word, then (after the last trip) of the whole cloud
+#pragma unroll
+		for (int k = 0; k < TRIPS; k++)
+		{
+			uint32_t below = run;
+			for (int w = 0; w < BLK / 64; w++)
+			{
+				const uint32_t c = words[k * (BLK / 64) + w];
+				below += (uint32_t)w < wave ? c : 0u;
+				run += c;
+			}
+			const uint32_t word = (uint32_t)k * (BLK / 64) + wave;
+			if (lane == 0u && word < n_words)
+			{
+				LiveWord v;
+				v.alive = bal[COMPACT ? k : 0], v.below = below, v.pad_ = 0u;
+				lw[word] = v;
+			}
+			const uint32_t nf = NF[COMPACT ? k : 0];
+			if (nf & MULLS_F_ALIVE)
+			{
+				const uint32_t ci = src_off + below + (uint32_t)__popcll(bal[COMPACT ? k : 0] & below_me);
+				spos[ci] = P4[COMPACT ? k : 0];
+				*reinterpret_cast<float3 *>(snrm + ci) = N1[k]; // (the fourth word, the curvature, stays where it is: nothing reads it after the setup)
+				hint2[ci] = H[COMPACT ? k : 0];
+#if MULLS_LDS_KCERT
+				if (C.cand)
+					C.cand[ci] = CR[COMPACT ? k : 0];
+#endif
+				flag[ci] = (uint8_t)(nf & (MULLS_F_ALIVE | MULLS_F_VALID));
+				match[ci] = M[k];
+				if (nf & MULLS_F_VALID)
+					wd[ci] = D[k];
+				if (nf & 8u)
+				{
+					mq[2u * ci] = Q2[COMPACT ? k : 0];
+					mq[2u * ci + 1u] = N2[COMPACT ? k : 0];
+				}
+			}
+		}
+		// the slots behind the live points are dead for whoever still walks d.src_n of them
+#pragma unroll
+		for (int k = 0; k < TRIPS; k++)
+		{
+			const uint32_t s = threadIdx.x + (uint32_t)k * BLK;
+			if (s >= run && s < q_end)
+				flag[src_off + s] = 0u;
+		}
+		if (threadIdx.x == 0)
+		{
+			d.src_c = run;
+			d.compacted = 1u;
+			if (rp.dbg_ticks)
+				atomicAdd(&rp.dbg_ticks[5], (unsigned long long)(q_end - run)); // diagnostics: slots taken out of the later walks
+		}
+	}
 	if (threadIdx.x == 0)
 	{
 		uint32_t ta = 0, tv = 0;
@@ -1021,7 +1152,7 @@ __device__ __forceinline__ bool cert_class(CertLds<SMALL> &CL, const RunParams &
 	uint32_t &ucount = CL.ucount;
 	int2 *__restrict__ hint2 = reinterpret_cast<int2 *>(nn_hint); // per source point: (hint word, bound on every OTHER target's distance)
 
-	const uint32_t src_n = d.src_n, tgt_n = d.tgt_n;
+	const uint32_t src_n = d.src_c, tgt_n = d.tgt_n; // (src_c: the slots that hold the cloud's points — d.src_n, or the live count at the compaction)
 	const bool called = class_called(rp, d, job.cls);
 	const ClassCtx C = class_ctx(rp, ps, g, job.cls, d.alive_cur, called);
 	const bool have_prev = ps.iter > 0; // hint records of this run exist from its second iteration on
@@ -1182,7 +1313,7 @@ __device__ __forceinline__ bool cert_class_flat(CertLds<SMALL> &CL, const RunPar
 	uint32_t *us = CL.us, *red = CL.red;
 	uint32_t &ucount = CL.ucount;
 	int2 *__restrict__ hint2 = reinterpret_cast<int2 *>(nn_hint);
-	const uint32_t src_n = d.src_n, tgt_n = d.tgt_n;
+	const uint32_t src_n = d.src_c, tgt_n = d.tgt_n; // (src_c: the slots that hold the cloud's points — d.src_n, or the live count at the compaction)
 	const ClassCtx C = class_ctx(rp, ps, g, job.cls, d.alive_cur, true);
 	const bool have_prev = ps.iter > 0; // hint records of this run exist from its second iteration on
 	const bool normal_check = job.cls != 5; // vertex correspondences skip the direction check (:1292)
@@ -1556,8 +1687,8 @@ __device__ __forceinline__ LdsLayout lds_layout(unsigned char *lds_raw, uint32_t
 // cert_class left uncertified (nn_idx == MULLS_NEEDS_SEARCH) in equal chunks, then the class's tail (duplicate rule, rejection
 // chain, counters).  Every lane of the workgroup must call it; the caller puts a barrier between two calls.
 __device__ __forceinline__ void lds_search_class(const RunParams &rp, const PairState &ps, const Job &job, CloudDesc &d, const GridDesc &g,
-												  const LdsLayout &Y, unsigned char *lds_raw, const float4 *__restrict__ spos,
-												  const float4 *__restrict__ snrm, const uint32_t *__restrict__ cell_start,
+												  const LdsLayout &Y, unsigned char *lds_raw, float4 *spos,
+												  float4 *snrm, const uint32_t *__restrict__ cell_start,
 												  const float4 *__restrict__ tsorted, uint8_t *flag, int32_t *__restrict__ nn_idx, float *__restrict__ nn_d2,
 												  unsigned long long *__restrict__ winner, const float4 *__restrict__ tnrm, int32_t *__restrict__ match,
 												  float *__restrict__ wd, const float4 *__restrict__ tpos, int32_t *__restrict__ nn_hint, float4 *__restrict__ mq,
@@ -1582,7 +1713,7 @@ __device__ __forceinline__ void lds_search_class(const RunParams &rp, const Pair
 	uint16_t *IDX = Y.IDX, *CS = Y.CS;
 	uint32_t *W = Y.W;
 	int2 *__restrict__ hint2 = reinterpret_cast<int2 *>(nn_hint);
-	const uint32_t src_n = d.src_n, tgt_n = d.tgt_n;
+	const uint32_t src_n = d.src_c, tgt_n = d.tgt_n; // (src_c: the slots that hold the cloud's points — d.src_n, or the live count at the compaction)
 	const ClassCtx C = class_ctx(rp, ps, g, job.cls, d.alive_cur, true);
 	const uint32_t q_end = min(src_n, job.start + (job.count ? job.count : (uint32_t)MULLS_SRC_PER_BLOCK));
 	// chunks of equal size (1200 points: 2 x 600, not 1024 + 176: the last chunk would leave most sub-groups idle)
@@ -1753,7 +1884,14 @@ __device__ __forceinline__ void lds_search_class(const RunParams &rp, const Pair
 	HEAVY_TICK(10)
 	uint32_t *red = reinterpret_cast<uint32_t *>(lds_raw); // the query block is free once the tail's first barrier has passed
 	if (rp.lds_dedup && rp.debug_stop != 9u && job.start == 0u && q_end <= 2u * MULLS_LDS_BLOCK)
-		class_tail_flat<MULLS_LDS_BLOCK, 2, false>(rp, ps, C, d, job, q_end, matched_cnt, searched, W, red, snrm, tnrm, flag, nn_idx, nn_d2, match, wd, tpos, mq);
+	{
+		// iteration 0 of a run that compacts (rp.live_mask): a class cloud the one-pass walk will take from here on — a class-level job of at most
+		// MULLS_COMPACT_MAX slots (cert_job's test, in every form of the light pass) — leaves this tail with its live points in front
+		if (first && rp.live_mask != nullptr && job.count >= d.src_n && d.src_n <= MULLS_COMPACT_MAX)
+			class_tail_flat<MULLS_LDS_BLOCK, 2, false, true>(rp, ps, C, d, job, q_end, matched_cnt, searched, W, red, snrm, tnrm, flag, nn_idx, nn_d2, match, wd, tpos, mq, spos, hint2);
+		else
+			class_tail_flat<MULLS_LDS_BLOCK, 2, false>(rp, ps, C, d, job, q_end, matched_cnt, searched, W, red, snrm, tnrm, flag, nn_idx, nn_d2, match, wd, tpos, mq);
+	}
 	else
 		class_tail<MULLS_LDS_BLOCK>(rp, ps, C, d, job, q_end, matched_cnt, searched, W, red, snrm, tnrm, flag, nn_idx, nn_d2, match, wd, winner, tpos, mq);
 	HEAVY_TICK(11)

@@ -127,6 +127,18 @@ int run_setup(Run &R)
 		rp.dbg_ticks = B->dbg;
 	}
 
+	// Live-point compaction (lds_tier.h: class_tail_flat): the tail of iteration 0's staged search moves every small class cloud's live points to the front of its
+	// range, and the searches walk only those from then on.  The accumulation keeps the library's summation order by ORIGINAL slot, which only k_accum_wave knows how
+	// to map (wave_trip): the run compacts when every accumulation launch of every sub-batch is that kernel's.  MULLS_OPT_DEBUG_STOP = 31: never (the former shape).
+	if (dstep && rp.lds_dedup != 0u && (tier == 2 || tier == 3) && rp.debug_stop != 31u)
+	{
+		bool waves = true;
+		for (int k = 0; k < B->nsub; k++)
+			waves = waves && accum_takes_waves(rp, B->ajob_split[k], (uint32_t)ctx->opt[MULLS_OPT_ACCUM_WAVE_MIN_TRIPS]);
+		if (waves)
+			rp.live_mask = B->live_mask;
+	}
+
 	// setup: clone + initial guess + intersection filter (cregistration.hpp:1180-1188), then the target grids
 	evt.begin(&ctx->prof.ms_setup);
 	queue_clone_crop(st, B, rp);
@@ -312,6 +324,7 @@ int results_from_device(Run &R)
 		// the k-candidate certificates of the one-pass walk, in the (otherwise unused) per-iteration slots: points the plain certificate left over, points
 		// that got the second chance, points it certified, points searched
 		ctx->prof.icp_search_ms[0] += (double)t[13], ctx->prof.icp_search_ms[1] += (double)t[14], ctx->prof.icp_search_ms[2] += (double)t[15], ctx->prof.icp_search_ms[3] += (double)t[7];
+		ctx->prof.icp_search_ms[4] += (double)t[5]; // slots the live-point compaction took out of the searches' walks (0: no class cloud was compacted)
 		for (int k = 0; k < 4; k++) // ... and the heavy pass's (k_nn_lds), in the phase slots ([4] = class clouds)
 			ctx->prof.icp_phase_ms[k] += (double)t[8 + k] * 1e-5;
 		ctx->prof.icp_phase_ms[4] += (double)t[12];
