@@ -11,6 +11,7 @@
 
 #include "classify_launch.h"
 #include "ground_launch.h"
+#include "subbatch.h"
 
 namespace mulls_ex
 {
@@ -143,8 +144,6 @@ inline Layout carve(unsigned char *base, uint32_t n, uint32_t K, uint32_t n_in)
 #define MULLS_EXB_HEAD_BYTES 4096u	// the round counters and other words the scans of a sub-batch share
 #define MULLS_EXB_MAX_SCANS 4096u	// scans of one sub-batch: a grid axis
 
-inline uint64_t up256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
-
 // how many points of a non-ground cloud of n_in the classification works on (random_downsample_pcl(cloud_in, unground_down_fixed_num), classify.cpp)
 inline uint32_t classify_work_points(uint32_t n_in, bool fixed_num, int unground_down_fixed_num)
 {
@@ -170,21 +169,8 @@ inline ScanCost extract_batch_scan_cost(uint32_t n, bool prefilter, int normal_m
 	return c;
 }
 
-// consecutive cuts: cuts[k] .. cuts[k + 1] is sub-batch k; a sub-batch takes scans while their bytes (and the head) stay at or below the limit, and one at
-// least (and MULLS_EXB_MAX_SCANS at most)
-inline void extract_batch_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts)
-{
-	cuts->assign(1, 0u);
-	uint64_t held = MULLS_EXB_HEAD_BYTES;
-	for (uint32_t b = 0; b < count; b++)
-	{
-		if (b > cuts->back() && (held + bytes[b] > limit || b - cuts->back() >= MULLS_EXB_MAX_SCANS))
-			cuts->push_back(b), held = MULLS_EXB_HEAD_BYTES;
-		held += bytes[b];
-	}
-	if (count)
-		cuts->push_back(count);
-}
+// the cut rule of subbatch.h: every sub-batch starts from the head
+inline void extract_batch_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts) { sub_batch_cuts(bytes, count, limit, MULLS_EXB_MAX_SCANS, cuts, MULLS_EXB_HEAD_BYTES); }
 
 struct ScanRegion
 {

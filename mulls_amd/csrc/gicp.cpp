@@ -8,6 +8,7 @@
 #include "ctx.h"
 #include "gicp_launch.h"
 #include "ndt_host.h"
+#include "subbatch.h"
 
 // a context's scratch of this entry point: one device arena, one pinned host buffer; grow-only
 struct mulls_gicp_scratch
@@ -30,8 +31,6 @@ void mulls_gicp_release(mulls_ctx *ctx)
 namespace
 {
 constexpr uint32_t MAX_SUB_BATCH = 4096u; // problems of one sub-batch (three tables each in one grid dimension of the per-point launches)
-
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 struct Plan
 {
@@ -293,18 +292,14 @@ int gicp_run(mulls_ctx *ctx, const mulls_gicp_problem *problems, uint32_t n_prob
 		ctx->gicp = new mulls_gicp_scratch();
 	const size_t limit = params->scratch_limit_bytes ? (size_t)params->scratch_limit_bytes : (size_t)MULLS_GICP_BATCH_DEFAULT_SCRATCH_BYTES;
 	std::vector<mulls_gicp_result> out(n_problems); // (results are written only when the whole call succeeds)
-	std::vector<uint32_t> work(n_problems);
+	std::vector<uint32_t> work(n_problems), cuts;
+	std::vector<uint64_t> bytes(n_problems);
 	for (uint32_t b = 0; b < n_problems; b++)
-		work[b] = b;
-	for (size_t first = 0; first < work.size();)
-	{
-		size_t count = 1, bytes = plans[work[first]].bytes;
-		while (first + count < work.size() && count < MAX_SUB_BATCH && bytes + plans[work[first + count]].bytes <= limit)
-			bytes += plans[work[first + count++]].bytes;
-		if (int rc = run_sub_batch(ctx, problems, plans, work.data() + first, (uint32_t)count, *params, opt, out.data(), who, single))
+		work[b] = b, bytes[b] = plans[b].bytes;
+	sub_batch_cuts(bytes.data(), n_problems, limit, MAX_SUB_BATCH, &cuts);
+	for (size_t c = 0; c + 1 < cuts.size(); c++)
+		if (int rc = run_sub_batch(ctx, problems, plans, work.data() + cuts[c], cuts[c + 1] - cuts[c], *params, opt, out.data(), who, single))
 			return rc;
-		first += count;
-	}
 	std::memcpy(results, out.data(), sizeof(mulls_gicp_result) * (size_t)n_problems);
 	return MULLS_OK;
 }

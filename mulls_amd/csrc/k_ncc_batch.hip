@@ -1,6 +1,6 @@
-// k_ncc_batch.hip — the kernels of mulls_ncc_correspond_batch: the steps of k_ncc.hip over the problems of one sub-batch per launch, driven by the records
-// of ncc_batch.h (a problem's sizes, K, column chunks, first workgroups and the offsets of its arrays in the arena).  The arithmetic is the text the
-// single call compiles (ncc_device.h); a kernel here only finds which problem, row block and column range its workgroup works on.
+// k_ncc_batch.hip — the kernels of mulls_ncc_correspond_batch and, as a batch of one, of mulls_ncc_correspond: every step over the problems of one
+// sub-batch per launch, driven by the records of ncc_batch.h (a problem's sizes, K, column chunks, first workgroups and the offsets of its arrays in the
+// arena).  The arithmetic is in ncc_device.h; a kernel here only finds which problem, row block and column range its workgroup works on.
 //   single-workgroup steps (intensity range, pick, reciprocal compaction): blockIdx.x is the problem.
 //   flat grids (descriptors; the table passes): a workgroup is one (problem, block of 256 key points) or one (problem, 256-row block, column chunk) and
 //   never spans two problems, so every lane of a wave reads the same column descriptor and ncc_sweep_at's loads stay wave-uniform scalar loads.  The

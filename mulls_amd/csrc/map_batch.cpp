@@ -19,6 +19,7 @@
 
 #include "batch.h"
 #include "map_internal.h"
+#include "subbatch.h"
 
 using namespace mulls_mapi;
 
@@ -67,8 +68,6 @@ namespace
 			return MULLS_E_HIP;                                                          \
 		}                                                                                \
 	} while (0)
-
-inline size_t up256(size_t b) { return (b + 255u) & ~(size_t)255; }
 
 struct Item
 {

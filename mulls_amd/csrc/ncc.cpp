@@ -1,8 +1,8 @@
 // ncc.cpp — mulls_ncc_correspond: CRegistration<PointT>::find_feature_correspondence_ncc (cregistration.hpp:409-601), the correspondence stage of the
-// reference's global (coarse) registration, on the device (k_ncc.hip).  Host side: argument checks, staging of host clouds (the five live floats per key
-// point), the launch sequence, one download, and — fixed-number mode — the ordering of the at most 65 536 selected entries and upstream's serial walk.
-// mulls_ncc_correspond_batch runs the same steps for many problems: the device steps once per sub-batch (ncc_batch.h plans it, k_ncc_batch.hip runs it),
-// the ordering and the walk per problem.
+// reference's global (coarse) registration, on the device, and mulls_ncc_correspond_batch, the same for many problems per call.  Host side: argument
+// checks, staging of host clouds (the five live floats per key point), the launch sequence, one download, and — fixed-number mode — the ordering of the
+// at most 65 536 selected entries and upstream's serial walk.  The device steps run once per sub-batch (ncc_batch.h plans it, k_ncc_batch.hip runs it),
+// the ordering and the walk per problem.  The single call is a batch of one.
 #include <cfloat>
 
 #include "ctx.h"
@@ -29,8 +29,6 @@ void mulls_ncc_release(mulls_ctx *ctx)
 
 namespace
 {
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
-
 // device-resident cloud (the library's own block / map memory, or any device allocation of the caller's) or host memory — as mulls_motion_compensate tells them apart
 bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
 {
@@ -54,7 +52,7 @@ void pack_live(const mulls_cloud &c, float *out)
 	}
 }
 
-// the nearest-neighbour modes' download (k_ncc_recip's out) -> the caller's lists; returns the full count
+// the nearest-neighbour modes' download (k_nb_recip's out) -> the caller's lists; returns the full count
 uint32_t finish_pairs(const uint32_t *h, uint32_t n_t, int32_t *tgt_idx, int32_t *src_idx, uint32_t cap)
 {
 	const uint32_t n = std::min(h[0], n_t), w = std::min(n, cap);
@@ -92,14 +90,66 @@ uint32_t finish_fixed(unsigned long long *keys, uint32_t K, uint32_t n_t, uint32
 	return n;
 }
 
-// ---- mulls_ncc_correspond_batch
-const char *const BATCH = "mulls_ncc_correspond_batch";
+// ---- both entry points: the single call is a batch of one
+const char *const SINGLE = "mulls_ncc_correspond", *const BATCH = "mulls_ncc_correspond_batch";
+
+// a refusal's message: `<entry point>: [problem <b>: ]<why>`
+struct Refusal
+{
+	mulls_ctx *ctx;
+	const char *who;
+	int64_t problem; // -1: the single call
+
+	int operator()(int code, const char *why) const
+	{
+		ctx->err = std::string(who) + (problem >= 0 ? ": problem " + std::to_string(problem) : std::string()) + ": " + why;
+		return code;
+	}
+};
 
 struct BatchProblem // a problem that reaches the device
 {
 	uint32_t index, K;
 	bool t_dev, s_dev;
 };
+
+// A problem as it was handed in: the refusals, in the order the single call has always had (it never named the first two, and still does not), and the
+// reference's answers without a table.  *ret: 0 ("Too few key points"), 1 (fixed-number mode with corr_num <= 0: `true` without a pair), or -1 for a
+// problem that goes to the device, with K and the two residences in *A.  The device is selected ahead of the first residence query of a call.
+int check_problem(const Refusal &refuse, const mulls_ncc_problem &P, const mulls_ncc_params &params, bool *device_set, BatchProblem *A, int32_t *ret)
+{
+	mulls_ctx *ctx = refuse.ctx;
+	const bool batch = refuse.problem >= 0;
+	const mulls_cloud &T = P.tgt, &S = P.src;
+	if ((P.cap && (!P.tgt_idx || !P.src_idx)) || (T.n && !T.pts) || (S.n && !S.pts))
+		return batch ? refuse(MULLS_E_INVALID, "a NULL cloud or index buffer") : MULLS_E_INVALID;
+	if (T.n > (uint32_t)INT32_MAX || S.n > (uint32_t)INT32_MAX) // upstream's sizes are ints
+		return batch ? refuse(MULLS_E_UNSUPPORTED, "more than 2^31 - 1 key points") : MULLS_E_UNSUPPORTED;
+	*ret = 0;
+	if (T.n < 10u || S.n < 10u) // "Too few key points" (:421-425)
+		return MULLS_OK;
+	A->K = 0;
+	if (params.fixed_num_corr)
+	{
+		if ((uint64_t)T.n * S.n > (uint64_t)INT32_MAX || params.corr_num > (int32_t)MULLS_NCC_MAX_CORR)
+			return refuse(MULLS_E_UNSUPPORTED, "fixed-number mode takes at most 2^31 - 1 table entries and corr_num <= 65536");
+		*ret = 1;
+		if (params.corr_num <= 0)
+			return MULLS_OK;
+		A->K = (uint32_t)std::min<uint64_t>((uint64_t)params.corr_num, (uint64_t)T.n * S.n); // :565
+	}
+	if (!*device_set)
+	{
+		HIPCHK(ctx, hipSetDevice(ctx->device));
+		*device_set = true;
+	}
+	A->t_dev = cloud_on_device(ctx, T), A->s_dev = cloud_on_device(ctx, S);
+	if ((A->t_dev && T.stride != MULLS_POINT_BYTES) || (A->s_dev && S.stride != MULLS_POINT_BYTES) || (!A->t_dev && (T.stride < 36u || T.stride % 4u)) ||
+		(!A->s_dev && (S.stride < 36u || S.stride % 4u)))
+		return refuse(MULLS_E_INVALID, "stride (device clouds: 48; host clouds: a multiple of 4, at least 36)");
+	*ret = -1;
+	return MULLS_OK;
+}
 
 void reset_results(mulls_ncc_result *results, uint32_t n)
 {
@@ -175,8 +225,9 @@ int ncc_sub_batch(mulls_ctx *ctx, const mulls_ncc_problem *problems, const Batch
 	return MULLS_OK;
 }
 
-int ncc_batch_run(mulls_ctx *ctx, const mulls_ncc_problem *problems, uint32_t n_problems, const mulls_ncc_params *params, uint64_t limit,
-				  mulls_ncc_result *results)
+// who: SINGLE (one problem, named by no number) or BATCH
+int ncc_run(mulls_ctx *ctx, const char *who, const mulls_ncc_problem *problems, uint32_t n_problems, const mulls_ncc_params *params, uint64_t limit,
+			mulls_ncc_result *results)
 {
 	if (!ctx || (n_problems && (!problems || !results)))
 		return MULLS_E_INVALID;
@@ -184,52 +235,23 @@ int ncc_batch_run(mulls_ctx *ctx, const mulls_ncc_problem *problems, uint32_t n_
 	if (!n_problems)
 		return MULLS_OK;
 	if (!params)
-	{
-		ctx->err = std::string(BATCH) + ": params is NULL";
-		return MULLS_E_INVALID;
-	}
+		return Refusal{ctx, who, -1}(MULLS_E_INVALID, "params is NULL");
 	const bool fixed = params->fixed_num_corr != 0;
 	bool device_set = false;
-	// every problem is checked before any device work: the single call's refusals, in its order, the first one found named
+	// every problem is checked before any device work: the first refusal found ends the call, every result at 0
 	std::vector<BatchProblem> act;
-	std::vector<uint32_t> early_true; // fixed-number mode with corr_num <= 0: the reference's `true` without a pair
+	std::vector<uint32_t> early_true;
 	for (uint32_t b = 0; b < n_problems; b++)
 	{
-		const mulls_ncc_problem &P = problems[b];
-		auto refuse = [&](int code, const char *why) {
-			ctx->err = std::string(BATCH) + ": problem " + std::to_string(b) + ": " + why;
-			return code;
-		};
-		const mulls_cloud &T = P.tgt, &S = P.src;
-		if ((P.cap && (!P.tgt_idx || !P.src_idx)) || (T.n && !T.pts) || (S.n && !S.pts))
-			return refuse(MULLS_E_INVALID, "a NULL cloud or index buffer");
-		if (T.n > (uint32_t)INT32_MAX || S.n > (uint32_t)INT32_MAX)
-			return refuse(MULLS_E_UNSUPPORTED, "more than 2^31 - 1 key points");
-		if (T.n < 10u || S.n < 10u) // "Too few key points" (:421-425): 0
-			continue;
 		BatchProblem A;
-		A.index = b, A.K = 0;
-		if (fixed)
-		{
-			if ((uint64_t)T.n * S.n > (uint64_t)INT32_MAX || params->corr_num > (int32_t)MULLS_NCC_MAX_CORR)
-				return refuse(MULLS_E_UNSUPPORTED, "fixed-number mode takes at most 2^31 - 1 table entries and corr_num <= 65536");
-			if (params->corr_num <= 0)
-			{
-				early_true.push_back(b);
-				continue;
-			}
-			A.K = (uint32_t)std::min<uint64_t>((uint64_t)params->corr_num, (uint64_t)T.n * S.n); // :565
-		}
-		if (!device_set)
-		{
-			HIPCHK(ctx, hipSetDevice(ctx->device));
-			device_set = true;
-		}
-		A.t_dev = cloud_on_device(ctx, T), A.s_dev = cloud_on_device(ctx, S);
-		if ((A.t_dev && T.stride != MULLS_POINT_BYTES) || (A.s_dev && S.stride != MULLS_POINT_BYTES) || (!A.t_dev && (T.stride < 36u || T.stride % 4u)) ||
-			(!A.s_dev && (S.stride < 36u || S.stride % 4u)))
-			return refuse(MULLS_E_INVALID, "stride (device clouds: 48; host clouds: a multiple of 4, at least 36)");
-		act.push_back(A);
+		int32_t ret;
+		if (int rc = check_problem(Refusal{ctx, who, who == SINGLE ? -1 : (int64_t)b}, problems[b], *params, &device_set, &A, &ret))
+			return rc;
+		A.index = b;
+		if (ret < 0)
+			act.push_back(A);
+		else if (ret)
+			early_true.push_back(b);
 	}
 	for (uint32_t b : early_true)
 		results[b].ret = 1;
@@ -277,101 +299,14 @@ extern "C"
 		if (!ctx || !tgt_kpts || !src_kpts || !params || !n_corr || (cap && (!tgt_idx || !src_idx)))
 			return MULLS_E_INVALID;
 		*n_corr = 0;
-		const mulls_cloud T = *tgt_kpts, S = *src_kpts;
-		if ((T.n && !T.pts) || (S.n && !S.pts))
-			return MULLS_E_INVALID;
-		if (T.n > (uint32_t)INT32_MAX || S.n > (uint32_t)INT32_MAX) // upstream's sizes are ints
-			return MULLS_E_UNSUPPORTED;
-		if (T.n < 10u || S.n < 10u) // "Too few key points" (:421-425)
-			return 0;
-		const bool fixed = params->fixed_num_corr != 0;
-		uint32_t K = 0;
-		if (fixed)
-		{
-			if ((uint64_t)T.n * S.n > (uint64_t)INT32_MAX || params->corr_num > (int32_t)MULLS_NCC_MAX_CORR)
-			{
-				ctx->err = "mulls_ncc_correspond: fixed-number mode takes at most 2^31 - 1 table entries and corr_num <= 65536";
-				return MULLS_E_UNSUPPORTED;
-			}
-			if (params->corr_num <= 0)
-				return 1;
-			K = (uint32_t)std::min<uint64_t>((uint64_t)params->corr_num, (uint64_t)T.n * S.n); // :565
-		}
-		HIPCHK(ctx, hipSetDevice(ctx->device));
-		const bool t_dev = cloud_on_device(ctx, T), s_dev = cloud_on_device(ctx, S);
-		if ((t_dev && T.stride != MULLS_POINT_BYTES) || (s_dev && S.stride != MULLS_POINT_BYTES) || (!t_dev && (T.stride < 36u || T.stride % 4u)) ||
-			(!s_dev && (S.stride < 36u || S.stride % 4u)))
-		{
-			ctx->err = "mulls_ncc_correspond: stride (device clouds: 48; host clouds: a multiple of 4, at least 36)";
-			return MULLS_E_INVALID;
-		}
-		if (!ctx->ncc)
-			ctx->ncc = new mulls_ncc_scratch();
-		mulls_ncc_scratch &sc = *ctx->ncc;
-
-		// device arena
-		size_t off = 0;
-		auto take = [&](size_t bytes) {
-			const size_t at = off;
-			off += up256(bytes);
-			return at;
-		};
-		const size_t live = MULLS_NCC_LIVE * sizeof(float);
-		const size_t up_bytes = (t_dev ? 0 : T.n * live) + (s_dev ? 0 : S.n * live);
-		const size_t o_in_t = take(up_bytes), o_in_s = o_in_t + (t_dev ? 0 : T.n * live); // side by side: one upload
-		const size_t o_desc_t = take((size_t)T.n * 48u), o_desc_s = take((size_t)S.n * 48u);
-		const size_t o_rowkey = take((size_t)T.n * 8u), o_colkey = take((size_t)S.n * 8u);
-		const size_t o_mm = take(8);
-		const size_t out_bytes = fixed ? (size_t)(1u + K) * 8u : (size_t)(2u + 2u * (size_t)T.n) * 4u;
-		const size_t o_out = take(out_bytes);
-		const size_t sel_bytes = sizeof(NccSel) + (size_t)MULLS_NCC_HIST_LEVELS * MULLS_NCC_HIST_BUCKETS * 4u;
-		const size_t o_sel = take(fixed ? sel_bytes : 0);
-		if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
+		mulls_ncc_problem P;
+		P.tgt = *tgt_kpts, P.src = *src_kpts;
+		P.tgt_idx = tgt_idx, P.src_idx = src_idx, P.cap = cap, P.reserved = 0;
+		mulls_ncc_result R;
+		if (int rc = ncc_run(ctx, SINGLE, &P, 1, params, 0, &R)) // (the default scratch limit; a lone problem runs whatever its size)
 			return rc;
-		if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, up256(up_bytes) + out_bytes, hipHostMallocDefault))
-			return rc;
-		unsigned char *pin_out = sc.pin + up256(up_bytes);
-		unsigned char *d = sc.dev;
-		hipStream_t st = ctx->stream;
-		mulls::StreamDrain drain{st};
-
-		// one upload: the live floats of the host clouds
-		if (!t_dev)
-			pack_live(T, reinterpret_cast<float *>(sc.pin));
-		if (!s_dev)
-			pack_live(S, reinterpret_cast<float *>(sc.pin + (t_dev ? 0 : T.n * live)));
-		if (up_bytes)
-			HIPCHK(ctx, hipMemcpyAsync(d + o_in_t, sc.pin, up_bytes, hipMemcpyHostToDevice, st));
-		const NccCloudIn in_t{t_dev ? static_cast<const float *>(T.pts) : reinterpret_cast<const float *>(d + o_in_t), T.n, t_dev ? 0u : 1u};
-		const NccCloudIn in_s{s_dev ? static_cast<const float *>(S.pts) : reinterpret_cast<const float *>(d + o_in_s), S.n, s_dev ? 0u : 1u};
-		float4 *desc_t = reinterpret_cast<float4 *>(d + o_desc_t), *desc_s = reinterpret_cast<float4 *>(d + o_desc_s);
-		unsigned long long *rowkey = reinterpret_cast<unsigned long long *>(d + o_rowkey), *colkey = reinterpret_cast<unsigned long long *>(d + o_colkey);
-		float *mm = reinterpret_cast<float *>(d + o_mm);
-		HIPCHK(ctx, launch_ncc_minmax(st, in_t, mm));
-		HIPCHK(ctx, launch_ncc_desc(st, in_t, in_s, mm, desc_t, desc_s, rowkey, colkey));
-
-		if (!fixed)
-		{
-			uint32_t *out = reinterpret_cast<uint32_t *>(d + o_out);
-			HIPCHK(ctx, launch_ncc_rowmin(st, desc_t, T.n, desc_s, S.n, rowkey));
-			if (params->reciprocal_on)
-				HIPCHK(ctx, launch_ncc_rowmin(st, desc_s, S.n, desc_t, T.n, colkey)); // the roles swapped: column minima
-			HIPCHK(ctx, launch_ncc_recip(st, rowkey, colkey, T.n, params->reciprocal_on != 0, out));
-			HIPCHK(ctx, hipMemcpyAsync(pin_out, out, out_bytes, hipMemcpyDeviceToHost, st));
-			HIPCHK(ctx, hipStreamSynchronize(st));
-			const uint32_t n = finish_pairs(reinterpret_cast<const uint32_t *>(pin_out), T.n, tgt_idx, src_idx, cap);
-			*n_corr = n;
-			return 1;
-		}
-
-		unsigned long long *cand = reinterpret_cast<unsigned long long *>(d + o_out);
-		HIPCHK(ctx, hipMemsetAsync(d + o_sel, 0, sel_bytes, st));
-		HIPCHK(ctx, hipMemsetAsync(cand, 0, 8, st));
-		HIPCHK(ctx, launch_ncc_select(st, desc_t, T.n, desc_s, S.n, K, reinterpret_cast<NccSel *>(d + o_sel), reinterpret_cast<uint32_t *>(d + o_sel + sizeof(NccSel)), cand));
-		HIPCHK(ctx, hipMemcpyAsync(pin_out, cand, out_bytes, hipMemcpyDeviceToHost, st));
-		HIPCHK(ctx, hipStreamSynchronize(st));
-		*n_corr = finish_fixed(reinterpret_cast<unsigned long long *>(pin_out), K, T.n, S.n, tgt_idx, src_idx, cap);
-		return 1;
+		*n_corr = R.n_corr;
+		return R.ret;
 	}
 	catch (...)
 	{
@@ -382,7 +317,7 @@ extern "C"
 								   uint64_t scratch_limit_bytes, mulls_ncc_result *results)
 	try
 	{
-		return ncc_batch_run(ctx, problems, n_problems, params, scratch_limit_bytes, results);
+		return ncc_run(ctx, BATCH, problems, n_problems, params, scratch_limit_bytes, results);
 	}
 	catch (...)
 	{

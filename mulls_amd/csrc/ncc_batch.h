@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ncc_launch.h"
+#include "subbatch.h"
 
 // one problem of a sub-batch as the device sees it.  Offsets are bytes from the arena's base, multiples of 256.
 struct NccBatchDesc
@@ -21,7 +22,7 @@ struct NccBatchDesc
 	uint64_t desc_t, desc_s;   // n_t / n_s descriptors of three float4
 	uint64_t rowkey, colkey;   // n_t / n_s 64-bit keys
 	uint64_t mm;			   // intensity_min, intensity_max
-	uint64_t out;			   // nearest-neighbour modes: 2 + 2 n_t words (k_ncc_recip's out); fixed-number mode: 1 + K keys (cand)
+	uint64_t out;			   // nearest-neighbour modes: 2 + 2 n_t words (ncc_recip_compact's out); fixed-number mode: 1 + K keys (cand)
 	uint64_t sel, hist;		   // fixed-number mode: the NccSel record and the MULLS_NCC_HIST_LEVELS x MULLS_NCC_HIST_BUCKETS words behind it
 	uint32_t n_t, n_s, K;	   // K: min(corr_num, n_t * n_s), fixed-number mode only
 	uint32_t ext_t, ext_s;	   // the cloud is device-resident
@@ -53,24 +54,23 @@ struct NccBatchLayout
 	uint64_t dev_bytes = 0;
 };
 
-inline uint64_t ncc_batch_up256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
-
 inline uint64_t ncc_batch_out_bytes(uint32_t n_t, bool fixed, uint32_t K) { return fixed ? (uint64_t)(1u + K) * 8u : (2u + 2u * (uint64_t)n_t) * 4u; }
-inline uint64_t ncc_batch_sel_bytes() { return ncc_batch_up256(sizeof(NccSel)) + (uint64_t)MULLS_NCC_HIST_LEVELS * MULLS_NCC_HIST_BUCKETS * 4u; }
+inline uint64_t ncc_batch_sel_bytes() { return up256(sizeof(NccSel)) + (uint64_t)MULLS_NCC_HIST_LEVELS * MULLS_NCC_HIST_BUCKETS * 4u; }
 
 // the arena bytes of one problem: an upper bound (both clouds counted as staged for this problem alone; its share of the head as 512)
 inline uint64_t ncc_batch_problem_bytes(uint32_t n_t, uint32_t n_s, bool fixed, uint32_t K)
 {
 	const uint64_t live = MULLS_NCC_LIVE * 4u;
-	return ncc_batch_up256(n_t * live) + ncc_batch_up256(n_s * live) + ncc_batch_up256((uint64_t)n_t * 48u) + ncc_batch_up256((uint64_t)n_s * 48u) +
-		   ncc_batch_up256((uint64_t)n_t * 8u) + ncc_batch_up256((uint64_t)n_s * 8u) + 256u + ncc_batch_up256(ncc_batch_out_bytes(n_t, fixed, K)) +
-		   (fixed ? ncc_batch_up256(ncc_batch_sel_bytes()) : 0u) + 512u;
+	return up256(n_t * live) + up256(n_s * live) + up256((uint64_t)n_t * 48u) + up256((uint64_t)n_s * 48u) +
+		   up256((uint64_t)n_t * 8u) + up256((uint64_t)n_s * 8u) + 256u + up256(ncc_batch_out_bytes(n_t, fixed, K)) +
+		   (fixed ? up256(ncc_batch_sel_bytes()) : 0u) + 512u;
 }
 
 inline uint64_t ncc_batch_row_blocks(uint32_t n_rows) { return ((uint64_t)n_rows + MULLS_NCC_ROWS - 1u) / MULLS_NCC_ROWS; }
 
-// Columns per workgroup of a table pass of n_rows x n_cols for a problem that is to have about `aim` workgroups: ncc_chunk of k_ncc.hip with `aim` in
-// the place of MULLS_NCC_WGS (a batch of one has aim = MULLS_NCC_WGS and the single call's split; there is no gridDim.y to stay below here).
+// Columns per workgroup of a table pass of n_rows x n_cols for a problem that is to have about `aim` workgroups: the column range is split until row
+// blocks x chunks reach `aim`, into chunks of 32 columns at least (a problem that runs alone has aim = MULLS_NCC_WGS; the grid is flat, so no gridDim.y
+// bounds the number of chunks).
 // THE CHUNK IS WORK SPLIT ONLY: the row minima are merged by a 64-bit atomicMin, the histograms are integer sums and the collected keys are ordered on the
 // host, so no result depends on it.
 inline uint32_t ncc_batch_chunk(uint32_t n_rows, uint32_t n_cols, uint64_t aim)
@@ -84,29 +84,17 @@ inline uint32_t ncc_batch_chunk(uint32_t n_rows, uint32_t n_cols, uint64_t aim)
 // the workgroups of that pass: row blocks x column chunks, at most max(row blocks, aim)
 inline uint64_t ncc_batch_wgs(uint32_t n_rows, uint32_t n_cols, uint32_t chunk) { return ncc_batch_row_blocks(n_rows) * (((uint64_t)n_cols + chunk - 1u) / chunk); }
 
-// more workgroups than any launch has for this problem (aim <= MULLS_NCC_WGS), the descriptor launch's blocks included
+// more workgroups than any launch has for this problem (aim <= MULLS_NCC_WGS), the descriptor launch's blocks included: sub_batch_cuts' second budget,
+// so that a launch's grid stays below MULLS_NCC_BATCH_MAX_WGS.  (At most 2^23 + 2048 + 2^24 for 2^31 - 1 key points a side: a problem that runs alone,
+// which no budget cuts, has its grids far below that too.)
 inline uint64_t ncc_batch_wgs_bound(uint32_t n_t, uint32_t n_s)
 {
 	const uint64_t rt = ncc_batch_row_blocks(n_t), rs = ncc_batch_row_blocks(n_s);
 	return (rt > rs ? rt : rs) + MULLS_NCC_WGS + ((uint64_t)n_t + n_s + 255u) / 256u;
 }
 
-// consecutive cuts: cuts[k] .. cuts[k + 1] is sub-batch k; a sub-batch takes problems while their bytes stay at or below the limit, and one at least.
-// wgs[b]: a bound of problem b's workgroups in any launch, so that a launch's grid stays below MULLS_NCC_BATCH_MAX_WGS
-inline void ncc_batch_cuts(const uint64_t *bytes, const uint64_t *wgs, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts)
-{
-	cuts->assign(1, 0u);
-	uint64_t held = 0, grid = 0;
-	for (uint32_t b = 0; b < count; b++)
-	{
-		if (b > cuts->back() && (held + bytes[b] > limit || grid + wgs[b] > MULLS_NCC_BATCH_MAX_WGS || b - cuts->back() >= MULLS_NCC_BATCH_MAX_PROBLEMS))
-			cuts->push_back(b), held = 0, grid = 0;
-		held += bytes[b];
-		grid += wgs[b];
-	}
-	if (count)
-		cuts->push_back(count);
-}
+// the cut rule of subbatch.h; wgs[b]: ncc_batch_wgs_bound of problem b
+inline void ncc_batch_cuts(const uint64_t *bytes, const uint64_t *wgs, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts) { sub_batch_cuts(bytes, count, limit, MULLS_NCC_BATCH_MAX_PROBLEMS, cuts, 0, wgs, MULLS_NCC_BATCH_MAX_WGS); }
 
 // the arena of the problems shape[0 .. count), and their records
 inline void ncc_batch_layout(NccBatchShape *shape, uint32_t count, bool fixed, NccBatchLayout *L)
@@ -117,7 +105,7 @@ inline void ncc_batch_layout(NccBatchShape *shape, uint32_t count, bool fixed, N
 	uint64_t off = 0;
 	auto take = [&](uint64_t bytes) {
 		const uint64_t at = off;
-		off += ncc_batch_up256(bytes);
+		off += up256(bytes);
 		return at;
 	};
 	L->o_desc = take(sizeof(NccBatchDesc) * (uint64_t)count);
@@ -183,8 +171,11 @@ inline void ncc_batch_layout(NccBatchShape *shape, uint32_t count, bool fixed, N
 // ---- launchers (k_ncc_batch.hip).  arena: the base the offsets count from; head: the records and prefix tables inside it, as laid out above; B problems.
 // intensity ranges, descriptors, key presets and — fixed-number mode — the zero of cand's counter
 hipError_t launch_ncc_batch_describe(hipStream_t st, unsigned char *arena, const NccBatchLayout &L, uint32_t B, int fixed);
-// the row minima of every problem; swapped: the column minima (the sources as rows)
+// the row minima of every problem, key[r] = min over the columns of (float bits of d(r, c) << 32 | c): the first column with the strictly smallest distance
+// below FLT_MAX; swapped: the column minima (the sources as rows)
 hipError_t launch_ncc_batch_rowmin(hipStream_t st, unsigned char *arena, const NccBatchLayout &L, uint32_t B, int swapped);
+// out[0] = count, out[2 + k] = i, out[2 + n_t + k] = j*(i) of the k-th surviving target in ascending i
 hipError_t launch_ncc_batch_recip(hipStream_t st, unsigned char *arena, const NccBatchLayout &L, uint32_t B, int reciprocal);
-// the six digit levels in lock-step and the collection; sel, hist zeroed by the caller
+// the six digit levels in lock-step (histogram + pick each), then the collection of every key up to the rank-K key into cand[1 ...] (at most
+// MULLS_NCC_MAX_CORR, unordered), their count in the low word of cand[0]; sel, hist zeroed by the caller
 hipError_t launch_ncc_batch_select(hipStream_t st, unsigned char *arena, const NccBatchLayout &L, uint32_t B);

@@ -1,7 +1,14 @@
-// ncc_device.h — the device code that k_ncc.hip (one problem per call) and k_ncc_batch.hip (the problems of a sub-batch per launch) share, so that both
-// compile the same text: the descriptor arithmetic, d(i, j), a table pass over one (row block, column range), the digit rule of the fixed-number
-// selection, and the bodies of the single-workgroup steps.  A kernel of either file only decides which problem, row block and column range a workgroup
+// ncc_device.h — key-point descriptor matching: CRegistration<PointT>::find_feature_correspondence_ncc (cregistration.hpp:409-601) for gfx950.  The
+// arithmetic of the k_nb_* kernels (k_ncc_batch.hip): the descriptors, d(i, j), a table pass over one (row block, column range), the digit rule of the
+// fixed-number selection, and the bodies of the single-workgroup steps.  A kernel only decides which problem, row block and column range a workgroup
 // works on; nothing here reads blockIdx.
+//
+// The reference fills an Nt x Ns table of L1 distances between 11-float "neighbourhood category context" descriptors and then reads it three ways: row minima
+// (nearest neighbour), column minima (the reciprocal test), or its corr_num smallest entries (a sort of all Nt * Ns).  Here the table is never stored.  One
+// lane owns one row point, its descriptor in registers; the column descriptors are the same for every lane of a wave at the same time, so they come
+// through the scalar cache into SGPRs (no LDS, no vector loads in the loop) and an entry costs its 22 VALU operations and nothing else.  d(i, j) is
+// recomputed by the same eleven float additions in k order in every pass and with either cloud as the rows (|a - b| == |b - a| bit for bit), which is what lets
+// the passes agree on equal distances.  Built with -ffp-contract=off like the rest of the library (there is no multiply in the distance anyway).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,6 +1,6 @@
-// ncc_launch.h — host-callable launchers of k_ncc.hip: key-point descriptor matching, CRegistration::find_feature_correspondence_ncc
-// (cregistration.hpp:409-601).  The Nt x Ns table of 11-term L1 distances is never stored: every pass recomputes d(i, j) from the two
-// descriptor arrays, with the same float expression, so that it has the same bits wherever it is formed.
+// ncc_launch.h — what the host and the device code of key-point descriptor matching, CRegistration::find_feature_correspondence_ncc
+// (cregistration.hpp:409-601), share: the input view, the constants and the selection record (ncc_device.h has the device code, ncc_batch.h the planner
+// and the launchers).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
@@ -30,18 +30,3 @@ struct NccSel
 	uint32_t none;		// no finite-or-infinite distance at all (every entry NaN): nothing is selected
 	uint32_t pad_[3];
 };
-
-// intensity_min / intensity_max over the target exactly as the loop of :436-442 leaves them -> mm[0], mm[1]
-hipError_t launch_ncc_minmax(hipStream_t st, NccCloudIn tgt, float *mm);
-// 11-float descriptors (padded to 12) of both clouds; rowkey[Nt] / colkey[Ns] preset to (FLT_MAX, 0)
-hipError_t launch_ncc_desc(hipStream_t st, NccCloudIn tgt, NccCloudIn src, const float *mm, float4 *desc_t, float4 *desc_s, unsigned long long *rowkey,
-						   unsigned long long *colkey);
-// key[r] = min over the columns of (float bits of d(r, c) << 32 | c): the first column with the strictly smallest distance below FLT_MAX
-hipError_t launch_ncc_rowmin(hipStream_t st, const float4 *rows, uint32_t n_rows, const float4 *cols, uint32_t n_cols, unsigned long long *key);
-// out[0] = count, out[2 + k] = i, out[2 + n_t + k] = j*(i) of the k-th surviving target in ascending i
-hipError_t launch_ncc_recip(hipStream_t st, const unsigned long long *rowkey, const unsigned long long *colkey, uint32_t n_t, int reciprocal, uint32_t *out);
-// fixed-number mode: the six digit levels (histogram + pick each), then the collection of every key up to the rank-K key into
-// cand[1 ...] (at most MULLS_NCC_MAX_CORR, unordered), their count in the low word of cand[0].  hist: MULLS_NCC_HIST_LEVELS x MULLS_NCC_HIST_BUCKETS words;
-// sel, hist and cand[0] zeroed by the caller
-hipError_t launch_ncc_select(hipStream_t st, const float4 *desc_t, uint32_t n_t, const float4 *desc_s, uint32_t n_s, uint32_t K, NccSel *sel, uint32_t *hist,
-							 unsigned long long *cand);

@@ -7,6 +7,7 @@
 #include "ctx.h"
 #include "ndt_host.h"
 #include "ndt_launch.h"
+#include "subbatch.h"
 
 // a context's scratch of this entry point: one device arena, one pinned host buffer; grow-only
 struct mulls_ndt_scratch
@@ -136,8 +137,6 @@ namespace
 {
 using namespace ndt_host;
 constexpr uint32_t MAX_SUB_BATCH = 4096u; // problems of one sub-batch (one grid dimension of the per-point launches)
-
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 struct Plan
 {
@@ -374,18 +373,14 @@ int ndt_run(mulls_ctx *ctx, const mulls_ndt_problem *problems, uint32_t n_proble
 	if (!ctx->ndt)
 		ctx->ndt = new mulls_ndt_scratch();
 	const size_t limit = params->scratch_limit_bytes ? (size_t)params->scratch_limit_bytes : (size_t)MULLS_NDT_BATCH_DEFAULT_SCRATCH_BYTES;
-	std::vector<uint32_t> work(n_problems);
+	std::vector<uint32_t> work(n_problems), cuts;
+	std::vector<uint64_t> bytes(n_problems);
 	for (uint32_t b = 0; b < n_problems; b++)
-		work[b] = b;
-	for (size_t first = 0; first < work.size();)
-	{
-		size_t count = 1, bytes = plans[work[first]].bytes;
-		while (first + count < work.size() && count < MAX_SUB_BATCH && bytes + plans[work[first + count]].bytes <= limit)
-			bytes += plans[work[first + count++]].bytes;
-		if (int rc = run_sub_batch(ctx, problems, plans, work.data() + first, (uint32_t)count, *params, opt, results, who, single))
+		work[b] = b, bytes[b] = plans[b].bytes;
+	sub_batch_cuts(bytes.data(), n_problems, limit, MAX_SUB_BATCH, &cuts);
+	for (size_t c = 0; c + 1 < cuts.size(); c++)
+		if (int rc = run_sub_batch(ctx, problems, plans, work.data() + cuts[c], cuts[c + 1] - cuts[c], *params, opt, results, who, single))
 			return rc;
-		first += count;
-	}
 	return MULLS_OK;
 }
 } // namespace

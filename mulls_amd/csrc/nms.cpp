@@ -14,6 +14,7 @@
 #include "nms_host.h"
 #include "nms_launch.h"
 #include "rounds.h"
+#include "subbatch.h"
 
 // a context's scratch of this entry point: one device arena, one pinned host buffer; grow-only
 struct mulls_nms_scratch
@@ -38,8 +39,6 @@ namespace
 {
 constexpr size_t REC = MULLS_POINT_BYTES;
 constexpr size_t HDR_BYTES = 256;
-
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
 {

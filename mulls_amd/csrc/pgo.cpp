@@ -7,6 +7,7 @@
 #include "ctx.h"
 #include "pgo_launch.h"
 #include "pgo_math.h"
+#include "subbatch.h"
 
 // a context's scratch of this entry point: one device arena, one pinned host buffer; grow-only
 struct mulls_pgo_scratch
@@ -29,8 +30,6 @@ void mulls_pgo_release(mulls_ctx *ctx)
 namespace
 {
 constexpr uint32_t MAX_SUB_BATCH = 4096u; // problems of one sub-batch (one grid dimension of the per-edge launches)
-
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 // what the host works out of one problem before any device work
 struct Plan
@@ -488,6 +487,7 @@ int pgo_run(mulls_ctx *ctx, const mulls_pgo_problem *problems, uint32_t n_proble
 	}
 	const size_t limit = scratch_limit_bytes ? (size_t)scratch_limit_bytes : (size_t)MULLS_PGO_BATCH_DEFAULT_SCRATCH_BYTES;
 	std::vector<uint32_t> work;
+	std::vector<uint64_t> bytes; // of the problems in `work`
 	for (uint32_t b = 0; b < n_problems; b++)
 	{
 		const mulls_pgo_problem &P = problems[b];
@@ -511,22 +511,18 @@ int pgo_run(mulls_ctx *ctx, const mulls_pgo_problem *problems, uint32_t n_proble
 			continue;
 		}
 		L.bytes = bytes_of(L, P.n_nodes);
-		work.push_back(b);
+		work.push_back(b), bytes.push_back(L.bytes);
 	}
 	if (work.empty())
 		return MULLS_OK;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	if (!ctx->pgo)
 		ctx->pgo = new mulls_pgo_scratch();
-	for (size_t first = 0; first < work.size();)
-	{
-		size_t count = 1, bytes = plans[work[first]].bytes;
-		while (first + count < work.size() && count < MAX_SUB_BATCH && bytes + plans[work[first + count]].bytes <= limit)
-			bytes += plans[work[first + count++]].bytes;
-		if (int rc = run_sub_batch(ctx, problems, plans, work.data() + first, (uint32_t)count, *params, results))
+	std::vector<uint32_t> cuts;
+	sub_batch_cuts(bytes.data(), (uint32_t)work.size(), limit, MAX_SUB_BATCH, &cuts);
+	for (size_t c = 0; c + 1 < cuts.size(); c++)
+		if (int rc = run_sub_batch(ctx, problems, plans, work.data() + cuts[c], cuts[c + 1] - cuts[c], *params, results))
 			return rc;
-		first += count;
-	}
 	return MULLS_OK;
 }
 } // namespace

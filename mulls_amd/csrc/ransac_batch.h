@@ -6,6 +6,8 @@
 
 #include <vector>
 
+#include "subbatch.h"
+
 #define MULLS_RANSAC_MODEL_BYTES 48u // sizeof(RansacModel), sizeof(RansacRound): ransac.cpp asserts both (ransac_launch.h needs HIP's headers)
 #define MULLS_RANSAC_ROUND_BYTES 64u
 #define MULLS_RANSAC_BATCH_MAX_PROBLEMS 16384u // problems of one sub-batch: a grid axis
@@ -53,8 +55,6 @@ struct RansacBatchLayout
 	uint64_t pts_bytes = 0, idx_bytes = 0, tri_bytes = 0, counts_bytes = 0, mask_bytes = 0, round_bytes = 0; // the regions that move whole
 };
 
-inline uint64_t ransac_batch_up256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
-
 // hypotheses of a problem at most: iteration max_iter_num is still evaluated
 inline uint32_t ransac_batch_hypotheses(int32_t max_iter_num) { return (uint32_t)(max_iter_num > 0 ? max_iter_num : 0) + 1u; }
 
@@ -62,26 +62,13 @@ inline uint32_t ransac_batch_hypotheses(int32_t max_iter_num) { return (uint32_t
 inline uint64_t ransac_batch_problem_bytes(uint32_t n, int32_t max_iter_num)
 {
 	const uint64_t H = ransac_batch_hypotheses(max_iter_num);
-	return 2u * ransac_batch_up256((uint64_t)n * 16u) + ransac_batch_up256((uint64_t)n * 8u) + ransac_batch_up256(H * 12u) +
-		   ransac_batch_up256(H * MULLS_RANSAC_MODEL_BYTES) + ransac_batch_up256(H * 4u) + 3u * ransac_batch_up256(n) + ransac_batch_up256((uint64_t)n * 4u) +
-		   ransac_batch_up256(MULLS_RANSAC_ROUND_BYTES) + 512u;
+	return 2u * up256((uint64_t)n * 16u) + up256((uint64_t)n * 8u) + up256(H * 12u) +
+		   up256(H * MULLS_RANSAC_MODEL_BYTES) + up256(H * 4u) + 3u * up256(n) + up256((uint64_t)n * 4u) +
+		   up256(MULLS_RANSAC_ROUND_BYTES) + 512u;
 }
 
-// consecutive cuts: cuts[k] .. cuts[k + 1] is sub-batch k; a sub-batch takes problems while their bytes stay at or below the limit, and one at least
-// (and MULLS_RANSAC_BATCH_MAX_PROBLEMS at most)
-inline void ransac_batch_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts)
-{
-	cuts->assign(1, 0u);
-	uint64_t held = 0;
-	for (uint32_t b = 0; b < count; b++)
-	{
-		if (b > cuts->back() && (held + bytes[b] > limit || b - cuts->back() >= MULLS_RANSAC_BATCH_MAX_PROBLEMS))
-			cuts->push_back(b), held = 0;
-		held += bytes[b];
-	}
-	if (count)
-		cuts->push_back(count);
-}
+// the cut rule of subbatch.h with this batch's constant
+inline void ransac_batch_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts) { sub_batch_cuts(bytes, count, limit, MULLS_RANSAC_BATCH_MAX_PROBLEMS, cuts); }
 
 // the arena of the problems n[0 .. count), each with room for the hypotheses of max_iter_num
 inline void ransac_batch_layout(const uint32_t *n, uint32_t count, int32_t max_iter_num, RansacBatchLayout *L)
@@ -96,13 +83,13 @@ inline void ransac_batch_layout(const uint32_t *n, uint32_t count, int32_t max_i
 	};
 	L->o_desc = table(sizeof(RansacBatchDesc)), L->o_win = table(MULLS_RANSAC_ROUND_BYTES), L->o_gather = table(2u * sizeof(RansacBatchGather));
 	L->o_jobs = table(sizeof(RansacBatchJob));
-	off = ransac_batch_up256(off); // (at most 512 bytes per problem)
+	off = up256(off); // (at most 512 bytes per problem)
 	auto region = [&](uint64_t RansacBatchDesc::*field, uint64_t per_pair, uint64_t fixed, uint64_t *bytes) {
 		const uint64_t at = off;
 		for (uint32_t b = 0; b < count; b++)
 		{
 			L->desc[b].*field = off;
-			off += ransac_batch_up256(fixed ? fixed : (uint64_t)n[b] * per_pair);
+			off += up256(fixed ? fixed : (uint64_t)n[b] * per_pair);
 		}
 		if (bytes)
 			*bytes = off - at;
@@ -112,8 +99,8 @@ inline void ransac_batch_layout(const uint32_t *n, uint32_t count, int32_t max_i
 	for (uint32_t b = 0; b < count; b++) // a problem's source and target points lie side by side
 	{
 		L->desc[b].n = n[b], L->desc[b].n_hyp = 0, L->desc[b].best = -1;
-		L->desc[b].src = off, off += ransac_batch_up256((uint64_t)n[b] * 16u);
-		L->desc[b].tgt = off, off += ransac_batch_up256((uint64_t)n[b] * 16u);
+		L->desc[b].src = off, off += up256((uint64_t)n[b] * 16u);
+		L->desc[b].tgt = off, off += up256((uint64_t)n[b] * 16u);
 	}
 	L->pts_bytes = off - L->o_pts;
 	L->o_idx = region(&RansacBatchDesc::idx, 8, 0, &L->idx_bytes);
@@ -123,8 +110,8 @@ inline void ransac_batch_layout(const uint32_t *n, uint32_t count, int32_t max_i
 	L->o_mask = off;
 	for (uint32_t b = 0; b < count; b++) // a problem's three masks lie side by side
 	{
-		L->desc[b].mask = off, L->desc[b].mask_stride = (uint32_t)ransac_batch_up256(n[b]);
-		off += 3u * ransac_batch_up256(n[b]);
+		L->desc[b].mask = off, L->desc[b].mask_stride = (uint32_t)up256(n[b]);
+		off += 3u * up256(n[b]);
 	}
 	L->mask_bytes = off - L->o_mask;
 	L->o_d2 = region(&RansacBatchDesc::d2, 4, 0, nullptr);
@@ -133,7 +120,7 @@ inline void ransac_batch_layout(const uint32_t *n, uint32_t count, int32_t max_i
 	uint64_t p = 0;
 	auto mirror = [&](uint64_t bytes) {
 		const uint64_t at = p;
-		p += ransac_batch_up256(bytes);
+		p += up256(bytes);
 		return at;
 	};
 	L->p_desc = mirror(sizeof(RansacBatchDesc) * count), L->p_win = mirror((uint64_t)MULLS_RANSAC_ROUND_BYTES * count);

@@ -8,6 +8,7 @@
 #include "ctx.h"
 #include "scan_host.h"
 #include "scan_launch.h"
+#include "subbatch.h"
 
 // a context's scratch of these entry points: one device arena (tables, per-chunk arrays, staged host frames), the records mulls_scan_prepare keeps on
 // their way back, one pinned host buffer for the tables; grow-only
@@ -29,8 +30,6 @@ using namespace mulls::scan;
 constexpr size_t REC = MULLS_POINT_BYTES;
 constexpr size_t STAGE_BUDGET_BYTES = (size_t)512 << 20; // host frames staged per sub-batch (a frame beyond it travels alone)
 constexpr uint32_t MAX_FRAMES_PER_SUBBATCH = 4096u, MAX_CHUNKS_PER_SUBBATCH = 1u << 20;
-
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 bool on_device(mulls_ctx *ctx, const void *pts, size_t bytes)
 {

@@ -7,6 +7,7 @@
 
 #include "ctx.h"
 #include "sor_launch.h"
+#include "subbatch.h"
 
 // a context's scratch of this entry point: one device arena, one device buffer for a device cloud's kept records, one pinned host buffer; grow-only
 struct mulls_sor_scratch
@@ -31,8 +32,6 @@ namespace
 {
 constexpr uint32_t BRUTE_QUERIES_PER_LAUNCH = 65536u; // bounds one brute-force launch's work whatever the cloud looks like
 constexpr size_t HDR_BYTES = 256;
-
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
 
 bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
 {

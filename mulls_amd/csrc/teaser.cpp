@@ -42,8 +42,6 @@ void mulls_teaser_release(mulls_ctx *ctx)
 
 namespace
 {
-size_t up256(size_t v) { return (v + 255u) & ~(size_t)255u; }
-
 bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
 {
 	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * MULLS_POINT_BYTES))

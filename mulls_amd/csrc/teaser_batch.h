@@ -10,6 +10,7 @@
 
 #include <vector>
 
+#include "subbatch.h"
 #include "teaser_math.h"
 
 // one problem of a sub-batch, as the device sees it: byte offsets into the arena (weights: into the weights arena), all multiples of 256
@@ -50,34 +51,19 @@ struct TeaserBatchLayout
 	uint64_t pts_bytes = 0, idx_bytes = 0, core_bytes = 0, keep_bytes = 0; // the regions that move whole
 };
 
-inline uint64_t teaser_batch_up256(uint64_t v) { return (v + 255u) & ~(uint64_t)255u; }
-
 // the arena bytes of one problem (its share of the tables is counted as 512)
 inline uint64_t teaser_batch_problem_bytes(uint32_t n)
 {
-	const uint64_t W = (n + 63u) / 64u, mat = teaser_batch_up256((uint64_t)n * W * 8u), p16 = teaser_batch_up256((uint64_t)n * 16u);
-	return 4u * p16 + 2u * teaser_batch_up256((uint64_t)n * 8u) + 2u * mat + 2u * teaser_batch_up256((uint64_t)n * 4u) +
-		   teaser_batch_up256((uint64_t)9u * MULLS_TEASER_PARTIALS * 8u) + 512u;
+	const uint64_t W = (n + 63u) / 64u, mat = up256((uint64_t)n * W * 8u), p16 = up256((uint64_t)n * 16u);
+	return 4u * p16 + 2u * up256((uint64_t)n * 8u) + 2u * mat + 2u * up256((uint64_t)n * 4u) +
+		   up256((uint64_t)9u * MULLS_TEASER_PARTIALS * 8u) + 512u;
 }
 
 // the weights of a clique of C
-inline uint64_t teaser_batch_weight_bytes(uint32_t C) { return C < 2u ? 0u : teaser_batch_up256((uint64_t)C * (C - 1u) / 2u * 8u); }
+inline uint64_t teaser_batch_weight_bytes(uint32_t C) { return C < 2u ? 0u : up256((uint64_t)C * (C - 1u) / 2u * 8u); }
 
-// consecutive cuts: cuts[k] .. cuts[k + 1] is sub-batch k; a sub-batch takes problems while their bytes stay at or below the limit, and one at least
-// (and MULLS_TEASER_BATCH_MAX_PROBLEMS at most)
-inline void teaser_batch_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts)
-{
-	cuts->assign(1, 0u);
-	uint64_t held = 0;
-	for (uint32_t b = 0; b < count; b++)
-	{
-		if (b > cuts->back() && (held + bytes[b] > limit || b - cuts->back() >= MULLS_TEASER_BATCH_MAX_PROBLEMS))
-			cuts->push_back(b), held = 0;
-		held += bytes[b];
-	}
-	if (count)
-		cuts->push_back(count);
-}
+// the cut rule of subbatch.h with this batch's constant
+inline void teaser_batch_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts) { sub_batch_cuts(bytes, count, limit, MULLS_TEASER_BATCH_MAX_PROBLEMS, cuts); }
 
 // the arena of the problems n[0 .. count): every offset but sub, cs, ct and weights
 inline void teaser_batch_layout(const uint32_t *n, uint32_t count, TeaserBatchLayout *L)
@@ -91,14 +77,14 @@ inline void teaser_batch_layout(const uint32_t *n, uint32_t count, TeaserBatchLa
 	};
 	L->o_desc = table(sizeof(TeaserBatchDesc)), L->o_gnc = table(sizeof(TeaserGnc)), L->o_sum = table(8);
 	L->o_jobs = table(2u * sizeof(TeaserBatchGather)), L->o_frozen = table(4);
-	off = teaser_batch_up256(off); // (at most 512 bytes per problem)
+	off = up256(off); // (at most 512 bytes per problem)
 	auto region = [&](uint64_t TeaserBatchDesc::*field, uint64_t per_point, bool matrix, bool fixed) {
 		const uint64_t at = off;
 		for (uint32_t b = 0; b < count; b++)
 		{
 			const uint64_t W = (n[b] + 63u) / 64u;
 			L->desc[b].*field = off;
-			off += teaser_batch_up256(fixed ? per_point : (matrix ? (uint64_t)n[b] * W * 8u : (uint64_t)n[b] * per_point));
+			off += up256(fixed ? per_point : (matrix ? (uint64_t)n[b] * W * 8u : (uint64_t)n[b] * per_point));
 		}
 		return at;
 	};
@@ -106,8 +92,8 @@ inline void teaser_batch_layout(const uint32_t *n, uint32_t count, TeaserBatchLa
 	for (uint32_t b = 0; b < count; b++) // a problem's source and target points lie side by side
 	{
 		L->desc[b].n = n[b], L->desc[b].W = (n[b] + 63u) / 64u;
-		L->desc[b].src = off, off += teaser_batch_up256((uint64_t)n[b] * 16u);
-		L->desc[b].tgt = off, off += teaser_batch_up256((uint64_t)n[b] * 16u);
+		L->desc[b].src = off, off += up256((uint64_t)n[b] * 16u);
+		L->desc[b].tgt = off, off += up256((uint64_t)n[b] * 16u);
 	}
 	L->pts_bytes = off - L->o_pts;
 	L->o_idx = region(&TeaserBatchDesc::idx, 8, false, false), L->idx_bytes = off - L->o_idx;
@@ -119,15 +105,15 @@ inline void teaser_batch_layout(const uint32_t *n, uint32_t count, TeaserBatchLa
 	L->o_cpts = off;
 	for (uint32_t b = 0; b < count; b++)
 	{
-		L->desc[b].cs = off, off += teaser_batch_up256((uint64_t)n[b] * 16u);
-		L->desc[b].ct = off, off += teaser_batch_up256((uint64_t)n[b] * 16u);
+		L->desc[b].cs = off, off += up256((uint64_t)n[b] * 16u);
+		L->desc[b].ct = off, off += up256((uint64_t)n[b] * 16u);
 	}
 	L->o_part = region(&TeaserBatchDesc::part, (uint64_t)9u * MULLS_TEASER_PARTIALS * 8u, false, true);
 	L->dev_bytes = off;
 	uint64_t p = 0;
 	auto mirror = [&](uint64_t bytes) {
 		const uint64_t at = p;
-		p += teaser_batch_up256(bytes);
+		p += up256(bytes);
 		return at;
 	};
 	L->p_desc = mirror(sizeof(TeaserBatchDesc) * count), L->p_gnc = mirror(sizeof(TeaserGnc) * count), L->p_sum = mirror((uint64_t)8u * count);
@@ -145,7 +131,7 @@ inline uint64_t teaser_batch_pack_sub(TeaserBatchLayout *L, const uint32_t *m)
 	{
 		TeaserBatchDesc &D = L->desc[b];
 		D.m = m[b], D.Wm = (m[b] + 63u) / 64u, D.sub = off; // (m <= n: the packed matrices end inside the region)
-		off += teaser_batch_up256((uint64_t)D.m * D.Wm * 8u);
+		off += up256((uint64_t)D.m * D.Wm * 8u);
 	}
 	return off - L->o_sub;
 }
@@ -158,8 +144,8 @@ inline uint64_t teaser_batch_pack_clique(TeaserBatchLayout *L, const uint32_t *C
 	{
 		TeaserBatchDesc &D = L->desc[b];
 		D.C = C[b], D.M = C[b] < 2u ? 0u : (uint64_t)C[b] * (C[b] - 1u) / 2u;
-		D.cs = off, off += teaser_batch_up256((uint64_t)C[b] * 16u);
-		D.ct = off, off += teaser_batch_up256((uint64_t)C[b] * 16u);
+		D.cs = off, off += up256((uint64_t)C[b] * 16u);
+		D.ct = off, off += up256((uint64_t)C[b] * 16u);
 	}
 	return off - L->o_cpts;
 }

@@ -482,3 +482,36 @@ def test_scratch_after_the_largest_table(ctx_auto, pairs_small):
                 ok, got, n = device_pairs(ctx_auto, a, b, *m)
                 assert ok and np.array_equal(got, before[tag, m]), (rep, tag, m)
         assert list(ctx_auto.icp(pairs_small[0][0], P)[0].T[:]) == T0
+
+
+def test_single_call_equals_a_batch_of_one(ctx_auto):
+    """mulls_ncc_correspond against mulls_ncc_correspond_batch on that one problem, on one context: the smallest table, a row block plus one row, and one
+    column past the 32-column chunk floor, in the three modes — equal return value, n_corr and both index lists.  A refused single call (a device cloud
+    with a stride of 49; fixed-number mode with corr_num 70 000) leaves the caller's index buffers alone and *n_corr at 0, and names itself."""
+    from test_gpu_ncc_batch import hip_runtime
+
+    for nt, ns in ((10, 10), (257, 1000), (1025, 33)):
+        t, s = ncc_restated.random_kpts(9000 + nt, nt), ncc_restated.random_kpts(9100 + ns, ns)
+        for m in ALL_MODES:
+            ok, ti, si, n = ctx_auto.ncc_correspond(t, s, abi.ncc_params(*m))
+            (b_ok, b_ti, b_si, b_n), = ctx_auto.ncc_correspond_batch([(t, s)], abi.ncc_params(*m))
+            assert (ok, n) == (b_ok, b_n) and ok is True and n > 0, (nt, ns, m)
+            assert np.array_equal(ti, b_ti) and np.array_equal(si, b_si), (nt, ns, m)
+    L, hip = lib.load(), hip_runtime()
+    good = abi.Cloud()
+    good.pts, good.n, good.stride = s.ctypes.data, len(s), 48
+    dev = C.c_void_p()
+    assert hip.hipMalloc(C.byref(dev), C.c_size_t(49 * len(t))) == 0
+    try:
+        bad = abi.Cloud()
+        bad.pts, bad.n, bad.stride = dev.value, len(t), 49
+        for a, b, m, code, why in ((bad, good, ALL_MODES[0], abi.MULLS_E_INVALID, "stride"), (good, bad, ALL_MODES[2], abi.MULLS_E_INVALID, "stride"),
+                                   (good, good, (1, 70000, 0), abi.MULLS_E_UNSUPPORTED, "corr_num <= 65536")):
+            idx, n = np.full((2, 8), -7, np.int32), C.c_uint32(9)
+            rc = L.mulls_ncc_correspond(ctx_auto.h, C.byref(a), C.byref(b), C.byref(abi.ncc_params(*m)), idx[0].ctypes.data_as(C.c_void_p),
+                                        idx[1].ctypes.data_as(C.c_void_p), 8, C.byref(n))
+            assert rc == code and n.value == 0 and (idx == -7).all(), (m, rc, n.value)
+            text = L.mulls_last_error(ctx_auto.h).decode()
+            assert text.startswith("mulls_ncc_correspond: ") and why in text, text
+    finally:
+        assert hip.hipFree(dev) == 0
