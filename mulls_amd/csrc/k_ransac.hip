@@ -1,11 +1,11 @@
 // k_ransac.hip — the RANSAC coarse-registration solver (CRegistration::coarse_reg_ransac, cregistration.hpp:605-661) for gfx950.
-//   k_ransac_gather  the four live floats of the pairs out of 48-byte records (optionally through an index list)
 //   k_ransac_models  one lane per hypothesis: float centroids and H of its three pairs, Horn's 4 x 4 by cyclic Jacobi in double
 //   k_ransac_score   one wave per four hypotheses: the lanes stride over the pairs, the models sit in scalar registers
 //   k_ransac_select  the inlier mask of one model
 //   k_ransac_refine  one workgroup: a round of PCL's refineModel — fit to the previous inliers, select, exact median by radix select
-//   k_rb_*           the same five steps for the problems of a sub-batch of mulls_coarse_reg_ransac_batch, read from a descriptor table (ransac_batch.h):
+//   k_rb_*           the same four steps for the problems of a sub-batch of mulls_coarse_reg_ransac_batch, read from a descriptor table (ransac_batch.h):
 //                    the second grid axis is the problem (refine: a job list), the arithmetic is the __device__ functions the kernels above call
+// The pairs' points are staged by pair_stage.h (k_pair_gather.hip gathers device-resident clouds).
 // Every float / double expression is written in the order include/mulls_hip.h and DESIGN.md section 7 define (built with -ffp-contract=off):
 // tests/ransac_restated.py reproduces the bits.
 #include <hip/hip_runtime.h>
@@ -29,15 +29,6 @@ __device__ __forceinline__ float resid2(const float *m, const float4 s, const fl
 	const float pz = ((m[8] * s.x + m[9] * s.y) + m[10] * s.z) + m[11];
 	const float dx = px - t.x, dy = py - t.y, dz = pz - t.z;
 	return (dx * dx + dy * dy) + dz * dz;
-}
-
-__global__ void __launch_bounds__(256) k_ransac_gather(const unsigned char *recs, const int32_t *idx, uint32_t n, float4 *out)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-		return;
-	const size_t r = idx ? (size_t)idx[i] : (size_t)i; // (the host has checked the index lists against the clouds' sizes)
-	out[i] = *reinterpret_cast<const float4 *>(recs + r * 48u);
 }
 
 // the rigid transform of the three pairs tri[0 .. 2]
@@ -283,16 +274,6 @@ __device__ __forceinline__ T *at(unsigned char *arena, uint64_t off)
 	return reinterpret_cast<T *>(arena + off);
 }
 
-__global__ void __launch_bounds__(256) k_rb_gather(const RansacBatchGather *jobs, unsigned char *arena)
-{
-	const RansacBatchGather J = jobs[blockIdx.y];
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= J.n)
-		return;
-	const size_t r = J.indexed ? (size_t)at<const int32_t>(arena, J.idx)[i] : (size_t)i; // (the host has checked the index lists against the clouds' sizes)
-	at<float4>(arena, J.out)[i] = *reinterpret_cast<const float4 *>(J.recs + r * 48u);
-}
-
 __global__ void __launch_bounds__(256) k_rb_models(const RansacBatchDesc *desc, unsigned char *arena)
 {
 	const RansacBatchDesc &D = desc[blockIdx.y];
@@ -366,14 +347,6 @@ __global__ void __launch_bounds__(RT) k_rb_refine(const RansacBatchDesc *desc, c
 }
 } // namespace
 
-hipError_t launch_ransac_gather(hipStream_t st, const void *recs, const int32_t *idx, uint32_t n, float4 *out)
-{
-	if (!n)
-		return hipSuccess;
-	hipLaunchKernelGGL(k_ransac_gather, dim3((n + 255u) / 256u), dim3(256), 0, st, static_cast<const unsigned char *>(recs), idx, n, out);
-	return hipGetLastError();
-}
-
 hipError_t launch_ransac_models(hipStream_t st, const float4 *src, const float4 *tgt, const int32_t *triples, uint32_t n_hyp, RansacModel *models)
 {
 	hipLaunchKernelGGL(k_ransac_models, dim3((n_hyp + 255u) / 256u), dim3(256), 0, st, src, tgt, triples, n_hyp, models);
@@ -402,14 +375,6 @@ hipError_t launch_ransac_refine(hipStream_t st, const float4 *src, const float4 
 }
 
 // ---- the sub-batch: grids of (blocks of the largest problem) x (problems); a block past its problem's end returns
-hipError_t launch_ransac_batch_gather(hipStream_t st, const RansacBatchGather *jobs, uint32_t n_jobs, uint32_t n_max, unsigned char *arena)
-{
-	if (!n_jobs || !n_max)
-		return hipSuccess;
-	hipLaunchKernelGGL(k_rb_gather, dim3((n_max + 255u) / 256u, n_jobs), dim3(256), 0, st, jobs, arena);
-	return hipGetLastError();
-}
-
 hipError_t launch_ransac_batch_models(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_hyp_max, unsigned char *arena)
 {
 	hipLaunchKernelGGL(k_rb_models, dim3((n_hyp_max + 255u) / 256u, count), dim3(256), 0, st, desc, arena);

@@ -424,18 +424,6 @@ __device__ __forceinline__ T *at(unsigned char *arena, uint64_t off)
 	return reinterpret_cast<T *>(arena + off);
 }
 
-// out[i] = the first four floats of record idx[i] (idx == NULL: i) of a device cloud of 48-byte records: launch_ransac_gather over a list of jobs
-__global__ void __launch_bounds__(256) k_tb_gather(const TeaserBatchGather *__restrict__ jobs, unsigned char *arena)
-{
-	const TeaserBatchGather J = jobs[blockIdx.y];
-	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i >= J.n)
-		return;
-	const int32_t *idx = J.indexed ? at<const int32_t>(arena, J.idx) : nullptr;
-	const uint32_t r = idx ? (uint32_t)idx[i] : i; // (the host checked every index against its cloud)
-	at<float4>(arena, J.out)[i] = *reinterpret_cast<const float4 *>(J.recs + (size_t)r * 48u);
-}
-
 __global__ void __launch_bounds__(256) k_tb_graph(const TeaserBatchDesc *__restrict__ desc, unsigned char *arena, double beta)
 {
 	const TeaserBatchDesc &D = desc[blockIdx.z];
@@ -596,14 +584,6 @@ hipError_t launch_teaser_gnc_iteration(hipStream_t st, const float4 *cs, const f
 	hipLaunchKernelGGL(k_teaser_cost, dim3(1), dim3(RT), 0, st, part, iter, nb2, S);
 	const uint32_t blocks = (uint32_t)std::min<uint64_t>((M + 255u) / 256u, 4096u);
 	hipLaunchKernelGGL(k_teaser_update, dim3(blocks), dim3(256), 0, st, cs, ct, C, M, nb2, weights, S);
-	return hipGetLastError();
-}
-
-hipError_t launch_teaser_batch_gather(hipStream_t st, const TeaserBatchGather *jobs, uint32_t n_jobs, uint32_t n_max, unsigned char *arena)
-{
-	if (!n_jobs || !n_max)
-		return hipSuccess;
-	hipLaunchKernelGGL(k_tb_gather, dim3((n_max + 255u) / 256u, n_jobs), dim3(256), 0, st, jobs, arena);
 	return hipGetLastError();
 }
 

@@ -1,11 +1,15 @@
 // ransac.cpp — mulls_coarse_reg_ransac: CRegistration<PointT>::coarse_reg_ransac (cregistration.hpp:605-661), the solver between the key-point matcher
-// (ncc.cpp) and mulls_icp, on the device (k_ransac.hip).  Host side: argument checks, staging, PCL's sample sequence (sequential and cheap: a Mersenne
-// twister and three swaps per hypothesis), PCL's sequential "first best wins, stop at k" rule applied to the counts the device returns for every
+// (ncc.cpp) and mulls_icp, on the device (k_ransac.hip).  Host side: argument checks, staging (pair_stage.h), PCL's sample sequence (sequential and cheap: a
+// Mersenne twister and three swaps per hypothesis), PCL's sequential "first best wins, stop at k" rule applied to the counts the device returns for every
 // hypothesis, and the control flow of refineModel around one launch per round.  include/mulls_hip.h has the definition this file follows.
 // mulls_coarse_reg_ransac_batch runs the same steps for many problems in lock step: ransac_batch.h plans a sub-batch's arena, the k_rb_* kernels of
 // k_ransac.hip run each step for all its problems in one launch, and the refinement keeps one resumable control state (ransac_host.h) per problem.  The
-// three entry points share one argument checker, pass_through and finish_inliers.
-#include "ctx.h"
+// three entry points share one argument checker, the staging, pass_through and finish_inliers.
+// WHY THE HOST SEQUENCE IS WRITTEN TWICE (ransac_run, ransac_sub_batch): the single calls run as a sub-batch of one were built and measured against ransac_run
+// on one MI355X and were 1.4 to 5 % slower (6 to 32 us) on 15 of 33 rows, outside the parent's spread (profiles/ransac_single_as_batch.txt).  The kernel
+// trace there shows the solver's kernels level and 3.4 more runtime dispatches per call: the 64-byte winner record is zeroed by three fill kernels where the
+// single call's 4-byte count takes one, and the descriptor and job uploads run as copy kernels.  So ransac_run keeps its kernels with launch arguments; the two share the __device__ steps of k_ransac.hip and everything named above.
+#include "pair_stage.h"
 #include "ransac_host.h"
 #include "ransac_launch.h"
 
@@ -29,32 +33,6 @@ void mulls_ransac_release(mulls_ctx *ctx)
 
 namespace
 {
-bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
-{
-	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * MULLS_POINT_BYTES))
-		return true;
-	hipPointerAttribute_t at;
-	std::memset(&at, 0, sizeof(at));
-	if (hipPointerGetAttributes(&at, c.pts) == hipSuccess)
-		return at.type == hipMemoryTypeDevice;
-	(void)hipGetLastError(); // (an ordinary host pointer: the query reports an error on some runtimes — cleared)
-	return false;
-}
-
-// x, y, z, data[3] of the n pairs' points out of a host cloud
-void pack_xyzw(const mulls_cloud &c, const int32_t *idx, uint32_t n, float *out)
-{
-	const unsigned char *p = static_cast<const unsigned char *>(c.pts);
-	for (uint32_t i = 0; i < n; i++, out += 4)
-		std::memcpy(out, p + (size_t)(idx ? (uint32_t)idx[i] : i) * c.stride, 16);
-}
-
-void identity16(double T[16])
-{
-	for (int k = 0; k < 16; k++)
-		T[k] = (k % 5 == 0) ? 1.0 : 0.0;
-}
-
 static_assert(sizeof(RansacModel) == MULLS_RANSAC_MODEL_BYTES && sizeof(RansacRound) == MULLS_RANSAC_ROUND_BYTES, "ransac_batch.h plans with these sizes");
 
 void reset_result(mulls_ransac_result *result)
@@ -96,28 +74,6 @@ void finish_inliers(const uint8_t *hm, uint32_t n, int min_in, const RansacModel
 	}
 }
 
-struct BatchProblem // a problem that reaches the device
-{
-	uint32_t index, n;
-	bool indexed, t_dev, s_dev;
-};
-
-// who refuses: the entry point's name and, in a batch, the problem's index — mulls_last_error reads "<entry point>: [problem <b>: ]<why>"
-struct Refusal
-{
-	mulls_ctx *ctx;
-	const char *who;
-	int64_t problem; // -1: a single call
-
-	int operator()(int code, const char *why) const
-	{
-		ctx->err = std::string(who) + (problem >= 0 ? ": problem " + std::to_string(problem) : std::string()) + ": " + why;
-		return code;
-	}
-	// a refusal the single calls make without a message
-	int quiet(int code, const char *why) const { return problem >= 0 ? (*this)(code, why) : code; }
-};
-
 // A problem as it was handed in, before the device is touched, in the single call's order: the refusals, or its number of pairs; *runs = false below three
 // pairs (getSamples: "Can not select 3 unique points out of n"), the pass-through outcome.  indexed: the batch ABI infers it from the lists and wants both or
 // none; the indexed single call says so itself and reads no list when n_corr = 0.
@@ -147,17 +103,6 @@ int check_pairs(const Refusal &refuse, const mulls_ransac_problem &P, bool index
 	return MULLS_OK;
 }
 
-// ... and once the device is set, for a problem that runs: where its clouds lie, and their strides
-int check_strides(const Refusal &refuse, const mulls_ransac_problem &P, BatchProblem *A)
-{
-	const mulls_cloud &T = P.tgt, &S = P.src;
-	A->t_dev = cloud_on_device(refuse.ctx, T), A->s_dev = cloud_on_device(refuse.ctx, S);
-	if ((A->t_dev && T.stride != MULLS_POINT_BYTES) || (A->s_dev && S.stride != MULLS_POINT_BYTES) || (!A->t_dev && (T.stride < 16u || T.stride % 4u)) ||
-		(!A->s_dev && (S.stride < 16u || S.stride % 4u)))
-		return refuse(MULLS_E_INVALID, "stride (device clouds: 48; host clouds: a multiple of 4, at least 16)");
-	return MULLS_OK;
-}
-
 int ransac_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src_in, const int32_t *tgt_idx, const int32_t *src_idx, uint32_t n_corr,
 			   bool indexed, const mulls_ransac_params *params, mulls_ransac_result *result, int32_t *inliers, uint32_t cap)
 {
@@ -174,7 +119,6 @@ int ransac_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 	bool runs;
 	if (int rc = check_pairs(refuse, P, indexed, params, &A, &runs))
 		return rc;
-	const mulls_cloud &T = P.tgt, &S = P.src;
 	const uint32_t n = A.n;
 	const int min_in = params->min_inlier_num;
 	if (!runs)
@@ -184,9 +128,8 @@ int ransac_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 	}
 
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	if (int rc = check_strides(refuse, P, &A))
+	if (int rc = check_strides(refuse, P.tgt, P.src, &A))
 		return rc;
-	const bool t_dev = A.t_dev, s_dev = A.s_dev;
 	if (!ctx->ransac)
 		ctx->ransac = new mulls_ransac_scratch();
 	mulls_ransac_scratch &sc = *ctx->ransac;
@@ -198,7 +141,7 @@ int ransac_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 		return at;
 	};
 	const size_t o_src = take((size_t)n * 16u), o_tgt = take((size_t)n * 16u);
-	const size_t o_idx = take((size_t)n * 8u);
+	const size_t o_idx = take((size_t)n * 8u), o_jobs = take(2u * sizeof(PairGather));
 	const size_t o_tri = take((size_t)n_hyp_max * 12u), o_models = take((size_t)n_hyp_max * sizeof(RansacModel)), o_counts = take((size_t)n_hyp_max * 4u);
 	const size_t o_mask0 = take(n), o_mask1 = take(n), o_mask2 = take(n), o_d2 = take((size_t)n * 4u), o_round = take(sizeof(RansacRound)), o_cnt = take(4);
 	if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
@@ -209,7 +152,7 @@ int ransac_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 		poff += up256(bytes);
 		return at;
 	};
-	const size_t p_src = ptake((size_t)n * 16u), p_tgt = ptake((size_t)n * 16u), p_idx = ptake((size_t)n * 8u), p_tri = ptake((size_t)n_hyp_max * 12u);
+	const size_t p_src = ptake(2u * up256((size_t)n * 16u)), p_idx = ptake((size_t)n * 8u), p_jobs = ptake(2u * sizeof(PairGather)), p_tri = ptake((size_t)n_hyp_max * 12u);
 	const size_t p_counts = ptake((size_t)n_hyp_max * 4u), p_mask = ptake(n), p_round = ptake(sizeof(RansacRound)), p_model = ptake(sizeof(RansacModel)), p_cnt = ptake(4);
 	if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, poff, hipHostMallocDefault))
 		return rc;
@@ -219,31 +162,15 @@ int ransac_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 	float4 *src4 = reinterpret_cast<float4 *>(d + o_src), *tgt4 = reinterpret_cast<float4 *>(d + o_tgt);
 	float *h_src = reinterpret_cast<float *>(h + p_src);
 
-	// staging: host clouds are packed (and gathered) on the host and go up; device clouds are gathered on the device, the source's floats come down for the draws
-	if (indexed && (t_dev || s_dev))
+	// staging: a list of one (the source's and the target's points lie side by side in the arena and in its mirror); with a device-resident source the
+	// points come down again, for the draws
+	const PairStageItem item{&P.tgt, &P.src, tgt_idx, src_idx, n, indexed, A.t_dev, A.s_dev, o_src, o_tgt, o_idx};
+	if (int rc = stage_pairs(ctx, st, d, h, PairStagePlaces{o_src, o_idx - o_src, o_idx, o_jobs - o_idx, o_jobs, p_src, p_idx, p_jobs}, &item, 1))
+		return rc;
+	if (A.s_dev)
 	{
-		std::memcpy(h + p_idx, tgt_idx, (size_t)n * 4u);
-		std::memcpy(h + p_idx + (size_t)n * 4u, src_idx, (size_t)n * 4u);
-		HIPCHK(ctx, hipMemcpyAsync(d + o_idx, h + p_idx, (size_t)n * 8u, hipMemcpyHostToDevice, st));
-	}
-	const int32_t *d_tidx = indexed ? reinterpret_cast<const int32_t *>(d + o_idx) : nullptr, *d_sidx = indexed ? d_tidx + n : nullptr;
-	if (t_dev)
-		HIPCHK(ctx, launch_ransac_gather(st, T.pts, d_tidx, n, tgt4));
-	else
-	{
-		pack_xyzw(T, indexed ? tgt_idx : nullptr, n, reinterpret_cast<float *>(h + p_tgt));
-		HIPCHK(ctx, hipMemcpyAsync(tgt4, h + p_tgt, (size_t)n * 16u, hipMemcpyHostToDevice, st));
-	}
-	if (s_dev)
-	{
-		HIPCHK(ctx, launch_ransac_gather(st, S.pts, d_sidx, n, src4));
 		HIPCHK(ctx, hipMemcpyAsync(h_src, src4, (size_t)n * 16u, hipMemcpyDeviceToHost, st));
 		HIPCHK(ctx, hipStreamSynchronize(st));
-	}
-	else
-	{
-		pack_xyzw(S, indexed ? src_idx : nullptr, n, h_src);
-		HIPCHK(ctx, hipMemcpyAsync(src4, h_src, (size_t)n * 16u, hipMemcpyHostToDevice, st));
 	}
 
 	// the samples of every iteration the sequential loop can reach
@@ -327,8 +254,6 @@ int ransac_run(mulls_ctx *ctx, const mulls_cloud *tgt_in, const mulls_cloud *src
 }
 
 // ---- mulls_coarse_reg_ransac_batch
-const char *const BATCH = "mulls_coarse_reg_ransac_batch";
-
 // one sub-batch: `count` problems of three pairs or more whose arena fits the limit (or one that does not).  The host steps are ransac_run's, each for all
 // problems at once: one upload, one launch, one download and one wait where the single call makes its own.
 int ransac_sub_batch(mulls_ctx *ctx, const mulls_ransac_problem *problems, const BatchProblem *act, uint32_t count, const mulls_ransac_params *params,
@@ -356,41 +281,16 @@ int ransac_sub_batch(mulls_ctx *ctx, const mulls_ransac_problem *problems, const
 	};
 	const int min_in = params->min_inlier_num;
 
-	// staging: the host clouds packed into the pinned mirror of the points and up in one copy; device clouds gathered by one launch; with a device-resident
-	// source the points come down again in one copy, for the draws
-	RansacBatchGather *gathers = reinterpret_cast<RansacBatchGather *>(h + L.p_gather);
-	uint32_t n_gathers = 0;
-	bool any_host = false, any_idx = false;
+	// staging; with a device-resident source the points come down again in one copy, for the draws
+	std::vector<PairStageItem> items(count);
 	for (uint32_t k = 0; k < count; k++)
 	{
 		const mulls_ransac_problem &P = problems[act[k].index];
 		const RansacBatchDesc &D = L.desc[k];
-		const uint32_t n = D.n;
-		int32_t *h_idx = reinterpret_cast<int32_t *>(h + L.p_idx + (D.idx - L.o_idx));
-		if (act[k].indexed && (act[k].t_dev || act[k].s_dev))
-		{
-			std::memcpy(h_idx, P.tgt_idx, (size_t)n * 4u);
-			std::memcpy(h_idx + n, P.src_idx, (size_t)n * 4u);
-			any_idx = true;
-		}
-		if (act[k].t_dev)
-			gathers[n_gathers++] = RansacBatchGather{static_cast<const unsigned char *>(P.tgt.pts), D.idx, D.tgt, n, act[k].indexed ? 1u : 0u};
-		else
-			pack_xyzw(P.tgt, act[k].indexed ? P.tgt_idx : nullptr, n, reinterpret_cast<float *>(h + L.p_pts + (D.tgt - L.o_pts))), any_host = true;
-		if (act[k].s_dev)
-			gathers[n_gathers++] = RansacBatchGather{static_cast<const unsigned char *>(P.src.pts), D.idx + (uint64_t)n * 4u, D.src, n, act[k].indexed ? 1u : 0u};
-		else
-			pack_xyzw(P.src, act[k].indexed ? P.src_idx : nullptr, n, reinterpret_cast<float *>(h + L.p_pts + (D.src - L.o_pts))), any_host = true;
+		items[k] = PairStageItem{&P.tgt, &P.src, P.tgt_idx, P.src_idx, D.n, act[k].indexed, act[k].t_dev, act[k].s_dev, D.src, D.tgt, D.idx};
 	}
-	if (any_host) // (the places of device-resident clouds go up as they are and are gathered over below)
-		HIPCHK(ctx, hipMemcpyAsync(d + L.o_pts, h + L.p_pts, L.pts_bytes, hipMemcpyHostToDevice, st));
-	if (any_idx)
-		HIPCHK(ctx, hipMemcpyAsync(d + L.o_idx, h + L.p_idx, L.idx_bytes, hipMemcpyHostToDevice, st));
-	if (n_gathers)
-	{
-		HIPCHK(ctx, hipMemcpyAsync(d + L.o_gather, gathers, sizeof(RansacBatchGather) * n_gathers, hipMemcpyHostToDevice, st));
-		HIPCHK(ctx, launch_ransac_batch_gather(st, reinterpret_cast<const RansacBatchGather *>(d + L.o_gather), n_gathers, n_max, d));
-	}
+	if (int rc = stage_pairs(ctx, st, d, h, PairStagePlaces{L.o_pts, L.pts_bytes, L.o_idx, L.idx_bytes, L.o_gather, L.p_pts, L.p_idx, L.p_gather}, items.data(), count))
+		return rc;
 	if (any_s_dev)
 	{
 		HIPCHK(ctx, hipMemcpyAsync(h + L.p_pts, d + L.o_pts, L.pts_bytes, hipMemcpyDeviceToHost, st));
@@ -566,7 +466,7 @@ int ransac_batch_run(mulls_ctx *ctx, const mulls_ransac_problem *problems, uint3
 	for (uint32_t b = 0; b < n_problems; b++)
 	{
 		const mulls_ransac_problem &P = problems[b];
-		const Refusal refuse{ctx, BATCH, b};
+		const Refusal refuse{ctx, "mulls_coarse_reg_ransac_batch", b};
 		BatchProblem A;
 		bool runs;
 		A.index = b;
@@ -577,7 +477,7 @@ int ransac_batch_run(mulls_ctx *ctx, const mulls_ransac_problem *problems, uint3
 			few.push_back(A);
 			continue;
 		}
-		if (int rc = check_strides(refuse, P, &A))
+		if (int rc = check_strides(refuse, P.tgt, P.src, &A))
 			return rc;
 		act.push_back(A);
 	}
@@ -603,6 +503,7 @@ int ransac_batch_run(mulls_ctx *ctx, const mulls_ransac_problem *problems, uint3
 		}
 	return MULLS_OK;
 }
+
 } // namespace
 
 extern "C"

@@ -6,6 +6,7 @@
 
 #include <vector>
 
+#include "pair_gather.h"
 #include "subbatch.h"
 
 #define MULLS_RANSAC_MODEL_BYTES 48u // sizeof(RansacModel), sizeof(RansacRound): ransac.cpp asserts both (ransac_launch.h needs HIP's headers)
@@ -28,13 +29,8 @@ struct RansacBatchDesc
 	uint32_t mask_stride;
 };
 
-// a gather of a device-resident cloud into a problem's points: out[i] = x, y, z, data[3] of record idx[i] (i when not indexed)
-struct RansacBatchGather
-{
-	const unsigned char *recs; // the cloud: 48-byte records in device memory
-	uint64_t idx, out;		   // arena offsets: n int32 (read when indexed), n float4
-	uint32_t n, indexed;
-};
+// a gather job of a sub-batch is the solvers' shared one (pair_gather.h); the planner's name for it, which tests/ransac_batch_harness.cpp sizes the table with
+using RansacBatchGather = PairGather;
 
 // one workgroup of a refinement round: the problem, the buffers of its previous and next inlier set, its squared threshold
 struct RansacBatchJob

@@ -27,8 +27,6 @@ struct RansacRound
 	uint32_t n_prev;
 };
 
-// out[i] = the first four floats (x, y, z, data[3]) of record idx[i] (idx == NULL: i) of a device cloud of 48-byte records
-hipError_t launch_ransac_gather(hipStream_t st, const void *recs, const int32_t *idx, uint32_t n, float4 *out);
 // models[h] = the rigid transform of the three pairs triples[3h .. 3h + 2]
 hipError_t launch_ransac_models(hipStream_t st, const float4 *src, const float4 *tgt, const int32_t *triples, uint32_t n_hyp, RansacModel *models);
 // counts[h] = number of pairs within thresh (squared, double) of models[h]
@@ -43,7 +41,6 @@ hipError_t launch_ransac_refine(hipStream_t st, const float4 *src, const float4 
 
 // ---- mulls_coarse_reg_ransac_batch: the same steps for the `count` problems of a sub-batch, read from their descriptors (ransac_batch.h; device memory);
 // arena: the base the descriptors' offsets count from.  n_max / n_hyp_max: the largest problem's pairs / hypotheses (both above 0: a zero-sized grid is an error)
-hipError_t launch_ransac_batch_gather(hipStream_t st, const RansacBatchGather *jobs, uint32_t n_jobs, uint32_t n_max, unsigned char *arena);
 hipError_t launch_ransac_batch_models(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_hyp_max, unsigned char *arena);
 hipError_t launch_ransac_batch_score(hipStream_t st, const RansacBatchDesc *desc, uint32_t count, uint32_t n_hyp_max, unsigned char *arena, double thresh);
 // every problem's winner (desc[b].best): its mask into buffer 0, its model and count into win[b] (T, n_new; zeroed by the caller)

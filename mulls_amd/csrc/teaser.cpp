@@ -9,12 +9,11 @@
 // MI355X and was 1.2 to 2.1 % slower on every launch-bound row (profiles/teaser_kernel_stats.txt, section 5).  The cause was not isolated.  Supposed: the kernels of a
 // sub-batch read their pointers and sizes from a descriptor in device memory before their own data, in a GNC loop of 22 to 42 iterations of five launches;
 // the batch path's descriptor uploads, its memset and its planner vectors may have a share.
-// So teaser_run keeps launch arguments; what the two share is one kernel text (the __device__ steps of k_teaser.hip), the argument checker, the searches
-// and teaser_finish.
+// So teaser_run keeps launch arguments; what the two share is one kernel text (the __device__ steps of k_teaser.hip), the argument checker, the staging of
+// the pairs (pair_stage.h, shared with ransac.cpp: teaser_run stages a list of one), the searches and teaser_finish.
 #include <chrono>
 
-#include "ctx.h"
-#include "ransac_launch.h" // launch_ransac_gather: x, y, z, data[3] out of device records
+#include "pair_stage.h"
 #include "teaser_host.h"
 #include "teaser_launch.h"
 
@@ -42,25 +41,6 @@ void mulls_teaser_release(mulls_ctx *ctx)
 
 namespace
 {
-bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
-{
-	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * MULLS_POINT_BYTES))
-		return true;
-	hipPointerAttribute_t at;
-	std::memset(&at, 0, sizeof(at));
-	if (hipPointerGetAttributes(&at, c.pts) == hipSuccess)
-		return at.type == hipMemoryTypeDevice;
-	(void)hipGetLastError(); // (an ordinary host pointer: the query reports an error on some runtimes — cleared)
-	return false;
-}
-
-void pack_xyzw(const mulls_cloud &c, const int32_t *idx, uint32_t n, float *out)
-{
-	const unsigned char *p = static_cast<const unsigned char *>(c.pts);
-	for (uint32_t i = 0; i < n; i++, out += 4)
-		std::memcpy(out, p + (size_t)(idx ? (uint32_t)idx[i] : i) * c.stride, 16);
-}
-
 // The executor of teaser_search_control on the device: one k_teaser_clique launch and one readback of the shared words per step.  Every word a phase reads
 // is written at its beginning (the shared words and the workers' states; stacks and cliques are written before they are read), so nothing of an earlier
 // call or phase is seen.
@@ -246,29 +226,8 @@ void reset_result(mulls_teaser_result *result)
 {
 	std::memset(result, 0, sizeof(*result));
 	result->status = -1;
-	for (int k = 0; k < 16; k++)
-		result->T[k] = (k % 5 == 0) ? 1.0 : 0.0;
+	identity16(result->T);
 }
-
-struct BatchProblem // a problem that reaches the device
-{
-	uint32_t index, n;
-	bool indexed, t_dev, s_dev;
-};
-
-// who refuses: the entry point's name and, in a batch, the problem's index — mulls_last_error reads "<entry point>: [problem <b>: ]<why>"
-struct Refusal
-{
-	mulls_ctx *ctx;
-	const char *who;
-	int64_t problem; // -1: a single call
-
-	int operator()(int code, const char *why) const
-	{
-		ctx->err = std::string(who) + (problem >= 0 ? ": problem " + std::to_string(problem) : std::string()) + ": " + why;
-		return code;
-	}
-};
 
 // one mulls_teaser_params for a call
 int check_params(const Refusal &refuse, const mulls_teaser_params *params)
@@ -300,17 +259,6 @@ int check_pairs(const Refusal &refuse, const mulls_teaser_problem &P, bool index
 			if (P.tgt_idx[i] < 0 || (uint32_t)P.tgt_idx[i] >= T.n || P.src_idx[i] < 0 || (uint32_t)P.src_idx[i] >= S.n)
 				return refuse(MULLS_E_INVALID, "an index lies outside its cloud");
 	*runs = true;
-	return MULLS_OK;
-}
-
-// ... and once the device is set: where its clouds lie, and their strides
-int check_strides(const Refusal &refuse, const mulls_teaser_problem &P, BatchProblem *A)
-{
-	const mulls_cloud &T = P.tgt, &S = P.src;
-	A->t_dev = cloud_on_device(refuse.ctx, T), A->s_dev = cloud_on_device(refuse.ctx, S);
-	if ((A->t_dev && T.stride != MULLS_POINT_BYTES) || (A->s_dev && S.stride != MULLS_POINT_BYTES) || (!A->t_dev && (T.stride < 16u || T.stride % 4u)) ||
-		(!A->s_dev && (S.stride < 16u || S.stride % 4u)))
-		return refuse(MULLS_E_INVALID, "stride (device clouds: 48; host clouds: a multiple of 4, at least 16)");
 	return MULLS_OK;
 }
 
@@ -369,11 +317,9 @@ int teaser_run(mulls_ctx *ctx, const char *who, bool indexed_call, const mulls_c
 	if (!runs)
 		return MULLS_OK; // upstream's early returns: -1
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	if (int rc = check_strides(refuse, P, &A))
+	if (int rc = check_strides(refuse, P.tgt, P.src, &A))
 		return rc;
-	const mulls_cloud &T = P.tgt, &S = P.src;
 	const uint32_t n = A.n;
-	const bool indexed = A.indexed, t_dev = A.t_dev, s_dev = A.s_dev;
 	if (!ctx->teaser)
 		ctx->teaser = new mulls_teaser_scratch();
 	mulls_teaser_scratch &sc = *ctx->teaser;
@@ -386,7 +332,7 @@ int teaser_run(mulls_ctx *ctx, const char *who, bool indexed_call, const mulls_c
 		off += up256(bytes);
 		return at;
 	};
-	const size_t o_src = take((size_t)n * 16u), o_tgt = take((size_t)n * 16u), o_idx = take((size_t)n * 8u), o_adj = take(mat), o_sub = take(mat);
+	const size_t o_src = take((size_t)n * 16u), o_tgt = take((size_t)n * 16u), o_idx = take((size_t)n * 8u), o_jobs = take(2u * sizeof(PairGather)), o_adj = take(mat), o_sub = take(mat);
 	const size_t o_deg = take((size_t)n * 4u), o_cg = take((size_t)n * 8u), o_sum = take(8), o_keep = take((size_t)n * 4u);
 	const size_t o_cs = take((size_t)n * 16u), o_ct = take((size_t)n * 16u), o_part = take((size_t)9u * MULLS_TEASER_PARTIALS * 8u), o_S = take(sizeof(TeaserGnc));
 	size_t poff = 0;
@@ -395,7 +341,8 @@ int teaser_run(mulls_ctx *ctx, const char *who, bool indexed_call, const mulls_c
 		poff += up256(bytes);
 		return at;
 	};
-	const size_t p_src = ptake((size_t)n * 16u), p_tgt = ptake((size_t)n * 16u), p_idx = ptake((size_t)n * 8u), p_sub = ptake(mat), p_cg = ptake((size_t)n * 8u);
+	const size_t p_pts = ptake(2u * up256((size_t)n * 16u)), p_idx = ptake((size_t)n * 8u), p_jobs = ptake(2u * sizeof(PairGather)), p_sub = ptake(mat);
+	const size_t p_cg = ptake((size_t)n * 8u);
 	const size_t p_sum = ptake(8), p_keep = ptake((size_t)n * 4u), p_cs = ptake((size_t)n * 32u), p_S = ptake(sizeof(TeaserGnc));
 	const bool device_search = ctx->opt[MULLS_OPT_TEASER_DEVICE_SEARCH] != 0.0;
 	const SearchPlaces search(device_search, n, off, poff);
@@ -408,28 +355,10 @@ int teaser_run(mulls_ctx *ctx, const char *who, bool indexed_call, const mulls_c
 	mulls::StreamDrain drain{st};
 	float4 *src4 = reinterpret_cast<float4 *>(d + o_src), *tgt4 = reinterpret_cast<float4 *>(d + o_tgt);
 
-	// staging, as mulls_coarse_reg_ransac: host clouds are packed (and gathered) on the host and go up; device clouds are gathered on the device
-	if (indexed && (t_dev || s_dev))
-	{
-		std::memcpy(h + p_idx, tgt_idx, (size_t)n * 4u);
-		std::memcpy(h + p_idx + (size_t)n * 4u, src_idx, (size_t)n * 4u);
-		HIPCHK(ctx, hipMemcpyAsync(d + o_idx, h + p_idx, (size_t)n * 8u, hipMemcpyHostToDevice, st));
-	}
-	const int32_t *d_tidx = indexed ? reinterpret_cast<const int32_t *>(d + o_idx) : nullptr, *d_sidx = indexed ? d_tidx + n : nullptr;
-	if (t_dev)
-		HIPCHK(ctx, launch_ransac_gather(st, T.pts, d_tidx, n, tgt4));
-	else
-	{
-		pack_xyzw(T, indexed ? tgt_idx : nullptr, n, reinterpret_cast<float *>(h + p_tgt));
-		HIPCHK(ctx, hipMemcpyAsync(tgt4, h + p_tgt, (size_t)n * 16u, hipMemcpyHostToDevice, st));
-	}
-	if (s_dev)
-		HIPCHK(ctx, launch_ransac_gather(st, S.pts, d_sidx, n, src4));
-	else
-	{
-		pack_xyzw(S, indexed ? src_idx : nullptr, n, reinterpret_cast<float *>(h + p_src));
-		HIPCHK(ctx, hipMemcpyAsync(src4, h + p_src, (size_t)n * 16u, hipMemcpyHostToDevice, st));
-	}
+	// staging: a list of one (the source's and the target's points lie side by side in the arena and in its mirror)
+	const PairStageItem item{&P.tgt, &P.src, tgt_idx, src_idx, n, A.indexed, A.t_dev, A.s_dev, o_src, o_tgt, o_idx};
+	if (int rc = stage_pairs(ctx, st, d, h, PairStagePlaces{o_src, o_idx - o_src, o_idx, o_jobs - o_idx, o_jobs, p_pts, p_idx, p_jobs}, &item, 1))
+		return rc;
 
 	// the graph, its core numbers and the greedy clique sizes
 	const double nb = (double)params->noise_bound, beta = (2.0 * nb) * sqrt(1.0);
@@ -557,40 +486,16 @@ int teaser_sub_batch(mulls_ctx *ctx, const mulls_teaser_problem *problems, const
 		return hipMemcpyAsync(d + L.o_desc, h + L.p_desc, sizeof(TeaserBatchDesc) * count, hipMemcpyHostToDevice, st);
 	};
 
-	// staging: the host clouds packed into the pinned mirror of the points and up in one copy; device clouds gathered by one launch
-	TeaserBatchGather *jobs = reinterpret_cast<TeaserBatchGather *>(h + L.p_jobs);
-	uint32_t n_jobs = 0;
-	bool any_host = false, any_idx = false;
+	// staging
+	std::vector<PairStageItem> items(count);
 	for (uint32_t k = 0; k < count; k++)
 	{
 		const mulls_teaser_problem &P = problems[act[k].index];
 		const TeaserBatchDesc &D = L.desc[k];
-		const uint32_t n = D.n;
-		int32_t *h_idx = reinterpret_cast<int32_t *>(h + L.p_idx + (D.idx - L.o_idx));
-		if (act[k].indexed && (act[k].t_dev || act[k].s_dev))
-		{
-			std::memcpy(h_idx, P.tgt_idx, (size_t)n * 4u);
-			std::memcpy(h_idx + n, P.src_idx, (size_t)n * 4u);
-			any_idx = true;
-		}
-		if (act[k].t_dev)
-			jobs[n_jobs++] = TeaserBatchGather{static_cast<const unsigned char *>(P.tgt.pts), D.idx, D.tgt, n, act[k].indexed ? 1u : 0u};
-		else
-			pack_xyzw(P.tgt, act[k].indexed ? P.tgt_idx : nullptr, n, reinterpret_cast<float *>(h + L.p_pts + (D.tgt - L.o_pts))), any_host = true;
-		if (act[k].s_dev)
-			jobs[n_jobs++] = TeaserBatchGather{static_cast<const unsigned char *>(P.src.pts), D.idx + (uint64_t)n * 4u, D.src, n, act[k].indexed ? 1u : 0u};
-		else
-			pack_xyzw(P.src, act[k].indexed ? P.src_idx : nullptr, n, reinterpret_cast<float *>(h + L.p_pts + (D.src - L.o_pts))), any_host = true;
+		items[k] = PairStageItem{&P.tgt, &P.src, P.tgt_idx, P.src_idx, D.n, act[k].indexed, act[k].t_dev, act[k].s_dev, D.src, D.tgt, D.idx};
 	}
-	if (any_host) // (the places of device-resident clouds go up as they are and are gathered over below)
-		HIPCHK(ctx, hipMemcpyAsync(d + L.o_pts, h + L.p_pts, L.pts_bytes, hipMemcpyHostToDevice, st));
-	if (any_idx)
-		HIPCHK(ctx, hipMemcpyAsync(d + L.o_idx, h + L.p_idx, L.idx_bytes, hipMemcpyHostToDevice, st));
-	if (n_jobs)
-	{
-		HIPCHK(ctx, hipMemcpyAsync(d + L.o_jobs, jobs, sizeof(TeaserBatchGather) * n_jobs, hipMemcpyHostToDevice, st));
-		HIPCHK(ctx, launch_teaser_batch_gather(st, reinterpret_cast<const TeaserBatchGather *>(d + L.o_jobs), n_jobs, n_max, d));
-	}
+	if (int rc = stage_pairs(ctx, st, d, h, PairStagePlaces{L.o_pts, L.pts_bytes, L.o_idx, L.idx_bytes, L.o_jobs, L.p_pts, L.p_idx, L.p_jobs}, items.data(), count))
+		return rc;
 
 	// the graphs, their core numbers and the greedy clique sizes
 	const double nb = (double)params->noise_bound, beta = (2.0 * nb) * sqrt(1.0);
@@ -764,7 +669,7 @@ int teaser_batch_run(mulls_ctx *ctx, const mulls_teaser_problem *problems, uint3
 			return rc;
 		if (!runs)
 			continue;
-		if (int rc = check_strides(refuse, P, &A))
+		if (int rc = check_strides(refuse, P.tgt, P.src, &A))
 			return rc;
 		act.push_back(A);
 	}

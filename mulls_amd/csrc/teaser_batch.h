@@ -10,6 +10,7 @@
 
 #include <vector>
 
+#include "pair_gather.h"
 #include "subbatch.h"
 #include "teaser_math.h"
 
@@ -27,14 +28,6 @@ struct TeaserBatchDesc
 	uint64_t M;			  // C (C - 1) / 2
 	uint32_t n, W, m, Wm; // pairs, words per row; kept vertices, words per row of sub
 	uint32_t C, pad;	  // clique size (below 2: the problem never enters the GNC loop)
-};
-
-// a gather of a device-resident cloud into a problem's points: out[i] = x, y, z, data[3] of record idx[i] (i when not indexed)
-struct TeaserBatchGather
-{
-	const unsigned char *recs; // the cloud: 48-byte records in device memory
-	uint64_t idx, out;		   // arena offsets: n int32 (read when indexed), n float4
-	uint32_t n, indexed;
 };
 
 #define MULLS_TEASER_BATCH_MAX_PROBLEMS 16384u // problems of one sub-batch: a grid axis
@@ -76,7 +69,7 @@ inline void teaser_batch_layout(const uint32_t *n, uint32_t count, TeaserBatchLa
 		return at;
 	};
 	L->o_desc = table(sizeof(TeaserBatchDesc)), L->o_gnc = table(sizeof(TeaserGnc)), L->o_sum = table(8);
-	L->o_jobs = table(2u * sizeof(TeaserBatchGather)), L->o_frozen = table(4);
+	L->o_jobs = table(2u * sizeof(PairGather)), L->o_frozen = table(4);
 	off = up256(off); // (at most 512 bytes per problem)
 	auto region = [&](uint64_t TeaserBatchDesc::*field, uint64_t per_point, bool matrix, bool fixed) {
 		const uint64_t at = off;
@@ -117,7 +110,7 @@ inline void teaser_batch_layout(const uint32_t *n, uint32_t count, TeaserBatchLa
 		return at;
 	};
 	L->p_desc = mirror(sizeof(TeaserBatchDesc) * count), L->p_gnc = mirror(sizeof(TeaserGnc) * count), L->p_sum = mirror((uint64_t)8u * count);
-	L->p_jobs = mirror(2u * sizeof(TeaserBatchGather) * count);
+	L->p_jobs = mirror(2u * sizeof(PairGather) * count);
 	L->p_pts = mirror(L->pts_bytes), L->p_idx = mirror(L->idx_bytes), L->p_sub = mirror(L->o_deg - L->o_sub), L->p_core = mirror(L->core_bytes);
 	L->p_keep = mirror(L->keep_bytes), L->p_cpts = mirror(L->o_part - L->o_cpts);
 	L->pin_bytes = p;

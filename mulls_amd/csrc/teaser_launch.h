@@ -31,8 +31,6 @@ hipError_t launch_teaser_gnc_iteration(hipStream_t st, const float4 *cs, const f
 
 // ---- the same steps over the problems of one sub-batch of mulls_coarse_reg_teaser_batch per launch.  desc: the sub-batch's descriptor table in device memory
 // (teaser_batch.h), arena: the base its offsets count from.
-// the jobs' device-resident clouds into the points of their problems; n_max: the largest job
-hipError_t launch_teaser_batch_gather(hipStream_t st, const TeaserBatchGather *jobs, uint32_t n_jobs, uint32_t n_max, unsigned char *arena);
 // of every problem: the bit matrix, the degrees and deg_sum[b] (zeroed by the caller), the core numbers, the greedy clique sizes (behind the core numbers)
 hipError_t launch_teaser_batch_graph(hipStream_t st, const TeaserBatchDesc *desc, uint32_t B, uint32_t n_max, unsigned char *arena, double beta,
 									 unsigned long long *deg_sum);

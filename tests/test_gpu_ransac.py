@@ -131,6 +131,96 @@ def test_refusals(ctx_auto):
     assert_same(device(ctx_auto, t, s, bound, 100, 1), want, "after refusals")
 
 
+def test_single_entry_points_at_their_own_edges(ctx_auto):
+    """what only the single entry points define: the pass-through below three pairs (before the stride check, the indexed call with no pairs and NULL lists
+    among them), the refusals without a message (a NULL cloud, one index list without the other) next to a NULL result and a capacity without a buffer, the
+    order of two refusals — and the message of every refusal that sets one names the entry point that was called"""
+    L = lib.load()
+    t, s, bound, _ = input_sets()["half_517"]
+    rt, rs = rr.records(t), rr.records(s)
+    ct, cs = cloud_of(rt), cloud_of(rs)
+    good = abi.ransac_params(bound, 8, 100, 1)
+    res, inl = abi.RansacResult(), np.full(8, -7, np.int32)
+    ip = inl.ctypes.data_as(C.c_void_p)
+    idx = np.arange(517, dtype=np.int32)
+    eye = np.eye(4)
+
+    def vp(a):
+        return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+    def plain(a, b, P=good, result=res, inliers=ip, cap=4):
+        return L.mulls_coarse_reg_ransac(ctx_auto.h, C.byref(a), C.byref(b), C.byref(P), result, inliers, cap)
+
+    def indexed(ti, si, n, a=ct, b=cs, P=good, result=res, inliers=ip, cap=4):
+        return L.mulls_coarse_reg_ransac_indexed(ctx_auto.h, C.byref(a), C.byref(b), vp(ti), vp(si), n, C.byref(P), result, inliers, cap)
+
+    def T():
+        return np.array(res.T[:]).reshape(4, 4)
+
+    # the pass-through below three pairs
+    res.status, res.n_inliers = 5, 9
+    assert indexed(None, None, 0) == abi.MULLS_OK
+    assert res.status == -1 and res.n_inliers == 0 and res.best_iteration == -1 and np.array_equal(T(), eye) and (inl == -7).all()
+    for call in (lambda: indexed(idx, idx, 2, cap=1), lambda: plain(cloud_of(rt, n=2), cloud_of(rs, n=2), cap=1)):
+        inl[:] = -7
+        res.status, res.n_inliers = 5, 9
+        assert call() == abi.MULLS_OK
+        assert res.status == -1 and res.n_inliers == 2 and res.best_iteration == -1 and np.array_equal(T(), eye)
+        assert inl[0] == 0 and (inl[1:] == -7).all()  # one slot was offered
+    inl[:] = -7
+    odd = np.zeros((517, 18), np.uint8)
+    for n in (0, 1, 2):  # ... comes before the stride check
+        assert plain(cloud_of(odd, 18, n=n), cloud_of(rs, n=n), cap=0) == abi.MULLS_OK and res.n_inliers == n
+        assert indexed(idx, idx, n, a=cloud_of(odd, 18), cap=0) == abi.MULLS_OK and res.n_inliers == n
+
+    def said(who):
+        msg = L.mulls_last_error(ctx_auto.h) or b""
+        assert msg.startswith(who + b":") and b"problem" not in msg, msg
+
+    big, many, bad = np.zeros((65537, 48), np.uint8), np.zeros(65537, np.int32), idx.copy()
+    bad[100] = 517
+    inf, long_run = abi.ransac_params(float("inf"), 8, 100, 1), abi.ransac_params(bound, 8, (1 << 20) + 1, 1)
+    one, two = b"mulls_coarse_reg_ransac", b"mulls_coarse_reg_ransac_indexed"
+    for refuse, who, code in ((lambda: plain(ct, cs, P=inf), one, abi.MULLS_E_INVALID),
+                              (lambda: plain(ct, cloud_of(rs, n=516)), one, abi.MULLS_E_INVALID),
+                              (lambda: plain(cloud_of(big), cloud_of(big)), one, abi.MULLS_E_UNSUPPORTED),
+                              (lambda: plain(ct, cs, P=long_run), one, abi.MULLS_E_UNSUPPORTED),
+                              (lambda: plain(cloud_of(odd, 18), cs), one, abi.MULLS_E_INVALID),
+                              (lambda: plain(ct, cloud_of(odd, 18)), one, abi.MULLS_E_INVALID),
+                              (lambda: indexed(idx, idx, 517, P=inf), two, abi.MULLS_E_INVALID),
+                              (lambda: indexed(many, many, 65537), two, abi.MULLS_E_UNSUPPORTED),
+                              (lambda: indexed(idx, idx, 517, P=long_run), two, abi.MULLS_E_UNSUPPORTED),
+                              (lambda: indexed(idx, idx, 517, a=cloud_of(odd, 18)), two, abi.MULLS_E_INVALID),
+                              (lambda: indexed(bad, idx, 517), two, abi.MULLS_E_INVALID),
+                              (lambda: indexed(idx, bad, 517), two, abi.MULLS_E_INVALID)):
+        res.status, res.best_iteration, res.T[3] = 5, 7, 2.0
+        assert refuse() == code
+        said(who)
+        assert res.status == -1 and res.best_iteration == -1 and np.array_equal(T(), eye) and (inl == -7).all()
+
+    # the refusals without a message leave the last one standing
+    assert plain(ct, cs, P=inf) == abi.MULLS_E_INVALID
+    before = L.mulls_last_error(ctx_auto.h)
+    said(one)
+    gone = abi.Cloud()
+    gone.pts, gone.n, gone.stride = None, 517, 48
+    for quiet in (lambda: plain(gone, cs), lambda: plain(ct, gone), lambda: indexed(idx, idx, 517, a=gone), lambda: indexed(idx, None, 517),
+                  lambda: indexed(None, idx, 517)):
+        res.status = 5
+        assert quiet() == abi.MULLS_E_INVALID
+        assert L.mulls_last_error(ctx_auto.h) == before and res.status == -1 and (inl == -7).all()
+    assert plain(ct, cs, result=None) == abi.MULLS_E_INVALID and indexed(idx, idx, 517, result=None) == abi.MULLS_E_INVALID
+    assert plain(ct, cs, inliers=None) == abi.MULLS_E_INVALID and indexed(idx, idx, 517, inliers=None) == abi.MULLS_E_INVALID
+    assert L.mulls_last_error(ctx_auto.h) == before
+
+    # of two refusals the earlier one of the checks wins: unequal sizes come before too many iterations
+    assert plain(ct, cloud_of(rs, n=516), P=long_run) == abi.MULLS_E_INVALID
+    said(one)
+    want = fixture_case(fixture(), "half_517_i100_r1", 517)  # and the context goes on
+    assert_same(device(ctx_auto, t, s, bound, 100, 1), want, "after refusals")
+    assert_same(device(ctx_auto, t, s, bound, 100, 1, tgt_idx=idx, src_idx=idx), want, "after refusals, indexed")
+
+
 def strided(raw, stride, seed):
     n, w = len(raw), min(stride, 48)
     buf = np.random.default_rng(seed).integers(0, 256, (n, stride), dtype=np.uint8)

@@ -2,7 +2,9 @@
 warm-ups, for N in {517, 2840, 16384} pairs x max_iter_num in {2000, 20000}, refinement on and off.  The pairs carry 2 % planted inliers, so that the
 sequential rule runs to max_iter_num and every hypothesis the device scores is one the definition evaluates; a 50 % set shows the other end (the rule stops
 after tens of iterations, the device has scored max_iter_num + 1 all the same).  Printed next to the times: scored point transforms per second,
-(max_iter_num + 1) x N / wall.
+(max_iter_num + 1) x N / wall.  Behind these rows: 2 840 pairs with 40 % inliers and 12 cm of noise at the bound 0.3 (a refinement of several rounds), the demo
+scans' four key-point pair lists through mulls_coarse_reg_ransac_indexed (two of them on device-resident key points as well), and 65 536 pairs from host and
+from device-resident clouds.
 
     python tools/gpu_ransac.py                 the table
     python tools/gpu_ransac.py --calls 5       five calls per case and nothing else: the run to put under `rocprofv3 --kernel-trace --stats -- ...`
@@ -105,6 +107,23 @@ def batch_table(sizes, calls, batch_only):
     ctx.close()
 
 
+class DevBuf:
+    """records in device memory (the HIP runtime the library has loaded)"""
+
+    def __init__(self, raw):
+        self.hip = C.CDLL("libamdhip64.so")
+        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        self.raw, self.p = np.ascontiguousarray(raw), C.c_void_p()
+        assert self.hip.hipMalloc(C.byref(self.p), self.raw.nbytes) == 0
+        assert self.hip.hipMemcpy(self.p, C.c_void_p(self.raw.ctypes.data), self.raw.nbytes, 1) == 0
+
+    def cloud(self):
+        c = abi.Cloud()
+        c.pts, c.n, c.stride = self.p.value, len(self.raw), abi.POINT_BYTES
+        return c
+
+
 def main():
     calls = int(sys.argv[sys.argv.index("--calls") + 1]) if "--calls" in sys.argv else 0
     if "--batch" in sys.argv:
@@ -113,31 +132,58 @@ def main():
     L = ctx.lib
     res = abi.RansacResult()
     inl = np.zeros(65536, np.int32)
+    ip = inl.ctypes.data_as(C.c_void_p)
+
+    def row(label, ct, cs, P, n, lists=None):
+        """one row: 3 warm-up calls, then the median of 20 (with --calls: that many calls and nothing else)"""
+        def call():
+            t0 = time.perf_counter()
+            if lists is None:
+                rc = L.mulls_coarse_reg_ransac(ctx.h, C.byref(ct), C.byref(cs), C.byref(P), C.byref(res), ip, 65536)
+            else:
+                rc = L.mulls_coarse_reg_ransac_indexed(ctx.h, C.byref(ct), C.byref(cs), lists[0].ctypes.data_as(C.c_void_p), lists[1].ctypes.data_as(C.c_void_p), n,
+                                                       C.byref(P), C.byref(res), ip, 65536)
+            dt = time.perf_counter() - t0
+            assert rc == 0, (rc, L.mulls_last_error(ctx.h))
+            return dt
+
+        if calls:
+            for _ in range(calls):
+                call()
+            return
+        for _ in range(3):
+            call()
+        ts = sorted(call() for _ in range(20))
+        print("%-58s  max_iter %6d  refine %d  status %2d  iterations %6d  refine rounds %d  n_inliers %6d  median %8.3f ms  (min %.3f, max %.3f)"
+              "  %7.2f G point transforms/s" % (label, P.max_iter_num, P.refine, res.status, res.iterations, res.refine_iterations, res.n_inliers, ts[10] * 1e3,
+                                                ts[0] * 1e3, ts[-1] * 1e3, (P.max_iter_num + 1) * n / ts[10] * 1e-9), flush=True)
+
     for ratio in (0.02, 0.5):
         for n in (517, 2840, 16384):
             t, s = planted(100 + n, n, ratio)
-            ct, cs = cloud(t), cloud(s)
             for max_iter in (2000, 20000):
                 for refine in (0, 1):
-                    P = abi.ransac_params(0.5, 8, max_iter, refine)
-
-                    def call():
-                        t0 = time.perf_counter()
-                        rc = L.mulls_coarse_reg_ransac(ctx.h, C.byref(ct), C.byref(cs), C.byref(P), C.byref(res), inl.ctypes.data_as(C.c_void_p), 65536)
-                        dt = time.perf_counter() - t0
-                        assert rc == 0, (rc, L.mulls_last_error(ctx.h))
-                        return dt
-
-                    if calls:
-                        for _ in range(calls):
-                            call()
-                        continue
-                    for _ in range(3):
-                        call()
-                    ts = sorted(call() for _ in range(20))
-                    print("inliers %4.0f %%  N %6d  max_iter %6d  refine %d  status %2d  iterations %6d  refine rounds %d  n_inliers %6d  median %8.3f ms  (min %.3f, max %.3f)"
-                          "  %7.2f G point transforms/s" % (100 * ratio, n, max_iter, refine, res.status, res.iterations, res.refine_iterations, res.n_inliers, ts[10] * 1e3,
-                                                            ts[0] * 1e3, ts[-1] * 1e3, (max_iter + 1) * n / ts[10] * 1e-9))
+                    row("inliers %2.0f %%  N %6d" % (100 * ratio, n), cloud(t), cloud(s), abi.ransac_params(0.5, 8, max_iter, refine), n)
+    # refinements of several rounds: the first synthetic set of --batch
+    t, s = planted(200, 2840, 0.4, sigma=0.12)
+    row("inliers 40 %  N   2840  sigma 0.12  bound 0.3", cloud(t), cloud(s), abi.ransac_params(0.3, 8, 20000, 1), 2840)
+    # the demo scans' key-point pair lists through the indexed entry point, on host and on device-resident key points
+    Z = np.load(os.path.join(ROOT, "tests", "golden", "ncc_demo.npz"))
+    kt, ks = np.ascontiguousarray(Z["kpts_0"]), np.ascontiguousarray(Z["kpts_15"])
+    dkt, dks = DevBuf(kt), DevBuf(ks)
+    P = abi.ransac_params(1.0, 8, 20000, 1)
+    for name in ("recip_0_15", "nn_0_15", "fixed2000_0_15", "fixed300_0_15"):
+        pr = np.ascontiguousarray(Z[name + "_pairs"], np.int32)
+        lists = (np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1]))
+        row("demo %-14s  N %6d  indexed, host key points" % (name, len(pr)), cloud(kt), cloud(ks), P, len(pr), lists)
+        if name in ("nn_0_15", "fixed300_0_15"):
+            row("demo %-14s  N %6d  indexed, device key points" % (name, len(pr)), dkt.cloud(), dks.cloud(), P, len(pr), lists)
+    # the largest problem: three masks come down, and with a device-resident source both point arrays
+    t, s = planted(100 + 65536, 65536, 0.5)
+    dt, ds = DevBuf(t), DevBuf(s)
+    P = abi.ransac_params(0.5, 8, 100, 1)
+    row("inliers 50 %  N  65536  host clouds", cloud(t), cloud(s), P, 65536)
+    row("inliers 50 %  N  65536  device clouds", dt.cloud(), ds.cloud(), P, 65536)
     ctx.close()
 
 

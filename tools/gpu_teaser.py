@@ -1,7 +1,7 @@
 """The TEASER coarse-registration solver (mulls_coarse_reg_teaser_indexed) timed on the device: wall time per call, host key points and index lists in to
 result out, median of 20 after 2 warm-ups (3 calls, the first among them, where one call takes more than a second: the host clique search is the whole of it), on the
 demo scans' key-point pair lists of 517, 294, 1 543 and 2 840 pairs (tests/golden/ncc_demo.npz) at the noise bounds 0.25 and 1.0, and on 4 000 random pairs
-with 5 % planted inliers.  The host clique search's time is reported on its own (result.search_seconds), and mulls_coarse_reg_ransac_indexed on the same
+with 5 % planted inliers; one row takes the key points from device memory ("dev").  The host clique search's time is reported on its own (result.search_seconds), and mulls_coarse_reg_ransac_indexed on the same
 pairs next to it.  The search is given --budget nodes (default 2^20, so that a timing run ends; the library's default is 2^28).
 
     python tools/gpu_teaser.py                 the table
@@ -137,6 +137,12 @@ def main():
             cases.append((name, nb, Z["kpts_%d" % a], Z["kpts_%d" % b], pr[:, 0], pr[:, 1]))
     ctx = lib.Context(0)
     ctx.set_option(abi.OPT_TEASER_DEVICE_SEARCH, 1 if search == "device" else 0)
+    if not only:  # one pair list on device-resident key points: the gather runs on the device
+        from gpu_ransac import DevBuf
+
+        pr = Z["recip_0_15_pairs"]
+        resident = DevBuf(np.ascontiguousarray(Z["kpts_0"])), DevBuf(np.ascontiguousarray(Z["kpts_15"]))
+        cases.append(("recip_0_15 dev", 0.25, resident[0].cloud(), resident[1].cloud(), pr[:, 0], pr[:, 1]))
     for name, nb, kt, ks, ti, si in cases:
         P = abi.teaser_params(nb, 8, budget)
         if search == "both":
