@@ -636,14 +636,17 @@ int mulls_block_download(mulls_ctx *ctx, const mulls_block *block, int which, vo
  *              classification, more than 500 000 points — leaves its block with all sizes zero and disturbs no other scan); path; n_out
  *   stats      optional (may be NULL)
  * Within a sub-batch every device step runs once for all scans (one launch whose workgroups find their scan in a table in device memory) and every host
- * wait of the single path happens once; both fixed-point loops run in lock step until no scan has an undecided point.  Two parameter points are handed scan
- * by scan to the single-scan path inside the call (path = 1, the same bits): vf_downsample_resolution >= 0.001 (its cost is a host sort per scan either way)
- * and estimate_ground_normal_method 1 / 2 (their own neighbour grid and error word).  Everything else runs in lock step (path = 0).
+ * wait of a scan's chain happens once; both fixed-point loops run in lock step until no scan has an undecided point.  Two steps have no lock-step form and
+ * run scan-locally: voxel_downsample (vf_downsample_resolution >= 0.001: a host sort per scan either way) and the ground normals of
+ * estimate_ground_normal_method 1 / 2 (their own neighbour grid and error word).  With either, and with parameters every scan is refused for, each scan is
+ * a sub-batch of its own, whatever the limit: the same code and the same bits, one scan at a time (path = 1; these scans count in n_single_path and in
+ * nothing else of the statistics).  Everything else runs in lock step (path = 0).  The single calls (mulls_extract_features, _resident, mulls_ground_filter,
+ * mulls_classify_nground) are this chain, or one stage of it, on a batch of one.
  * Returns the status of the lowest-index scan whose status is not MULLS_OK (mulls_last_error names it), else MULLS_OK; n_scans == 0: MULLS_OK. */
 typedef struct mulls_extract_batch_result
 {
 	int32_t status;					/* this scan's code: what its single call returns */
-	uint32_t path;					/* 0 = ran in lock step, 1 = handed to the single-scan path */
+	uint32_t path;					/* 0 = ran in lock step, 1 = ran alone, with the two scan-local steps */
 	uint32_t n_out[MULLS_EX_COUNT];
 } mulls_extract_batch_result;
 typedef struct mulls_extract_batch_stats

@@ -56,11 +56,8 @@ struct ClParams // classify parameters as the kernels use them
 	int32_t min_neighbor_feature_pts;
 };
 
+// the direct-argument forms other code still calls: the search grid of one cloud (k_ground_normals.hip), the suppression and the gather (nms.cpp, vox_run)
 void launch_cl_grid(hipStream_t st, const ClArrays &A, const ClParams &P);
-void launch_cl_pca(hipStream_t st, const ClArrays &A, const ClParams &P);
-void launch_cl_label(hipStream_t st, const ClArrays &A, const ClParams &P);
-void launch_cl_promote_round(hipStream_t st, const ClArrays &A, const ClParams &P, uint32_t round);
-void launch_cl_encode_and_masks(hipStream_t st, const ClArrays &A, const ClParams &P);
 
 #define MULLS_CL_NMS_CAP 32u
 struct ClNmsArgs
@@ -79,12 +76,10 @@ struct ClNmsArgs
 };
 void launch_cl_nms_lists(hipStream_t st, const ClNmsArgs &a, uint32_t *round_cnt); // round_cnt: 64 counters, zeroed here with the lists' own arrays
 void launch_cl_nms_round(hipStream_t st, const ClNmsArgs &a, uint32_t *round_cnt); // *round_cnt += points still undecided
-// keys[i] = normal[3] of record i
-void launch_cl_keys(hipStream_t st, const float4 *recs, uint32_t n, float *keys);
 // out[i] = in[perm[i]], whole 48-byte records
 void launch_cl_gather(hipStream_t st, const float4 *in, const uint32_t *perm, float4 *out, uint32_t n);
 
-// ---- mulls_extract_features_batch: the same kernels for many scans per launch -------------------------------------------------------------------
+// ---- the table forms: the kernels for many scans per launch (extract_batch.cpp; a single call is a table of one) -------------------------------------------------------------------
 // One scan of a lock-step launch (a table entry in device memory, found at blockIdx.y); n == 0: the scan takes no part.
 struct ClScan
 {

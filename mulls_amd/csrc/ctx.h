@@ -76,22 +76,17 @@ struct mulls_ctx
 	mulls_batch *scratch = nullptr; // cached batch reused by mulls_icp / mulls_icp_batch (no allocator traffic per call)
 	std::vector<mulls_map *> maps; // live local maps: their buffers are the device clouds mulls_pair may point to
 	std::vector<mulls_block *> blocks; // live feature blocks (mulls_extract_features_resident): device clouds too
-	void *gf_buf = nullptr; // mulls_ground_filter's device arena (grow-only)
-	void *gf_rnd = nullptr; // ... and PCL's RANSAC sample sequence (normal method 3), made on first use
-	void *cl_buf = nullptr; // mulls_classify_nground's device arena (grow-only)
-	size_t cl_cap = 0;
-	size_t gf_cap = 0;
+	void *gf_rnd = nullptr; // PCL's RANSAC sample sequence (ground normal method 3), made on first use
 	double opt[MULLS_OPT_COUNT] = {}; // enum mulls_option (mulls_set_option; preset from the environment by mulls_create)
 	unsigned char *mail_h = nullptr; // host-mapped mailbox of the small-table uploads (SegCopier, batch.h): written by the host, read by k_copy_segs
 	size_t mail_cap = 0;
-	unsigned char *cl_pin = nullptr, *scan_pin = nullptr; // pinned host scratch of the feature stage: the visiting orders' keys and permutations; the raw scan on its way up
-	size_t cl_pin_cap = 0, scan_pin_cap = 0;
-	void *exb_buf = nullptr; // mulls_extract_features_batch's device arena of one sub-batch (grow-only; gf_buf and cl_buf stay the single calls')
+	unsigned char *scan_pin = nullptr; // pinned host scratch of the feature stage: the raw scan on its way up
+	size_t scan_pin_cap = 0;
+	void *exb_buf = nullptr; // the feature stage's device arena of one sub-batch (extract_batch.cpp; grow-only; a single call is a sub-batch of one scan)
 	size_t exb_cap = 0;
 	unsigned char *exb_tab_pin = nullptr, *exb_pin = nullptr; // ... its pinned scratch: the tables on their way up; the words, keys, orders and records that cross (host-mapped)
 	size_t exb_tab_pin_cap = 0, exb_pin_cap = 0;
-	uint32_t exb_rounds_hint[2] = {4, 8}; // ... and its two round loops' lengths in the previous call
-	uint32_t cl_rounds_hint[2] = {4, 8}; // rounds the promotion loop / the suppression rounds needed in the previous call: this call's first batch
+	uint32_t exb_rounds_hint[2] = {4, 8}; // ... and rounds the promotion loop / the suppression rounds needed in the previous call: this call's first batch
 	mulls_ncc_scratch *ncc = nullptr; // mulls_ncc_correspond's device arena and pinned buffer (ncc.cpp; grow-only)
 	mulls_ransac_scratch *ransac = nullptr; // mulls_coarse_reg_ransac's (ransac.cpp; grow-only)
 	mulls_teaser_scratch *teaser = nullptr; // mulls_coarse_reg_teaser's (teaser.cpp; grow-only)
@@ -288,16 +283,4 @@ struct mulls_block
 	size_t cap = 0;					 // bytes
 	size_t off[MULLS_EX_COUNT] = {}; // where cloud k starts
 	uint32_t n[MULLS_EX_COUNT] = {}; // its size (RAW and DOWN are not kept: 0)
-};
-
-// classify_nground_pts' clouds where the kernels left them (mulls_classify_impl with a ClassifyDev instead of host buffers): valid until the
-// context's next classification; the *_down clouds the fixed-number samplers thin on the host come back as host records
-struct ClassifyDev
-{
-	const void *dev[MULLS_CL_COUNT] = {};
-	uint32_t n[MULLS_CL_COUNT] = {};
-	std::vector<unsigned char> host[MULLS_CL_COUNT]; // non-empty: this cloud's records are here instead
-	bool on_host[MULLS_CL_COUNT] = {};
-	const void *cloud_in_after = nullptr; // cloud_in as upstream leaves it (device)
-	uint32_t n_after = 0;
 };

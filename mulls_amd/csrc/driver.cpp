@@ -246,12 +246,8 @@ extern "C"
 		if (!ctx)
 			return;
 		(void)hipSetDevice(ctx->device);
-		if (ctx->gf_buf)
-			(void)hipFree(ctx->gf_buf);
 		if (ctx->gf_rnd)
 			(void)hipFree(ctx->gf_rnd);
-		if (ctx->cl_buf)
-			(void)hipFree(ctx->cl_buf);
 		if (ctx->scratch)
 			mulls_batch_destroy(ctx, ctx->scratch);
 		if (ctx->mail_h)
@@ -262,8 +258,6 @@ extern "C"
 			(void)hipHostFree(ctx->exb_tab_pin);
 		if (ctx->exb_pin)
 			(void)hipHostFree(ctx->exb_pin);
-		if (ctx->cl_pin)
-			(void)hipHostFree(ctx->cl_pin);
 		if (ctx->scan_pin)
 			(void)hipHostFree(ctx->scan_pin);
 		mulls_ncc_release(ctx);

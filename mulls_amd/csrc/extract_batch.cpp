@@ -1,11 +1,13 @@
-// extract_batch.cpp — host side of mulls_extract_features_batch (include/mulls_hip.h): extract_impl's chain (ground.cpp) and
-// mulls_classify_impl's (classify.cpp) for many scans per call.  A sub-batch's scans lie side by side in one arena (extract_batch.h: every scan gets the
-// regions its single call carves); every device step is ONE launch over a table with one entry per scan (the *_batch launchers of k_ground.hip,
-// k_classify.hip, map_kernels.hip), every copy or fill the single path issues per array is one range of a k_ex_segs launch, and every host wait of the
-// single path happens once per sub-batch:
+// extract_batch.cpp — the host chain of the feature stage (include/mulls_hip.h): extract_semantic_pts' scanner / distance filter ->
+// voxel_downsample -> fast_ground_filter -> classify_nground_pts for many scans per call, and every single call as a batch of one (mulls_extract_features,
+// mulls_extract_features_resident, mulls_ground_filter, mulls_classify_nground: the whole chain or one stage of it).  A sub-batch's scans lie side by side in
+// one arena (extract_batch.h: a ground region and a classify region per scan); every device step is ONE launch over a table with one entry per scan (the
+// *_batch launchers of k_ground.hip, k_classify.hip, map_kernels.hip), every copy or fill per array is one range of a k_ex_segs launch, and every host wait
+// happens once per sub-batch:
 //   1 sizes after the pre-filter   2 GfOut   3 (thinning masks up)   4 promotion rounds   5 class counts, non-finite flag   6 keys down, orders up
 //   7 suppression rounds           8 *_down sizes (and the clouds the host thins)          9 block placement
-// What the host decides per scan — thin_mask, std::sort's visiting orders, the sector samplers — is the single path's code on the single path's inputs.
+// What the host decides per scan — thin_mask, std::sort's visiting orders, the sector samplers — sees that scan's data only.  The two steps without a table
+// form (vox_run, launch_ground_normals) run scan-locally in sub-batches of one scan.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -39,7 +41,7 @@ struct ScanState
 	std::string err;
 	bool live = false; // still part of the lock step
 	GfArena a;
-	unsigned char *gf = nullptr, *cl = nullptr, *cur = nullptr, *other = nullptr;
+	unsigned char *gf = nullptr, *cl = nullptr, *cur = nullptr, *other = nullptr, *ug = nullptr; // the two regions; the scan ahead of the ground filter; the non-ground cloud
 	GfOut go = {};
 	uint32_t n_ug = 0, n_cl = 0; // non-ground points; those the classification works on
 	bool classify = false;		 // n_cl > 0
@@ -51,7 +53,22 @@ struct ScanState
 	Bytes host[MULLS_CL_COUNT];
 	bool on_host[MULLS_CL_COUNT] = {};
 	std::vector<uint32_t> gd_idx;
+	// the nine clouds of the classification in MULLS_CL_* order: where the kernels left them (host[k] instead where on_host[k]) and their sizes
+	void clouds(const float4 *dev[MULLS_CL_COUNT], uint32_t cnt[MULLS_CL_COUNT]) const
+	{
+		for (int c = 0; c < 4; c++)
+			dev[c] = cls[c], cnt[c] = ncls[c], dev[4 + c] = L.down[c], cnt[4 + c] = ndown[c];
+		dev[MULLS_CL_VERTEX] = L.vertex, cnt[MULLS_CL_VERTEX] = nvertex;
+	}
 };
+
+#define EXCHK(call)            \
+	do                         \
+	{                          \
+		const int rc_ = (call); \
+		if (rc_ != MULLS_OK)   \
+			return rc_;        \
+	} while (0)
 
 // the tables and byte ranges of one sub-batch on their way to the device, and the statistics
 struct Run
@@ -59,6 +76,7 @@ struct Run
 	mulls_ctx *ctx;
 	hipStream_t st;
 	mulls_extract_batch_stats *S;
+	const char *who; // the entry point's name for its messages (the round loops of a single call are mulls_classify_nground's)
 	unsigned char *tab_dev = nullptr; // device table area (inside the arena), mirrored by ctx->exb_tab_pin
 	size_t tab_cap = 0, tab_off = 0;
 	unsigned char *pin_dev = nullptr; // device address of ctx->exb_pin
@@ -66,6 +84,12 @@ struct Run
 	std::vector<ExSeg> segs;
 	uint32_t seg_max = 0;
 
+	const char *msg(const char *what)
+	{
+		text = std::string(who) + ": " + what;
+		return text.c_str();
+	}
+	std::string text;
 	// a table to the device (one copy command); nullptr: failed
 	template <typename T>
 	const T *upload(const std::vector<T> &v)
@@ -74,13 +98,13 @@ struct Run
 		tab_off = (tab_off + 63u) & ~(size_t)63u;
 		if (tab_off + bytes > tab_cap)
 		{
-			ctx->err = "mulls_extract_features_batch: table area exhausted";
+			ctx->err = msg("table area exhausted");
 			return nullptr;
 		}
 		std::memcpy(ctx->exb_tab_pin + tab_off, v.data(), bytes);
 		if (hipMemcpyAsync(tab_dev + tab_off, ctx->exb_tab_pin + tab_off, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
 		{
-			ctx->err = "mulls_extract_features_batch: table upload failed";
+			ctx->err = msg("table upload failed");
 			return nullptr;
 		}
 		const T *p = reinterpret_cast<const T *>(tab_dev + tab_off);
@@ -90,15 +114,7 @@ struct Run
 	// the pinned scratch holds `bytes` from its start (called with the stream idle)
 	int pin_reserve(size_t bytes)
 	{
-		if (ctx->exb_pin_cap < bytes)
-		{
-			if (ctx->exb_pin)
-				(void)hipHostFree(ctx->exb_pin);
-			ctx->exb_pin = nullptr, ctx->exb_pin_cap = 0;
-			const size_t want = bytes + bytes / 4 + 4096;
-			HIPCHK(ctx, hipHostMalloc((void **)&ctx->exb_pin, want, hipHostMallocMapped));
-			ctx->exb_pin_cap = want;
-		}
+		EXCHK(grow_pinned(ctx, &ctx->exb_pin, &ctx->exb_pin_cap, bytes, hipHostMallocMapped));
 		HIPCHK(ctx, hipHostGetDevicePointer((void **)&pin_dev, ctx->exb_pin, 0));
 		return MULLS_OK;
 	}
@@ -138,47 +154,93 @@ struct Run
 	}
 };
 
-#define EXCHK(call)            \
-	do                         \
-	{                          \
-		const int rc_ = (call); \
-		if (rc_ != MULLS_OK)   \
-			return rc_;        \
-	} while (0)
-
-// one sub-batch: the scans first .. last of `sc` whose `live` is set, in lock step
-int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X, mulls_block *const *blocks, mulls_extract_batch_result *results, std::vector<ScanState> &sc,
-				 uint32_t first, uint32_t last, const ScanRegion *reg, uint64_t arena_bytes)
+// which part of the chain a run of the core covers
+enum Part
 {
-	mulls_ctx *ctx = R.ctx;
-	hipStream_t st = R.st;
-	mulls_extract_batch_stats &S = *R.S;
-	const mulls_ground_params *P = &X->ground;
-	const mulls_classify_params *C = &X->classify;
-	const uint32_t m = last - first;
-	const bool scanner = X->apply_scanner_filter != 0, dist = X->apply_dist_filter != 0, prefilter = scanner || dist;
-	// ---- the arena and the tables -----------------------------------------------------------------------------------------------------------
-	if (ctx->exb_cap < arena_bytes)
+	EX_ALL,		// scans -> blocks (mulls_extract_features_batch, mulls_extract_features, mulls_extract_features_resident)
+	EX_GROUND,	// scan -> ground / non-ground in the scan's region (mulls_ground_filter)
+	EX_CLASSIFY // a cloud in the scan's region -> its class clouds, where the kernels leave them (mulls_classify_nground)
+};
+// where a one-scan run leaves the two clouds no block keeps (mulls_extract_features)
+struct HostSinks
+{
+	void *raw, *down;
+	uint32_t cap_raw, cap_down;
+};
+
+// voxel_downsample (vox_run: a host sort) and the ground normals of methods 1 and 2 (their own neighbour grid and error word) have no table form
+bool scan_local_steps(const mulls_extract_params *X, const mulls_ground_params *P)
+{
+	return (X && !(X->vf_downsample_resolution < 0.001)) || (P && (P->estimate_ground_normal_method == 1 || P->estimate_ground_normal_method == 2));
+}
+
+// The lock step: the scans of `sc` whose `live` is set, one sub-batch after the other.  The checks of a scan's size and parameters are the entry point's.
+struct Core
+{
+	Run R;
+	Part part;
+	const mulls_cloud *scans;
+	const mulls_extract_params *X; // EX_ALL only
+	const mulls_ground_params *P;
+	const mulls_classify_params *C;
+	mulls_block *const *blocks;
+	mulls_extract_batch_result *results;
+	std::vector<ScanState> &sc;
+	const HostSinks *sinks; // one scan only, or null
+	mulls_ctx *ctx;
+	hipStream_t st;
+	mulls_extract_batch_stats &S;
+	bool scanner, dist, prefilter, voxels;
+	bool alone; // every scan a sub-batch of its own: the two steps without a table form run scan-locally
+	// of the sub-batch under way
+	uint32_t first = 0, last = 0, m = 0;
+	unsigned char *arena = nullptr;
+	uint32_t *d_round = nullptr; // 64 counters of the round loops, shared by the scans
+	size_t words_bytes = 0;		 // a row of 64 words per scan: what every wait reads
+
+	Core(mulls_ctx *c, const char *who, mulls_extract_batch_stats *stats, Part part_, const mulls_cloud *scans_, const mulls_extract_params *X_, const mulls_ground_params *P_,
+		 const mulls_classify_params *C_, mulls_block *const *blocks_, mulls_extract_batch_result *results_, std::vector<ScanState> &sc_, const HostSinks *sinks_ = nullptr)
+		: R{c, c->stream, stats, who}, part(part_), scans(scans_), X(X_), P(P_), C(C_), blocks(blocks_), results(results_), sc(sc_), sinks(sinks_), ctx(c), st(c->stream), S(*stats)
 	{
-		if (ctx->exb_buf)
-			(void)hipFree(ctx->exb_buf);
-		ctx->exb_buf = nullptr, ctx->exb_cap = 0;
-		HIPCHK(ctx, hipMalloc(&ctx->exb_buf, arena_bytes));
-		ctx->exb_cap = arena_bytes;
+		scanner = X && X->apply_scanner_filter != 0, dist = X && X->apply_dist_filter != 0, prefilter = scanner || dist;
+		voxels = X && !(X->vf_downsample_resolution < 0.001); // voxel_downsample hands the cloud on below 0.001 m (:90-97)
+		alone = scan_local_steps(X, P);
 	}
-	unsigned char *arena = static_cast<unsigned char *>(ctx->exb_buf);
-	uint32_t *d_round = reinterpret_cast<uint32_t *>(arena); // 64 counters of the round loops, shared by the scans
+	uint32_t *words_of(uint32_t s) const { return reinterpret_cast<uint32_t *>(ctx->exb_pin) + (size_t)(s - first) * 64; }
+	int method() const { return P ? P->estimate_ground_normal_method : 0; }
+
+	int begin(uint32_t first_, uint32_t last_, uint64_t arena_bytes, uint64_t limit);
+	int upload(const ScanRegion *reg);
+	int prefilter_stage();
+	int ground_stage();
+	int classify_stage();
+	int place();
+	int run(uint32_t n_scans, uint64_t limit);
+};
+
+// ---- the arena and the tables -----------------------------------------------------------------------------------------------------------
+int Core::begin(uint32_t first_, uint32_t last_, uint64_t arena_bytes, uint64_t limit)
+{
+	first = first_, last = last_, m = last - first;
+	EXCHK(ex_arena_reserve(ctx, arena_bytes, limit));
+	arena = static_cast<unsigned char *>(ctx->exb_buf);
+	d_round = reinterpret_cast<uint32_t *>(arena);
 	R.tab_dev = arena + MULLS_EXB_HEAD_BYTES, R.tab_cap = (size_t)MULLS_EXB_TABLE_BYTES * m, R.tab_off = 0;
 	if (grow_pinned(ctx, &ctx->exb_tab_pin, &ctx->exb_tab_pin_cap, R.tab_cap, hipHostMallocDefault) != MULLS_OK)
 		return MULLS_E_HIP;
-	const size_t words_bytes = (size_t)m * 256; // a row of 64 words per scan: what every wait reads
-	auto words_of = [&](uint32_t s) { return reinterpret_cast<uint32_t *>(ctx->exb_pin) + (size_t)(s - first) * 64; };
+	words_bytes = (size_t)m * 256;
 	EXCHK(R.pin_reserve(words_bytes + 64));
 	R.pin_off = words_bytes;
-	if (P->estimate_ground_normal_method == 3 && gf_rnd_table(ctx) != MULLS_OK)
+	if (method() == 3 && gf_rnd_table(ctx) != MULLS_OK)
 		return MULLS_E_HIP;
+	return MULLS_OK;
+}
 
-	// ---- the scans go up (pageable ones of a MB and more through the context's pinned scratch, as a single call's) ---------------------------------
+// ---- the scans go up (pageable ones of a MB and more through the context's pinned scratch; a caller's pinned buffer goes up as it is) ----------------
+// A pageable scan of a few MB is pinned and unpinned by the runtime around its copy (0.15 ms in front of a 0.1 ms transfer on the frame path): the
+// process's host pool moves it into the context's pinned scratch instead, and the transfer starts from there.
+int Core::upload(const ScanRegion *reg)
+{
 	{
 		std::vector<uint8_t> stage(m, 0), on_dev(m, 0);
 		size_t pin_need = 0;
@@ -187,9 +249,20 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 			ScanState &Z = sc[s];
 			if (!Z.live)
 				continue;
-			Z.a = gf_layout(Z.n_in, prefilter, false, P->estimate_ground_normal_method);
 			Z.gf = arena + reg[s].o_gf, Z.cl = arena + reg[s].o_cl;
-			Z.cur = prefilter ? Z.gf + Z.a.o_alt : Z.gf, Z.other = prefilter ? Z.gf : Z.gf + Z.a.o_alt;
+			if (part == EX_CLASSIFY)
+			{
+				// the region holds the cloud and nothing else: it is the non-ground cloud of a scan whose ground stage has run
+				Z.cur = Z.ug = Z.gf;
+				Z.go.n_unground = Z.n_in;
+			}
+			else
+			{
+				// two scan-sized buffers (gf, alt): every stage ahead of the ground filter reads one and writes the other, and the last one writes gf
+				Z.a = gf_layout(Z.n_in, prefilter, voxels, method());
+				Z.cur = (prefilter != voxels) ? Z.gf + Z.a.o_alt : Z.gf, Z.other = (prefilter != voxels) ? Z.gf : Z.gf + Z.a.o_alt;
+				Z.ug = Z.gf + Z.a.o_unground;
+			}
 			hipPointerAttribute_t at;
 			const hipError_t qe = hipPointerGetAttributes(&at, scans[s].pts);
 			const bool pageable = qe != hipSuccess || at.type == hipMemoryTypeUnregistered;
@@ -197,7 +270,8 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 				(void)hipGetLastError(); // not an error of this call
 			else
 				on_dev[s - first] = at.type == hipMemoryTypeDevice;
-			if (scans[s].stride == REC && pageable && (size_t)Z.n_in * REC >= ((size_t)1 << 20))
+			// (the stage-alone calls send their cloud as it is: staged, mulls_ground_filter measured 0.06 ms slower on a 121 k-return scan)
+			if (part == EX_ALL && scans[s].stride == REC && pageable && (size_t)Z.n_in * REC >= ((size_t)1 << 20))
 				stage[s - first] = 1, pin_need += ((size_t)Z.n_in * REC + 255u) & ~(size_t)255u;
 		}
 		if (pin_need && grow_pinned(ctx, &ctx->scan_pin, &ctx->scan_pin_cap, pin_need, hipHostMallocDefault) != MULLS_OK)
@@ -233,8 +307,12 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 			HIPCHK(ctx, hipMemcpyAsync(Z.cur, up, rec_in, kind, st));
 		}
 	}
+	return MULLS_OK;
+}
 
-	// ---- dist_filter, scanner_filter: one mask launch, one compaction, one look at the sizes (wait 1) ---------------------------------------------------
+// ---- dist_filter, scanner_filter: one mask launch, one compaction, one look at the sizes (wait 1); voxel_downsample behind them, scan-locally --------
+int Core::prefilter_stage()
+{
 	if (prefilter)
 	{
 		std::vector<RawMaskJob> mj(m);
@@ -291,10 +369,36 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 			continue;
 		results[s].n_out[MULLS_EX_RAW] = results[s].n_out[MULLS_EX_DOWN] = Z.n;
 		if (Z.n == 0)
+		{
 			Z.live = false; // an empty block, MULLS_OK
+			continue;
+		}
+		if (sinks && std::min(Z.n, sinks->cap_raw))
+			HIPCHK(ctx, hipMemcpyAsync(sinks->raw, Z.cur, (size_t)std::min(Z.n, sinks->cap_raw) * REC, hipMemcpyDeviceToHost, st));
+		if (voxels)
+		{
+			// (a sub-batch of one: vox_run waits for its bounding box and its keys, and sorts on the host)
+			uint32_t nd = 0;
+			const int rcv = vox_run(ctx, Z.gf, Z.a, reinterpret_cast<const float4 *>(Z.cur), Z.n, X->vf_downsample_resolution, reinterpret_cast<float4 *>(Z.other), &nd);
+			if (rcv == MULLS_E_HIP)
+				return rcv;
+			if (rcv != MULLS_OK)
+			{
+				Z.err = ctx->err, Z.status = rcv, Z.live = false;
+				continue;
+			}
+			std::swap(Z.cur, Z.other);
+			results[s].n_out[MULLS_EX_DOWN] = Z.n = nd;
+		}
+		if (sinks && std::min(Z.n, sinks->cap_down))
+			HIPCHK(ctx, hipMemcpyAsync(sinks->down, Z.cur, (size_t)std::min(Z.n, sinks->cap_down) * REC, hipMemcpyDeviceToHost, st));
 	}
+	return MULLS_OK;
+}
 
-	// ---- fast_ground_filter: GfOut of every scan in one look (wait 2) ----------------------------------------------------------------------------------------
+// ---- fast_ground_filter: GfOut of every scan in one look (wait 2); the normals of methods 1 and 2 behind it, scan-locally ------------------------------------
+int Core::ground_stage()
+{
 	{
 		std::vector<GfScan> gt(m);
 		std::memset(gt.data(), 0, gt.size() * sizeof(GfScan));
@@ -334,11 +438,39 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 			{
 				Z.err = "mulls_ground_filter: the grid has too many cells (more than 65536, or more than 64 M table entries: grid_resolution too fine for this scan's extent)";
 				Z.status = MULLS_E_UNSUPPORTED, Z.live = false;
+				continue;
+			}
+			if ((method() == 1 || method() == 2) && Z.go.n_ground)
+			{
+				// normals of cloud_ground from its own neighbourhoods (:1943-1954); the error word of the state reports a neighbourhood beyond the buffer
+				uint32_t *err_word = reinterpret_cast<uint32_t *>(Z.gf + Z.a.o_aux) + 3;
+				launch_ground_normals(st, reinterpret_cast<float4 *>(Z.gf + Z.a.o_ground), Z.go.n_ground, method() == 1 ? P->normal_estimation_radius : 0.0f, 2 * P->min_grid_pt_num,
+									  Z.gf + Z.a.o_normals, err_word);
+				uint32_t e = 0;
+				HIPCHK(ctx, hipMemcpyAsync(&e, err_word, sizeof(e), hipMemcpyDeviceToHost, st));
+				HIPCHK(ctx, hipStreamSynchronize(st));
+				if (e)
+				{
+					Z.err = "mulls_ground_filter: more than 1024 ground points within normal_estimation_radius of one point";
+					Z.status = MULLS_E_UNSUPPORTED, Z.live = false;
+				}
 			}
 		}
 	}
+	return MULLS_OK;
+}
 
-	// ---- classify_nground_pts ----------------------------------------------------------------------------------------------------------------------------------
+// ---- classify_nground_pts ----------------------------------------------------------------------------------------------------------------------------------
+int Core::classify_stage()
+{
+	// (a whole-chain call reaches the classification's own refusal here, behind the ground filter's)
+	if (mulls_classify_check(ctx, C) != MULLS_OK)
+	{
+		for (uint32_t s = first; s < last; s++)
+			if (sc[s].live)
+				sc[s].err = ctx->err, sc[s].status = MULLS_E_INVALID, sc[s].live = false;
+		return MULLS_OK;
+	}
 	ClParams Q;
 	mulls_classify_kernel_params(C, &Q);
 	const uint32_t K = Q.K;
@@ -383,7 +515,7 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 			Z.L = carve(Z.cl, Z.n_cl, K, Z.n_ug);
 			const ClArrays &A = Z.L.A;
 			ct[s - first].A = A, ct[s - first].n = Z.n_cl;
-			const unsigned char *src = Z.gf + Z.a.o_unground;
+			const unsigned char *src = Z.ug;
 			if (Z.in_mask.empty())
 				R.seg(A.recs, src, (size_t)Z.n_cl * REC);
 			else
@@ -436,7 +568,7 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 					S.n_kernel_launches += (uint32_t)launch_cl_promote_round_batch(st, ct_d, m, ncl_max, Q, d_round + slot);
 					S.promote_rounds++;
 				},
-				"mulls_extract_features_batch: the promotion loop did not settle", &S.n_syncs);
+				R.msg("the promotion loop did not settle"), &S.n_syncs);
 			if (rcr != MULLS_OK)
 				return rcr;
 		}
@@ -623,7 +755,7 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 					S.n_kernel_launches += (uint32_t)launch_cl_nms_round_batch(st, nt_d, m, nmax, d_round + slot);
 					S.nms_rounds++;
 				},
-				"mulls_extract_features_batch: the suppression rounds did not settle", &S.n_syncs); // wait 7
+				R.msg("the suppression rounds did not settle"), &S.n_syncs); // wait 7
 			if (rcn != MULLS_OK)
 				return rcn;
 			S.n_kernel_launches += (uint32_t)launch_map_compact_batch(st, jd_d, jd.data(), m);
@@ -681,8 +813,12 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 			shared_host_pool().parallel_for(0, (long)m, 1, thin);
 		}
 	}
+	return MULLS_OK;
+}
 
-	// ---- block placement (wait 9): every block sized first and grown at most once, then all clouds of all scans in one launch ---------------------------------
+// ---- block placement (wait 9): every block sized first and grown at most once, then all clouds of all scans in one launch ---------------------------------
+int Core::place()
+{
 	{
 		size_t bytes = 64;
 		for (uint32_t s = first; s < last; s++)
@@ -706,20 +842,16 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 				continue;
 			mulls_block *blk = blocks[s];
 			uint32_t *n_out = results[s].n_out;
-			const uint32_t cntk[MULLS_CL_COUNT] = {Z.ncls[0], Z.ncls[1], Z.ncls[2], Z.ncls[3], Z.ndown[0], Z.ndown[1], Z.ndown[2], Z.ndown[3], Z.nvertex};
-			const float4 *dev[MULLS_CL_COUNT] = {Z.cls[0], Z.cls[1], Z.cls[2], Z.cls[3], Z.L.down[0], Z.L.down[1], Z.L.down[2], Z.L.down[3], Z.L.vertex};
+			uint32_t cntk[MULLS_CL_COUNT];
+			const float4 *dev[MULLS_CL_COUNT];
+			Z.clouds(dev, cntk);
 			uint32_t cnt[MULLS_EX_COUNT] = {};
 			cnt[MULLS_EX_GROUND] = Z.go.n_ground, cnt[MULLS_EX_GROUND_DOWN] = (uint32_t)Z.gd_idx.size(), cnt[MULLS_EX_UNGROUND] = Z.n_cl;
 			for (int k = 0; k < MULLS_CL_COUNT; k++)
 				cnt[MULLS_EX_PILLAR + k] = Z.classify ? cntk[k] : 0u, n_out[MULLS_EX_PILLAR + k] = cnt[MULLS_EX_PILLAR + k];
 			n_out[MULLS_EX_GROUND] = cnt[MULLS_EX_GROUND], n_out[MULLS_EX_GROUND_DOWN] = cnt[MULLS_EX_GROUND_DOWN];
-			size_t need = 0, off[MULLS_EX_COUNT];
-			for (int k = 0; k < MULLS_EX_COUNT; k++)
-			{
-				off[k] = need;
-				need += ((size_t)cnt[k] * REC + 255) & ~(size_t)255;
-			}
-			need += Z.gd_idx.size() * 4 + 256; // the selection indices ride at the end
+			const BlockLayout bl = block_layout(cnt, Z.gd_idx.size());
+			const size_t need = bl.need, *off = bl.off;
 			if (blk->cap < need)
 			{
 				if (blk->buf)
@@ -731,7 +863,7 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 			R.seg(blk->buf + off[MULLS_EX_GROUND], Z.gf + Z.a.o_ground, (size_t)cnt[MULLS_EX_GROUND] * REC);
 			if (!Z.gd_idx.empty())
 			{
-				uint32_t *d_idx = reinterpret_cast<uint32_t *>(blk->buf + need - (Z.gd_idx.size() * 4 + 128));
+				uint32_t *d_idx = reinterpret_cast<uint32_t *>(blk->buf + bl.o_idx);
 				unsigned char *hp = R.pin_take(Z.gd_idx.size() * 4);
 				std::memcpy(hp, Z.gd_idx.data(), Z.gd_idx.size() * 4);
 				R.seg(d_idx, R.dev(hp), Z.gd_idx.size() * 4);
@@ -777,10 +909,130 @@ int run_subbatch(Run &R, const mulls_cloud *scans, const mulls_extract_params *X
 	}
 	return MULLS_OK;
 }
+
+// plan the sub-batches and run them
+int Core::run(uint32_t n_scans, uint64_t limit)
+{
+	// (a neighbor_k the classification refuses sizes nothing: classify_stage turns those scans away)
+	const uint32_t K = C && C->neighbor_k >= 1 && C->neighbor_k <= (int)MULLS_CL_MAX_K ? (uint32_t)C->neighbor_k : 1u;
+	std::vector<ScanCost> cost(n_scans);
+	std::vector<uint64_t> bytes(n_scans);
+	for (uint32_t s = 0; s < n_scans; s++)
+	{
+		const uint32_t n = sc[s].live ? sc[s].n_in : 0u;
+		if (part == EX_ALL)
+			cost[s] = extract_batch_scan_cost(n, prefilter, method(), C->fixed_num_downsampling != 0, C->unground_down_fixed_num, K, voxels);
+		else
+		{
+			// one stage's region: the ground arena alone, or the cloud and the classify arena of its work points
+			cost[s].gf = !n ? 0u : part == EX_GROUND ? up256(gf_layout(n, false, false, method()).total) : up256((uint64_t)n * REC);
+			cost[s].cl = !n || part == EX_GROUND ? 0u : up256(carve(nullptr, classify_work_points(n, C->fixed_num_downsampling != 0, C->unground_down_fixed_num), K, n).total);
+			cost[s].total = cost[s].gf + cost[s].cl + MULLS_EXB_TABLE_BYTES;
+		}
+		bytes[s] = cost[s].total;
+	}
+	std::vector<uint32_t> cuts;
+	extract_batch_cuts(bytes.data(), n_scans, limit, &cuts, alone ? 1u : MULLS_EXB_MAX_SCANS);
+	std::vector<ScanRegion> reg(n_scans);
+	for (size_t k = 0; k + 1 < cuts.size(); k++)
+	{
+		const uint64_t arena_bytes = extract_batch_offsets(cost.data(), cuts[k], cuts[k + 1], reg.data());
+		S.n_subbatches++;
+		EXCHK(begin(cuts[k], cuts[k + 1], arena_bytes, limit));
+		EXCHK(upload(reg.data()));
+		if (part == EX_ALL)
+			EXCHK(prefilter_stage());
+		if (part != EX_CLASSIFY)
+			EXCHK(ground_stage());
+		if (part != EX_GROUND)
+			EXCHK(classify_stage());
+		if (part == EX_ALL && blocks[first])
+			EXCHK(place()); // (a one-scan run without a block: mulls_extract_features takes the clouds from where they are)
+	}
+	return MULLS_OK;
+}
+
+// a single call: one scan, one sub-batch, the scan's own status and message
+int run_one(mulls_ctx *ctx, Part part, const char *who, const void *pts, uint32_t n, uint32_t stride, const mulls_extract_params *X, const mulls_ground_params *P,
+			const mulls_classify_params *C, mulls_block *blk, const HostSinks *sinks, uint32_t *n_out, std::vector<ScanState> &sc)
+{
+	const mulls_cloud cloud = {pts, n, stride};
+	mulls_extract_batch_result res;
+	mulls_extract_batch_stats stats;
+	std::memset(&res, 0, sizeof(res));
+	std::memset(&stats, 0, sizeof(stats));
+	sc.assign(1, ScanState());
+	sc[0].n_in = sc[0].n = n, sc[0].live = true;
+	Core K(ctx, who, &stats, part, &cloud, X, P, C, &blk, &res, sc, sinks);
+	const int rc = K.run(1, MULLS_EXTRACT_BATCH_DEFAULT_SCRATCH_BYTES);
+	if (n_out)
+		std::memcpy(n_out, res.n_out, sizeof(res.n_out));
+	if (rc == MULLS_OK && sc[0].status != MULLS_OK)
+		ctx->err = sc[0].err;
+	return rc != MULLS_OK ? rc : sc[0].status;
+}
+
+// cloud_ground (n_ground records in the scan's region) and cloud_ground_down, taken from it on the host, cut to the capacities; waits for the stream
+int ground_clouds_down(mulls_ctx *ctx, const mulls_ground_params *P, const ScanState &Z, void *ground, uint32_t cap_ground, void *ground_down, uint32_t cap_ground_down,
+					   uint32_t *n_ground, uint32_t *n_ground_down)
+{
+	const uint32_t ng = Z.go.n_ground;
+	std::vector<unsigned char> g((size_t)ng * REC);
+	if (ng)
+		HIPCHK(ctx, hipMemcpyAsync(g.data(), Z.gf + Z.a.o_ground, g.size(), hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	if (std::min(ng, cap_ground))
+		std::memcpy(ground, g.data(), (size_t)std::min(ng, cap_ground) * REC);
+	std::vector<uint32_t> idx;
+	gf_ground_down_indices(P, ng, idx);
+	for (size_t k = 0; k < idx.size() && k < cap_ground_down; k++)
+		std::memcpy(static_cast<unsigned char *>(ground_down) + k * REC, g.data() + (size_t)idx[k] * REC, REC);
+	*n_ground = ng, *n_ground_down = (uint32_t)idx.size();
+	return MULLS_OK;
+}
+// the nine clouds of the classification from where the kernels (or the host's samplers) left them, cut to the capacities, and cloud_in as the stage leaves it
+// (whole, or not at all: cloud_in null); queued on the stream
+int class_clouds_down(mulls_ctx *ctx, const ScanState &Z, void *const out[MULLS_CL_COUNT], const uint32_t cap[MULLS_CL_COUNT], uint32_t n_out[MULLS_CL_COUNT], void *cloud_in)
+{
+	if (!Z.classify)
+		return MULLS_OK;
+	const float4 *dev[MULLS_CL_COUNT];
+	uint32_t cnt[MULLS_CL_COUNT];
+	Z.clouds(dev, cnt);
+	for (int k = 0; k < MULLS_CL_COUNT; k++)
+	{
+		n_out[k] = cnt[k];
+		const size_t want = std::min(cnt[k], cap[k]);
+		if (!want)
+			continue;
+		if (Z.on_host[k])
+			std::memcpy(out[k], Z.host[k].data(), want * REC);
+		else
+			HIPCHK(ctx, hipMemcpyAsync(out[k], dev[k], want * REC, hipMemcpyDeviceToHost, ctx->stream));
+	}
+	if (cloud_in)
+		HIPCHK(ctx, hipMemcpyAsync(cloud_in, Z.L.A.recs, (size_t)Z.n_cl * REC, hipMemcpyDeviceToHost, ctx->stream));
+	return MULLS_OK;
+}
 } // namespace
 
 extern "C"
 {
+	// the feature stage's one device arena holds `need` bytes: grown by a quarter (frames whose sizes creep upward do not reallocate at every new
+	// maximum), but not beyond the limit a batch was given unless one scan needs it
+	MULLS_HIDDEN int ex_arena_reserve(mulls_ctx *ctx, uint64_t need, uint64_t limit)
+	{
+		if (ctx->exb_buf && ctx->exb_cap >= need)
+			return MULLS_OK;
+		if (ctx->exb_buf)
+			(void)hipFree(ctx->exb_buf);
+		ctx->exb_buf = nullptr, ctx->exb_cap = 0;
+		const uint64_t want = std::max<uint64_t>(std::min(need + need / 4, std::max(need, limit)), 64);
+		HIPCHK(ctx, hipMalloc(&ctx->exb_buf, want));
+		ctx->exb_cap = want;
+		return MULLS_OK;
+	}
+
 	int mulls_extract_features_batch(mulls_ctx *ctx, const mulls_cloud *scans, uint32_t n_scans, const mulls_extract_params *X, mulls_block *const *blocks,
 									 uint64_t scratch_limit_bytes, mulls_extract_batch_result *results, mulls_extract_batch_stats *stats)
 	try
@@ -802,49 +1054,20 @@ extern "C"
 				if (blocks[t] == blocks[s])
 					return MULLS_E_INVALID;
 		}
-		mulls_extract_batch_stats local;
+		mulls_extract_batch_stats local, unseen;
 		std::memset(&local, 0, sizeof(local));
+		std::memset(&unseen, 0, sizeof(unseen));
 		mulls_extract_batch_stats &S = stats ? *stats : local;
 		std::memset(results, 0, sizeof(*results) * n_scans);
 		const mulls_ground_params *P = &X->ground;
-		auto finish = [&](const std::vector<std::string> &errs) {
-			for (uint32_t s = 0; s < n_scans; s++)
-				if (results[s].status != MULLS_OK)
-				{
-					ctx->err = "mulls_extract_features_batch: scan " + std::to_string(s) + ": " + errs[s];
-					return (int)results[s].status;
-				}
-			return (int)MULLS_OK;
-		};
-		std::vector<std::string> errs(n_scans);
-		// the two parameter points of the single-scan path (and parameters every single call would refuse: it says how)
-		const bool voxels = !(X->vf_downsample_resolution < 0.001);
-		const int method = P->estimate_ground_normal_method;
-		const bool refused = gf_check(ctx, P, 0) != MULLS_OK || mulls_classify_check(ctx, &X->classify) != MULLS_OK;
-		if (voxels || method == 1 || method == 2 || refused)
-		{
-			void *no_out[MULLS_EX_COUNT] = {};
-			uint32_t no_cap[MULLS_EX_COUNT] = {};
-			for (uint32_t s = 0; s < n_scans; s++)
-			{
-				results[s].path = 1;
-				results[s].status = extract_impl(ctx, scans[s].pts, scans[s].n, scans[s].stride, X, no_out, no_cap, results[s].n_out, blocks[s]);
-				if (results[s].status != MULLS_OK)
-				{
-					errs[s] = ctx->err;
-					for (int k = 0; k < MULLS_EX_COUNT; k++)
-						blocks[s]->n[k] = 0;
-				}
-				S.n_single_path++;
-			}
-			return finish(errs);
-		}
 		HIPCHK(ctx, hipSetDevice(ctx->device));
 		const mulls::StreamDrain drain{ctx->stream};
-		const bool prefilter = X->apply_scanner_filter != 0 || X->apply_dist_filter != 0;
 		std::vector<ScanState> sc(n_scans);
-		std::vector<ScanCost> cost(n_scans);
-		std::vector<uint64_t> bytes(n_scans);
+		// the statistics count the lock step: scans that run alone (path = 1) are counted as such and nothing else
+		// (parameters every single call would refuse: each scan says how, as a scan that ran alone)
+		const bool alone = scan_local_steps(X, P) || gf_check(ctx, P, 0) != MULLS_OK || mulls_classify_check(ctx, &X->classify) != MULLS_OK;
+		Core K(ctx, "mulls_extract_features_batch", alone ? &unseen : &S, EX_ALL, scans, X, P, &X->classify, blocks, results, sc);
+		K.alone = alone;
 		for (uint32_t s = 0; s < n_scans; s++)
 		{
 			for (int k = 0; k < MULLS_EX_COUNT; k++)
@@ -854,22 +1077,10 @@ extern "C"
 			if (sc[s].status != MULLS_OK)
 				sc[s].err = ctx->err;
 			sc[s].live = sc[s].status == MULLS_OK && scans[s].n > 0;
-			cost[s] = extract_batch_scan_cost(sc[s].live ? scans[s].n : 0u, prefilter, method, X->classify.fixed_num_downsampling != 0, X->classify.unground_down_fixed_num,
-											  (uint32_t)X->classify.neighbor_k);
-			bytes[s] = cost[s].total;
-			S.n_lockstep++;
+			results[s].path = alone ? 1u : 0u;
+			(alone ? S.n_single_path : S.n_lockstep)++;
 		}
-		std::vector<uint32_t> cuts;
-		extract_batch_cuts(bytes.data(), n_scans, scratch_limit_bytes ? scratch_limit_bytes : MULLS_EXTRACT_BATCH_DEFAULT_SCRATCH_BYTES, &cuts);
-		std::vector<ScanRegion> reg(n_scans);
-		Run R{ctx, ctx->stream, &S};
-		int rc = MULLS_OK;
-		for (size_t k = 0; k + 1 < cuts.size() && rc == MULLS_OK; k++)
-		{
-			const uint64_t arena_bytes = extract_batch_offsets(cost.data(), cuts[k], cuts[k + 1], reg.data());
-			S.n_subbatches++;
-			rc = run_subbatch(R, scans, X, blocks, results, sc, cuts[k], cuts[k + 1], reg.data(), arena_bytes);
-		}
+		const int rc = K.run(n_scans, scratch_limit_bytes ? scratch_limit_bytes : MULLS_EXTRACT_BATCH_DEFAULT_SCRATCH_BYTES);
 		if (rc != MULLS_OK)
 		{
 			// the device or the runtime failed: no scan's result stands
@@ -886,12 +1097,154 @@ extern "C"
 		for (uint32_t s = 0; s < n_scans; s++)
 		{
 			results[s].status = sc[s].status;
-			errs[s] = sc[s].err;
 			if (sc[s].status != MULLS_OK)
 				for (int k = 0; k < MULLS_EX_COUNT; k++)
 					blocks[s]->n[k] = 0;
 		}
-		return finish(errs);
+		for (uint32_t s = 0; s < n_scans; s++)
+			if (results[s].status != MULLS_OK)
+			{
+				ctx->err = "mulls_extract_features_batch: scan " + std::to_string(s) + ": " + sc[s].err;
+				return (int)results[s].status;
+			}
+		return MULLS_OK;
+	}
+	catch (...)
+	{
+		return mulls::abi_caught(ctx); // nothing is thrown across the ABI
+	}
+
+	// ---- the single calls: a batch of one -------------------------------------------------------------------------------------------------
+	// (the round loops' messages are mulls_classify_nground's in a single call, whichever entry point it is)
+	int mulls_extract_features_resident(mulls_ctx *ctx, const void *scan, uint32_t n, uint32_t stride, const mulls_extract_params *X, mulls_block *block,
+										uint32_t n_out[MULLS_EX_COUNT])
+	try
+	{
+		if (!block || !ctx || !X || !n_out || (n && !scan) || stride < MULLS_POINT_BYTES)
+			return MULLS_E_INVALID;
+		for (int k = 0; k < MULLS_EX_COUNT; k++)
+			block->n[k] = 0, n_out[k] = 0;
+		const int chk = gf_check(ctx, &X->ground, n);
+		if (chk != MULLS_OK || n == 0)
+			return chk;
+		HIPCHK(ctx, hipSetDevice(ctx->device));
+		const mulls::StreamDrain drain{ctx->stream};
+		std::vector<ScanState> sc;
+		const int rc = run_one(ctx, EX_ALL, "mulls_classify_nground", scan, n, stride, X, &X->ground, &X->classify, block, nullptr, n_out, sc);
+		if (rc != MULLS_OK)
+			for (int k = 0; k < MULLS_EX_COUNT; k++)
+				block->n[k] = 0;
+		return rc;
+	}
+	catch (...)
+	{
+		return mulls::abi_caught(ctx);
+	}
+
+	// the whole chain without a block: the clouds come down from where the stages leave them, cut to the capacities
+	int mulls_extract_features(mulls_ctx *ctx, const void *scan, uint32_t n_in, uint32_t stride, const mulls_extract_params *X, void *const out[MULLS_EX_COUNT],
+							   const uint32_t cap[MULLS_EX_COUNT], uint32_t n_out[MULLS_EX_COUNT])
+	try
+	{
+		if (!ctx || !X || !out || !cap || !n_out || (n_in && !scan) || stride < MULLS_POINT_BYTES)
+			return MULLS_E_INVALID;
+		for (int k = 0; k < MULLS_EX_COUNT; k++)
+		{
+			n_out[k] = 0;
+			if (cap[k] && !out[k])
+				return MULLS_E_INVALID;
+		}
+		const int chk = gf_check(ctx, &X->ground, n_in);
+		if (chk != MULLS_OK || n_in == 0)
+			return chk;
+		HIPCHK(ctx, hipSetDevice(ctx->device));
+		const mulls::StreamDrain drain{ctx->stream}; // error returns leave copies into out[] queued
+		const HostSinks sinks = {out[MULLS_EX_RAW], out[MULLS_EX_DOWN], cap[MULLS_EX_RAW], cap[MULLS_EX_DOWN]};
+		std::vector<ScanState> sc;
+		const int rc = run_one(ctx, EX_ALL, "mulls_classify_nground", scan, n_in, stride, X, &X->ground, &X->classify, nullptr, &sinks, n_out, sc);
+		if (rc != MULLS_OK)
+			return rc;
+		const ScanState &Z = sc[0];
+		// (cloud_in comes back only whole: a capacity below the non-ground cloud's size ahead of its thinning leaves the buffer alone)
+		EXCHK(class_clouds_down(ctx, Z, out + MULLS_EX_PILLAR, cap + MULLS_EX_PILLAR, n_out + MULLS_EX_PILLAR, cap[MULLS_EX_UNGROUND] >= Z.go.n_unground ? out[MULLS_EX_UNGROUND] : nullptr));
+		return ground_clouds_down(ctx, &X->ground, Z, out[MULLS_EX_GROUND], cap[MULLS_EX_GROUND], out[MULLS_EX_GROUND_DOWN], cap[MULLS_EX_GROUND_DOWN], &n_out[MULLS_EX_GROUND],
+								  &n_out[MULLS_EX_GROUND_DOWN]);
+	}
+	catch (...)
+	{
+		return mulls::abi_caught(ctx); // nothing is thrown across the ABI
+	}
+
+	// the ground stage alone; cloud_ground_down is taken on the host from the downloaded cloud
+	int mulls_ground_filter(mulls_ctx *ctx, const void *pts, uint32_t n, uint32_t stride, const mulls_ground_params *P, void *ground, uint32_t cap_ground,
+							void *ground_down, uint32_t cap_ground_down, void *unground, uint32_t cap_unground, uint32_t n_out[3])
+	try
+	{
+		if (!ctx || !P || !n_out || (n && !pts) || stride < MULLS_POINT_BYTES || (cap_ground && !ground) || (cap_ground_down && !ground_down) ||
+			(cap_unground && !unground))
+			return MULLS_E_INVALID;
+		n_out[0] = n_out[1] = n_out[2] = 0;
+		const int chk = gf_check(ctx, P, n);
+		if (chk != MULLS_OK)
+			return chk;
+		if (n == 0)
+			return MULLS_OK; // (the reference divides by a zero sample count here)
+		HIPCHK(ctx, hipSetDevice(ctx->device));
+		hipStream_t st = ctx->stream;
+		const mulls::StreamDrain drain{st}; // error returns below leave copies into `unground` / `g` queued
+		std::vector<ScanState> sc;
+		const int rc = run_one(ctx, EX_GROUND, "mulls_ground_filter", pts, n, stride, nullptr, P, nullptr, nullptr, nullptr, nullptr, sc);
+		if (rc != MULLS_OK)
+			return rc;
+		const ScanState &Z = sc[0];
+		const uint32_t ku = std::min(Z.go.n_unground, cap_unground);
+		if (ku)
+			HIPCHK(ctx, hipMemcpyAsync(unground, Z.ug, (size_t)ku * REC, hipMemcpyDeviceToHost, st));
+		EXCHK(ground_clouds_down(ctx, P, Z, ground, cap_ground, ground_down, cap_ground_down, &n_out[0], &n_out[1]));
+		n_out[2] = Z.go.n_unground;
+		return MULLS_OK;
+	}
+	catch (...)
+	{
+		return mulls::abi_caught(ctx); // nothing is thrown across the ABI
+	}
+
+	// the host cloud into the scan's region, the classification stage alone, the clouds down from where the kernels (or the host's samplers) left them
+	int mulls_classify_nground(mulls_ctx *ctx, const void *pts, uint32_t n_in, uint32_t stride, const mulls_classify_params *P, void *const out[MULLS_CL_COUNT],
+							   const uint32_t cap[MULLS_CL_COUNT], uint32_t n_out[MULLS_CL_COUNT], void *cloud_in_after, uint32_t *n_cloud_in_after)
+	try
+	{
+		if (!ctx || !P || !out || !cap || !n_out || (n_in && !pts) || stride < MULLS_POINT_BYTES)
+			return MULLS_E_INVALID;
+		for (int k = 0; k < MULLS_CL_COUNT; k++)
+		{
+			n_out[k] = 0;
+			if (cap[k] && !out[k])
+				return MULLS_E_INVALID;
+		}
+		if (mulls_classify_check(ctx, P) != MULLS_OK)
+			return MULLS_E_INVALID;
+		if (n_in > 2000000u)
+		{
+			ctx->err = "mulls_classify_nground: more than 2000000 points in one cloud";
+			return MULLS_E_UNSUPPORTED;
+		}
+		// random_downsample_pcl(cloud_in, unground_down_fixed_num) (:2088-2089) leaves this many
+		const uint32_t n = classify_work_points(n_in, P->fixed_num_downsampling != 0, P->unground_down_fixed_num);
+		if (n_cloud_in_after)
+			*n_cloud_in_after = n;
+		if (n == 0)
+			return MULLS_OK;
+		HIPCHK(ctx, hipSetDevice(ctx->device));
+		hipStream_t st = ctx->stream;
+		const mulls::StreamDrain drain{st};
+		std::vector<ScanState> sc;
+		const int rc = run_one(ctx, EX_CLASSIFY, "mulls_classify_nground", pts, n_in, stride, nullptr, nullptr, P, nullptr, nullptr, nullptr, sc);
+		if (rc != MULLS_OK)
+			return rc;
+		EXCHK(class_clouds_down(ctx, sc[0], out, cap, n_out, cloud_in_after));
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		return MULLS_OK;
 	}
 	catch (...)
 	{

@@ -1,6 +1,6 @@
 // extract_batch.h — arena arithmetic of the feature stage and the planner of mulls_extract_features_batch (include/mulls_hip.h).
-// Host code only (no kernel, no runtime call), so that tests/extract_batch_harness.cpp can hold it on the CPU.  gf_layout and carve are THE formulas of the
-// single calls' arenas (ground.cpp, classify.cpp): a scan of a batch gets exactly the regions its single call would carve, side by side with the others',
+// Host code only (no kernel, no runtime call), so that tests/extract_batch_harness.cpp can hold it on the CPU.  gf_layout and carve are the formulas of a
+// scan's two regions, whichever entry point runs it (a single call is a batch of one): the scans of a sub-batch lie side by side,
 //   arena = tables (EXB_TABLE_BYTES per scan, behind EXB_HEAD_BYTES of shared words) | scan 0: ground region, classify region | scan 1: ... | ...
 // and the batch is cut into consecutive sub-batches whose arenas stay at or below the caller's limit; a scan larger than the limit runs alone.
 #pragma once
@@ -158,19 +158,23 @@ struct ScanCost
 };
 // What a scan of n points may need: its ground arena, and the classify arena of the largest non-ground cloud it can leave (all n points).
 // A scan without points takes its table row only.
-inline ScanCost extract_batch_scan_cost(uint32_t n, bool prefilter, int normal_method, bool fixed_num, int unground_down_fixed_num, uint32_t K)
+inline ScanCost extract_batch_scan_cost(uint32_t n, bool prefilter, int normal_method, bool fixed_num, int unground_down_fixed_num, uint32_t K, bool voxels = false)
 {
 	ScanCost c = {0, 0, MULLS_EXB_TABLE_BYTES};
 	if (!n)
 		return c;
-	c.gf = up256(gf_layout(n, prefilter, false, normal_method).total);
+	c.gf = up256(gf_layout(n, prefilter, voxels, normal_method).total);
 	c.cl = up256(carve(nullptr, classify_work_points(n, fixed_num, unground_down_fixed_num), K, n).total);
 	c.total = c.gf + c.cl + MULLS_EXB_TABLE_BYTES;
 	return c;
 }
 
-// the cut rule of subbatch.h: every sub-batch starts from the head
-inline void extract_batch_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts) { sub_batch_cuts(bytes, count, limit, MULLS_EXB_MAX_SCANS, cuts, MULLS_EXB_HEAD_BYTES); }
+// the cut rule of subbatch.h: every sub-batch starts from the head.  max_scans = 1: every scan a sub-batch of its own, whatever the limit (the steps
+// without a table form run scan-locally)
+inline void extract_batch_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, std::vector<uint32_t> *cuts, uint32_t max_scans = MULLS_EXB_MAX_SCANS)
+{
+	sub_batch_cuts(bytes, count, limit, max_scans, cuts, MULLS_EXB_HEAD_BYTES);
+}
 
 struct ScanRegion
 {
@@ -186,5 +190,25 @@ inline uint64_t extract_batch_offsets(const ScanCost *cost, uint32_t first, uint
 		out[b].o_cl = off, off += cost[b].cl;
 	}
 	return off;
+}
+
+// a feature block's buffer: the clouds of MULLS_EX_* in order, every offset a multiple of 256, and behind them the n_idx selection indices of
+// cloud_ground_down (the gather that fills it reads them from the block)
+struct BlockLayout
+{
+	size_t off[MULLS_EX_COUNT], o_idx, need;
+};
+inline BlockLayout block_layout(const uint32_t cnt[MULLS_EX_COUNT], size_t n_idx)
+{
+	BlockLayout b;
+	size_t at = 0;
+	for (int k = 0; k < MULLS_EX_COUNT; k++)
+	{
+		b.off[k] = at;
+		at += up256((uint64_t)cnt[k] * MULLS_POINT_BYTES);
+	}
+	b.o_idx = at + 128;
+	b.need = at + n_idx * 4 + 256;
+	return b;
 }
 } // namespace mulls_ex

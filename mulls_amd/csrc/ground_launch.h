@@ -26,8 +26,6 @@ struct GfRansac
 	const uint32_t *rnd; // [MULLS_GF_RND] PCL's sample sequence: boost::mt19937(12345u) outputs / 2
 };
 #define MULLS_GF_RND 63008u // draws one cell can take at most: 21 iterations x 1000 sample checks x 3 (+ padding)
-int launch_ground_filter(hipStream_t st, const float4 *pts, uint32_t n, const mulls_ground_params &P, uint32_t *ids, uint16_t *cellof, uint8_t *code, float *d3v,
-						 float4 *ground, float4 *unground, void *aux, const GfRansac &R);
 #define MULLS_GF_MAXCELLS 65536u
 #define MULLS_GF_BLOCK 256
 #define MULLS_GF_SEG 1024u // points per segment (one wave walks a segment in 16 steps of 64)
@@ -58,7 +56,7 @@ inline size_t ground_filter_aux_bytes(uint32_t n)
 	return sizeof(GfState) + 64 + (ns + 2 * nblk + 16 + 8 * (size_t)MULLS_GF_MAXCELLS + ns * nc_room) * sizeof(uint32_t);
 }
 
-// one scan of mulls_extract_features_batch's ground filter: what launch_ground_filter takes as arguments, as a table entry in device memory.
+// one scan of the ground filter, as a table entry in device memory.
 // The kernels of a lock-step launch find their scan at blockIdx.y; n == 0: the scan takes no part.
 struct GfScan
 {
@@ -72,7 +70,7 @@ struct GfScan
 	void *aux;
 	GfRansac R;
 };
-// the same launch sequence as launch_ground_filter, once for the `count` scans of tab_dev (tab_host: its host copy); returns the kernels launched
+// the filter's launch sequence, once for the `count` scans of tab_dev (tab_host: its host copy); returns the kernels launched
 int launch_ground_filter_batch(hipStream_t st, const GfScan *tab_dev, const GfScan *tab_host, uint32_t count, const mulls_ground_params &P);
 
 // estimate_ground_normal_method 1 / 2: pcl::NormalEstimationOMP over the n_ground records at `ground` (radius > 0: every neighbour within it,
@@ -87,7 +85,6 @@ struct RawMaskArgs // dist_filter (cfilter.hpp:806-832) and scanner_filter (cfil
 	double dist_min_sq, dist_max_sq; // xy_dist_min * xy_dist_min, xy_dist_max * xy_dist_max as the reference forms them (doubles)
 	float self_radius, ghost_radius, z_min_ghost, z_min_global;
 };
-void launch_raw_mask(hipStream_t st, const float4 *pts, uint32_t n, const RawMaskArgs &a, uint8_t *mask);
 struct RawMaskJob // one scan of a lock-step launch (blockIdx.y)
 {
 	const float4 *pts;

@@ -806,9 +806,10 @@ __device__ __forceinline__ void d_cl_gather(const float4 *__restrict__ in, const
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The kernels: every body above once with its arguments by value (one cloud: mulls_classify_nground) and once with the arguments of the scan at
-// blockIdx.y (the suppression kernels, whose blockIdx.y is the class: blockIdx.z) of a table in device memory (mulls_extract_features_batch).
-// The table entry is wave-uniform: scalar loads.  A workgroup past its scan's size leaves through the body's own bound check.
+// The kernels: every body above with the arguments of the scan at blockIdx.y (the suppression kernels, whose blockIdx.y is the class: blockIdx.z)
+// of a table in device memory (extract_batch.cpp; a single call's table has one entry).  The table entry is wave-uniform: scalar loads.  A workgroup
+// past its scan's size leaves through the body's own bound check.  The grid, the suppression and the gather exist with their arguments by value too,
+// for the callers outside the feature chain (k_ground_normals.hip, nms.cpp, vox_run).
 __global__ __launch_bounds__(256) void k_cl_bbox(const float4 *__restrict__ recs, uint32_t n, ClGrid *g) { d_cl_bbox(recs, n, g); }
 __global__ void k_cl_setup(ClGrid *g, float cell_hint) { d_cl_setup(g, cell_hint); }
 __global__ __launch_bounds__(256) void k_cl_count(const float4 *__restrict__ recs, uint32_t n, const ClGrid *__restrict__ g, uint32_t *__restrict__ cellof, uint32_t *__restrict__ cnt) { d_cl_count(recs, n, g, cellof, cnt); }
@@ -816,17 +817,11 @@ __global__ __launch_bounds__(256) void k_cl_scan_seg(const uint32_t *__restrict_
 __global__ __launch_bounds__(1024) void k_cl_scan_top(uint32_t *__restrict__ seg_sum, const ClGrid *__restrict__ g) { d_cl_scan_top(seg_sum, g); }
 __global__ __launch_bounds__(256) void k_cl_scan_apply(uint32_t *__restrict__ v, const ClGrid *__restrict__ g, const uint32_t *__restrict__ seg_sum, uint32_t *__restrict__ copy) { d_cl_scan_apply(v, g, seg_sum, copy); }
 __global__ __launch_bounds__(256) void k_cl_scatter(const float4 *__restrict__ recs, uint32_t n, const uint32_t *__restrict__ cellof, uint32_t *__restrict__ fill, float4 *__restrict__ sorted) { d_cl_scatter(recs, n, cellof, fill, sorted); }
-__global__ __launch_bounds__(256) void k_cl_knn(ClArrays A, ClParams P) { d_cl_knn(A, P); }
-__global__ __launch_bounds__(256) void k_cl_eig(ClArrays A, ClParams P) { d_cl_eig(A, P); }
-__global__ __launch_bounds__(256) void k_cl_label(ClArrays A, ClParams P) { d_cl_label(A, P); }
-__global__ __launch_bounds__(256) void k_cl_promote(ClArrays A, ClParams P, uint32_t round) { d_cl_promote(A, P, A.round_cnt + round); }
-__global__ __launch_bounds__(256) void k_cl_encode(ClArrays A, ClParams P) { d_cl_encode(A, P); }
 __global__ __launch_bounds__(256) void k_cl_nms_lists(ClNmsArgs a) { d_cl_nms_lists(a); }
 __global__ __launch_bounds__(256) void k_cl_nms_init(ClNmsArgs a, uint32_t *round_cnt) { d_cl_nms_init(a, round_cnt); }
 __global__ __launch_bounds__(256) void k_cl_nms_reserve(ClNmsArgs a) { d_cl_nms_reserve(a); }
 __global__ __launch_bounds__(256) void k_cl_nms_lists_long(ClNmsArgs a) { d_cl_nms_lists_long(a); }
 __global__ __launch_bounds__(256) void k_cl_nms_round(ClNmsArgs a, uint32_t *round_cnt) { d_cl_nms_round(a, round_cnt); }
-__global__ __launch_bounds__(256) void k_cl_keys(const float4 *__restrict__ recs, uint32_t n, float *__restrict__ keys) { d_cl_keys(recs, n, keys); }
 __global__ __launch_bounds__(256) void k_cl_gather(const float4 *__restrict__ in, const uint32_t *__restrict__ perm, float4 *__restrict__ out, uint32_t n) { d_cl_gather(in, perm, out, n); }
 
 #define CL_BATCH(name, bounds, extra, call)                                          \
@@ -899,24 +894,6 @@ void launch_cl_grid(hipStream_t st, const ClArrays &A, const ClParams &P)
 	hipLaunchKernelGGL(k_cl_scan_apply, dim3(max_seg), dim3(256), 0, st, A.cell_start, A.grid, A.seg_sum, A.cell_fill);
 	hipLaunchKernelGGL(k_cl_scatter, dim3(nb), dim3(256), 0, st, A.recs, n, A.cellof, A.cell_fill, A.sorted);
 }
-void launch_cl_pca(hipStream_t st, const ClArrays &A, const ClParams &P)
-{
-	const uint32_t nq = (P.n + (uint32_t)P.down_rate - 1u) / (uint32_t)P.down_rate;
-	hipLaunchKernelGGL(k_cl_knn, dim3((nq + 3u) / 4u), dim3(256), 0, st, A, P);
-	hipLaunchKernelGGL(k_cl_eig, dim3((nq + 255u) / 256u), dim3(256), 0, st, A, P);
-}
-void launch_cl_label(hipStream_t st, const ClArrays &A, const ClParams &P)
-{
-	hipLaunchKernelGGL(k_cl_label, dim3((P.n + 255u) / 256u), dim3(256), 0, st, A, P);
-}
-void launch_cl_promote_round(hipStream_t st, const ClArrays &A, const ClParams &P, uint32_t round)
-{
-	hipLaunchKernelGGL(k_cl_promote, dim3((P.n + 255u) / 256u), dim3(256), 0, st, A, P, round);
-}
-void launch_cl_encode_and_masks(hipStream_t st, const ClArrays &A, const ClParams &P)
-{
-	hipLaunchKernelGGL(k_cl_encode, dim3((P.n + 255u) / 256u), dim3(256), 0, st, A, P);
-}
 void launch_cl_nms_lists(hipStream_t st, const ClNmsArgs &a, uint32_t *round_cnt)
 {
 	uint32_t nmax = 0;
@@ -938,11 +915,6 @@ void launch_cl_nms_round(hipStream_t st, const ClNmsArgs &a, uint32_t *round_cnt
 		nmax = max(nmax, a.n[c]);
 	if (nmax)
 		hipLaunchKernelGGL(k_cl_nms_round, dim3((nmax + 255u) / 256u, 4), dim3(256), 0, st, a, round_cnt);
-}
-void launch_cl_keys(hipStream_t st, const float4 *recs, uint32_t n, float *keys)
-{
-	if (n)
-		hipLaunchKernelGGL(k_cl_keys, dim3((n + 255u) / 256u), dim3(256), 0, st, recs, n, keys);
 }
 void launch_cl_gather(hipStream_t st, const float4 *in, const uint32_t *perm, float4 *out, uint32_t n)
 {

@@ -898,11 +898,11 @@ __device__ __forceinline__ void d_gf_write_high(const float4 *__restrict__ pts, 
 // ---------------------------------------------------------------------------------------------------------------
 
 // ---------------------------------------------------------------------------------------------------------------
-// The kernels: every body above once with its arguments by value (one scan: launch_ground_filter) and once with the arguments of the scan at
-// blockIdx.y of a table in device memory (mulls_extract_features_batch: launch_ground_filter_batch).  The table entry is wave-uniform: scalar loads.
+// The kernels: every body above with the arguments of the scan at blockIdx.y of a table in device memory (launch_ground_filter_batch; a single
+// call's table has one entry).  The table entry is wave-uniform: scalar loads.
 namespace
 {
-struct GfView // where the pieces of a scan's aux arena are (launch_ground_filter's arithmetic)
+struct GfView // where the pieces of a scan's aux arena are
 {
 	GfState *S;
 	uint32_t *seg_high, *blk_cnt, *arena;
@@ -924,8 +924,6 @@ __device__ __forceinline__ uint32_t gf_cell_room_dev(uint32_t ns) // gf_cell_roo
 	const uint32_t room = (64u << 20) / (ns ? ns : 1u);
 	return room < MULLS_GF_MAXCELLS ? room : MULLS_GF_MAXCELLS;
 }
-#define GF_ONE(name, bounds, params, args) \
-	__global__ __launch_bounds__(bounds) void name params { args; }
 // a lock-step kernel: `limit` workgroups of the launch belong to the scan (the launch is as wide as the widest scan needs)
 #define GF_BATCH(name, bounds, extra, limit, call)                                 \
 	__global__ __launch_bounds__(bounds) void name(const GfScan *__restrict__ tab extra) \
@@ -940,41 +938,7 @@ __device__ __forceinline__ uint32_t gf_cell_room_dev(uint32_t ns) // gf_cell_roo
 	}
 #define GF_COMMA ,
 #define GF_SEGB ((v.ns + MULLS_GF_BLOCK / 64 - 1) / (MULLS_GF_BLOCK / 64))
-GF_ONE(k_gf_bbox, MULLS_GF_BLOCK, (const float4 *__restrict__ pts, uint32_t n, GfState *S), d_gf_bbox(pts, n, S))
-GF_ONE(k_gf_setup, 512, (const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, GfState *S, uint32_t max_cells), d_gf_setup(pts, n, P, S, max_cells))
-GF_ONE(k_gf_init, MULLS_GF_BLOCK, (const GfState *S, uint32_t *arena, uint32_t ns), d_gf_init(S, arena, ns))
-template <int MODE>
-__global__ __launch_bounds__(MULLS_GF_BLOCK) void k_gf_walk(const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns,
-															 uint32_t *__restrict__ ids, uint16_t *__restrict__ cellof, uint32_t *__restrict__ seg_high)
-{
-	d_gf_walk<MODE>(pts, n, P, S, arena, ns, ids, cellof, seg_high);
-}
-GF_ONE(k_gf_prefix, 1024, (GfState * S, uint32_t *arena, uint32_t ns), d_gf_prefix(S, arena, ns))
-GF_ONE(k_gf_cells1, MULLS_GF_BLOCK, (const GfState *S, uint32_t *arena, uint32_t ns), d_gf_cells1(S, arena, ns))
-GF_ONE(k_gf_outlier, MULLS_GF_BLOCK, (const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns, const uint32_t *__restrict__ ids),
-	   d_gf_outlier(pts, P, S, arena, ns, ids))
-GF_ONE(k_gf_cells2, MULLS_GF_BLOCK, (mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns), d_gf_cells2(P, S, arena, ns))
-GF_ONE(k_gf_verdict, MULLS_GF_BLOCK,
-	   (const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns, const uint32_t *__restrict__ ids,
-		const uint16_t *__restrict__ cellof, uint8_t *__restrict__ code, float *__restrict__ d3v, uint32_t *__restrict__ blk_cnt),
-	   d_gf_verdict(pts, P, S, arena, ns, ids, cellof, code, d3v, blk_cnt))
-GF_ONE(k_gf_ransac, MULLS_GF_BLOCK,
-	   (const float4 *__restrict__ pts, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns, const uint32_t *__restrict__ ids, uint8_t *__restrict__ code,
-		GfRansac X),
-	   d_gf_ransac(pts, P, S, arena, ns, ids, code, X))
-GF_ONE(k_gf_recount, MULLS_GF_BLOCK, (const GfState *S, const uint8_t *__restrict__ code, uint32_t *__restrict__ blk_cnt), d_gf_recount(S, code, blk_cnt))
-GF_ONE(k_gf_scan, 1024, (GfState * S, uint32_t *__restrict__ blk_cnt, uint32_t nblk, uint32_t *__restrict__ seg_high, uint32_t ns), d_gf_scan(S, blk_cnt, nblk, seg_high, ns))
-GF_ONE(k_gf_write, MULLS_GF_BLOCK,
-	   (const float4 *__restrict__ pts, const GfState *S, const uint32_t *__restrict__ ids, const uint8_t *__restrict__ code, const float *__restrict__ d3v,
-		const uint32_t *__restrict__ blk_base, float4 *__restrict__ ground, float4 *__restrict__ unground, int normal_method, const uint16_t *__restrict__ cellof,
-		const float4 *__restrict__ cell_nrm),
-	   d_gf_write(pts, S, ids, code, d3v, blk_base, ground, unground, normal_method, cellof, cell_nrm))
-GF_ONE(k_gf_write_high, MULLS_GF_BLOCK,
-	   (const float4 *__restrict__ pts, uint32_t n, mulls_ground_params P, const GfState *S, uint32_t *arena, uint32_t ns, const uint32_t *__restrict__ seg_base,
-		float4 *__restrict__ unground),
-	   d_gf_write_high(pts, n, P, S, arena, ns, seg_base, unground))
-
-// the bounding box's start values, which the single call copies from the host
+// the bounding box's start values
 __global__ void k_gf_box0_b(const GfScan *__restrict__ tab, uint32_t count)
 {
 	const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1000,41 +964,6 @@ GF_BATCH(k_gf_scan_b, 1024, , 1u, d_gf_scan(v.S, v.blk_cnt, v.nblk, v.seg_high, 
 GF_BATCH(k_gf_write_b, MULLS_GF_BLOCK, GF_COMMA int normal_method, v.nblk,
 		 d_gf_write(e.pts, v.S, e.ids, e.code, e.d3v, v.blk_cnt, e.ground, e.unground, normal_method, e.cellof, e.R.cell_nrm))
 GF_BATCH(k_gf_write_high_b, MULLS_GF_BLOCK, GF_COMMA mulls_ground_params P, GF_SEGB, d_gf_write_high(e.pts, e.n, P, v.S, v.arena, v.ns, v.seg_high, e.unground))
-
-int launch_ground_filter(hipStream_t st, const float4 *pts, uint32_t n, const mulls_ground_params &P, uint32_t *ids, uint16_t *cellof, uint8_t *code, float *d3v,
-						 float4 *ground, float4 *unground, void *aux, const GfRansac &R)
-{
-	const uint32_t ns = (n + MULLS_GF_SEG - 1) / MULLS_GF_SEG, nblk = (n + MULLS_GF_BLOCK - 1) / MULLS_GF_BLOCK;
-	GfState *S = static_cast<GfState *>(aux);
-	uint32_t *seg_high = reinterpret_cast<uint32_t *>(static_cast<unsigned char *>(aux) + ((sizeof(GfState) + 63) & ~(size_t)63));
-	uint32_t *blk_cnt = seg_high + ns;
-	uint32_t *arena = blk_cnt + 2 * nblk + 16;
-	static const uint32_t box0[4] = {0xffffffffu, 0xffffffffu, 0u, 0u};
-	if (hipMemcpyAsync(&S->box[0], box0, sizeof(box0), hipMemcpyHostToDevice, st) != hipSuccess)
-		return -1;
-	const uint32_t seg_blocks = (ns + MULLS_GF_BLOCK / 64 - 1) / (MULLS_GF_BLOCK / 64);
-	hipLaunchKernelGGL(k_gf_bbox, dim3(std::min<uint32_t>(nblk, 64u)), dim3(MULLS_GF_BLOCK), 0, st, pts, n, S);
-	hipLaunchKernelGGL(k_gf_setup, dim3(1), dim3(512), 0, st, pts, n, P, S, (uint32_t)gf_cell_room(n));
-	hipLaunchKernelGGL(k_gf_init, dim3(512), dim3(MULLS_GF_BLOCK), 0, st, S, arena, ns);
-	hipLaunchKernelGGL(k_gf_walk<0>, dim3(seg_blocks), dim3(MULLS_GF_BLOCK), 0, st, pts, n, P, S, arena, ns, ids, cellof, seg_high);
-	hipLaunchKernelGGL(k_gf_prefix, dim3(1), dim3(1024), 0, st, S, arena, ns);
-	hipLaunchKernelGGL(k_gf_walk<1>, dim3(seg_blocks), dim3(MULLS_GF_BLOCK), 0, st, pts, n, P, S, arena, ns, ids, cellof, seg_high);
-	hipLaunchKernelGGL(k_gf_cells1, dim3(MULLS_GF_MAXCELLS / MULLS_GF_BLOCK), dim3(MULLS_GF_BLOCK), 0, st, S, arena, ns);
-	if (P.apply_grid_wise_outlier_filter)
-		hipLaunchKernelGGL(k_gf_outlier, dim3(MULLS_GF_MAXCELLS / (MULLS_GF_BLOCK / 64)), dim3(MULLS_GF_BLOCK), 0, st, pts, P, S, arena, ns, ids);
-	hipLaunchKernelGGL(k_gf_cells2, dim3(MULLS_GF_MAXCELLS / MULLS_GF_BLOCK), dim3(MULLS_GF_BLOCK), 0, st, P, S, arena, ns);
-	hipLaunchKernelGGL(k_gf_verdict, dim3(nblk), dim3(MULLS_GF_BLOCK), 0, st, pts, P, S, arena, ns, ids, cellof, code, d3v, blk_cnt);
-	if (P.estimate_ground_normal_method == 3)
-	{
-		hipLaunchKernelGGL(k_gf_ransac, dim3(MULLS_GF_MAXCELLS / (MULLS_GF_BLOCK / 64)), dim3(MULLS_GF_BLOCK), 0, st, pts, P, S, arena, ns, ids, code, R);
-		hipLaunchKernelGGL(k_gf_recount, dim3(nblk), dim3(MULLS_GF_BLOCK), 0, st, S, code, blk_cnt);
-	}
-	hipLaunchKernelGGL(k_gf_scan, dim3(1), dim3(1024), 0, st, S, blk_cnt, nblk, seg_high, ns);
-	hipLaunchKernelGGL(k_gf_write, dim3(nblk), dim3(MULLS_GF_BLOCK), 0, st, pts, S, ids, code, d3v, blk_cnt, ground, unground, (int)P.estimate_ground_normal_method,
-					   cellof, R.cell_nrm);
-	hipLaunchKernelGGL(k_gf_write_high, dim3(seg_blocks), dim3(MULLS_GF_BLOCK), 0, st, pts, n, P, S, arena, ns, seg_high, unground);
-	return 0;
-}
 
 #define GF_GO(...)                      \
 	do                                  \
@@ -1099,7 +1028,6 @@ __device__ __forceinline__ void d_raw_mask(const float4 *__restrict__ pts, uint3
 	}
 	mask[i] = keep ? 1 : 0;
 }
-__global__ __launch_bounds__(256) void k_raw_mask(const float4 *__restrict__ pts, uint32_t n, RawMaskArgs a, uint8_t *__restrict__ mask) { d_raw_mask(pts, n, a, mask); }
 __global__ __launch_bounds__(256) void k_raw_mask_b(const RawMaskJob *__restrict__ tab, RawMaskArgs a)
 {
 	const RawMaskJob e = tab[blockIdx.y];
@@ -1110,12 +1038,6 @@ void launch_raw_mask_batch(hipStream_t st, const RawMaskJob *tab, uint32_t count
 	if (n_max && count)
 		hipLaunchKernelGGL(k_raw_mask_b, dim3((n_max + 255u) / 256u, count), dim3(256), 0, st, tab, a);
 }
-void launch_raw_mask(hipStream_t st, const float4 *pts, uint32_t n, const RawMaskArgs &a, uint8_t *mask)
-{
-	if (n)
-		hipLaunchKernelGGL(k_raw_mask, dim3((n + 255u) / 256u), dim3(256), 0, st, pts, n, a, mask);
-}
-
 // CFilter::voxel_downsample (cfilter.hpp:83-160), device part: pcl::getMinMax3D as ordered keys (box[0..2] min, box[3..5] max, box[6] != 0: a
 // non-finite coordinate) and the voxel index of every point (:128-139: float difference times the float inverse size, floor, 64-bit index).
 __global__ __launch_bounds__(256) void k_vox_bbox(const float4 *__restrict__ pts, uint32_t n, uint32_t *__restrict__ box)

@@ -1,4 +1,4 @@
-// rounds.h — the host loop around a device fixed point that is settled by repeated launches (classify.cpp: the promotion of vertex candidates and the
+// rounds.h — the host loop around a device fixed point that is settled by repeated launches (extract_batch.cpp: the promotion of vertex candidates and the
 // suppression rounds of the class clouds; nms.cpp: the multi-launch path of mulls_non_max_suppress).
 #pragma once
 #include "ctx.h"

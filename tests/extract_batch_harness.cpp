@@ -23,6 +23,31 @@ extern "C"
 		const ScanCost c = extract_batch_scan_cost(n, prefilter != 0, normal_method, fixed_num != 0, unground_down_fixed_num, K);
 		out[0] = c.gf, out[1] = c.cl, out[2] = c.total;
 	}
+	// ... of a scan that is voxel-down-sampled ahead of the ground filter (a sub-batch of one), and the ground arena it is measured against
+	void eb_scan_cost_vox(uint32_t n, int prefilter, int voxels, int normal_method, int fixed_num, int unground_down_fixed_num, uint32_t K, uint64_t *out)
+	{
+		const ScanCost c = extract_batch_scan_cost(n, prefilter != 0, normal_method, fixed_num != 0, unground_down_fixed_num, K, voxels != 0);
+		out[0] = c.gf, out[1] = c.cl, out[2] = c.total;
+	}
+	uint64_t eb_gf_total_vox(uint32_t n, int prefilter, int voxels, int normal_method) { return gf_layout(n, prefilter != 0, voxels != 0, normal_method).total; }
+	// the cuts with at most max_scans scans per sub-batch (1: the scan-local steps)
+	uint32_t eb_cuts_max(const uint64_t *bytes, uint32_t count, uint64_t limit, uint32_t max_scans, uint32_t *out)
+	{
+		std::vector<uint32_t> cuts;
+		extract_batch_cuts(bytes, count, limit, &cuts, max_scans);
+		for (size_t k = 0; k < cuts.size(); k++)
+			out[k] = cuts[k];
+		return (uint32_t)cuts.size();
+	}
+	uint32_t eb_ex_count(void) { return MULLS_EX_COUNT; }
+	// out: MULLS_EX_COUNT offsets, where the selection indices start, the bytes the block needs
+	void eb_block_layout(const uint32_t *cnt, uint64_t n_idx, uint64_t *out)
+	{
+		const BlockLayout b = block_layout(cnt, (size_t)n_idx);
+		for (int k = 0; k < MULLS_EX_COUNT; k++)
+			out[k] = b.off[k];
+		out[MULLS_EX_COUNT] = b.o_idx, out[MULLS_EX_COUNT + 1] = b.need;
+	}
 	uint32_t eb_cuts(const uint64_t *bytes, uint32_t count, uint64_t limit, uint32_t *out)
 	{
 		std::vector<uint32_t> cuts;
@@ -101,6 +126,48 @@ int main()
 				}
 				EB_REQUIRE(at == arena);
 			}
+		}
+	}
+	// the voxel flag: never cheaper, and the ground arena gf_layout gives with it
+	for (uint32_t n : sizes)
+		for (int method = 0; method < 4; method++)
+		{
+			uint64_t with[3], without[3];
+			eb_scan_cost_vox(n, 1, 1, method, 1, 3000, 50, with);
+			eb_scan_cost_vox(n, 1, 0, method, 1, 3000, 50, without);
+			EB_REQUIRE(with[0] >= without[0] && with[1] == without[1] && with[2] == with[0] + with[1] + MULLS_EXB_TABLE_BYTES);
+			EB_REQUIRE(with[0] == (n ? up256(eb_gf_total_vox(n, 1, 1, method)) : 0u));
+		}
+	// the one-scan cut rule: `count` sub-batches whatever the limit
+	{
+		std::vector<uint64_t> bytes(count, MULLS_EXB_TABLE_BYTES);
+		bytes[3] = (uint64_t)1 << 33;
+		for (uint64_t limit : {(uint64_t)1, (uint64_t)1 << 20, ~(uint64_t)0})
+		{
+			std::vector<uint32_t> cuts(count + 2);
+			EB_REQUIRE(eb_cuts_max(bytes.data(), count, limit, 1, cuts.data()) == count + 1);
+			for (uint32_t b = 0; b <= count; b++)
+				EB_REQUIRE(cuts[b] == b);
+		}
+	}
+	// the block layout against the two forms it replaces: the offsets' loop, and the indices 128 bytes + their own size ahead of the end
+	{
+		const uint32_t counts[][3] = {{0, 0, 0}, {16, 0, 5}, {4097, 2049, 0}, {1, 1, 1}, {121000, 60500, 20000}}; // 16 records: 768 bytes, a multiple of 256 already
+		for (const uint32_t *c : counts)
+		{
+			uint32_t cnt[MULLS_EX_COUNT];
+			for (int k = 0; k < MULLS_EX_COUNT; k++)
+				cnt[k] = c[k % 3] + (k > 8 ? (uint32_t)k : 0u) * (c[0] ? 1u : 0u);
+			const uint64_t n_idx = c[1];
+			uint64_t got[MULLS_EX_COUNT + 2], need = 0;
+			eb_block_layout(cnt, n_idx, got);
+			for (int k = 0; k < MULLS_EX_COUNT; k++)
+			{
+				EB_REQUIRE(got[k] == need && got[k] % 256 == 0);
+				need += ((uint64_t)cnt[k] * MULLS_POINT_BYTES + 255) & ~(uint64_t)255;
+			}
+			need += n_idx * 4 + 256;
+			EB_REQUIRE(got[MULLS_EX_COUNT + 1] == need && got[MULLS_EX_COUNT] == need - (n_idx * 4 + 128));
 		}
 	}
 	std::vector<uint32_t> none(2);

@@ -151,6 +151,57 @@ def test_cuts_and_offsets(planner, shape):
     assert cuts_of(planner, [table] * (cap + 5), 1 << 40) == [0, cap, cap + 5]  # the grid axis bounds a sub-batch too
 
 
+def test_voxel_flag_of_the_scan_cost(planner):
+    """a scan that is voxel-down-sampled ahead of the ground filter: never cheaper than without, and the ground arena gf_layout gives with the flag"""
+    planner.eb_scan_cost_vox.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p]
+    planner.eb_gf_total_vox.restype, planner.eb_gf_total_vox.argtypes = C.c_uint64, [C.c_uint32, C.c_int, C.c_int, C.c_int]
+    table = planner.eb_table_bytes()
+    for n in SIZES:
+        for prefilter in (0, 1):
+            for method in (0, 1, 2, 3):
+                a, b = (C.c_uint64 * 3)(), (C.c_uint64 * 3)()
+                planner.eb_scan_cost_vox(n, prefilter, 1, method, 1, 3000, 50, a)
+                planner.eb_scan_cost_vox(n, prefilter, 0, method, 1, 3000, 50, b)
+                assert a[0] >= b[0] and a[1] == b[1] and a[2] == a[0] + a[1] + table
+                assert a[0] == (up256(planner.eb_gf_total_vox(n, prefilter, 1, method)) if n else 0)
+                assert n == 0 or a[0] > b[0]  # the keys and the order take room
+                assert b[0] == (up256(planner.eb_gf_total(n, prefilter, method)) if n else 0)
+
+
+def test_one_scan_cuts(planner):
+    """the scan-local steps: `count` sub-batches of one scan each, whatever the limit"""
+    planner.eb_cuts_max.restype, planner.eb_cuts_max.argtypes = C.c_uint32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
+    need = [c[2] for c in costs(planner, SIZES, SHAPES["K"])]
+    arr, out = (C.c_uint64 * len(need))(*need), (C.c_uint32 * (len(need) + 2))()
+    for limit in (1, need[0], planner.eb_head_bytes() + sum(need), 1 << 62):
+        assert planner.eb_cuts_max(arr, len(need), limit, 1, out) == len(need) + 1
+        assert list(out[:len(need) + 1]) == list(range(len(need) + 1))
+        k = planner.eb_cuts_max(arr, len(need), limit, planner.eb_max_scans(), out)
+        assert list(out[:k]) == cuts_of(planner, need, limit)  # the default is the grid axis's bound
+    assert planner.eb_cuts_max(arr, 0, 1, 1, out) == 1 and out[0] == 0
+
+
+def test_block_layout(planner):
+    """a feature block's buffer against the two hand-written forms the function replaces: offsets rounded to 256, the selection indices riding at the end"""
+    planner.eb_ex_count.restype = C.c_uint32
+    planner.eb_block_layout.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+    count = planner.eb_ex_count()
+    assert count == abi.EX_COUNT
+    rec = abi.POINT_BYTES
+    cases = [([0] * count, 0), ([16] * count, 0), ([0, 0, 16, 8, 0] + [0] * (count - 5), 8),  # 16 records are 768 bytes: a multiple of 256 already
+             ([0, 0, 4097, 2049, 1900, 7, 300, 0, 41, 7, 200, 0, 17, 3][:count], 2049), ([0, 0, 121000, 60500, 20000] + [1] * (count - 5), 60500)]
+    for cnt, n_idx in cases:
+        out = (C.c_uint64 * (count + 2))()
+        planner.eb_block_layout((C.c_uint32 * count)(*cnt), n_idx, out)
+        need = 0
+        for k in range(count):
+            assert out[k] == need and out[k] % 256 == 0
+            need += (cnt[k] * rec + 255) & ~255
+        need += n_idx * 4 + 256
+        assert out[count + 1] == need and out[count] == need - (n_idx * 4 + 128)
+        assert out[count] >= out[count - 1] + cnt[count - 1] * rec and out[count] + n_idx * 4 <= need  # the indices lie behind the last cloud, inside the block
+
+
 def test_planner_under_sanitizers(tmp_path):
     """the harness as a stand-alone program (its own main checks the same properties on the same inputs), built with -fsanitize=address,undefined"""
     exe = str(tmp_path / "extract_batch_harness")

@@ -289,7 +289,7 @@ def test_a_refused_scan_in_the_middle(ctx_auto, which):
 # ---------------------------------------------------------------------------------------------------------------------------------- 7
 @pytest.mark.parametrize("case", ["voxels", "normals1", "normals2"])
 def test_single_scan_path(ctx_auto, case):
-    """7: the two parameter points that are handed to the single-scan path inside the call"""
+    """7: the two parameter points whose scans run alone inside the call (path 1: a sub-batch of one scan each, with the two scan-local steps)"""
     X = {"voxels": lambda: set_d(vf_downsample_resolution=0.5), "normals1": lambda: set_d(ground=abi.ground_params(estimate_ground_normal_method=1)),
          "normals2": lambda: set_d(ground=abi.ground_params(estimate_ground_normal_method=2, min_grid_pt_num=6))}[case]()
     assert 2 * X.ground.min_grid_pt_num <= 64

@@ -1,7 +1,9 @@
 """Feature extraction on the device vs the CPU oracle, one 64-beam scan: fast_ground_filter + classify_nground_pts.  usage gpu_features.py
 [--batch 1,8,64 [--repeats R] [--out profiles/features_batch.txt]: mulls_extract_features_batch against as many mulls_extract_features_resident calls, 121 k-return
 scans of the synthetic drive under the KITTI parameter shape — for each B the median over R alternating repeats (after a warm-up of the same shape) of one batch
-call of B scans and of B single calls, the same process, the same context; the launch / wait / round counts of the batch call; one check that the bits agree]"""
+call of B scans and of B single calls, the same process, the same context; the launch / wait / round counts of the batch call; one check that the bits agree]
+[--single-rows [--calls N]: every single entry point of the feature stage and batches of 1, 8 and 64, on 121 k-return scans and on their 4 097-point subsamples,
+KITTI parameter shape, one row each in the format tools/gpu_ab_single_calls.py parses (profiles/features_single_as_batch.txt)]"""
 import ctypes as C
 import os, sys, time, warnings
 sys.path.insert(0, "."); warnings.filterwarnings("ignore")
@@ -119,9 +121,61 @@ def batch_report(sizes, repeats, out_path):
         open(out_path, "w").write("\n".join(lines) + "\n")
 
 
+def single_rows(calls):
+    """One row per entry point and scan size: the median wall time of `calls` calls after two warm-up calls, and the call's status."""
+    full = drive_scans(64)
+    small = [np.ascontiguousarray(s[np.linspace(0, len(s) - 1, 4097).astype(np.int64)]) for s in full]
+    X = kitti_shape()
+    XV = kitti_shape()
+    XV.vf_downsample_resolution = 0.2
+    ctx = lib.Context(0)
+    L, h = ctx.lib, ctx.h
+
+    def row(name, n, fn, count):
+        fn(), fn()
+        ts = []
+        for _ in range(count):
+            t = time.perf_counter()
+            rc = fn()
+            ts.append((time.perf_counter() - t) * 1e3)
+        print("%-44s n %6d  status %d  median of %2d: %.3f ms (min %.3f, max %.3f)" % (name, n, rc, count, float(np.median(ts)), min(ts), max(ts)), flush=True)
+
+    for scans in (full, small):
+        raw = scans[0]
+        n, p = len(raw), raw.ctypes.data_as(C.c_void_p)
+        blk = lib.Block(ctx)
+        nout = (C.c_uint32 * abi.EX_COUNT)()
+        outs = [np.zeros((n, abi.POINT_BYTES), np.uint8) for _ in range(abi.EX_COUNT)]
+        out_p = (C.c_void_p * abi.EX_COUNT)(*[o.ctypes.data for o in outs])
+        cap = (C.c_uint32 * abi.EX_COUNT)(*([n] * abi.EX_COUNT))
+        n3 = (C.c_uint32 * 3)()
+        vp = lambda k: outs[k].ctypes.data_as(C.c_void_p)  # noqa: E731
+        ung = ctx.ground_filter(abi.points_of(raw), X.ground)[2]
+        up, n_after = ung.ctypes.data_as(C.c_void_p), C.c_uint32(0)
+        row("mulls_extract_features_resident", n, lambda: L.mulls_extract_features_resident(h, p, n, abi.POINT_BYTES, C.byref(X), blk.h, nout), calls)
+        row("mulls_extract_features", n, lambda: L.mulls_extract_features(h, p, n, abi.POINT_BYTES, C.byref(X), out_p, cap, nout), calls)
+        row("mulls_ground_filter", n, lambda: L.mulls_ground_filter(h, p, n, abi.POINT_BYTES, C.byref(X.ground), vp(1), n, vp(2), n, vp(3), n, n3), calls)
+        row("mulls_classify_nground", len(ung), lambda: L.mulls_classify_nground(h, up, len(ung), abi.POINT_BYTES, C.byref(X.classify), out_p, cap, nout, None, C.byref(n_after)), calls)
+        row("mulls_extract_features_resident voxels 0.2", n, lambda: L.mulls_extract_features_resident(h, p, n, abi.POINT_BYTES, C.byref(XV), blk.h, nout), calls)
+        blk.close()
+        for B in (1, 8, 64):
+            blocks = [lib.Block(ctx) for _ in range(B)]
+            clouds = (abi.Cloud * B)()
+            for i in range(B):
+                clouds[i].pts, clouds[i].n, clouds[i].stride = scans[i].ctypes.data, len(scans[i]), abi.POINT_BYTES
+            handles = (C.c_void_p * B)(*[b.h for b in blocks])
+            results = (abi.ExtractBatchResult * B)()
+            row("mulls_extract_features_batch B %2d" % B, n, lambda: L.mulls_extract_features_batch(h, clouds, B, C.byref(X), handles, 0, results, None), calls if B < 64 else max(3, calls // 4))
+            for b in blocks:
+                b.close()
+    ctx.close()
+
+
 if __name__ == "__main__":
     argv = sys.argv[1:]
-    if "--batch" in argv:
+    if "--single-rows" in argv:
+        single_rows(int(argv[argv.index("--calls") + 1]) if "--calls" in argv else 20)
+    elif "--batch" in argv:
         batch_report([int(v) for v in argv[argv.index("--batch") + 1].split(",")], int(argv[argv.index("--repeats") + 1]) if "--repeats" in argv else 9,
                      argv[argv.index("--out") + 1] if "--out" in argv else os.path.join("profiles", "features_batch.txt"))
     else:
