@@ -1551,8 +1551,9 @@ int mulls_ndt_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, uint32_t 
  *   C_ab = (v0_a v0_b + v1_a v1_b) + 0.01 (v2_a v2_b): PLANE, U diag(1, 1, 1e-2) V^T.  Upstream's JacobiSVD signs for a symmetric matrix are not
  *   reproduced.  Six doubles per point (xx xy xz yy yz zz).
  * Voxel map [upstream]  the coordinate of a float point is floorf(x / resolution - 0.5f) per axis, computed in float and cast to int (the -0.5 is
- *   upstream's and is kept).  [LIB] the key is three 21-bit fields of coordinate + 2^20; a coordinate of a cropped point outside [-2^20, 2^20), of the
- *   voxel map or of the neighbour search's cells of the same edge: MULLS_E_UNSUPPORTED.  Per occupied voxel, in ascending point index and in
+ *   upstream's and is kept).  [LIB] the key is three 21-bit fields of coordinate + 2^20; a coordinate outside [-2^20, 2^20), of a cropped target
+ *   point in the voxel map or of a cropped point of either cloud in the neighbour search's cells of the same edge (floor(x (1 / edge)) in double):
+ *   MULLS_E_UNSUPPORTED.  Per occupied voxel, in ascending point index and in
  *   double: n, the sum of the points, the sum of their C; mean = sum / n, cov = sum / n.  A voxel of one point is a voxel (upstream has no minimum).
  *   The map is an open-addressing hash table; no dense grid exists.
  * State and start [upstream]  x = (r, t), rotation vector and translation, from 0 (omp_gicp has applied the guess to the cloud).  Since |r| < 1e-2

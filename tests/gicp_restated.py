@@ -107,6 +107,14 @@ def voxel_coords(P, resolution):
     return np.where(ok[:, None], q, 0).astype(np.int64), ok
 
 
+def knn_coords(P, edge):
+    """the cells of the neighbour search, of the voxels' edge: (n, 3) float32 -> (n, 3) int64 and ok (n,): floor(x (1 / edge)) in double, inside
+    [-2^20, 2^20).  The last accepted coordinate is not voxel_coords': at 1 m, x = -1048576 and x = 1048575.875 here, -1048575.5 and 1048576.25 there."""
+    q = np.floor(np.asarray(P, np.float32).astype(np.float64) * (1.0 / float(np.float32(edge))))
+    ok = ((q >= -1048576.0) & (q < 1048576.0)).all(axis=1)
+    return np.where(ok[:, None], q, 0).astype(np.int64), ok
+
+
 def pack(c):
     return (int(c[0]) + 1048576) | ((int(c[1]) + 1048576) << 21) | ((int(c[2]) + 1048576) << 42)
 
@@ -231,8 +239,8 @@ def point_terms(ap, CA, mean, CB, R):
     return out
 
 
-def evaluate(src, C_src, vm, R, t):
-    """-> the 28 sums, n_corr"""
+def evaluate(src, C_src, vm, R, t, per_point_out=None):
+    """-> the 28 sums, n_corr; per_point_out, a list, receives the (n, 28) terms the sums are taken over"""
     ap = move(R, t, src)
     with np.errstate(all="ignore"):
         coords, ok = voxel_coords(ap.astype(np.float32), vm.resolution)
@@ -240,6 +248,8 @@ def evaluate(src, C_src, vm, R, t):
     sel = np.flatnonzero(vox >= 0)
     per_point = np.zeros((len(src), 28))
     per_point[sel] = point_terms(ap[sel], C_src[sel], vm.mean[vox[sel]], vm.cov[vox[sel]], R)
+    if per_point_out is not None:
+        per_point_out.append(per_point)
     return tree_sum(per_point), len(sel)
 
 
@@ -350,9 +360,11 @@ def gicp(tgt, src, tgt_bound, src_bound, guess, prm=None, trace=None):
                T=G.copy() if apply_guess else np.eye(4), fitness=DBL_MAX, loss=0.0)
     if len(src_c) < k or len(tgt_c) < k:
         return res
-    _, ok_t = voxel_coords(tgt_c, prm["voxel_resolution"])
-    _, ok_s = voxel_coords(src_c, prm["voxel_resolution"])
-    if not ok_t.all() or not ok_s.all():
+    # the refusal: a target point outside the voxel map's range, or a point of either cloud outside the range of the neighbour search's cells
+    _, ok_v = voxel_coords(tgt_c, prm["voxel_resolution"])
+    _, ok_t = knn_coords(tgt_c, prm["voxel_resolution"])
+    _, ok_s = knn_coords(src_c, prm["voxel_resolution"])
+    if not ok_v.all() or not ok_t.all() or not ok_s.all():
         return None
     C_src, C_tgt = covariances(src_c, k), covariances(tgt_c, k)
     vm = build_voxels(tgt_c, C_tgt, prm["voxel_resolution"])

@@ -332,8 +332,8 @@ def tree_sum(terms):
     return part[0]
 
 
-def evaluate(src, p, grid, d1, d2, with_hessian, method=DIRECT7, frame=None):
-    """the 28 sums at p"""
+def evaluate(src, p, grid, d1, d2, with_hessian, method=DIRECT7, frame=None, per_point_out=None):
+    """the 28 sums at p; per_point_out, a list, receives the (n, 28) terms the sums are taken over"""
     F = frame if frame is not None else make_frame(p)
     xp = transform(F, src)
     n = len(src)
@@ -358,6 +358,8 @@ def evaluate(src, p, grid, d1, d2, with_hessian, method=DIRECT7, frame=None):
         terms = contribution(x64[sel], xp64[sel] - grid.mean[li], grid.icov[li], F, d1, d2, with_hessian)
         with np.errstate(all="ignore"):
             per_point[sel] += terms
+    if per_point_out is not None:
+        per_point_out.append(per_point)
     return tree_sum(per_point)
 
 
