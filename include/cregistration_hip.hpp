@@ -1738,6 +1738,77 @@ inline std::vector<int> omp_gicp_batch(std::vector<constraint_t> &registration_c
 	return codes;
 }
 
+// CRegistration<PointT>::pcl_icp (include/common/cregistration.hpp:882-942), verbatim signature and defaults: the classical ICP baseline that
+// test/mulls_slam.cpp:195 names "pclicp", in one device call (mulls_pcl_icp).  The binding is one early return at the top of the member function:
+//     #ifdef MULLS_USE_HIP
+//         return lo::hip::pcl_icp<PointT>(registration_cons, max_iter_num, dis_thre_unit, metrics, ce, te, use_reciprocal_correspondence,
+//                                         use_trimmed_rejector, neighbor_radius, initial_guess, apply_intersection_filter, fitness_score_thre);
+//     #endif
+// block1->pc_down is the target, block2->pc_down the source; Trans1_2 receives the pose, the return value is upstream's process code (1 or -3).
+// metrics, ce and te are upstream's DistMetricType, CorresEstimationType and TransformEstimationType (cregistration.hpp:59-75; the library's enums
+// have their values), taken as template parameters because this header does not define them.  Plane2Plane, LM, NS and the trimmed rejector are not
+// built: the call throws with MULLS_E_UNSUPPORTED's message.  With an identity guess upstream registers an empty source (include/mulls_hip.h);
+// this call registers block2->pc_down.
+inline mulls_pcl_icp_params pcl_icp_params(int max_iter_num, float dis_thre_unit, int metrics, int ce, int te, bool use_reciprocal_correspondence,
+										   bool use_trimmed_rejector, float neighbor_radius = 2.0, bool apply_intersection_filter = true,
+										   float fitness_score_thre = 10.0)
+{
+	mulls_pcl_icp_params P;
+	mulls_pcl_icp_default_params(&P);
+	P.max_iter_num = max_iter_num, P.dis_thre_unit = dis_thre_unit, P.metrics = metrics, P.ce = ce, P.te = te;
+	P.use_reciprocal_correspondence = use_reciprocal_correspondence ? 1 : 0, P.use_trimmed_rejector = use_trimmed_rejector ? 1 : 0;
+	P.neighbor_radius = neighbor_radius, P.apply_intersection_filter = apply_intersection_filter ? 1 : 0, P.fitness_score_thre = fitness_score_thre;
+	return P;
+}
+template <typename PointT, typename Metric, typename Ce, typename Te>
+inline int pcl_icp(constraint_t &registration_cons, int max_iter_num, float dis_thre_unit, Metric metrics, Ce ce, Te te, bool use_reciprocal_correspondence,
+				   bool use_trimmed_rejector, float neighbor_radius = 2.0, Eigen::Matrix4d initial_guess = Eigen::Matrix4d::Identity(),
+				   bool apply_intersection_filter = true, float fitness_score_thre = 10.0)
+{
+	mulls_ctx *ctx = thread_context();
+	mulls_pcl_icp_problem P;
+	detail::ndt_fill(registration_cons, initial_guess, P);
+	const mulls_pcl_icp_params prm = pcl_icp_params(max_iter_num, dis_thre_unit, (int)metrics, (int)ce, (int)te, use_reciprocal_correspondence, use_trimmed_rejector,
+													neighbor_radius, apply_intersection_filter, fitness_score_thre);
+	mulls_pcl_icp_result R;
+	const int rc = mulls_pcl_icp(ctx, &P, &prm, &R);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_pcl_icp failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (int k = 0; k < 16; k++)
+		registration_cons.Trans1_2.data()[k] = R.T[k];
+	return R.code;
+}
+// many constraints in one call (mulls_pcl_icp_batch): every constraint with the bits of its pcl_icp call; initial_guesses is empty (identity for all)
+// or one matrix per constraint.  Returns the process codes.
+template <typename PointT, typename Metric, typename Ce, typename Te>
+inline std::vector<int> pcl_icp_batch(std::vector<constraint_t> &registration_cons, int max_iter_num, float dis_thre_unit, Metric metrics, Ce ce, Te te,
+									  bool use_reciprocal_correspondence, bool use_trimmed_rejector, float neighbor_radius = 2.0,
+									  const std::vector<Eigen::Matrix4d, Eigen::aligned_allocator<Eigen::Matrix4d>> &initial_guesses = {},
+									  bool apply_intersection_filter = true, float fitness_score_thre = 10.0)
+{
+	const size_t B = registration_cons.size();
+	if (!initial_guesses.empty() && initial_guesses.size() != B)
+		throw std::runtime_error("lo::hip::pcl_icp_batch: one initial guess per constraint, or none");
+	mulls_ctx *ctx = thread_context();
+	std::vector<mulls_pcl_icp_problem> problems(B);
+	for (size_t k = 0; k < B; k++)
+		detail::ndt_fill(registration_cons[k], initial_guesses.empty() ? Eigen::Matrix4d(Eigen::Matrix4d::Identity()) : initial_guesses[k], problems[k]);
+	const mulls_pcl_icp_params prm = pcl_icp_params(max_iter_num, dis_thre_unit, (int)metrics, (int)ce, (int)te, use_reciprocal_correspondence, use_trimmed_rejector,
+													neighbor_radius, apply_intersection_filter, fitness_score_thre);
+	std::vector<mulls_pcl_icp_result> R(B);
+	const int rc = mulls_pcl_icp_batch(ctx, problems.data(), (uint32_t)B, &prm, R.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_pcl_icp_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	std::vector<int> codes(B);
+	for (size_t k = 0; k < B; k++)
+	{
+		for (int e = 0; e < 16; e++)
+			registration_cons[k].Trans1_2.data()[e] = R[k].T[e];
+		codes[k] = R[k].code;
+	}
+	return codes;
+}
+
 } // namespace hip
 } // namespace lo
 

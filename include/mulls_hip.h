@@ -1578,7 +1578,7 @@ int mulls_ndt_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, uint32_t 
  *   the float squared distance from float(a') under the final x to the nearest cropped target point; code = fitness > fitness_score_thre ? -3 : 1.
  *   loss = the last evaluation's e . e sum, n_corr its count.
  * Not built: plain GICP (using_voxel_gicp = false); FastVGICP's DIRECT7 / DIRECT27, MULTIPLICATIVE / ADDITIVE_WEIGHTED voxels and the other
- *   regularisations (omp_gicp cannot select them); keeping a cloud's covariances between calls; pcl_icp. */
+ *   regularisations (omp_gicp cannot select them); keeping a cloud's covariances between calls. */
 enum mulls_gicp_stop
 {
 	MULLS_GICP_STOP_NONE = 0, /* no registration ran */
@@ -1619,6 +1619,131 @@ int mulls_gicp(mulls_ctx *ctx, const mulls_gicp_problem *problem, const mulls_gi
  * step: a tick is one evaluation launch over the problems that still run, one launch that solves and updates every problem, and one 4-byte readback;
  * at most max_iterations ticks.  Sub-batches are sized by params->scratch_limit_bytes; a problem larger than the limit runs alone.  n_problems = 0: MULLS_OK. */
 int mulls_gicp_batch(mulls_ctx *ctx, const mulls_gicp_problem *problems, uint32_t n_problems, const mulls_gicp_params *params, mulls_gicp_result *results);
+
+/* ---- Classical ICP registration: CRegistration::pcl_icp (cregistration.hpp:882-942) over icp_registration (:84-315), the part of it that is plain
+ * ICP: pcl::IterativeClosestPoint / IterativeClosestPointWithNormals with nearest-neighbour correspondences within a distance, optionally reciprocal,
+ * TransformationEstimationSVD or TransformationEstimationPointToPlaneLLS, DefaultConvergenceCriteria, get_pc_normal_pcar and
+ * pcl::Registration::getFitnessScore.  NOTHING WAS COMPARED WITH PCL, FLANN OR EIGEN THEMSELVES (none is a dependency of this repository, and no PCL
+ * source was at hand): the skeleton was read from cregistration.hpp and pca.hpp, and what PCL 1.8.1 does inside was restated FROM MEMORY; those
+ * clauses say so.  The yardstick is a numpy restatement of this text (tests/pcl_icp_restated.py).  [upstream]: kept as upstream has it; [LIB]:
+ * defined here.  Every 3-term dot product is (u0 v0 + u1 v1) + u2 v2; sin and cos are detmath.h's correctly rounded ones; no contraction.
+ *
+ * Pre-steps [upstream, pcl_icp]  exactly mulls_ndt's (the same code runs): pc_down clouds, the isIdentity(1e-6) rule, the guess applied to the source
+ *   in double and stored as float, get_intersection_bbx, the crop, T = T_icp * guess at the end.  Quirk NOT kept: with an identity guess upstream never
+ *   fills cloud_s_guess (:895-917), hands icp_registration an empty source and registers nothing (identity, fitness DBL_MAX, code -3); [LIB] with an
+ *   identity guess the source is block2->pc_down itself.  [LIB] a cloud that is empty after the crop: no registration runs, T = guess (or identity),
+ *   fitness = DBL_MAX, code = -3, converged = 0, stop = MULLS_PCL_ICP_STOP_NONE (mulls_ndt's rule).  max_iter_num and dis_thre_unit have no default
+ *   upstream; [LIB] 20 and 1.5, mm_lls_icp's.  transformation_epsilon 1e-8 and euclidean_fitness_epsilon 1e-5 are the constants of :136-138.
+ * d2 [upstream]  of two float points: dx = ax - bx, ..; ((dx dx + dy dy) + dz dz) in float.
+ * Correspondences [upstream set, LIB tie order]  for the moved source point i, in ascending i: m = the cropped target point smallest by (d2, index);
+ *   the pair is dropped when (double)d2 > (double)dis_thre_unit * (double)dis_thre_unit.  use_reciprocal_correspondence: i keeps its pair only if i
+ *   is the smallest of all moved source points by (d2 to m, index).  No other rejector runs.  FLANN's tie order is unknown and not claimed.  Fewer
+ *   than 3 pairs end the loop: converged = 0, stop = MULLS_PCL_ICP_STOP_NO_CORRESPONDENCES, the pose reached so far is kept.
+ *   [LIB] the search walks hash tables of cubic cells (no dense grid) of edge dis_thre_unit (1 + 2^-20), cell = floor(x (1 / edge)) in double, and
+ *   looks into the 27 cells around a point's own.  The margin makes the walk exact: a pair the float test accepts is apart by at most
+ *   dis_thre_unit (1 + 2^-23) per axis, below one edge however the two products round.  The reciprocity test needs no unbounded search either: a
+ *   source point that beats i at m lies within d(i, m) <= dis_thre_unit of m.  A coordinate of a cropped cloud outside [-2^20, 2^20) cells (of either
+ *   edge, below): MULLS_E_UNSUPPORTED; a source point that leaves that range while it is moved takes no part in that iteration.
+ * Sums [LIB]  over the pairs in ascending source index, in double: MULLS_NDT_TREE's strided-partial rule (lane l adds the pairs of the source points
+ *   l, l + MULLS_NDT_TREE, .. in order, then the halving tree).
+ * Point-to-point step [upstream shape: TransformationEstimationSVD, Umeyama without scale; from memory]  cs, ct = the sums of the paired moved source
+ *   points and of their target points, each divided by the number of pairs; H_ab = the sum of (s_a - cs_a) (t_b - ct_b); R = the proper rotation that
+ *   maximises trace(R H); t = ct - R cs.  [LIB] R by csrc/ransac_math.h's decomposition kept in double (Horn's symmetric 4 x 4, ten sweeps of cyclic
+ *   Jacobi, the eigenvector of the largest diagonal entry as a unit quaternion); upstream's float JacobiSVD is not reproduced.
+ * Point-to-plane step [upstream shape: TransformationEstimationPointToPlaneLLS; from memory]  per pair, with s the moved source point, t its target
+ *   point and n the target point's normal as doubles: row = (s x n, n) with s x n = (s1 n2 - s2 n1, s2 n0 - s0 n2, s0 n1 - s1 n0), b = n . (t - s);
+ *   the sums of row_i row_k for i <= k row by row (21) and of row_i b (6); x = (alpha, beta, gamma, tx, ty, tz) solves them.  [LIB] by
+ *   csrc/gicp_math.h's 6 x 6 Cholesky; a pivot that is <= 0 or not finite or a non-finite x ends the loop: converged = 0, stop =
+ *   MULLS_PCL_ICP_STOP_SINGULAR, the pose reached so far is kept.  R = Rz(gamma) Ry(beta) Rx(alpha), written out: R00 = cg cb, R01 = (-sg) ca +
+ *   (cg sb) sa, R02 = sg sa + (cg sb) ca, R10 = sg cb, R11 = cg ca + (sg sb) sa, R12 = (-cg) sa + (sg sb) ca, R20 = -sb, R21 = cb sa, R22 = cb ca;
+ *   the translation is (tx, ty, tz).  [LIB] a step of either kind with a non-finite element is SINGULAR as well.
+ *   te selects nothing else: SVD or LLS under Point2Point both mean the first step, under Point2Plane both the second (upstream's default: branches).
+ * Target normals (Point2Plane only) [upstream shape: get_pc_normal_pcar, NormalEstimationOMP with a radius, the viewpoint at the origin,
+ *   check_normal; from memory]  the neighbourhood of a cropped target point p: every cropped target point q, p among them, with [LIB] (double)d2(q, p)
+ *   <= (double)neighbor_radius * (double)neighbor_radius — a neighbour at exactly the radius counts; FLANN's rule there is not claimed.  Fewer than 3
+ *   neighbours: the normal is (0.577f, 0.577f, 0.577f) (check_normal's value for PCL's NaN).  Otherwise [LIB] in double, the neighbours in ascending
+ *   index, two passes as csrc/gicp_math.h's sum_add / mean_of / scatter_add: m = the sum / k, S = the sum of the outer products of (q - m); S by the
+ *   cyclic Jacobi rotations of csrc/jacobi_rot.h (pairs (0,1) (0,2) (1,2), at most 60 sweeps, until the squared off-diagonal sum is below 1e-300);
+ *   the column of the smallest diagonal entry, ties by the lower column index; divided by its norm; negated when n . (-p) < 0; stored as float
+ *   ((0.577f, ..) if not finite).  The cells of this search have the edge neighbor_radius (1 + 2^-20).  Source normals are not computed: with
+ *   ce = NN nothing reads them.
+ * Loop [upstream: IterativeClosestPoint::computeTransformation and DefaultConvergenceCriteria; from memory]  an iteration takes the pairs of the moved
+ *   source, estimates the step from them, moves the source in place, x <- float(((R_r0 x + R_r1 y) + R_r2 z) + t_r), composes final = step * final
+ *   and counts the iteration.  Then, in this order: iterations >= max_iter_num: ITERATIONS; 0.5 (((R00 + R11) + R22) - 1) >= 1 -
+ *   transformation_epsilon and (t0 t0 + t1 t1) + t2 t2 <= transformation_epsilon, of the step: TRANSFORM; with mse = the sum of the pairs' d2 (as
+ *   recorded by the search, before the move) / the number of pairs: |mse - prev| < 1e-12: ABS_MSE; |mse - prev| / prev < euclidean_fitness_epsilon:
+ *   REL_MSE; each of these with converged = 1.  prev starts at DBL_MAX and becomes mse when nothing fired.  [LIB] the step and the product are double
+ *   (upstream's are float).  n_corr and mse are the last iteration's.
+ * Fitness [upstream getFitnessScore(thre_dis), quirk kept]  the cropped source under the final pose, x' = float(((R_r0 x + R_r1 y) + R_r2 z) + t_r);
+ *   d2 to the nearest cropped target point; a point counts when (double)d2 <= (double)dis_thre_unit — a squared distance against an unsquared range,
+ *   as upstream has it; fitness = the sum over the counted points (the strided-partial rule) / n_fit, DBL_MAX when n_fit = 0; code = fitness >
+ *   fitness_score_thre ? -3 : 1.
+ * Not built (MULLS_E_UNSUPPORTED): use_trimmed_rejector (CorrespondenceRejectorVarTrimmed removes the distance bound: an unbounded search), te = LM,
+ *   ce = NS (normal shooting), metrics = Plane2Plane (PCL's GICP). */
+enum mulls_pcl_icp_metric
+{
+	MULLS_PCL_ICP_POINT2POINT = 0,
+	MULLS_PCL_ICP_POINT2PLANE = 1,
+	MULLS_PCL_ICP_PLANE2PLANE = 2 /* not built: MULLS_E_UNSUPPORTED */
+};
+enum mulls_pcl_icp_ce
+{
+	MULLS_PCL_ICP_NN = 0,
+	MULLS_PCL_ICP_NS = 1 /* not built: MULLS_E_UNSUPPORTED */
+};
+enum mulls_pcl_icp_te
+{
+	MULLS_PCL_ICP_SVD = 0,
+	MULLS_PCL_ICP_LM = 1, /* not built: MULLS_E_UNSUPPORTED */
+	MULLS_PCL_ICP_LLS = 2
+};
+enum mulls_pcl_icp_stop
+{
+	MULLS_PCL_ICP_STOP_NONE = 0, /* no registration ran */
+	MULLS_PCL_ICP_STOP_ITERATIONS = 1,
+	MULLS_PCL_ICP_STOP_TRANSFORM = 2,
+	MULLS_PCL_ICP_STOP_ABS_MSE = 3,
+	MULLS_PCL_ICP_STOP_REL_MSE = 4,
+	MULLS_PCL_ICP_STOP_NO_CORRESPONDENCES = 5,
+	MULLS_PCL_ICP_STOP_SINGULAR = 6
+};
+#define MULLS_PCL_ICP_BATCH_DEFAULT_SCRATCH_BYTES (1024ull << 20) /* a value chosen without a measurement */
+typedef struct mulls_pcl_icp_params
+{
+	int32_t max_iter_num;				   /* 20 [LIB] */
+	float dis_thre_unit;				   /* 1.5 [LIB] */
+	int32_t metrics;					   /* enum mulls_pcl_icp_metric; MULLS_PCL_ICP_POINT2POINT */
+	int32_t ce;							   /* enum mulls_pcl_icp_ce; MULLS_PCL_ICP_NN */
+	int32_t te;							   /* enum mulls_pcl_icp_te; MULLS_PCL_ICP_SVD */
+	int32_t use_reciprocal_correspondence; /* 0 */
+	int32_t use_trimmed_rejector;		   /* 0; 1: MULLS_E_UNSUPPORTED */
+	float neighbor_radius;				   /* 2.0 */
+	int32_t apply_intersection_filter;	   /* 1 */
+	float fitness_score_thre;			   /* 10.0 */
+	double transformation_epsilon;		   /* 1e-8 */
+	double euclidean_fitness_epsilon;	   /* 1e-5 */
+	uint64_t scratch_limit_bytes;		   /* of one sub-batch of mulls_pcl_icp_batch; 0: MULLS_PCL_ICP_BATCH_DEFAULT_SCRATCH_BYTES */
+} mulls_pcl_icp_params;
+typedef mulls_ndt_problem mulls_pcl_icp_problem; /* tgt, src, tgt_bound, src_bound, init_guess */
+typedef struct mulls_pcl_icp_result
+{
+	int32_t code; /* 1 or -3 */
+	int32_t iterations, converged, stop; /* enum mulls_pcl_icp_stop */
+	uint32_t n_src, n_tgt; /* after the crop */
+	uint32_t n_corr, n_fit; /* the last iteration's pairs; the source points the fitness counted */
+	double mse;				/* of the last iteration's pairs */
+	double T[16];			/* column-major */
+	double fitness;
+} mulls_pcl_icp_result;
+void mulls_pcl_icp_default_params(mulls_pcl_icp_params *p);
+/* MULLS_OK, or MULLS_E_INVALID (an empty cloud, a NULL pointer, a non-finite coordinate, bound or guess, a bad stride or parameter), MULLS_E_UNSUPPORTED
+ * (the options above, a coordinate beyond 2^20 cells, a cloud above MULLS_NDT_MAX_POINTS); the results are then not written. */
+int mulls_pcl_icp(mulls_ctx *ctx, const mulls_pcl_icp_problem *problem, const mulls_pcl_icp_params *params, mulls_pcl_icp_result *result);
+/* the bits of n_problems mulls_pcl_icp calls.  The tables and normals of a sub-batch are built in one launch set; then its problems run in lock step:
+ * a tick re-bins the moved sources (reciprocal only), searches, accumulates and decides for every problem that still runs, and reads 4 bytes back; at
+ * most max_iter_num ticks.  Sub-batches are sized by params->scratch_limit_bytes; a problem larger than the limit runs alone.  n_problems = 0: MULLS_OK. */
+int mulls_pcl_icp_batch(mulls_ctx *ctx, const mulls_pcl_icp_problem *problems, uint32_t n_problems, const mulls_pcl_icp_params *params,
+						mulls_pcl_icp_result *results);
 
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 

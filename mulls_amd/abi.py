@@ -598,6 +598,44 @@ def gicp_params(**kw):
     return p
 
 
+class PclIcpParams(C.Structure):
+    """mulls_pcl_icp_params"""
+
+    _fields_ = [("max_iter_num", C.c_int32), ("dis_thre_unit", C.c_float), ("metrics", C.c_int32), ("ce", C.c_int32), ("te", C.c_int32),
+                ("use_reciprocal_correspondence", C.c_int32), ("use_trimmed_rejector", C.c_int32), ("neighbor_radius", C.c_float),
+                ("apply_intersection_filter", C.c_int32), ("fitness_score_thre", C.c_float), ("transformation_epsilon", C.c_double),
+                ("euclidean_fitness_epsilon", C.c_double), ("scratch_limit_bytes", C.c_uint64)]
+
+
+PclIcpProblem = NdtProblem  # mulls_pcl_icp_problem is mulls_ndt_problem
+
+
+class PclIcpResult(C.Structure):
+    """mulls_pcl_icp_result"""
+
+    _fields_ = [("code", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("stop", C.c_int32), ("n_src", C.c_uint32), ("n_tgt", C.c_uint32),
+                ("n_corr", C.c_uint32), ("n_fit", C.c_uint32), ("mse", C.c_double), ("T", C.c_double * 16), ("fitness", C.c_double)]
+
+
+PCL_ICP_POINT2POINT, PCL_ICP_POINT2PLANE, PCL_ICP_PLANE2PLANE = range(3)  # enum mulls_pcl_icp_metric
+PCL_ICP_NN, PCL_ICP_NS = range(2)  # enum mulls_pcl_icp_ce
+PCL_ICP_SVD, PCL_ICP_LM, PCL_ICP_LLS = range(3)  # enum mulls_pcl_icp_te
+(PCL_ICP_STOP_NONE, PCL_ICP_STOP_ITERATIONS, PCL_ICP_STOP_TRANSFORM, PCL_ICP_STOP_ABS_MSE, PCL_ICP_STOP_REL_MSE, PCL_ICP_STOP_NO_CORRESPONDENCES,
+ PCL_ICP_STOP_SINGULAR) = range(7)  # enum mulls_pcl_icp_stop
+
+
+def pcl_icp_params(**kw):
+    """mulls_pcl_icp_default_params' values, then the keyword arguments"""
+    p = PclIcpParams()
+    p.max_iter_num, p.dis_thre_unit, p.metrics, p.ce, p.te = 20, 1.5, PCL_ICP_POINT2POINT, PCL_ICP_NN, PCL_ICP_SVD
+    p.neighbor_radius, p.apply_intersection_filter, p.fitness_score_thre = 2.0, 1, 10.0
+    p.transformation_epsilon, p.euclidean_fitness_epsilon = 1e-8, 1e-5
+    for k, v in kw.items():
+        getattr(p, k)
+        setattr(p, k, v)
+    return p
+
+
 class NmsParams(C.Structure):
     """mulls_nms_params: non_max_suppress' radius (cfilter.hpp:1183) and which path runs it"""
 

@@ -133,6 +133,10 @@ def load():
     lib.mulls_gicp_default_params.restype = None
     lib.mulls_gicp.argtypes = [vp, C.POINTER(abi.GicpProblem), C.POINTER(abi.GicpParams), C.POINTER(abi.GicpResult)]
     lib.mulls_gicp_batch.argtypes = [vp, C.POINTER(abi.GicpProblem), C.c_uint32, C.POINTER(abi.GicpParams), C.POINTER(abi.GicpResult)]
+    lib.mulls_pcl_icp_default_params.argtypes = [C.POINTER(abi.PclIcpParams)]
+    lib.mulls_pcl_icp_default_params.restype = None
+    lib.mulls_pcl_icp.argtypes = [vp, C.POINTER(abi.PclIcpProblem), C.POINTER(abi.PclIcpParams), C.POINTER(abi.PclIcpResult)]
+    lib.mulls_pcl_icp_batch.argtypes = [vp, C.POINTER(abi.PclIcpProblem), C.c_uint32, C.POINTER(abi.PclIcpParams), C.POINTER(abi.PclIcpResult)]
     lib.mulls_sor_default_params.argtypes = [C.POINTER(abi.SorParams)]
     lib.mulls_sor_default_params.restype = None
     lib.mulls_sor_filter.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.SorParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
@@ -191,6 +195,7 @@ EXPORTS = [
     "mulls_sor_default_params", "mulls_sor_filter",
     "mulls_pgo_default_params", "mulls_pgo_optimize", "mulls_pgo_optimize_batch",
     "mulls_ndt_default_params", "mulls_ndt", "mulls_ndt_batch", "mulls_gicp_default_params", "mulls_gicp", "mulls_gicp_batch",
+    "mulls_pcl_icp_default_params", "mulls_pcl_icp", "mulls_pcl_icp_batch",
     "mulls_nms_default_params", "mulls_non_max_suppress",
     "mulls_scan_prep_default_params", "mulls_scan_prepare",
     "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
@@ -834,6 +839,31 @@ class Context:
         if rc != 0:
             raise MullsError("mulls_gicp_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
         return [abi.GicpResult.from_buffer_copy(res[b]) for b in range(B)]
+
+    # --- classical ICP registration -----------------------------------------------------------------------------------
+    def pcl_icp(self, tgt, src, tgt_bound, src_bound, init_guess=None, params=None):
+        """CRegistration::pcl_icp, the part that is plain ICP (mulls_pcl_icp).  The arguments are ndt's.  Returns the mulls_pcl_icp_result."""
+        keep = []
+        P = self._ndt_problem((tgt, src, tgt_bound, src_bound, init_guess), keep)
+        p = params if params is not None else abi.pcl_icp_params()
+        res = abi.PclIcpResult()
+        rc = self.lib.mulls_pcl_icp(self.h, C.byref(P), C.byref(p), C.byref(res))
+        if rc != 0:
+            raise MullsError("mulls_pcl_icp failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return res
+
+    def pcl_icp_batch(self, problems, params=None):
+        """mulls_pcl_icp_batch: many problems per call in lock step, each with the bits of its pcl_icp call.  problems: as _ndt_problem takes them.
+        One params for the whole batch (its scratch_limit_bytes sizes the sub-batches).  Returns [mulls_pcl_icp_result, ...]."""
+        keep, B = [], len(problems)
+        arr, res = (abi.PclIcpProblem * max(B, 1))(), (abi.PclIcpResult * max(B, 1))()
+        for b, prob in enumerate(problems):
+            arr[b] = self._ndt_problem(prob, keep)
+        p = params if params is not None else abi.pcl_icp_params()
+        rc = self.lib.mulls_pcl_icp_batch(self.h, arr, B, C.byref(p), res)
+        if rc != 0:
+            raise MullsError("mulls_pcl_icp_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return [abi.PclIcpResult.from_buffer_copy(res[b]) for b in range(B)]
 
     # --- pose graph optimisation --------------------------------------------------------------------------------------
     def pgo_optimize(self, poses, fixed, stable, edges, params=None):

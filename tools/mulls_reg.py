@@ -57,9 +57,11 @@ def flags(argv=None):
     p.add_argument("--reciprocal_corr_on", type=boolean, default=False)
     p.add_argument("--fixed_num_corr_on", type=boolean, default=False)
     p.add_argument("--device", type=int, default=0)
-    p.add_argument("--baseline_reg_method", choices=("", "ndt", "gicp"), default="",
-                   help="ndt: CRegistration::omp_ndt (mulls_ndt), gicp: CRegistration::omp_gicp with voxelised GICP (mulls_gicp), on the two pc_down clouds "
-                        "in place of mm_lls_icp, as test/mulls_slam.cpp's baselines")
+    p.add_argument("--baseline_reg_method", "--method", dest="baseline_reg_method", choices=("", "ndt", "gicp", "pclicp"), default="",
+                   help="ndt: CRegistration::omp_ndt (mulls_ndt), gicp: CRegistration::omp_gicp with voxelised GICP (mulls_gicp), pclicp: CRegistration::pcl_icp "
+                        "(mulls_pcl_icp), on the two pc_down clouds in place of mm_lls_icp, as test/mulls_slam.cpp's baselines")
+    p.add_argument("--pclicp_metric", choices=("point2point", "point2plane"), default="point2plane", help="pclicp: the step (upstream names no default)")
+    p.add_argument("--pclicp_reciprocal", type=boolean, default=False, help="pclicp: use_reciprocal_correspondence")
     p.add_argument("--reg_voxel_size", type=float, default=1.0, help="the NDT leaf size or the VGICP voxel size (test/mulls_slam.cpp's reg_voxel_size)")
     a, _ = p.parse_known_args(argv)  # glog / viewer flags of the reference's script are accepted and ignored
     return a
@@ -125,7 +127,7 @@ def global_registration(ctx, tgt_kpts, src_kpts, F):
 
 
 class NdtOutcome:
-    """mulls_ndt_result or mulls_gicp_result with the three members main() reads of an abi.Result"""
+    """mulls_ndt_result, mulls_gicp_result or mulls_pcl_icp_result with the three members main() reads of an abi.Result"""
 
     def __init__(self, r):
         self.ndt, self.code, self.iters = r, r.code, r.iterations
@@ -166,6 +168,17 @@ def register(ctx, scan1, scan2, F):
         r = ctx.gicp((p1, p2)[2 - source], (p1, p2)[source - 1], scan_bound(abi.as_points(tgt_scan)), scan_bound(abi.as_points(src_scan)), init_mat,
                      abi.gicp_params(voxel_resolution=F.reg_voxel_size))
         print("omp_gicp: %d iterations, stop %d, fitness %.4f, %d voxels, %d of %d source points with a voxel" % (r.iterations + 1, r.stop, r.fitness, r.n_voxels, r.n_corr, r.n_src))
+        return NdtOutcome(r), source, (p1, p2)[source - 1]
+    if F.baseline_reg_method == "pclicp":
+        # pcl_icp(reg_con, max_iter, thre, metrics, NN, te, reciprocal, false, 2.0, init_mat): test/mulls_slam.cpp:195 names the method and never calls
+        # it; the iteration cap and the distance are mm_lls_icp's flags, the same clouds and bounds as the other baselines
+        tgt_scan, src_scan = (scan1, scan2) if source == 2 else (scan2, scan1)
+        plane = F.pclicp_metric == "point2plane"
+        prm = abi.pcl_icp_params(max_iter_num=F.reg_max_iter_num, dis_thre_unit=F.corr_dis_thre, metrics=abi.PCL_ICP_POINT2PLANE if plane else abi.PCL_ICP_POINT2POINT,
+                                 te=abi.PCL_ICP_LLS if plane else abi.PCL_ICP_SVD, use_reciprocal_correspondence=int(F.pclicp_reciprocal))
+        r = ctx.pcl_icp((p1, p2)[2 - source], (p1, p2)[source - 1], scan_bound(abi.as_points(tgt_scan)), scan_bound(abi.as_points(src_scan)), init_mat, prm)
+        print("pcl_icp (%s): %d iterations, stop %d, %d pairs, mse %.4f, fitness %.4f over %d of %d source points"
+              % (F.pclicp_metric, r.iterations, r.stop, r.n_corr, r.mse, r.fitness, r.n_fit, r.n_src))
         return NdtOutcome(r), source, (p1, p2)[source - 1]
     pair = abi.PairData([abi.points_of(t) for t in tgt_full], [abi.points_of(s) for s in src_down],
                         init_guess=init_mat, tgt_bound=scan_bound(abi.as_points(scan1 if source == 2 else scan2)) if len(scan1) and len(scan2) else None)
