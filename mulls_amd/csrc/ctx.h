@@ -27,9 +27,7 @@ struct mulls_sor_scratch;
 struct mulls_nms_scratch;
 struct mulls_scan_scratch;
 struct mulls_pgo_scratch;
-struct mulls_ndt_scratch;
-struct mulls_gicp_scratch;
-struct mulls_pcl_icp_scratch;
+struct mulls_reg_scratch;
 struct mulls_mapper;
 struct mulls_mapb_scratch;
 
@@ -95,9 +93,7 @@ struct mulls_ctx
 	mulls_nms_scratch *nms = nullptr; // mulls_non_max_suppress's (nms.cpp; grow-only)
 	mulls_scan_scratch *scanprep = nullptr; // mulls_scan_prepare's and mulls_mapper_add's (scan.cpp; grow-only)
 	mulls_pgo_scratch *pgo = nullptr; // mulls_pgo_optimize's (pgo.cpp; grow-only)
-	mulls_ndt_scratch *ndt = nullptr; // mulls_ndt's (ndt.cpp; grow-only)
-	mulls_gicp_scratch *gicp = nullptr; // mulls_gicp's (gicp.cpp; grow-only)
-	mulls_pcl_icp_scratch *pcl_icp = nullptr; // mulls_pcl_icp's (pcl_icp.cpp; grow-only)
+	mulls_reg_scratch *reg = nullptr; // mulls_ndt's, mulls_gicp's and mulls_pcl_icp's (reg_host.cpp; grow-only)
 	mulls_mapb_scratch *mapb = nullptr; // mulls_map_update_batch's staging: tables up, counts and keys down (map_batch.cpp; grow-only)
 	std::vector<mulls_mapper *> mappers; // live merged maps (scan.cpp)
 	std::vector<mulls_submaps *> submap_stores; // live submap archives (submaps.cpp): their arenas are device clouds mulls_pair may point to
@@ -260,9 +256,7 @@ void mulls_teaser_release(mulls_ctx *ctx); // frees ctx->teaser (teaser.cpp)
 void mulls_sor_release(mulls_ctx *ctx); // frees ctx->sor (sor.cpp)
 void mulls_nms_release(mulls_ctx *ctx); // frees ctx->nms (nms.cpp)
 void mulls_pgo_release(mulls_ctx *ctx); // frees ctx->pgo (pgo.cpp)
-void mulls_ndt_release(mulls_ctx *ctx); // frees ctx->ndt (ndt.cpp)
-void mulls_gicp_release(mulls_ctx *ctx); // frees ctx->gicp (gicp.cpp)
-void mulls_pcl_icp_release(mulls_ctx *ctx); // frees ctx->pcl_icp (pcl_icp.cpp)
+void mulls_reg_release(mulls_ctx *ctx); // frees ctx->reg (reg_host.cpp)
 void mulls_mapb_release(mulls_ctx *ctx); // frees ctx->mapb (map_batch.cpp)
 void mulls_scan_release(mulls_ctx *ctx); // frees ctx->scanprep and destroys the mappers still alive (scan.cpp)
 void mulls_submaps_release(mulls_ctx *ctx); // destroys the submap archives still alive (submaps.cpp)

@@ -265,9 +265,7 @@ extern "C"
 		mulls_teaser_release(ctx);
 		mulls_sor_release(ctx);
 		mulls_pgo_release(ctx);
-		mulls_ndt_release(ctx);
-		mulls_gicp_release(ctx);
-		mulls_pcl_icp_release(ctx);
+		mulls_reg_release(ctx);
 		mulls_mapb_release(ctx);
 		mulls_nms_release(ctx);
 		mulls_scan_release(ctx); // (merged maps die with their context, like local maps and feature blocks)

@@ -1,6 +1,6 @@
 // k_gicp.hip — the device side of mulls_gicp / mulls_gicp_batch (gfx950).  One launch of each kernel serves every problem of a sub-batch: blockIdx.y is the
 // problem's table or cloud for the per-point and per-slot kernels, blockIdx.x the problem for those that give a problem one workgroup.  The crop and the
-// fitness pass are k_ndt.hip's.  Setup: three hash tables of occupied cells per problem (k_gicp_cells, k_gicp_offsets, k_gicp_scatter), the exact
+// fitness pass are k_ndt.hip's.  Setup: three tables of occupied cells per problem (k_reg_table.hip, reg_table.h), the exact
 // k-nearest ring walk with the (d2, index) list in registers and the covariance tail (k_gicp_knn, the setup's hot path), a wave per query the walk did
 // not certify (k_gicp_brute), one lane per voxel that sorts its points' indices and adds in that order (k_gicp_voxels) — atomics place entries, they never
 // decide an order of additions.  Iteration: k_gicp_eval (the loop's hot path: 28 double sums per source point, strided partials) and k_gicp_decide (the
@@ -9,47 +9,11 @@
 #include <hip/hip_runtime.h>
 
 #include "gicp_launch.h"
-#include "ndt_tree.h"
+#include "reg_device.h"
 #include "sor_math.h"
 
 namespace
 {
-template <typename T>
-__device__ inline T *at(unsigned char *arena, uint64_t off)
-{
-	return reinterpret_cast<T *>(arena + off);
-}
-constexpr uint64_t EMPTY = 0xffffffffffffffffull;
-constexpr uint32_t NO_SLOT = 0xffffffffu;
-
-// the cell of the neighbour grid: in double, so that the assignment's rounding is far below the certificate's margin (sor_math.h)
-__device__ inline int32_t knn_coord(float x, double inv_edge, int *ok)
-{
-	const double q = floor((double)x * inv_edge);
-	if (!(q >= -1048576.0 && q < 1048576.0))
-	{
-		*ok = 0;
-		return 0;
-	}
-	return (int32_t)q;
-}
-
-// the slot of a key, or NO_SLOT
-__device__ inline uint32_t find_slot(const uint64_t *__restrict__ keys, uint64_t key, uint32_t slots, uint32_t shift)
-{
-	uint32_t h = gicp::home_slot(key, shift);
-	for (uint32_t probe = 0; probe < slots; probe++)
-	{
-		const uint64_t k = keys[h];
-		if (k == key)
-			return h;
-		if (k == EMPTY)
-			return NO_SLOT;
-		h = (h + 1u) & (slots - 1u);
-	}
-	return NO_SLOT;
-}
-
 // The k smallest (d2, index) pairs seen so far, ascending in slots CAP - k .. CAP - 1; the slots in front of them hold -inf, which no value passes, so
 // one text serves every k <= CAP with static indices only: the list stays in registers.
 template <int CAP>
@@ -81,130 +45,32 @@ struct KBest
 	}
 };
 
-__global__ void __launch_bounds__(64) k_gicp_begin(const NdtRec *__restrict__ nrec, GicpRec *rec, double *frames, GicpOpts opt, uint32_t P)
+__global__ void __launch_bounds__(64) k_gicp_begin(const NdtRec *__restrict__ nrec, GicpRec *rec, RegHead *head, double *frames, GicpOpts opt, uint32_t P)
 {
 	const uint32_t p = blockIdx.x * 64u + threadIdx.x;
 	if (p >= P)
 		return;
 	GicpRec &R = rec[p];
-	R.n[0] = nrec[p].n_src, R.n[1] = nrec[p].n_tgt;
-	R.n_left[0] = R.n_left[1] = 0, R.n_voxels = 0, R.range = 0, R.pad = 0;
+	RegHead H{};
+	H.n[0] = nrec[p].n_src, H.n[1] = nrec[p].n_tgt;
+	R.n_left[0] = R.n_left[1] = 0;
 	int status = GICP_ST_OK;
 	if (nrec[p].status == NDT_ST_NONFINITE)
 		status = GICP_ST_NONFINITE;
-	else if (nrec[p].status != NDT_ST_OK || R.n[0] < (uint32_t)opt.k || R.n[1] < (uint32_t)opt.k)
+	else if (nrec[p].status != NDT_ST_OK || H.n[0] < (uint32_t)opt.k || H.n[1] < (uint32_t)opt.k)
 		status = GICP_ST_FEW;
-	R.status = status;
+	H.status = status;
 	gicp::State S;
 	gicp::begin(S, opt.start_rotvec);
 	if (status != GICP_ST_OK)
 		S.running = 0;
 	R.S = S;
+	H.running = S.running;
+	head[p] = H;
 	for (int k = 0; k < 9; k++)
 		frames[12u * p + k] = S.R[k];
 	for (int k = 0; k < 3; k++)
 		frames[12u * p + 9 + k] = S.t[k];
-}
-
-// every cropped point of a table's cloud: its cell, the cell's slot (claimed by compare-and-swap), the slot's count
-__global__ void __launch_bounds__(256) k_gicp_cells(const GicpDesc *__restrict__ desc, unsigned char *arena, GicpOpts opt, GicpRec *rec)
-{
-	const uint32_t p = blockIdx.y / GICP_TABS, tb = blockIdx.y % GICP_TABS;
-	GicpRec &R = rec[p];
-	if (R.status != GICP_ST_OK)
-		return;
-	const GicpTab T = desc[p].tab[tb];
-	const uint32_t n = R.n[tb == GICP_TAB_KNN_SRC ? 0 : 1];
-	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i >= n || i >= T.n_cap)
-		return;
-	const float *P3 = at<const float>(arena, T.o_pts);
-	const float x = P3[3 * i], y = P3[3 * i + 1], z = P3[3 * i + 2];
-	int ok = 1;
-	int32_t c0, c1, c2;
-	if (tb == GICP_TAB_VOXEL)
-		c0 = gicp::voxel_coord(x, opt.resolution, &ok), c1 = gicp::voxel_coord(y, opt.resolution, &ok), c2 = gicp::voxel_coord(z, opt.resolution, &ok);
-	else
-		c0 = knn_coord(x, opt.knn_inv_edge, &ok), c1 = knn_coord(y, opt.knn_inv_edge, &ok), c2 = knn_coord(z, opt.knn_inv_edge, &ok);
-	uint32_t found = NO_SLOT;
-	if (ok)
-	{
-		const uint64_t key = gicp::pack_coords(c0, c1, c2);
-		unsigned long long *keys = at<unsigned long long>(arena, T.o_keys);
-		uint32_t h = gicp::home_slot(key, T.shift);
-		for (uint32_t probe = 0; probe < T.slots; probe++)
-		{
-			const unsigned long long was = atomicCAS(&keys[h], (unsigned long long)EMPTY, (unsigned long long)key);
-			if (was == EMPTY || was == key)
-			{
-				found = h;
-				break;
-			}
-			h = (h + 1u) & (T.slots - 1u);
-		}
-	}
-	else
-		atomicOr(&R.range, 1u); // does not fit the packed key: refused by the host, never wrapped
-	at<uint32_t>(arena, T.o_cell)[i] = found; // (always found when ok: the table has at least twice as many slots as there are points)
-	if (found != NO_SLOT)
-		atomicAdd(&at<uint32_t>(arena, T.o_count)[found], 1u);
-}
-
-// start[slot]: the exclusive sum of the counts; the number of occupied slots
-__global__ void __launch_bounds__(MULLS_GICP_SEG) k_gicp_offsets(const GicpDesc *__restrict__ desc, unsigned char *arena, GicpRec *rec)
-{
-	__shared__ uint32_t s_cnt[MULLS_GICP_SEG], s_occ[MULLS_GICP_SEG];
-	const uint32_t p = blockIdx.x / GICP_TABS, tb = blockIdx.x % GICP_TABS, t = threadIdx.x;
-	if (rec[p].status != GICP_ST_OK)
-		return;
-	const GicpTab T = desc[p].tab[tb];
-	const uint32_t *count = at<const uint32_t>(arena, T.o_count);
-	uint32_t *start = at<uint32_t>(arena, T.o_start);
-	const uint32_t seg = T.slots / MULLS_GICP_SEG, b = t * seg;
-	uint32_t sum = 0, occ = 0;
-	for (uint32_t k = 0; k < seg; k++)
-		sum += count[b + k], occ += count[b + k] ? 1u : 0u;
-	s_cnt[t] = sum, s_occ[t] = occ;
-	__syncthreads();
-	if (t == 0)
-	{
-		uint32_t run = 0, cells = 0;
-		for (uint32_t k = 0; k < MULLS_GICP_SEG; k++)
-		{
-			const uint32_t v = s_cnt[k];
-			s_cnt[k] = run;
-			run += v;
-			cells += s_occ[k];
-		}
-		if (tb == GICP_TAB_VOXEL)
-			rec[p].n_voxels = cells;
-	}
-	__syncthreads();
-	uint32_t run = s_cnt[t];
-	for (uint32_t k = 0; k < seg; k++)
-	{
-		start[b + k] = run;
-		run += count[b + k];
-	}
-}
-
-__global__ void __launch_bounds__(256) k_gicp_scatter(const GicpDesc *__restrict__ desc, unsigned char *arena, const GicpRec *__restrict__ rec)
-{
-	const uint32_t p = blockIdx.y / GICP_TABS, tb = blockIdx.y % GICP_TABS;
-	const GicpRec &R = rec[p];
-	if (R.status != GICP_ST_OK)
-		return;
-	const GicpTab T = desc[p].tab[tb];
-	const uint32_t n = R.n[tb == GICP_TAB_KNN_SRC ? 0 : 1];
-	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i >= n || i >= T.n_cap)
-		return;
-	const uint32_t slot = at<const uint32_t>(arena, T.o_cell)[i];
-	if (slot >= T.slots)
-		return;
-	const uint32_t pos = at<const uint32_t>(arena, T.o_start)[slot] + atomicAdd(&at<uint32_t>(arena, T.o_fill)[slot], 1u);
-	if (pos < T.n_cap)
-		at<uint32_t>(arena, T.o_list)[pos] = i;
 }
 
 // the tail of a neighbour query: the mean and the scatter of the k neighbours in the list's order, the PLANE covariance
@@ -237,14 +103,16 @@ __device__ __forceinline__ void covariance_tail(const KBest<CAP> &kb, int k, con
 // The setup's hot path.  One lane per point of a cloud, in cell order: Chebyshev rings around its cell until its k-th best is certainly nearer than
 // anything unscanned (sor_certified), then the tail.  A query no ring certifies is left for k_gicp_brute.
 template <int CAP>
-__global__ void __launch_bounds__(256) k_gicp_knn(const GicpDesc *__restrict__ desc, unsigned char *arena, GicpOpts opt, GicpRec *rec, uint32_t *max_left)
+__global__ void __launch_bounds__(256) k_gicp_knn(const GicpDesc *__restrict__ desc, const RegTab *__restrict__ tabs, unsigned char *arena, GicpOpts opt,
+												  GicpRec *rec, const RegHead *__restrict__ head, uint32_t *max_left)
 {
 	const uint32_t p = blockIdx.y >> 1, c = blockIdx.y & 1u;
 	GicpRec &R = rec[p];
-	if (R.status != GICP_ST_OK || R.range)
+	const RegHead &H = head[p];
+	if (H.status != GICP_ST_OK || H.range)
 		return;
-	const GicpTab T = desc[p].tab[c];
-	const uint32_t n = R.n[c] < T.n_cap ? R.n[c] : T.n_cap;
+	const RegTab T = tabs[MULLS_REG_TABS * p + c];
+	const uint32_t n = H.n[c] < T.n_cap ? H.n[c] : T.n_cap;
 	const uint32_t t = blockIdx.x * 256u + threadIdx.x;
 	if (t >= n)
 		return;
@@ -253,7 +121,8 @@ __global__ void __launch_bounds__(256) k_gicp_knn(const GicpDesc *__restrict__ d
 	const float *P3 = at<const float>(arena, T.o_pts);
 	const float qx = P3[3 * qi], qy = P3[3 * qi + 1], qz = P3[3 * qi + 2];
 	int ok = 1;
-	const int32_t cx = knn_coord(qx, opt.knn_inv_edge, &ok), cy = knn_coord(qy, opt.knn_inv_edge, &ok), cz = knn_coord(qz, opt.knn_inv_edge, &ok);
+	// (the cell in double, so that the assignment's rounding is far below the certificate's margin, sor_math.h)
+	const int32_t cx = pcl_icp::cell_coord(qx, T.inv_edge, &ok), cy = pcl_icp::cell_coord(qy, T.inv_edge, &ok), cz = pcl_icp::cell_coord(qz, T.inv_edge, &ok);
 	const uint64_t *keys = at<const uint64_t>(arena, T.o_keys);
 	const uint32_t *start = at<const uint32_t>(arena, T.o_start), *count = at<const uint32_t>(arena, T.o_count);
 	KBest<CAP> kb;
@@ -269,7 +138,7 @@ __global__ void __launch_bounds__(256) k_gicp_knn(const GicpDesc *__restrict__ d
 				for (int dx = -ring; dx <= ring; dx += stepx)
 				{
 					const int32_t nx = cx + dx, ny = cy + dy, nz = cz + dz;
-					if (nx < -1048576 || ny < -1048576 || nz < -1048576 || nx >= 1048576 || ny >= 1048576 || nz >= 1048576)
+					if (!cell_in_range(nx, ny, nz))
 						continue;
 					const uint32_t slot = find_slot(keys, gicp::pack_coords(nx, ny, nz), T.slots, T.shift);
 					if (slot == NO_SLOT)
@@ -300,15 +169,17 @@ __global__ void __launch_bounds__(256) k_gicp_knn(const GicpDesc *__restrict__ d
 // One wavefront per query the walk left.  Every lane keeps the k best of the points lane, lane + 64, ..; then k rounds, each taking the smallest pair
 // above the one taken before over all the lanes' lists: the neighbours in (d2, index) order.  Lane 0 runs the tail.
 template <int CAP>
-__global__ void __launch_bounds__(64) k_gicp_brute(const GicpDesc *__restrict__ desc, unsigned char *arena, GicpOpts opt, const GicpRec *__restrict__ rec)
+__global__ void __launch_bounds__(64) k_gicp_brute(const GicpDesc *__restrict__ desc, const RegTab *__restrict__ tabs, unsigned char *arena, GicpOpts opt,
+												   const GicpRec *__restrict__ rec, const RegHead *__restrict__ head)
 {
 	__shared__ uint32_t s_idx[CAP];
 	const uint32_t p = blockIdx.y >> 1, c = blockIdx.y & 1u, lane = threadIdx.x;
 	const GicpRec &R = rec[p];
-	if (R.status != GICP_ST_OK || R.range)
+	const RegHead &H = head[p];
+	if (H.status != GICP_ST_OK || H.range)
 		return;
-	const GicpTab T = desc[p].tab[c];
-	const uint32_t n = R.n[c] < T.n_cap ? R.n[c] : T.n_cap;
+	const RegTab T = tabs[MULLS_REG_TABS * p + c];
+	const uint32_t n = H.n[c] < T.n_cap ? H.n[c] : T.n_cap;
 	const uint32_t n_left = R.n_left[c] < T.n_cap ? R.n_left[c] : T.n_cap;
 	if (blockIdx.x >= n_left)
 		return;
@@ -372,15 +243,15 @@ __global__ void __launch_bounds__(64) k_gicp_brute(const GicpDesc *__restrict__ 
 		out[a] = C[a];
 }
 
-// one lane per occupied slot of the voxel map: its points' indices ascending (a shell sort: the indices are distinct, so the order does not depend on
-// how they arrived), the sums in that order, the voxel
-__global__ void __launch_bounds__(256) k_gicp_voxels(const GicpDesc *__restrict__ desc, unsigned char *arena, const GicpRec *__restrict__ rec)
+// one lane per occupied slot of the voxel map: its points' indices ascending, the sums in that order, the voxel
+__global__ void __launch_bounds__(256) k_gicp_voxels(const GicpDesc *__restrict__ desc, const RegTab *__restrict__ tabs, unsigned char *arena,
+													 const RegHead *__restrict__ head)
 {
 	const uint32_t p = blockIdx.y;
-	const GicpRec &R = rec[p];
-	if (R.status != GICP_ST_OK || R.range)
+	const RegHead &H = head[p];
+	if (H.status != GICP_ST_OK || H.range)
 		return;
-	const GicpTab T = desc[p].tab[GICP_TAB_VOXEL];
+	const RegTab T = tabs[MULLS_REG_TABS * p + GICP_TAB_VOXEL];
 	const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
 	if (slot >= T.slots)
 		return;
@@ -391,19 +262,7 @@ __global__ void __launch_bounds__(256) k_gicp_voxels(const GicpDesc *__restrict_
 	if (first >= T.n_cap || n > T.n_cap - first)
 		return;
 	uint32_t *L = at<uint32_t>(arena, T.o_list) + first;
-	const uint32_t gaps[9] = {1750u, 701u, 301u, 132u, 57u, 23u, 10u, 4u, 1u};
-	for (int gi = 0; gi < 9; gi++)
-	{
-		const uint32_t gap = gaps[gi];
-		for (uint32_t i = gap; i < n; i++)
-		{
-			const uint32_t v = L[i];
-			uint32_t k = i;
-			for (; k >= gap && L[k - gap] > v; k -= gap)
-				L[k] = L[k - gap];
-			L[k] = v;
-		}
-	}
+	sort_list(L, n);
 	const float *P3 = at<const float>(arena, T.o_pts);
 	const double *cov = at<const double>(arena, desc[p].o_cov[1]);
 	double s[3] = {0.0, 0.0, 0.0}, q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -425,7 +284,8 @@ __global__ void __launch_bounds__(256) k_gicp_voxels(const GicpDesc *__restrict_
 
 // The loop's hot path.  Lane l of the problem's MULLS_NDT_TREE lanes takes the source points l, l + MULLS_NDT_TREE, ..: the point under (R, t) in double,
 // the voxel of its float rounding, the 3 x 3 algebra of gicp_math.h into the lane's 28 sums.  The frame's 12 doubles are read from LDS.
-__global__ void __launch_bounds__(256) k_gicp_eval(const GicpDesc *__restrict__ desc, unsigned char *arena, GicpOpts opt, const GicpRec *__restrict__ rec)
+__global__ void __launch_bounds__(256) k_gicp_eval(const GicpDesc *__restrict__ desc, const RegTab *__restrict__ tabs, unsigned char *arena, GicpOpts opt,
+												   const GicpRec *__restrict__ rec, const RegHead *__restrict__ head)
 {
 	__shared__ double s_F[12];
 	const uint32_t p = blockIdx.y;
@@ -438,10 +298,10 @@ __global__ void __launch_bounds__(256) k_gicp_eval(const GicpDesc *__restrict__ 
 		s_F[threadIdx.x] = R.S.t[threadIdx.x - 9];
 	__syncthreads();
 	const GicpDesc &D = desc[p];
-	const GicpTab T = D.tab[GICP_TAB_VOXEL];
-	const uint32_t n_cap = D.tab[GICP_TAB_KNN_SRC].n_cap;
-	const uint32_t n = R.n[0] < n_cap ? R.n[0] : n_cap;
-	const float *S3 = at<const float>(arena, D.tab[GICP_TAB_KNN_SRC].o_pts);
+	const RegTab T = tabs[MULLS_REG_TABS * p + GICP_TAB_VOXEL];
+	const RegTab &TS = tabs[MULLS_REG_TABS * p + GICP_TAB_KNN_SRC];
+	const uint32_t n = head[p].n[0] < TS.n_cap ? head[p].n[0] : TS.n_cap;
+	const float *S3 = at<const float>(arena, TS.o_pts);
 	const double *cov = at<const double>(arena, D.o_cov[0]);
 	const uint64_t *keys = at<const uint64_t>(arena, T.o_keys);
 	const uint32_t *start = at<const uint32_t>(arena, T.o_start);
@@ -491,51 +351,31 @@ __global__ void __launch_bounds__(256) k_gicp_eval(const GicpDesc *__restrict__ 
 	at<uint32_t>(arena, D.o_hits)[lane] = hits;
 }
 
-__global__ void __launch_bounds__(256) k_gicp_decide(const GicpDesc *__restrict__ desc, unsigned char *arena, GicpOpts opt, GicpRec *rec, double *frames,
-													 uint32_t *running)
+__global__ void __launch_bounds__(256) k_gicp_decide(const GicpDesc *__restrict__ desc, unsigned char *arena, GicpOpts opt, GicpRec *rec, RegHead *head,
+													 double *frames, uint32_t *running, uint32_t *next)
 {
 	__shared__ double s_p[256];
 	__shared__ double s_sum[28];
 	__shared__ uint32_t s_hits[256];
 	__shared__ int s_run;
 	const uint32_t p = blockIdx.x, t = threadIdx.x;
+	if (p == 0 && t == 0)
+		*next = 0u; // (the next tick's count starts from 0)
 	if (t == 0)
 		s_run = rec[p].S.running;
 	__syncthreads();
 	if (!s_run)
 		return;
 	const GicpDesc &D = desc[p];
-	const double *partial = at<const double>(arena, D.o_partial);
-	for (int k = 0; k < 28; k++)
-	{
-		double r[16];
-#pragma unroll
-		for (int m = 0; m < 16; m++)
-			r[m] = partial[(uint32_t)k * MULLS_NDT_TREE + t + 256u * m];
-		const double v = tree_of_partials(r, s_p);
-		if (t == 0)
-			s_sum[k] = v;
-	}
-	{
-		const uint32_t *hits = at<const uint32_t>(arena, D.o_hits);
-		uint32_t h = 0;
-		for (int m = 0; m < 16; m++)
-			h += hits[t + 256u * m];
-		s_hits[t] = h;
-		__syncthreads();
-		for (uint32_t w = 128; w >= 1; w >>= 1)
-		{
-			if (t < w)
-				s_hits[t] += s_hits[t + w];
-			__syncthreads();
-		}
-	}
+	tree_of_sums(at<const double>(arena, D.o_partial), 28, [](int) { return true; }, s_p, s_sum);
+	const uint32_t n_corr = hits_of(at<const uint32_t>(arena, D.o_hits), s_hits);
 	if (t != 0)
 		return;
 	GicpRec &R = rec[p];
 	gicp::State S = R.S;
-	gicp::advance(S, s_sum, s_hits[0], opt.max_iterations, opt.rotation_epsilon, opt.transformation_epsilon);
+	gicp::advance(S, s_sum, n_corr, opt.max_iterations, opt.rotation_epsilon, opt.transformation_epsilon);
 	R.S = S;
+	head[p].running = S.running;
 	for (int k = 0; k < 9; k++)
 		frames[12u * p + k] = S.R[k];
 	for (int k = 0; k < 3; k++)
@@ -543,57 +383,53 @@ __global__ void __launch_bounds__(256) k_gicp_decide(const GicpDesc *__restrict_
 	if (S.running)
 		atomicAdd(running, 1u);
 }
-inline uint32_t blocks_of(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 } // namespace
 
-hipError_t launch_gicp_begin(hipStream_t st, uint32_t P, const NdtRec *nrec, GicpRec *rec, double *frames, GicpOpts opt)
+hipError_t launch_gicp_begin(hipStream_t st, uint32_t P, const NdtRec *nrec, GicpRec *rec, RegHead *head, double *frames, GicpOpts opt)
 {
-	hipLaunchKernelGGL(k_gicp_begin, dim3(blocks_of(P, 64)), dim3(64), 0, st, nrec, rec, frames, opt, P);
+	hipLaunchKernelGGL(k_gicp_begin, dim3(blocks_of(P, 64)), dim3(64), 0, st, nrec, rec, head, frames, opt, P);
 	return hipGetLastError();
 }
-hipError_t launch_gicp_tables(hipStream_t st, const GicpDesc *desc, uint32_t P, uint32_t n_max, unsigned char *arena, GicpOpts opt, GicpRec *rec)
-{
-	hipLaunchKernelGGL(k_gicp_cells, dim3(blocks_of(n_max, 256), GICP_TABS * P), dim3(256), 0, st, desc, arena, opt, rec);
-	hipLaunchKernelGGL(k_gicp_offsets, dim3(GICP_TABS * P), dim3(MULLS_GICP_SEG), 0, st, desc, arena, rec);
-	hipLaunchKernelGGL(k_gicp_scatter, dim3(blocks_of(n_max, 256), GICP_TABS * P), dim3(256), 0, st, desc, arena, rec);
-	return hipGetLastError();
-}
-hipError_t launch_gicp_knn(hipStream_t st, const GicpDesc *desc, uint32_t P, uint32_t n_max, unsigned char *arena, GicpOpts opt, GicpRec *rec, uint32_t *max_left)
+hipError_t launch_gicp_knn(hipStream_t st, const GicpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t n_max, unsigned char *arena, GicpOpts opt, GicpRec *rec,
+						   const RegHead *head, uint32_t *max_left)
 {
 	const dim3 grid(blocks_of(n_max, 256), 2u * P), block(256);
 	if (opt.k <= 8)
-		hipLaunchKernelGGL(k_gicp_knn<8>, grid, block, 0, st, desc, arena, opt, rec, max_left);
+		hipLaunchKernelGGL(k_gicp_knn<8>, grid, block, 0, st, desc, tabs, arena, opt, rec, head, max_left);
 	else if (opt.k <= 20)
-		hipLaunchKernelGGL(k_gicp_knn<20>, grid, block, 0, st, desc, arena, opt, rec, max_left);
+		hipLaunchKernelGGL(k_gicp_knn<20>, grid, block, 0, st, desc, tabs, arena, opt, rec, head, max_left);
 	else
-		hipLaunchKernelGGL(k_gicp_knn<32>, grid, block, 0, st, desc, arena, opt, rec, max_left);
+		hipLaunchKernelGGL(k_gicp_knn<32>, grid, block, 0, st, desc, tabs, arena, opt, rec, head, max_left);
 	return hipGetLastError();
 }
-hipError_t launch_gicp_brute(hipStream_t st, const GicpDesc *desc, uint32_t P, uint32_t max_left, unsigned char *arena, GicpOpts opt, const GicpRec *rec)
+hipError_t launch_gicp_brute(hipStream_t st, const GicpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t max_left, unsigned char *arena, GicpOpts opt,
+							 const GicpRec *rec, const RegHead *head)
 {
 	if (!max_left)
 		return hipSuccess;
 	const dim3 grid(max_left, 2u * P), block(64);
 	if (opt.k <= 8)
-		hipLaunchKernelGGL(k_gicp_brute<8>, grid, block, 0, st, desc, arena, opt, rec);
+		hipLaunchKernelGGL(k_gicp_brute<8>, grid, block, 0, st, desc, tabs, arena, opt, rec, head);
 	else if (opt.k <= 20)
-		hipLaunchKernelGGL(k_gicp_brute<20>, grid, block, 0, st, desc, arena, opt, rec);
+		hipLaunchKernelGGL(k_gicp_brute<20>, grid, block, 0, st, desc, tabs, arena, opt, rec, head);
 	else
-		hipLaunchKernelGGL(k_gicp_brute<32>, grid, block, 0, st, desc, arena, opt, rec);
+		hipLaunchKernelGGL(k_gicp_brute<32>, grid, block, 0, st, desc, tabs, arena, opt, rec, head);
 	return hipGetLastError();
 }
-hipError_t launch_gicp_voxels(hipStream_t st, const GicpDesc *desc, uint32_t P, uint32_t slots_max, unsigned char *arena, const GicpRec *rec)
+hipError_t launch_gicp_voxels(hipStream_t st, const GicpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t slots_max, unsigned char *arena, const RegHead *head)
 {
-	hipLaunchKernelGGL(k_gicp_voxels, dim3(blocks_of(slots_max, 256), P), dim3(256), 0, st, desc, arena, rec);
+	hipLaunchKernelGGL(k_gicp_voxels, dim3(blocks_of(slots_max, 256), P), dim3(256), 0, st, desc, tabs, arena, head);
 	return hipGetLastError();
 }
-hipError_t launch_gicp_eval(hipStream_t st, const GicpDesc *desc, uint32_t P, unsigned char *arena, GicpOpts opt, const GicpRec *rec)
+hipError_t launch_gicp_eval(hipStream_t st, const GicpDesc *desc, const RegTab *tabs, uint32_t P, unsigned char *arena, GicpOpts opt, const GicpRec *rec,
+							const RegHead *head)
 {
-	hipLaunchKernelGGL(k_gicp_eval, dim3(MULLS_NDT_TREE / 256u, P), dim3(256), 0, st, desc, arena, opt, rec);
+	hipLaunchKernelGGL(k_gicp_eval, dim3(MULLS_NDT_TREE / 256u, P), dim3(256), 0, st, desc, tabs, arena, opt, rec, head);
 	return hipGetLastError();
 }
-hipError_t launch_gicp_decide(hipStream_t st, const GicpDesc *desc, uint32_t P, unsigned char *arena, GicpOpts opt, GicpRec *rec, double *frames, uint32_t *running)
+hipError_t launch_gicp_decide(hipStream_t st, const GicpDesc *desc, uint32_t P, unsigned char *arena, GicpOpts opt, GicpRec *rec, RegHead *head, double *frames,
+							  uint32_t *running, uint32_t *next)
 {
-	hipLaunchKernelGGL(k_gicp_decide, dim3(P), dim3(256), 0, st, desc, arena, opt, rec, frames, running);
+	hipLaunchKernelGGL(k_gicp_decide, dim3(P), dim3(256), 0, st, desc, arena, opt, rec, head, frames, running, next);
 	return hipGetLastError();
 }

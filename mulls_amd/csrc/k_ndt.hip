@@ -1,21 +1,17 @@
 // k_ndt.hip — the device side of mulls_ndt / mulls_ndt_batch (gfx950).  One launch of each kernel serves every problem of a sub-batch: blockIdx.y is the
 // problem for the per-point and per-slot kernels, blockIdx.x for those that give a problem one workgroup.  Setup: the guess, the box and the stable crop
-// (k_ndt_crop), the target's cells into a hash table keyed by the cell index (k_ndt_cells, k_ndt_offsets, k_ndt_scatter) and one lane per leaf that sorts
+// (k_ndt_crop), the target's cells into a hash table keyed by the cell index (k_ndt_clear, k_ndt_cells, k_ndt_offsets, k_ndt_scatter) and one lane per leaf that sorts
 // its points' indices and adds the points in input order (k_ndt_leaves) — atomics place entries, they never decide an order of additions.  Iteration: the
 // host launches k_ndt_eval (the hot path: 28 double sums per source point, strided partials) and k_ndt_decide (the tree, then the Newton / More-Thuente
 // state of ndt_math.h on one lane) once per tick; a problem that has stopped returns at once.  No kernel waits for another workgroup.
 #include <hip/hip_runtime.h>
 
 #include "ndt_launch.h"
-#include "ndt_tree.h"
+#include "reg_device.h"
 
 namespace
 {
-template <typename T>
-__device__ inline T *at(unsigned char *arena, uint64_t off)
-{
-	return reinterpret_cast<T *>(arena + off);
-}
+static_assert(MULLS_NDT_SEG == MULLS_REG_SEG, "k_ndt_offsets runs reg_device.h's scan");
 __device__ inline bool finite3(float x, float y, float z) { return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z); }
 
 // rows 0 .. 6: DIRECT7 (row 0 alone: DIRECT1); rows 7 .. 32: DIRECT26
@@ -195,6 +191,17 @@ __global__ void __launch_bounds__(MULLS_NDT_SEG) k_ndt_crop(const NdtDesc *__res
 	R.status = status;
 }
 
+// the empty hash table: every key free, every count, start and fill 0
+__global__ void __launch_bounds__(256) k_ndt_clear(const NdtDesc *__restrict__ desc, unsigned char *arena)
+{
+	const NdtDesc D = desc[blockIdx.y];
+	const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+	if (s >= D.table_size)
+		return;
+	at<int32_t>(arena, D.o_keys)[s] = -1;
+	at<uint32_t>(arena, D.o_count)[s] = 0u, at<uint32_t>(arena, D.o_start)[s] = 0u, at<uint32_t>(arena, D.o_fill)[s] = 0u;
+}
+
 // every cropped target point: its cell, the cell's slot in the hash table (claimed by compare-and-swap), the slot's count
 __global__ void __launch_bounds__(256) k_ndt_cells(const NdtDesc *__restrict__ desc, unsigned char *arena, NdtOpts opt, const NdtRec *__restrict__ rec)
 {
@@ -238,33 +245,9 @@ __global__ void __launch_bounds__(MULLS_NDT_SEG) k_ndt_offsets(const NdtDesc *__
 	if (rec[p].status != NDT_ST_OK)
 		return;
 	const NdtDesc D = desc[p];
-	const uint32_t *count = at<const uint32_t>(arena, D.o_count);
-	uint32_t *start = at<uint32_t>(arena, D.o_start);
-	const uint32_t seg = D.table_size / MULLS_NDT_SEG, b = t * seg;
-	uint32_t sum = 0, occ = 0;
-	for (uint32_t k = 0; k < seg; k++)
-		sum += count[b + k], occ += count[b + k] ? 1u : 0u;
-	s_cnt[t] = sum, s_occ[t] = occ;
-	__syncthreads();
+	const uint32_t leaves = scan_counts(at<const uint32_t>(arena, D.o_count), at<uint32_t>(arena, D.o_start), D.table_size, s_cnt, s_occ);
 	if (t == 0)
-	{
-		uint32_t run = 0, leaves = 0;
-		for (uint32_t k = 0; k < MULLS_NDT_SEG; k++)
-		{
-			const uint32_t v = s_cnt[k];
-			s_cnt[k] = run;
-			run += v;
-			leaves += s_occ[k];
-		}
 		rec[p].n_leaves = leaves;
-	}
-	__syncthreads();
-	uint32_t run = s_cnt[t];
-	for (uint32_t k = 0; k < seg; k++)
-	{
-		start[b + k] = run;
-		run += count[b + k];
-	}
 }
 
 __global__ void __launch_bounds__(256) k_ndt_scatter(const NdtDesc *__restrict__ desc, unsigned char *arena, const NdtRec *__restrict__ rec)
@@ -277,16 +260,11 @@ __global__ void __launch_bounds__(256) k_ndt_scatter(const NdtDesc *__restrict__
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= R.n_tgt || i >= D.n_tgt_in)
 		return;
-	const uint32_t slot = at<const uint32_t>(arena, D.o_cell)[i];
-	if (slot >= D.table_size)
-		return;
-	const uint32_t pos = at<const uint32_t>(arena, D.o_start)[slot] + atomicAdd(&at<uint32_t>(arena, D.o_fill)[slot], 1u);
-	if (pos < D.n_tgt_in)
-		at<uint32_t>(arena, D.o_list)[pos] = i;
+	(void)list_point(at<const uint32_t>(arena, D.o_cell), at<const uint32_t>(arena, D.o_start), at<uint32_t>(arena, D.o_fill), at<uint32_t>(arena, D.o_list), D.table_size,
+					 D.n_tgt_in, i);
 }
 
-// one lane per occupied slot: its points' indices ascending (a shell sort: the indices are distinct, so the order does not depend on how they arrived),
-// the sums in input order, the leaf
+// one lane per occupied slot: its points' indices ascending, the sums in input order, the leaf
 __global__ void __launch_bounds__(256) k_ndt_leaves(const NdtDesc *__restrict__ desc, unsigned char *arena, NdtOpts opt, NdtRec *rec)
 {
 	const uint32_t p = blockIdx.y;
@@ -303,19 +281,7 @@ __global__ void __launch_bounds__(256) k_ndt_leaves(const NdtDesc *__restrict__ 
 	if (first >= D.n_tgt_in || n > D.n_tgt_in - first)
 		return;
 	uint32_t *L = at<uint32_t>(arena, D.o_list) + first;
-	const uint32_t gaps[9] = {1750u, 701u, 301u, 132u, 57u, 23u, 10u, 4u, 1u};
-	for (int gi = 0; gi < 9; gi++)
-	{
-		const uint32_t gap = gaps[gi];
-		for (uint32_t i = gap; i < n; i++)
-		{
-			const uint32_t v = L[i];
-			uint32_t k = i;
-			for (; k >= gap && L[k - gap] > v; k -= gap)
-				L[k] = L[k - gap];
-			L[k] = v;
-		}
-	}
+	sort_list(L, n);
 	const float *Tg = at<const float>(arena, D.o_tgt);
 	double s[3] = {0.0, 0.0, 0.0}, q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 	for (uint32_t k = 0; k < n; k++)
@@ -430,35 +396,23 @@ __global__ void __launch_bounds__(256) k_ndt_eval(const NdtDesc *__restrict__ de
 		partial[(uint32_t)k * MULLS_NDT_TREE + lane] = acc[k];
 }
 
-__global__ void __launch_bounds__(256) k_ndt_decide(const NdtDesc *__restrict__ desc, unsigned char *arena, NdtOpts opt, NdtRec *rec, uint32_t *running)
+__global__ void __launch_bounds__(256) k_ndt_decide(const NdtDesc *__restrict__ desc, unsigned char *arena, NdtOpts opt, NdtRec *rec, uint32_t *running,
+													uint32_t *next)
 {
 	__shared__ double s_p[256];
 	__shared__ double s_sum[28];
 	__shared__ int s_run, s_with_h;
 	const uint32_t p = blockIdx.x, t = threadIdx.x;
+	if (p == 0 && t == 0)
+		*next = 0u; // (the next tick's count starts from 0)
 	if (t == 0)
 		s_run = rec[p].S.running, s_with_h = rec[p].S.with_hessian;
 	__syncthreads();
 	if (!s_run)
 		return;
 	const NdtDesc D = desc[p];
-	const double *partial = at<const double>(arena, D.o_partial);
 	const int n_sums = s_with_h ? 28 : 7;
-	for (int k = 0; k < 28; k++)
-	{
-		double v = 0.0;
-		if (k < n_sums)
-		{
-			double r[16];
-#pragma unroll
-			for (int m = 0; m < 16; m++)
-				r[m] = partial[(uint32_t)k * MULLS_NDT_TREE + t + 256u * m];
-			v = tree_of_partials(r, s_p);
-		}
-		if (t == 0)
-			s_sum[k] = v;
-	}
-	__syncthreads();
+	tree_of_sums(at<const double>(arena, D.o_partial), 28, [&](int k) { return k < n_sums; }, s_p, s_sum);
 	if (t != 0)
 		return;
 	NdtRec &R = rec[p];
@@ -542,7 +496,6 @@ __global__ void __launch_bounds__(256) k_ndt_fitness(const NdtDesc *__restrict__
 	if (t == 0)
 		R.fitness = sum / (double)ns;
 }
-inline uint32_t blocks_of(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 } // namespace
 
 hipError_t launch_ndt_crop(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, NdtRec *rec)
@@ -550,8 +503,9 @@ hipError_t launch_ndt_crop(hipStream_t st, const NdtDesc *desc, uint32_t P, unsi
 	hipLaunchKernelGGL(k_ndt_crop, dim3(P), dim3(MULLS_NDT_SEG), 0, st, desc, arena, opt, rec);
 	return hipGetLastError();
 }
-hipError_t launch_ndt_cells(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_tgt_max, unsigned char *arena, NdtOpts opt, NdtRec *rec)
+hipError_t launch_ndt_cells(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_tgt_max, uint32_t table_max, unsigned char *arena, NdtOpts opt, NdtRec *rec)
 {
+	hipLaunchKernelGGL(k_ndt_clear, dim3(blocks_of(table_max, 256), P), dim3(256), 0, st, desc, arena);
 	hipLaunchKernelGGL(k_ndt_cells, dim3(blocks_of(n_tgt_max, 256), P), dim3(256), 0, st, desc, arena, opt, rec);
 	return hipGetLastError();
 }
@@ -580,9 +534,9 @@ hipError_t launch_ndt_eval(hipStream_t st, const NdtDesc *desc, uint32_t P, unsi
 	hipLaunchKernelGGL(k_ndt_eval, dim3(MULLS_NDT_TREE / 256u, P), dim3(256), 0, st, desc, arena, opt, rec);
 	return hipGetLastError();
 }
-hipError_t launch_ndt_decide(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, NdtRec *rec, uint32_t *running)
+hipError_t launch_ndt_decide(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, NdtRec *rec, uint32_t *running, uint32_t *next)
 {
-	hipLaunchKernelGGL(k_ndt_decide, dim3(P), dim3(256), 0, st, desc, arena, opt, rec, running);
+	hipLaunchKernelGGL(k_ndt_decide, dim3(P), dim3(256), 0, st, desc, arena, opt, rec, running, next);
 	return hipGetLastError();
 }
 hipError_t launch_ndt_fitness(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, NdtRec *rec, const double *frames)

@@ -1,7 +1,7 @@
 // k_pcl_icp.hip — the device side of mulls_pcl_icp / mulls_pcl_icp_batch (gfx950).  One launch of each kernel serves every problem of a sub-batch:
 // blockIdx.y is the problem for the per-point, per-slot and per-cell kernels, blockIdx.x for those that give a problem one workgroup.  The crop and the
-// nearest-neighbour pass of the fitness are k_ndt.hip's.  Setup: hash tables of occupied cells (k_pcl_icp_cells, k_pcl_icp_offsets, k_pcl_icp_scatter,
-// as k_gicp.hip's, with the coordinates copied into cell order) and, for Point2Plane, the normals: every cell's list sorted (k_pcl_icp_sort), then one
+// nearest-neighbour pass of the fitness are k_ndt.hip's.  Setup: tables of occupied cells (k_reg_table.hip, reg_table.h, with the coordinates
+// copied into cell order) and, for Point2Plane, the normals: every cell's list sorted (k_pcl_icp_sort), then one
 // workgroup per cell that merges its 27 lists through LDS tiles in ascending index (k_pcl_icp_normals).  A tick: the moved source re-binned when the
 // correspondences are reciprocal, k_pcl_icp_search (the hot path: the exact nearest target point within the distance, 27 cells, ties by index),
 // k_pcl_icp_recip, k_pcl_icp_accum (and k_pcl_icp_cross for Point2Point: the centroids come first) into strided partials, k_pcl_icp_decide (the tree,
@@ -9,70 +9,36 @@
 // an order of additions.  No kernel waits for another workgroup.  Every loop is bounded by a descriptor field, a launch argument or a constant.
 #include <hip/hip_runtime.h>
 
-#include "ndt_tree.h"
 #include "pcl_icp_launch.h"
+#include "reg_device.h"
 
 namespace
 {
-template <typename T>
-__device__ inline T *at(unsigned char *arena, uint64_t off)
-{
-	return reinterpret_cast<T *>(arena + off);
-}
-constexpr uint64_t EMPTY = 0xffffffffffffffffull;
-constexpr uint32_t NO_SLOT = 0xffffffffu, NO_POINT = 0xffffffffu;
+constexpr uint32_t NO_POINT = 0xffffffffu;
 constexpr uint32_t TILE = MULLS_PCL_ICP_TILE;
 
-// the slot of a key, or NO_SLOT
-__device__ inline uint32_t find_slot(const uint64_t *__restrict__ keys, uint64_t key, uint32_t slots, uint32_t shift)
-{
-	uint32_t h = gicp::home_slot(key, shift);
-	for (uint32_t probe = 0; probe < slots; probe++)
-	{
-		const uint64_t k = keys[h];
-		if (k == key)
-			return h;
-		if (k == EMPTY)
-			return NO_SLOT;
-		h = (h + 1u) & (slots - 1u);
-	}
-	return NO_SLOT;
-}
-__device__ inline bool cell_in_range(int32_t x, int32_t y, int32_t z)
-{
-	return x >= -1048576 && y >= -1048576 && z >= -1048576 && x < 1048576 && y < 1048576 && z < 1048576;
-}
-// a table's points: the source for PCL_ICP_TAB_SRC, the target for the others
-__device__ inline uint32_t points_of(const PclIcpRec &R, const PclIcpTab &T, int tb)
-{
-	const uint32_t n = R.n[tb == PCL_ICP_TAB_SRC ? 0 : 1];
-	return n < T.n_cap ? n : T.n_cap;
-}
-// does a table take part in this launch?  The source's is rebuilt while the problem runs
-__device__ inline bool table_live(const PclIcpRec &R, const PclIcpTab &T, int tb)
-{
-	return R.status == PCL_ICP_ST_OK && T.n_cap != 0 && (tb != PCL_ICP_TAB_SRC || (R.S.running && !R.range));
-}
-
-__global__ void __launch_bounds__(64) k_pcl_icp_begin(const NdtRec *__restrict__ nrec, PclIcpRec *rec, double *frames, uint32_t P)
+__global__ void __launch_bounds__(64) k_pcl_icp_begin(const NdtRec *__restrict__ nrec, PclIcpRec *rec, RegHead *head, double *frames, uint32_t P)
 {
 	const uint32_t p = blockIdx.x * 64u + threadIdx.x;
 	if (p >= P)
 		return;
-	PclIcpRec &R = rec[p]; // (zeroed by the host: range is only ever set)
-	R.n[0] = nrec[p].n_src, R.n[1] = nrec[p].n_tgt;
+	PclIcpRec &R = rec[p];
+	RegHead H{};
+	H.n[0] = nrec[p].n_src, H.n[1] = nrec[p].n_tgt;
 	R.n_fit = 0, R.fitness = 0.0, R.pad = 0;
 	int status = PCL_ICP_ST_OK;
 	if (nrec[p].status == NDT_ST_NONFINITE)
 		status = PCL_ICP_ST_NONFINITE;
-	else if (nrec[p].status != NDT_ST_OK || R.n[0] == 0 || R.n[1] == 0)
+	else if (nrec[p].status != NDT_ST_OK || H.n[0] == 0 || H.n[1] == 0)
 		status = PCL_ICP_ST_EMPTY;
-	R.status = status;
+	H.status = status;
 	pcl_icp::State S;
 	pcl_icp::begin(S);
 	if (status != PCL_ICP_ST_OK)
 		S.running = 0;
 	R.S = S;
+	H.running = S.running;
+	head[p] = H;
 	for (int k = 0; k < 9; k++)
 		frames[12u * p + k] = S.R[k];
 	for (int k = 0; k < 3; k++)
@@ -80,14 +46,14 @@ __global__ void __launch_bounds__(64) k_pcl_icp_begin(const NdtRec *__restrict__
 }
 
 // the moved source starts as the cropped source; a source point outside the cells' range refuses the problem
-__global__ void __launch_bounds__(256) k_pcl_icp_copy(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec)
+__global__ void __launch_bounds__(256) k_pcl_icp_copy(const PclIcpDesc *__restrict__ desc, const RegTab *__restrict__ tabs, unsigned char *arena, RegHead *head)
 {
 	const uint32_t p = blockIdx.y;
-	PclIcpRec &R = rec[p];
-	if (R.status != PCL_ICP_ST_OK)
+	RegHead &H = head[p];
+	if (H.status != PCL_ICP_ST_OK)
 		return;
 	const PclIcpDesc &D = desc[p];
-	const uint32_t ns = R.n[0] < D.n_src_cap ? R.n[0] : D.n_src_cap;
+	const uint32_t ns = H.n[0] < D.n_src_cap ? H.n[0] : D.n_src_cap;
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= ns)
 		return;
@@ -96,131 +62,19 @@ __global__ void __launch_bounds__(256) k_pcl_icp_copy(const PclIcpDesc *__restri
 	const float x = S3[3 * i], y = S3[3 * i + 1], z = S3[3 * i + 2];
 	M3[3 * i] = x, M3[3 * i + 1] = y, M3[3 * i + 2] = z;
 	int ok = 1;
-	const double inv = opt.inv_edge[PCL_ICP_TAB_TGT];
+	const double inv = tabs[MULLS_REG_TABS * p + PCL_ICP_TAB_TGT].inv_edge;
 	(void)pcl_icp::cell_coord(x, inv, &ok), (void)pcl_icp::cell_coord(y, inv, &ok), (void)pcl_icp::cell_coord(z, inv, &ok);
 	if (!ok)
-		atomicOr(&R.range, 1u);
+		atomicOr(&H.range, 1u);
 }
 
-__global__ void __launch_bounds__(256) k_pcl_icp_clear(const PclIcpDesc *__restrict__ desc, unsigned char *arena, const PclIcpRec *__restrict__ rec, int tb)
+// one lane per occupied slot of the normals' table: its points' indices ascending
+__global__ void __launch_bounds__(256) k_pcl_icp_sort(const RegTab *__restrict__ tabs, unsigned char *arena, const RegHead *__restrict__ head)
 {
 	const uint32_t p = blockIdx.y;
-	const PclIcpTab T = desc[p].tab[tb];
-	if (!table_live(rec[p], T, tb))
-		return;
-	const uint32_t s = blockIdx.x * 256u + threadIdx.x;
-	if (s >= T.slots)
-		return;
-	at<uint64_t>(arena, T.o_keys)[s] = EMPTY;
-	at<uint32_t>(arena, T.o_count)[s] = 0u, at<uint32_t>(arena, T.o_start)[s] = 0u, at<uint32_t>(arena, T.o_fill)[s] = 0u;
-}
-
-// every point of a table's cloud: its cell, the cell's slot (claimed by compare-and-swap), the slot's count
-__global__ void __launch_bounds__(256) k_pcl_icp_cells(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, int tb)
-{
-	const uint32_t p = blockIdx.y;
-	PclIcpRec &R = rec[p];
-	const PclIcpTab T = desc[p].tab[tb];
-	if (!table_live(R, T, tb))
-		return;
-	const uint32_t n = points_of(R, T, tb);
-	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i >= n)
-		return;
-	const float *P3 = at<const float>(arena, T.o_pts);
-	const double inv = opt.inv_edge[tb];
-	int ok = 1;
-	const int32_t c0 = pcl_icp::cell_coord(P3[3 * i], inv, &ok), c1 = pcl_icp::cell_coord(P3[3 * i + 1], inv, &ok), c2 = pcl_icp::cell_coord(P3[3 * i + 2], inv, &ok);
-	uint32_t found = NO_SLOT;
-	if (ok)
-	{
-		const uint64_t key = gicp::pack_coords(c0, c1, c2);
-		unsigned long long *keys = at<unsigned long long>(arena, T.o_keys);
-		uint32_t h = gicp::home_slot(key, T.shift);
-		for (uint32_t probe = 0; probe < T.slots; probe++)
-		{
-			const unsigned long long was = atomicCAS(&keys[h], (unsigned long long)EMPTY, (unsigned long long)key);
-			if (was == EMPTY || was == key)
-			{
-				found = h;
-				break;
-			}
-			h = (h + 1u) & (T.slots - 1u);
-		}
-	}
-	else if (tb != PCL_ICP_TAB_SRC)
-		atomicOr(&R.range, 1u); // a target point that does not fit the packed key: refused by the host.  A moved source point that does not takes no part.
-	at<uint32_t>(arena, T.o_cell)[i] = found;
-	if (found != NO_SLOT)
-		atomicAdd(&at<uint32_t>(arena, T.o_count)[found], 1u);
-}
-
-// start[slot]: the exclusive sum of the counts
-__global__ void __launch_bounds__(MULLS_PCL_ICP_SEG) k_pcl_icp_offsets(const PclIcpDesc *__restrict__ desc, unsigned char *arena, const PclIcpRec *__restrict__ rec, int tb)
-{
-	__shared__ uint32_t s_cnt[MULLS_PCL_ICP_SEG];
-	const uint32_t p = blockIdx.x, t = threadIdx.x;
-	const PclIcpTab T = desc[p].tab[tb];
-	if (!table_live(rec[p], T, tb))
-		return;
-	const uint32_t *count = at<const uint32_t>(arena, T.o_count);
-	uint32_t *start = at<uint32_t>(arena, T.o_start);
-	const uint32_t seg = T.slots / MULLS_PCL_ICP_SEG, b = t * seg;
-	uint32_t sum = 0;
-	for (uint32_t k = 0; k < seg; k++)
-		sum += count[b + k];
-	s_cnt[t] = sum;
-	__syncthreads();
-	if (t == 0)
-	{
-		uint32_t run = 0;
-		for (uint32_t k = 0; k < MULLS_PCL_ICP_SEG; k++)
-		{
-			const uint32_t v = s_cnt[k];
-			s_cnt[k] = run;
-			run += v;
-		}
-	}
-	__syncthreads();
-	uint32_t run = s_cnt[t];
-	for (uint32_t k = 0; k < seg; k++)
-	{
-		start[b + k] = run;
-		run += count[b + k];
-	}
-}
-
-__global__ void __launch_bounds__(256) k_pcl_icp_scatter(const PclIcpDesc *__restrict__ desc, unsigned char *arena, const PclIcpRec *__restrict__ rec, int tb)
-{
-	const uint32_t p = blockIdx.y;
-	const PclIcpRec &R = rec[p];
-	const PclIcpTab T = desc[p].tab[tb];
-	if (!table_live(R, T, tb))
-		return;
-	const uint32_t n = points_of(R, T, tb);
-	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i >= n)
-		return;
-	const uint32_t slot = at<const uint32_t>(arena, T.o_cell)[i];
-	if (slot >= T.slots)
-		return;
-	const uint32_t pos = at<const uint32_t>(arena, T.o_start)[slot] + atomicAdd(&at<uint32_t>(arena, T.o_fill)[slot], 1u);
-	if (pos >= T.n_cap)
-		return;
-	const float *P3 = at<const float>(arena, T.o_pts);
-	float *Q3 = at<float>(arena, T.o_sorted);
-	at<uint32_t>(arena, T.o_list)[pos] = i;
-	Q3[3 * pos] = P3[3 * i], Q3[3 * pos + 1] = P3[3 * i + 1], Q3[3 * pos + 2] = P3[3 * i + 2];
-}
-
-// one lane per occupied slot of the normals' table: its points' indices ascending (a shell sort: the indices are distinct, so the order does not
-// depend on how they arrived)
-__global__ void __launch_bounds__(256) k_pcl_icp_sort(const PclIcpDesc *__restrict__ desc, unsigned char *arena, const PclIcpRec *__restrict__ rec)
-{
-	const uint32_t p = blockIdx.y;
-	const PclIcpRec &R = rec[p];
-	const PclIcpTab T = desc[p].tab[PCL_ICP_TAB_NRM];
-	if (!table_live(R, T, PCL_ICP_TAB_NRM) || R.range)
+	const RegHead &H = head[p];
+	const RegTab T = tabs[MULLS_REG_TABS * p + PCL_ICP_TAB_NRM];
+	if (!table_live(H, T) || H.range)
 		return;
 	const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
 	if (slot >= T.slots)
@@ -231,37 +85,25 @@ __global__ void __launch_bounds__(256) k_pcl_icp_sort(const PclIcpDesc *__restri
 	const uint32_t first = at<const uint32_t>(arena, T.o_start)[slot];
 	if (first >= T.n_cap || n > T.n_cap - first)
 		return;
-	uint32_t *L = at<uint32_t>(arena, T.o_list) + first;
-	const uint32_t gaps[9] = {1750u, 701u, 301u, 132u, 57u, 23u, 10u, 4u, 1u};
-	for (int gi = 0; gi < 9; gi++)
-	{
-		const uint32_t gap = gaps[gi];
-		for (uint32_t i = gap; i < n; i++)
-		{
-			const uint32_t v = L[i];
-			uint32_t k = i;
-			for (; k >= gap && L[k - gap] > v; k -= gap)
-				L[k] = L[k - gap];
-			L[k] = v;
-		}
-	}
+	sort_list(at<uint32_t>(arena, T.o_list) + first, n);
 }
 
 // The normals.  One workgroup per occupied cell; a thread per point of the cell (256 at a time).  The neighbours of those points lie in the 27 cells
 // around it, whose sorted lists are merged window by window: a window is TILE consecutive target indices, the lists' entries inside it are flagged,
 // compacted in index order into an LDS tile of coordinates, and every thread walks the tile.  So a point adds its neighbours in ascending index
 // whatever their number; two passes (the sum, then the scatter about the mean), then pcl_icp_math.h's normal.
-__global__ void __launch_bounds__(256) k_pcl_icp_normals(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *__restrict__ rec)
+__global__ void __launch_bounds__(256) k_pcl_icp_normals(const PclIcpDesc *__restrict__ desc, const RegTab *__restrict__ tabs, unsigned char *arena, PclIcpOpts opt,
+														 const RegHead *__restrict__ head)
 {
 	__shared__ uint32_t s_beg[27], s_end[27], s_cur[27], s_lo[27], s_hi[27];
 	__shared__ uint32_t s_flag[TILE], s_wave[4];
 	__shared__ float s_tile[TILE][3];
 	const uint32_t p = blockIdx.y, slot = blockIdx.x, t = threadIdx.x;
-	const PclIcpRec &R = rec[p];
-	const PclIcpTab T = desc[p].tab[PCL_ICP_TAB_NRM];
-	if (!table_live(R, T, PCL_ICP_TAB_NRM) || R.range || slot >= T.slots)
+	const RegHead &H = head[p];
+	const RegTab T = tabs[MULLS_REG_TABS * p + PCL_ICP_TAB_NRM];
+	if (!table_live(H, T) || H.range || slot >= T.slots)
 		return;
-	const uint32_t n = points_of(R, T, PCL_ICP_TAB_NRM);
+	const uint32_t n = points_of(H, T);
 	const uint64_t *keys = at<const uint64_t>(arena, T.o_keys);
 	const uint32_t *start = at<const uint32_t>(arena, T.o_start), *count = at<const uint32_t>(arena, T.o_count), *list = at<const uint32_t>(arena, T.o_list);
 	const uint32_t cnt = count[slot], first = start[slot];
@@ -272,15 +114,12 @@ __global__ void __launch_bounds__(256) k_pcl_icp_normals(const PclIcpDesc *__res
 	if (t < 27u)
 	{
 		const uint64_t key = keys[slot];
-		const int32_t cx = (int32_t)(key & 0x1fffffu) - 1048576 + ((int32_t)(t % 3u) - 1), cy = (int32_t)((key >> 21) & 0x1fffffu) - 1048576 + ((int32_t)((t / 3u) % 3u) - 1),
-					  cz = (int32_t)((key >> 42) & 0x1fffffu) - 1048576 + ((int32_t)(t / 9u) - 1);
+		const int32_t cx = (int32_t)(key & 0x1fffffu) - 1048576, cy = (int32_t)((key >> 21) & 0x1fffffu) - 1048576, cz = (int32_t)((key >> 42) & 0x1fffffu) - 1048576;
 		uint32_t b = 0, e = 0;
-		if (cell_in_range(cx, cy, cz))
-		{
-			const uint32_t s = find_slot(keys, gicp::pack_coords(cx, cy, cz), T.slots, T.shift);
-			if (s != NO_SLOT && start[s] < n && count[s] <= n - start[s])
+		visit_cells(keys, T.slots, T.shift, cx, cy, cz, (int)t, (int)t + 1, [&](int, uint32_t s) { // (thread t: the t-th of the 27 lists)
+			if (start[s] < n && count[s] <= n - start[s])
 				b = start[s], e = b + count[s];
-		}
+		});
 		s_beg[t] = b, s_end[t] = e;
 	}
 	__syncthreads();
@@ -381,49 +220,39 @@ __global__ void __launch_bounds__(256) k_pcl_icp_normals(const PclIcpDesc *__res
 
 // The loop's hot path.  One lane per moved source point: the 27 cells around its own, every target point in them, the smallest by (float d2, index);
 // no pair when the distance is above the threshold.
-__global__ void __launch_bounds__(256) k_pcl_icp_search(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *__restrict__ rec)
+__global__ void __launch_bounds__(256) k_pcl_icp_search(const PclIcpDesc *__restrict__ desc, const RegTab *__restrict__ tabs, unsigned char *arena, PclIcpOpts opt,
+														const PclIcpRec *__restrict__ rec, const RegHead *__restrict__ head)
 {
 	const uint32_t p = blockIdx.y;
-	const PclIcpRec &R = rec[p];
-	if (!R.S.running || R.range)
+	const RegHead &H = head[p];
+	if (!rec[p].S.running || H.range)
 		return;
 	const PclIcpDesc &D = desc[p];
-	const PclIcpTab T = D.tab[PCL_ICP_TAB_TGT];
-	const uint32_t ns = R.n[0] < D.n_src_cap ? R.n[0] : D.n_src_cap, nt = points_of(R, T, PCL_ICP_TAB_TGT);
+	const RegTab T = tabs[MULLS_REG_TABS * p + PCL_ICP_TAB_TGT];
+	const uint32_t ns = H.n[0] < D.n_src_cap ? H.n[0] : D.n_src_cap, nt = points_of(H, T);
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= ns)
 		return;
 	const float *M3 = at<const float>(arena, D.o_mov), *Q3 = at<const float>(arena, T.o_sorted);
 	const float qx = M3[3 * i], qy = M3[3 * i + 1], qz = M3[3 * i + 2];
-	const uint64_t *keys = at<const uint64_t>(arena, T.o_keys);
 	const uint32_t *start = at<const uint32_t>(arena, T.o_start), *count = at<const uint32_t>(arena, T.o_count), *list = at<const uint32_t>(arena, T.o_list);
 	int ok = 1;
-	const double inv = opt.inv_edge[PCL_ICP_TAB_TGT];
-	const int32_t cx = pcl_icp::cell_coord(qx, inv, &ok), cy = pcl_icp::cell_coord(qy, inv, &ok), cz = pcl_icp::cell_coord(qz, inv, &ok);
+	const int32_t cx = pcl_icp::cell_coord(qx, T.inv_edge, &ok), cy = pcl_icp::cell_coord(qy, T.inv_edge, &ok), cz = pcl_icp::cell_coord(qz, T.inv_edge, &ok);
 	float best = __builtin_huge_valf();
 	uint32_t bi = NO_POINT;
 	if (ok)
-		for (int dz = -1; dz <= 1; dz++)
-			for (int dy = -1; dy <= 1; dy++)
-				for (int dx = -1; dx <= 1; dx++)
-				{
-					const int32_t nx = cx + dx, ny = cy + dy, nz = cz + dz;
-					if (!cell_in_range(nx, ny, nz))
-						continue;
-					const uint32_t slot = find_slot(keys, gicp::pack_coords(nx, ny, nz), T.slots, T.shift);
-					if (slot == NO_SLOT)
-						continue;
-					const uint32_t b = start[slot], cnt = count[slot];
-					if (b >= nt || cnt > nt - b)
-						continue;
-					for (uint32_t j = b; j < b + cnt; j++)
-					{
-						const float d2 = pcl_icp::dist2(qx, qy, qz, Q3[3 * j], Q3[3 * j + 1], Q3[3 * j + 2]);
-						const uint32_t m = list[j];
-						if (m < nt && pcl_icp::before(d2, m, best, bi))
-							best = d2, bi = m;
-					}
-				}
+		visit_cells(at<const uint64_t>(arena, T.o_keys), T.slots, T.shift, cx, cy, cz, 0, 27, [&](int, uint32_t slot) {
+			const uint32_t b = start[slot], cnt = count[slot];
+			if (b >= nt || cnt > nt - b)
+				return;
+			for (uint32_t j = b; j < b + cnt; j++)
+			{
+				const float d2 = pcl_icp::dist2(qx, qy, qz, Q3[3 * j], Q3[3 * j + 1], Q3[3 * j + 2]);
+				const uint32_t m = list[j];
+				if (m < nt && pcl_icp::before(d2, m, best, bi))
+					best = d2, bi = m;
+			}
+		});
 	if (bi != NO_POINT && (double)best > opt.thr2)
 		bi = NO_POINT;
 	at<int32_t>(arena, D.o_match)[i] = bi == NO_POINT ? -1 : (int32_t)bi;
@@ -432,17 +261,19 @@ __global__ void __launch_bounds__(256) k_pcl_icp_search(const PclIcpDesc *__rest
 
 // The reciprocity test.  A source point that beats i at its target point m lies within d(i, m) <= the threshold of m: the 27 cells of the moved
 // source around m's cell decide it.  i keeps its pair only if no moved source point is before it by (d2 to m, index).
-__global__ void __launch_bounds__(256) k_pcl_icp_recip(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *__restrict__ rec)
+__global__ void __launch_bounds__(256) k_pcl_icp_recip(const PclIcpDesc *__restrict__ desc, const RegTab *__restrict__ tabs, unsigned char *arena,
+													   const PclIcpRec *__restrict__ rec, const RegHead *__restrict__ head)
 {
 	const uint32_t p = blockIdx.y;
-	const PclIcpRec &R = rec[p];
-	if (!R.S.running || R.range)
+	const RegHead &H = head[p];
+	if (!rec[p].S.running || H.range)
 		return;
 	const PclIcpDesc &D = desc[p];
-	const PclIcpTab T = D.tab[PCL_ICP_TAB_SRC];
+	const RegTab T = tabs[MULLS_REG_TABS * p + PCL_ICP_TAB_SRC];
 	if (!T.n_cap)
 		return;
-	const uint32_t ns = points_of(R, T, PCL_ICP_TAB_SRC), nt = points_of(R, D.tab[PCL_ICP_TAB_TGT], PCL_ICP_TAB_TGT);
+	const RegTab &TT = tabs[MULLS_REG_TABS * p + PCL_ICP_TAB_TGT];
+	const uint32_t ns = points_of(H, T), nt = points_of(H, TT);
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i >= ns)
 		return;
@@ -451,47 +282,37 @@ __global__ void __launch_bounds__(256) k_pcl_icp_recip(const PclIcpDesc *__restr
 	if (m < 0 || (uint32_t)m >= nt)
 		return;
 	const float di = at<const float>(arena, D.o_d2)[i];
-	const float *G3 = at<const float>(arena, D.tab[PCL_ICP_TAB_TGT].o_pts), *Q3 = at<const float>(arena, T.o_sorted);
+	const float *G3 = at<const float>(arena, TT.o_pts), *Q3 = at<const float>(arena, T.o_sorted);
 	const float tx = G3[3 * m], ty = G3[3 * m + 1], tz = G3[3 * m + 2];
-	const uint64_t *keys = at<const uint64_t>(arena, T.o_keys);
 	const uint32_t *start = at<const uint32_t>(arena, T.o_start), *count = at<const uint32_t>(arena, T.o_count), *list = at<const uint32_t>(arena, T.o_list);
 	int ok = 1;
-	const double inv = opt.inv_edge[PCL_ICP_TAB_SRC];
-	const int32_t cx = pcl_icp::cell_coord(tx, inv, &ok), cy = pcl_icp::cell_coord(ty, inv, &ok), cz = pcl_icp::cell_coord(tz, inv, &ok);
+	const int32_t cx = pcl_icp::cell_coord(tx, T.inv_edge, &ok), cy = pcl_icp::cell_coord(ty, T.inv_edge, &ok), cz = pcl_icp::cell_coord(tz, T.inv_edge, &ok);
 	bool beaten = false;
 	if (ok)
-		for (int dz = -1; dz <= 1; dz++)
-			for (int dy = -1; dy <= 1; dy++)
-				for (int dx = -1; dx <= 1; dx++)
-				{
-					const int32_t nx = cx + dx, ny = cy + dy, nz = cz + dz;
-					if (!cell_in_range(nx, ny, nz))
-						continue;
-					const uint32_t slot = find_slot(keys, gicp::pack_coords(nx, ny, nz), T.slots, T.shift);
-					if (slot == NO_SLOT)
-						continue;
-					const uint32_t b = start[slot], cnt = count[slot];
-					if (b >= ns || cnt > ns - b)
-						continue;
-					for (uint32_t j = b; j < b + cnt; j++)
-						if (pcl_icp::before(pcl_icp::dist2(Q3[3 * j], Q3[3 * j + 1], Q3[3 * j + 2], tx, ty, tz), list[j], di, i))
-							beaten = true;
-				}
+		visit_cells(at<const uint64_t>(arena, T.o_keys), T.slots, T.shift, cx, cy, cz, 0, 27, [&](int, uint32_t slot) {
+			const uint32_t b = start[slot], cnt = count[slot];
+			if (b >= ns || cnt > ns - b)
+				return;
+			for (uint32_t j = b; j < b + cnt; j++)
+				if (pcl_icp::before(pcl_icp::dist2(Q3[3 * j], Q3[3 * j + 1], Q3[3 * j + 2], tx, ty, tz), list[j], di, i))
+					beaten = true;
+		});
 	if (beaten)
 		match[i] = -1;
 }
 
 // Lane l of the problem's MULLS_NDT_TREE lanes takes the source points l, l + MULLS_NDT_TREE, ..: a pair's terms into the lane's sums.  Point2Plane:
 // all 28.  Point2Point: the sums of the paired points and of d2; the cross-covariance follows in k_pcl_icp_cross.
-__global__ void __launch_bounds__(256) k_pcl_icp_accum(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *__restrict__ rec)
+__global__ void __launch_bounds__(256) k_pcl_icp_accum(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *__restrict__ rec,
+													   const RegHead *__restrict__ head)
 {
 	const uint32_t p = blockIdx.y;
-	const PclIcpRec &R = rec[p];
-	if (!R.S.running || R.range)
+	const RegHead &H = head[p];
+	if (!rec[p].S.running || H.range)
 		return;
 	const PclIcpDesc &D = desc[p];
-	const uint32_t ns = R.n[0] < D.n_src_cap ? R.n[0] : D.n_src_cap, nt = R.n[1] < D.n_tgt_cap ? R.n[1] : D.n_tgt_cap;
-	const float *M3 = at<const float>(arena, D.o_mov), *G3 = at<const float>(arena, D.tab[PCL_ICP_TAB_TGT].o_pts), *N3 = at<const float>(arena, D.o_nrm);
+	const uint32_t ns = H.n[0] < D.n_src_cap ? H.n[0] : D.n_src_cap, nt = H.n[1] < D.n_tgt_cap ? H.n[1] : D.n_tgt_cap;
+	const float *M3 = at<const float>(arena, D.o_mov), *G3 = at<const float>(arena, D.o_tgt), *N3 = at<const float>(arena, D.o_nrm);
 	const int32_t *match = at<const int32_t>(arena, D.o_match);
 	const float *d2 = at<const float>(arena, D.o_d2);
 	const uint32_t lane = blockIdx.x * 256u + threadIdx.x;
@@ -528,51 +349,27 @@ __global__ void __launch_bounds__(256) k_pcl_icp_accum(const PclIcpDesc *__restr
 	at<uint32_t>(arena, D.o_hits)[lane] = hits;
 }
 
-// the number of pairs: the lanes' counts added up by a 256-thread workgroup; the sum in every thread
-__device__ inline uint32_t pairs_of(const uint32_t *__restrict__ hits, uint32_t *s_hits)
-{
-	const uint32_t t = threadIdx.x;
-	uint32_t h = 0;
-	for (int m = 0; m < 16; m++)
-		h += hits[t + 256u * m];
-	__syncthreads();
-	s_hits[t] = h;
-	__syncthreads();
-	for (uint32_t w = 128; w >= 1; w >>= 1)
-	{
-		if (t < w)
-			s_hits[t] += s_hits[t + w];
-		__syncthreads();
-	}
-	return s_hits[0];
-}
-
 // Point2Point's second pass.  Every workgroup takes the tree over the six sums itself (the same text as k_pcl_icp_decide's, so the same centroids),
 // then its lanes add the products of the demeaned pairs.
-__global__ void __launch_bounds__(256) k_pcl_icp_cross(const PclIcpDesc *__restrict__ desc, unsigned char *arena, const PclIcpRec *__restrict__ rec)
+__global__ void __launch_bounds__(256) k_pcl_icp_cross(const PclIcpDesc *__restrict__ desc, unsigned char *arena, const PclIcpRec *__restrict__ rec,
+													   const RegHead *__restrict__ head)
 {
 	__shared__ double s_p[256];
+	__shared__ double s_c[6];
 	__shared__ uint32_t s_hits[256];
 	const uint32_t p = blockIdx.y, t = threadIdx.x;
-	const PclIcpRec &R = rec[p];
-	if (!R.S.running || R.range)
+	const RegHead &H = head[p];
+	if (!rec[p].S.running || H.range)
 		return;
 	const PclIcpDesc &D = desc[p];
 	double *partial = at<double>(arena, D.o_partial);
+	tree_of_sums(partial, 6, [](int) { return true; }, s_p, s_c);
+	const double dn = (double)hits_of(at<const uint32_t>(arena, D.o_hits), s_hits);
 	double c[6];
 	for (int k = 0; k < 6; k++)
-	{
-		double r[16];
-#pragma unroll
-		for (int m = 0; m < 16; m++)
-			r[m] = partial[(uint32_t)k * MULLS_NDT_TREE + t + 256u * m];
-		c[k] = tree_of_partials(r, s_p);
-	}
-	const double dn = (double)pairs_of(at<const uint32_t>(arena, D.o_hits), s_hits);
-	for (int k = 0; k < 6; k++)
-		c[k] = c[k] / dn;
-	const uint32_t ns = R.n[0] < D.n_src_cap ? R.n[0] : D.n_src_cap, nt = R.n[1] < D.n_tgt_cap ? R.n[1] : D.n_tgt_cap;
-	const float *M3 = at<const float>(arena, D.o_mov), *G3 = at<const float>(arena, D.tab[PCL_ICP_TAB_TGT].o_pts);
+		c[k] = s_c[k] / dn;
+	const uint32_t ns = H.n[0] < D.n_src_cap ? H.n[0] : D.n_src_cap, nt = H.n[1] < D.n_tgt_cap ? H.n[1] : D.n_tgt_cap;
+	const float *M3 = at<const float>(arena, D.o_mov), *G3 = at<const float>(arena, D.o_tgt);
 	const int32_t *match = at<const int32_t>(arena, D.o_match);
 	const uint32_t lane = blockIdx.x * 256u + t;
 	double acc[9];
@@ -598,8 +395,8 @@ __global__ void __launch_bounds__(256) k_pcl_icp_cross(const PclIcpDesc *__restr
 }
 
 // one workgroup per problem: the tree over the sums, pcl_icp_math.h's advance on one lane, then the stored source moved by the step
-__global__ void __launch_bounds__(256) k_pcl_icp_decide(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, double *frames,
-														uint32_t *running, uint32_t *next)
+__global__ void __launch_bounds__(256) k_pcl_icp_decide(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, RegHead *head,
+														double *frames, uint32_t *running, uint32_t *next)
 {
 	__shared__ double s_p[256];
 	__shared__ double s_sum[pcl_icp::N_SUMS];
@@ -612,37 +409,24 @@ __global__ void __launch_bounds__(256) k_pcl_icp_decide(const PclIcpDesc *__rest
 	if (t == 0)
 	{
 		s_run = rec[p].S.running;
-		if (s_run && rec[p].range)
-			rec[p].S.running = 0, s_run = 0; // refused by the host
+		if (s_run && head[p].range)
+			rec[p].S.running = 0, head[p].running = 0, s_run = 0; // refused by the host
 	}
 	__syncthreads();
 	if (!s_run)
 		return;
 	const PclIcpDesc &D = desc[p];
-	const double *partial = at<const double>(arena, D.o_partial);
-	for (int k = 0; k < pcl_icp::N_SUMS; k++)
-	{
-		if (opt.metric == pcl_icp::POINT2POINT && k >= pcl_icp::SUM_H + 9 && k != pcl_icp::SUM_D2)
-		{
-			if (t == 0)
-				s_sum[k] = 0.0;
-			continue;
-		}
-		double r[16];
-#pragma unroll
-		for (int m = 0; m < 16; m++)
-			r[m] = partial[(uint32_t)k * MULLS_NDT_TREE + t + 256u * m];
-		const double v = tree_of_partials(r, s_p);
-		if (t == 0)
-			s_sum[k] = v;
-	}
-	const uint32_t n_corr = pairs_of(at<const uint32_t>(arena, D.o_hits), s_hits);
+	// (Point2Point has no sums between the cross-covariance and the squared distances)
+	tree_of_sums(at<const double>(arena, D.o_partial), pcl_icp::N_SUMS,
+				 [&](int k) { return !(opt.metric == pcl_icp::POINT2POINT && k >= pcl_icp::SUM_H + 9 && k != pcl_icp::SUM_D2); }, s_p, s_sum);
+	const uint32_t n_corr = hits_of(at<const uint32_t>(arena, D.o_hits), s_hits);
 	if (t == 0)
 	{
 		PclIcpRec &R = rec[p];
 		pcl_icp::State S = R.S;
 		pcl_icp::advance(S, opt.metric, s_sum, n_corr, opt.max_iter_num, opt.transformation_epsilon, opt.euclidean_fitness_epsilon);
 		R.S = S;
+		head[p].running = S.running;
 		for (int k = 0; k < 9; k++)
 			frames[12u * p + k] = S.R[k], s_step[k] = S.Rs[k];
 		for (int k = 0; k < 3; k++)
@@ -654,23 +438,24 @@ __global__ void __launch_bounds__(256) k_pcl_icp_decide(const PclIcpDesc *__rest
 	__syncthreads();
 	if (!s_moved)
 		return;
-	const uint32_t ns = rec[p].n[0] < D.n_src_cap ? rec[p].n[0] : D.n_src_cap;
+	const uint32_t ns = head[p].n[0] < D.n_src_cap ? head[p].n[0] : D.n_src_cap;
 	float *M3 = at<float>(arena, D.o_mov);
 	for (uint32_t i = t; i < ns; i += 256u)
 		pcl_icp::move_stored(s_step, s_step + 9, M3 + 3 * i);
 }
 
 // the fitness: over the source points whose nearest squared distance is within the range, the mean; the strided partials and the tree as every sum here
-__global__ void __launch_bounds__(256) k_pcl_icp_fitness(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec)
+__global__ void __launch_bounds__(256) k_pcl_icp_fitness(const PclIcpDesc *__restrict__ desc, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec,
+														 const RegHead *__restrict__ head)
 {
 	__shared__ double s_p[256];
 	__shared__ uint32_t s_hits[256];
 	const uint32_t p = blockIdx.x, t = threadIdx.x;
 	PclIcpRec &R = rec[p];
-	if (R.status != PCL_ICP_ST_OK)
+	if (head[p].status != PCL_ICP_ST_OK)
 		return;
 	const PclIcpDesc &D = desc[p];
-	const uint32_t ns = R.n[0] < D.n_src_cap ? R.n[0] : D.n_src_cap;
+	const uint32_t ns = head[p].n[0] < D.n_src_cap ? head[p].n[0] : D.n_src_cap;
 	const float *dist = at<const float>(arena, D.o_dist);
 	double r[16];
 	uint32_t h = 0;
@@ -684,70 +469,54 @@ __global__ void __launch_bounds__(256) k_pcl_icp_fitness(const PclIcpDesc *__res
 		r[m] = a;
 	}
 	const double sum = tree_of_partials(r, s_p);
-	s_hits[t] = h;
-	__syncthreads();
-	for (uint32_t w = 128; w >= 1; w >>= 1)
-	{
-		if (t < w)
-			s_hits[t] += s_hits[t + w];
-		__syncthreads();
-	}
+	const uint32_t n_fit = sum_of_counts(h, s_hits);
 	if (t == 0)
 	{
-		R.n_fit = s_hits[0];
-		R.fitness = s_hits[0] ? sum / (double)s_hits[0] : DBL_MAX;
+		R.n_fit = n_fit;
+		R.fitness = n_fit ? sum / (double)n_fit : DBL_MAX;
 	}
 }
-inline uint32_t blocks_of(uint64_t n, uint32_t b) { return (uint32_t)((n + b - 1) / b); }
 } // namespace
 
-hipError_t launch_pcl_icp_begin(hipStream_t st, const PclIcpDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, PclIcpOpts opt, const NdtRec *nrec,
-								PclIcpRec *rec, double *frames)
+hipError_t launch_pcl_icp_begin(hipStream_t st, const PclIcpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t n_src_max, unsigned char *arena, const NdtRec *nrec,
+								PclIcpRec *rec, RegHead *head, double *frames)
 {
-	hipLaunchKernelGGL(k_pcl_icp_begin, dim3(blocks_of(P, 64)), dim3(64), 0, st, nrec, rec, frames, P);
-	hipLaunchKernelGGL(k_pcl_icp_copy, dim3(blocks_of(n_src_max, 256), P), dim3(256), 0, st, desc, arena, opt, rec);
+	hipLaunchKernelGGL(k_pcl_icp_begin, dim3(blocks_of(P, 64)), dim3(64), 0, st, nrec, rec, head, frames, P);
+	hipLaunchKernelGGL(k_pcl_icp_copy, dim3(blocks_of(n_src_max, 256), P), dim3(256), 0, st, desc, tabs, arena, head);
 	return hipGetLastError();
 }
-hipError_t launch_pcl_icp_table(hipStream_t st, const PclIcpDesc *desc, uint32_t P, int tb, uint32_t n_max, uint32_t slots_max, bool clear, unsigned char *arena,
-								PclIcpOpts opt, PclIcpRec *rec)
+hipError_t launch_pcl_icp_normals(hipStream_t st, const PclIcpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t slots_max, unsigned char *arena, PclIcpOpts opt,
+								  const RegHead *head)
 {
-	if (clear)
-		hipLaunchKernelGGL(k_pcl_icp_clear, dim3(blocks_of(slots_max, 256), P), dim3(256), 0, st, desc, arena, rec, tb);
-	hipLaunchKernelGGL(k_pcl_icp_cells, dim3(blocks_of(n_max, 256), P), dim3(256), 0, st, desc, arena, opt, rec, tb);
-	hipLaunchKernelGGL(k_pcl_icp_offsets, dim3(P), dim3(MULLS_PCL_ICP_SEG), 0, st, desc, arena, rec, tb);
-	hipLaunchKernelGGL(k_pcl_icp_scatter, dim3(blocks_of(n_max, 256), P), dim3(256), 0, st, desc, arena, rec, tb);
+	hipLaunchKernelGGL(k_pcl_icp_sort, dim3(blocks_of(slots_max, 256), P), dim3(256), 0, st, tabs, arena, head);
+	hipLaunchKernelGGL(k_pcl_icp_normals, dim3(slots_max, P), dim3(256), 0, st, desc, tabs, arena, opt, head);
 	return hipGetLastError();
 }
-hipError_t launch_pcl_icp_normals(hipStream_t st, const PclIcpDesc *desc, uint32_t P, uint32_t slots_max, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *rec)
-{
-	hipLaunchKernelGGL(k_pcl_icp_sort, dim3(blocks_of(slots_max, 256), P), dim3(256), 0, st, desc, arena, rec);
-	hipLaunchKernelGGL(k_pcl_icp_normals, dim3(slots_max, P), dim3(256), 0, st, desc, arena, opt, rec);
-	return hipGetLastError();
-}
-hipError_t launch_pcl_icp_search(hipStream_t st, const PclIcpDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *rec)
+hipError_t launch_pcl_icp_search(hipStream_t st, const PclIcpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t n_src_max, unsigned char *arena, PclIcpOpts opt,
+								 const PclIcpRec *rec, const RegHead *head)
 {
 	const dim3 grid(blocks_of(n_src_max, 256), P), block(256);
-	hipLaunchKernelGGL(k_pcl_icp_search, grid, block, 0, st, desc, arena, opt, rec);
+	hipLaunchKernelGGL(k_pcl_icp_search, grid, block, 0, st, desc, tabs, arena, opt, rec, head);
 	if (opt.reciprocal)
-		hipLaunchKernelGGL(k_pcl_icp_recip, grid, block, 0, st, desc, arena, opt, rec);
+		hipLaunchKernelGGL(k_pcl_icp_recip, grid, block, 0, st, desc, tabs, arena, rec, head);
 	return hipGetLastError();
 }
-hipError_t launch_pcl_icp_accum(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *rec)
+hipError_t launch_pcl_icp_accum(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *rec, const RegHead *head)
 {
 	const dim3 grid(MULLS_NDT_TREE / 256u, P), block(256);
-	hipLaunchKernelGGL(k_pcl_icp_accum, grid, block, 0, st, desc, arena, opt, rec);
+	hipLaunchKernelGGL(k_pcl_icp_accum, grid, block, 0, st, desc, arena, opt, rec, head);
 	if (opt.metric == pcl_icp::POINT2POINT)
-		hipLaunchKernelGGL(k_pcl_icp_cross, grid, block, 0, st, desc, arena, rec);
+		hipLaunchKernelGGL(k_pcl_icp_cross, grid, block, 0, st, desc, arena, rec, head);
 	return hipGetLastError();
 }
-hipError_t launch_pcl_icp_decide(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, double *frames,
-								 uint32_t *running, uint32_t *next)
+hipError_t launch_pcl_icp_decide(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, RegHead *head,
+								 double *frames, uint32_t *running, uint32_t *next)
 {
-	hipLaunchKernelGGL(k_pcl_icp_decide, dim3(P), dim3(256), 0, st, desc, arena, opt, rec, frames, running, next);
+	hipLaunchKernelGGL(k_pcl_icp_decide, dim3(P), dim3(256), 0, st, desc, arena, opt, rec, head, frames, running, next);
 	return hipGetLastError();
 }
-hipError_t launch_pcl_icp_fitness(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec)
+hipError_t launch_pcl_icp_fitness(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, const RegHead *head)
 {
-	hipLaunchKernelGGL(k_pcl_icp_fitness, dim3(P), dim3(256), 0, st, desc, arena, opt, rec);
+	hipLaunchKernelGGL(k_pcl_icp_fitness, dim3(P), dim3(256), 0, st, desc, arena, opt, rec, head);
 	return hipGetLastError();
 }

@@ -1,147 +1,18 @@
 // ndt.cpp — mulls_ndt / mulls_ndt_batch: CRegistration::omp_ndt (cregistration.hpp:945-1021) with what it calls.  Host side: argument checks of every
-// problem before any device work, the identity test of the guess, the score constants, the arena of a sub-batch, the uploads, the lock-step tick loop
-// (k_ndt.hip) and the output pose.  include/mulls_hip.h has the definition this file follows.
+// problem before any device work, the score constants, the arena of a sub-batch, the uploads, the lock-step tick loop (k_ndt.hip) and the results.  What
+// a call and a sub-batch have in common with mulls_gicp's and mulls_pcl_icp's is reg_host.h's.  include/mulls_hip.h has the definition this file follows.
 #include <cfloat>
 #include <cmath>
 
 #include "ctx.h"
-#include "ndt_host.h"
 #include "ndt_launch.h"
-#include "subbatch.h"
-
-// a context's scratch of this entry point: one device arena, one pinned host buffer; grow-only
-struct mulls_ndt_scratch
-{
-	unsigned char *dev = nullptr, *pin = nullptr;
-	size_t dev_cap = 0, pin_cap = 0;
-};
-
-void mulls_ndt_release(mulls_ctx *ctx)
-{
-	if (!ctx->ndt)
-		return;
-	staggered_free(ctx->ndt->dev);
-	if (ctx->ndt->pin)
-		(void)hipHostFree(ctx->ndt->pin);
-	delete ctx->ndt;
-	ctx->ndt = nullptr;
-}
-
-// what mulls_gicp shares with this file (ndt_host.h): the pre-steps of omp_ndt and omp_gicp are the same text upstream
-namespace ndt_host
-{
-bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
-{
-	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * c.stride))
-		return true;
-	hipPointerAttribute_t at;
-	std::memset(&at, 0, sizeof(at));
-	if (hipPointerGetAttributes(&at, c.pts) == hipSuccess)
-		return at.type == hipMemoryTypeDevice;
-	(void)hipGetLastError(); // (an ordinary host pointer: the query reports an error on some runtimes — cleared)
-	return false;
-}
-
-// Eigen's isIdentity(prec) of a column-major 4 x 4
-bool is_identity(const double *G, double prec)
-{
-	for (int c = 0; c < 4; c++)
-		for (int r = 0; r < 4; r++)
-		{
-			const double v = G[r + 4 * c];
-			if (r == c)
-			{
-				if (!(std::fabs(v - 1.0) <= std::min(std::fabs(v), 1.0) * prec))
-					return false;
-			}
-			else if (!(std::fabs(v) <= prec))
-				return false;
-		}
-	return true;
-}
-
-int check_problem(const mulls_ndt_problem &P, std::string &msg)
-{
-	const mulls_cloud *cl[2] = {&P.tgt, &P.src};
-	for (int k = 0; k < 2; k++)
-	{
-		const char *name = k ? "the source" : "the target";
-		if (cl[k]->n == 0)
-		{
-			msg = std::string(name) + " is empty";
-			return MULLS_E_INVALID;
-		}
-		if (!cl[k]->pts)
-		{
-			msg = std::string(name) + " is NULL";
-			return MULLS_E_INVALID;
-		}
-		if (cl[k]->stride < 12 || cl[k]->stride % 4)
-		{
-			msg = std::string(name) + " has a stride below 12 or not a multiple of 4";
-			return MULLS_E_INVALID;
-		}
-		if (cl[k]->n > MULLS_NDT_MAX_POINTS)
-		{
-			msg = std::string(name) + " has more than 2^24 points";
-			return MULLS_E_UNSUPPORTED;
-		}
-	}
-	for (int k = 0; k < 16; k++)
-		if (!std::isfinite(P.init_guess[k]))
-		{
-			msg = "init_guess is not finite";
-			return MULLS_E_INVALID;
-		}
-	for (int k = 0; k < 6; k++)
-		if (!std::isfinite(P.tgt_bound[k]) || !std::isfinite(P.src_bound[k]))
-		{
-			msg = "a bound is not finite";
-			return MULLS_E_INVALID;
-		}
-	return MULLS_OK;
-}
-
-// the coordinates of a cloud, packed to 12 bytes a point, into the arena (a host cloud through the pinned buffer, a device cloud by a strided copy)
-int upload_cloud(mulls_ctx *ctx, const mulls_cloud &c, unsigned char *dst, unsigned char *pinned)
-{
-	hipStream_t st = ctx->stream;
-	if (cloud_on_device(ctx, c))
-		HIPCHK(ctx, hipMemcpy2DAsync(dst, 12, c.pts, c.stride, 12, c.n, hipMemcpyDeviceToDevice, st));
-	else
-	{
-		const unsigned char *src = static_cast<const unsigned char *>(c.pts);
-		for (uint32_t i = 0; i < c.n; i++)
-			std::memcpy(pinned + 12ull * i, src + (size_t)i * c.stride, 12);
-		HIPCHK(ctx, hipMemcpyAsync(dst, pinned, 12ull * c.n, hipMemcpyHostToDevice, st));
-		HIPCHK(ctx, hipStreamSynchronize(st)); // (the pinned buffer is reused)
-	}
-	return MULLS_OK;
-}
-
-// T = Tn * G (column-major 4 x 4, G = NULL: the identity)
-void pose_times_guess(const double *Tn, const double *G, double *T)
-{
-	if (!G)
-	{
-		std::memcpy(T, Tn, 16 * sizeof(double));
-		return;
-	}
-	for (int r = 0; r < 4; r++)
-		for (int c = 0; c < 4; c++)
-			T[r + 4 * c] = ((Tn[r] * G[4 * c] + Tn[r + 4] * G[1 + 4 * c]) + Tn[r + 8] * G[2 + 4 * c]) + Tn[r + 12] * G[3 + 4 * c];
-}
-} // namespace ndt_host
+#include "reg_host.h"
 
 namespace
 {
-using namespace ndt_host;
-constexpr uint32_t MAX_SUB_BATCH = 4096u; // problems of one sub-batch (one grid dimension of the per-point launches)
-
 struct Plan
 {
 	bool apply_guess = false;
-	size_t bytes = 0;
 	NdtDesc D{};
 };
 
@@ -164,14 +35,8 @@ const char *check_params(const mulls_ndt_params &p)
 	return nullptr;
 }
 
-void lay_out(Plan &L, const mulls_ndt_problem &P, size_t &off)
+void lay_out(NdtDesc &D, const mulls_ndt_problem &P, reg_host::Arena &take)
 {
-	auto take = [&](size_t bytes) {
-		const size_t at = off;
-		off += up256(bytes);
-		return (uint64_t)at;
-	};
-	NdtDesc &D = L.D;
 	const size_t ns = P.src.n, nt = P.tgt.n;
 	D.n_src_in = P.src.n, D.n_tgt_in = P.tgt.n;
 	uint32_t ts = MULLS_NDT_SEG, lg = 10;
@@ -184,94 +49,59 @@ void lay_out(Plan &L, const mulls_ndt_problem &P, size_t &off)
 	D.o_leaves = take(sizeof(ndt::Leaf) * nt), D.o_partial = take(8ull * 28u * MULLS_NDT_TREE), D.o_dist = take(4 * ns);
 }
 
-void fill_result_idle(const mulls_ndt_problem &P, const Plan &L, mulls_ndt_result &res)
-{
-	for (int k = 0; k < 16; k++)
-		res.T[k] = L.apply_guess ? P.init_guess[k] : (k % 5 == 0 ? 1.0 : 0.0);
-	res.fitness = DBL_MAX;
-	res.code = -3;
-}
-
 // one sub-batch: problems idx[0 .. B) of the call
 int run_sub_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, std::vector<Plan> &plans, const uint32_t *idx, uint32_t B, const mulls_ndt_params &prm,
 				  const NdtOpts &opt, mulls_ndt_result *results, const std::string &who, bool single)
 {
-	mulls_ndt_scratch &sc = *ctx->ndt;
 	hipStream_t st = ctx->stream;
 	mulls::StreamDrain drain{st};
 	// the first evaluation, then per Newton iteration (at most max_iterations + 2 of them) one trial, the inner steps and the Hessian pass
 	const uint32_t max_ticks = (uint32_t)(prm.max_iterations + 2) * (uint32_t)(prm.max_step_iterations + 2) + 1u;
-	size_t off = 0;
-	const size_t o_desc = off;
-	off += up256(sizeof(NdtDesc) * (size_t)B);
-	const size_t o_rec = off;
-	off += up256(sizeof(NdtRec) * (size_t)B);
-	const size_t o_cnt = off;
-	off += up256(4ull * (max_ticks + 1u));
+	reg_host::Arena take;
+	const size_t desc_bytes = sizeof(NdtDesc) * (size_t)B, rec_bytes = sizeof(NdtRec) * (size_t)B;
+	const size_t o_desc = take(desc_bytes), o_rec = take(rec_bytes), o_cnt = take(8);
 	uint32_t ns_max = 0, nt_max = 0, table_max = 0;
-	size_t pin_need = std::max(up256(sizeof(NdtDesc) * (size_t)B), up256(sizeof(NdtRec) * (size_t)B));
+	std::vector<NdtDesc> descs(B);
 	for (uint32_t k = 0; k < B; k++)
 	{
 		const mulls_ndt_problem &P = problems[idx[k]];
-		Plan &L = plans[idx[k]];
-		lay_out(L, P, off);
-		ns_max = std::max(ns_max, P.src.n), nt_max = std::max(nt_max, P.tgt.n), table_max = std::max(table_max, L.D.table_size);
-		pin_need = std::max<size_t>(pin_need, 12ull * std::max(P.src.n, P.tgt.n));
+		lay_out(plans[idx[k]].D, P, take);
+		descs[k] = plans[idx[k]].D;
+		ns_max = std::max(ns_max, P.src.n), nt_max = std::max(nt_max, P.tgt.n), table_max = std::max(table_max, descs[k].table_size);
 	}
-	if (int rc = grow(ctx, &sc.dev, &sc.dev_cap, off))
+	unsigned char *d, *h;
+	if (int rc = reg_host::reserve(ctx, take.off, std::max<size_t>(up256(std::max(desc_bytes, rec_bytes)), 12ull * std::max(ns_max, nt_max)), &d, &h))
 		return rc;
-	if (int rc = grow_pinned(ctx, &sc.pin, &sc.pin_cap, pin_need, hipHostMallocDefault))
-		return rc;
-	unsigned char *d = sc.dev, *h = sc.pin;
-	// up: the clouds' coordinates, packed (a host cloud through the pinned buffer, a device cloud by a strided copy), and the empty hash tables
 	for (uint32_t k = 0; k < B; k++)
-	{
-		const mulls_ndt_problem &P = problems[idx[k]];
-		const NdtDesc &D = plans[idx[k]].D;
-		if (int rc = ndt_host::upload_cloud(ctx, P.src, d + D.o_src_in, h))
+		if (int rc = reg_host::upload_problem(ctx, problems[idx[k]], descs[k], d, h))
 			return rc;
-		if (int rc = ndt_host::upload_cloud(ctx, P.tgt, d + D.o_tgt_in, h))
-			return rc;
-		HIPCHK(ctx, hipMemsetAsync(d + D.o_keys, 0xff, 4ull * D.table_size, st));
-		HIPCHK(ctx, hipMemsetAsync(d + D.o_count, 0, D.o_leaves - D.o_count, st)); // count, start, fill
-	}
-	{
-		NdtDesc *hd = reinterpret_cast<NdtDesc *>(h);
-		for (uint32_t k = 0; k < B; k++)
-			hd[k] = plans[idx[k]].D;
-		HIPCHK(ctx, hipMemcpyAsync(d + o_desc, h, sizeof(NdtDesc) * (size_t)B, hipMemcpyHostToDevice, st));
-	}
-	HIPCHK(ctx, hipMemsetAsync(d + o_rec, 0, sizeof(NdtRec) * (size_t)B, st));
-	HIPCHK(ctx, hipMemsetAsync(d + o_cnt, 0, 4ull * (max_ticks + 1u), st));
+	if (int rc = reg_host::stage(ctx, h, {{d + o_desc, descs.data(), desc_bytes}}))
+		return rc;
+	HIPCHK(ctx, hipMemsetAsync(d + o_rec, 0, rec_bytes, st));
+	HIPCHK(ctx, hipMemsetAsync(d + o_cnt, 0, 8, st));
 	const NdtDesc *desc = reinterpret_cast<const NdtDesc *>(d + o_desc);
 	NdtRec *rec = reinterpret_cast<NdtRec *>(d + o_rec);
-	uint32_t *cnt = reinterpret_cast<uint32_t *>(d + o_cnt);
 	HIPCHK(ctx, launch_ndt_crop(st, desc, B, d, opt, rec));
-	HIPCHK(ctx, launch_ndt_cells(st, desc, B, nt_max, d, opt, rec));
+	HIPCHK(ctx, launch_ndt_cells(st, desc, B, nt_max, table_max, d, opt, rec));
 	HIPCHK(ctx, launch_ndt_offsets(st, desc, B, d, rec));
 	HIPCHK(ctx, launch_ndt_scatter(st, desc, B, nt_max, d, rec));
 	HIPCHK(ctx, launch_ndt_leaves(st, desc, B, table_max, d, opt, rec));
 	HIPCHK(ctx, launch_ndt_begin(st, B, rec));
 	HIPCHK(ctx, hipStreamSynchronize(st)); // (the descriptors have left the pinned buffer)
-	uint32_t *h_running = reinterpret_cast<uint32_t *>(h);
-	for (uint32_t tick = 0; tick < max_ticks; tick++)
-	{
-		HIPCHK(ctx, launch_ndt_eval(st, desc, B, d, opt, rec));
-		HIPCHK(ctx, launch_ndt_decide(st, desc, B, d, opt, rec, cnt + tick));
-		HIPCHK(ctx, hipMemcpyAsync(h_running, cnt + tick, 4, hipMemcpyDeviceToHost, st));
-		HIPCHK(ctx, hipStreamSynchronize(st));
-		if (*h_running == 0)
-			break;
-	}
+	if (int rc = reg_host::tick_loop(ctx, reinterpret_cast<uint32_t *>(d + o_cnt), h, max_ticks, [&](uint32_t *running, uint32_t *next) -> int {
+			HIPCHK(ctx, launch_ndt_eval(st, desc, B, d, opt, rec));
+			HIPCHK(ctx, launch_ndt_decide(st, desc, B, d, opt, rec, running, next));
+			return MULLS_OK;
+		}))
+		return rc;
 	HIPCHK(ctx, launch_ndt_fitness(st, desc, B, ns_max, d, rec, nullptr));
 	std::vector<NdtRec> recs(B);
-	HIPCHK(ctx, hipMemcpyAsync(h, rec, sizeof(NdtRec) * (size_t)B, hipMemcpyDeviceToHost, st));
-	HIPCHK(ctx, hipStreamSynchronize(st));
-	std::memcpy(recs.data(), h, sizeof(NdtRec) * (size_t)B);
+	if (int rc = reg_host::download(ctx, h, {{rec, recs.data(), rec_bytes}}))
+		return rc;
 	for (uint32_t k = 0; k < B; k++)
 		if (recs[k].status == NDT_ST_NONFINITE || recs[k].status == NDT_ST_GRID)
 		{
-			ctx->err = who + (single ? std::string() : "problem " + std::to_string(idx[k]) + ": ") +
+			ctx->err = reg_host::refusal_prefix(who, single, idx[k]) +
 					   (recs[k].status == NDT_ST_GRID ? "the voxel grid has more than INT32_MAX cells" : "a coordinate is not finite");
 			return recs[k].status == NDT_ST_GRID ? MULLS_E_UNSUPPORTED : MULLS_E_INVALID;
 		}
@@ -284,7 +114,9 @@ int run_sub_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, std::vector
 		res.n_src = R.n_src, res.n_tgt = R.n_tgt;
 		if (R.status == NDT_ST_EMPTY)
 		{
-			fill_result_idle(P, L, res);
+			reg_host::idle_pose(P, L.apply_guess, res.T);
+			res.fitness = DBL_MAX;
+			res.code = -3;
 			continue;
 		}
 		res.n_leaves = R.n_leaves, res.n_leaves_used = R.n_leaves_used;
@@ -293,18 +125,9 @@ int run_sub_batch(mulls_ctx *ctx, const mulls_ndt_problem *problems, std::vector
 		res.trans_probability = R.S.trans_probability;
 		res.fitness = R.fitness;
 		res.code = res.fitness > (double)prm.fitness_score_thre ? -3 : 1;
-		// T = T(p) guess
-		ndt::Frame F;
+		ndt::Frame F; // T = T(p) guess
 		ndt::make_frame(R.S.p, &F);
-		double Tn[16] = {0};
-		for (int r = 0; r < 3; r++)
-		{
-			for (int c = 0; c < 3; c++)
-				Tn[r + 4 * c] = F.R[3 * r + c];
-			Tn[r + 12] = F.t[r];
-		}
-		Tn[15] = 1.0;
-		ndt_host::pose_times_guess(Tn, L.apply_guess ? P.init_guess : nullptr, res.T);
+		reg_host::pose_of(F.R, F.t, P, L.apply_guess, res.T);
 	}
 	return MULLS_OK;
 }
@@ -325,16 +148,8 @@ int ndt_run(mulls_ctx *ctx, const mulls_ndt_problem *problems, uint32_t n_proble
 		ctx->err = who + "the kd-tree search over leaf centroids (use_direct_search = false) is not built";
 		return MULLS_E_UNSUPPORTED;
 	}
-	std::vector<Plan> plans(n_problems);
-	for (uint32_t b = 0; b < n_problems; b++)
-	{
-		std::string msg;
-		if (int rc = check_problem(problems[b], msg))
-		{
-			ctx->err = who + (single ? std::string() : "problem " + std::to_string(b) + ": ") + msg;
-			return rc;
-		}
-	}
+	if (int rc = reg_host::check_problems(ctx, problems, n_problems, who, single))
+		return rc;
 	if (!n_problems)
 		return MULLS_OK;
 	// the score constants (ndt_omp_impl.hpp:86-93), by the host's C library
@@ -345,39 +160,28 @@ int ndt_run(mulls_ctx *ctx, const mulls_ndt_problem *problems, uint32_t n_proble
 	opt.resolution = params->resolution, opt.inv_resolution = 1.0f / params->resolution, opt.min_points = params->min_points_per_voxel;
 	opt.o.step_size = params->step_size, opt.o.transformation_epsilon = params->transformation_epsilon, opt.o.mu = 1.e-4, opt.o.nu = 0.9;
 	opt.o.max_iterations = params->max_iterations, opt.o.max_step_iterations = params->max_step_iterations;
+	std::vector<Plan> plans(n_problems);
+	std::vector<uint64_t> bytes(n_problems);
 	for (uint32_t b = 0; b < n_problems; b++)
 	{
-		const mulls_ndt_problem &P = problems[b];
 		Plan &L = plans[b];
-		NdtDesc &D = L.D;
-		L.apply_guess = !is_identity(P.init_guess, 1e-6);
-		D.apply_guess = L.apply_guess ? 1 : 0, D.crop = params->apply_intersection_filter ? 1 : 0;
-		D.n_offsets = params->search_method == MULLS_NDT_DIRECT1 ? 1 : (params->search_method == MULLS_NDT_DIRECT7 ? 7 : 26);
-		D.offset_first = params->search_method == MULLS_NDT_DIRECT26 ? 7 : 0;
-		for (int r = 0; r < 3; r++)
-		{
-			for (int c = 0; c < 3; c++)
-				D.G[3 * r + c] = P.init_guess[r + 4 * c];
-			D.G[9 + r] = P.init_guess[12 + r];
-		}
-		std::memcpy(D.tgt_bound, P.tgt_bound, sizeof(D.tgt_bound)), std::memcpy(D.src_bound, P.src_bound, sizeof(D.src_bound));
-		size_t off = 0;
-		Plan t = L;
-		lay_out(t, P, off);
-		L.bytes = off;
+		L.apply_guess = reg_host::crop_desc(problems[b], params->apply_intersection_filter != 0, L.D);
+		L.D.n_offsets = params->search_method == MULLS_NDT_DIRECT1 ? 1 : (params->search_method == MULLS_NDT_DIRECT7 ? 7 : 26);
+		L.D.offset_first = params->search_method == MULLS_NDT_DIRECT26 ? 7 : 0;
+		reg_host::Arena dry;
+		NdtDesc t = L.D;
+		lay_out(t, problems[b], dry);
+		bytes[b] = dry.off;
 		mulls_ndt_result &res = results[b];
 		std::memset(&res, 0, sizeof(res));
 		res.gauss_d1 = d1, res.gauss_d2 = d2, res.gauss_d3 = d3;
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	if (!ctx->ndt)
-		ctx->ndt = new mulls_ndt_scratch();
 	const size_t limit = params->scratch_limit_bytes ? (size_t)params->scratch_limit_bytes : (size_t)MULLS_NDT_BATCH_DEFAULT_SCRATCH_BYTES;
-	std::vector<uint32_t> work(n_problems), cuts;
-	std::vector<uint64_t> bytes(n_problems);
+	std::vector<uint32_t> work(n_problems);
 	for (uint32_t b = 0; b < n_problems; b++)
-		work[b] = b, bytes[b] = plans[b].bytes;
-	sub_batch_cuts(bytes.data(), n_problems, limit, MAX_SUB_BATCH, &cuts);
+		work[b] = b;
+	const std::vector<uint32_t> cuts = reg_host::cuts_of(bytes, limit);
 	for (size_t c = 0; c + 1 < cuts.size(); c++)
 		if (int rc = run_sub_batch(ctx, problems, plans, work.data() + cuts[c], cuts[c + 1] - cuts[c], *params, opt, results, who, single))
 			return rc;

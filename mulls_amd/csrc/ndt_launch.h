@@ -49,12 +49,14 @@ struct NdtOpts
 };
 
 hipError_t launch_ndt_crop(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, NdtRec *rec);
-hipError_t launch_ndt_cells(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_tgt_max, unsigned char *arena, NdtOpts opt, NdtRec *rec);
+// the table emptied (every slot below table_max), then the cells
+hipError_t launch_ndt_cells(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_tgt_max, uint32_t table_max, unsigned char *arena, NdtOpts opt, NdtRec *rec);
 hipError_t launch_ndt_offsets(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtRec *rec);
 hipError_t launch_ndt_scatter(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_tgt_max, unsigned char *arena, const NdtRec *rec);
 hipError_t launch_ndt_leaves(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t table_max, unsigned char *arena, NdtOpts opt, NdtRec *rec);
 hipError_t launch_ndt_begin(hipStream_t st, uint32_t P, NdtRec *rec);
 hipError_t launch_ndt_eval(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, const NdtRec *rec);
-hipError_t launch_ndt_decide(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, NdtRec *rec, uint32_t *running);
+// *running: += the problems still running; *next: set to 0 (the word of the tick after)
+hipError_t launch_ndt_decide(hipStream_t st, const NdtDesc *desc, uint32_t P, unsigned char *arena, NdtOpts opt, NdtRec *rec, uint32_t *running, uint32_t *next);
 // frames: NULL (the pose is T(rec[p].S.p)), or 12 doubles a problem: the rotation row-major, the translation (mulls_gicp)
 hipError_t launch_ndt_fitness(hipStream_t st, const NdtDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, NdtRec *rec, const double *frames);

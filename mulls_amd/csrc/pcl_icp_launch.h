@@ -8,13 +8,13 @@
 #include "../../include/mulls_hip.h"
 #include "ndt_launch.h"
 #include "pcl_icp_math.h"
+#include "reg_launch.h"
 
-#define MULLS_PCL_ICP_SEG 1024u // threads of the one-workgroup-per-table scan; a table has a multiple of this many slots
 #define MULLS_PCL_ICP_TILE 256u // target indices of one LDS tile of the normals kernel
 
-// a hash table of occupied cells over one cloud, open addressing with linear probing, and the cloud's points in cell order (gicp_launch.h's GicpTab
-// with a copy of the coordinates in that order).  Three per problem: the cropped target in cells of the correspondence distance, the cropped target in
-// cells of the normals' radius (Point2Plane only) and the moved source in cells of the correspondence distance (reciprocal only; rebuilt every tick).
+// Three cell tables (reg_table.h) per problem, each with a copy of the coordinates in cell order: the cropped target in cells of the correspondence
+// distance, the cropped target in cells of the normals' radius (Point2Plane only) and the moved source in cells of the correspondence distance
+// (reciprocal only; rebuilt every tick, and a moved point outside the cells' range takes no part instead of refusing the problem).
 enum
 {
 	PCL_ICP_TAB_TGT = 0,
@@ -22,22 +22,10 @@ enum
 	PCL_ICP_TAB_SRC = 2,
 	PCL_ICP_TABS = 3
 };
-struct PclIcpTab
-{
-	uint32_t n_cap;		   // the cloud's points before the crop: the bound of every per-point loop; 0: the table is not built
-	uint32_t slots, shift; // a power of two >= max(2 n_cap, MULLS_PCL_ICP_SEG); 64 - log2(slots)
-	uint32_t pad;
-	uint64_t o_pts;					   // packed float xyz
-	uint64_t o_cell, o_list;		   // per point: its slot; the points of every slot
-	uint64_t o_sorted;				   // packed float xyz in the order of o_list
-	uint64_t o_keys;				   // uint64 a slot: the packed cell coordinates, all ones where free
-	uint64_t o_count, o_start, o_fill; // uint32 a slot: points, first entry in list, fill counter (contiguous: cleared together)
-};
 struct PclIcpDesc
 {
-	PclIcpTab tab[PCL_ICP_TABS];
 	uint32_t n_src_cap, n_tgt_cap;
-	uint64_t o_src;		// the cropped source (the crop's output: read only)
+	uint64_t o_src, o_tgt; // the cropped clouds (the crop's output: read only)
 	uint64_t o_mov;		// the moved source, packed float xyz
 	uint64_t o_match;	// int32 a source point: its target point, -1 without a pair
 	uint64_t o_d2;		// float a source point: the pair's squared distance
@@ -56,30 +44,27 @@ struct PclIcpRec
 {
 	pcl_icp::State S;
 	double fitness;
-	uint32_t n[2]; // points after the crop: source, target
-	uint32_t n_fit, range;
-	int32_t status, pad;
+	uint32_t n_fit, pad;
 };
 struct PclIcpOpts
 {
-	double inv_edge[PCL_ICP_TABS]; // of a table's cells
 	double thr2, radius2, fit_range;
 	double transformation_epsilon, euclidean_fitness_epsilon;
 	int32_t metric, reciprocal, max_iter_num, pad;
 };
 
+// The head's status is a PclIcpStatus; the problem's tables are tabs[MULLS_REG_TABS * p + PCL_ICP_TAB_*].
 // the records' start, the moved copy of the cropped source, the source's range check
-hipError_t launch_pcl_icp_begin(hipStream_t st, const PclIcpDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, PclIcpOpts opt, const NdtRec *nrec,
-								PclIcpRec *rec, double *frames);
-// one table of every problem: (the clear, when `clear`,) cells, the scan, the scatter
-hipError_t launch_pcl_icp_table(hipStream_t st, const PclIcpDesc *desc, uint32_t P, int tb, uint32_t n_max, uint32_t slots_max, bool clear, unsigned char *arena,
-								PclIcpOpts opt, PclIcpRec *rec);
+hipError_t launch_pcl_icp_begin(hipStream_t st, const PclIcpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t n_src_max, unsigned char *arena, const NdtRec *nrec,
+								PclIcpRec *rec, RegHead *head, double *frames);
 // the target's normals: every cell's list ascending, then a workgroup per cell
-hipError_t launch_pcl_icp_normals(hipStream_t st, const PclIcpDesc *desc, uint32_t P, uint32_t slots_max, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *rec);
-hipError_t launch_pcl_icp_search(hipStream_t st, const PclIcpDesc *desc, uint32_t P, uint32_t n_src_max, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *rec);
-hipError_t launch_pcl_icp_accum(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *rec);
+hipError_t launch_pcl_icp_normals(hipStream_t st, const PclIcpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t slots_max, unsigned char *arena, PclIcpOpts opt,
+								  const RegHead *head);
+hipError_t launch_pcl_icp_search(hipStream_t st, const PclIcpDesc *desc, const RegTab *tabs, uint32_t P, uint32_t n_src_max, unsigned char *arena, PclIcpOpts opt,
+								 const PclIcpRec *rec, const RegHead *head);
+hipError_t launch_pcl_icp_accum(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, const PclIcpRec *rec, const RegHead *head);
 // *running: += the problems still running; *next: set to 0 (the word of the tick after)
-hipError_t launch_pcl_icp_decide(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, double *frames,
-								 uint32_t *running, uint32_t *next);
+hipError_t launch_pcl_icp_decide(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, RegHead *head,
+								 double *frames, uint32_t *running, uint32_t *next);
 // after launch_ndt_fitness has left the nearest squared distances: the thresholded mean
-hipError_t launch_pcl_icp_fitness(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec);
+hipError_t launch_pcl_icp_fitness(hipStream_t st, const PclIcpDesc *desc, uint32_t P, unsigned char *arena, PclIcpOpts opt, PclIcpRec *rec, const RegHead *head);

@@ -2,7 +2,8 @@
 profiles/gicp.txt.  One 64-beam scan (about 121 600 returns) against the next: one call, and the same call cut after its first iteration (what the
 setup costs); batches of 1, 8 and 64 such pairs against as many single calls; the numpy restatement (tests/gicp_restated.py) on one small case of the
 fixture for scale, with its bits compared; the pose error against the drive's ground truth.  Medians over the repetitions after one warm-up call.
-usage: gpu_gicp.py [--pairs N: distinct pairs, default 8] [--no-restated] [--one: the single call only, for a kernel trace]"""
+usage: gpu_gicp.py [--pairs N: distinct pairs, default 8] [--no-restated] [--one: the single call only, for a kernel trace] [--rows: only the rows
+tools/gpu_ab_single_calls.py reads (tools/reg_rows.py); no file is written]"""
 import json
 import os
 import sys
@@ -15,6 +16,7 @@ sys.path.insert(0, "tools")
 warnings.filterwarnings("ignore")
 import numpy as np
 
+import reg_rows
 from gpu_ndt import bound, raw_drive
 from mulls_amd import abi, lib, synth
 
@@ -42,6 +44,10 @@ def main(argv=None):
         for _ in range(3):
             r = ctx.gicp(**probs[0], params=prm)
         print("one call, three times: %d iterations" % r.iterations)
+        return
+    if "--rows" in argv:
+        reg_rows.rows("mulls_gicp", lambda: ctx.gicp(**probs[0], params=prm), lambda: ctx.gicp(**probs[0], params=abi.gicp_params(max_iterations=1)),
+                      lambda: ctx.gicp_batch([probs[k % n_pairs] for k in range(64)], prm))
         return
     os.makedirs("profiles", exist_ok=True)
     out = open("profiles/gicp.txt", "w")

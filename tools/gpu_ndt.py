@@ -1,7 +1,8 @@
 """NDT registration on the device (mulls_ndt / mulls_ndt_batch): times and accuracy on the synthetic drive of tools/gpu_odometry.py, written to
 profiles/ndt.txt.  One 64-beam scan (about 121 600 returns) against the next: one call; batches of 1, 8 and 64 such pairs against as many single calls;
 the numpy restatement (tests/ndt_restated.py) on the first pair for scale, with its bits compared; the pose error of NDT and of scan-to-scan mm_lls_icp
-against the drive's ground truth on the same pairs.  usage: gpu_ndt.py [--pairs N: distinct pairs, default 8] [--no-restated]"""
+against the drive's ground truth on the same pairs.  usage: gpu_ndt.py [--pairs N: distinct pairs, default 8] [--no-restated] [--rows: only the rows
+tools/gpu_ab_single_calls.py reads (tools/reg_rows.py); no file is written]"""
 import os
 import sys
 import time
@@ -9,9 +10,11 @@ import warnings
 
 sys.path.insert(0, ".")
 sys.path.insert(0, "tests")
+sys.path.insert(0, "tools")
 warnings.filterwarnings("ignore")
 import numpy as np
 
+import reg_rows
 from mulls_amd import abi, lib, synth
 
 
@@ -54,6 +57,16 @@ def timed(fn, reps):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     n_pairs = int(argv[argv.index("--pairs") + 1]) if "--pairs" in argv else 8
+    frames = raw_drive(11, n_pairs + 1)
+    xyz = [np.ascontiguousarray(np.stack([f[0]["x"], f[0]["y"], f[0]["z"]], axis=1), dtype=np.float32) for f in frames]
+    gt = [np.linalg.inv(frames[k][1]) @ frames[k + 1][1] for k in range(n_pairs)]  # frame k + 1 in frame k
+    probs = [dict(tgt=xyz[k], src=xyz[k + 1], tgt_bound=bound(xyz[k]), src_bound=bound(xyz[k + 1]), init_guess=None) for k in range(n_pairs)]
+    ctx = lib.Context(0)
+    prm = abi.ndt_params()
+    if "--rows" in argv:
+        reg_rows.rows("mulls_ndt", lambda: ctx.ndt(**probs[0], params=prm), lambda: ctx.ndt(**probs[0], params=abi.ndt_params(max_iterations=1)),
+                      lambda: ctx.ndt_batch([probs[k % n_pairs] for k in range(64)], prm))
+        return
     os.makedirs("profiles", exist_ok=True)
     out = open("profiles/ndt.txt", "w")
 
@@ -62,12 +75,6 @@ def main(argv=None):
         out.write(s + "\n")
         out.flush()
 
-    frames = raw_drive(11, n_pairs + 1)
-    xyz = [np.ascontiguousarray(np.stack([f[0]["x"], f[0]["y"], f[0]["z"]], axis=1), dtype=np.float32) for f in frames]
-    gt = [np.linalg.inv(frames[k][1]) @ frames[k + 1][1] for k in range(n_pairs)]  # frame k + 1 in frame k
-    probs = [dict(tgt=xyz[k], src=xyz[k + 1], tgt_bound=bound(xyz[k]), src_bound=bound(xyz[k + 1]), init_guess=None) for k in range(n_pairs)]
-    ctx = lib.Context(0)
-    prm = abi.ndt_params()
     say("NDT (mulls_ndt), default parameters (1 m leaves, DIRECT7), scan k + 1 onto scan k of the synthetic drive; %d and %d points in the first pair" % (len(xyz[0]), len(xyz[1])))
     t1, r = timed(lambda: ctx.ndt(**probs[0], params=prm), 5)
     say("one call: %.2f ms (%d iterations, %d evaluations, %d of %d leaves used, %d source points after the crop)" % (t1 * 1e3, r.iterations, r.evaluations, r.n_leaves_used, r.n_leaves, r.n_src))

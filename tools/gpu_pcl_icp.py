@@ -4,7 +4,8 @@ reciprocity, alone, and each cut after its first iteration (what the setup costs
 64 single calls, with the bits compared; the numpy restatement (tests/pcl_icp_restated.py) on the fixture's street case for scale, with its bits
 compared.  Medians over the repetitions after one warm-up call, host clock around synchronised calls.  Per kernel: run `--one` under a kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/gpu_pcl_icp.py --one).
-usage: gpu_pcl_icp.py [--pairs N: distinct pairs, default 8] [--no-restated] [--one: the Point2Plane reciprocal call three times, for a kernel trace]"""
+usage: gpu_pcl_icp.py [--pairs N: distinct pairs, default 8] [--no-restated] [--one: the Point2Plane reciprocal call three times, for a kernel trace]
+[--rows: only the rows tools/gpu_ab_single_calls.py reads (tools/reg_rows.py), for Point2Point and Point2Plane reciprocal; no file is written]"""
 import os
 import sys
 import time
@@ -13,9 +14,11 @@ import warnings
 sys.path.insert(0, ".")
 sys.path.insert(0, "tests")
 sys.path.insert(0, os.path.join("tests", "golden"))
+sys.path.insert(0, "tools")
 warnings.filterwarnings("ignore")
 import numpy as np
 
+import reg_rows
 from mulls_amd import abi, lib
 from ndt_scenes import bound_of, street
 
@@ -46,6 +49,13 @@ def main(argv=None):
         for _ in range(3):
             r = ctx.pcl_icp(**probs[0], params=abi.pcl_icp_params(**combos[3][1]))
         print("one call, three times: %d iterations" % r.iterations)
+        return
+    if "--rows" in argv:
+        for name, over in (combos[0], combos[3]):
+            prm = abi.pcl_icp_params(**over)
+            reg_rows.rows("mulls_pcl_icp " + name, lambda: ctx.pcl_icp(**probs[0], params=prm),
+                          lambda: ctx.pcl_icp(**probs[0], params=abi.pcl_icp_params(max_iter_num=1, **over)),
+                          lambda: ctx.pcl_icp_batch([probs[k % n_pairs] for k in range(64)], prm))
         return
     os.makedirs("profiles", exist_ok=True)
     out = open(os.path.join("profiles", "pcl_icp.txt"), "w")
