@@ -33,47 +33,12 @@
 #include <vector>
 
 #include "mulls_hip.h"
+#include "cregistration_fpfh_hip.hpp" // the library context of a thread, borrow(), and the FPFH / SAC-IA bridge, which needs no type of utility.hpp
 
 namespace lo
 {
 namespace hip
 {
-
-// One library context per host thread (the reference path is single-threaded and stateless, SURVEY §8b "Threading").
-inline mulls_ctx *thread_context(int device = 0)
-{
-	struct Holder
-	{
-		mulls_ctx *ctx = nullptr;
-		~Holder()
-		{
-			if (ctx)
-				mulls_destroy(ctx);
-		}
-	};
-	static thread_local Holder holder;
-	if (!holder.ctx)
-	{
-		const int rc = mulls_create(device, &holder.ctx);
-		if (rc != MULLS_OK)
-			throw std::runtime_error("mulls_create failed (" + std::to_string(rc) + "): no usable gfx950 device; there is no CPU fallback");
-		// constraint_t carries no per-class cloud sizes: stage only the clouds the registration reads (mulls_result.nsrc0 / ntgt0 of the others read 0)
-		(void)mulls_set_option(holder.ctx, MULLS_OPT_LEAN_STAGING, 1.0);
-	}
-	return holder.ctx;
-}
-
-template <typename CloudPtr>
-inline mulls_cloud borrow(const CloudPtr &cloud)
-{
-	typedef typename std::remove_reference<decltype(cloud->points[0])>::type PointT;
-	static_assert(sizeof(PointT) >= MULLS_POINT_BYTES, "expects pcl::PointXYZINormal-compatible records (48 bytes)");
-	mulls_cloud c;
-	c.pts = cloud->points.empty() ? nullptr : static_cast<const void *>(cloud->points.data());
-	c.n = static_cast<uint32_t>(cloud->points.size());
-	c.stride = static_cast<uint32_t>(sizeof(PointT));
-	return c;
-}
 
 // When set (default), block1->tree_{ground,pillar,beam,facade,roof,vertex} are rebuilt on the cropped target clouds
 // like cregistration.hpp:1209-1232 does, because MapManager::map_based_dynamic_close_removal (src/map_manager.cpp:187-243)

@@ -1745,6 +1745,101 @@ int mulls_pcl_icp(mulls_ctx *ctx, const mulls_pcl_icp_problem *problem, const mu
 int mulls_pcl_icp_batch(mulls_ctx *ctx, const mulls_pcl_icp_problem *problems, uint32_t n_problems, const mulls_pcl_icp_params *params,
 						mulls_pcl_icp_result *results);
 
+/* ---- FPFH descriptors and FPFH-based SAC-IA coarse registration: CRegistration::compute_fpfh_feature (cregistration.hpp:351-369) and
+ * coarse_reg_fpfhsac (:372-406): pcl::FPFHEstimationOMP with a radius of 2.0 * search_radius over the records' own normals, and
+ * pcl::SampleConsensusInitialAlignment with setCorrespondenceRandomness(15) and every other setting at its default.  NOTHING WAS COMPARED WITH PCL,
+ * FLANN OR EIGEN THEMSELVES (none is a dependency of this repository, and no PCL source was at hand): the skeleton was read from cregistration.hpp,
+ * and what PCL does inside (FPFHEstimation, computePairFeatures, SampleConsensusInitialAlignment::computeTransformation) was restated FROM MEMORY;
+ * those clauses say so.  The yardstick is a numpy restatement of this text (tests/fpfh_restated.py).  [upstream shape, from memory]: kept as upstream
+ * is remembered to have it; [LIB]: defined here.  Arithmetic is double on the float fields unless a clause says float; every 3-term product is
+ * (u0 v0 + u1 v1) + u2 v2; u x v = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0); atan2 is detmath.h's correctly rounded one; no contraction.
+ *
+ * Inputs  a cloud is host memory or device memory (a map's cloud, or any device pointer), told apart as mulls_scan_prepare does; the stride is a
+ *   multiple of 4 and at least 28: the normals are the records' own, at bytes 16 .. 27, as upstream passes setInputNormals(input_cloud).  Nothing
+ *   estimates normals here.
+ * Neighbourhood [LIB]  r = 2.0f * search_radius.  The neighbourhood of p is every point q of the cloud, p included, with (double)d2(q, p) <= (double)r *
+ *   (double)r, d2 the float ((dx dx + dy dy) + dz dz) — a neighbour at exactly the radius counts; FLANN's rule there is not claimed.  k = its size.
+ *   The search walks the hash table of cubic cells of edge r (1 + 2^-20), cell = floor(x (1 / edge)) in double, and looks into the 27 cells around
+ *   p's own; the margin makes the walk exact for the reason given for mulls_pcl_icp above.  A coordinate outside [-2^20, 2^20) cells:
+ *   MULLS_E_UNSUPPORTED.  A cell that holds more than MULLS_FPFH_MAX_CELL_POINTS points: MULLS_E_UNSUPPORTED as well — the radius is then so large
+ *   against the cloud that the work, quadratic in a cell's points, would hold the device for a long time.
+ * Pair feature [upstream shape: computePairFeatures, from memory]  of p and a neighbour q that is not p itself (another record at p's position is a
+ *   neighbour): dp = q - p, f4 = sqrt(dp . dp); f4 == 0: the pair adds nothing.  a1 = (n_p . dp) / f4, a2 = (n_q . dp) / f4.  PCL swaps the roles when
+ *   acos|a1| > acos|a2|; [LIB] that is |a1| < |a2|.  Swapped: n1 = n_q, n2 = n_p, dp = -dp, f3 = -a2; else n1 = n_p, n2 = n_q, f3 = a1.  v = dp x n1;
+ *   |v| = sqrt(v . v) == 0: the pair adds nothing; v = v / |v|, w = n1 x v, f2 = v . n2, f1 = atan2(w . n2, n1 . n2).
+ * Bins [LIB: in double; upstream's float d_pi_ is not reproduced]  b1 = floor(11 ((f1 + pi) (1 / (2 pi)))), b2 = floor(11 ((f2 + 1) 0.5)), b3 =
+ *   floor(11 ((f3 + 1) 0.5)), each clamped to 0 .. 10; pi = 0x1.921fb54442d18p+1.  A NaN feature: the pair adds nothing.
+ * SPFH [LIB]  the pairs are counted per bin as integers, three times 11 counters a point, so the order of the neighbours cannot matter;
+ *   spfh[b] = (float)(((double)count_b * 100.0) / (double)(k - 1)), all zero when k <= 1.  [upstream shape] the divisor is k - 1 even when pairs
+ *   added nothing.
+ * FPFH [upstream shape: weightPointSPFHSignature, from memory]  over the neighbours q of p with d2(q, p) != 0: acc[b] += (double)spfh_q[b] *
+ *   (1.0 / (double)d2).  [LIB] the accumulators are double and the neighbours come in this order, which depends on the cloud and r alone: the 27
+ *   cells around p's own, cell l = 9 (dz + 1) + 3 (dy + 1) + (dx + 1) for l = 0 .. 26, ascending index inside a cell.  Then per sub-histogram: s =
+ *   the 11 accumulators added in bin order; hist[b] = (float)(acc[b] * (100.0 / s)) when s != 0, else 0.  A result that is not finite is stored as 0.
+ *   hist is n x 33 floats: f1's 11 bins, then f2's, then f3's. */
+#define MULLS_FPFH_MAX_CELL_POINTS 16384u /* points of one cell of edge r (1 + 2^-20) */
+typedef struct mulls_fpfh_params
+{
+	float search_radius; /* 1.0 [LIB: upstream has no default]; the feature radius is 2.0 * search_radius, as upstream */
+	int32_t reserved;
+} mulls_fpfh_params;
+void mulls_fpfh_default_params(mulls_fpfh_params *p);
+/* hist: n x 33 floats, host or device memory; n_neighbours: n, host or device memory, may be NULL.  MULLS_OK, or MULLS_E_INVALID (an empty cloud, a
+ * NULL pointer, a coordinate or normal that is not finite, a bad stride or radius), MULLS_E_UNSUPPORTED (a coordinate beyond 2^20 cells, a cell above MULLS_FPFH_MAX_CELL_POINTS, a cloud
+ * above MULLS_NDT_MAX_POINTS); nothing is then written. */
+int mulls_fpfh(mulls_ctx *ctx, const mulls_cloud *cloud, const mulls_fpfh_params *params, float *hist, uint32_t *n_neighbours);
+
+/* SAC-IA [upstream shape: SampleConsensusInitialAlignment::computeTransformation, from memory]  both clouds' descriptors as above, then
+ * max_iterations hypotheses, each from nr_samples = 3 source points and one similar target descriptor for each.
+ * Draws [LIB; upstream uses rand()]  one std::mt19937(seed); index(n) = eng() % n.  Per iteration, the sample selection first: draw a source index
+ *   index(n_src); reject it when it equals an already chosen one of this iteration or lies closer to one than min_sample_distance (the float
+ *   sqrtf of d2); at the 3 n_src-th rejection in a row min_sample_distance is halved for the rest of the call and the count starts again; repeat
+ *   until nr_samples are chosen.  Then one index(k_eff) per sample, k_eff = min(k_correspondences, n_tgt).  Nothing here depends on a device result:
+ *   the host draws every iteration up front.
+ * Similar features [LIB]  the k_eff nearest target descriptors of a sampled source descriptor by (d2, target index), d2 = the 33 float differences
+ *   squared and added in bin order in float; the drawn rank picks one.  FLANN's order among equals is unknown and not claimed.
+ * Model [LIB]  csrc/ransac_math.h's three-pair fit, as mulls_coarse_reg_ransac's hypotheses use it: a float 3 x 4.
+ * Error of a hypothesis [upstream shape, quirk kept]  over all source points: x' = float(((R_r0 x + R_r1 y) + R_r2 z) + t_r) in double on the float
+ *   model, e = the float d2 to the nearest target point; with thr = max_correspondence_distance, in double: MULLS_SACIA_TRUNCATED e <= thr ? e / thr
+ *   : 1; MULLS_SACIA_HUBER e <= thr ? (0.5 e) e : (0.5 thr) (2 |e| - thr) — a squared distance against an unsquared range, as PCL has it.  The terms are
+ *   summed by MULLS_NDT_TREE's strided-partial rule.  The lowest error wins, the first among equals; [LIB] an error that is NaN (e = inf under an infinite
+ *   range gives inf / inf) comes after every number, NaNs among themselves by index.  UNDER THE DEFAULTS thr IS INFINITE, EVERY
+ *   TERM IS e / inf = 0 AND HYPOTHESIS 0 WINS: upstream never sets a correspondence distance, and that is its call as remembered.  Set a finite
+ *   max_correspondence_distance for a search that selects.
+ * Fitness [upstream getFitnessScore()]  the mean float d2 of the source under T to its nearest target point, by the same summation rule.
+ * A batch entry point is not built. */
+enum mulls_sacia_error
+{
+	MULLS_SACIA_TRUNCATED = 0,
+	MULLS_SACIA_HUBER = 1
+};
+typedef struct mulls_fpfhsac_params
+{
+	float search_radius;			   /* 1.0 [LIB]; as mulls_fpfh */
+	int32_t nr_samples;				   /* 3 [PCL, from memory]; only 3 is built, anything else MULLS_E_UNSUPPORTED */
+	int32_t k_correspondences;		   /* 15 [upstream: setCorrespondenceRandomness(15)]; 1 .. 64 */
+	int32_t max_iterations;			   /* 10 [pcl::Registration's default, from memory]; at most 65536 */
+	float min_sample_distance;		   /* 0 [PCL, from memory] */
+	float max_correspondence_distance; /* +inf: upstream never sets it; see the quirk above.  Above 0 */
+	int32_t error_function;			   /* enum mulls_sacia_error; MULLS_SACIA_TRUNCATED [PCL's default, from memory] */
+	uint32_t seed;					   /* 0 [LIB] upstream uses rand() */
+} mulls_fpfhsac_params;
+typedef struct mulls_fpfhsac_result
+{
+	int32_t best_iteration, iterations;
+	uint32_t n_src, n_tgt;
+	double best_error, fitness;
+	double T[16]; /* column-major; source to target */
+} mulls_fpfhsac_result;
+void mulls_fpfhsac_default_params(mulls_fpfhsac_params *p);
+/* MULLS_OK, or MULLS_E_INVALID (n_src < 3, n_tgt = 0, a NULL pointer, a coordinate, normal or parameter that is not finite or out of its range, a
+ * bad stride), MULLS_E_UNSUPPORTED (nr_samples other than 3, max_iterations above 65536, a coordinate beyond 2^20 cells, a cell above
+ * MULLS_FPFH_MAX_CELL_POINTS, a cloud above MULLS_NDT_MAX_POINTS); the result is then not written.  Each cloud goes up once, as two packed copies
+ * (coordinates, normals); both descriptor sets come from one launch set, during which the host draws the samples of a host source; the clouds'
+ * refusals are read back before anything else is launched; then the similar features of all samples, all models, all hypotheses' errors, the
+ * winner and its fitness, and one download of the result. */
+int mulls_coarse_reg_fpfhsac(mulls_ctx *ctx, const mulls_cloud *tgt, const mulls_cloud *src, const mulls_fpfhsac_params *params, mulls_fpfhsac_result *result);
+
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 
 /* batch_transform_feature_points (cregistration.hpp:1685-1696): in place on a host cloud via the device kernel */

@@ -636,6 +636,50 @@ def pcl_icp_params(**kw):
     return p
 
 
+class FpfhParams(C.Structure):
+    """mulls_fpfh_params"""
+
+    _fields_ = [("search_radius", C.c_float), ("reserved", C.c_int32)]
+
+
+class FpfhSacParams(C.Structure):
+    """mulls_fpfhsac_params"""
+
+    _fields_ = [("search_radius", C.c_float), ("nr_samples", C.c_int32), ("k_correspondences", C.c_int32), ("max_iterations", C.c_int32),
+                ("min_sample_distance", C.c_float), ("max_correspondence_distance", C.c_float), ("error_function", C.c_int32), ("seed", C.c_uint32)]
+
+
+class FpfhSacResult(C.Structure):
+    """mulls_fpfhsac_result"""
+
+    _fields_ = [("best_iteration", C.c_int32), ("iterations", C.c_int32), ("n_src", C.c_uint32), ("n_tgt", C.c_uint32), ("best_error", C.c_double),
+                ("fitness", C.c_double), ("T", C.c_double * 16)]
+
+
+SACIA_TRUNCATED, SACIA_HUBER = range(2)  # enum mulls_sacia_error
+FPFH_DIMS = 33
+FPFH_MAX_CELL_POINTS = 16384  # MULLS_FPFH_MAX_CELL_POINTS
+FPFH_HYP_CHUNK = 1024  # MULLS_FPFH_HYP_CHUNK (csrc/fpfh_launch.h): hypotheses whose nearest-target distances are held at a time
+
+
+def fpfh_params(search_radius=1.0):
+    """mulls_fpfh_default_params' values, then the argument"""
+    p = FpfhParams()
+    p.search_radius = search_radius
+    return p
+
+
+def fpfhsac_params(**kw):
+    """mulls_fpfhsac_default_params' values, then the keyword arguments"""
+    p = FpfhSacParams()
+    p.search_radius, p.nr_samples, p.k_correspondences, p.max_iterations = 1.0, 3, 15, 10
+    p.min_sample_distance, p.max_correspondence_distance, p.error_function, p.seed = 0.0, float("inf"), SACIA_TRUNCATED, 0
+    for k, v in kw.items():
+        getattr(p, k)
+        setattr(p, k, v)
+    return p
+
+
 class NmsParams(C.Structure):
     """mulls_nms_params: non_max_suppress' radius (cfilter.hpp:1183) and which path runs it"""
 

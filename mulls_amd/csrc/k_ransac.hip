@@ -43,27 +43,8 @@ __device__ __forceinline__ RansacModel sample_model(const float4 *src, const flo
 		s[k][0] = a.x, s[k][1] = a.y, s[k][2] = a.z;
 		t[k][0] = b.x, t[k][1] = b.y, t[k][2] = b.z;
 	}
-	float cs[3], ct[3];
-#pragma unroll
-	for (int a = 0; a < 3; a++)
-	{
-		cs[a] = ((s[0][a] + s[1][a]) + s[2][a]) / 3.0f;
-		ct[a] = ((t[0][a] + t[1][a]) + t[2][a]) / 3.0f;
-	}
-	double H[9], csd[3], ctd[3];
-#pragma unroll
-	for (int a = 0; a < 3; a++)
-	{
-#pragma unroll
-		for (int b = 0; b < 3; b++)
-		{
-			const float h0 = (s[0][a] - cs[a]) * (t[0][b] - ct[b]), h1 = (s[1][a] - cs[a]) * (t[1][b] - ct[b]), h2 = (s[2][a] - cs[a]) * (t[2][b] - ct[b]);
-			H[a * 3 + b] = (double)((h0 + h1) + h2);
-		}
-		csd[a] = (double)cs[a], ctd[a] = (double)ct[a];
-	}
 	RansacModel M;
-	horn_fit(H, csd, ctd, M.m);
+	fit_three_pairs(s, t, M.m);
 	return M;
 }
 

@@ -1,5 +1,5 @@
 // ransac_math.h — the rigid-transform estimator of the RANSAC coarse registration (include/mulls_hip.h), one text for the device
-// kernels (k_ransac.hip) and for a CPU build (tests/ransac_harness.cpp, which tests/test_ransac.py holds against the numpy restatement bit for bit).
+// kernels (k_ransac.hip; k_fpfh.hip's SAC-IA hypotheses call fit_three_pairs as well) and for a CPU build (tests/ransac_harness.cpp, which tests/test_ransac.py holds against the numpy restatement bit for bit).
 #pragma once
 #include <math.h>
 
@@ -98,4 +98,29 @@ RANSAC_UNROLL
 		out[r * 4 + 2] = (float)R[r][2];
 		out[r * 4 + 3] = (float)tr;
 	}
+}
+
+// The rigid transform of three pairs s[k] -> t[k]: the centroids and the demeaned cross-covariance in float, then horn_fit.  out: 3 x 4 row-major.
+RANSAC_HD inline void fit_three_pairs(const float (*s)[3], const float (*t)[3], float *out)
+{
+	float cs[3], ct[3];
+RANSAC_UNROLL
+	for (int a = 0; a < 3; a++)
+	{
+		cs[a] = ((s[0][a] + s[1][a]) + s[2][a]) / 3.0f;
+		ct[a] = ((t[0][a] + t[1][a]) + t[2][a]) / 3.0f;
+	}
+	double H[9], csd[3], ctd[3];
+RANSAC_UNROLL
+	for (int a = 0; a < 3; a++)
+	{
+RANSAC_UNROLL
+		for (int b = 0; b < 3; b++)
+		{
+			const float h0 = (s[0][a] - cs[a]) * (t[0][b] - ct[b]), h1 = (s[1][a] - cs[a]) * (t[1][b] - ct[b]), h2 = (s[2][a] - cs[a]) * (t[2][b] - ct[b]);
+			H[a * 3 + b] = (double)((h0 + h1) + h2);
+		}
+		csd[a] = (double)cs[a], ctd[a] = (double)ct[a];
+	}
+	horn_fit(H, csd, ctd, out);
 }

@@ -1,4 +1,4 @@
-// reg_device.h — what the registrations' kernels (k_ndt.hip, k_gicp.hip, k_pcl_icp.hip, k_reg_table.hip) share, device only: the arena accessor, the
+// reg_device.h — what the registrations' kernels (k_ndt.hip, k_gicp.hip, k_pcl_icp.hip, k_fpfh.hip, k_reg_table.hip) share, device only: the arena accessor, the
 // cell table's probe, claim and 27-cell visitor (reg_table.h), the shell sort of a slot's list, the scan of a table's counts, and the sums: the halving
 // tree over MULLS_NDT_TREE strided partials and the count of hits.  Every translation unit expands the same text, so a sum has the same bits in all.
 #pragma once

@@ -24,18 +24,6 @@ void mulls_reg_release(mulls_ctx *ctx)
 
 namespace
 {
-bool cloud_on_device(mulls_ctx *ctx, const mulls_cloud &c)
-{
-	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * c.stride))
-		return true;
-	hipPointerAttribute_t at;
-	std::memset(&at, 0, sizeof(at));
-	if (hipPointerGetAttributes(&at, c.pts) == hipSuccess)
-		return at.type == hipMemoryTypeDevice;
-	(void)hipGetLastError(); // (an ordinary host pointer: the query reports an error on some runtimes — cleared)
-	return false;
-}
-
 // Eigen's isIdentity(prec) of a column-major 4 x 4
 bool is_identity(const double *G, double prec)
 {
@@ -96,15 +84,30 @@ int check_problem(const mulls_ndt_problem &P, std::string &msg)
 	return MULLS_OK;
 }
 
-// the coordinates of a cloud, packed to 12 bytes a point, into the arena
-int upload_cloud(mulls_ctx *ctx, const mulls_cloud &c, unsigned char *dst, unsigned char *pinned)
+} // namespace
+
+namespace reg_host
+{
+bool on_device(mulls_ctx *ctx, const mulls_cloud &c)
+{
+	if (mulls_is_map_memory(ctx, c.pts, (size_t)c.n * c.stride))
+		return true;
+	hipPointerAttribute_t at;
+	std::memset(&at, 0, sizeof(at));
+	if (hipPointerGetAttributes(&at, c.pts) == hipSuccess)
+		return at.type == hipMemoryTypeDevice;
+	(void)hipGetLastError(); // (an ordinary host pointer: the query reports an error on some runtimes — cleared)
+	return false;
+}
+
+int upload_xyz(mulls_ctx *ctx, const mulls_cloud &c, uint32_t offset, unsigned char *dst, unsigned char *pinned)
 {
 	hipStream_t st = ctx->stream;
-	if (cloud_on_device(ctx, c))
-		HIPCHK(ctx, hipMemcpy2DAsync(dst, 12, c.pts, c.stride, 12, c.n, hipMemcpyDeviceToDevice, st));
+	if (on_device(ctx, c))
+		HIPCHK(ctx, hipMemcpy2DAsync(dst, 12, static_cast<const unsigned char *>(c.pts) + offset, c.stride, 12, c.n, hipMemcpyDeviceToDevice, st));
 	else
 	{
-		const unsigned char *src = static_cast<const unsigned char *>(c.pts);
+		const unsigned char *src = static_cast<const unsigned char *>(c.pts) + offset;
 		for (uint32_t i = 0; i < c.n; i++)
 			std::memcpy(pinned + 12ull * i, src + (size_t)i * c.stride, 12);
 		HIPCHK(ctx, hipMemcpyAsync(dst, pinned, 12ull * c.n, hipMemcpyHostToDevice, st));
@@ -112,10 +115,6 @@ int upload_cloud(mulls_ctx *ctx, const mulls_cloud &c, unsigned char *dst, unsig
 	}
 	return MULLS_OK;
 }
-} // namespace
-
-namespace reg_host
-{
 std::string refusal_prefix(const std::string &who, bool single, uint32_t index)
 {
 	return who + (single ? std::string() : "problem " + std::to_string(index) + ": ");
@@ -171,9 +170,9 @@ int reserve(mulls_ctx *ctx, size_t dev_bytes, size_t pinned_bytes, unsigned char
 
 int upload_problem(mulls_ctx *ctx, const mulls_ndt_problem &P, const NdtDesc &N, unsigned char *dev, unsigned char *pinned)
 {
-	if (int rc = upload_cloud(ctx, P.src, dev + N.o_src_in, pinned))
+	if (int rc = upload_xyz(ctx, P.src, 0, dev + N.o_src_in, pinned))
 		return rc;
-	return upload_cloud(ctx, P.tgt, dev + N.o_tgt_in, pinned);
+	return upload_xyz(ctx, P.tgt, 0, dev + N.o_tgt_in, pinned);
 }
 
 int stage(mulls_ctx *ctx, unsigned char *pinned, std::initializer_list<Block> blocks)

@@ -1,4 +1,4 @@
-// reg_host.h — the host part that mulls_ndt, mulls_gicp and mulls_pcl_icp have in common (reg_host.cpp): the pre-steps of omp_ndt, omp_gicp and pcl_icp
+// reg_host.h — the host part that mulls_ndt, mulls_gicp and mulls_pcl_icp have in common (reg_host.cpp; fpfh.cpp uses its arena, uploads and staging): the pre-steps of omp_ndt, omp_gicp and pcl_icp
 // are the same text upstream, and a sub-batch of any of them is the same sequence around its own launches.  Plain functions that ndt.cpp, gicp.cpp and
 // pcl_icp.cpp call in the order they need: the checks of a call, a problem's crop descriptor, the sub-batch's memory, the uploads, the staging of
 // descriptors, the tick loop, the download of records, and the output pose.
@@ -42,6 +42,10 @@ std::vector<uint32_t> cuts_of(const std::vector<uint64_t> &bytes, uint64_t limit
 int reserve(mulls_ctx *ctx, size_t dev_bytes, size_t pinned_bytes, unsigned char **dev, unsigned char **pinned);
 // a problem's two clouds, packed to 12 bytes a point, to N.o_src_in and N.o_tgt_in (a host cloud through the pinned buffer, a device cloud by a strided copy)
 int upload_problem(mulls_ctx *ctx, const mulls_ndt_problem &P, const NdtDesc &N, unsigned char *dev, unsigned char *pinned);
+// is a cloud's memory the device's (a map's, or what the runtime calls device memory)?
+bool on_device(mulls_ctx *ctx, const mulls_cloud &c);
+// the three floats at byte `offset` of every record (0: the coordinates, 16: the normal), packed to 12 bytes a point, to dst
+int upload_xyz(mulls_ctx *ctx, const mulls_cloud &c, uint32_t offset, unsigned char *dst, unsigned char *pinned);
 // blocks between the host and the arena through the pinned buffer, each at the next multiple of 256 bytes of it.  stage() queues the copies up: the
 // pinned buffer is free again after the next wait on the stream.  download() waits, then fills the hosts' blocks.
 struct Block

@@ -1,4 +1,4 @@
-// reg_table.h — the cell table of the registrations (mulls_gicp, mulls_pcl_icp): a hash table of occupied cells over one cloud, open addressing with
+// reg_table.h — the cell table of the registrations (mulls_gicp, mulls_pcl_icp; mulls_fpfh, where a cloud stands for a problem): a hash table of occupied cells over one cloud, open addressing with
 // linear probing over 64-bit packed cell coordinates, and the cloud's points in cell order.  The descriptor (written by the host, read by the kernels of
 // k_reg_table.hip and by every kernel that walks a table), the per-problem head the table kernels and the methods' own kernels share, and the one
 // function that lays a table out.  Host and device, without the HIP runtime, so that a harness under tests/ can hold the layout on the CPU.

@@ -137,6 +137,12 @@ def load():
     lib.mulls_pcl_icp_default_params.restype = None
     lib.mulls_pcl_icp.argtypes = [vp, C.POINTER(abi.PclIcpProblem), C.POINTER(abi.PclIcpParams), C.POINTER(abi.PclIcpResult)]
     lib.mulls_pcl_icp_batch.argtypes = [vp, C.POINTER(abi.PclIcpProblem), C.c_uint32, C.POINTER(abi.PclIcpParams), C.POINTER(abi.PclIcpResult)]
+    lib.mulls_fpfh_default_params.argtypes = [C.POINTER(abi.FpfhParams)]
+    lib.mulls_fpfh_default_params.restype = None
+    lib.mulls_fpfh.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.FpfhParams), vp, vp]
+    lib.mulls_fpfhsac_default_params.argtypes = [C.POINTER(abi.FpfhSacParams)]
+    lib.mulls_fpfhsac_default_params.restype = None
+    lib.mulls_coarse_reg_fpfhsac.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.FpfhSacParams), C.POINTER(abi.FpfhSacResult)]
     lib.mulls_sor_default_params.argtypes = [C.POINTER(abi.SorParams)]
     lib.mulls_sor_default_params.restype = None
     lib.mulls_sor_filter.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.SorParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
@@ -196,6 +202,7 @@ EXPORTS = [
     "mulls_pgo_default_params", "mulls_pgo_optimize", "mulls_pgo_optimize_batch",
     "mulls_ndt_default_params", "mulls_ndt", "mulls_ndt_batch", "mulls_gicp_default_params", "mulls_gicp", "mulls_gicp_batch",
     "mulls_pcl_icp_default_params", "mulls_pcl_icp", "mulls_pcl_icp_batch",
+    "mulls_fpfh_default_params", "mulls_fpfh", "mulls_fpfhsac_default_params", "mulls_coarse_reg_fpfhsac",
     "mulls_nms_default_params", "mulls_non_max_suppress",
     "mulls_scan_prep_default_params", "mulls_scan_prepare",
     "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
@@ -864,6 +871,39 @@ class Context:
         if rc != 0:
             raise MullsError("mulls_pcl_icp_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
         return [abi.PclIcpResult.from_buffer_copy(res[b]) for b in range(B)]
+
+    # --- FPFH descriptors and SAC-IA coarse registration -----------------------------------------------------------------
+    @staticmethod
+    def _normal_cloud(k, keep):
+        """a cloud with normals: a POINT_DTYPE array, a (pts, normals) pair of (n, 3) arrays, or an abi.Cloud (host or device memory, stride >= 28)"""
+        if isinstance(k, abi.Cloud):
+            return k
+        raw = abi.make_points(k[0], k[1]) if isinstance(k, tuple) else np.ascontiguousarray(abi.as_points(k))
+        keep.append(raw)
+        return abi.as_cloud(raw)
+
+    def fpfh(self, cloud, params=None):
+        """CRegistration::compute_fpfh_feature (mulls_fpfh).  cloud: as _normal_cloud takes it.  Returns (hist (n, 33) float32, n_neighbours (n,) uint32)."""
+        keep = []
+        c = self._normal_cloud(cloud, keep)
+        p = params if params is not None else abi.fpfh_params()
+        hist, k = np.zeros((max(c.n, 1), abi.FPFH_DIMS), np.float32), np.zeros(max(c.n, 1), np.uint32)
+        rc = self.lib.mulls_fpfh(self.h, C.byref(c), C.byref(p), hist.ctypes.data, k.ctypes.data)
+        if rc != 0:
+            raise MullsError("mulls_fpfh failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return hist[: c.n], k[: c.n]
+
+    def coarse_reg_fpfhsac(self, tgt, src, params=None):
+        """CRegistration::coarse_reg_fpfhsac (mulls_coarse_reg_fpfhsac).  tgt, src: as _normal_cloud takes them.  Returns the mulls_fpfhsac_result;
+        np.array(res.T).reshape(4, 4).T is the pose, source to target."""
+        keep = []
+        ct, cs = self._normal_cloud(tgt, keep), self._normal_cloud(src, keep)
+        p = params if params is not None else abi.fpfhsac_params()
+        res = abi.FpfhSacResult()
+        rc = self.lib.mulls_coarse_reg_fpfhsac(self.h, C.byref(ct), C.byref(cs), C.byref(p), C.byref(res))
+        if rc != 0:
+            raise MullsError("mulls_coarse_reg_fpfhsac failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return res
 
     # --- pose graph optimisation --------------------------------------------------------------------------------------
     def pgo_optimize(self, poses, fixed, stable, edges, params=None):
