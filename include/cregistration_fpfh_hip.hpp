@@ -122,6 +122,86 @@ inline double coarse_reg_fpfhsac(const typename pcl::PointCloud<PointT>::Ptr &so
 	return R.fitness;
 }
 
+// The two calls for the candidate edges of one loop-closure event (test/mulls_slam.cpp:517-596 tries one query submap against several candidates): every
+// cloud's descriptors, and every (source, target) pair's SAC-IA, in one device call each (mulls_compute_fpfh_batch, mulls_coarse_reg_fpfhsac_batch).  Each
+// cloud and each pair gets the bits of its single bridge call.  A cloud pointer given several times, the query submap as every pair's target for instance,
+// is one cloud to the library: staged once, its descriptors computed once.
+template <typename PointT, typename FpfhPtr>
+inline void compute_fpfh_feature_batch(const std::vector<typename pcl::PointCloud<PointT>::Ptr> &input_clouds, std::vector<FpfhPtr> &clouds_fpfh, float search_radius)
+{
+	if (clouds_fpfh.size() != input_clouds.size())
+		throw std::runtime_error("compute_fpfh_feature_batch: as many descriptor clouds as input clouds are expected");
+	std::vector<mulls_cloud> clouds;
+	std::vector<size_t> which;
+	for (size_t c = 0; c < input_clouds.size(); c++)
+	{
+		const mulls_cloud cl = borrow(input_clouds[c]);
+		clouds_fpfh[c]->points.resize(cl.n);
+		if (cl.n) // (the single bridge call returns an empty cloud's empty descriptors without a device call)
+			clouds.push_back(cl), which.push_back(c);
+	}
+	if (clouds.empty())
+		return;
+	static_assert(sizeof(clouds_fpfh[0]->points[0].histogram) == 33 * sizeof(float), "expects pcl::FPFHSignature33-compatible records");
+	mulls_ctx *ctx = thread_context();
+	mulls_fpfh_params P;
+	mulls_fpfh_default_params(&P);
+	P.search_radius = search_radius;
+	std::vector<std::vector<float>> hist(clouds.size());
+	std::vector<float *> out(clouds.size());
+	for (size_t k = 0; k < clouds.size(); k++)
+		hist[k].resize((size_t)33 * clouds[k].n), out[k] = hist[k].data();
+	const int rc = mulls_compute_fpfh_batch(ctx, clouds.data(), (uint32_t)clouds.size(), &P, out.data(), nullptr, 0);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_compute_fpfh_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (size_t k = 0; k < clouds.size(); k++)
+		for (uint32_t i = 0; i < clouds[k].n; i++)
+			std::memcpy(clouds_fpfh[which[k]]->points[i].histogram, &hist[k][(size_t)33 * i], 33 * sizeof(float));
+}
+
+// Pair b is (source_clouds[b], target_clouds[b]); traned_sources[b] and transformationS2T[b] receive what the single bridge call gives them; the
+// fitness scores are returned.  fpfhsac_params() applies as it does for the single bridge call: one set of parameters for the whole call.
+template <typename PointT>
+inline std::vector<double> coarse_reg_fpfhsac_batch(const std::vector<typename pcl::PointCloud<PointT>::Ptr> &source_clouds,
+													 const std::vector<typename pcl::PointCloud<PointT>::Ptr> &target_clouds,
+													 std::vector<typename pcl::PointCloud<PointT>::Ptr> &traned_sources, std::vector<Eigen::Matrix4d> &transformationS2T,
+													 float search_radius)
+{
+	const size_t B = source_clouds.size();
+	if (target_clouds.size() != B || traned_sources.size() != B)
+		throw std::runtime_error("coarse_reg_fpfhsac_batch: as many targets and moved sources as sources are expected");
+	transformationS2T.resize(B);
+	std::vector<double> fitness(B, 0.0);
+	if (!B)
+		return fitness;
+	mulls_ctx *ctx = thread_context();
+	mulls_fpfhsac_params P = fpfhsac_params();
+	P.search_radius = search_radius;
+	std::vector<mulls_fpfhsac_problem> problems(B);
+	for (size_t b = 0; b < B; b++)
+		problems[b].src = borrow(source_clouds[b]), problems[b].tgt = borrow(target_clouds[b]);
+	std::vector<mulls_fpfhsac_result> R(B);
+	const int rc = mulls_coarse_reg_fpfhsac_batch(ctx, problems.data(), (uint32_t)B, &P, 0, R.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_coarse_reg_fpfhsac_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (size_t b = 0; b < B; b++)
+	{
+		const double *T = R[b].T;
+		for (int k = 0; k < 16; k++)
+			transformationS2T[b].data()[k] = T[k];
+		traned_sources[b]->points = source_clouds[b]->points;
+		for (auto &p : traned_sources[b]->points)
+		{
+			const double x = p.x, y = p.y, z = p.z;
+			p.x = (float)(((T[0] * x + T[4] * y) + T[8] * z) + T[12]);
+			p.y = (float)(((T[1] * x + T[5] * y) + T[9] * z) + T[13]);
+			p.z = (float)(((T[2] * x + T[6] * y) + T[10] * z) + T[14]);
+		}
+		fitness[b] = R[b].fitness;
+	}
+	return fitness;
+}
+
 } // namespace hip
 } // namespace lo
 

@@ -1807,7 +1807,7 @@ int mulls_fpfh(mulls_ctx *ctx, const mulls_cloud *cloud, const mulls_fpfh_params
  *   TERM IS e / inf = 0 AND HYPOTHESIS 0 WINS: upstream never sets a correspondence distance, and that is its call as remembered.  Set a finite
  *   max_correspondence_distance for a search that selects.
  * Fitness [upstream getFitnessScore()]  the mean float d2 of the source under T to its nearest target point, by the same summation rule.
- * A batch entry point is not built. */
+ * Many clouds and many problems per call: mulls_compute_fpfh_batch and mulls_coarse_reg_fpfhsac_batch, below the single calls. */
 enum mulls_sacia_error
 {
 	MULLS_SACIA_TRUNCATED = 0,
@@ -1839,6 +1839,51 @@ void mulls_fpfhsac_default_params(mulls_fpfhsac_params *p);
  * refusals are read back before anything else is launched; then the similar features of all samples, all models, all hypotheses' errors, the
  * winner and its fitness, and one download of the result. */
 int mulls_coarse_reg_fpfhsac(mulls_ctx *ctx, const mulls_cloud *tgt, const mulls_cloud *src, const mulls_fpfhsac_params *params, mulls_fpfhsac_result *result);
+
+/* ---- many FPFH clouds and many SAC-IA problems per call: the candidate edges of one loop-closure event (test/mulls_slam.cpp:517-596 tries one query
+ * submap against several candidates) by the way that needs nothing but points and normals, in front of mulls_icp_batch.
+ * results[b] is THE BYTES THE SINGLE CALL RETURNS for (problems[b].tgt, problems[b].src, params) on the same context, and every cloud of the descriptor
+ * batch gets the bits of its single descriptor call.  No arithmetic, order of summation, tie rule or draw is redefined; there is one params for the
+ * whole call, seed included.  The device steps run for all problems of a sub-batch per launch: one launch set for the descriptors of all its distinct
+ * clouds, one launch for the similar features of all samples (a wave per sample, which finds its problem in the sub-batch's table), one for all models,
+ * then the hypotheses of all problems as one flat list in problem order, cut into consecutive stretches of at most MULLS_FPFH_HYP_CHUNK (1 024) slots
+ * whose nearest-target distances fit the distance pool (a stretch may begin and end inside a problem; three launches a stretch), one pick launch with a
+ * workgroup per problem, one nearest-target pass over the winners, and one download (addendum).  The draws run per problem on
+ * the host, the problems side by side, while the descriptors run; a device source's packed coordinates come back with the heads and its draws follow.
+ *   shared clouds  a cloud named by several problems of a sub-batch, as a source, a target or both (or by several entries of clouds[]), is staged once
+ *                 and its descriptors are computed once per sub-batch.  Identity is (pts, n, stride), for host and device clouds alike.  No result
+ *                 depends on it.
+ *   whole call    checked before any device work and before anything is written: a NULL it needs, a problem or cloud the single call would refuse (by
+ *                 the single call's own checks: n_src < 3, an empty cloud, a bad stride, a cloud above MULLS_NDT_MAX_POINTS, a refused parameter) make
+ *                 the call return the single call's code and name the first such index in mulls_last_error ("problem 3: the source ...", "cloud 2
+ *                 ..."; a refused parameter refuses problem 0).
+ *   device refusals  a coordinate or normal that is not finite, a coordinate beyond 2^20 cells, a cell above MULLS_FPFH_MAX_CELL_POINTS: read from the
+ *                 sub-batch's heads before anything else is launched for it; the call returns the single call's code and names the first problem (or
+ *                 cloud) that uses the refused cloud.  NO OUTPUT OF THE CALL IS WRITTEN, earlier sub-batches' included: results are kept on the host
+ *                 and copied out after the last sub-batch succeeded.  The descriptor batch, whose outputs may be device memory: when the limit
+ *                 cuts it into several sub-batches, a first pass runs every sub-batch and reads its heads only, and when all are good a second pass
+ *                 computes them again and copies out; a call of one sub-batch reads its heads and copies out of the arena.
+ *   scratch_limit_bytes  bounds the device arena of a sub-batch.  Counted per cloud of n points: cloud(n) = 4 up256(12 n) + 2 up256(132 n) +
+ *                 3 up256(4 n) + 20 slots(n) + 1024 (coordinates and normals as given and in cell order, SPFH and FPFH, neighbourhood sizes, slots and
+ *                 lists, the cell table of slots(n) = the power of two >= max(2 n, 1024), its table entries; up256 rounds up to 256 bytes).  Per
+ *                 problem: cloud(n_src) + cloud(n_tgt) + 140 max_iterations + 1280 + 2 up256(4 n_src) + 4096 (samples, ranks, correspondences,
+ *                 frames and errors; the winner's distances and one hypothesis of the distance pool; its table entries), and 2 MiB per sub-batch for
+ *                 the slots of a stretch.  A shared cloud is counted for every problem that names it, so the arena is never larger than counted.  The
+ *                 batch is cut into consecutive sub-batches that fit, of at most MULLS_FPFH_HYP_CHUNK problems (4 096 clouds); a problem larger than
+ *                 the limit runs alone.  The distance pool (4 n_src bytes per hypothesis) is what the limit leaves, at most the 256 MB the single call
+ *                 allows itself and what all hypotheses need, and at least one hypothesis of the sub-batch's largest source.
+ *                 0: MULLS_FPFHSAC_BATCH_DEFAULT_SCRATCH_BYTES, a value chosen without a measurement.
+ * n_problems = 0, n_clouds = 0: MULLS_OK, nothing is touched. */
+#define MULLS_FPFHSAC_BATCH_DEFAULT_SCRATCH_BYTES (1024ull << 20)
+/* hist[c]: clouds[c].n x 33 floats; n_neighbours: NULL, or n_neighbours[c] NULL or clouds[c].n entries; host or device memory each */
+int mulls_compute_fpfh_batch(mulls_ctx *ctx, const mulls_cloud *clouds, uint32_t n_clouds, const mulls_fpfh_params *params, float *const *hist,
+							 uint32_t *const *n_neighbours, uint64_t scratch_limit_bytes);
+typedef struct mulls_fpfhsac_problem
+{
+	mulls_cloud tgt, src; /* host or device-resident clouds, by the single call's rules */
+} mulls_fpfhsac_problem;
+int mulls_coarse_reg_fpfhsac_batch(mulls_ctx *ctx, const mulls_fpfhsac_problem *problems, uint32_t n_problems, const mulls_fpfhsac_params *params,
+								   uint64_t scratch_limit_bytes, mulls_fpfhsac_result *results);
 
 /* ---- stage-level entry points (used by the parity tests; same kernels the driver launches) ---- */
 

@@ -656,7 +656,14 @@ class FpfhSacResult(C.Structure):
                 ("fitness", C.c_double), ("T", C.c_double * 16)]
 
 
+class FpfhSacProblem(C.Structure):
+    """mulls_fpfhsac_problem"""
+
+    _fields_ = [("tgt", Cloud), ("src", Cloud)]
+
+
 SACIA_TRUNCATED, SACIA_HUBER = range(2)  # enum mulls_sacia_error
+FPFHSAC_BATCH_DEFAULT_SCRATCH_BYTES = 1024 << 20  # MULLS_FPFHSAC_BATCH_DEFAULT_SCRATCH_BYTES
 FPFH_DIMS = 33
 FPFH_MAX_CELL_POINTS = 16384  # MULLS_FPFH_MAX_CELL_POINTS
 FPFH_HYP_CHUNK = 1024  # MULLS_FPFH_HYP_CHUNK (csrc/fpfh_launch.h): hypotheses whose nearest-target distances are held at a time

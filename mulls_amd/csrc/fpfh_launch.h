@@ -47,3 +47,28 @@ hipError_t launch_fpfh_slots(hipStream_t st, NdtDesc base, uint32_t n_src, uint3
 hipError_t launch_fpfh_errors(hipStream_t st, const NdtDesc *desc, uint32_t n, uint32_t n_src, unsigned char *arena, float thr, int huber, double *err);
 // the lowest error, the first among equals
 hipError_t launch_fpfh_pick(hipStream_t st, const double *err, const double *frames, uint32_t n_hyp, FpfhSacOut *out);
+
+// ---- many problems per launch (k_fpfh_batch.hip): a sub-batch's table, written by the host.  The samples, ranks, correspondences, frames and errors of
+// all problems are flat lists in problem order; problem b's hypotheses are first_hyp .. first_hyp + n_hyp - 1, its samples first_sample .. + 3 n_hyp - 1.
+struct FpfhProb
+{
+	uint64_t o_src, o_tgt;			 // packed float xyz
+	uint64_t o_src_hist, o_tgt_hist; // n x 33 float
+	uint64_t o_win_dist;			 // float per source point: the winner's distances
+	uint64_t dist_first;			 // the distance bytes of all hypotheses before first_hyp
+	uint32_t n_src, n_tgt, k_eff;
+	uint32_t first_sample, first_hyp, n_hyp;
+};
+// corr[s], s < n_samples: as launch_fpfh_similar, the wave finding its problem from s
+hipError_t launch_fpfh_batch_similar(hipStream_t st, const FpfhProb *prob, uint32_t P, unsigned char *arena, const int32_t *samples, const int32_t *ranks,
+									 uint32_t n_samples, int32_t *corr);
+// frames[12 h ..], h < n_hyp
+hipError_t launch_fpfh_batch_models(hipStream_t st, const FpfhProb *prob, uint32_t P, unsigned char *arena, const int32_t *samples, const int32_t *corr,
+									uint32_t n_hyp, double *frames);
+// desc[j], rec[j], j < n: hypothesis h0 + j of the flat list, its distances at o_pool + d(h0 + j) - d0
+hipError_t launch_fpfh_batch_slots(hipStream_t st, const FpfhProb *prob, uint32_t P, uint32_t h0, uint32_t n, uint64_t o_pool, uint64_t d0, NdtDesc *desc, NdtRec *rec);
+// err[j], j < n: over desc[j]'s distances, n_src its own
+hipError_t launch_fpfh_batch_errors(hipStream_t st, const NdtDesc *desc, uint32_t n, unsigned char *arena, float thr, int huber, double *err);
+// a workgroup per problem: out[b], the winner's frame in win_frames[12 b ..], and the slot of its fitness pass in desc[b], rec[b]
+hipError_t launch_fpfh_batch_pick(hipStream_t st, const FpfhProb *prob, uint32_t P, const double *err, const double *frames, FpfhSacOut *out, double *win_frames,
+								  NdtDesc *desc, NdtRec *rec);

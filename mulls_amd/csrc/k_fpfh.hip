@@ -9,6 +9,7 @@
 // is bounded by a descriptor field, a launch argument or a constant.
 #include <hip/hip_runtime.h>
 
+#include "fpfh_device.h"
 #include "fpfh_launch.h"
 #include "ransac_math.h"
 #include "reg_device.h"
@@ -218,52 +219,14 @@ __global__ void __launch_bounds__(256) k_fpfh_hist(const FpfhDesc *__restrict__ 
 		hist[b] = out[b];
 }
 
-// Similar features.  A wave per sample: lane l keeps the l-th smallest (d2, index) seen so far in registers.  64 target descriptors a step, a lane
-// each; a candidate before the list's entry of rank k_eff - 1 is inserted by a shift across the lanes.
+// Similar features: a wave per sample (fpfh_device.h has the text, as it has that of the four kernels below)
 __global__ void __launch_bounds__(256) k_fpfh_similar(const float *__restrict__ src_hist, const float *__restrict__ tgt_hist, const int32_t *__restrict__ samples,
 													  const int32_t *__restrict__ ranks, uint32_t n_samples, uint32_t n_src, uint32_t n_tgt, uint32_t k_eff, int32_t *corr)
 {
 	const uint32_t s = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-	if (s >= n_samples || k_eff == 0u || k_eff > 64u)
+	if (s >= n_samples)
 		return;
-	const uint32_t si = (uint32_t)samples[s] < n_src ? (uint32_t)samples[s] : 0u;
-	float a[MULLS_FPFH_DIMS];
-#pragma unroll
-	for (int k = 0; k < MULLS_FPFH_DIMS; k++)
-		a[k] = src_hist[(size_t)MULLS_FPFH_DIMS * si + k];
-	float ld = __builtin_huge_valf();
-	uint32_t li = NO_POINT;
-	for (uint32_t base = 0; base < n_tgt; base += 64u)
-	{
-		const uint32_t t = base + lane;
-		float cd = __builtin_huge_valf();
-		uint32_t ci = NO_POINT;
-		if (t < n_tgt)
-		{
-			cd = fpfh::desc_dist2(a, tgt_hist + (size_t)MULLS_FPFH_DIMS * t), ci = t;
-		}
-		unsigned long long mask = __ballot(pcl_icp::before(cd, ci, __shfl(ld, (int)k_eff - 1), __shfl(li, (int)k_eff - 1)));
-		while (mask)
-		{
-			const int c = __ffsll((long long)mask) - 1;
-			mask &= mask - 1ull;
-			const float xd = __shfl(cd, c);
-			const uint32_t xi = __shfl(ci, c);
-			if (!pcl_icp::before(xd, xi, __shfl(ld, (int)k_eff - 1), __shfl(li, (int)k_eff - 1)))
-				continue;
-			const uint32_t pos = (uint32_t)__popcll(__ballot(pcl_icp::before(ld, li, xd, xi))); // (the list is sorted: those before are its first pos lanes)
-			const float pd = __shfl_up(ld, 1);
-			const uint32_t pi = __shfl_up(li, 1);
-			if (lane == pos)
-				ld = xd, li = xi;
-			else if (lane > pos)
-				ld = pd, li = pi;
-		}
-	}
-	const uint32_t r = (uint32_t)ranks[s] < k_eff ? (uint32_t)ranks[s] : 0u;
-	const uint32_t pick = __shfl(li, (int)r);
-	if (lane == 0u)
-		corr[s] = pick < n_tgt ? (int32_t)pick : -1;
+	fpfh_dev::similar_wave(src_hist, tgt_hist, samples, ranks, s, n_src, n_tgt, k_eff, lane, corr);
 }
 
 __global__ void __launch_bounds__(256) k_fpfh_models(const float *__restrict__ src, const float *__restrict__ tgt, const int32_t *__restrict__ samples,
@@ -272,21 +235,7 @@ __global__ void __launch_bounds__(256) k_fpfh_models(const float *__restrict__ s
 	const uint32_t h = blockIdx.x * 256u + threadIdx.x;
 	if (h >= n_hyp)
 		return;
-	float s[3][3], t[3][3];
-	for (int k = 0; k < 3; k++)
-	{
-		const uint32_t i = (uint32_t)samples[3 * h + k] < n_src ? (uint32_t)samples[3 * h + k] : 0u, m = (uint32_t)corr[3 * h + k] < n_tgt ? (uint32_t)corr[3 * h + k] : 0u;
-		for (int a = 0; a < 3; a++)
-			s[k][a] = src[3 * i + a], t[k][a] = tgt[3 * m + a];
-	}
-	float M[12];
-	fit_three_pairs(s, t, M);
-	for (int r = 0; r < 3; r++)
-	{
-		for (int a = 0; a < 3; a++)
-			frames[12u * h + 3 * r + a] = (double)M[4 * r + a];
-		frames[12u * h + 9 + r] = (double)M[4 * r + 3];
-	}
+	fpfh_dev::model_of(src, tgt, samples + 3 * h, corr + 3 * h, n_src, n_tgt, frames + 12u * h);
 }
 
 __global__ void __launch_bounds__(256) k_fpfh_slots(NdtDesc base, uint32_t n_src, uint32_t n_tgt, uint32_t n, NdtDesc *desc, NdtRec *rec)
@@ -294,29 +243,16 @@ __global__ void __launch_bounds__(256) k_fpfh_slots(NdtDesc base, uint32_t n_src
 	const uint32_t h = blockIdx.x * 256u + threadIdx.x;
 	if (h >= n)
 		return;
-	NdtDesc d = base;
-	d.o_dist = base.o_dist + 4ull * n_src * h;
-	desc[h] = d;
-	rec[h].status = NDT_ST_OK, rec[h].n_src = n_src, rec[h].n_tgt = n_tgt, rec[h].fitness = 0.0;
+	fpfh_dev::slot_of(base, n_src, n_tgt, base.o_dist + 4ull * n_src * h, desc + h, rec + h);
 }
 
 // one workgroup per hypothesis: the error terms of its source points by the strided-partial rule
 __global__ void __launch_bounds__(256) k_fpfh_errors(const NdtDesc *__restrict__ desc, uint32_t n_src, const unsigned char *arena, float thr, int huber, double *err)
 {
 	__shared__ double s_p[256];
-	const uint32_t h = blockIdx.x, t = threadIdx.x;
-	const float *dist = reinterpret_cast<const float *>(arena + desc[h].o_dist);
-	double r[16];
-#pragma unroll
-	for (int m = 0; m < 16; m++)
-	{
-		double a = 0.0;
-		for (uint32_t i = t + 256u * m; i < n_src; i += MULLS_NDT_TREE)
-			a += fpfh::error_term(dist[i], thr, huber);
-		r[m] = a;
-	}
-	const double sum = tree_of_partials(r, s_p);
-	if (t == 0)
+	const uint32_t h = blockIdx.x;
+	const double sum = fpfh_dev::error_sum(reinterpret_cast<const float *>(arena + desc[h].o_dist), n_src, thr, huber, s_p);
+	if (threadIdx.x == 0)
 		err[h] = sum;
 }
 
@@ -325,30 +261,7 @@ __global__ void __launch_bounds__(256) k_fpfh_pick(const double *__restrict__ er
 {
 	__shared__ double s_e[256];
 	__shared__ uint32_t s_i[256];
-	const uint32_t t = threadIdx.x;
-	double be = 0.0;
-	uint32_t bi = NO_POINT;
-	for (uint32_t h = t; h < n_hyp; h += 256u)
-		if (bi == NO_POINT || fpfh::error_before(err[h], h, be, bi))
-			be = err[h], bi = h;
-	s_e[t] = be, s_i[t] = bi;
-	__syncthreads();
-	for (uint32_t w = 128; w >= 1; w >>= 1)
-	{
-		if (t < w)
-		{
-			const double oe = s_e[t + w];
-			const uint32_t oi = s_i[t + w];
-			if (oi != NO_POINT && (s_i[t] == NO_POINT || fpfh::error_before(oe, oi, s_e[t], s_i[t])))
-				s_e[t] = oe, s_i[t] = oi;
-		}
-		__syncthreads();
-	}
-	const uint32_t best = s_i[0] < n_hyp ? s_i[0] : 0u;
-	if (t == 0)
-		out->best = (int32_t)best, out->pad = 0, out->error = s_e[0];
-	if (t < 12)
-		out->frame[t] = frames[12u * best + t];
+	fpfh_dev::pick_into(err, frames, n_hyp, out, s_e, s_i);
 }
 } // namespace
 

@@ -143,6 +143,9 @@ def load():
     lib.mulls_fpfhsac_default_params.argtypes = [C.POINTER(abi.FpfhSacParams)]
     lib.mulls_fpfhsac_default_params.restype = None
     lib.mulls_coarse_reg_fpfhsac.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Cloud), C.POINTER(abi.FpfhSacParams), C.POINTER(abi.FpfhSacResult)]
+    lib.mulls_compute_fpfh_batch.argtypes = [vp, C.POINTER(abi.Cloud), C.c_uint32, C.POINTER(abi.FpfhParams), C.POINTER(vp), C.POINTER(vp), C.c_uint64]
+    lib.mulls_coarse_reg_fpfhsac_batch.argtypes = [vp, C.POINTER(abi.FpfhSacProblem), C.c_uint32, C.POINTER(abi.FpfhSacParams), C.c_uint64,
+                                                   C.POINTER(abi.FpfhSacResult)]
     lib.mulls_sor_default_params.argtypes = [C.POINTER(abi.SorParams)]
     lib.mulls_sor_default_params.restype = None
     lib.mulls_sor_filter.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.SorParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
@@ -203,6 +206,7 @@ EXPORTS = [
     "mulls_ndt_default_params", "mulls_ndt", "mulls_ndt_batch", "mulls_gicp_default_params", "mulls_gicp", "mulls_gicp_batch",
     "mulls_pcl_icp_default_params", "mulls_pcl_icp", "mulls_pcl_icp_batch",
     "mulls_fpfh_default_params", "mulls_fpfh", "mulls_fpfhsac_default_params", "mulls_coarse_reg_fpfhsac",
+    "mulls_compute_fpfh_batch", "mulls_coarse_reg_fpfhsac_batch",
     "mulls_nms_default_params", "mulls_non_max_suppress",
     "mulls_scan_prep_default_params", "mulls_scan_prepare",
     "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
@@ -904,6 +908,46 @@ class Context:
         if rc != 0:
             raise MullsError("mulls_coarse_reg_fpfhsac failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
         return res
+
+    def _normal_clouds(self, items, keep):
+        """_normal_cloud of every item; the same Python object given twice becomes the same mulls_cloud, so that the batch calls see a shared cloud"""
+        seen = {}
+        out = []
+        for k in items:
+            if id(k) not in seen:
+                seen[id(k)] = self._normal_cloud(k, keep)
+                keep.append(k)
+            out.append(seen[id(k)])
+        return out
+
+    def fpfh_batch(self, clouds, params=None, scratch_limit=0):
+        """mulls_compute_fpfh_batch: the descriptors of many clouds per call, each with the bits of its fpfh() call.  clouds: as _normal_cloud takes them; an
+        object given twice is one cloud, computed once.  Returns [(hist (n, 33) float32, n_neighbours (n,) uint32), ...]."""
+        keep, n = [], len(clouds)
+        cl = self._normal_clouds(clouds, keep)
+        arr = (abi.Cloud * max(n, 1))(*cl)
+        p = params if params is not None else abi.fpfh_params()
+        out = [(np.zeros((max(c.n, 1), abi.FPFH_DIMS), np.float32), np.zeros(max(c.n, 1), np.uint32)) for c in cl]
+        hp, kp = (C.c_void_p * max(n, 1))(*[h.ctypes.data for h, _ in out]), (C.c_void_p * max(n, 1))(*[k.ctypes.data for _, k in out])
+        rc = self.lib.mulls_compute_fpfh_batch(self.h, arr, n, C.byref(p), hp, kp, scratch_limit)
+        if rc != 0:
+            raise MullsError("mulls_compute_fpfh_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return [(h[: c.n], k[: c.n]) for (h, k), c in zip(out, cl)]
+
+    def coarse_reg_fpfhsac_batch(self, problems, params=None, scratch_limit=0):
+        """mulls_coarse_reg_fpfhsac_batch: many SAC-IA problems per call in lock step, each with the bytes of its coarse_reg_fpfhsac call.  problems:
+        (tgt, src) pairs as _normal_cloud takes them; an object given twice (as a source, a target or both) is one cloud, staged once with its
+        descriptors computed once per sub-batch.  One params for the whole batch.  Returns [mulls_fpfhsac_result, ...]."""
+        keep, B = [], len(problems)
+        flat = self._normal_clouds([k for prob in problems for k in prob], keep)
+        arr, res = (abi.FpfhSacProblem * max(B, 1))(), (abi.FpfhSacResult * max(B, 1))()
+        for b in range(B):
+            arr[b].tgt, arr[b].src = flat[2 * b], flat[2 * b + 1]
+        p = params if params is not None else abi.fpfhsac_params()
+        rc = self.lib.mulls_coarse_reg_fpfhsac_batch(self.h, arr, B, C.byref(p), scratch_limit, res)
+        if rc != 0:
+            raise MullsError("mulls_coarse_reg_fpfhsac_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        return [abi.FpfhSacResult.from_buffer_copy(res[b]) for b in range(B)]
 
     # --- pose graph optimisation --------------------------------------------------------------------------------------
     def pgo_optimize(self, poses, fixed, stable, edges, params=None):

@@ -4,7 +4,14 @@ scene (1 500 / 1 200 points, 120 hypotheses) and on 20 000 / 16 000 points with 
 on the recovery scene for scale, with its bits compared.  Medians over the repetitions after one warm-up call, host clock around synchronised calls.  No
 target was fixed in advance: the file records what was found.  Per kernel: run `--one` under a kernel trace
 (rocprofv3 --kernel-trace --stats -- python tools/gpu_fpfh.py --one).
-usage: gpu_fpfh.py [--no-restated] [--one: the recovery scene's solver three times, for a kernel trace]"""
+
+--batch 1,8,64 times the batch entry points (mulls_compute_fpfh_batch, mulls_coarse_reg_fpfhsac_batch) against as many single calls, written to
+profiles/fpfh_batch.txt: B distinct 1 500 / 1 200 pairs at 120 hypotheses; one 20 000-point target against B 16 000-point sources at 10 hypotheses (the
+shared-descriptor case); the descriptors of B clouds of 20 000 points.  Same process and context, a batch call and its B single calls alternating,
+medians after one warm-up of each, host clock around synchronised calls; the results' bytes are compared on the way.  The descriptor rows go through
+the C calls into reused output arrays (see batch_table).
+usage: gpu_fpfh.py [--no-restated] [--one: the recovery scene's solver three times, for a kernel trace] [--batch B,B,...]"""
+import ctypes as C
 import os
 import sys
 import time
@@ -37,9 +44,89 @@ def pair(n_tgt, n_src, side, seed):
     return (A, An), (B, Bn)
 
 
+def alternating(batch, singles, reps):
+    """-> median seconds of batch(), median seconds of singles(), and whether both gave the same bytes; the two alternate after one warm-up of each"""
+    same = batch() == singles()
+    tb, ts = [], []
+    for _ in range(reps):
+        t = time.perf_counter()
+        batch()
+        tb.append(time.perf_counter() - t)
+        t = time.perf_counter()
+        singles()
+        ts.append(time.perf_counter() - t)
+    return float(np.median(tb)), float(np.median(ts)), same
+
+
+def result_bytes(results):
+    return [bytes(r) for r in results]
+
+
+def batch_table(ctx, sizes):
+    os.makedirs("profiles", exist_ok=True)
+    out = open(os.path.join("profiles", "fpfh_batch.txt"), "w")
+
+    def say(s):
+        print(s, flush=True)
+        out.write(s + "\n")
+        out.flush()
+
+    say("One batch call against B single calls (mulls_coarse_reg_fpfhsac_batch, mulls_compute_fpfh_batch), search_radius 0.4, host clouds of 48-byte records,")
+    say("the default scratch limit; one MI355X; a batch call and its single calls alternating in one process and context, medians after a warm-up of each")
+    small = dict(fpfh_scenes.RECOVERY)
+    big = dict(search_radius=0.4, k_correspondences=2, max_iterations=10, min_sample_distance=2.0, max_correspondence_distance=0.05, seed=1)
+    for B in sizes:
+        reps = 7 if B <= 8 else 3
+        pairs = [pair(1500, 1200, 8.0, 100 + 2 * b) for b in range(B)]
+        p = abi.fpfhsac_params(**small)
+        tb, ts, same = alternating(lambda: result_bytes(ctx.coarse_reg_fpfhsac_batch(pairs, p)), lambda: result_bytes([ctx.coarse_reg_fpfhsac(t, s, p) for t, s in pairs]), reps)
+        say("B = %2d distinct 1 500 / 1 200 pairs, 120 hypotheses: batch %8.2f ms, single calls %8.2f ms (x %.2f), median of %d; equal bytes: %s"
+            % (B, tb * 1e3, ts * 1e3, ts / tb, reps, same))
+    for B in sizes:
+        reps = 5 if B <= 8 else 3
+        tgt = fpfh_scenes.bumpy(41, 20000, 29.2)
+        srcs = []
+        for b in range(B):
+            sel = np.sort(np.random.default_rng(200 + b).choice(20000, 16000, replace=False))
+            srcs.append(fpfh_scenes.moved(tgt[0][sel], tgt[1][sel], np.linalg.inv(fpfh_scenes.sac_truth())))
+        probs = [(tgt, s) for s in srcs]
+        p = abi.fpfhsac_params(**big)
+        tb, ts, same = alternating(lambda: result_bytes(ctx.coarse_reg_fpfhsac_batch(probs, p)), lambda: result_bytes([ctx.coarse_reg_fpfhsac(t, s, p) for t, s in probs]), reps)
+        say("B = %2d sources of 16 000 against one target of 20 000, 10 hypotheses: batch %8.2f ms, single calls %8.2f ms (x %.2f), median of %d; equal bytes: %s"
+            % (B, tb * 1e3, ts * 1e3, ts / tb, reps, same))
+    # The descriptors through the C calls into output arrays that are reused: with fresh arrays of 2.6 MB a cloud per call (Context.fpfh,
+    # Context.fpfh_batch) either way spends tens of milliseconds of host time in this process on memory that was a copy's target and is freed again,
+    # which is not what is compared here.
+    fp = abi.fpfh_params(0.4)
+    for B in sizes:
+        reps = 7 if B <= 8 else 3
+        raws = [abi.make_points(*fpfh_scenes.bumpy(300 + b, 20000, 29.2)) for b in range(B)]
+        arr = (abi.Cloud * B)(*[abi.as_cloud(r) for r in raws])
+        outs = [[(np.zeros((len(r), 33), np.float32), np.zeros(len(r), np.uint32)) for r in raws] for _ in range(2)]
+        hp, kp = (C.c_void_p * B)(*[h.ctypes.data for h, _ in outs[0]]), (C.c_void_p * B)(*[k.ctypes.data for _, k in outs[0]])
+
+        def batch():
+            assert ctx.lib.mulls_compute_fpfh_batch(ctx.h, arr, B, C.byref(fp), hp, kp, 0) == 0
+            return True
+
+        def singles():
+            for b in range(B):
+                assert ctx.lib.mulls_fpfh(ctx.h, C.byref(arr[b]), C.byref(fp), outs[1][b][0].ctypes.data, outs[1][b][1].ctypes.data) == 0
+            return True
+
+        tb, ts, _ = alternating(batch, singles, reps)
+        same = all(a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes() for a, b in zip(*outs))
+        say("B = %2d clouds of 20 000 points, descriptors (C calls, reused outputs): batch %8.2f ms, single calls %8.2f ms (x %.2f), median of %d; equal bytes: %s"
+            % (B, tb * 1e3, ts * 1e3, ts / tb, reps, same))
+    out.close()
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     ctx = lib.Context(0)
+    if "--batch" in argv:
+        batch_table(ctx, [int(v) for v in argv[argv.index("--batch") + 1].split(",")])
+        return
     rec = fpfh_scenes.sac_cases()["sac_recovery"]
     tgt, src, prm = (rec["tgt"], rec["tgt_nrm"]), (rec["src"], rec["src_nrm"]), abi.fpfhsac_params(**rec["prm"])
     if "--one" in argv:
