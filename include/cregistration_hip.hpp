@@ -1174,6 +1174,48 @@ inline bool non_max_suppress(typename pcl::PointCloud<PointT>::Ptr &cloud_in_out
 	take_cloud<PointT>(cloud_in_out, raw, n_out, false); // :1230
 	return true;
 }
+// The in-place overload applied to every cloud of a vector in one device call (mulls_non_max_suppress_batch): the key points of every scan of an event,
+// or both clouds of mulls_reg.cpp:147-148.  ok[k] is what the in-place overload returns for cloud k (false, and the cloud untouched, below 10 points).
+// The refusals are the single bridge's: distance_adaptive_on and kd_tree_already_built throw, as does a cloud the single call refuses (a NaN key, a
+// non-finite coordinate); no cloud is changed then.
+template <typename PointT>
+inline std::vector<bool> non_max_suppress_batch(std::vector<typename pcl::PointCloud<PointT>::Ptr> &clouds_in_out, float non_max_radius,
+												 bool distance_adaptive_on = false, bool kd_tree_already_built = false)
+{
+	if (distance_adaptive_on || kd_tree_already_built)
+		throw std::runtime_error("lo::hip::non_max_suppress_batch: distance_adaptive_on and kd_tree_already_built are not supported");
+	const size_t B = clouds_in_out.size();
+	std::vector<bool> ok(B, false);
+	if (B == 0)
+		return ok;
+	mulls_ctx *ctx = thread_context();
+	mulls_nms_params P;
+	mulls_nms_default_params(&P);
+	P.non_max_radius = non_max_radius;
+	std::vector<mulls_nms_problem> problems(B);
+	std::vector<mulls_nms_report> reports(B);
+	std::vector<std::vector<unsigned char>> raw(B);
+	for (size_t k = 0; k < B; k++)
+	{
+		mulls_nms_problem &Q = problems[k];
+		Q.cloud = borrow(clouds_in_out[k]);
+		raw[k].resize((size_t)Q.cloud.n * MULLS_POINT_BYTES);
+		Q.out = raw[k].empty() ? nullptr : raw[k].data();
+		Q.cap = Q.cloud.n;
+		Q.kept_idx = nullptr, Q.order = nullptr, Q.idx_cap = 0;
+	}
+	const int rc = mulls_non_max_suppress_batch(ctx, problems.data(), static_cast<uint32_t>(B), &P, 0, reports.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_non_max_suppress_batch failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	for (size_t k = 0; k < B; k++)
+	{
+		if (clouds_in_out[k]->points.size() < 10) // :1189-1191
+			continue;
+		take_cloud<PointT>(clouds_in_out[k], raw[k], reports[k].n_kept, false); // :1230
+		ok[k] = true;
+	}
+	return ok;
+}
 
 // The raw-scan steps of CFilter<PointT> in front of extract_semantic_pts and of the map export (test/mulls_slam.cpp:359-362, :404-412, :966-974), verbatim
 // signatures and defaults, each one device call on the cloud's records in place (mulls_scan_prepare with one step switched on; a caller that owns the

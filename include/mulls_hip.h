@@ -1054,6 +1054,44 @@ void mulls_nms_default_params(mulls_nms_params *p); /* radius 0.25, path 0 */
 int mulls_non_max_suppress(mulls_ctx *ctx, const mulls_cloud *cloud, const mulls_nms_params *params, void *out, uint32_t cap, uint32_t *n_out, int32_t *kept_idx,
 						   uint32_t idx_cap, int32_t *order, mulls_nms_report *report);
 
+/* Many key-point clouds per call: problem b gets, byte for byte, what mulls_non_max_suppress gives for problems[b].cloud with the same params
+ * (reports[b].n_in, n_kept and ran; the records in out, the entries of kept_idx, the whole order): the gate, the key, the host std::sort, the radius
+ * test and the cell edge above are not redefined.  reports[b].path is the path problem b took and rounds that path's count; ms_total is the wall time of
+ * the whole call, the same in every report.  reports may be NULL.
+ *   paths       params->path 0: a problem of 10 .. MULLS_NMS_LDS_MAX_POINTS points takes path 1 — here as ONE launch for the whole sub-batch, one
+ *               workgroup per problem (B clouds on B compute units cost about what one costs, and no host poll separates the rounds) —, a larger one
+ *               path 2.  path 1: a problem beyond MULLS_NMS_LDS_MAX_POINTS that passes the gate: MULLS_E_UNSUPPORTED.  path 2: every problem through
+ *               the multi-launch kernels.  Problems on path 2 run one after another inside the call, each as the single call runs it: they are the
+ *               exception (key-point clouds have a few thousand points), and nothing about them is batched.
+ *   per problem n == 0: nothing kept.  n < 10: the identity, ran = 0.  The rest of the batch runs.
+ *   refused     a problem the single call would refuse (a bad stride, a NULL pointer that is needed, a non-finite coordinate or radius, a NaN key, more
+ *               than MULLS_NMS_MAX_POINTS points), or NULL params: the call returns the single call's code, mulls_last_error names the first such
+ *               problem ("problem 2"), no output of any problem is written and every report is zeroed.  Host clouds are checked before any device
+ *               work; a NaN key or non-finite coordinate of a device-resident cloud is found by the key pass, which runs for the whole call before
+ *               anything is written.  n_problems == 0: MULLS_OK.
+ *   arena       scratch_limit_bytes (0: MULLS_NMS_BATCH_DEFAULT_SCRATCH_BYTES) bounds the call's device arena, which belongs to the context, only
+ *               grows and is released with it.  Per staged point it holds the 48-byte record in visiting order (a device-resident cloud: also its key
+ *               and its permutation entry), per problem a header, the kept positions and room for the kept records it may return.  The batch is cut
+ *               into consecutive sub-batches that fit; a problem larger than the limit runs alone.  The same cloud may appear in several problems:
+ *               it is staged once per distinct (pts, n, stride) of a sub-batch, and no result depends on that.
+ * A sub-batch is: one key launch over its device-resident clouds and one download (for all sub-batches, first); the orders on the host's thread pool;
+ * one upload of the records in visiting order (device-resident clouds: of the permutations, and one gather launch); the suppression launch; one download
+ * of the headers and kept positions and one of the kept records. */
+typedef struct mulls_nms_problem
+{
+	mulls_cloud cloud; /* host or device-resident, by the single call's rules (strides included); never modified */
+	void *out;		   /* cap records of 48 bytes, or NULL with cap = 0 */
+	int32_t *kept_idx; /* idx_cap entries, or NULL with idx_cap = 0 */
+	int32_t *order;	   /* cloud.n entries, or NULL */
+	uint32_t cap, idx_cap;
+} mulls_nms_problem;
+
+#define MULLS_NMS_BATCH_DEFAULT_SCRATCH_BYTES (512ull << 20) /* a value chosen without a measurement */
+int mulls_non_max_suppress_batch(mulls_ctx *ctx, const mulls_nms_problem *problems, uint32_t n_problems, const mulls_nms_params *params,
+								 uint64_t scratch_limit_bytes, mulls_nms_report *reports);
+/* bytes of the batch entry's device arena as it stands (0 before the first call that needed one): what tests watch grow */
+uint64_t mulls_nms_batch_arena_bytes(const mulls_ctx *ctx);
+
 /* ---- scan preparation: the raw-scan steps of CFilter in front of extract_semantic_pts and of the map export (include/common/cfilter.hpp) ----
  * What test/mulls_slam.cpp runs on pc_raw before the feature extraction (:359-362 and :404-412: dist_filter, vertical_intrinsic_calibration,
  * get_pts_timestamp_ratio_in_frame) and per frame of the merged map (:966-974: calibration, dist_filter, random_downsample, time ratio), on the device and

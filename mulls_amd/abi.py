@@ -703,6 +703,15 @@ NMS_MAX_POINTS = 1 << 18  # MULLS_NMS_MAX_POINTS
 NMS_LDS_MAX_POINTS = 4096  # MULLS_NMS_LDS_MAX_POINTS: the one-workgroup path's limit
 
 
+class NmsProblem(C.Structure):
+    """mulls_nms_problem: one problem of mulls_non_max_suppress_batch"""
+
+    _fields_ = [("cloud", Cloud), ("out", C.c_void_p), ("kept_idx", C.c_void_p), ("order", C.c_void_p), ("cap", C.c_uint32), ("idx_cap", C.c_uint32)]
+
+
+NMS_BATCH_DEFAULT_SCRATCH_BYTES = 512 << 20  # MULLS_NMS_BATCH_DEFAULT_SCRATCH_BYTES
+
+
 def nms_params(non_max_radius=0.25, path=0):
     p = NmsParams()
     p.non_max_radius, p.path = float(non_max_radius), int(path)

@@ -2,7 +2,10 @@
 // thousand key points): the whole suppression in ONE workgroup of 1024 lanes on one CU, with workgroup barriers where the multi-launch path
 // (k_cl_nms_* in k_classify.hip) has launches and host polls.
 //   k_nms_keys   normal[3] of every record of a device cloud, and the non-finite flag
-//   k_nms_one    records in visiting order -> kept positions, kept records:
+//   k_nms_batch_keys, k_nms_batch_gather, k_nms_batch    mulls_non_max_suppress_batch: the keys of all device-resident clouds of a sub-batch, their
+//                records in visiting order, and the suppression of every problem with one workgroup each (nms_suppress, the body k_nms_one runs), in
+//                one launch each.  Alone one workgroup loses to the multi-launch path; B clouds on B CUs cost what one costs (profiles/nms_batch.txt)
+//   k_nms_one    records in visiting order -> kept positions, kept records (nms_suppress):
 //                  stage    x, y, z as three float arrays in LDS, a state byte per point (0 suppressed, 1 kept, 2 undecided)
 //                  cells    a hashed grid in LDS, cell edge a hair above the radius: bucket of every point (the cell's three integer-valued doubles,
 //                           hashed into H = the power of two >= n buckets), counts, their scan, the points' positions in bucket order (a counting sort)
@@ -118,11 +121,12 @@ __device__ __forceinline__ void nms_walk(const NmsLds &L, uint32_t p, float r2, 
 	}
 }
 
-__global__ __launch_bounds__(MULLS_NMS_BLOCK) void k_nms_one(const float4 *__restrict__ recs, uint32_t n, uint32_t H, float r2, double inv_edge,
-															  NmsHeader *__restrict__ hdr, uint32_t *__restrict__ kept_pos, float4 *__restrict__ out, uint32_t out_cap)
+// The whole suppression of one cloud by one workgroup of MULLS_NMS_BLOCK lanes: the one text of the staging, the cells, the lists, the rounds and the
+// compaction, for k_nms_one (the single call's path 1) and k_nms_batch (one workgroup per problem).  nms_lds: nms_lds_bytes(n) bytes of LDS at least;
+// wsum: MULLS_NMS_BLOCK / 64 words of LDS.  Returns the kept count (the same in every lane); *rounds_out: the rounds run.
+__device__ __forceinline__ uint32_t nms_suppress(const float4 *__restrict__ recs, uint32_t n, uint32_t H, float r2, double inv_edge, uint32_t *__restrict__ kept_pos,
+												  float4 *__restrict__ out, uint32_t out_cap, unsigned char *nms_lds, uint32_t *wsum, uint32_t *rounds_out)
 {
-	extern __shared__ unsigned char nms_lds[];
-	__shared__ uint32_t wsum[MULLS_NMS_BLOCK / 64u];
 	NmsLds L;
 	L.sx = reinterpret_cast<float *>(nms_lds), L.sy = L.sx + n, L.sz = L.sy + n;
 	L.start = reinterpret_cast<uint32_t *>(L.sz + n);
@@ -269,11 +273,103 @@ __global__ __launch_bounds__(MULLS_NMS_BLOCK) void k_nms_one(const float4 *__res
 		n_kept += all;
 		__syncthreads();
 	}
-	if (t == 0)
+	*rounds_out = rounds;
+	return n_kept;
+}
+
+__global__ __launch_bounds__(MULLS_NMS_BLOCK) void k_nms_one(const float4 *__restrict__ recs, uint32_t n, uint32_t H, float r2, double inv_edge,
+															  NmsHeader *__restrict__ hdr, uint32_t *__restrict__ kept_pos, float4 *__restrict__ out, uint32_t out_cap)
+{
+	extern __shared__ unsigned char nms_lds[];
+	__shared__ uint32_t wsum[MULLS_NMS_BLOCK / 64u];
+	uint32_t rounds;
+	const uint32_t n_kept = nms_suppress(recs, n, H, r2, inv_edge, kept_pos, out, out_cap, nms_lds, wsum, &rounds);
+	if (threadIdx.x == 0)
 	{
 		hdr->n_kept = n_kept;
 		hdr->rounds = rounds;
 	}
+}
+
+// ---- mulls_non_max_suppress_batch (nms_batch.h has the arena's layout).  Every trip count below is bounded by a value of a record the host validated
+// and wrote: a cloud's n (<= MULLS_NMS_MAX_POINTS; <= MULLS_NMS_LDS_MAX_POINTS where a workgroup holds it), the count of cloud records, the kept count (<= n).
+template <class T>
+__device__ __forceinline__ T *at(unsigned char *arena, uint64_t off)
+{
+	return reinterpret_cast<T *>(arena + off);
+}
+// the cloud whose blocks hold `block`: first[c] <= block < first[c + 1]; first[0] = 0, first[count] = the grid
+__device__ __forceinline__ uint32_t nms_find_cloud(const uint32_t *__restrict__ first, uint32_t count, uint32_t block)
+{
+	uint32_t lo = 0, hi = count;
+	while (hi - lo > 1u)
+	{
+		const uint32_t mid = (lo + hi) >> 1;
+		if (first[mid] <= block)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	return lo;
+}
+
+// keys and non-finite flags of every device-resident cloud of a sub-batch: a block of 256 lanes belongs to one cloud
+__global__ __launch_bounds__(256) void k_nms_batch_keys(unsigned char *__restrict__ arena, uint64_t o_src, uint64_t o_blk, uint32_t n_src, uint64_t o_bad)
+{
+	const uint32_t c = nms_find_cloud(at<uint32_t>(arena, o_blk), n_src, blockIdx.x);
+	const NmsBatchSrc S = at<NmsBatchSrc>(arena, o_src)[c];
+	const uint32_t i = (blockIdx.x - S.blk) * 256u + threadIdx.x;
+	if (i >= S.n)
+		return;
+	const float4 *recs = reinterpret_cast<const float4 *>(S.src);
+	const float4 r0 = recs[(size_t)i * 3];
+	at<float>(arena, S.keys)[i] = recs[(size_t)i * 3 + 1].w;
+	if (!(isfinite(r0.x) && isfinite(r0.y) && isfinite(r0.z)))
+		atomicOr(at<uint32_t>(arena, o_bad) + c, 1u);
+}
+
+// the records of the first n_src device-resident clouds in visiting order: recs[i] = src[perm[i]] (perm: the host's permutation of 0 .. n - 1)
+__global__ __launch_bounds__(256) void k_nms_batch_gather(unsigned char *__restrict__ arena, uint64_t o_src, uint64_t o_blk, uint32_t n_src)
+{
+	const uint32_t c = nms_find_cloud(at<uint32_t>(arena, o_blk), n_src, blockIdx.x);
+	const NmsBatchSrc S = at<NmsBatchSrc>(arena, o_src)[c];
+	const uint32_t i = (blockIdx.x - S.blk) * 256u + threadIdx.x;
+	if (i >= S.n)
+		return;
+	const uint32_t j = at<uint32_t>(arena, S.perm)[i];
+	if (j >= S.n) // (never: the host sorted 0 .. n - 1)
+		return;
+	const float4 *src = reinterpret_cast<const float4 *>(S.src);
+	float4 *dst = at<float4>(arena, S.recs);
+	dst[(size_t)i * 3] = src[(size_t)j * 3];
+	dst[(size_t)i * 3 + 1] = src[(size_t)j * 3 + 1];
+	dst[(size_t)i * 3 + 2] = src[(size_t)j * 3 + 2];
+}
+
+// one workgroup per problem: problem blockIdx.x of the sub-batch's records.  The kept records go to the sub-batch's one compact region: the
+// workgroup reserves min(n_kept, out_cap) records at the cursor (the order of the ranges is the order of arrival; the header says where the range is).
+__global__ __launch_bounds__(MULLS_NMS_BLOCK) void k_nms_batch(unsigned char *__restrict__ arena, uint64_t o_desc, float r2, double inv_edge, uint64_t o_cursor,
+																uint64_t o_out)
+{
+	extern __shared__ unsigned char nms_lds[];
+	__shared__ uint32_t wsum[MULLS_NMS_BLOCK / 64u];
+	__shared__ uint32_t out_at;
+	const NmsBatchDesc D = at<NmsBatchDesc>(arena, o_desc)[blockIdx.x];
+	const float4 *recs = at<float4>(arena, D.recs);
+	uint32_t *kept_pos = at<uint32_t>(arena, D.kept);
+	uint32_t rounds;
+	const uint32_t n_kept = nms_suppress(recs, D.n, D.H, r2, inv_edge, kept_pos, nullptr, 0u, nms_lds, wsum, &rounds);
+	const uint32_t n_rec = n_kept < D.out_cap ? n_kept : D.out_cap;
+	if (threadIdx.x == 0)
+	{
+		out_at = atomicAdd(at<uint32_t>(arena, o_cursor), n_rec);
+		NmsBatchHeader *hdr = at<NmsBatchHeader>(arena, D.hdr);
+		hdr->n_kept = n_kept, hdr->rounds = rounds, hdr->out_at = out_at, hdr->pad = 0u;
+	}
+	__syncthreads(); // (the kept positions were written before the compaction's last barrier)
+	float4 *out = at<float4>(arena, o_out) + (size_t)out_at * 3;
+	for (uint32_t k = threadIdx.x; k < n_rec * 3u; k += MULLS_NMS_BLOCK)
+		out[k] = recs[(size_t)kept_pos[k / 3u] * 3 + k % 3u];
 }
 } // namespace
 
@@ -284,21 +380,70 @@ hipError_t launch_nms_keys(hipStream_t st, const void *recs, uint32_t n, float *
 	return hipGetLastError();
 }
 
+namespace
+{
+// per device (launch.h: DevLaunch): the one-workgroup kernels may take the whole LDS of a CU
+bool nms_dev_ready()
+{
+	const DevLaunch D = dev_launch<4>([](DevLaunch &) {
+		return hipFuncSetAttribute(reinterpret_cast<const void *>(k_nms_one), hipFuncAttributeMaxDynamicSharedMemorySize,
+								   (int)nms_lds_bytes(MULLS_NMS_LDS_MAX_POINTS)) == hipSuccess &&
+			   hipFuncSetAttribute(reinterpret_cast<const void *>(k_nms_batch), hipFuncAttributeMaxDynamicSharedMemorySize,
+								   (int)nms_lds_bytes(MULLS_NMS_LDS_MAX_POINTS)) == hipSuccess;
+	});
+	return D.ok;
+}
+// r2 and the reciprocal cell edge of a radius
+void nms_radius_args(float radius, float *r2, double *inv_edge)
+{
+	*r2 = (float)((double)radius * (double)radius);
+	const double edge = std::fabs((double)radius) * (1.0 + 1e-5);
+	// the grid's exactness rests on d2's relative rounding error; an r2 near the subnormal range has none to speak of: one cell then (inv_edge 0), all pairs
+	*inv_edge = *r2 >= 1e-30f ? 1.0 / edge : 0.0;
+}
+} // namespace
+
 hipError_t launch_nms_one(hipStream_t st, const float4 *recs, uint32_t n, float radius, NmsHeader *hdr, uint32_t *kept_pos, float4 *out, uint32_t out_cap)
 {
 	if (n == 0 || n > MULLS_NMS_LDS_MAX_POINTS)
 		return hipErrorInvalidValue;
-	// per device (launch.h: DevLaunch): the kernel may take the whole LDS of a CU
-	const DevLaunch D = dev_launch<4>([](DevLaunch &) {
-		return hipFuncSetAttribute(reinterpret_cast<const void *>(k_nms_one), hipFuncAttributeMaxDynamicSharedMemorySize,
-								   (int)nms_lds_bytes(MULLS_NMS_LDS_MAX_POINTS)) == hipSuccess;
-	});
-	if (!D.ok)
+	if (!nms_dev_ready())
 		return hipErrorInvalidValue;
-	const float r2 = (float)((double)radius * (double)radius);
-	const double edge = std::fabs((double)radius) * (1.0 + 1e-5);
-	// the grid's exactness rests on d2's relative rounding error; an r2 near the subnormal range has none to speak of: one cell then (inv_edge 0), all pairs
-	const double inv_edge = r2 >= 1e-30f ? 1.0 / edge : 0.0;
+	float r2;
+	double inv_edge;
+	nms_radius_args(radius, &r2, &inv_edge);
 	hipLaunchKernelGGL(k_nms_one, dim3(1), dim3(MULLS_NMS_BLOCK), nms_lds_bytes(n), st, recs, n, nms_buckets(n), r2, inv_edge, hdr, kept_pos, out, out_cap);
+	return hipGetLastError();
+}
+
+hipError_t launch_nms_batch_keys(hipStream_t st, unsigned char *arena, const NmsBatchLayout &L)
+{
+	const uint32_t n_src = (uint32_t)L.src.size();
+	if (n_src && L.blk[n_src])
+		hipLaunchKernelGGL(k_nms_batch_keys, dim3(L.blk[n_src]), dim3(256), 0, st, arena, L.o_src, L.o_blk, n_src, L.o_bad);
+	return hipGetLastError();
+}
+
+hipError_t launch_nms_batch_gather(hipStream_t st, unsigned char *arena, const NmsBatchLayout &L)
+{
+	if (L.n_gather && L.gather_blk)
+		hipLaunchKernelGGL(k_nms_batch_gather, dim3(L.gather_blk), dim3(256), 0, st, arena, L.o_src, L.o_blk, L.n_gather);
+	return hipGetLastError();
+}
+
+hipError_t launch_nms_batch(hipStream_t st, unsigned char *arena, const NmsBatchLayout &L, float radius)
+{
+	const uint32_t B = (uint32_t)L.desc.size();
+	if (!B)
+		return hipSuccess;
+	if (L.n_max > MULLS_NMS_LDS_MAX_POINTS || B > MULLS_NMS_BATCH_MAX_PROBLEMS || !nms_dev_ready())
+		return hipErrorInvalidValue;
+	float r2;
+	double inv_edge;
+	nms_radius_args(radius, &r2, &inv_edge);
+	// Dynamic LDS is one size per launch: the largest cloud's.  Measured against a launch per size class (the clouds that fit half a CU's LDS first, so that
+	// two of their workgroups share a CU whatever else the batch holds; profiles/nms_batch.txt): 448 clouds of 1024 points with 64 of 4096 take 6.28 ms this
+	// way and 6.50 ms as two launches, which run one after the other; a batch of small clouds alone has a small launch either way.
+	hipLaunchKernelGGL(k_nms_batch, dim3(B), dim3(MULLS_NMS_BLOCK), nms_lds_bytes(L.n_max), st, arena, L.o_desc, r2, inv_edge, L.o_cursor, L.o_out);
 	return hipGetLastError();
 }

@@ -154,6 +154,9 @@ def load():
     lib.mulls_nms_default_params.restype = None
     lib.mulls_non_max_suppress.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.NmsParams), vp, C.c_uint32, C.POINTER(C.c_uint32), vp, C.c_uint32, vp,
                                            C.POINTER(abi.NmsReport)]
+    lib.mulls_non_max_suppress_batch.argtypes = [vp, C.POINTER(abi.NmsProblem), C.c_uint32, C.POINTER(abi.NmsParams), C.c_uint64, C.POINTER(abi.NmsReport)]
+    lib.mulls_nms_batch_arena_bytes.argtypes = [vp]
+    lib.mulls_nms_batch_arena_bytes.restype = C.c_uint64
     lib.mulls_scan_prep_default_params.argtypes = [C.POINTER(abi.ScanPrepParams)]
     lib.mulls_scan_prep_default_params.restype = None
     lib.mulls_scan_prepare.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(abi.ScanPrepParams), C.POINTER(C.c_uint32), C.POINTER(abi.ScanPrepReport)]
@@ -207,7 +210,7 @@ EXPORTS = [
     "mulls_pcl_icp_default_params", "mulls_pcl_icp", "mulls_pcl_icp_batch",
     "mulls_fpfh_default_params", "mulls_fpfh", "mulls_fpfhsac_default_params", "mulls_coarse_reg_fpfhsac",
     "mulls_compute_fpfh_batch", "mulls_coarse_reg_fpfhsac_batch",
-    "mulls_nms_default_params", "mulls_non_max_suppress",
+    "mulls_nms_default_params", "mulls_non_max_suppress", "mulls_non_max_suppress_batch", "mulls_nms_batch_arena_bytes",
     "mulls_scan_prep_default_params", "mulls_scan_prepare",
     "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
     "mulls_overlap_default_params", "mulls_submaps_create", "mulls_submaps_destroy", "mulls_submaps_push", "mulls_submaps_push_map", "mulls_submaps_count",
@@ -1035,6 +1038,37 @@ class Context:
             raise MullsError("mulls_non_max_suppress failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
         assert idx[n] == -1 and order[n] == -1 and n_out.value <= n
         return out[: n_out.value].copy(), idx[: n_out.value].copy(), order[:n].copy(), rep
+
+    def non_max_suppress_batch(self, clouds, radius=0.25, path=0, scratch_limit_bytes=0):
+        """mulls_non_max_suppress_batch: many clouds per call.  clouds: a list of what non_max_suppress takes (the same object may appear more than once).
+        Returns a list with, per cloud, what non_max_suppress returns: (kept, kept_idx, order, report).  path: 0 = the library chooses per cloud (one
+        workgroup per cloud up to abi.NMS_LDS_MAX_POINTS points, all of them in one launch; the multi-launch path beyond), 1 and 2 force a path."""
+        n = len(clouds)
+        arr, reps, keep, bufs = (abi.NmsProblem * max(n, 1))(), (abi.NmsReport * max(n, 1))(), [], []
+        for b, pts in enumerate(clouds):
+            if isinstance(pts, abi.Cloud):
+                c = pts
+            else:
+                raw = abi.records(pts)
+                c = abi.Cloud()
+                c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+                keep.append(raw)
+            m = c.n
+            out, idx, order = np.zeros((m + 1, abi.POINT_BYTES), np.uint8), np.full(m + 1, -1, np.int32), np.full(m + 1, -1, np.int32)  # one slot past m: left alone
+            arr[b].cloud, arr[b].out, arr[b].kept_idx, arr[b].order, arr[b].cap, arr[b].idx_cap = c, out.ctypes.data, idx.ctypes.data, order.ctypes.data, m, m
+            bufs.append((out, idx, order))
+        p = abi.nms_params(radius, path)
+        rc = self.lib.mulls_non_max_suppress_batch(self.h, arr, n, C.byref(p), int(scratch_limit_bytes), reps)
+        if rc != 0:
+            raise MullsError("mulls_non_max_suppress_batch failed with %d: %s" % (rc, self.lib.mulls_last_error(self.h).decode()), rc)
+        res = []
+        for b in range(n):
+            out, idx, order = bufs[b]
+            m, nk = arr[b].cloud.n, reps[b].n_kept
+            assert idx[m] == -1 and order[m] == -1 and nk <= m
+            rep = abi.NmsReport.from_buffer_copy(reps[b])
+            res.append((out[:nk].copy(), idx[:nk].copy(), order[:m].copy(), rep))
+        return res
 
     # --- scan preparation ----------------------------------------------------------------------------------------------
     def scan_prepare(self, pts, params):
