@@ -1319,6 +1319,78 @@ inline uint32_t merged_map_add(mulls_mapper *mapper, const typename pcl::PointCl
 	return n_out;
 }
 
+// The pictures of a cloud: CloudUtility<PointT>::get_cloud_cpt (include/common/utility.hpp:800-814), CFilter<PointT>::generate_2d_map (cfilter.hpp:2751-2790)
+// and CFilter<PointT>::pointcloud_to_rangeimage (:2714-2746) with upstream's parameter lists, each one device call (mulls_cloud_centre, mulls_map_image_2d,
+// mulls_range_image; include/mulls_hip.h has the definition and says what of it is upstream's, what restates OpenCV from memory and what is the library's).
+// The pictures are filled into a std::vector<uint8_t>, row by row, plus width and height, so that the export needs no OpenCV (mulls_io_write_pgm writes
+// them); the cv::Mat overloads with upstream's verbatim signatures exist under OPENCV_ON only.  image_2d_of_cloud takes a mulls_cloud, so that the merged
+// map is pictured where it lies: lo::hip::generate_2d_map(mulls_mapper's cloud, ...) moves nothing but the picture.
+template <typename PointT>
+inline void get_cloud_cpt(const typename pcl::PointCloud<PointT>::Ptr &cloud, centerpoint_t &cp)
+{
+	mulls_ctx *ctx = thread_context();
+	const mulls_cloud c = borrow(cloud);
+	double centre[3];
+	const int rc = mulls_cloud_centre(ctx, &c, centre);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_cloud_centre failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	cp.x = centre[0], cp.y = centre[1], cp.z = centre[2];
+}
+inline void image_2d_of_cloud(const mulls_cloud &cloud, std::vector<uint8_t> &image, double m2pix, int map_width, int map_height, int min_points_in_pix,
+							  int max_points_in_pix, double min_height, double max_height, bool shift_or_not)
+{
+	mulls_ctx *ctx = thread_context();
+	mulls_image2d_params P;
+	mulls_image2d_default_params(&P);
+	P.m2pix = m2pix, P.map_width = map_width, P.map_height = map_height;
+	P.min_points_in_pix = min_points_in_pix, P.max_points_in_pix = max_points_in_pix;
+	P.min_height = min_height, P.max_height = max_height, P.shift = shift_or_not;
+	image.assign(map_width > 0 && map_height > 0 ? (size_t)map_width * (size_t)map_height : 0, 0);
+	const int rc = mulls_map_image_2d(ctx, &cloud, &P, image.data(), nullptr, nullptr);
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_map_image_2d failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+}
+template <typename PointT>
+inline void generate_2d_map(const typename pcl::PointCloud<PointT>::Ptr &cloud, std::vector<uint8_t> &image, double m2pix, int map_width, int map_height,
+							int min_points_in_pix, int max_points_in_pix, double min_height, double max_height, bool shift_or_not = false)
+{
+	image_2d_of_cloud(borrow(cloud), image, m2pix, map_width, map_height, min_points_in_pix, max_points_in_pix, min_height, max_height, shift_or_not);
+}
+// the HDL-64 constants are upstream's own (:2717-2721): width and height come back as 900 and 64
+template <typename PointT>
+inline bool pointcloud_to_rangeimage(typename pcl::PointCloud<PointT>::Ptr &point_cloud, std::vector<uint8_t> &range_image, int &width, int &height)
+{
+	mulls_ctx *ctx = thread_context();
+	mulls_range_image_params P;
+	mulls_range_image_default_params(&P);
+	const mulls_cloud c = borrow(point_cloud);
+	range_image.assign((size_t)P.width * (size_t)P.height, 0);
+	const int rc = mulls_range_image(ctx, &c, &P, range_image.data());
+	if (rc != MULLS_OK)
+		throw std::runtime_error(std::string("mulls_range_image failed (") + std::to_string(rc) + "): " + mulls_last_error(ctx));
+	width = P.width, height = P.height;
+	return true;
+}
+#if OPENCV_ON
+template <typename PointT>
+inline cv::Mat generate_2d_map(const typename pcl::PointCloud<PointT>::Ptr &cloud, double m2pix, int map_width, int map_height, int min_points_in_pix,
+							   int max_points_in_pix, double min_height, double max_height, bool shift_or_not = false)
+{
+	std::vector<uint8_t> image;
+	generate_2d_map<PointT>(cloud, image, m2pix, map_width, map_height, min_points_in_pix, max_points_in_pix, min_height, max_height, shift_or_not);
+	return cv::Mat(map_height, map_width, CV_8UC1, image.data()).clone();
+}
+template <typename PointT>
+inline bool pointcloud_to_rangeimage(typename pcl::PointCloud<PointT>::Ptr &point_cloud, cv::Mat &range_image)
+{
+	std::vector<uint8_t> image;
+	int width = 0, height = 0;
+	pointcloud_to_rangeimage<PointT>(point_cloud, image, width, height);
+	range_image = cv::Mat(height, width, CV_8UC1, image.data()).clone();
+	return true;
+}
+#endif
+
 // the pieces lo::hip::extract_semantic_pts and lo::hip::extract_semantic_pts_batch share
 namespace detail
 {

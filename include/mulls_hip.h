@@ -1157,8 +1157,8 @@ int mulls_scan_prepare(mulls_ctx *ctx, void *pts, uint32_t n, uint32_t stride, c
  * apply_motion_compensation(pc_raw, adjacent_tran) with threshold 0 (:977-981; mulls_motion_compensate's arithmetic, theta = acos(|q.w|) by the host's
  * C library once per frame); pcl::transformPointCloud by pose (:982: positions in double, stored as float, every other field copied); appended in frame
  * order (:990).  mulls_mapper_cloud hands the result to mulls_sor_filter (:1009).  Many frames per call run in lock step: one launch per pass for all of
- * them.  The viewer's thinning (:991), write_map_each_frame and generate_2d_map are not part of this; the ground-truth map (:996-1005) is a second
- * mapper fed pose_gt.
+ * them.  The viewer's thinning (:991) and write_map_each_frame are not part of this; the ground-truth map (:996-1005) is a second mapper fed pose_gt.
+ * The export's picture of the map (:1016-1025, generate_2d_map) is mulls_map_image_2d below, on the map where it lies.
  *   capacity [LIB] frames are appended while they fit.  If frame k does not fit, frames 0 .. k-1 of the call stay appended, frames k onward are not, and
  *            the call returns MULLS_E_UNSUPPORTED with report.frames_added = k and report.n_needed = the size the map would have had with every frame.
  *   refused  [LIB] what mulls_scan_prepare refuses, for any frame: MULLS_E_INVALID and nothing is appended.  A mapper of another context: MULLS_E_INVALID.
@@ -1194,6 +1194,118 @@ int mulls_mapper_cloud(mulls_ctx *ctx, const mulls_mapper *mapper, mulls_cloud *
 /* records first .. of the map to host memory, at most cap of them; *n: the map's size minus first (pts NULL with cap 0: the size query) */
 int mulls_mapper_download(mulls_ctx *ctx, const mulls_mapper *mapper, uint32_t first, void *pts, uint32_t cap, uint32_t *n);
 int mulls_mapper_clear(mulls_ctx *ctx, mulls_mapper *mapper);
+
+/* ---- the pictures of a cloud: CloudUtility::get_cloud_cpt (include/common/utility.hpp:800-814), CFilter::generate_2d_map (cfilter.hpp:2751-2790) and
+ * CFilter::pointcloud_to_rangeimage (:2714-2746) ----
+ * What test/mulls_slam.cpp draws per frame from pc_raw (:722-733: the range image and a 400 x 400 bird's-eye view) and at the export from the merged map
+ * (:1016-1025: merged_map_2d.png), on the device: a device-resident cloud (mulls_mapper_cloud, mulls_block_cloud, mulls_map_cloud, any device allocation)
+ * crosses PCIe in no direction, only the images and the report come down.  Lines marked [UP] are upstream's, [LIB] this library's, "from memory" marks
+ * OpenCV's inside as it is restated here.  OpenCV, PCL and Eigen are not available where this library is built and tested: NOTHING BELOW WAS COMPARED WITH
+ * THEM.  tests/images_restated.py restates all of it in numpy float32 / float64 element-wise operations, and every comparison with it is equality of
+ * bytes; DESIGN.md section 7.12 says what is upstream's, what is OpenCV's and what is this library's, with the reasons.
+ *
+ * Centre point (mulls_cloud_centre)
+ *   term     [UP :807-809] the term of point i is x_i / (float)n: upstream divides a float by an int, a float division.  The term is widened to double
+ *            and added; y and z likewise.  n == 0: (0, 0, 0).  Non-finite coordinates follow the arithmetic.
+ *   order    [LIB] MULLS_NDT_TREE's strided-partial rule: lane l adds the terms of the points l, l + MULLS_NDT_TREE, .. in that order, from 0, then for
+ *            w = MULLS_NDT_TREE / 2 .. 1: partial[l] += partial[l + w], l < w.  Upstream's sequential order cannot be kept on a device; this is the rule
+ *            of every other long sum of this header.
+ *   refused  more than MULLS_SCAN_MAX_POINTS points: MULLS_E_UNSUPPORTED.  A stride other than 48: MULLS_E_INVALID.
+ *
+ * 2-D map image (mulls_map_image_2d)
+ *   shift    [UP :2757-2768] shift_x = (float)c.x, shift_y = (float)c.y of the centre above over the same cloud when `shift` is set, else 0.
+ *   height   [UP :2775] a point is skipped when (double)z < min_height || (double)z > max_height.  A NaN z passes.
+ *   pixel    [UP :2778-2779] dx = (double)(x - shift_x) * m2pix + (double)(map_width / 2): the difference in float, map_width / 2 the integer division;
+ *            dy = (double)(-(y - shift_y)) * m2pix + (double)(map_height / 2).  The pixel is (int)dx, (int)dy: truncation toward zero, so every dx in
+ *            (-1, 0) lands in column 0.  The quirk is kept.
+ *            [LIB] a point takes part iff t = trunc(dx), evaluated in double, has 0 <= t < map_width, and likewise for y.  Upstream's cast of a
+ *            non-finite or huge double to int is undefined; such points are skipped (counted as outside the frame).
+ *   counts   counts[y * map_width + x] = the number of points in the pixel.
+ *   8 bits   [UP shape :2786-2787, OpenCV from memory] map -= min_points_in_pix; map.convertTo(map, CV_8UC1, -255.0 / (max - min), 255).
+ *            [LIB] restated: a = (float)(-255.0 / (double)(max_points_in_pix - min_points_in_pix)); v = (float)(count - min_points_in_pix) * a + 255.0f,
+ *            the product and the sum in float and not contracted; image = clamp(round-half-to-even(v), 0, 255).  OpenCV's working type (float for
+ *            a 32-bit integer source) and its rounding (cvRound, saturate_cast) were restated from memory and not compared with OpenCV.
+ *   refused  [LIB] MULLS_E_INVALID with nothing written: max_points_in_pix == min_points_in_pix; map_width or map_height < 1 or their product above
+ *            MULLS_IMAGE_MAX_PIXELS; m2pix, min_height or max_height NaN; count_form outside 0..2; a stride other than 48; a NULL image.  More than
+ *            MULLS_SCAN_MAX_POINTS points: MULLS_E_UNSUPPORTED.  n == 0: the all-empty image, every pixel what count 0 gives.
+ *
+ * Range image (mulls_range_image); upstream hard-codes the HDL-64 constants (:2717-2721), which are the defaults of mulls_range_image_params
+ *   per point, in this order:
+ *            [UP :2730] d = sqrtf((x x + y y) + z z).
+ *            [LIB] hor = (float)atan2_cr((double)y, (double)x); a = (float)asin_cr((double)(z / d)), the quotient in float.  atan2_cr and asin_cr are
+ *            detmath.h's correctly rounded functions where upstream calls the C library's float overloads: mulls_scan_prepare's convention (the double
+ *            evaluation is this library's definition and differs from a float function by that function's rounding).
+ *            [UP :2732] ver = (float)(((double)a / M_PI) * 180.0).
+ *            [UP :2734] u = (float)((0.5 * (1 - (double)hor / M_PI)) * width).
+ *            [UP :2735] v = (1 - (f_up - ver) / (f_up + f_down)) * height, entirely in float.
+ *            [UP :2737-2738] c = clamp((int)u, 0, width - 1), r = clamp((int)v, 0, height - 1).
+ *            [LIB] a point whose u or v is not finite is skipped (upstream's cast is undefined there; the scanner's own origin is such a point); the
+ *            clamp is applied to the truncated float before the conversion to int.
+ *            [UP :2743] value = (uint8_t)(255.0 * min_(1.0, (double)(d / max_distance))): the quotient in float, the conversion truncates.
+ *            [UP :2743] the value is written at row height - 1 - r, column c.
+ *   overlap  [UP] a pixel holds the value of the HIGHEST-INDEX point that lands in it: upstream's sequential overwrite.  Pixels nobody lands in are 0.
+ *            [LIB] on the device a pixel is the maximum of the 32-bit words (index << 8) | value: the limit of MULLS_SCAN_MAX_POINTS = 2^24 points is
+ *            what makes that word fit, and the maximum is independent of the order the points arrive in.
+ *   refused  [LIB] MULLS_E_INVALID with nothing written: width or height < 1 or their product above MULLS_IMAGE_MAX_PIXELS; f_up_deg, f_down_deg or
+ *            max_distance not finite, max_distance <= 0 (the value's conversion would be of a negative or NaN double); a stride other than 48; a NULL
+ *            image.  More than MULLS_SCAN_MAX_POINTS points: MULLS_E_UNSUPPORTED.
+ *
+ * Many scans per call (mulls_scan_images_batch): every scan gets the bytes of its single calls, whatever the batch size and its position.  The single
+ * calls are this path with one scan.  Per call (per sub-batch of a call whose images and staged host clouds exceed the arena's budget of 1 GiB; a scan
+ * beyond it runs alone): one zeroing of all counts and words, one launch per pass over a chunk table of all scans — chunks of MULLS_SCAN_CHUNK points, one
+ * workgroup each —, one launch that converts all pixels to 8 bits, one download of all images and reports.  Both images are integer results of commutative
+ * atomics (add, max): nothing depends on which workgroup runs first.  A refusal (any scan's) writes no output of the call.  n_scans == 0: MULLS_OK. */
+#define MULLS_IMAGE_MAX_PIXELS (1u << 26)
+typedef struct mulls_image2d_params
+{
+	double m2pix;				/* [1] pixels per metre */
+	int32_t map_width;			/* [1920] */
+	int32_t map_height;			/* [1080] */
+	int32_t min_points_in_pix;	/* [20] */
+	int32_t max_points_in_pix;	/* [1000] */
+	double min_height;			/* [-FLT_MAX] */
+	double max_height;			/* [FLT_MAX] */
+	int32_t shift;				/* [1] shift_or_not: the picture is centred on the cloud's centre point */
+	int32_t count_form;			/* [0] which form of the counting pass runs: 0 the library's choice (form 2, the faster in profiles/images.txt), 1 one atomic add per
+								   point, 2 a wave folds runs of equal pixels among neighbouring lanes and one lane per run adds the run's length.  Same bytes. */
+} mulls_image2d_params;
+
+typedef struct mulls_image2d_report
+{
+	double centre[3];		  /* the centre point that was used (computed also when shift is 0) */
+	uint32_t n_counted;		  /* points that landed in a pixel */
+	uint32_t n_skipped_height; /* points outside [min_height, max_height] */
+	uint32_t n_skipped_frame;  /* points of the height range outside the picture (non-finite ones included) */
+	float ms_total;			  /* wall time of the call (a batch: of the whole call, in every report) */
+} mulls_image2d_report;
+
+typedef struct mulls_range_image_params
+{
+	int32_t width;		/* [900] */
+	int32_t height;		/* [64] */
+	float f_up_deg;		/* [3] */
+	float f_down_deg;	/* [25] */
+	float max_distance; /* [70] */
+	int32_t reserved;
+} mulls_range_image_params;
+
+void mulls_image2d_default_params(mulls_image2d_params *p);		   /* the export's values (test/mulls_slam.cpp:1018); the bird's-eye view of :731 is
+																	  (4, 400, 400, 2, 50, -5, 15, no shift) */
+void mulls_range_image_default_params(mulls_range_image_params *p); /* upstream's HDL-64 constants */
+/* cloud: host memory or device memory, told apart as mulls_scan_prepare tells them apart; never modified.  All outputs are host memory. */
+int mulls_cloud_centre(mulls_ctx *ctx, const mulls_cloud *cloud, double c[3]);
+/* image: map_height rows of map_width bytes.  counts: NULL, or as many int32.  report may be NULL. */
+int mulls_map_image_2d(mulls_ctx *ctx, const mulls_cloud *cloud, const mulls_image2d_params *p, uint8_t *image, int32_t *counts,
+					   mulls_image2d_report *report);
+/* image: height rows of width bytes */
+int mulls_range_image(mulls_ctx *ctx, const mulls_cloud *scan, const mulls_range_image_params *p, uint8_t *image);
+/* rp NULL: no range images (range_out is not read); bp NULL: no 2-D map images (bev_out and reports are not read).  range_out / bev_out: n_scans
+ * pointers, one image each.  reports: NULL or n_scans of them. */
+int mulls_scan_images_batch(mulls_ctx *ctx, const mulls_cloud *scans, uint32_t n_scans, const mulls_range_image_params *rp, const mulls_image2d_params *bp,
+							uint8_t *const *range_out, uint8_t *const *bev_out, mulls_image2d_report *reports);
+/* a binary PGM (P5, maxval 255) of an 8-bit image: what the export writes where upstream calls cv::imwrite.  Host code; MULLS_E_IO when the file cannot be
+ * written, MULLS_E_INVALID for a NULL argument or a width or height < 1. */
+int mulls_io_write_pgm(const char *path, const uint8_t *image, int32_t width, int32_t height);
 
 /* ---- pose graph optimisation: GlobalOptimize::optimize_pose_graph_ceres (src/graph_optimizer.cpp:385-417, with set_pgo_problem_ceres :481-636) and update_optimized_edges (:713-776) ----
  * The step behind a closed loop: registration edges (mulls_result.T / .info) and the odometry chain in, one pose per node out — the poses

@@ -760,6 +760,52 @@ def scan_prep_params(calib_on=0, dist_filter_on=0, calib_first=0, downsample_rat
     return p
 
 
+class Image2dParams(C.Structure):
+    """mulls_image2d_params: generate_2d_map's arguments (cfilter.hpp:2751-2752) and which form of the counting pass runs"""
+
+    _fields_ = [("m2pix", C.c_double), ("map_width", C.c_int32), ("map_height", C.c_int32), ("min_points_in_pix", C.c_int32), ("max_points_in_pix", C.c_int32),
+                ("min_height", C.c_double), ("max_height", C.c_double), ("shift", C.c_int32), ("count_form", C.c_int32)]
+
+
+class Image2dReport(C.Structure):
+    """mulls_image2d_report"""
+
+    _fields_ = [("centre", C.c_double * 3), ("n_counted", C.c_uint32), ("n_skipped_height", C.c_uint32), ("n_skipped_frame", C.c_uint32), ("ms_total", C.c_float)]
+
+
+class RangeImageParams(C.Structure):
+    """mulls_range_image_params: pointcloud_to_rangeimage's constants (cfilter.hpp:2717-2721)"""
+
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("f_up_deg", C.c_float), ("f_down_deg", C.c_float), ("max_distance", C.c_float), ("reserved", C.c_int32)]
+
+
+IMAGE_MAX_PIXELS = 1 << 26  # MULLS_IMAGE_MAX_PIXELS
+FLT_MAX = 3.4028234663852886e38
+
+
+def image2d_params(m2pix=1.0, map_width=1920, map_height=1080, min_points_in_pix=20, max_points_in_pix=1000, min_height=-FLT_MAX, max_height=FLT_MAX, shift=1,
+                   count_form=0):
+    """the export's values (test/mulls_slam.cpp:1018)"""
+    p = Image2dParams()
+    p.m2pix, p.map_width, p.map_height, p.min_points_in_pix, p.max_points_in_pix = float(m2pix), int(map_width), int(map_height), int(min_points_in_pix), int(max_points_in_pix)
+    p.min_height, p.max_height, p.shift, p.count_form = float(min_height), float(max_height), int(shift), int(count_form)
+    return p
+
+
+def bev_params(**kw):
+    """the per-frame bird's-eye view (test/mulls_slam.cpp:731)"""
+    d = dict(m2pix=4.0, map_width=400, map_height=400, min_points_in_pix=2, max_points_in_pix=50, min_height=-5.0, max_height=15.0, shift=0)
+    d.update(kw)
+    return image2d_params(**d)
+
+
+def range_image_params(width=900, height=64, f_up_deg=3.0, f_down_deg=25.0, max_distance=70.0):
+    """upstream's HDL-64 constants (cfilter.hpp:2717-2721)"""
+    p = RangeImageParams()
+    p.width, p.height, p.f_up_deg, p.f_down_deg, p.max_distance, p.reserved = int(width), int(height), float(f_up_deg), float(f_down_deg), float(max_distance), 0
+    return p
+
+
 class SubmapInfo(C.Structure):
     """mulls_submap_info: one submap of the device-resident archive (n in the ABI's class order; bounds as {min xyz, max xyz})"""
 

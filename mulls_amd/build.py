@@ -13,8 +13,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmulls_hip.so")
-SOURCES = ["k_setup.hip", "k_grid.hip", "k_search.hip", "k_reduce.hip", "k_ground.hip", "k_ground_normals.hip", "k_classify.hip", "map_kernels.hip", "k_map_batch.hip", "k_ncc_batch.hip", "k_pair_gather.hip", "k_ransac.hip", "k_teaser.hip", "k_teaser_clique.hip", "k_sor.hip", "k_nms.hip", "k_scan.hip", "k_pgo.hip", "k_submaps.hip", "k_ndt.hip", "k_gicp.hip", "k_pcl_icp.hip", "k_reg_table.hip", "k_fpfh.hip", "k_fpfh_batch.hip", "k_extract_batch.hip", "driver.cpp", "batch.cpp", "loop.cpp", "variants.cpp", "stage.cpp", "shard.cpp", "map.cpp", "map_batch.cpp", "ground.cpp", "classify.cpp", "extract_batch.cpp", "io.cpp", "ncc.cpp", "pair_stage.cpp", "ransac.cpp", "teaser.cpp", "sor.cpp", "nms.cpp", "scan.cpp", "pgo.cpp", "submaps.cpp", "ndt.cpp", "gicp.cpp", "pcl_icp.cpp", "reg_host.cpp", "fpfh.cpp"]
-DEPS = ["device_types.h", "device_util.h", "lds_tier.h", "big_tier.h", "crop_grid.h", "solve_wave.h", "detmath.h", "accum.h", "icp_step.h", "launch.h", "map_launch.h", "map_internal.h", "classify_launch.h", "ground_launch.h", "ncc_launch.h", "ncc_device.h", "ncc_batch.h", "pair_gather.h", "pair_stage.h", "ransac_launch.h", "ransac_math.h", "ransac_host.h", "ransac_batch.h", "teaser_launch.h", "teaser_math.h", "teaser_host.h", "teaser_search.h", "teaser_batch.h", "sor_launch.h", "sor_math.h", "nms_launch.h", "nms_host.h", "nms_batch.h", "scan_launch.h", "scan_math.h", "scan_host.h", "pgo_launch.h", "pgo_math.h", "ndt_launch.h", "ndt_math.h", "gicp_launch.h", "gicp_math.h", "pcl_icp_launch.h", "pcl_icp_math.h", "fpfh_launch.h", "fpfh_device.h", "fpfh_batch.h", "fpfh_math.h", "reg_table.h", "reg_device.h", "reg_launch.h", "reg_host.h", "jacobi_rot.h", "submaps_launch.h", "submaps_host.h", "rounds.h", "extract_batch.h", "subbatch.h", "extract_internal.h", "extract_launch.h", "pca_device.h", "ctx.h", "batch.h", "hostmath.h", os.path.join("..", "..", "include", "mulls_hip.h")]
+SOURCES = ["k_setup.hip", "k_grid.hip", "k_search.hip", "k_reduce.hip", "k_ground.hip", "k_ground_normals.hip", "k_classify.hip", "map_kernels.hip", "k_map_batch.hip", "k_ncc_batch.hip", "k_pair_gather.hip", "k_ransac.hip", "k_teaser.hip", "k_teaser_clique.hip", "k_sor.hip", "k_nms.hip", "k_scan.hip", "k_image.hip", "k_pgo.hip", "k_submaps.hip", "k_ndt.hip", "k_gicp.hip", "k_pcl_icp.hip", "k_reg_table.hip", "k_fpfh.hip", "k_fpfh_batch.hip", "k_extract_batch.hip", "driver.cpp", "batch.cpp", "loop.cpp", "variants.cpp", "stage.cpp", "shard.cpp", "map.cpp", "map_batch.cpp", "ground.cpp", "classify.cpp", "extract_batch.cpp", "io.cpp", "ncc.cpp", "pair_stage.cpp", "ransac.cpp", "teaser.cpp", "sor.cpp", "nms.cpp", "scan.cpp", "image.cpp", "pgo.cpp", "submaps.cpp", "ndt.cpp", "gicp.cpp", "pcl_icp.cpp", "reg_host.cpp", "fpfh.cpp"]
+DEPS = ["device_types.h", "device_util.h", "lds_tier.h", "big_tier.h", "crop_grid.h", "solve_wave.h", "detmath.h", "accum.h", "icp_step.h", "launch.h", "map_launch.h", "map_internal.h", "classify_launch.h", "ground_launch.h", "ncc_launch.h", "ncc_device.h", "ncc_batch.h", "pair_gather.h", "pair_stage.h", "ransac_launch.h", "ransac_math.h", "ransac_host.h", "ransac_batch.h", "teaser_launch.h", "teaser_math.h", "teaser_host.h", "teaser_search.h", "teaser_batch.h", "sor_launch.h", "sor_math.h", "nms_launch.h", "nms_host.h", "nms_batch.h", "scan_launch.h", "scan_math.h", "scan_host.h", "image_launch.h", "image_math.h", "pgo_launch.h", "pgo_math.h", "ndt_launch.h", "ndt_math.h", "gicp_launch.h", "gicp_math.h", "pcl_icp_launch.h", "pcl_icp_math.h", "fpfh_launch.h", "fpfh_device.h", "fpfh_batch.h", "fpfh_math.h", "reg_table.h", "reg_device.h", "reg_launch.h", "reg_host.h", "jacobi_rot.h", "submaps_launch.h", "submaps_host.h", "rounds.h", "extract_batch.h", "subbatch.h", "extract_internal.h", "extract_launch.h", "pca_device.h", "ctx.h", "batch.h", "hostmath.h", os.path.join("..", "..", "include", "mulls_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fopenmp", "-Wall", "-Wno-unused-function"]
 
 

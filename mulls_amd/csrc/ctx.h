@@ -26,6 +26,7 @@ struct mulls_teaser_scratch;
 struct mulls_sor_scratch;
 struct mulls_nms_scratch;
 struct mulls_scan_scratch;
+struct mulls_image_scratch;
 struct mulls_pgo_scratch;
 struct mulls_reg_scratch;
 struct mulls_mapper;
@@ -92,6 +93,7 @@ struct mulls_ctx
 	mulls_sor_scratch *sor = nullptr; // mulls_sor_filter's (sor.cpp; grow-only)
 	mulls_nms_scratch *nms = nullptr; // mulls_non_max_suppress's (nms.cpp; grow-only)
 	mulls_scan_scratch *scanprep = nullptr; // mulls_scan_prepare's and mulls_mapper_add's (scan.cpp; grow-only)
+	mulls_image_scratch *image = nullptr; // mulls_map_image_2d's, mulls_range_image's and mulls_scan_images_batch's (image.cpp; grow-only)
 	mulls_pgo_scratch *pgo = nullptr; // mulls_pgo_optimize's (pgo.cpp; grow-only)
 	mulls_reg_scratch *reg = nullptr; // mulls_ndt's, mulls_gicp's and mulls_pcl_icp's (reg_host.cpp; grow-only)
 	mulls_mapb_scratch *mapb = nullptr; // mulls_map_update_batch's staging: tables up, counts and keys down (map_batch.cpp; grow-only)
@@ -259,6 +261,7 @@ void mulls_pgo_release(mulls_ctx *ctx); // frees ctx->pgo (pgo.cpp)
 void mulls_reg_release(mulls_ctx *ctx); // frees ctx->reg (reg_host.cpp)
 void mulls_mapb_release(mulls_ctx *ctx); // frees ctx->mapb (map_batch.cpp)
 void mulls_scan_release(mulls_ctx *ctx); // frees ctx->scanprep and destroys the mappers still alive (scan.cpp)
+void mulls_image_release(mulls_ctx *ctx); // frees ctx->image (image.cpp)
 void mulls_submaps_release(mulls_ctx *ctx); // destroys the submap archives still alive (submaps.cpp)
 bool mulls_submaps_memory(const mulls_ctx *ctx, const void *p, size_t bytes); // is [p, p + bytes) inside a live archive's arena? (submaps.cpp)
 

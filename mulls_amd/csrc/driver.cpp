@@ -270,6 +270,7 @@ extern "C"
 		mulls_nms_release(ctx);
 		mulls_scan_release(ctx); // (merged maps die with their context, like local maps and feature blocks)
 		mulls_submaps_release(ctx); // ... and submap archives
+		mulls_image_release(ctx);
 		while (!ctx->maps.empty()) // local maps die with their context (mulls_map_destroy unregisters them)
 			mulls_map_destroy(ctx, ctx->maps.back());
 		while (!ctx->blocks.empty()) // ... and so do feature blocks

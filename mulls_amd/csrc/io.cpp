@@ -289,4 +289,23 @@ extern "C"
 	{
 		return io_caught(); // nothing is thrown across the ABI
 	}
+
+	// an 8-bit image as a binary PGM: "P5\n<width> <height>\n255\n" and the rows (what the export writes where upstream calls cv::imwrite)
+	int mulls_io_write_pgm(const char *path, const uint8_t *image, int32_t width, int32_t height)
+	try
+	{
+		if (!path || !image || width < 1 || height < 1)
+			return MULLS_E_INVALID;
+		std::ofstream out(path, std::ios::binary);
+		if (!out)
+			return MULLS_E_IO;
+		out << "P5\n" << width << " " << height << "\n255\n";
+		out.write(reinterpret_cast<const char *>(image), (std::streamsize)width * (std::streamsize)height);
+		out.close();
+		return out ? MULLS_OK : MULLS_E_IO;
+	}
+	catch (...)
+	{
+		return io_caught(); // nothing is thrown across the ABI
+	}
 }

@@ -167,6 +167,16 @@ def load():
     lib.mulls_mapper_cloud.argtypes = [vp, vp, C.POINTER(abi.Cloud)]
     lib.mulls_mapper_download.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
     lib.mulls_mapper_clear.argtypes = [vp, vp]
+    lib.mulls_image2d_default_params.argtypes = [C.POINTER(abi.Image2dParams)]
+    lib.mulls_image2d_default_params.restype = None
+    lib.mulls_range_image_default_params.argtypes = [C.POINTER(abi.RangeImageParams)]
+    lib.mulls_range_image_default_params.restype = None
+    lib.mulls_cloud_centre.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(C.c_double)]
+    lib.mulls_map_image_2d.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.Image2dParams), vp, vp, C.POINTER(abi.Image2dReport)]
+    lib.mulls_range_image.argtypes = [vp, C.POINTER(abi.Cloud), C.POINTER(abi.RangeImageParams), vp]
+    lib.mulls_scan_images_batch.argtypes = [vp, C.POINTER(abi.Cloud), C.c_uint32, C.POINTER(abi.RangeImageParams), C.POINTER(abi.Image2dParams), C.POINTER(vp),
+                                            C.POINTER(vp), C.POINTER(abi.Image2dReport)]
+    lib.mulls_io_write_pgm.argtypes = [C.c_char_p, vp, C.c_int32, C.c_int32]
     lib.mulls_overlap_default_params.argtypes = [C.POINTER(abi.OverlapParams)]
     lib.mulls_overlap_default_params.restype = None
     lib.mulls_submaps_create.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]
@@ -213,6 +223,8 @@ EXPORTS = [
     "mulls_nms_default_params", "mulls_non_max_suppress", "mulls_non_max_suppress_batch", "mulls_nms_batch_arena_bytes",
     "mulls_scan_prep_default_params", "mulls_scan_prepare",
     "mulls_mapper_create", "mulls_mapper_destroy", "mulls_mapper_add", "mulls_mapper_cloud", "mulls_mapper_download", "mulls_mapper_clear",
+    "mulls_image2d_default_params", "mulls_range_image_default_params", "mulls_cloud_centre", "mulls_map_image_2d", "mulls_range_image",
+    "mulls_scan_images_batch", "mulls_io_write_pgm",
     "mulls_overlap_default_params", "mulls_submaps_create", "mulls_submaps_destroy", "mulls_submaps_push", "mulls_submaps_push_map", "mulls_submaps_count",
     "mulls_submaps_info", "mulls_submaps_cloud", "mulls_submaps_download", "mulls_submaps_clear", "mulls_submaps_set_poses", "mulls_submaps_find_overlap",
     "mulls_submaps_pairs",
@@ -253,6 +265,14 @@ def write_pose(path, T, append=False):
     rc = load().mulls_io_write_pose(path.encode(), abi.colmajor16(T), int(append))
     if rc != 0:
         raise MullsError("mulls_io_write_pose(%s) failed with %d" % (path, rc))
+
+
+def write_pgm(path, image):
+    """mulls_io_write_pgm: a (height, width) uint8 image as a binary PGM"""
+    image = np.ascontiguousarray(image, np.uint8)
+    rc = load().mulls_io_write_pgm(path.encode(), image.ctypes.data_as(C.c_void_p), image.shape[1], image.shape[0])
+    if rc != 0:
+        raise MullsError("mulls_io_write_pgm(%s) failed with %d" % (path, rc), rc)
 
 
 def icp_batch_sharded(contexts, pairs, params, marshalled=None):
@@ -1083,6 +1103,89 @@ class Context:
 
     def mapper(self, capacity_points):
         return Mapper(self, capacity_points)
+
+    # --- the pictures of a cloud ----------------------------------------------------------------------------------------
+    GUARD = 0xA5  # what the image buffers are filled with, and what their one slot past the end must still hold
+
+    @staticmethod
+    def _image_cloud(pts, keep):
+        """a host cloud (POINT_DTYPE records or raw (n, 48) bytes) or a device-resident abi.Cloud as an abi.Cloud"""
+        if isinstance(pts, abi.Cloud):
+            return pts
+        raw = abi.records(pts)
+        keep.append(raw)
+        c = abi.Cloud()
+        c.pts, c.n, c.stride = (raw.ctypes.data if len(raw) else None), len(raw), abi.POINT_BYTES
+        return c
+
+    def _image_raise(self, rc, what):
+        raise MullsError("%s failed with %d: %s" % (what, rc, self.lib.mulls_last_error(self.h).decode()), rc)
+
+    def cloud_centre(self, pts):
+        """CloudUtility::get_cloud_cpt (mulls_cloud_centre): the (3,) float64 centre point of a host cloud or a device-resident abi.Cloud"""
+        keep, c = [], np.zeros(3, np.float64)
+        cl = self._image_cloud(pts, keep)
+        rc = self.lib.mulls_cloud_centre(self.h, C.byref(cl), c.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            self._image_raise(rc, "mulls_cloud_centre")
+        return c
+
+    def map_image_2d(self, pts, params=None, want_counts=False):
+        """CFilter::generate_2d_map (mulls_map_image_2d).  Returns (image, report), or (image, counts, report) when want_counts: the (map_height, map_width)
+        uint8 picture, the int32 counts behind it, the abi.Image2dReport."""
+        p = params if params is not None else abi.image2d_params()
+        keep = []
+        cl = self._image_cloud(pts, keep)
+        npix = max(p.map_width, 0) * max(p.map_height, 0)
+        img = np.full(npix + 1, self.GUARD, np.uint8)  # one slot past the end: checked to be left alone
+        cnt = np.full(npix + 1, -7, np.int32) if want_counts else None
+        rep = abi.Image2dReport()
+        rc = self.lib.mulls_map_image_2d(self.h, C.byref(cl), C.byref(p), img.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p) if want_counts else None, C.byref(rep))
+        if rc != 0:
+            self._image_raise(rc, "mulls_map_image_2d")
+        assert img[npix] == self.GUARD and (cnt is None or cnt[npix] == -7)
+        img = img[:npix].reshape(p.map_height, p.map_width).copy()
+        return (img, cnt[:npix].reshape(p.map_height, p.map_width).copy(), rep) if want_counts else (img, rep)
+
+    def range_image(self, pts, params=None):
+        """CFilter::pointcloud_to_rangeimage (mulls_range_image): the (height, width) uint8 range image"""
+        p = params if params is not None else abi.range_image_params()
+        keep = []
+        cl = self._image_cloud(pts, keep)
+        npix = max(p.width, 0) * max(p.height, 0)
+        img = np.full(npix + 1, self.GUARD, np.uint8)
+        rc = self.lib.mulls_range_image(self.h, C.byref(cl), C.byref(p), img.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            self._image_raise(rc, "mulls_range_image")
+        assert img[npix] == self.GUARD
+        return img[:npix].reshape(p.height, p.width).copy()
+
+    def scan_images_batch(self, scans, range_params=None, bev_params=None):
+        """mulls_scan_images_batch: the range image and / or the 2-D map image of many scans in one call.  scans: a list of what map_image_2d takes.
+        Returns (range images or None, 2-D map images or None, reports or None): lists with one entry per scan."""
+        n, keep = len(scans), []
+        arr = (abi.Cloud * max(n, 1))()
+        for k, s in enumerate(scans):
+            arr[k] = self._image_cloud(s, keep)
+
+        def outputs(npix):
+            bufs = [np.full(npix + 1, self.GUARD, np.uint8) for _ in range(n)]
+            return bufs, (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+
+        rp, bp = range_params, bev_params
+        rpix = rp.width * rp.height if rp is not None else 0
+        bpix = bp.map_width * bp.map_height if bp is not None else 0
+        rbufs, rptr = outputs(rpix) if rp is not None else (None, None)
+        bbufs, bptr = outputs(bpix) if bp is not None else (None, None)
+        reps = (abi.Image2dReport * max(n, 1))() if bp is not None else None
+        rc = self.lib.mulls_scan_images_batch(self.h, arr, n, C.byref(rp) if rp is not None else None, C.byref(bp) if bp is not None else None, rptr, bptr, reps)
+        if rc != 0:
+            self._image_raise(rc, "mulls_scan_images_batch")
+        for bufs, npix in ((rbufs, rpix), (bbufs, bpix)):
+            assert bufs is None or all(b[npix] == self.GUARD for b in bufs)
+        return (None if rbufs is None else [b[:rpix].reshape(rp.height, rp.width).copy() for b in rbufs],
+                None if bbufs is None else [b[:bpix].reshape(bp.map_height, bp.map_width).copy() for b in bbufs],
+                None if reps is None else [abi.Image2dReport.from_buffer_copy(reps[k]) for k in range(n)])
 
     def submaps(self, capacity_points, capacity_submaps):
         """a device-resident submap archive (mulls_submaps_*)"""
